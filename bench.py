@@ -19,6 +19,12 @@ the image.  `--weak` keeps rounds 1-3's mode: every rank renders the config's sp
 MASTER_* set, 127.0.0.1 rendezvous) BEFORE anything touches the GPU or imports torch; under torch.distributed.run the
 environment is taken as given.  `n_gpus` in the line is the size of the process group that actually ran.
 
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+`--full` adds what takes work of its own beyond the timed steps: `roofline` (an instrumented render pass plus the committed PMC
+figures) and `cpu_baseline`.  `--dump-outputs DIR` writes the film of the last timed step (what a caller of mcpt_render receives) to
+DIR/film.npy, float32 [H, W, 4] = {sum rgb, sample count}; a film over 64 MB is written as a fixed seeded sample of its pixels instead
+(DIR/film_sample.npy, [n, 4]).  The inputs of that step depend only on the arguments, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.  `roofline` is computed from device counters (algorithmic bytes) and the
 HIP-event kernel time the library records around launches of the timed region; `cpu_baseline` times the REAL reference
 (oracle/_ref, built from /root/reference by oracle/build_ref.sh) -- or, for the multi-million-triangle configs whose OBJ text the
@@ -44,6 +50,8 @@ L2_BYTES, MALL_BYTES = 32 << 20, 256 << 20   # aggregate L2, Infinity Cache (sam
 # algorithmic bytes per unit of work with THIS build's layouts
 B_BOX, B_TRI = 10, 48            # an eighth of an 80-B eight-child node per child-box test; one 48-B {v0,e1,e2} record per triangle test
 B_RAY = 32 + 16                  # trace kernel: ray fetch (origin + direction records) + 16-B result write-back per ray
+DUMP_BYTES = 64 << 20            # --dump-outputs: at most this much in all
+DUMP_SAMPLE_PIXELS = 1 << 21     # pixels kept of a film larger than that (32 MB), chosen by a fixed seed
 
 CONFIGS = {
     # name: scene generator, its arguments, resolution, the config's spp, spp per bench step, depth, BASELINE.json wording
@@ -175,6 +183,99 @@ def cpu_baseline(pkg, cfg, scene, rays_per_path_ref, budget_s=20.0):
                 "mpath_per_s": round(c["paths"] / t / 1e6, 4)}
 
 
+def dump_outputs(out_dir, film):
+    """--dump-outputs: the float32 [H, W, 4] film of the last timed step, or a seeded sample of its pixels where it exceeds DUMP_BYTES."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "film.npy"), film)
+    else:
+        px = film.reshape(-1, 4)
+        keep = np.sort(np.random.default_rng(20251004).choice(px.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "film_sample.npy"), px[keep])
+
+
+def roofline(pkg, cfg_name, scene, info, c, dt, steps, n_ranks, total_rays, depth, device):
+    """The `roofline` block of a --full run: kernel times from the timed region's counters, algorithmic bytes from an instrumented pass of
+    its own, measured traffic from the committed PMC passes."""
+    W, H = scene.camera.width, scene.camera.height
+    # ---- kernel durations: the library brackets the launches of every MCPT_TIME_KERNELS-th iteration of the timed region with HIP
+    # events recorded on the launch stream (a sub-pipeline stream forked from `side`); *_ms_total = sampled mean x launches
+    # since reset_counters().  Dominant kernel = wf_trace8_kernel (BVH traversal); one launch of it per pipeline iteration.
+    launches = max(1, c.iterations)
+    trace_ms = c.trace_ms_total / launches
+    shade_ms = c.shade_ms_total / launches
+    rays_per_launch = c.rays / launches
+    # ---- algorithmic bytes per ray from an instrumented pass (same scene / depth / seed, a few spp)
+    ri = pkg.Renderer(scene, max_depth=depth, device=device, flags=pkg.FLAG_COUNT_TRAVERSAL)
+    ri.render(32 if W * H <= 1 << 20 else 4, seed=20251004); ci = ri.counters(); ri.close()
+    trav_bytes_per_ray = (B_BOX * ci.box_tests + B_TRI * ci.tri_tests) / max(1, ci.rays)
+    trace_bytes_per_ray = trav_bytes_per_ray + B_RAY
+    algo_bytes = trace_bytes_per_ray * rays_per_launch
+    achieved = algo_bytes / (trace_ms * 1e-3) / 1e9
+    scene_bytes = int(info.traversal_bytes)                       # wide nodes + triangle test records, from the library
+    resident = scene_bytes <= L2_BYTES
+    residency = "L2" if scene_bytes <= L2_BYTES else "Infinity Cache (MALL)" if scene_bytes <= MALL_BYTES else "HBM"
+    # ---- measured HBM traffic / VALU issue / lane utilisation: PMC counters cannot be read inside this process; they come from the
+    # committed rocprofv3 --pmc passes of the same workload and build (tools/r03_profile.sh -> profiles/r03_traffic.json), per traced ray,
+    # x this run's rays per launch / rays per second
+    traffic = None; traffic_source = None; pmc = {}
+    tpath = next((q for q in (os.path.join(ROOT, "profiles", "r04_traffic.json"), os.path.join(ROOT, "profiles", "r03_traffic.json")) if os.path.exists(q)), None)
+    tname = "profiles/" + os.path.basename(tpath) if tpath else None
+    if tpath:
+        pmc = json.load(open(tpath)).get(cfg_name, {})
+        if pmc.get("wf_trace_kernel_hbm_bytes_per_ray"):
+            traffic = int(pmc["wf_trace_kernel_hbm_bytes_per_ray"] * rays_per_launch)
+            traffic_source = "%s[%s]: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (not this run), bytes per ray x this run's rays per launch" % (tname, cfg_name)
+    rays_per_s = total_rays / dt / max(1, n_ranks)                     # this GPU's share of the job's ray rate
+    hbm_measured = None
+    if pmc.get("wf_trace_kernel_hbm_bytes_per_ray") and pmc.get("wf_shade_kernel_hbm_bytes_per_ray"):
+        tb, sb = pmc["wf_trace_kernel_hbm_bytes_per_ray"], pmc["wf_shade_kernel_hbm_bytes_per_ray"]
+        hbm_measured = {"level": "step (bytes per traced ray from the PMC passes of this build x this run's rays/s per GPU)",
+                        "trace_bytes_per_ray": tb, "shade_bytes_per_ray": sb,
+                        "trace_GBps": round(tb * rays_per_s / 1e9, 1), "shade_GBps": round(sb * rays_per_s / 1e9, 1),
+                        "total_GBps": round((tb + sb) * rays_per_s / 1e9, 1), "frac_of_hbm_peak": round((tb + sb) * rays_per_s / 1e9 / HBM_PEAK_GBS, 4),
+                        "fetch_correction": pmc.get("fetch_correction_note"),
+                        "source": "%s[%s]" % (tname, cfg_name)}
+    n_streams = 2 if (c.shade_ms_total > 0 and launches >= 2) else 1
+    per_stream_ms = launches / max(1, steps) / n_streams * (trace_ms + shade_ms)
+    frac_alg = round(achieved / HBM_PEAK_GBS, 4)
+    # what binds, decided from the counters the line carries (not from the scene's size): the memory system when the measured HBM-side traffic is
+    # at least half of the peak; else VALU issue when the two kernels keep the SIMDs' vector ALUs busy most of the time (SQ_ACTIVE_INST_VALU over
+    # the SIMD-cycles of the render: `valu_busy_frac`); else latency / occupancy
+    hbm_frac = hbm_measured["frac_of_hbm_peak"] if hbm_measured else None
+    valu_busy = pmc.get("valu_busy_frac", pmc.get("valu_issue_frac"))
+    bound = "hbm" if (hbm_frac is not None and hbm_frac >= 0.5) else "valu-issue" if (valu_busy is not None and valu_busy >= 0.6) else "latency" if (hbm_frac is not None or valu_busy is not None) else ("valu-issue" if resident else "hbm")
+    return {"bound": bound, "bound_rule": "hbm if measured HBM-side traffic >= 0.5 of peak, else valu-issue if valu_busy_frac >= 0.6, else latency (counters: %s)" % tname,
+            "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": frac_alg, "frac_algorithmic": frac_alg,
+            "frac_note": "ALGORITHMIC bytes of the dominant kernel / its launch time / HBM peak (the contract's definition); the bytes the "
+                         "memory system really moved are in hbm_measured and traffic",
+            "traffic": traffic, "traffic_source": traffic_source, "hbm_measured": hbm_measured,
+            "kernel": "wf_trace8_kernel<false>", "kernel_ms": round(trace_ms, 4), "launches_per_step": round(launches / max(1, steps), 1),
+            "rays_per_launch": int(rays_per_launch),
+            "algorithmic_bytes_per_ray": round(trace_bytes_per_ray, 1),
+            "box_tests_per_ray": round(ci.box_tests / max(1, ci.rays), 2), "tri_tests_per_ray": round(ci.tri_tests / max(1, ci.rays), 2),
+            "traversal_data_bytes": int(scene_bytes), "cache_resident": resident, "traversal_data_lives_in": residency,
+            "l2_relative": {"traversal_GBps": round(trav_bytes_per_ray * rays_per_launch / (trace_ms * 1e-3) / 1e9, 1), "l2_peak_GBps": L2_PEAK_GBS,
+                            "frac": round(trav_bytes_per_ray * rays_per_launch / (trace_ms * 1e-3) / 1e9 / L2_PEAK_GBS, 4)},
+            "valu_busy_frac": valu_busy, "valu_issue_note": pmc.get("valu_issue_note"),
+            "valu_lane_utilisation": pmc.get("wf_trace_kernel_valu_lane_utilisation"),
+            "salu_to_valu_instructions": pmc.get("wf_trace_kernel_salu_to_valu"),
+            "inner_steps_per_ray": pmc.get("wf_trace_kernel_inner_steps_per_ray"),
+            "second_kernel": {"kernel": "wf_shade_kernel<false>", "kernel_ms": round(shade_ms, 4),
+                              "valu_lane_utilisation": pmc.get("wf_shade_kernel_valu_lane_utilisation")},
+            "streams": n_streams,
+            "per_stream_ms_per_step": round(per_stream_ms, 2),
+            "reconciliation": "each of the %d sub-pipeline streams runs launches_per_step / %d x (trace %.4f + shade %.4f ms) = %.1f ms of "
+                              "back-to-back kernels per step; ms_per_step = %.1f (the two streams overlap: a kernel's duration is that of a kernel "
+                              "sharing the GPU with the other stream's)" % (n_streams, n_streams, trace_ms, shade_ms, per_stream_ms, dt / steps * 1e3),
+            "note": ("%.1f MB of nodes + triangle records live in %s%s; `frac` (vs HBM peak) is the contract's algorithmic figure -- for cache-resident data a cache "
+                     "bandwidth --, `hbm_measured` what the L2's memory side moved (FETCH_SIZE counts Infinity-Cache hits too: for data that fits the "
+                     "256-MB MALL that is not all HBM)") % (scene_bytes / 1e6, residency, ": HBM carries only the path-pool stream" if resident else "")}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -192,10 +293,14 @@ def main():
                          "(tools/scaling_emulation.py turns the sweep into profiles/r04_scaling_emulation.json)")
     ap.add_argument("--emulate-rank", default="0", metavar="R|all", help="which rank of the emulated split to render; 'all' = every rank in turn, "
                     "ms_per_step = the slowest (what an N-GPU step would take), per-rank times in emulated_ranks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline (an instrumented pass) and cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the film of the last timed step to DIR/film.npy (float32)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl")
     ap.add_argument("--dry", action="store_true", help="launcher / collective rehearsal without a GPU: no rendering, films are synthetic")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))           # the parent does no GPU work and imports no torch
@@ -244,6 +349,8 @@ def main():
         t_all = torch.tensor([dt], dtype=torch.float64)
         if dist is not None:
             dist.all_reduce(t_all, op=dist.ReduceOp.MAX)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, film.view(H, W, 4).numpy())
         if rank == 0:
             print(json.dumps({"metric": "Mray/s (primary+secondary), %s %dspp" % (cfg["scene"], cfg["spp"]), "value": 0.0, "unit": "Mray/s", "dry": True,
                               "n_gpus": n_ranks, "rccl_ranks": n_ranks, "backend": args.backend, "steps": args.steps, "warmup": args.warmup,
@@ -337,80 +444,6 @@ def main():
 
     out = None
     if rank == 0:
-        # ---- kernel durations: the library brackets the launches of every MCPT_TIME_KERNELS-th iteration of the timed region with HIP
-        # events recorded on the launch stream (a sub-pipeline stream forked from `side`); *_ms_total = sampled mean x launches
-        # since reset_counters().  Dominant kernel = wf_trace8_kernel (BVH traversal); one launch of it per pipeline iteration.
-        launches = max(1, c.iterations)
-        trace_ms = c.trace_ms_total / launches
-        shade_ms = c.shade_ms_total / launches
-        rays_per_launch = c.rays / launches
-        # ---- algorithmic bytes per ray from an instrumented pass (same scene / depth / seed, a few spp)
-        ri = pkg.Renderer(scene, max_depth=depth, device=local, flags=pkg.FLAG_COUNT_TRAVERSAL)
-        ri.render(32 if W * H <= 1 << 20 else 4, seed=20251004); ci = ri.counters(); ri.close()
-        trav_bytes_per_ray = (B_BOX * ci.box_tests + B_TRI * ci.tri_tests) / max(1, ci.rays)
-        trace_bytes_per_ray = trav_bytes_per_ray + B_RAY
-        algo_bytes = trace_bytes_per_ray * rays_per_launch
-        achieved = algo_bytes / (trace_ms * 1e-3) / 1e9
-        scene_bytes = int(info.traversal_bytes)                       # wide nodes + triangle test records, from the library
-        resident = scene_bytes <= L2_BYTES
-        residency = "L2" if scene_bytes <= L2_BYTES else "Infinity Cache (MALL)" if scene_bytes <= MALL_BYTES else "HBM"
-        # ---- measured HBM traffic / VALU issue / lane utilisation: PMC counters cannot be read inside this process; they come from the
-        # committed rocprofv3 --pmc passes of the same workload and build (tools/r03_profile.sh -> profiles/r03_traffic.json), per traced ray,
-        # x this run's rays per launch / rays per second
-        traffic = None; traffic_source = None; pmc = {}
-        tpath = next((q for q in (os.path.join(ROOT, "profiles", "r04_traffic.json"), os.path.join(ROOT, "profiles", "r03_traffic.json")) if os.path.exists(q)), None)
-        tname = "profiles/" + os.path.basename(tpath) if tpath else None
-        if tpath:
-            pmc = json.load(open(tpath)).get(args.config, {})
-            if pmc.get("wf_trace_kernel_hbm_bytes_per_ray"):
-                traffic = int(pmc["wf_trace_kernel_hbm_bytes_per_ray"] * rays_per_launch)
-                traffic_source = "%s[%s]: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (not this run), bytes per ray x this run's rays per launch" % (tname, args.config)
-        rays_per_s = total_rays / dt / max(1, n_ranks)                     # this GPU's share of the job's ray rate
-        hbm_measured = None
-        if pmc.get("wf_trace_kernel_hbm_bytes_per_ray") and pmc.get("wf_shade_kernel_hbm_bytes_per_ray"):
-            tb, sb = pmc["wf_trace_kernel_hbm_bytes_per_ray"], pmc["wf_shade_kernel_hbm_bytes_per_ray"]
-            hbm_measured = {"level": "step (bytes per traced ray from the PMC passes of this build x this run's rays/s per GPU)",
-                            "trace_bytes_per_ray": tb, "shade_bytes_per_ray": sb,
-                            "trace_GBps": round(tb * rays_per_s / 1e9, 1), "shade_GBps": round(sb * rays_per_s / 1e9, 1),
-                            "total_GBps": round((tb + sb) * rays_per_s / 1e9, 1), "frac_of_hbm_peak": round((tb + sb) * rays_per_s / 1e9 / HBM_PEAK_GBS, 4),
-                            "fetch_correction": pmc.get("fetch_correction_note"),
-                            "source": "%s[%s]" % (tname, args.config)}
-        n_streams = 2 if (c.shade_ms_total > 0 and launches >= 2) else 1
-        per_stream_ms = launches / max(1, args.steps) / n_streams * (trace_ms + shade_ms)
-        frac_alg = round(achieved / HBM_PEAK_GBS, 4)
-        # what binds, decided from the counters the line carries (not from the scene's size): the memory system when the measured HBM-side traffic is
-        # at least half of the peak; else VALU issue when the two kernels keep the SIMDs' vector ALUs busy most of the time (SQ_ACTIVE_INST_VALU over
-        # the SIMD-cycles of the render: `valu_busy_frac`); else latency / occupancy
-        hbm_frac = hbm_measured["frac_of_hbm_peak"] if hbm_measured else None
-        valu_busy = pmc.get("valu_busy_frac", pmc.get("valu_issue_frac"))
-        bound = "hbm" if (hbm_frac is not None and hbm_frac >= 0.5) else "valu-issue" if (valu_busy is not None and valu_busy >= 0.6) else "latency" if (hbm_frac is not None or valu_busy is not None) else ("valu-issue" if resident else "hbm")
-        roofline = {"bound": bound, "bound_rule": "hbm if measured HBM-side traffic >= 0.5 of peak, else valu-issue if valu_busy_frac >= 0.6, else latency (counters: %s)" % tname,
-                    "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": frac_alg, "frac_algorithmic": frac_alg,
-                    "frac_note": "ALGORITHMIC bytes of the dominant kernel / its launch time / HBM peak (the contract's definition); the bytes the "
-                                 "memory system really moved are in hbm_measured and traffic",
-                    "traffic": traffic, "traffic_source": traffic_source, "hbm_measured": hbm_measured,
-                    "kernel": "wf_trace8_kernel<false>", "kernel_ms": round(trace_ms, 4), "launches_per_step": round(launches / max(1, args.steps), 1),
-                    "rays_per_launch": int(rays_per_launch),
-                    "algorithmic_bytes_per_ray": round(trace_bytes_per_ray, 1),
-                    "box_tests_per_ray": round(ci.box_tests / max(1, ci.rays), 2), "tri_tests_per_ray": round(ci.tri_tests / max(1, ci.rays), 2),
-                    "traversal_data_bytes": int(scene_bytes), "cache_resident": resident, "traversal_data_lives_in": residency,
-                    "l2_relative": {"traversal_GBps": round(trav_bytes_per_ray * rays_per_launch / (trace_ms * 1e-3) / 1e9, 1), "l2_peak_GBps": L2_PEAK_GBS,
-                                    "frac": round(trav_bytes_per_ray * rays_per_launch / (trace_ms * 1e-3) / 1e9 / L2_PEAK_GBS, 4)},
-                    "valu_busy_frac": valu_busy, "valu_issue_note": pmc.get("valu_issue_note"),
-                    "valu_lane_utilisation": pmc.get("wf_trace_kernel_valu_lane_utilisation"),
-                    "salu_to_valu_instructions": pmc.get("wf_trace_kernel_salu_to_valu"),
-                    "inner_steps_per_ray": pmc.get("wf_trace_kernel_inner_steps_per_ray"),
-                    "second_kernel": {"kernel": "wf_shade_kernel<false>", "kernel_ms": round(shade_ms, 4),
-                                      "valu_lane_utilisation": pmc.get("wf_shade_kernel_valu_lane_utilisation")},
-                    "streams": n_streams,
-                    "per_stream_ms_per_step": round(per_stream_ms, 2),
-                    "reconciliation": "each of the %d sub-pipeline streams runs launches_per_step / %d x (trace %.4f + shade %.4f ms) = %.1f ms of "
-                                      "back-to-back kernels per step; ms_per_step = %.1f (the two streams overlap: a kernel's duration is that of a kernel "
-                                      "sharing the GPU with the other stream's)" % (n_streams, n_streams, trace_ms, shade_ms, per_stream_ms, dt / args.steps * 1e3),
-                    "note": ("%.1f MB of nodes + triangle records live in %s%s; `frac` (vs HBM peak) is the contract's algorithmic figure -- for cache-resident data a cache "
-                             "bandwidth --, `hbm_measured` what the L2's memory side moved (FETCH_SIZE counts Infinity-Cache hits too: for data that fits the "
-                             "256-MB MALL that is not all HBM)") % (scene_bytes / 1e6, residency, ": HBM carries only the path-pool stream" if resident else "")}
         rpp_ref = (c.rays_primary + c.rays_continuation + c.self_shadow_tests) / max(1, c.paths)
         out = {
             "metric": "Mray/s (primary+secondary), %s %dspp" % (cfg["scene"], cfg["spp"]), "value": round(total_rays / dt / 1e6, 2), "unit": "Mray/s",
@@ -432,12 +465,15 @@ def main():
             "self_shadow_rate": round(c.self_shadow_hits / max(1, c.self_shadow_tests), 4),
             "film_count_plane_ok": film_ok,
             "emulated_world": emu if emu > 1 else None, "emulated_rank": (my_rank if emu > 1 else None), "emulated_ranks": emu_ranks,
-            "roofline": roofline,
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(pkg, cfg, scene, rpp_ref)
-        elif not args.no_cpu_baseline:
-            out["cpu_baseline"] = None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, accum.view(H, W, 4).cpu().numpy())
+        if args.full:
+            out["roofline"] = roofline(pkg, args.config, scene, info, c, dt, args.steps, n_ranks, total_rays, depth, local)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(pkg, cfg, scene, rpp_ref)
+            elif not args.no_cpu_baseline:
+                out["cpu_baseline"] = None
     r.close()
     if world > 1:
         dist.barrier()

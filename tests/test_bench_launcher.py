@@ -30,6 +30,22 @@ def test_gpus_flag_launches_that_many_ranks():
     assert out["scaling"] == "weak" and out["count_plane_ok"] is True and out["first_samples_rank0"] == [0, 16, 32]   # rounds 1-3's mode: 8 spp per rank
 
 
+def test_dump_outputs_writes_the_last_steps_film(tmp_path):
+    """--dump-outputs DIR: the [H, W, 4] float32 film of the last timed step as DIR/film.npy (the dry rehearsal's synthetic film here)."""
+    import numpy as np
+    p = _run(["--gpus", "1", "--backend", "gloo", "--dry", "--steps", "2", "--warmup", "1", "--spp", "8", "--dump-outputs", str(tmp_path)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len([l for l in p.stdout.splitlines() if l.startswith("{")]) == 1
+    film = np.load(tmp_path / "film.npy")
+    assert film.dtype == np.float32 and film.shape == (800, 800, 4)
+    assert np.all(film[..., 3] == 8.0)
+
+
+def test_steps_below_one_is_an_error():
+    p = _run(["--gpus", "1", "--backend", "gloo", "--dry", "--steps", "0"])
+    assert p.returncode == 2 and "--steps" in p.stderr
+
+
 def test_world_size_mismatch_is_an_error():
     p = _run(["--gpus", "4", "--backend", "gloo", "--dry"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"}, drop=())
     assert p.returncode == 2 and "WORLD_SIZE" in p.stderr

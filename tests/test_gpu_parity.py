@@ -1359,6 +1359,31 @@ def test_bench_two_ranks_over_rccl_when_two_gpus_are_visible():
         assert out["scaling"] == ("strong" if shard == "tiles" else "weak") and out["value"] > 0
 
 
+def test_bench_plain_run_reports_the_headline_and_dumps_the_film(tmp_path):
+    """A plain `bench.py` run carries the headline only and writes the last timed step's film with --dump-outputs; `--full` adds the
+    roofline of its own instrumented pass."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+
+    def bench(*extra):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--spp", "8"] + list(extra),
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        return json.loads(lines[0])
+
+    out = bench("--dump-outputs", str(tmp_path))
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0 and out["film_count_plane_ok"] is True
+    assert "roofline" not in out and "cpu_baseline" not in out
+    film = np.load(tmp_path / "film.npy")
+    assert film.dtype == np.float32 and film.shape == (800, 800, 4)
+    assert np.all(film[..., 3] == 8.0) and np.all(np.isfinite(film)) and film[..., :3].mean() > 0
+    full = bench("--full", "--no-cpu-baseline")
+    assert full["roofline"]["kernel_ms"] > 0 and full["roofline"]["algorithmic_bytes_per_ray"] > 0 and "cpu_baseline" not in full
+
+
 def test_path_pools_grow_with_the_job_and_keep_the_film_exact(pkg):
     """The path pools are allocated by the first render call and grown to the largest job seen (mcpt_api.cpp: ensure_pool): a context that
     rendered one sample of a small film holds a small pool; a later, larger job re-allocates it between two calls -- nothing of a job lives in

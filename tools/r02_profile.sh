@@ -6,7 +6,7 @@ set -uo pipefail
 CFG="$1"; SPP="$2"; STEPS="${3:-3}"
 OUT="$GRAFT_REPO_ROOT/gpurun_out/r02_prof_$CFG"; mkdir -p "$OUT"
 cd "$GRAFT_REPO_ROOT"
-timeout -k 10 500 python3 bench.py --config "$CFG" --steps "$STEPS" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 500 python3 bench.py --full --config "$CFG" --steps "$STEPS" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json" | cut -c1-400
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$GRAFT_REPO_ROOT/bench.py" --config "$CFG" --steps "$STEPS" --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err" ) || { tail -20 "$OUT/rocprof.err"; exit 1; }
 find "$OUT/stats" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;
