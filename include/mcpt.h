@@ -188,6 +188,26 @@ mcpt_status mcpt_tonemap_buffer(mcpt_ctx* ctx, const void* device_rgba, uint8_t*
 mcpt_status mcpt_get_counters(mcpt_ctx* ctx, mcpt_counters* out);  /* synchronises */
 mcpt_status mcpt_reset_counters(mcpt_ctx* ctx);
 
+/* ---- denoised preview ---------------------------------------------------------------------------------- */
+/* Edge-avoiding a-trous wavelet filter of a film, guided by first-hit feature buffers.  The features are rendered by
+ * mcpt_render_features from the camera rays mcpt_render(ctx, ..., seed, first_sample = 0) traces for samples 0 .. spp-1: per pixel
+ * 8 floats {albedo r, g, b, coverage f, normal x, y, z, depth z} (albedo = kd + ks of non-emissive first hits summed / spp, f = their
+ * share of the spp, normal = sum of camera-facing shading normals / max(hits, 1), z = mean hit distance, 0 without hits).  They depend
+ * on the scene, the camera, spp and seed only: clearing or writing the film keeps them; a clone starts without them.
+ * mcpt_denoise filters a film of {sum rgb, count} records (NULL = the context film, which it never writes) into the context's
+ * denoised film {r, g, b, 1} (count 0: {0, 0, 0, 0}) -- a mean, so mcpt_tonemap_buffer displays it as it is. */
+typedef struct mcpt_denoise_opts {
+    uint32_t struct_size;                           /* = sizeof(mcpt_denoise_opts) */
+    uint32_t iterations;                            /* a-trous levels, 0 = default 5, max 10 */
+    float sigma_color, sigma_normal, sigma_depth;   /* 0 = default (4, 128, 4) */
+    uint32_t reserved[3];
+} mcpt_denoise_opts;
+mcpt_status mcpt_render_features(mcpt_ctx* ctx, uint32_t spp, uint64_t seed);          /* 1 <= spp <= 64, asynchronous */
+mcpt_status mcpt_read_features(mcpt_ctx* ctx, float* out8);                            /* synchronises, then D2H: width*height*8 floats */
+mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_denoise_opts* opts);  /* NULL film = ctx film; NULL opts = defaults; asynchronous */
+mcpt_status mcpt_read_denoised(mcpt_ctx* ctx, float* rgba_host);                       /* synchronises, then D2H: width*height*4 floats */
+mcpt_status mcpt_denoised_device_ptr(mcpt_ctx* ctx, void** out_device_rgba);           /* the denoised film on the device (after a first mcpt_denoise) */
+
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that
  * torch.distributed / RCCL all-reduces in place).  NULL re-binds the internal buffer. */

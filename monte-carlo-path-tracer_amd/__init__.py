@@ -86,6 +86,11 @@ class SceneInfo(C.Structure):
                 ("reserved0", C.c_uint32), ("traversal_bytes", C.c_uint64), ("centre", C.c_double * 3), ("wide_tree_hash", C.c_uint64)]
 
 
+class DenoiseOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
 def texture_to_float(img_u8: np.ndarray) -> np.ndarray:
     """What stbi_loadf gives the reference for an 8-bit image (model.cpp:8-23; stb_image.h:1553,1849):
     (c/255)^2.2 per channel, row 0 = first row of the file."""
@@ -184,6 +189,11 @@ def load_library() -> C.CDLL:
         "mcpt_probe_paths": [vp, C.c_uint32, vp, vp, C.c_uint64, vp],
         "mcpt_probe_rng": [vp, C.c_uint32, vp, C.c_uint64, vp],
         "mcpt_probe_texture": [vp, C.c_uint32, C.c_uint32, vp, vp],
+        "mcpt_render_features": [vp, C.c_uint32, C.c_uint64],
+        "mcpt_read_features": [vp, vp],
+        "mcpt_denoise": [vp, vp, P(DenoiseOpts)],
+        "mcpt_read_denoised": [vp, vp],
+        "mcpt_denoised_device_ptr": [vp, P(vp)],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -203,6 +213,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_get_counters", "mcpt_reset_counters", "mcpt_bind_accum", "mcpt_accum_device_ptr", "mcpt_set_stream",
     "mcpt_set_null_stream", "mcpt_probe_trace", "mcpt_probe_trace4", "mcpt_probe_cast_ray", "mcpt_probe_hit_shade", "mcpt_probe_bsdf", "mcpt_probe_sample_light",
     "mcpt_probe_paths", "mcpt_probe_rng", "mcpt_probe_texture",
+    "mcpt_render_features", "mcpt_read_features", "mcpt_denoise", "mcpt_read_denoised", "mcpt_denoised_device_ptr",
 ]
 
 
@@ -336,6 +347,32 @@ class Renderer:
             self.set_stream(h)
         else:
             self.set_null_stream()
+
+    # ---- denoised preview
+    def render_features(self, spp: int = 4, seed: int = 0):
+        """First-hit feature buffers from the camera rays of samples 0 .. spp-1 of `seed` (asynchronous)."""
+        self._check(self.lib.mcpt_render_features(self.ctx, spp, seed))
+
+    def features(self) -> np.ndarray:
+        """(h, w, 8): albedo rgb, coverage, normal xyz, depth."""
+        out = np.zeros((self.height, self.width, 8), np.float32)
+        self._check(self.lib.mcpt_read_features(self.ctx, _ptr(out)))
+        return out
+
+    def denoise(self, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, device_ptr: Optional[int] = None) -> np.ndarray:
+        """A-trous filter of the context film (or of the device film at `device_ptr`): (h, w, 4) records {r, g, b, 1}."""
+        o = DenoiseOpts()
+        o.struct_size = C.sizeof(DenoiseOpts); o.iterations = iterations
+        o.sigma_color = sigma_color; o.sigma_normal = sigma_normal; o.sigma_depth = sigma_depth
+        self._check(self.lib.mcpt_denoise(self.ctx, None if device_ptr is None else C.c_void_p(device_ptr), C.byref(o)))
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self.lib.mcpt_read_denoised(self.ctx, _ptr(out)))
+        return out
+
+    def denoised_device_ptr(self) -> int:
+        p = C.c_void_p()
+        self._check(self.lib.mcpt_denoised_device_ptr(self.ctx, C.byref(p)))
+        return p.value
 
     # ---- probes
     def probe_trace(self, origin, direction, t1=None, t2=None, any_hit=False):

@@ -5,6 +5,7 @@
 #include "scene_build.h"
 #include "bvh_gpu.h"
 #include "wavefront.h"
+#include "denoise.h"
 
 #include <chrono>
 #include <cstdlib>
@@ -80,6 +81,10 @@ struct mcpt_ctx {
     // Scene::getPixelsColor every frame (main.cpp:26-33): the tonemapped film's device buffer and its pinned host image live as long as the
     // context (allocated by the first tonemap call) -- no hipMalloc / hipMemset / hipFree per frame
     DevBuf tone_dev; uint8_t* tone_host = nullptr;
+    // Denoised preview (denoise.hip): first-hit features (2 float4 / pixel), allocated by the first mcpt_render_features; the filter's guide,
+    // two ping-pong {irr, var} buffers and the denoised film (1 float4 / pixel each), allocated by the first mcpt_denoise
+    DevBuf dn_feat, dn_guide, dn_iv0, dn_iv1, dn_out;
+    bool dn_have_features = false, dn_have_out = false;
 };
 
 namespace {
@@ -111,6 +116,7 @@ void destroy_ctx(mcpt_ctx* c) {
         if (L.stream) (void)hipStreamDestroy(L.stream);
     }
     c->tone_dev.free_(); if (c->tone_host) (void)hipHostFree(c->tone_host);
+    c->dn_feat.free_(); c->dn_guide.free_(); c->dn_iv0.free_(); c->dn_iv1.free_(); c->dn_out.free_();
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     for (uint32_t i = 0; i < mcpt_ctx::TIMED; i++) { if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]); if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -839,6 +845,76 @@ mcpt_status mcpt_set_null_stream(mcpt_ctx* ctx) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     st = resolve_timing(ctx); if (st != MCPT_OK) return st;
     ctx->stream = nullptr;                                             // the device's legacy default stream
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ denoised preview
+mcpt_status mcpt_render_features(mcpt_ctx* ctx, uint32_t spp, uint64_t seed) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (spp < 1 || spp > DN_MAX_SPP) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_features: need 1 <= spp <= 64");
+    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
+    const size_t n = size_t(ctx->width) * ctx->height;
+    if (!ctx->dn_feat.p) {
+        HIP_TRY(ctx->dn_feat.alloc(2 * n * sizeof(float4)));
+        ctx->info.device_bytes += ctx->dn_feat.bytes;
+    }
+    HIP_TRY(launch_dn_features(ctx->dev, spp, uint32_t(seed), uint32_t(seed >> 32), static_cast<float4*>(ctx->dn_feat.p), ctx->stream));
+    ctx->dn_have_features = true;
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_read_features(mcpt_ctx* ctx, float* out8) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out8) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    if (!ctx->dn_have_features) return fail(MCPT_ERR_INVALID_ARG, "mcpt_read_features: no features rendered yet (mcpt_render_features)");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(out8, ctx->dn_feat.p, ctx->dn_feat.bytes, hipMemcpyDeviceToHost));
+    return resolve_timing(ctx);
+}
+
+mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_denoise_opts* opts) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    mcpt_denoise_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o;
+    if (opts) {
+        if (opts->struct_size != sizeof(mcpt_denoise_opts)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: opts->struct_size != sizeof(mcpt_denoise_opts)");
+        o = *opts;
+    }
+    if (o.iterations > DN_MAX_LEVELS) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: at most 10 iterations");
+    if (!(o.sigma_color >= 0.f) || !(o.sigma_normal >= 0.f) || !(o.sigma_depth >= 0.f)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be >= 0 (0 = default)");
+    if (!ctx->dn_have_features) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: no features rendered yet (mcpt_render_features)");
+    const size_t n = size_t(ctx->width) * ctx->height;
+    if (!ctx->dn_out.p) {
+        DevBuf* bufs[4] = {&ctx->dn_guide, &ctx->dn_iv0, &ctx->dn_iv1, &ctx->dn_out};
+        for (DevBuf* b : bufs) { HIP_TRY(b->alloc(n * sizeof(float4))); ctx->info.device_bytes += b->bytes; }
+    }
+    DnParams p;
+    p.width = ctx->width; p.height = ctx->height;
+    p.sigma_c = o.sigma_color > 0.f ? o.sigma_color : 4.f;
+    p.sigma_n = o.sigma_normal > 0.f ? o.sigma_normal : 128.f;
+    p.sigma_z = o.sigma_depth > 0.f ? o.sigma_depth : 4.f;
+    p.theta = float(ctx->dev.cam.h / double(ctx->height));
+    const uint32_t levels = o.iterations ? o.iterations : 5u;
+    const float4* film = device_rgba ? static_cast<const float4*>(device_rgba) : ctx->accum;
+    HIP_TRY(launch_dn_filter(p, levels, film, static_cast<const float4*>(ctx->dn_feat.p), static_cast<float4*>(ctx->dn_guide.p),
+                             static_cast<float4*>(ctx->dn_iv0.p), static_cast<float4*>(ctx->dn_iv1.p), static_cast<float4*>(ctx->dn_out.p), ctx->stream));
+    ctx->dn_have_out = true;
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_read_denoised(mcpt_ctx* ctx, float* rgba_host) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!rgba_host) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    if (!ctx->dn_have_out) return fail(MCPT_ERR_INVALID_ARG, "mcpt_read_denoised: nothing denoised yet (mcpt_denoise)");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(rgba_host, ctx->dn_out.p, ctx->dn_out.bytes, hipMemcpyDeviceToHost));
+    return resolve_timing(ctx);
+}
+
+mcpt_status mcpt_denoised_device_ptr(mcpt_ctx* ctx, void** out_device_rgba) {
+    if (!ctx || !out_device_rgba) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    *out_device_rgba = nullptr;
+    if (!ctx->dn_have_out) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoised_device_ptr: nothing denoised yet (mcpt_denoise)");
+    *out_device_rgba = ctx->dn_out.p;
     return MCPT_OK;
 }
 

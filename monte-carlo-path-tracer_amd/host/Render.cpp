@@ -73,6 +73,33 @@ const Color3b* Render::tonemapped(Scene& scene) {
     if (mcpt_tonemap_map(ctx, 0, &px) != MCPT_OK) { std::cerr << "Error: mcpt_tonemap_map: " << mcpt_last_error() << std::endl; return nullptr; }
     return reinterpret_cast<const Color3b*>(px);
 }
+const Color3b* Render::denoised(Scene& scene, const mcpt_denoise_opts* opts) {
+    if (!ctx) return nullptr;
+    if (scene.width() * scene.height() * 4 != int(film.size())) { std::cerr << "Error: Render::denoised: the Scene's size differs from the camera's" << std::endl; return nullptr; }
+    if (!features) {
+        if (mcpt_render_features(ctx, 4, seed) != MCPT_OK) { std::cerr << "Error: mcpt_render_features: " << mcpt_last_error() << std::endl; return nullptr; }
+        features = true;
+    }
+    mcpt_status st;
+    if (&scene == target && dirty && !scene.host_samples()) {
+        st = mcpt_denoise(ctx, nullptr, opts);                    // the whole film is this Render's device film: filtered where it lies
+    } else {
+        // The film is (partly) on the host: fold it the way getPixelsColor does and upload the sum.  This layer has no HIP of its own, so the
+        // upload goes through this Render's device film, which holds nothing once its samples have been handed over (flush_into clears it),
+        // and is cleared again afterwards.
+        if (target && target != &scene) flush_into(*target);
+        const float* sum = reinterpret_cast<const float*>(scene.pixels());     // (folds whichever source the Scene has)
+        st = mcpt_write_accum(ctx, sum);
+        if (st == MCPT_OK) st = mcpt_denoise(ctx, nullptr, opts);
+        if (st == MCPT_OK) st = mcpt_clear_accum(ctx);
+    }
+    void* dev = nullptr;
+    denoised_rgb.resize(size_t(scene.width()) * scene.height());
+    if (st == MCPT_OK) st = mcpt_denoised_device_ptr(ctx, &dev);
+    if (st == MCPT_OK) st = mcpt_tonemap_buffer(ctx, dev, reinterpret_cast<uint8_t*>(denoised_rgb.data()), 0);
+    if (st != MCPT_OK) { std::cerr << "Error: Render::denoised: " << mcpt_last_error() << std::endl; return nullptr; }
+    return denoised_rgb.data();
+}
 void Render::displaced(Scene& scene) { if (&scene == target) target = nullptr; }   // (already flushed by Scene::attach)
 void Render::scene_gone(Scene& scene) {
     if (&scene != target) return;

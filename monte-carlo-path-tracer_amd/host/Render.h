@@ -20,6 +20,10 @@ public:
     void scene_gone(Scene& scene) override;
     void displaced(Scene& scene) override;
     const Color3b* tonemapped(Scene& scene) override;
+    // Denoised preview of what `scene` holds: the a-trous filter of the film getPixelsColor shows, tonemapped the same
+    // way -- width * height pixels in getPixelsColor's orientation, valid until the next call.  The first call renders the feature buffers
+    // (4 samples of `seed`).  nullptr on failure.
+    const Color3b* denoised(Scene& scene, const mcpt_denoise_opts* opts = nullptr);
     Render(const Render&) = delete;
     Render& operator=(const Render&) = delete;
     bool ok() const { return ctx != nullptr; }
@@ -31,6 +35,8 @@ private:
     std::vector<float> film;
     Scene* target = nullptr;                          // the Scene the device film belongs to
     bool dirty = false;                               // the device film holds samples `target` has not seen
+    bool features = false;                            // mcpt_render_features has run for this context
+    std::vector<Color3b> denoised_rgb;
     void create(Model& m, const mcpt_opts& opts);
 };
 // Fills an mcpt_scene_desc that points INTO `m` (and into the two scratch vectors); valid while all three live.

@@ -40,6 +40,7 @@ public:
     void attach(FilmSource* source);                                  // at most one source at a time: attaching another flushes the first
     void detach(FilmSource* source);                                  // (no flush: the source is going away and has flushed itself)
     FilmSource* source() const { return m_source; }
+    bool host_samples() const { return m_host_samples; }               // m_Pixels holds part of the film (else all of it is with the source)
     void sync();                                                      // fold the device part in now
     Pixels* pixels() { sync(); return m_Pixels.get(); }
     int width() const { return w; }

@@ -19,6 +19,7 @@
 static void usage() {
     std::cout << "usage: mcpt_cli scene.obj [--spp N] [--batch B] [--depth D] [--gpus G] [--shard samples|tiles] [--out prefix] [--seed S] [--recursive] [--corrected]\n"
                  "                          [--deterministic] [--ref-index-order] [--ref-tie-order] [--gpu-bvh] [--check] [--dump-model file] [--save-every K]\n"
+                 "                          [--denoise]   (also writes <prefix><frames>_denoised.png, and one per --save-every image)\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -43,7 +44,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     std::string filename = argv[1], out, dump_model;
-    uint32_t spp = 64, batch = 0, depth = 0, gpus = 1, save_every = 0; uint64_t seed = 20251004; uint32_t flags = 0, integrator = 0; bool ref_order = false, check_only = false, shard_tiles = false;
+    uint32_t spp = 64, batch = 0, depth = 0, gpus = 1, save_every = 0; uint64_t seed = 20251004; uint32_t flags = 0, integrator = 0; bool ref_order = false, check_only = false, shard_tiles = false, denoise = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -57,6 +58,7 @@ int main(int argc, char** argv) {
         else if (a == "--dump-model") dump_model = next();
         else if (a == "--save-every") save_every = uint32_t(std::atoi(next()));
         else if (a == "--shard") shard_tiles = std::string(next()) == "tiles";
+        else if (a == "--denoise") denoise = true;
         else { usage(); return 2; }
     }
     Model model(filename, ref_order);
@@ -125,6 +127,19 @@ int main(int argc, char** argv) {
     std::vector<float> film(size_t(w) * h * 4);
     std::atomic<int> failed{0};                       // any device error or failed collective: no image, non-zero exit
     auto fail_with = [&](const std::string& what) { std::cerr << "Error: " << what << std::endl; failed.store(1); };
+    // --denoise: the a-trous preview filter of device 0's film -- or of the films summed on device 0 -- guided by first-hit
+    // features rendered once, from 4 camera samples of the run's seed
+    if (denoise && mcpt_render_features(renders[0]->handle(), 4, seed) != MCPT_OK) { std::cerr << "Error: mcpt_render_features: " << mcpt_last_error() << std::endl; return 1; }
+    auto save_denoised = [&](const void* device_film, uint32_t at) {
+        std::vector<uint8_t> rgb(size_t(w) * h * 3);
+        void* den = nullptr;
+        mcpt_ctx* c = renders[0]->handle();
+        if (mcpt_denoise(c, device_film, nullptr) != MCPT_OK || mcpt_denoised_device_ptr(c, &den) != MCPT_OK || mcpt_tonemap_buffer(c, den, rgb.data(), 1) != MCPT_OK)
+            return fail_with(std::string("denoised image: ") + mcpt_last_error());
+        const std::string file = out + std::to_string(at) + "_denoised.png";
+        if (write_png_rgb8(file, w, h, rgb.data())) std::cout << "Image saved successfully: " << file << std::endl;
+        else std::cerr << "Failed to save image: " << file << std::endl;
+    };
     // The films stay on the devices from batch to batch (the reference's loop reads its film every frame only to display it): per batch
     // one mcpt_render per device, at the end the path's one exchange step and one read-back.
     while (frame < spp && !failed.load()) {
@@ -176,6 +191,7 @@ int main(int argc, char** argv) {
             const std::string file = out + std::to_string(frame) + ".png";
             if (write_png_rgb8(file, w, h, rgb.data())) std::cout << "Image saved successfully: " << file << std::endl;
             else std::cerr << "Failed to save image: " << file << std::endl;
+            if (denoise) { save_denoised(gpus == 1 ? nullptr : progress_film, frame); if (failed.load()) break; }
         }
     }
     if (!failed.load()) {
@@ -190,6 +206,11 @@ int main(int argc, char** argv) {
             ok = (ncclGroupEnd() == ncclSuccess) && ok;
             for (uint32_t g = 0; g < gpus && ok; g++) ok = hipSetDevice(int(g)) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
             if (!ok) fail_with("RCCL all-reduce of the films failed");
+        }
+        if (!failed.load() && denoise) {            // device 0's film is the whole image now (all-reduced in place with several devices)
+            void* p = nullptr;
+            if (mcpt_accum_device_ptr(renders[0]->handle(), &p) != MCPT_OK) fail_with(std::string("mcpt_accum_device_ptr: ") + mcpt_last_error());
+            else save_denoised(gpus == 1 ? nullptr : p, frame);
         }
         if (!failed.load()) {
             if (mcpt_read_accum(renders[0]->handle(), film.data()) != MCPT_OK) fail_with(std::string("mcpt_read_accum: ") + mcpt_last_error());
