@@ -13,10 +13,9 @@ struct GpuBvh {
     double ms = 0.0;               // wall time incl. upload / download
 };
 
-// Needs n > MCPT_LEAF_MAX and a current HIP device.  Returns false with `err` set on any HIP error.
-bool gpu_build_bvh2(const float* tri_boxes, uint32_t n, GpuBvh& out, std::string& err);
-// Same contract, SAH-costed: PLOC (parallel locally-ordered clustering, Meister & Bittner 2018) over the Morton order -- every merge is
-// the one that minimises the merged box's surface area within a +-16 window.  The default of MCPT_FLAG_GPU_BVH_BUILD.
+// The builder of MCPT_FLAG_GPU_BVH_BUILD: PLOC (parallel locally-ordered clustering, Meister & Bittner 2018) over the Morton order --
+// every merge is the one that minimises the merged box's surface area within a +-16 window.  Needs n > MCPT_LEAF_MAX and a current HIP
+// device.  Returns false with `err` set on any HIP error.
 bool gpu_build_ploc(const float* tri_boxes, uint32_t n, GpuBvh& out, std::string& err);
 
 // The 8-wide collapse of build_bvh8 (scene_build.cpp) on the device: same dynamic programme, same octant slots, same numbering -- the records

@@ -35,7 +35,7 @@
 #define MCPT_LEAF_MAX 2
 #endif
 #ifndef MCPT_STACK_DEPTH
-#define MCPT_STACK_DEPTH 64        // LDS traversal stack entries per lane of the binary-tree kernels (host SAH trees: depth <= 30; device LBVH trees: <= 63, checked)
+#define MCPT_STACK_DEPTH 64        // LDS traversal stack entries per lane of the binary-tree kernels (host SAH trees: depth <= 30; device-built trees: <= 63, checked)
 #endif
 #ifndef MCPT_BLOCK
 #define MCPT_BLOCK 256             // threads per workgroup = 4 waves of 64

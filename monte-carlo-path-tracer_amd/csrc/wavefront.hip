@@ -26,7 +26,6 @@
 typedef float wf_v4f __attribute__((ext_vector_type(4)));
 typedef unsigned int wf_v4u __attribute__((ext_vector_type(4)));
 typedef double wf_v2d __attribute__((ext_vector_type(2)));
-#ifndef MCPT_NO_NT
 __device__ __forceinline__ float4 ld_s(const float4* p) { const wf_v4f v = __builtin_nontemporal_load(reinterpret_cast<const wf_v4f*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ void st_s(float4* p, float4 v) { wf_v4f t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w; __builtin_nontemporal_store(t, reinterpret_cast<wf_v4f*>(p)); }
 __device__ __forceinline__ uint4 ld_s(const uint4* p) { const wf_v4u v = __builtin_nontemporal_load(reinterpret_cast<const wf_v4u*>(p)); return make_uint4(v.x, v.y, v.z, v.w); }
@@ -44,10 +43,6 @@ __device__ __forceinline__ uint2 ld_s(const uint2* p) { const wf_v2u v = __built
 __device__ __forceinline__ void st_s(uint2* p, uint2 v) { wf_v2u t; t.x = v.x; t.y = v.y; __builtin_nontemporal_store(t, reinterpret_cast<wf_v2u*>(p)); }
 __device__ __forceinline__ uint32_t ld_s(const uint32_t* p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ void st_s(uint32_t* p, uint32_t v) { __builtin_nontemporal_store(v, p); }
-#else
-template <class T> __device__ __forceinline__ T ld_s(const T* p) { return *p; }
-template <class T> __device__ __forceinline__ void st_s(T* p, T v) { *p = v; }
-#endif
 __device__ __forceinline__ f3 xyz(const float4 v) { return mk3(v.x, v.y, v.z); }
 __device__ __forceinline__ float4 mk4(f3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
 __device__ __forceinline__ f3 wf_scrub_nan(f3 c) {        // Scene::set_Pixel (Scene.cpp:16-18)
@@ -181,30 +176,20 @@ __global__ void __launch_bounds__(WF_SHADE_BLOCK, MCPT_SHADE_MIN_WAVES) wf_shade
             }
             key = ends ? K_EMIT : K_DIFF + ((uint32_t)tri0 >> HIT_CLASS_SHIFT);
         }
-#ifdef MCPT_SHADE_NOSORT                                                                           // A/B build: slot order, same code otherwise
-        const uint32_t skey = 0;
-#else
-        const uint32_t skey = key;
-#endif
         uint32_t my_rank = 0;
 #pragma unroll
         for (uint32_t k = 0; k < K_COUNT; k++) {
-            const uint64_t m = __ballot(skey == k);
-            if (skey == k) my_rank = lane_rank(m);
+            const uint64_t m = __ballot(key == k);
+            if (key == k) my_rank = lane_rank(m);
             if (lane == k) s_kcnt[k * (WF_SHADE_BLOCK / 64) + wv] = (uint32_t)__popcll(m);
         }
         __syncthreads();
-        // exclusive prefix of the slot's (key, wave) counter over the [key][wave] table, summed by every thread for itself (20 broadcast LDS
-        // reads) -- a serial scan by one thread between two barriers cost a barrier
-        const uint32_t my_cell = skey * (WF_SHADE_BLOCK / 64) + wv;
-#ifdef MCPT_SHADE_SERIAL_PREFIX      // A/B: every thread sums the table itself (20 broadcast reads, 60 VALU issues per wave)
-        uint32_t before_me = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < K_COUNT * (WF_SHADE_BLOCK / 64); i++) before_me += i < my_cell ? s_kcnt[i] : 0u;
-#else
-        // ... as a wave scan: lane i < 20 holds cell i, five DPP adds make the inclusive prefix over lanes 0..31 (row_shr 1/2/4/8 inside
-        // each row of 16 lanes, row_bcast:15 carries row 0's total into row 1), and every lane fetches the entry of its own cell with one
-        // ds_bpermute -- ~15 instead of ~60 VALU issues per wave, in a kernel half of whose issues are this prologue and the epilogue
+        // exclusive prefix of the slot's (key, wave) counter over the [key][wave] table, as a wave scan (a serial scan by one thread
+        // between two barriers cost a barrier; every thread summing the table itself cost ~60 VALU issues per wave): lane i < 20 holds
+        // cell i, five DPP adds make the inclusive prefix over lanes 0..31 (row_shr 1/2/4/8 inside each row of 16 lanes, row_bcast:15
+        // carries row 0's total into row 1), and every lane fetches the entry of its own cell with one ds_bpermute -- ~15 VALU issues per
+        // wave, in a kernel half of whose issues are this prologue and the epilogue
+        const uint32_t my_cell = key * (WF_SHADE_BLOCK / 64) + wv;
         static_assert(K_COUNT * (WF_SHADE_BLOCK / 64) <= 32, "the scan covers two DPP rows");
         const uint32_t cell_cnt = lane < K_COUNT * (WF_SHADE_BLOCK / 64) ? s_kcnt[lane] : 0u;
         int inc = (int)cell_cnt;
@@ -214,15 +199,10 @@ __global__ void __launch_bounds__(WF_SHADE_BLOCK, MCPT_SHADE_MIN_WAVES) wf_shade
         inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, true);      // row_shr:8
         inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);     // row_bcast:15 into rows 1 and 3 (other rows add the `old` operand, 0)
         const uint32_t before_me = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(my_cell << 2), inc - (int)cell_cnt);   // exclusive prefix of my cell
-#endif
         s_perm[(before_me + my_rank) & (WF_SHADE_BLOCK - 1u)] = tid | (key << 16);
         __syncthreads();
     }
-#ifdef MCPT_SHADE_PERM_TEST     // diagnostic: a class-blind interleave -- every wave touches every line of the window, no sorting benefit
-    const uint32_t pk = s_perm[((tid & 63u) << 2) | (tid >> 6)];
-#else
     const uint32_t pk = s_perm[tid];
-#endif
     const uint32_t key = pk >> 16, src = pk & 0xffffu, slot = base + src;
     SH_TICK(0)                                                                                    // tables + slot records + classification sort
 
@@ -700,11 +680,6 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK) wf_trace8_kernel(DevScene sc, 
     // One inner step in two halves: `issue` picks the next child of the group on top of the stack and requests its record, `consume` tests the
     // eight boxes and updates the stack.
     v4f R0, R1, R2, R3, R4;
-#if defined(WF_DUMMY_VMEM)
-    v4f DM[WF_DUMMY_VMEM];
-#elif defined(WF_DUMMY_LDS)
-    v4f DM[WF_DUMMY_LDS];
-#endif
     bool order_matters = true;
     uint32_t k64 = 0x64646464u; asm volatile("" : "+v"(k64));      // the fp16 exponent byte of WF8_CHILD's plane values, pinned in a VGPR (v_perm_b32 has one constant-bus operand: the selector)
     auto inner_issue = [&]() __attribute__((always_inline)) {
@@ -715,16 +690,6 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK) wf_trace8_kernel(DevScene sc, 
         cur_y &= cur_y - 1u;
         if (node < MCPT_TOP_NODES8) { R0 = top[node]; R1 = top[MCPT_TOP_NODES8 + node]; R2 = top[2 * MCPT_TOP_NODES8 + node]; R3 = top[3 * MCPT_TOP_NODES8 + node]; R4 = top[4 * MCPT_TOP_NODES8 + node]; }
         else { glb_cf4* n = (glb_cf4*)((const __attribute__((address_space(1))) char*)gnodes + node * 80u); R0 = n[0]; R1 = n[1]; R2 = n[2]; R3 = n[3]; R4 = n[4]; }   // (32-bit byte offset from a uniform base: saddr + voffset addressing)
-#ifdef WF_DUMMY_VMEM    /* regime probe: N extra 16-B gathers per inner step from the record just requested (L1 hits: pure vector-memory address work) */
-        { const volatile __attribute__((address_space(1))) v4f* n = (const volatile __attribute__((address_space(1))) v4f*)((const __attribute__((address_space(1))) char*)gnodes + node * 80u);
-#pragma unroll
-          for (int k = 0; k < WF_DUMMY_VMEM; k++) DM[k] = n[k % 5]; }
-#endif
-#ifdef WF_DUMMY_LDS     /* regime probe: N extra 16-B LDS reads per inner step */
-        { const volatile lds_f4* n = (const volatile lds_f4*)top;
-#pragma unroll
-          for (int k = 0; k < WF_DUMMY_LDS; k++) DM[k] = n[(k * MCPT_TOP_NODES8 + node) % (5 * MCPT_TOP_NODES8)]; }
-#endif
     };
     auto inner_consume = [&]() __attribute__((always_inline)) {
         const uint32_t sxy = __float_as_uint(R0.w), masks = __float_as_uint(R1.w);
@@ -765,21 +730,6 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK) wf_trace8_kernel(DevScene sc, 
         }
         if (t_park) { t_x = e_tn.x; t_y = tn_y; }
         WF8_PARK()
-#if defined(WF_DUMMY_VMEM) || defined(WF_DUMMY_LDS)    /* (the probes' results are only kept alive until here) */
-#pragma unroll
-        for (int k = 0; k < (int)(sizeof(DM) / sizeof(DM[0])); k++) asm volatile("" :: "v"(DM[k]));
-#endif
-#ifdef WF_DUMMY_VNOP    /* regime probe: N v_nop per inner step -- VALU issue slots without operands, registers or a dependence chain */
-        {
-#pragma unroll
-          for (int k = 0; k < WF_DUMMY_VNOP; k++) asm volatile("v_nop"); }
-#endif
-#ifdef WF_DUMMY_VALU    /* regime probe: N extra DEPENDENT v_fma_f32 per inner step (one chain: adds issue slots AND ~N x the FMA latency to the wave's critical path) */
-        { float dz = idx;
-#pragma unroll
-          for (int k = 0; k < WF_DUMMY_VALU; k++) asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(dz));
-          asm volatile("" :: "v"(dz)); }
-#endif
     };
 
     uint32_t watchdog = 0;

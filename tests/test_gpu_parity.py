@@ -229,7 +229,7 @@ def test_gpu_matches_reference_statistics_more_scenes(pkg, g2, tag):
 
 
 @pytest.mark.parametrize("tag", sorted(SCENES2))
-@pytest.mark.parametrize("tree", ["host-sah", "device-lbvh"])
+@pytest.mark.parametrize("tree", ["host-sah", "device-lbvh"])   # (the id predates PLOC: "device-lbvh" = the device-built tree)
 def test_probe_trace4_vs_reference_more_scenes(pkg, g2, tag, tree):
     """BVH::hit / has_hit of the REAL reference on 2 000 rays per scene through the production trace kernel."""
     name, kw, res = SCENES2[tag]
@@ -308,12 +308,12 @@ def _trace4_vs_reference(r, p):
     return t, tri, u, v, anyh
 
 
-@pytest.mark.parametrize("tree", ["host-sah", "device-lbvh"])
+@pytest.mark.parametrize("tree", ["host-sah", "device-lbvh"])   # (the id predates PLOC: "device-lbvh" = the device-built tree)
 @pytest.mark.parametrize("grid", [0, 1])
 def test_probe_trace4_hot_kernel_vs_reference(pkg, paths, tree, grid):
     """The PRODUCTION traversal (wf_trace8_kernel: 8-wide compressed nodes, LDS top levels, LDS + overflow group stack, chunked ray list)
     on the reference's own 4 000 rays: BVH::hit (same triangle, same t) and BVH::has_hit (same verdict with the reference's t2) on
-    >= 99.9 % of rays -- with the host SAH tree and the device-built LBVH, on the full persistent grid and on ONE block
+    >= 99.9 % of rays -- with the host SAH tree and the device-built tree, on the full persistent grid and on ONE block
     (MCPT_WF_GRID=1: every chunk of the ray list comes from the atomic cursor)."""
     if grid: os.environ["MCPT_WF_GRID"] = str(grid)
     try:
@@ -387,7 +387,7 @@ def _needle_forest(pkg, n_needles=6000, seed=5):
     return m.finish("needles", mats, pkg.scenes._qcam((2.0, 0.5, 4.0), (2.0, 0.5, 0.0), (0, 1, 0), 40.0, 16, 16))
 
 
-@pytest.mark.parametrize("tree", ["host-sah", "device-lbvh"])
+@pytest.mark.parametrize("tree", ["host-sah", "device-lbvh"])   # (the id predates PLOC: "device-lbvh" = the device-built tree)
 def test_probe_trace4_overflow_stack_and_random_rays(pkg, orc, tree):
     """Rays that push the per-lane group stack past its LDS levels (WF8_LDS_STACK = 8 since r04: the forest is 80 000 needles, an 8-level
     wide tree) into the global overflow area (counted by the kernel), compared with the binary-tree traversal on 200 000 rays and with

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool (GPU box): build time and render speed of the three tree builders (host binned SAH, device LBVH, device PLOC)."""
+"""Developer tool (GPU box): build time and render speed of the two tree builders (host binned SAH, device PLOC)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge
@@ -9,8 +9,7 @@ spp = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 if name == "cornell-box": scene, depth = pkg.scenes.cornell_box(800, 800), 8
 else:
     d = int(name.split(":")[1]); scene, depth = pkg.scenes.bathroom_stress(3840 if d >= 400 else 1920, 2160 if d >= 400 else 1080, detail=d), 16 if d >= 400 else 8
-for kind in ("host", "lbvh", "ploc"):
-    if kind != "host": os.environ["MCPT_GPU_BVH"] = kind
+for kind in ("host", "ploc"):
     t0 = time.time()
     r = pkg.Renderer(scene, max_depth=depth, flags=(pkg.FLAG_GPU_BVH_BUILD if kind != "host" else 0) | pkg.FLAG_COUNT_TRAVERSAL)
     t_create = time.time() - t0

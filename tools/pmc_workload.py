@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool (GPU box): ONE render of a BASELINE.json configuration, for rocprofv3 --pmc passes (tools/r02_profile.sh).
+"""Developer tool (GPU box): ONE render of a BASELINE.json configuration, for rocprofv3 --pmc passes (tools/r04_profile.sh).
 usage: python3 tools/pmc_workload.py <c2|c3|c4|c5> <spp> [out.json]   -- writes the ray / path / launch counts of exactly what ran"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
