@@ -168,6 +168,11 @@ mcpt_status mcpt_render(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t fir
  * "pixel-tile shard" of BASELINE.json's bathroom2 configuration -- the films of the G shares are disjoint and their sum (the same RCCL
  * all-reduce as for sample sharding) is the full image.  (1, 0) = mcpt_render. */
 mcpt_status mcpt_render_tiles(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample, uint32_t tile_mod, uint32_t tile_rem);
+/* The same for an arbitrary set of tiles: `tiles` holds n_tiles distinct tile numbers (row-major over ceil(w/8) x ceil(h/8), as for
+ * mcpt_render_tiles), in any order; every other pixel of the film is left untouched.  The list is validated before any device work (an
+ * index out of range, a duplicate, or a NULL list with n_tiles > 0: MCPT_ERR_INVALID_ARG) and copied to the device in stream order, so the
+ * caller may reuse it as soon as the call returns.  n_tiles = 0 does nothing.  Asynchronous on the context's stream. */
+mcpt_status mcpt_render_tile_list(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample, const uint32_t* tiles, uint32_t n_tiles);
 mcpt_status mcpt_sync(mcpt_ctx* ctx);
 
 /* Film = Scene::m_Pixels (Scene.h:7-12,25): width*height records {r_sum, g_sum, b_sum, spp}, index y*width+x,
@@ -207,6 +212,40 @@ mcpt_status mcpt_read_features(mcpt_ctx* ctx, float* out8);                     
 mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_denoise_opts* opts);  /* NULL film = ctx film; NULL opts = defaults; asynchronous */
 mcpt_status mcpt_read_denoised(mcpt_ctx* ctx, float* rgba_host);                       /* synchronises, then D2H: width*height*4 floats */
 mcpt_status mcpt_denoised_device_ptr(mcpt_ctx* ctx, void** out_device_rgba);           /* the denoised film on the device (after a first mcpt_denoise) */
+
+/* ---- adaptive sampling ------------------------------------------------------------------------------------------- */
+/* Samples go where the image is still noisy, per 8x8 tile.  During a call the samples go into two internal half films H and O (the first and
+ * the second half of every pass's sample range).  Per in-image pixel e_p = sum over rgb of |sqrt(clamp(H/nH, 0, 1)) - sqrt(clamp(O/nO, 0, 1))|
+ * -- how different the two halves look after mcpt_tonemap -- and per tile E_t = max e_p, c_t = nH + nO.  A tile is active while
+ * E_t >= threshold && c_t < max_spp.  Pass 0 gives every tile min_spp samples; each later pass doubles the active tiles' count (the last one
+ * stops at max_spp).  At the end H + O is added to the bound film, whatever it held before.  Every tile t ends with samples
+ * first_sample .. first_sample + N_t - 1, N_t in {min_spp * 2^k} and {max_spp}: the same image as mcpt_render_tile_list of N_t samples, up to
+ * fp32 summation order.  One small read-back and one synchronisation per pass; the call returns when the merge has been enqueued.
+ * The counters account the call's rays and paths as usual; it counts as ONE launch, and its kernel_ms is the device time from its first to
+ * its last operation, the per-pass host round trips included. */
+typedef struct mcpt_adaptive_opts {
+    uint32_t struct_size;   /* = sizeof(mcpt_adaptive_opts) */
+    uint32_t min_spp;       /* samples every tile gets in pass 0; even, >= 2; 0 = default 16 */
+    uint32_t max_spp;       /* cap per tile, >= min_spp; 0 = default 1024 */
+    float    threshold;     /* finite, > 0; 0 = default (MCPT_ADAPTIVE_DEFAULT_THRESHOLD) */
+    uint32_t reserved[4];
+} mcpt_adaptive_opts;
+typedef struct mcpt_adaptive_stats {
+    uint32_t struct_size, passes;           /* passes: render passes, pass 0 included */
+    uint64_t pixel_samples;                 /* samples added to in-image pixels by this call */
+    uint32_t tiles_converged, tiles_capped; /* E_t < threshold / E_t >= threshold at max_spp */
+    uint32_t reserved[4];
+} mcpt_adaptive_stats;
+#define MCPT_ADAPTIVE_DEFAULT_THRESHOLD 0.25f
+/* opts NULL = all defaults; out_stats may be NULL.  Invalid options return MCPT_ERR_INVALID_ARG before any device work, as does
+ * first_sample + max_spp > 2^32. */
+mcpt_status mcpt_render_adaptive(mcpt_ctx* ctx, uint64_t seed, uint32_t first_sample, const mcpt_adaptive_opts* opts, mcpt_adaptive_stats* out_stats);
+/* Synchronises, then D2H: tiles_y * tiles_x floats, E_t of the last pass of the last mcpt_render_adaptive call. */
+mcpt_status mcpt_read_tile_error(mcpt_ctx* ctx, float* out);
+/* The error and compaction kernels on caller films of this context's size (width * height {sum rgb, count} each): out_err gets E_t of every
+ * tile, out_list (room for tiles_y * tiles_x entries) the active tiles in ascending order, *out_n their number.  Synchronous. */
+mcpt_status mcpt_probe_tile_error(mcpt_ctx* ctx, const float* h_rgba_host, const float* o_rgba_host, float threshold, uint32_t max_spp,
+                                  float* out_err, uint32_t* out_list, uint32_t* out_n);
 
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that

@@ -91,6 +91,19 @@ class DenoiseOpts(C.Structure):
                 ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 3)]
 
 
+class AdaptiveOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class AdaptiveStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("passes", C.c_uint32), ("pixel_samples", C.c_uint64),
+                ("tiles_converged", C.c_uint32), ("tiles_capped", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 def texture_to_float(img_u8: np.ndarray) -> np.ndarray:
     """What stbi_loadf gives the reference for an 8-bit image (model.cpp:8-23; stb_image.h:1553,1849):
     (c/255)^2.2 per channel, row 0 = first row of the file."""
@@ -194,6 +207,10 @@ def load_library() -> C.CDLL:
         "mcpt_denoise": [vp, vp, P(DenoiseOpts)],
         "mcpt_read_denoised": [vp, vp],
         "mcpt_denoised_device_ptr": [vp, P(vp)],
+        "mcpt_render_tile_list": [vp, C.c_uint32, C.c_uint64, C.c_uint32, vp, C.c_uint32],
+        "mcpt_render_adaptive": [vp, C.c_uint64, C.c_uint32, P(AdaptiveOpts), P(AdaptiveStats)],
+        "mcpt_read_tile_error": [vp, vp],
+        "mcpt_probe_tile_error": [vp, vp, vp, C.c_float, C.c_uint32, vp, vp, P(C.c_uint32)],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -214,6 +231,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_null_stream", "mcpt_probe_trace", "mcpt_probe_trace4", "mcpt_probe_cast_ray", "mcpt_probe_hit_shade", "mcpt_probe_bsdf", "mcpt_probe_sample_light",
     "mcpt_probe_paths", "mcpt_probe_rng", "mcpt_probe_texture",
     "mcpt_render_features", "mcpt_read_features", "mcpt_denoise", "mcpt_read_denoised", "mcpt_denoised_device_ptr",
+    "mcpt_render_tile_list", "mcpt_render_adaptive", "mcpt_read_tile_error", "mcpt_probe_tile_error",
 ]
 
 
@@ -278,6 +296,40 @@ class Renderer:
     def render_tiles(self, spp: int, seed: int, first_sample: int, tile_mod: int, tile_rem: int):
         """One interleaved share of the image: the 8x8 tiles t with t % tile_mod == tile_rem."""
         self._check(self.lib.mcpt_render_tiles(self.ctx, spp, seed, first_sample, tile_mod, tile_rem))
+
+    def render_tile_list(self, spp: int, seed: int, first_sample: int, tiles):
+        """The 8x8 tiles in `tiles` (row-major tile numbers, distinct, any order) only."""
+        t = np.ascontiguousarray(tiles, np.uint32).reshape(-1)
+        self._check(self.lib.mcpt_render_tile_list(self.ctx, spp, seed, first_sample, _ptr(t), t.size))
+
+    @property
+    def tiles_shape(self):
+        return (self.height + 7) // 8, (self.width + 7) // 8
+
+    def render_adaptive(self, seed: int = 0, first_sample: int = 0, min_spp: int = 0, max_spp: int = 0, threshold: float = 0.0) -> AdaptiveStats:
+        """Adaptive sampling per 8x8 tile; 0 = the default of each option.  Adds to the film."""
+        o = AdaptiveOpts()
+        o.struct_size = C.sizeof(AdaptiveOpts); o.min_spp = min_spp; o.max_spp = max_spp; o.threshold = threshold
+        st = AdaptiveStats()
+        st.struct_size = C.sizeof(AdaptiveStats)
+        self._check(self.lib.mcpt_render_adaptive(self.ctx, seed, first_sample, C.byref(o), C.byref(st)))
+        return st
+
+    def tile_error(self) -> np.ndarray:
+        """(tiles_y, tiles_x) E_t of the last pass of the last render_adaptive call."""
+        out = np.zeros(self.tiles_shape, np.float32)
+        self._check(self.lib.mcpt_read_tile_error(self.ctx, _ptr(out)))
+        return out
+
+    def probe_tile_error(self, h: np.ndarray, o: np.ndarray, threshold: float, max_spp: int):
+        """The error + compaction kernels on two caller films: ((tiles_y, tiles_x) E_t, active tile list in ascending order)."""
+        a = np.ascontiguousarray(h, np.float32); b = np.ascontiguousarray(o, np.float32)
+        assert a.size == b.size == self.width * self.height * 4
+        err = np.zeros(self.tiles_shape, np.float32)
+        lst = np.zeros(err.size, np.uint32)
+        n = C.c_uint32(0)
+        self._check(self.lib.mcpt_probe_tile_error(self.ctx, _ptr(a), _ptr(b), threshold, max_spp, _ptr(err), _ptr(lst), C.byref(n)))
+        return err, lst[:n.value].copy()
 
     def sync(self):
         self._check(self.lib.mcpt_sync(self.ctx))

@@ -137,6 +137,10 @@ struct RenderParams {
     // {m, s} with x / d == (uint64(x) * m) >> s for every x < 2^30 (Granlund & Montgomery 1994: m = floor(2^(30 + L) / d) + 1, s = 30 + L,
     // L = ceil(log2 d); m < 2^32).  The compiler's general 32-bit division is ~20 VALU instructions, and every shade wave runs all three.
     uint32_t div_owned_m, div_owned_s, div_tiles_x_m, div_tiles_x_s, div_width_m, div_width_s;
+    // mcpt_render_tile_list: the call's tile sequence is this device list (j-th tile = tile_list[j]) instead of the tile numbers themselves;
+    // tile_mod / tile_rem / n_owned then index the LIST (j = tile_rem + k * tile_mod).  Null = the identity: every other caller.  (Last member:
+    // the offsets of the fields above, which the hot kernels read, do not move.)
+    const uint32_t* tile_list;
 };
 #define MCPT_FASTDIV_MAX (1u << 30)   // exclusive bound on the dividends (work-item units, tiles, pixels: mcpt_create refuses larger films)
 

@@ -63,7 +63,8 @@ __global__ void __launch_bounds__(MCPT_BLOCK, MCPT_MIN_WAVES) render_mis_kernel(
     const uint32_t wave = lb * (MCPT_BLOCK / 64) + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n_tiles = p.n_owned;
-    const uint32_t chunk = PROBE ? 0u : wave / n_tiles, tile = p.tile_rem + (wave - chunk * n_tiles) * p.tile_mod;
+    const uint32_t chunk = PROBE ? 0u : wave / n_tiles, j = p.tile_rem + (wave - chunk * n_tiles) * p.tile_mod;
+    const uint32_t tile = (!PROBE && p.tile_list) ? p.tile_list[j] : j;                    // mcpt_render_tile_list: j indexes the call's list
     const int px = (int)((tile % p.tiles_x) * 8 + (lane & 7)), py = (int)((tile / p.tiles_x) * 8 + (lane >> 3));
     const bool valid = PROBE ? (wave * 64 + lane < probe_n) : (chunk < p.chunks && px < sc.cam.width && py < sc.cam.height);
     const uint32_t pixel = PROBE ? (wave * 64 + lane) : (uint32_t)(py * sc.cam.width + px);
@@ -205,7 +206,8 @@ __global__ void __launch_bounds__(MCPT_BLOCK, MCPT_MIN_WAVES) render_recursive_k
     const uint32_t wave = lb * (MCPT_BLOCK / 64) + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n_tiles = p.n_owned;
-    const uint32_t chunk = wave / n_tiles, tile = p.tile_rem + (wave - chunk * n_tiles) * p.tile_mod;
+    const uint32_t chunk = wave / n_tiles, j = p.tile_rem + (wave - chunk * n_tiles) * p.tile_mod;
+    const uint32_t tile = p.tile_list ? p.tile_list[j] : j;                                  // mcpt_render_tile_list: j indexes the call's list
     const int px = (int)((tile % p.tiles_x) * 8 + (lane & 7)), py = (int)((tile / p.tiles_x) * 8 + (lane >> 3));
     const bool valid = chunk < p.chunks && px < sc.cam.width && py < sc.cam.height;
     const uint32_t pixel = (uint32_t)(py * sc.cam.width + px);

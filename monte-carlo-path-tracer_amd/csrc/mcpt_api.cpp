@@ -6,8 +6,10 @@
 #include "bvh_gpu.h"
 #include "wavefront.h"
 #include "denoise.h"
+#include "adaptive.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -85,6 +87,14 @@ struct mcpt_ctx {
     // two ping-pong {irr, var} buffers and the denoised film (1 float4 / pixel each), allocated by the first mcpt_denoise
     DevBuf dn_feat, dn_guide, dn_iv0, dn_iv1, dn_out;
     bool dn_have_features = false, dn_have_out = false;
+    // mcpt_render_tile_list: the caller's list, staged in pinned memory and copied to the device in stream order (tl_ev: that copy has been made,
+    // the staging buffer may be written again); both grow to the longest list seen
+    DevBuf tl_dev; uint32_t* tl_host = nullptr; size_t tl_cap = 0; hipEvent_t tl_ev = nullptr; bool tl_pending = false;
+    // Adaptive sampling (adaptive.hip), allocated by the first mcpt_render_adaptive: the half films H and O (1 float4 / pixel each), per tile
+    // E_t, the active list and its flags, per error block counts and offsets, the totals and their pinned read-back
+    DevBuf ad_h, ad_o, ad_err, ad_list, ad_flags, ad_counts, ad_offs, ad_tot;
+    AdTotals* ad_host = nullptr;
+    bool ad_have_err = false;
 };
 
 namespace {
@@ -117,6 +127,9 @@ void destroy_ctx(mcpt_ctx* c) {
     }
     c->tone_dev.free_(); if (c->tone_host) (void)hipHostFree(c->tone_host);
     c->dn_feat.free_(); c->dn_guide.free_(); c->dn_iv0.free_(); c->dn_iv1.free_(); c->dn_out.free_();
+    c->tl_dev.free_(); if (c->tl_host) (void)hipHostFree(c->tl_host); if (c->tl_ev) (void)hipEventDestroy(c->tl_ev);
+    for (DevBuf* b : {&c->ad_h, &c->ad_o, &c->ad_err, &c->ad_list, &c->ad_flags, &c->ad_counts, &c->ad_offs, &c->ad_tot}) b->free_();
+    if (c->ad_host) (void)hipHostFree(c->ad_host);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     for (uint32_t i = 0; i < mcpt_ctx::TIMED; i++) { if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]); if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -663,19 +676,22 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, RenderParams& p0, float4* acc
 
 mcpt_status mcpt_render(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample) { return mcpt_render_tiles(ctx, spp, seed, first_sample, 1u, 0u); }
 
-mcpt_status mcpt_render_tiles(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample, uint32_t tile_mod, uint32_t tile_rem) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (tile_mod == 0 || tile_rem >= tile_mod) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_tiles: need tile_rem < tile_mod");
+// One render call: `spp` samples of the tiles (tile_mod, tile_rem) selects -- of the tile numbers themselves, or, with a device list `list` of
+// n_list entries, of the list -- into `accum`.  `timed`: bracket it with an event pair and count it as a launch (what every entry point does;
+// mcpt_render_adaptive brackets its passes as one call instead).
+static mcpt_status render_call(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample, uint32_t tile_mod, uint32_t tile_rem,
+                               const uint32_t* list, uint32_t n_list, float4* accum, bool timed) {
     if (spp == 0) return MCPT_OK;
     if (!ctx->use_wavefront && !ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the megakernel's traversal stack");
+    mcpt_status st;
     // durations of earlier calls: read what has finished; wait only when the ring of event pairs is full -- or when per-kernel timing is on,
     // whose sampled kernel events belong to one call at a time
-    st = resolve_timing(ctx, ctx->time_kernels != 0 || ctx->timed_head - ctx->timed_tail >= mcpt_ctx::TIMED - 1); if (st != MCPT_OK) return st;
+    if (timed) { st = resolve_timing(ctx, ctx->time_kernels != 0 || ctx->timed_head - ctx->timed_tail >= mcpt_ctx::TIMED - 1); if (st != MCPT_OK) return st; }
     RenderParams p; std::memset(&p, 0, sizeof p);
     p.spp = spp; p.first_sample = first_sample;
     p.tiles_x = uint32_t((ctx->width + 7) / 8); p.tiles_y = uint32_t((ctx->height + 7) / 8);
-    p.tile_mod = tile_mod; p.tile_rem = tile_rem;
-    {   const uint64_t all = uint64_t(p.tiles_x) * p.tiles_y;
+    p.tile_mod = tile_mod; p.tile_rem = tile_rem; p.tile_list = list;
+    {   const uint64_t all = list ? uint64_t(n_list) : uint64_t(p.tiles_x) * p.tiles_y;
         p.n_owned = all > tile_rem ? uint32_t((all - tile_rem + tile_mod - 1) / tile_mod) : 0u; }
     if (p.n_owned == 0) return MCPT_OK;                                   // more shards than tiles: nothing for this one
     const uint64_t tiles = p.n_owned;
@@ -706,15 +722,50 @@ mcpt_status mcpt_render_tiles(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32
     p.seed_lo = uint32_t(seed); p.seed_hi = uint32_t(seed >> 32);
     if (tiles * p.chunks > 0x3ffffffull) return fail(MCPT_ERR_UNSUPPORTED, "launch too large: lower spp per call or raise samples_per_item");
     const uint32_t tk = ctx->timed_head % mcpt_ctx::TIMED;
-    HIP_TRY(hipEventRecord(ctx->ev0[tk], ctx->stream));
+    if (timed) HIP_TRY(hipEventRecord(ctx->ev0[tk], ctx->stream));
     if (ctx->use_wavefront) {
-        st = render_wavefront(ctx, p, ctx->accum); if (st != MCPT_OK) return st;
+        st = render_wavefront(ctx, p, accum); if (st != MCPT_OK) return st;
     } else {
-        HIP_TRY(launch_render(ctx->dev, p, ctx->accum, static_cast<DevCounters*>(ctx->counters.p), ctx->stream));
+        HIP_TRY(launch_render(ctx->dev, p, accum, static_cast<DevCounters*>(ctx->counters.p), ctx->stream));
     }
-    HIP_TRY(hipEventRecord(ctx->ev1[tk], ctx->stream));
-    ctx->timed_head++; ctx->launches++;
+    if (timed) { HIP_TRY(hipEventRecord(ctx->ev1[tk], ctx->stream)); ctx->timed_head++; ctx->launches++; }
     return MCPT_OK;
+}
+
+mcpt_status mcpt_render_tiles(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample, uint32_t tile_mod, uint32_t tile_rem) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (tile_mod == 0 || tile_rem >= tile_mod) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_tiles: need tile_rem < tile_mod");
+    return render_call(ctx, spp, seed, first_sample, tile_mod, tile_rem, nullptr, 0u, ctx->accum, true);
+}
+
+mcpt_status mcpt_render_tile_list(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample, const uint32_t* tiles, uint32_t n_tiles) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (n_tiles == 0) return MCPT_OK;
+    if (!tiles) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_tile_list: null list");
+    // one-sample items write the film with a plain read-modify-write (RenderParams::atomic_accum = 0): a tile listed twice would race with itself
+    const uint64_t all = uint64_t((ctx->width + 7) / 8) * uint64_t((ctx->height + 7) / 8);
+    if (n_tiles > all) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_tile_list: more tiles than the image has (a duplicate)");
+    std::vector<uint8_t> seen(all, 0);
+    for (uint32_t i = 0; i < n_tiles; i++) {
+        if (tiles[i] >= all) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_tile_list: tile " + std::to_string(tiles[i]) + " out of range");
+        if (seen[tiles[i]]++) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_tile_list: tile " + std::to_string(tiles[i]) + " listed twice");
+    }
+    if (spp == 0) return MCPT_OK;
+    if (ctx->tl_pending) { HIP_TRY(hipEventSynchronize(ctx->tl_ev)); ctx->tl_pending = false; }   // the staging buffer's last copy has been made
+    if (ctx->tl_cap < n_tiles) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));                        // (kernels of earlier calls may still read the device list)
+        ctx->info.device_bytes -= ctx->tl_dev.bytes; ctx->tl_dev.free_();
+        if (ctx->tl_host) { (void)hipHostFree(ctx->tl_host); ctx->tl_host = nullptr; }
+        ctx->tl_cap = 0;
+        HIP_TRY(ctx->tl_dev.alloc(size_t(n_tiles) * sizeof(uint32_t)));
+        HIP_TRY(hipHostMalloc((void**)&ctx->tl_host, size_t(n_tiles) * sizeof(uint32_t), hipHostMallocDefault));
+        ctx->info.device_bytes += ctx->tl_dev.bytes; ctx->tl_cap = n_tiles;
+        if (!ctx->tl_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tl_ev, hipEventDisableTiming));
+    }
+    std::memcpy(ctx->tl_host, tiles, size_t(n_tiles) * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(ctx->tl_dev.p, ctx->tl_host, size_t(n_tiles) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->tl_ev, ctx->stream)); ctx->tl_pending = true;
+    return render_call(ctx, spp, seed, first_sample, 1u, 0u, static_cast<const uint32_t*>(ctx->tl_dev.p), n_tiles, ctx->accum, true);
 }
 
 mcpt_status mcpt_sync(mcpt_ctx* ctx) {
@@ -913,6 +964,120 @@ mcpt_status mcpt_denoised_device_ptr(mcpt_ctx* ctx, void** out_device_rgba) {
     *out_device_rgba = nullptr;
     if (!ctx->dn_have_out) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoised_device_ptr: nothing denoised yet (mcpt_denoise)");
     *out_device_rgba = ctx->dn_out.p;
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ adaptive sampling
+// Device buffers of the error + compaction round, allocated on first use and counted in device_bytes (the half films are what costs: 32 B per pixel).
+static mcpt_status ad_ensure(mcpt_ctx* ctx) {
+    if (ctx->ad_h.p) return MCPT_OK;
+    const size_t n = size_t(ctx->width) * ctx->height;
+    const uint32_t n_tiles = uint32_t(((ctx->width + 7) / 8) * ((ctx->height + 7) / 8)), nb = ad_blocks(n_tiles);
+    const size_t bytes[8] = {n * sizeof(float4), n * sizeof(float4), n_tiles * sizeof(float), n_tiles * sizeof(uint32_t), n_tiles * sizeof(uint32_t),
+                             nb * sizeof(uint4), nb * sizeof(uint32_t), sizeof(AdTotals)};
+    DevBuf* bufs[8] = {&ctx->ad_h, &ctx->ad_o, &ctx->ad_err, &ctx->ad_list, &ctx->ad_flags, &ctx->ad_counts, &ctx->ad_offs, &ctx->ad_tot};
+    for (int i = 0; i < 8; i++) {
+        const hipError_t e = bufs[i]->alloc(bytes[i]);
+        if (e != hipSuccess) { for (DevBuf* b : bufs) b->free_(); return hip_fail(e, "alloc adaptive buffers"); }
+    }
+    HIP_TRY(hipHostMalloc((void**)&ctx->ad_host, sizeof(AdTotals), hipHostMallocDefault));
+    for (DevBuf* b : bufs) ctx->info.device_bytes += b->bytes;
+    return MCPT_OK;
+}
+static AdScratch ad_scratch(mcpt_ctx* ctx) {
+    AdScratch s;
+    s.block_counts = static_cast<uint4*>(ctx->ad_counts.p); s.block_offsets = static_cast<uint32_t*>(ctx->ad_offs.p);
+    s.flags = static_cast<uint32_t*>(ctx->ad_flags.p); s.totals = static_cast<AdTotals*>(ctx->ad_tot.p);
+    return s;
+}
+
+mcpt_status mcpt_render_adaptive(mcpt_ctx* ctx, uint64_t seed, uint32_t first_sample, const mcpt_adaptive_opts* opts, mcpt_adaptive_stats* out_stats) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    mcpt_adaptive_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o;
+    if (opts) {
+        if (opts->struct_size != sizeof(mcpt_adaptive_opts)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_adaptive: opts->struct_size != sizeof(mcpt_adaptive_opts)");
+        o = *opts;
+    }
+    const uint32_t min_spp = o.min_spp ? o.min_spp : 16u, max_spp = o.max_spp ? o.max_spp : 1024u;
+    if (min_spp < 2 || (min_spp & 1u)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_adaptive: min_spp must be even and >= 2");
+    if (max_spp < min_spp) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_adaptive: max_spp < min_spp");
+    if (!std::isfinite(o.threshold) || o.threshold < 0.f) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_adaptive: threshold must be finite and > 0 (0 = default)");
+    if (uint64_t(first_sample) + max_spp > 0x100000000ull) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_adaptive: first_sample + max_spp overflows the sample index");
+    const float thr = o.threshold > 0.f ? o.threshold : MCPT_ADAPTIVE_DEFAULT_THRESHOLD;
+    if (!ctx->use_wavefront && !ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the megakernel's traversal stack");
+    st = ad_ensure(ctx); if (st != MCPT_OK) return st;
+    st = resolve_timing(ctx, ctx->time_kernels != 0 || ctx->timed_head - ctx->timed_tail >= mcpt_ctx::TIMED - 1); if (st != MCPT_OK) return st;
+    const size_t n_px = size_t(ctx->width) * ctx->height;
+    const uint32_t n_tiles = uint32_t(((ctx->width + 7) / 8) * ((ctx->height + 7) / 8));
+    float4* H = static_cast<float4*>(ctx->ad_h.p); float4* O = static_cast<float4*>(ctx->ad_o.p);
+    const uint32_t* list = static_cast<const uint32_t*>(ctx->ad_list.p);
+    const AdScratch scr = ad_scratch(ctx);
+    mcpt_adaptive_stats stats; std::memset(&stats, 0, sizeof stats); stats.struct_size = sizeof stats;
+    const uint32_t tk = ctx->timed_head % mcpt_ctx::TIMED;
+    HIP_TRY(hipEventRecord(ctx->ev0[tk], ctx->stream));
+    HIP_TRY(hipMemsetAsync(H, 0, n_px * sizeof(float4), ctx->stream));
+    HIP_TRY(hipMemsetAsync(O, 0, n_px * sizeof(float4), ctx->stream));
+    ctx->ad_have_err = false;
+    // pass 0: every tile, samples [fs, fs + min/2) into H and [fs + min/2, fs + min) into O
+    const uint32_t half = min_spp / 2;
+    st = render_call(ctx, half, seed, first_sample, 1u, 0u, nullptr, 0u, H, false); if (st != MCPT_OK) return st;
+    st = render_call(ctx, half, seed, first_sample + half, 1u, 0u, nullptr, 0u, O, false); if (st != MCPT_OK) return st;
+    stats.passes = 1; stats.pixel_samples = uint64_t(min_spp) * n_px;
+    uint32_t c = min_spp;                                                  // the count every active tile has
+    for (;;) {
+        HIP_TRY(launch_ad_error_compact(H, O, ctx->width, ctx->height, thr, max_spp, static_cast<float*>(ctx->ad_err.p), static_cast<uint32_t*>(ctx->ad_list.p), scr, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->ad_host, ctx->ad_tot.p, sizeof(AdTotals), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        ctx->ad_have_err = true;
+        const AdTotals t = *ctx->ad_host;
+        if (t.n_active == 0 || c >= max_spp) {                            // (c < max_spp for every active tile: the second test is a guard)
+            stats.tiles_capped = t.n_hot; stats.tiles_converged = n_tiles - t.n_hot;
+            break;
+        }
+        // the next pass doubles the active tiles' count, or brings it to max_spp: n samples [fs + c, fs + c + n), the first floor(n/2) into H
+        const uint32_t n = std::min(c, max_spp - c), nh = n / 2;
+        st = render_call(ctx, nh, seed, first_sample + c, 1u, 0u, list, t.n_active, H, false); if (st != MCPT_OK) return st;
+        st = render_call(ctx, n - nh, seed, first_sample + c + nh, 1u, 0u, list, t.n_active, O, false); if (st != MCPT_OK) return st;
+        stats.passes++; stats.pixel_samples += uint64_t(n) * t.active_pixels;
+        c += n;
+    }
+    HIP_TRY(launch_ad_merge(ctx->accum, H, O, uint32_t(n_px), ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev1[tk], ctx->stream));
+    ctx->timed_head++; ctx->launches++;
+    if (out_stats) *out_stats = stats;
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_read_tile_error(mcpt_ctx* ctx, float* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    if (!ctx->ad_have_err) return fail(MCPT_ERR_INVALID_ARG, "mcpt_read_tile_error: no adaptive render yet (mcpt_render_adaptive)");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(out, ctx->ad_err.p, ctx->ad_err.bytes, hipMemcpyDeviceToHost));
+    return resolve_timing(ctx);
+}
+
+mcpt_status mcpt_probe_tile_error(mcpt_ctx* ctx, const float* h_rgba_host, const float* o_rgba_host, float threshold, uint32_t max_spp,
+                                  float* out_err, uint32_t* out_list, uint32_t* out_n) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!h_rgba_host || !o_rgba_host || !out_err || !out_list || !out_n) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    if (!std::isfinite(threshold) || threshold < 0.f) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_tile_error: threshold must be finite and >= 0");
+    const size_t n_px = size_t(ctx->width) * ctx->height;
+    const uint32_t n_tiles = uint32_t(((ctx->width + 7) / 8) * ((ctx->height + 7) / 8)), nb = ad_blocks(n_tiles);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    Scratch s; float4 *h, *o; float* err; uint32_t *list, *flags, *offs; uint4* counts; AdTotals* tot;
+    HIP_TRY(s.in(reinterpret_cast<const float4*>(h_rgba_host), n_px, &h)); HIP_TRY(s.in(reinterpret_cast<const float4*>(o_rgba_host), n_px, &o));
+    HIP_TRY(s.out(n_tiles, &err)); HIP_TRY(s.out(n_tiles, &list)); HIP_TRY(s.out(n_tiles, &flags));
+    HIP_TRY(s.out(nb, &offs)); HIP_TRY(s.out(nb, &counts)); HIP_TRY(s.out(1, &tot));
+    AdScratch scr; scr.block_counts = counts; scr.block_offsets = offs; scr.flags = flags; scr.totals = tot;
+    HIP_TRY(launch_ad_error_compact(h, o, ctx->width, ctx->height, threshold, max_spp, err, list, scr, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    AdTotals t;
+    HIP_TRY(hipMemcpy(&t, tot, sizeof t, hipMemcpyDeviceToHost));
+    if (t.n_active > n_tiles) return fail(MCPT_ERR_HIP, "mcpt_probe_tile_error: active count out of range (internal error)");
+    HIP_TRY(hipMemcpy(out_err, err, n_tiles * sizeof(float), hipMemcpyDeviceToHost));
+    if (t.n_active) HIP_TRY(hipMemcpy(out_list, list, t.n_active * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *out_n = t.n_active;
     return MCPT_OK;
 }
 

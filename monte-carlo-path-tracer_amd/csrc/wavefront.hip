@@ -98,7 +98,9 @@ __device__ __forceinline__ int wf_sel(uint64_t mask, int if_set, int if_clear) {
 #define K_COUNT 5u
 // x / d by multiply + shift (RenderParams::div_*): exact for x < MCPT_FASTDIV_MAX
 __device__ __forceinline__ uint32_t wf_fastdiv(uint32_t x, uint32_t m, uint32_t s) { return (uint32_t)(((unsigned long long)x * m) >> s); }
-template <bool COUNT>
+// LIST: the call's tiles come from p.tile_list (mcpt_render_tile_list).  A variant of its own, so that the list pointer and its load cost the
+// kernel every other call launches nothing (shade-kernel registers are the currency).
+template <bool COUNT, bool LIST>
 __global__ void __launch_bounds__(WF_SHADE_BLOCK, MCPT_SHADE_MIN_WAVES) wf_shade_kernel(DevScene sc, RenderParams p, PathPool pool, IterCtl* ctl, uint32_t it, uint32_t n_items,
                                                               float4* __restrict__ accum, DevCounters* gcnt) {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // wave index: scalar
@@ -428,7 +430,8 @@ __global__ void __launch_bounds__(WF_SHADE_BLOCK, MCPT_SHADE_MIN_WAVES) wf_shade
                 } else if (mine || shared_item < n_items) {
                     const uint32_t n_tiles = p.n_owned;
                     const uint32_t iw = item >> 6, il = item & 63u;
-                    const uint32_t chunk = wf_fastdiv(iw, p.div_owned_m, p.div_owned_s), tile = p.tile_rem + (iw - chunk * n_tiles) * p.tile_mod;   // iw / n_tiles
+                    const uint32_t chunk = wf_fastdiv(iw, p.div_owned_m, p.div_owned_s), j = p.tile_rem + (iw - chunk * n_tiles) * p.tile_mod;      // iw / n_tiles
+                    const uint32_t tile = LIST ? p.tile_list[j] : j;                                                                          // (LIST: mcpt_render_tile_list only)
                     const uint32_t ty = wf_fastdiv(tile, p.div_tiles_x_m, p.div_tiles_x_s);                                                    // tile / tiles_x
                     const uint32_t px = (tile - ty * p.tiles_x) * 8 + (il & 7), py = ty * 8 + (il >> 3);
                     if (px < (uint32_t)sc.cam.width && py < (uint32_t)sc.cam.height) {
@@ -1054,8 +1057,12 @@ hipError_t launch_wf_shade(const DevScene& sc, const RenderParams& p, const Path
     wf_make_fastdiv(p.n_owned, q.div_owned_m, q.div_owned_s);
     wf_make_fastdiv(p.tiles_x, q.div_tiles_x_m, q.div_tiles_x_s);
     wf_make_fastdiv((uint32_t)sc.cam.width, q.div_width_m, q.div_width_s);
-    if (p.flags & MCPT_FLAG_COUNT_TRAVERSAL) hipLaunchKernelGGL(wf_shade_kernel<true>, grid, block, 0, stream, sc, q, pool, ctl, iteration, n_items, accum, cnt);
-    else hipLaunchKernelGGL(wf_shade_kernel<false>, grid, block, 0, stream, sc, q, pool, ctl, iteration, n_items, accum, cnt);
+    const bool count = (p.flags & MCPT_FLAG_COUNT_TRAVERSAL) != 0;
+    if (p.tile_list) {
+        if (count) hipLaunchKernelGGL((wf_shade_kernel<true, true>), grid, block, 0, stream, sc, q, pool, ctl, iteration, n_items, accum, cnt);
+        else hipLaunchKernelGGL((wf_shade_kernel<false, true>), grid, block, 0, stream, sc, q, pool, ctl, iteration, n_items, accum, cnt);
+    } else if (count) hipLaunchKernelGGL((wf_shade_kernel<true, false>), grid, block, 0, stream, sc, q, pool, ctl, iteration, n_items, accum, cnt);
+    else hipLaunchKernelGGL((wf_shade_kernel<false, false>), grid, block, 0, stream, sc, q, pool, ctl, iteration, n_items, accum, cnt);
     return hipGetLastError();
 }
 hipError_t launch_wf_trace(const DevScene& sc, const PathPool& pool, IterCtl* ctl, uint32_t iteration, const WaveTuning& tune, bool count,

@@ -1,5 +1,6 @@
 #include "Render.h"
 
+#include <algorithm>
 #include <cstring>
 #include <iostream>
 
@@ -59,6 +60,26 @@ void Render::render(Scene& scene, uint32_t spp) {
     scene.attach(this);                               // (flushes whichever other Render held samples for `scene`)
     if (mcpt_render(ctx, spp, seed, next_sample) != MCPT_OK) { std::cerr << "Error: mcpt_render: " << mcpt_last_error() << std::endl; return; }
     next_sample += spp; dirty = true;
+}
+mcpt_adaptive_stats Render::render_adaptive(Scene& scene, const mcpt_adaptive_opts* opts) {
+    mcpt_adaptive_stats st; std::memset(&st, 0, sizeof st); st.struct_size = sizeof st;
+    if (!ctx) return st;
+    if (scene.width() * scene.height() * 4 != int(film.size())) { std::cerr << "Error: Render::render_adaptive: the Scene's size differs from the camera's" << std::endl; return st; }
+    if (target != &scene) {
+        if (target) { flush_into(*target); target->detach(this); }
+        target = &scene;
+    }
+    scene.attach(this);
+    if (mcpt_render_adaptive(ctx, seed, next_sample, opts, &st) != MCPT_OK) {
+        std::cerr << "Error: mcpt_render_adaptive: " << mcpt_last_error() << std::endl;
+        std::memset(&st, 0, sizeof st); st.struct_size = sizeof st; return st;
+    }
+    // the largest count a tile reached: min_spp doubled once per later pass, the last doubling capped at max_spp
+    const uint32_t min_spp = opts && opts->min_spp ? opts->min_spp : 16u, max_spp = opts && opts->max_spp ? opts->max_spp : 1024u;
+    uint32_t c = min_spp;
+    for (uint32_t p = 1; p < st.passes; p++) c += std::min(c, max_spp - c);
+    next_sample += c; dirty = true;
+    return st;
 }
 void Render::flush_into(Scene& scene) {
     if (!ctx || !dirty || &scene != target) return;

@@ -24,6 +24,9 @@ public:
     // way -- width * height pixels in getPixelsColor's orientation, valid until the next call.  The first call renders the feature buffers
     // (4 samples of `seed`).  nullptr on failure.
     const Color3b* denoised(Scene& scene, const mcpt_denoise_opts* opts = nullptr);
+    // Adaptive sampling into `scene` (mcpt_render_adaptive): the samples stay on the device like render()'s, and the next frame
+    // starts past the largest per-tile count this call reached, so no sample index is used twice.  passes == 0 on failure.
+    mcpt_adaptive_stats render_adaptive(Scene& scene, const mcpt_adaptive_opts* opts = nullptr);
     Render(const Render&) = delete;
     Render& operator=(const Render&) = delete;
     bool ok() const { return ctx != nullptr; }

@@ -3,6 +3,8 @@
 // devices of this node from ONE process and sums the films with RCCL (ncclAllReduce over xGMI).
 #include <atomic>
 #include <chrono>
+#include <cmath>
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +22,8 @@ static void usage() {
     std::cout << "usage: mcpt_cli scene.obj [--spp N] [--batch B] [--depth D] [--gpus G] [--shard samples|tiles] [--out prefix] [--seed S] [--recursive] [--corrected]\n"
                  "                          [--deterministic] [--ref-index-order] [--ref-tie-order] [--gpu-bvh] [--check] [--dump-model file] [--save-every K]\n"
                  "                          [--denoise]   (also writes <prefix><frames>_denoised.png, and one per --save-every image)\n"
+                 "                          [--adaptive T [--min-spp N]]   adaptive sampling per 8x8 tile down to error T, --spp samples at most per pixel\n"
+                 "                                        (one GPU; also writes <prefix>_spp.png, a grey map of log2(samples) / log2(spp))\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -45,6 +49,7 @@ int main(int argc, char** argv) {
     }
     std::string filename = argv[1], out, dump_model;
     uint32_t spp = 64, batch = 0, depth = 0, gpus = 1, save_every = 0; uint64_t seed = 20251004; uint32_t flags = 0, integrator = 0; bool ref_order = false, check_only = false, shard_tiles = false, denoise = false;
+    float adaptive = -1.f; uint32_t min_spp = 0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -59,8 +64,11 @@ int main(int argc, char** argv) {
         else if (a == "--save-every") save_every = uint32_t(std::atoi(next()));
         else if (a == "--shard") shard_tiles = std::string(next()) == "tiles";
         else if (a == "--denoise") denoise = true;
+        else if (a == "--adaptive") adaptive = float(std::atof(next()));
+        else if (a == "--min-spp") min_spp = uint32_t(std::atoi(next()));
         else { usage(); return 2; }
     }
+    if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
     std::cout << model.face.size() << " " << model.normal.size() << " " << model.vertex.size() << std::endl;   // main.cpp:14
@@ -140,6 +148,38 @@ int main(int argc, char** argv) {
         if (write_png_rgb8(file, w, h, rgb.data())) std::cout << "Image saved successfully: " << file << std::endl;
         else std::cerr << "Failed to save image: " << file << std::endl;
     };
+    // --adaptive T: one mcpt_render_adaptive call instead of the batch loop -- --spp samples per pixel at most, --min-spp in pass 0
+    if (adaptive >= 0.f) {
+        mcpt_ctx* c = renders[0]->handle();
+        mcpt_adaptive_opts ao; std::memset(&ao, 0, sizeof ao); ao.struct_size = sizeof ao; ao.min_spp = min_spp; ao.max_spp = spp; ao.threshold = adaptive;
+        mcpt_adaptive_stats st;
+        auto t0 = std::chrono::steady_clock::now();
+        if (mcpt_render_adaptive(c, seed, 0, &ao, &st) != MCPT_OK || mcpt_sync(c) != MCPT_OK) { std::cerr << "Error: mcpt_render_adaptive: " << mcpt_last_error() << std::endl; return 1; }
+        total_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        std::printf("adaptive: %u passes, %.1f samples per pixel, %u tiles converged, %u capped: %.3f s\n", st.passes,
+                    double(st.pixel_samples) / (double(w) * h), st.tiles_converged, st.tiles_capped, total_s);
+        if (denoise) save_denoised(nullptr, spp);
+        if (failed.load() || mcpt_read_accum(c, film.data()) != MCPT_OK) { std::cerr << "Error: " << mcpt_last_error() << std::endl; return 1; }
+        // the sample-count map: log2(count) / log2(spp) as grey, top row first like the saved image
+        std::vector<uint8_t> grey(size_t(w) * h * 3);
+        const double top = std::log2(std::max(2.0, double(spp)));
+        for (int y = 0; y < h; y++) for (int x = 0; x < w; x++) {
+            const float n = film[4 * (size_t(h - 1 - y) * w + x) + 3];
+            const double g = n > 0.f ? std::min(1.0, std::max(0.0, std::log2(double(n)) / top)) : 0.0;
+            for (int k = 0; k < 3; k++) grey[3 * (size_t(y) * w + x) + k] = uint8_t(g * 255.0 + 0.5);
+        }
+        const std::string map = out + "_spp.png";
+        if (write_png_rgb8(map, w, h, grey.data())) std::cout << "Image saved successfully: " << map << std::endl;
+        else std::cerr << "Failed to save image: " << map << std::endl;
+        scene.add_film(film.data());
+        mcpt_counters cn;
+        if (mcpt_get_counters(c, &cn) != MCPT_OK) { std::cerr << "Error: " << mcpt_last_error() << std::endl; return 1; }
+        rays = cn.rays_primary + cn.rays_continuation + cn.rays_shadow;
+        std::printf("%u spp max, %dx%d, 1 GPU(s): %.3f s, %.1f Mray/s\n", spp, w, h, total_s, rays / total_s / 1e6);
+        scene.save_image(int(spp), out);
+        for (auto r : renders) delete r;
+        return 0;
+    }
     // The films stay on the devices from batch to batch (the reference's loop reads its film every frame only to display it): per batch
     // one mcpt_render per device, at the end the path's one exchange step and one read-back.
     while (frame < spp && !failed.load()) {
