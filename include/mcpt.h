@@ -91,6 +91,10 @@ typedef struct mcpt_scene_desc {
                                                refuses the flag with MCPT_ERR_UNSUPPORTED for MCPT_INTEGRATOR_RECURSIVE_NEE and for the cross-check megakernel
                                                (MCPT_PIPELINE=mega), whose binary-tree traversal lets the first triangle IT tests win -- as does mcpt_probe_trace */
 
+#define MCPT_FLAG_DYNAMIC             0x20u /* mcpt_create keeps what mcpt_update_vertices needs: per triangle its vertex and normal indices, the level structure
+                                               of both trees and refit scratch (counted in device_bytes); without it that call returns
+                                               MCPT_ERR_UNSUPPORTED, and device_bytes and every stream are what they are without the flag */
+
 typedef struct mcpt_opts {
     uint32_t struct_size;       /* = sizeof(mcpt_opts) */
     int32_t  device;            /* HIP device ordinal */
@@ -246,6 +250,46 @@ mcpt_status mcpt_read_tile_error(mcpt_ctx* ctx, float* out);
  * tile, out_list (room for tiles_y * tiles_x entries) the active tiles in ascending order, *out_n their number.  Synchronous. */
 mcpt_status mcpt_probe_tile_error(mcpt_ctx* ctx, const float* h_rgba_host, const float* o_rgba_host, float threshold, uint32_t max_spp,
                                   float* out_err, uint32_t* out_list, uint32_t* out_n);
+
+/* ---- live scenes: camera moves and vertex updates --------------------------------------------------------------------- */
+/* Both calls below are ordered like any other call on the context: renders enqueued before them see the old scene, renders enqueued after
+ * them the new one (their device work runs on the context's stream, which every sub-pipeline forks from and joins).  Neither touches the film
+ * or the counters: the caller clears the film (mcpt_clear_accum) when the old samples no longer belong to the picture.  The first-hit feature
+ * buffers and the tile error of the last adaptive call describe the old scene: after either call the context is without them, as a clone is
+ * (mcpt_denoise / mcpt_read_features / mcpt_read_tile_error answer as on a context that never had them). */
+
+/* New camera for the same film size.  camera->width / height must equal the context's (else MCPT_ERR_INVALID_ARG, nothing changed);
+ * eye == lookat or a non-finite field: MCPT_ERR_INVALID_ARG.  Works on every context, MCPT_FLAG_DYNAMIC or not.  The constants are formed by
+ * the function mcpt_create uses: the same camera gives the same rays, bit for bit, either way. */
+mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* camera);
+
+/* New positions (and optionally new normals) for the SAME faces: n_vertex / n_normal must equal those of the mcpt_scene_desc the context was
+ * created from; normal == NULL keeps the normals.  Rewrites the triangle streams and the light records and refits BOTH trees on the device.
+ *  - `vertex` is validated on the host before any device work, by mcpt_create's rules (every vertex a face uses finite and |x| <= 1e18; the
+ *    counts; NULL): MCPT_ERR_INVALID_ARG, context unchanged.  It is staged through pinned memory and copied in stream order, so the caller
+ *    may reuse the arrays when the call returns.
+ *  - Device coordinates stay relative to the CREATION-time centre; mcpt_scene_info::centre does not change.  Geometry that travels far from
+ *    it loses fp32 precision (the absolute ray epsilon 1e-4 needs |coordinate| * 2^-24 << 1e-4): create a new context then.
+ *  - Tie ranks, leaf order, lobe classes, materials, textures and the light list's membership and order are those of creation; with
+ *    MCPT_FLAG_REFERENCE_TIE_ORDER the ranks are the creation geometry's.
+ *  - Topology and octant slots are kept, so a large deformation makes traversal slower, never wrong; mcpt_update_info::wide_area_ratio tells
+ *    the caller when a fresh mcpt_create is due.
+ *  - mcpt_clone_to_device of a dynamic context gives a dynamic context.  Works with either builder, with deep device-built binary trees and
+ *    with both integrators. */
+mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal);
+
+typedef struct mcpt_update_info {
+    uint32_t struct_size, updates;      /* mcpt_update_vertices calls on this context so far */
+    double   last_update_ms;            /* device time of the last one, first to last operation on the stream (HIP events) */
+    double   wide_area_ratio;           /* sum of the child-box areas of the 8-wide tree now / at creation (dequantised boxes; 1.0 before any update) */
+    uint32_t reserved[4];
+} mcpt_update_info;
+mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out);   /* synchronises */
+
+/* Probe: downloads the context's CURRENT device streams and runs the host soundness walks on them: the 8-wide tree's (every triangle's fp32
+ * test data inside every dequantised box on its root path, referenced once) and the same containment check on the binary tree.
+ * MCPT_OK = sound; otherwise MCPT_ERR_INVALID_ARG with the walk's message in mcpt_last_error(). */
+mcpt_status mcpt_probe_validate_trees(mcpt_ctx* ctx);
 
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that

@@ -29,6 +29,7 @@ FLAG_DETERMINISTIC = 0x2
 FLAG_COUNT_TRAVERSAL = 0x4
 FLAG_GPU_BVH_BUILD = 0x8
 FLAG_REFERENCE_TIE_ORDER = 0x10
+FLAG_DYNAMIC = 0x20
 
 
 class Texture(C.Structure):
@@ -99,6 +100,14 @@ class AdaptiveOpts(C.Structure):
 class AdaptiveStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("passes", C.c_uint32), ("pixel_samples", C.c_uint64),
                 ("tiles_converged", C.c_uint32), ("tiles_capped", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class UpdateInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("updates", C.c_uint32), ("last_update_ms", C.c_double),
+                ("wide_area_ratio", C.c_double), ("reserved", C.c_uint32 * 4)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -211,6 +220,10 @@ def load_library() -> C.CDLL:
         "mcpt_render_adaptive": [vp, C.c_uint64, C.c_uint32, P(AdaptiveOpts), P(AdaptiveStats)],
         "mcpt_read_tile_error": [vp, vp],
         "mcpt_probe_tile_error": [vp, vp, vp, C.c_float, C.c_uint32, vp, vp, P(C.c_uint32)],
+        "mcpt_set_camera": [vp, P(CameraC)],
+        "mcpt_update_vertices": [vp, vp, C.c_uint32, vp, C.c_uint32],
+        "mcpt_get_update_info": [vp, P(UpdateInfo)],
+        "mcpt_probe_validate_trees": [vp],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -232,6 +245,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_probe_paths", "mcpt_probe_rng", "mcpt_probe_texture",
     "mcpt_render_features", "mcpt_read_features", "mcpt_denoise", "mcpt_read_denoised", "mcpt_denoised_device_ptr",
     "mcpt_render_tile_list", "mcpt_render_adaptive", "mcpt_read_tile_error", "mcpt_probe_tile_error",
+    "mcpt_set_camera", "mcpt_update_vertices", "mcpt_get_update_info", "mcpt_probe_validate_trees",
 ]
 
 
@@ -330,6 +344,30 @@ class Renderer:
         n = C.c_uint32(0)
         self._check(self.lib.mcpt_probe_tile_error(self.ctx, _ptr(a), _ptr(b), threshold, max_spp, _ptr(err), _ptr(lst), C.byref(n)))
         return err, lst[:n.value].copy()
+
+    # ---- live scenes
+    def set_camera(self, camera):
+        """A new camera (scenes.Camera) for the same film size; free.  The caller clears the film when the old samples no longer belong."""
+        c = CameraC()
+        for k in range(3):
+            c.eye[k] = camera.eye[k]; c.lookat[k] = camera.lookat[k]; c.up[k] = camera.up[k]
+        c.fovy = camera.fovy; c.width = camera.width; c.height = camera.height
+        self._check(self.lib.mcpt_set_camera(self.ctx, C.byref(c)))
+
+    def update_vertices(self, vertex, normal=None):
+        """New positions (and optionally normals) for the same faces: refits both trees on the device.  Needs FLAG_DYNAMIC."""
+        v = np.ascontiguousarray(vertex, np.float64).reshape(-1, 3)
+        n = None if normal is None else np.ascontiguousarray(normal, np.float64).reshape(-1, 3)
+        self._check(self.lib.mcpt_update_vertices(self.ctx, _ptr(v), v.shape[0], _ptr(n), 0 if n is None else n.shape[0]))
+
+    def update_info(self) -> UpdateInfo:
+        i = UpdateInfo()
+        self._check(self.lib.mcpt_get_update_info(self.ctx, C.byref(i)))
+        return i
+
+    def validate_trees(self):
+        """The host soundness walks over the context's current device trees; raises McptError with the walk's message if one fails."""
+        self._check(self.lib.mcpt_probe_validate_trees(self.ctx))
 
     def sync(self):
         self._check(self.lib.mcpt_sync(self.ctx))

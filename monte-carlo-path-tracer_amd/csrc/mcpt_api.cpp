@@ -7,6 +7,7 @@
 #include "wavefront.h"
 #include "denoise.h"
 #include "adaptive.h"
+#include "refit.h"
 
 #include <chrono>
 #include <cmath>
@@ -95,6 +96,17 @@ struct mcpt_ctx {
     DevBuf ad_h, ad_o, ad_err, ad_list, ad_flags, ad_counts, ad_offs, ad_tot;
     AdTotals* ad_host = nullptr;
     bool ad_have_err = false;
+    // Live scenes (refit.hip).  MCPT_FLAG_DYNAMIC only: per triangle its vertex and normal indices (leaf order), the device copy of
+    // the caller's vertices / normals and its pinned staging, per triangle and per 8-wide node an fp32 box (refit scratch), the binary nodes sorted
+    // by height and the level boundaries of both trees (one launch per level), the per-block partial sums of the wide tree's box areas.
+    bool dynamic = false;
+    uint32_t rf_n_vertex = 0, rf_n_normal = 0;
+    DevBuf rf_idx, rf_vtx, rf_nrm, rf_tri_box, rf_node_box, rf_bin_order, rf_area;
+    std::vector<uint32_t> rf_bin_level, rf_wide_level;      // [k], [k + 1]: the nodes of height k in rf_bin_order / the records of depth k in nodes8
+    std::vector<uint8_t> rf_used_vertex;                    // a face uses this vertex: it is validated
+    double* rf_stage = nullptr; hipEvent_t rf_stage_ev = nullptr; bool rf_stage_pending = false;
+    hipEvent_t rf_ev0 = nullptr, rf_ev1 = nullptr; bool rf_timed = false;
+    uint32_t rf_updates = 0; double rf_last_ms = 0.0, rf_area0 = 0.0;
 };
 
 namespace {
@@ -130,6 +142,9 @@ void destroy_ctx(mcpt_ctx* c) {
     c->tl_dev.free_(); if (c->tl_host) (void)hipHostFree(c->tl_host); if (c->tl_ev) (void)hipEventDestroy(c->tl_ev);
     for (DevBuf* b : {&c->ad_h, &c->ad_o, &c->ad_err, &c->ad_list, &c->ad_flags, &c->ad_counts, &c->ad_offs, &c->ad_tot}) b->free_();
     if (c->ad_host) (void)hipHostFree(c->ad_host);
+    for (DevBuf* b : {&c->rf_idx, &c->rf_vtx, &c->rf_nrm, &c->rf_tri_box, &c->rf_node_box, &c->rf_bin_order, &c->rf_area}) b->free_();
+    if (c->rf_stage) (void)hipHostFree(c->rf_stage);
+    for (hipEvent_t ev : {c->rf_stage_ev, c->rf_ev0, c->rf_ev1}) if (ev) (void)hipEventDestroy(ev);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     for (uint32_t i = 0; i < mcpt_ctx::TIMED; i++) { if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]); if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -260,6 +275,98 @@ static void fill_wide_info(mcpt_scene_info& in, const HostScene& hs) {
     in.wide_tree_hash = h;
 }
 
+
+// ------------------------------------------------------------------------------------------------ live scenes: set-up
+// Sum of the dequantised child-box areas of the context's 8-wide tree, as it is on the device when the stream reaches this point.  Synchronises.
+static mcpt_status rf_wide_area(mcpt_ctx* c, double& out) {
+    const uint32_t n8 = uint32_t(c->dev.n_nodes8), nb = rf_area_blocks(n8);
+    HIP_TRY(launch_rf_wide_area(c->dev.nodes8, n8, static_cast<double*>(c->rf_area.p), c->stream));
+    std::vector<double> part(nb);
+    HIP_TRY(hipMemcpyAsync(part.data(), c->rf_area.p, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out = 0.0;
+    for (double v : part) out += v;
+    return MCPT_OK;
+}
+// The level structure of both trees from their host records.  Binary tree: the renumbering puts every parent before its children, so one
+// descending pass gives the heights (0 = both children are leaves); the nodes are then sorted by height.  8-wide tree: build_bvh8 and
+// gpu_collapse_bvh8 number the records breadth-first, level by level -- a level's inner children are the next level, consecutively.
+static bool rf_levels(const std::vector<f4h>& n2, const std::vector<f4h>& n8, std::vector<uint32_t>& bin_order, std::vector<uint32_t>& bin_level,
+                      std::vector<uint32_t>& wide_level, std::string& err) {
+    const size_t N = n2.size() / 4, N8 = n8.size() / 5;
+    auto as_i = [](float f) { int v; std::memcpy(&v, &f, 4); return v; };
+    std::vector<uint32_t> height(N, 0);
+    uint32_t top = 0;
+    for (size_t n = N; n-- > 0;) {
+        uint32_t h = 0;
+        for (int k = 0; k < 2; k++) {
+            const int c = as_i(k == 0 ? n2[4 * n + 3].x : n2[4 * n + 3].y);
+            if (c < 0) continue;
+            if (size_t(c) <= n || size_t(c) >= N) { err = "binary tree is not numbered parents first (internal error)"; return false; }
+            h = std::max(h, height[size_t(c)] + 1);
+        }
+        height[n] = h; top = std::max(top, h);
+    }
+    bin_level.assign(size_t(top) + 2, 0);
+    for (size_t n = 0; n < N; n++) bin_level[height[n] + 1]++;
+    for (size_t k = 1; k < bin_level.size(); k++) bin_level[k] += bin_level[k - 1];
+    bin_order.resize(N);
+    { std::vector<uint32_t> at(bin_level.begin(), bin_level.end() - 1); for (size_t n = 0; n < N; n++) bin_order[at[height[n]]++] = uint32_t(n); }
+    wide_level.clear();
+    size_t begin = 0, end = 1;
+    while (begin < end) {
+        wide_level.push_back(uint32_t(begin));
+        size_t kids = 0;
+        for (size_t r = begin; r < end; r++) {
+            uint32_t masks, base; std::memcpy(&masks, &n8[5 * r + 1].w, 4); std::memcpy(&base, &n8[5 * r + 1].x, 4);
+            const uint32_t ni = uint32_t(__builtin_popcount(masks & 0xffu));
+            if (ni && base != end + kids) { err = "8-wide tree is not numbered level by level (internal error)"; return false; }
+            kids += ni;
+        }
+        begin = end; end += kids;
+        if (end > N8) { err = "8-wide tree: child link out of range (internal error)"; return false; }
+    }
+    wide_level.push_back(uint32_t(begin));
+    if (begin != N8) { err = "8-wide tree: unreachable records (internal error)"; return false; }
+    return true;
+}
+static mcpt_status rf_alloc(mcpt_ctx* c) {
+    const size_t nt = size_t(c->dev.n_tris), n8 = size_t(c->dev.n_nodes8), n2 = size_t(c->dev.n_nodes);
+    HIP_TRY(c->rf_idx.alloc(nt * 6 * sizeof(int32_t))); HIP_TRY(c->rf_vtx.alloc(size_t(c->rf_n_vertex) * 3 * sizeof(double)));
+    HIP_TRY(c->rf_nrm.alloc(size_t(c->rf_n_normal) * 3 * sizeof(double))); HIP_TRY(c->rf_tri_box.alloc(nt * 6 * sizeof(float)));
+    HIP_TRY(c->rf_node_box.alloc(n8 * 6 * sizeof(float))); HIP_TRY(c->rf_bin_order.alloc(n2 * sizeof(uint32_t)));
+    HIP_TRY(c->rf_area.alloc(size_t(rf_area_blocks(uint32_t(n8))) * sizeof(double)));
+    HIP_TRY(hipHostMalloc((void**)&c->rf_stage, (size_t(c->rf_n_vertex) + c->rf_n_normal) * 3 * sizeof(double) + 16, hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&c->rf_stage_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventCreate(&c->rf_ev0)); HIP_TRY(hipEventCreate(&c->rf_ev1));
+    for (DevBuf* b : {&c->rf_idx, &c->rf_vtx, &c->rf_nrm, &c->rf_tri_box, &c->rf_node_box, &c->rf_bin_order, &c->rf_area}) c->info.device_bytes += b->bytes;
+    c->dynamic = true;
+    return MCPT_OK;
+}
+static mcpt_status rf_setup(mcpt_ctx* c, const HostScene& hs, const mcpt_scene_desc* scene) {
+    std::vector<uint32_t> bin_order; std::string err;
+    if (!rf_levels(hs.nodes, hs.nodes8, bin_order, c->rf_bin_level, c->rf_wide_level, err)) return fail(MCPT_ERR_UNSUPPORTED, "MCPT_FLAG_DYNAMIC: " + err);
+    c->rf_n_vertex = scene->n_vertex; c->rf_n_normal = scene->n_normal;
+    c->rf_used_vertex.assign(scene->n_vertex, 0);
+    for (size_t i = 0; i < hs.dyn_idx.size(); i += 6) for (int k = 0; k < 3; k++) c->rf_used_vertex[size_t(hs.dyn_idx[i + k])] = 1;
+    mcpt_status st = rf_alloc(c); if (st != MCPT_OK) return st;
+    HIP_TRY(hipMemcpy(c->rf_idx.p, hs.dyn_idx.data(), c->rf_idx.bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->rf_bin_order.p, bin_order.data(), c->rf_bin_order.bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return rf_wide_area(c, c->rf_area0);
+}
+static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
+    c->rf_n_vertex = src->rf_n_vertex; c->rf_n_normal = src->rf_n_normal; c->rf_used_vertex = src->rf_used_vertex;
+    c->rf_bin_level = src->rf_bin_level; c->rf_wide_level = src->rf_wide_level; c->rf_area0 = src->rf_area0;
+    mcpt_status st = rf_alloc(c); if (st != MCPT_OK) return st;
+    HIP_TRY(hipMemcpyPeer(c->rf_idx.p, c->device, src->rf_idx.p, src->device, c->rf_idx.bytes));
+    HIP_TRY(hipMemcpyPeer(c->rf_bin_order.p, c->device, src->rf_bin_order.p, src->device, c->rf_bin_order.bytes));
+    HIP_TRY(hipDeviceSynchronize());
+    return MCPT_OK;
+}
+// The first-hit features and the last adaptive call's tile error describe the scene as it was.
+static void rf_forget_derived(mcpt_ctx* c) { c->dn_have_features = false; c->dn_have_out = false; c->ad_have_err = false; }
+
 extern "C" {
 
 uint32_t mcpt_abi_version(void) { return MCPT_ABI_VERSION; }
@@ -291,6 +398,7 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
 
     HostScene hs; std::string err;
     hs.reference_tie_order = (o.flags & MCPT_FLAG_REFERENCE_TIE_ORDER) != 0;
+    hs.keep_dynamic = (o.flags & MCPT_FLAG_DYNAMIC) != 0;
     // which pipeline this context runs is decided ONCE, here: it sets how deep a device-built binary tree may be (below) and which kernels
     // mcpt_render launches -- the two must agree, or a megakernel context could walk a tree deeper than its LDS stack
     const bool use_wavefront = [&]() { const char* pipe = std::getenv("MCPT_PIPELINE"); return !(pipe && std::string(pipe) == "mega") && o.integrator == MCPT_INTEGRATOR_MIS; }();
@@ -358,6 +466,7 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
     fill_wide_info(in, hs);
     const mcpt_status fs = finish_ctx(c);
     if (fs != MCPT_OK) { destroy_ctx(c); return fs; }
+    if (o.flags & MCPT_FLAG_DYNAMIC) { const mcpt_status ds = rf_setup(c, hs, scene); if (ds != MCPT_OK) { destroy_ctx(c); return ds; } }
     in.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out_ctx = c;
     return MCPT_OK;
@@ -389,6 +498,7 @@ mcpt_status mcpt_clone_to_device(mcpt_ctx* src, int32_t device, mcpt_ctx** out_c
     }
     const mcpt_status fs = finish_ctx(c);
     if (fs != MCPT_OK) { destroy_ctx(c); return fs; }
+    if (src->dynamic) { const mcpt_status ds = rf_clone(c, src); if (ds != MCPT_OK) { destroy_ctx(c); return ds; } }
     c->info.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out_ctx = c;
     return MCPT_OK;
@@ -1078,6 +1188,101 @@ mcpt_status mcpt_probe_tile_error(mcpt_ctx* ctx, const float* h_rgba_host, const
     HIP_TRY(hipMemcpy(out_err, err, n_tiles * sizeof(float), hipMemcpyDeviceToHost));
     if (t.n_active) HIP_TRY(hipMemcpy(out_list, list, t.n_active * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *out_n = t.n_active;
+    return MCPT_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------ live scenes
+mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* cm) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!cm) return fail(MCPT_ERR_INVALID_ARG, "mcpt_set_camera: null camera");
+    if (cm->width != ctx->width || cm->height != ctx->height) return fail(MCPT_ERR_INVALID_ARG, "mcpt_set_camera: width / height differ from the context's film");
+    bool finite = std::isfinite(cm->fovy);
+    for (int a = 0; a < 3; a++) finite = finite && std::isfinite(cm->eye[a]) && std::isfinite(cm->lookat[a]) && std::isfinite(cm->up[a]);
+    if (!finite) return fail(MCPT_ERR_INVALID_ARG, "mcpt_set_camera: a camera field is not finite");
+    if (cm->eye[0] == cm->lookat[0] && cm->eye[1] == cm->lookat[1] && cm->eye[2] == cm->lookat[2]) return fail(MCPT_ERR_INVALID_ARG, "mcpt_set_camera: eye == lookat");
+    // the camera travels by value with every launch (DevScene::cam): launches already enqueued keep the old one, later ones get this one
+    camera_constants(*cm, ctx->dev.centre, ctx->dev.cam);
+    rf_forget_derived(ctx);
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_update_vertices: the context was created without MCPT_FLAG_DYNAMIC");
+    if (!vertex) return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_vertices: null vertex array");
+    if (n_vertex != ctx->rf_n_vertex) return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_vertices: n_vertex differs from the scene's");
+    if (normal && n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_vertices: n_normal differs from the scene's");
+    for (uint32_t v = 0; v < n_vertex; v++) {
+        if (!ctx->rf_used_vertex[v]) continue;
+        const double* x = vertex + 3 * size_t(v);
+        if (!(std::fabs(x[0]) <= MCPT_MAX_COORD && std::fabs(x[1]) <= MCPT_MAX_COORD && std::fabs(x[2]) <= MCPT_MAX_COORD))
+            return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_vertices: vertex " + std::to_string(v) + ": coordinate is not finite or exceeds 1e18");
+    }
+    // the staging buffer's last copy has been made; the last update's duration is read before its events are recorded again
+    if (ctx->rf_stage_pending) { HIP_TRY(hipEventSynchronize(ctx->rf_stage_ev)); ctx->rf_stage_pending = false; }
+    if (ctx->rf_timed) { HIP_TRY(hipEventSynchronize(ctx->rf_ev1)); float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ctx->rf_ev0, ctx->rf_ev1)); ctx->rf_last_ms = ms; ctx->rf_timed = false; }
+    const size_t vd = size_t(n_vertex) * 3, nd = size_t(ctx->rf_n_normal) * 3;
+    std::memcpy(ctx->rf_stage, vertex, vd * sizeof(double));
+    if (normal) std::memcpy(ctx->rf_stage + vd, normal, nd * sizeof(double));
+    // Everything below is stream work on the context's stream: it starts after every render enqueued so far has finished (the sub-pipelines'
+    // streams joined it at the end of their call, known-length jobs included) and the next render's sub-pipelines fork from it after the last
+    // kernel here.
+    hipStream_t s = ctx->stream;
+    HIP_TRY(hipEventRecord(ctx->rf_ev0, s));
+    HIP_TRY(hipMemcpyAsync(ctx->rf_vtx.p, ctx->rf_stage, vd * sizeof(double), hipMemcpyHostToDevice, s));
+    if (normal) HIP_TRY(hipMemcpyAsync(ctx->rf_nrm.p, ctx->rf_stage + vd, nd * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(ctx->rf_stage_ev, s)); ctx->rf_stage_pending = true;
+    const double* d_nrm = normal ? static_cast<const double*>(ctx->rf_nrm.p) : nullptr;
+    const int32_t* idx = static_cast<const int32_t*>(ctx->rf_idx.p);
+    float* tri_box = static_cast<float*>(ctx->rf_tri_box.p);
+    const DevScene& d = ctx->dev;
+    HIP_TRY(launch_rf_triangles(static_cast<const double*>(ctx->rf_vtx.p), d_nrm, idx, RfCentre{d.centre[0], d.centre[1], d.centre[2]}, static_cast<float4*>(ctx->tri_isect.p),
+                                static_cast<float4*>(ctx->tri_shade.p), static_cast<double*>(ctx->tri_pos64.p), tri_box, uint32_t(d.n_tris), s));
+    HIP_TRY(launch_rf_lights(static_cast<DevLight*>(ctx->lights.p), static_cast<double*>(ctx->light_pos64.p), d.tri_isect, d.tri_pos64, d_nrm, idx, uint32_t(d.n_lights), s));
+    for (size_t k = 0; k + 1 < ctx->rf_bin_level.size(); k++)                    // heights, lowest first
+        HIP_TRY(launch_rf_binary_level(static_cast<float4*>(ctx->nodes.p), static_cast<const uint32_t*>(ctx->rf_bin_order.p), ctx->rf_bin_level[k], ctx->rf_bin_level[k + 1], tri_box, s));
+    for (size_t k = ctx->rf_wide_level.size() - 1; k-- > 0;)                     // depths, deepest first
+        HIP_TRY(launch_rf_wide_level(static_cast<float4*>(ctx->nodes8.p), ctx->rf_wide_level[k], ctx->rf_wide_level[k + 1], tri_box, static_cast<float*>(ctx->rf_node_box.p), s));
+    HIP_TRY(launch_rf_wide_area(d.nodes8, uint32_t(d.n_nodes8), static_cast<double*>(ctx->rf_area.p), s));
+    HIP_TRY(hipEventRecord(ctx->rf_ev1, s)); ctx->rf_timed = true;
+    ctx->rf_updates++;
+    rf_forget_derived(ctx);
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    if (ctx->rf_timed) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ctx->rf_ev0, ctx->rf_ev1)); ctx->rf_last_ms = ms; ctx->rf_timed = false; }
+    std::memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out; out->updates = ctx->rf_updates; out->last_update_ms = ctx->rf_last_ms; out->wide_area_ratio = 1.0;
+    if (ctx->rf_updates) {                                                      // the last update left its partial sums behind
+        std::vector<double> part(rf_area_blocks(uint32_t(ctx->dev.n_nodes8)));
+        HIP_TRY(hipMemcpy(part.data(), ctx->rf_area.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+        double a = 0.0; for (double v : part) a += v;
+        out->wide_area_ratio = ctx->rf_area0 > 0.0 ? a / ctx->rf_area0 : 1.0;
+    }
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_validate_trees(mcpt_ctx* ctx) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    HostScene hs;
+    hs.nodes.resize(ctx->nodes.bytes / sizeof(f4h)); hs.nodes8.resize(ctx->nodes8.bytes / sizeof(f4h)); hs.tri_isect.resize(ctx->tri_isect.bytes / sizeof(f4h));
+    hs.tri_face.resize(size_t(ctx->dev.n_tris));
+    HIP_TRY(hipMemcpy(hs.nodes.data(), ctx->nodes.p, ctx->nodes.bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hs.nodes8.data(), ctx->nodes8.p, ctx->nodes8.bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hs.tri_isect.data(), ctx->tri_isect.p, ctx->tri_isect.bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hs.tri_face.data(), ctx->tri_face.p, ctx->tri_face.bytes, hipMemcpyDeviceToHost));
+    std::string bad = validate_bvh8(hs);
+    if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, "8-wide tree: " + bad);
+    bad = validate_bvh2(hs);
+    if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, bad);
     return MCPT_OK;
 }
 

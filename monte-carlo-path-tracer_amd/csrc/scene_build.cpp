@@ -23,7 +23,7 @@
 #include <system_error>
 #include <thread>
 
-static constexpr double kMaxCoord = 1e18;
+static constexpr double kMaxCoord = MCPT_MAX_COORD;
 
 namespace {
 
@@ -467,6 +467,56 @@ std::string validate_bvh8(const HostScene& hs) {
     return "";
 }
 
+// ---- camera constants (Render.cpp:73-75), fp64, glm operation order: the one place they are formed (mcpt_create and mcpt_set_camera)
+void camera_constants(const mcpt_camera& cm, const double* ctr, DevCamera& cam) {
+    const double PI_D = 3.14159265358979323846;
+    cam.h = std::tan(cm.fovy * PI_D / 180.0 * 0.5) * 2.0;
+    double fr[3] = {cm.lookat[0] - cm.eye[0], cm.lookat[1] - cm.eye[1], cm.lookat[2] - cm.eye[2]};
+    double inv = 1.0 / len3(fr);
+    for (int a = 0; a < 3; a++) { cam.front[a] = fr[a] * inv; cam.eye[a] = cm.eye[a] - ctr[a]; cam.up[a] = cm.up[a]; }   // (front from the world coordinates, like Render.cpp:74)
+    double rt[3] = {cam.front[1] * cm.up[2] - cm.up[1] * cam.front[2], cam.front[2] * cm.up[0] - cm.up[2] * cam.front[0],
+                    cam.front[0] * cm.up[1] - cm.up[0] * cam.front[1]};
+    inv = 1.0 / len3(rt);
+    for (int a = 0; a < 3; a++) cam.right[a] = rt[a] * inv;
+    cam.width = cm.width; cam.height = cm.height;
+}
+
+// The same containment walk for the binary tree (mcpt_probe_validate_trees): every leaf triangle's fp32 test data inside every child box on its
+// root path, every triangle referenced exactly once, child links in range; empty string = sound.
+std::string validate_bvh2(const HostScene& hs) {
+    const size_t n2 = hs.nodes.size() / 4, nt = hs.tri_face.size();
+    if (n2 == 0) return "empty nodes";
+    std::vector<uint8_t> seen(nt, 0);
+    struct Item { int node; float lo[3], hi[3]; };
+    std::vector<Item> stack;
+    Item root; root.node = 0; for (int a = 0; a < 3; a++) { root.lo[a] = -INFINITY; root.hi[a] = INFINITY; }
+    stack.push_back(root);
+    size_t visited = 0;
+    while (!stack.empty()) {
+        const Item it = stack.back(); stack.pop_back();
+        if (it.node < 0 || size_t(it.node) >= n2) return "binary tree: child link out of range";
+        if (++visited > n2) return "binary tree: cycle";
+        for (int k = 0; k < 2; k++) {
+            const int c = child2(hs.nodes, it.node, k);
+            const Box3f b = box2(hs.nodes, it.node, k);
+            Item ch; ch.node = c;
+            for (int a = 0; a < 3; a++) { ch.lo[a] = std::max(it.lo[a], b.lo[a]); ch.hi[a] = std::min(it.hi[a], b.hi[a]); }
+            if (c >= 0) { stack.push_back(ch); continue; }
+            const uint32_t leaf = uint32_t(~c), first = leaf >> 3, cnt = leaf & 7u;
+            if (size_t(first) + cnt > nt) return "binary tree: leaf range out of bounds";
+            for (uint32_t t = first; t < first + cnt; t++) {
+                if (seen[t]++) return "binary tree: triangle referenced twice";
+                const f4h v0 = hs.tri_isect[3 * size_t(t)], e1 = hs.tri_isect[3 * size_t(t) + 1], e2 = hs.tri_isect[3 * size_t(t) + 2];
+                const float P[3][3] = {{v0.x, v0.y, v0.z}, {v0.x + e1.x, v0.y + e1.y, v0.z + e1.z}, {v0.x + e2.x, v0.y + e2.y, v0.z + e2.z}};
+                for (int q = 0; q < 3; q++) for (int a = 0; a < 3; a++)
+                    if (!(P[q][a] >= ch.lo[a] && P[q][a] <= ch.hi[a])) return "binary tree: triangle " + std::to_string(t) + " sticks out of a box on its path";
+            }
+        }
+    }
+    for (size_t t = 0; t < nt; t++) if (!seen[t]) return "binary tree: triangle " + std::to_string(t) + " not reachable";
+    return "";
+}
+
 // MCPT_FLAG_REFERENCE_TIE_ORDER: where every face ends up in the reference's BVH::triangles.  BVH::build (BVH.cpp:15-54) partitions the
 // range [l, r) about the midpoint (narrowed to float, :39) of the CENTROID box's longest axis (AABB::max_axis, AABB.cpp:12-23) with
 // std::partition -- the same libstdc++ algorithm `oracle/_ref` is built with, so the order is the same element for element -- halves the
@@ -644,6 +694,8 @@ mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::stri
     std::vector<uint32_t> ref_rank;
     if (out.reference_tie_order) reference_triangle_order(d, ref_rank);
     out.tri_isect.assign(3 * size_t(nf) + 3, f4h{0.f, 0.f, 0.f, 0.f});    /* + one spare record: the trace kernel fetches triangles in pairs */ out.tri_shade.assign(size_t(MCPT_TRI_SHADE_F4) * nf, f4h{0.f, 0.f, 0.f, 0.f}); out.tri_pos64.resize(9 * size_t(nf)); out.tri_face.resize(nf);
+    out.dyn_idx.clear();
+    if (out.keep_dynamic) out.dyn_idx.resize(6 * size_t(nf));          // MCPT_FLAG_DYNAMIC: what mcpt_update_vertices gathers by
     parallel_for(nf, [&](uint32_t i_begin, uint32_t i_end) {
     for (uint32_t i = i_begin; i < i_end; i++) {
         const int f = order[i];
@@ -671,6 +723,7 @@ mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::stri
             std::memcpy(&S[4], pl, sizeof pl);                              // the fp64 plane: second half of the record
         }
         out.tri_face[i] = f;
+        if (out.keep_dynamic) for (int k = 0; k < 3; k++) { out.dyn_idx[6 * size_t(i) + k] = c[4 * k]; out.dyn_idx[6 * size_t(i) + 3 + k] = c[4 * k + 1]; }
     }
     });
 
@@ -694,18 +747,6 @@ mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::stri
     }
     if (out.lights.empty()) { err = "scene has no emissive triangle (|radiance| > 0.01); the reference indexes lights[-1] here"; return MCPT_ERR_NO_LIGHTS; }
 
-    // ---- camera constants (Render.cpp:73-75), fp64, glm operation order
-    const mcpt_camera& cm = d->camera;
-    DevCamera& cam = out.cam;
-    const double PI_D = 3.14159265358979323846;
-    cam.h = std::tan(cm.fovy * PI_D / 180.0 * 0.5) * 2.0;
-    double fr[3] = {cm.lookat[0] - cm.eye[0], cm.lookat[1] - cm.eye[1], cm.lookat[2] - cm.eye[2]};
-    double inv = 1.0 / len3(fr);
-    for (int a = 0; a < 3; a++) { cam.front[a] = fr[a] * inv; cam.eye[a] = cm.eye[a] - ctr[a]; cam.up[a] = cm.up[a]; }   // (front from the world coordinates, like Render.cpp:74)
-    double rt[3] = {cam.front[1] * cm.up[2] - cm.up[1] * cam.front[2], cam.front[2] * cm.up[0] - cm.up[2] * cam.front[0],
-                    cam.front[0] * cm.up[1] - cm.up[0] * cam.front[1]};
-    inv = 1.0 / len3(rt);
-    for (int a = 0; a < 3; a++) cam.right[a] = rt[a] * inv;
-    cam.width = cm.width; cam.height = cm.height;
+    camera_constants(d->camera, ctr, out.cam);
     return MCPT_OK;
 }

@@ -30,6 +30,8 @@ struct HostScene {
     bool allow_deep_binary = false;  // in: the caller never traverses `nodes` (wavefront pipeline only) -> a device tree deeper than MCPT_STACK_DEPTH is fine
     bool binary_ok = true;           // out: `nodes` fits the binary-tree kernels' stack
     double bvh_build_ms = 0.0;
+    bool keep_dynamic = false;       // in: MCPT_FLAG_DYNAMIC -- also fill dyn_idx
+    std::vector<int32_t> dyn_idx;    // 6 per triangle (leaf order): its three vertex indices, then its three normal indices
 };
 
 // Optional replacement for the host SAH builder (bvh_gpu.hip): gets one fp32 box per face (lo xyz, hi xyz, rounded outward) and
@@ -48,4 +50,11 @@ mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::stri
 
 // Host-side soundness check of the quantised 8-wide tree (empty string = sound); run by mcpt_check_scene.
 std::string validate_bvh8(const HostScene& hs);
+// The same containment walk over the binary tree `nodes`.
+std::string validate_bvh2(const HostScene& hs);
 inline std::string validate_wide_bvh(const HostScene& hs) { return validate_bvh8(hs); }
+
+// DevCamera of `camera` for a scene centred at `centre` (fp64, the reference's operation order): used by mcpt_create and mcpt_set_camera.
+void camera_constants(const mcpt_camera& camera, const double* centre, DevCamera& out);
+// The coordinate bound build_host_scene enforces on every vertex a face uses.
+constexpr double MCPT_MAX_COORD = 1e18;

@@ -81,6 +81,33 @@ mcpt_adaptive_stats Render::render_adaptive(Scene& scene, const mcpt_adaptive_op
     next_sample += c; dirty = true;
     return st;
 }
+static mcpt_camera to_camera(const CameraInfo& c) {
+    mcpt_camera k; std::memset(&k, 0, sizeof k);
+    k.eye[0] = c.eye.x; k.eye[1] = c.eye.y; k.eye[2] = c.eye.z; k.lookat[0] = c.lookat.x; k.lookat[1] = c.lookat.y; k.lookat[2] = c.lookat.z;
+    k.up[0] = c.up.x; k.up[1] = c.up.y; k.up[2] = c.up.z; k.fovy = c.fovy; k.width = c.width; k.height = c.height;
+    return k;
+}
+bool Render::restart(Scene& scene) {
+    if (target && target != &scene) { flush_into(*target); target->detach(this); target = nullptr; }   // another Scene's samples are still that Scene's
+    scene.clear();                                    // (drops what this Render held for `scene`: scene_gone)
+    if (mcpt_clear_accum(ctx) != MCPT_OK) { std::cerr << "Error: mcpt_clear_accum: " << mcpt_last_error() << std::endl; return false; }
+    dirty = false; next_sample = 0; features = false;
+    return true;
+}
+bool Render::set_camera(Scene& scene, const CameraInfo& camera) {
+    if (!ctx) return false;
+    const mcpt_camera k = to_camera(camera);
+    if (mcpt_set_camera(ctx, &k) != MCPT_OK) { std::cerr << "Error: mcpt_set_camera: " << mcpt_last_error() << std::endl; return false; }
+    return restart(scene);
+}
+bool Render::update(Scene& scene, Model& m) {
+    if (!ctx) return false;
+    const mcpt_camera k = to_camera(m.camerainfo);
+    if (mcpt_update_vertices(ctx, reinterpret_cast<const double*>(m.vertex.data()), uint32_t(m.vertex.size()), reinterpret_cast<const double*>(m.normal.data()),
+                             uint32_t(m.normal.size())) != MCPT_OK) { std::cerr << "Error: mcpt_update_vertices: " << mcpt_last_error() << std::endl; return false; }
+    if (mcpt_set_camera(ctx, &k) != MCPT_OK) { std::cerr << "Error: mcpt_set_camera: " << mcpt_last_error() << std::endl; return false; }
+    return restart(scene);
+}
 void Render::flush_into(Scene& scene) {
     if (!ctx || !dirty || &scene != target) return;
     dirty = false;

@@ -27,6 +27,13 @@ public:
     // Adaptive sampling into `scene` (mcpt_render_adaptive): the samples stay on the device like render()'s, and the next frame
     // starts past the largest per-tile count this call reached, so no sample index is used twice.  passes == 0 on failure.
     mcpt_adaptive_stats render_adaptive(Scene& scene, const mcpt_adaptive_opts* opts = nullptr);
+    // Live scenes.  set_camera: a new camera of the same film size (mcpt_set_camera).  update: positions, normals and camera
+    // re-read from `m_model`, the Model this Render was made from, after the caller edited Model::vertex / normal / camerainfo in place -- same
+    // faces and materials; the Render must have been created with MCPT_FLAG_DYNAMIC in its mcpt_opts (mcpt_update_vertices).  Both start the
+    // picture again: the device film and `scene` are cleared, the sample numbering restarts at 0, the feature buffers are forgotten -- the
+    // reference's loop goes on with render(scene) as before.  false (and an unchanged Render and Scene) on failure.
+    bool set_camera(Scene& scene, const CameraInfo& camera);
+    bool update(Scene& scene, Model& m_model);
     Render(const Render&) = delete;
     Render& operator=(const Render&) = delete;
     bool ok() const { return ctx != nullptr; }
@@ -41,6 +48,7 @@ private:
     bool features = false;                            // mcpt_render_features has run for this context
     std::vector<Color3b> denoised_rgb;
     void create(Model& m, const mcpt_opts& opts);
+    bool restart(Scene& scene);
 };
 // Fills an mcpt_scene_desc that points INTO `m` (and into the two scratch vectors); valid while all three live.
 void model_to_desc(Model& m, std::vector<mcpt_material>& mats, std::vector<mcpt_texture>& texs, mcpt_scene_desc& d);

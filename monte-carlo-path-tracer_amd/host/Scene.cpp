@@ -34,6 +34,11 @@ void Scene::attach(FilmSource* source) {
     m_source = source;
 }
 void Scene::detach(FilmSource* source) { if (m_source == source) m_source = nullptr; }
+void Scene::clear() {
+    if (m_source) { m_source->scene_gone(*this); m_source = nullptr; }    // (the source forgets this Scene; the next render attaches it again)
+    for (size_t i = 0; i < size_t(w) * h; i++) m_Pixels[i] = Pixels();
+    m_host_samples = false;
+}
 void Scene::sync() { if (m_source) m_source->flush_into(*this); }
 const Color3b* Scene::getPixelsColor() {
     // The reference's loop calls this after EVERY render(scene) (main.cpp:26-33).  While the whole film is on the device -- nothing was ever

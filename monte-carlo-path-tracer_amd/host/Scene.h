@@ -42,6 +42,7 @@ public:
     FilmSource* source() const { return m_source; }
     bool host_samples() const { return m_host_samples; }               // m_Pixels holds part of the film (else all of it is with the source)
     void sync();                                                      // fold the device part in now
+    void clear();                                                     // an empty film again: the host part zeroed, what a source held for it dropped
     Pixels* pixels() { sync(); return m_Pixels.get(); }
     int width() const { return w; }
     int height() const { return h; }

@@ -24,6 +24,8 @@ static void usage() {
                  "                          [--denoise]   (also writes <prefix><frames>_denoised.png, and one per --save-every image)\n"
                  "                          [--adaptive T [--min-spp N]]   adaptive sampling per 8x8 tile down to error T, --spp samples at most per pixel\n"
                  "                                        (one GPU; also writes <prefix>_spp.png, a grey map of log2(samples) / log2(spp))\n"
+                 "                          [--turntable N]   N frames of --spp samples each, the camera rotated about lookat around up by 360/N degrees per frame\n"
+                 "                                        (one GPU; writes <prefix>_turn<frame>.png)\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -49,7 +51,7 @@ int main(int argc, char** argv) {
     }
     std::string filename = argv[1], out, dump_model;
     uint32_t spp = 64, batch = 0, depth = 0, gpus = 1, save_every = 0; uint64_t seed = 20251004; uint32_t flags = 0, integrator = 0; bool ref_order = false, check_only = false, shard_tiles = false, denoise = false;
-    float adaptive = -1.f; uint32_t min_spp = 0;
+    float adaptive = -1.f; uint32_t min_spp = 0, turntable = 0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -66,9 +68,11 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") denoise = true;
         else if (a == "--adaptive") adaptive = float(std::atof(next()));
         else if (a == "--min-spp") min_spp = uint32_t(std::atoi(next()));
+        else if (a == "--turntable") turntable = uint32_t(std::atoi(next()));
         else { usage(); return 2; }
     }
     if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
+    if (turntable && (gpus > 1 || adaptive >= 0.f)) { std::cerr << "Error: --turntable renders on one GPU, without --adaptive" << std::endl; return 2; }
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
     std::cout << model.face.size() << " " << model.normal.size() << " " << model.vertex.size() << std::endl;   // main.cpp:14
@@ -124,6 +128,29 @@ int main(int argc, char** argv) {
             renders[0] = new Render(model, o); renders[0]->seed = seed;
         } else renders[g] = new Render(*renders[0], int(g));
         if (!renders[g]->ok()) return 1;
+    }
+    // --turntable N: the camera moves, the scene stays -- Render::set_camera per frame, no rebuild, no upload
+    if (turntable) {
+        const CameraInfo base = model.camerainfo;
+        const double ul = std::sqrt(base.up.x * base.up.x + base.up.y * base.up.y + base.up.z * base.up.z);
+        if (!(ul > 0.0)) { std::cerr << "Error: --turntable needs a camera with an up vector" << std::endl; return 1; }
+        const double k[3] = {base.up.x / ul, base.up.y / ul, base.up.z / ul}, v[3] = {base.eye.x - base.lookat.x, base.eye.y - base.lookat.y, base.eye.z - base.lookat.z};
+        for (uint32_t f = 0; f < turntable; f++) {
+            const double a = 2.0 * 3.14159265358979323846 * double(f) / double(turntable), ca = std::cos(a), sa = std::sin(a);
+            const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2], kx[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
+            CameraInfo cam = base;                                           // Rodrigues: v cos a + (k x v) sin a + k (k . v)(1 - cos a)
+            cam.eye.x = base.lookat.x + v[0] * ca + kx[0] * sa + k[0] * kv * (1.0 - ca);
+            cam.eye.y = base.lookat.y + v[1] * ca + kx[1] * sa + k[1] * kv * (1.0 - ca);
+            cam.eye.z = base.lookat.z + v[2] * ca + kx[2] * sa + k[2] * kv * (1.0 - ca);
+            auto t0 = std::chrono::steady_clock::now();
+            if (!renders[0]->set_camera(scene, cam)) return 1;
+            renders[0]->render(scene, spp);
+            scene.sync();
+            std::cout << "frame: " << f << "    frame cost: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << "s\n";
+            scene.save_image(int(f), out + "_turn");
+        }
+        for (auto r : renders) delete r;
+        return 0;
     }
     std::vector<ncclComm_t> comms(gpus);
     if (gpus > 1) {
