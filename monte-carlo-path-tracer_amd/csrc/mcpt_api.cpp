@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -21,10 +22,35 @@ namespace {
 
 thread_local std::string g_err;
 
+// Owners of what a context holds on the device: move-only, each gives its handle back when it dies, so `delete` of a context frees all of it.
+template <class H, auto Free> struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned& operator=(Owned&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Owned() { if (h) (void)Free(h); }
+    operator H() const { return h; }
+    H* out() { return &h; }            // for the hip*Create / hipHostMalloc call that fills an empty owner
+};
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+template <class T> using Pinned = Owned<T*, hipHostFree>;
+
+// A device buffer.  `tally` (the context's mcpt_scene_info::device_bytes, or null for a buffer that is not counted) follows the allocation:
+// it grows by `bytes` when the buffer is allocated and shrinks when it is released, regrown or destroyed.
 struct DevBuf {
-    void* p = nullptr; size_t bytes = 0;
-    hipError_t alloc(size_t n) { bytes = n; return hipMalloc(&p, n ? n : 16); }
-    void free_() { if (p) (void)hipFree(p); p = nullptr; }
+    void* p = nullptr; size_t bytes = 0; uint64_t* tally = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes), tally(o.tally) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); std::swap(tally, o.tally); return *this; }
+    ~DevBuf() { release(); }
+    void release() { if (p) { (void)hipFree(p); if (tally) *tally -= bytes; } p = nullptr; bytes = 0; }
+    hipError_t alloc(size_t n, uint64_t* count = nullptr) {
+        release();
+        const hipError_t e = hipMalloc(&p, n ? n : 16);
+        if (e == hipSuccess) { bytes = n; tally = count; if (tally) *tally += n; } else p = nullptr;
+        return e;
+    }
 };
 
 }  // namespace
@@ -35,11 +61,11 @@ struct mcpt_ctx {
     DevScene dev{};
     DevBuf nodes, nodes8, tri_isect, tri_shade, tri_pos64, tri_face, mats, lights, light_pos64, texels, accum_own, counters;
     float4* accum = nullptr;           // bound accumulator (own or external)
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    Stream own_stream; hipStream_t stream = nullptr;   // the stream in use: own_stream, the caller's (mcpt_set_stream) or the default stream
     // HIP-event brackets of the render calls whose duration has not been read yet: a ring, so that a call does not have to wait for the one
     // before it (the reference's loop issues a call per sample); resolve_timing() reads the finished ones, oldest first
     static constexpr uint32_t TIMED = 16;
-    hipEvent_t ev0[TIMED] = {}, ev1[TIMED] = {};
+    Event ev0[TIMED], ev1[TIMED];
     uint32_t timed_head = 0, timed_tail = 0;      // calls [timed_tail, timed_head) are outstanding
     double last_kernel_ms = 0.0, total_kernel_ms = 0.0;
     uint64_t launches = 0;
@@ -55,11 +81,11 @@ struct mcpt_ctx {
         CompactBufs compact{};             // scratch of the end-of-job drain compaction (wavefront.h); capacity 0 = none (small pools)
         std::vector<DevBuf> pool_bufs;
         DevBuf ctl_buf, ovf_buf;
-        IterCtl* h_ctl = nullptr;          // pinned ring of control-block snapshots (termination check)
-        std::vector<hipEvent_t> chk_ev;
-        std::vector<hipEvent_t> k_ev;      // per-kernel event chain (only with detailed timing)
-        hipStream_t stream = nullptr;
-        hipEvent_t done_ev = nullptr;
+        Pinned<IterCtl> h_ctl;             // pinned ring of control-block snapshots (termination check)
+        std::vector<Event> chk_ev;
+        std::vector<Event> k_ev;           // per-kernel event chain (only with detailed timing)
+        Stream stream;
+        Event done_ev;
         uint64_t last_iterations = 0, last_timed = 0;
         // Known-length jobs (every item has its own slot and one sample, depth-limited: render_wavefront) are enqueued whole and NOT waited for:
         // the control-block snapshot taken after their last iteration is looked at later -- by the next call that drains the stream, or when the
@@ -69,7 +95,7 @@ struct mcpt_ctx {
         uint32_t ring_next = 0;            // next h_ctl / chk_ev slot this lane uses (jobs of either kind take them in turn)
     };
     std::vector<WfLane> lanes;
-    hipEvent_t fork_ev = nullptr;
+    Event fork_ev;
     WaveTuning tune{};
     uint32_t trace_grid = 0;
     uint32_t pool_cap = 1u << 23;       // most slots a sub-pipeline's pool may have (MCPT_WF_POOL_LOG2); pools are allocated on first use, sized to the job
@@ -82,19 +108,19 @@ struct mcpt_ctx {
     uint32_t wide_depth = 0;              // depth of the 8-wide tree the wavefront trace kernel walks
     std::vector<int32_t> h_tri_face;      // leaf order -> face index, fetched on first use by mcpt_probe_trace4
     // Scene::getPixelsColor every frame (main.cpp:26-33): the tonemapped film's device buffer and its pinned host image live as long as the
-    // context (allocated by the first tonemap call) -- no hipMalloc / hipMemset / hipFree per frame
-    DevBuf tone_dev; uint8_t* tone_host = nullptr;
+    // context (allocated by the first tonemap call) -- nothing is allocated, cleared or released per frame
+    DevBuf tone_dev; Pinned<uint8_t> tone_host;
     // Denoised preview (denoise.hip): first-hit features (2 float4 / pixel), allocated by the first mcpt_render_features; the filter's guide,
     // two ping-pong {irr, var} buffers and the denoised film (1 float4 / pixel each), allocated by the first mcpt_denoise
     DevBuf dn_feat, dn_guide, dn_iv0, dn_iv1, dn_out;
     bool dn_have_features = false, dn_have_out = false;
     // mcpt_render_tile_list: the caller's list, staged in pinned memory and copied to the device in stream order (tl_ev: that copy has been made,
     // the staging buffer may be written again); both grow to the longest list seen
-    DevBuf tl_dev; uint32_t* tl_host = nullptr; size_t tl_cap = 0; hipEvent_t tl_ev = nullptr; bool tl_pending = false;
+    DevBuf tl_dev; Pinned<uint32_t> tl_host; size_t tl_cap = 0; Event tl_ev; bool tl_pending = false;
     // Adaptive sampling (adaptive.hip), allocated by the first mcpt_render_adaptive: the half films H and O (1 float4 / pixel each), per tile
     // E_t, the active list and its flags, per error block counts and offsets, the totals and their pinned read-back
     DevBuf ad_h, ad_o, ad_err, ad_list, ad_flags, ad_counts, ad_offs, ad_tot;
-    AdTotals* ad_host = nullptr;
+    Pinned<AdTotals> ad_host;
     bool ad_have_err = false;
     // Live scenes (refit.hip).  MCPT_FLAG_DYNAMIC only: per triangle its vertex and normal indices (leaf order), the device copy of
     // the caller's vertices / normals and its pinned staging, per triangle and per 8-wide node an fp32 box (refit scratch), the binary nodes sorted
@@ -104,8 +130,8 @@ struct mcpt_ctx {
     DevBuf rf_idx, rf_vtx, rf_nrm, rf_tri_box, rf_node_box, rf_bin_order, rf_area;
     std::vector<uint32_t> rf_bin_level, rf_wide_level;      // [k], [k + 1]: the nodes of height k in rf_bin_order / the records of depth k in nodes8
     std::vector<uint8_t> rf_used_vertex;                    // a face uses this vertex: it is validated
-    double* rf_stage = nullptr; hipEvent_t rf_stage_ev = nullptr; bool rf_stage_pending = false;
-    hipEvent_t rf_ev0 = nullptr, rf_ev1 = nullptr; bool rf_timed = false;
+    Pinned<double> rf_stage; Event rf_stage_ev; bool rf_stage_pending = false;
+    Event rf_ev0, rf_ev1; bool rf_timed = false;
     uint32_t rf_updates = 0; double rf_last_ms = 0.0, rf_area0 = 0.0;
 };
 
@@ -115,39 +141,15 @@ mcpt_status fail(mcpt_status s, const std::string& msg) { g_err = msg; return s;
 mcpt_status hip_fail(hipError_t e, const char* what) { g_err = std::string(what) + ": " + hipGetErrorString(e); return MCPT_ERR_HIP; }
 #define HIP_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, #call); } while (0)
 
-template <class T>
-hipError_t upload(DevBuf& b, const std::vector<T>& v) {
-    hipError_t e = b.alloc(v.size() * sizeof(T));
-    if (e != hipSuccess) return e;
-    if (!v.empty()) e = hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e;
+template <class T> hipError_t upload(DevBuf& b, const std::vector<T>& v, uint64_t* tally) {
+    const hipError_t e = b.alloc(v.size() * sizeof(T), tally);
+    return e != hipSuccess || v.empty() ? e : hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
+// The device must be current while the members give their handles back.
 void destroy_ctx(mcpt_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    c->nodes.free_(); c->nodes8.free_(); c->tri_isect.free_(); c->tri_shade.free_(); c->tri_pos64.free_(); c->tri_face.free_();
-    c->mats.free_(); c->lights.free_(); c->light_pos64.free_(); c->texels.free_(); c->accum_own.free_(); c->counters.free_();
-    for (auto& L : c->lanes) {
-        for (auto& b : L.pool_bufs) b.free_();
-        L.ctl_buf.free_(); L.ovf_buf.free_();
-        if (L.h_ctl) (void)hipHostFree(L.h_ctl);
-        for (auto e : L.chk_ev) (void)hipEventDestroy(e);
-        for (auto e : L.k_ev) (void)hipEventDestroy(e);
-        if (L.done_ev) (void)hipEventDestroy(L.done_ev);
-        if (L.stream) (void)hipStreamDestroy(L.stream);
-    }
-    c->tone_dev.free_(); if (c->tone_host) (void)hipHostFree(c->tone_host);
-    c->dn_feat.free_(); c->dn_guide.free_(); c->dn_iv0.free_(); c->dn_iv1.free_(); c->dn_out.free_();
-    c->tl_dev.free_(); if (c->tl_host) (void)hipHostFree(c->tl_host); if (c->tl_ev) (void)hipEventDestroy(c->tl_ev);
-    for (DevBuf* b : {&c->ad_h, &c->ad_o, &c->ad_err, &c->ad_list, &c->ad_flags, &c->ad_counts, &c->ad_offs, &c->ad_tot}) b->free_();
-    if (c->ad_host) (void)hipHostFree(c->ad_host);
-    for (DevBuf* b : {&c->rf_idx, &c->rf_vtx, &c->rf_nrm, &c->rf_tri_box, &c->rf_node_box, &c->rf_bin_order, &c->rf_area}) b->free_();
-    if (c->rf_stage) (void)hipHostFree(c->rf_stage);
-    for (hipEvent_t ev : {c->rf_stage_ev, c->rf_ev0, c->rf_ev1}) if (ev) (void)hipEventDestroy(ev);
-    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
-    for (uint32_t i = 0; i < mcpt_ctx::TIMED; i++) { if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]); if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]); }
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
 
@@ -155,6 +157,48 @@ mcpt_status use(mcpt_ctx* c) {
     if (!c) return fail(MCPT_ERR_INVALID_ARG, "null context");
     HIP_TRY(hipSetDevice(c->device));
     return MCPT_OK;
+}
+
+mcpt_status check_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(MCPT_ERR_NO_DEVICE, "device ordinal out of range");
+    return MCPT_OK;
+}
+
+// The optional options struct of an entry point: absent = all defaults, present = exactly this library's layout.
+template <class O> mcpt_status read_opts(const O* opts, O& o, const char* fn, const char* type) {
+    std::memset(&o, 0, sizeof o); o.struct_size = sizeof o;
+    if (opts && opts->struct_size != sizeof(O)) return fail(MCPT_ERR_INVALID_ARG, std::string(fn) + ": opts->struct_size != sizeof(" + type + ")");
+    if (opts) o = *opts;
+    return MCPT_OK;
+}
+
+uint64_t film_tiles(const mcpt_ctx* c) { return uint64_t((c->width + 7) / 8) * uint64_t((c->height + 7) / 8); }   // 8 x 8 pixel tiles
+
+// leaf order -> face index on the host, fetched on first use (probes only)
+mcpt_status fetch_tri_face(mcpt_ctx* c) {
+    if (!c->h_tri_face.empty()) return MCPT_OK;
+    std::vector<int32_t> f(size_t(c->dev.n_tris));
+    HIP_TRY(hipMemcpy(f.data(), c->dev.tri_face, f.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    c->h_tri_face.swap(f);
+    return MCPT_OK;
+}
+
+// What a control-block snapshot taken after iteration `it` says about a job with n_shared shared work items.
+enum class JobState { Watchdog, Finished, NotFinished };
+const char* const WATCHDOG_MSG = "trace kernel watchdog: a wave did not finish its ray list (internal error)";
+JobState job_state(const IterCtl& s, uint32_t it, uint32_t n_shared) {
+    if (s.pad[WF_CTL_WATCHDOG]) return JobState::Watchdog;
+    for (uint32_t q = 0; q < WF_ITEM_SHARDS; q++) if (s.item_cursor[q].v < wf_shard_capacity(n_shared, q)) return JobState::NotFinished;
+    return s.any_active[it & 3] != 0 ? JobState::NotFinished : JobState::Finished;
+}
+
+// Has `ev` happened?  `block`: wait for it.
+hipError_t event_done(hipEvent_t ev, bool block, bool& done) {
+    const hipError_t e = block ? hipEventSynchronize(ev) : hipEventQuery(ev);
+    done = e == hipSuccess;
+    return e == hipErrorNotReady ? hipSuccess : e;
 }
 
 uint32_t env_u32(const char* name, uint32_t dflt) {
@@ -169,7 +213,6 @@ std::vector<double> to_local(const mcpt_ctx* c, const double* p, size_t n) {
     return v;
 }
 
-// scratch device buffer for probes
 // Device scratch of one probe / tonemap call.  The fills below go through the legacy default stream, the kernels that use the buffers
 // run on the context's stream, which is NON-BLOCKING (no implicit ordering with the default stream): hipMemset on device memory
 // returns before it has executed, so without the explicit wait a kernel could write its results first and have them zeroed afterwards
@@ -197,19 +240,17 @@ struct Scratch {
 // Everything of a context that is not the scene: streams, events, film, counters, the wavefront sub-pipelines, and the device pointers of
 // c->dev (the scene streams c->nodes ... c->texels are on the device already: uploaded by mcpt_create or copied by mcpt_clone_to_device).
 static mcpt_status finish_ctx(mcpt_ctx* c) {
-    hipError_t e = hipSuccess;
-    auto bail = [&](hipError_t he, const char* what) { return hip_fail(he, what); };
-    if ((e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
+    HIP_TRY(hipStreamCreateWithFlags(c->own_stream.out(), hipStreamNonBlocking));
     c->stream = c->own_stream;
-    for (uint32_t i = 0; i < mcpt_ctx::TIMED; i++) if ((e = hipEventCreate(&c->ev0[i])) != hipSuccess || (e = hipEventCreate(&c->ev1[i])) != hipSuccess) return bail(e, "hipEventCreate");
+    for (uint32_t i = 0; i < mcpt_ctx::TIMED; i++) { HIP_TRY(hipEventCreate(c->ev0[i].out())); HIP_TRY(hipEventCreate(c->ev1[i].out())); }
     const size_t accum_bytes = size_t(c->width) * c->height * sizeof(float4);
-    if ((e = c->accum_own.alloc(accum_bytes)) != hipSuccess) return bail(e, "alloc accumulator");
-    if ((e = hipMemset(c->accum_own.p, 0, accum_bytes)) != hipSuccess) return bail(e, "clear accumulator");
-    if ((e = c->counters.alloc(sizeof(DevCounters) * WF_COUNTER_REPLICAS)) != hipSuccess) return bail(e, "alloc counters");
-    if ((e = hipMemset(c->counters.p, 0, sizeof(DevCounters) * WF_COUNTER_REPLICAS)) != hipSuccess) return bail(e, "clear counters");
+    HIP_TRY(c->accum_own.alloc(accum_bytes, &c->info.device_bytes));
+    HIP_TRY(hipMemset(c->accum_own.p, 0, accum_bytes));
+    HIP_TRY(c->counters.alloc(sizeof(DevCounters) * WF_COUNTER_REPLICAS));
+    HIP_TRY(hipMemset(c->counters.p, 0, sizeof(DevCounters) * WF_COUNTER_REPLICAS));
     {   // ---- wavefront pool.  Tunables are developer knobs (environment), not part of the ABI.
         hipDeviceProp_t prop;
-        if ((e = hipGetDeviceProperties(&prop, c->device)) != hipSuccess) return bail(e, "hipGetDeviceProperties");
+        HIP_TRY(hipGetDeviceProperties(&prop, c->device));
         c->n_cus = prop.multiProcessorCount;
         c->pool_cap = 1u << std::min(26u, env_u32("MCPT_WF_POOL_LOG2", 23));
         c->pool_cap = env_u32("MCPT_WF_POOL_SLOTS", c->pool_cap) & ~uint32_t(16 * WF_SHADE_BLOCK - 1);   // (developer knob: any multiple of 4096 slots)
@@ -232,26 +273,25 @@ static mcpt_status finish_ctx(mcpt_ctx* c) {
             // speculative traversal: S-cornell 469 -> 450 ms; on the 4 M-triangle configuration, where the extra node visits are HBM
             // traffic, it is neutral within the noise (same box: 367 ms with, 371 ms without) -- on everywhere; MCPT_WF_PEND=0 turns it off
             c->tune.pend_cap = env_u32("MCPT_WF_PEND", 48u);
-            if ((e = hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
+            HIP_TRY(hipEventCreateWithFlags(c->fork_ev.out(), hipEventDisableTiming));
             c->lanes.resize(n_lanes);
             for (auto& L : c->lanes) {
                 L.pool.P = 0;                                             // allocated by ensure_pool() when the first job arrives
-                if ((e = L.ctl_buf.alloc(sizeof(IterCtl))) != hipSuccess) return bail(e, "alloc IterCtl");
-                if ((e = hipHostMalloc((void**)&L.h_ctl, 8 * sizeof(IterCtl), hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc");
+                HIP_TRY(L.ctl_buf.alloc(sizeof(IterCtl)));
+                HIP_TRY(hipHostMalloc((void**)L.h_ctl.out(), 8 * sizeof(IterCtl), hipHostMallocDefault));
                 L.chk_ev.resize(8);
-                for (auto& ev : L.chk_ev) if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-                if ((e = hipEventCreateWithFlags(&L.done_ev, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-                if ((e = hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
+                for (auto& ev : L.chk_ev) HIP_TRY(hipEventCreateWithFlags(ev.out(), hipEventDisableTiming));
+                HIP_TRY(hipEventCreateWithFlags(L.done_ev.out(), hipEventDisableTiming));
+                HIP_TRY(hipStreamCreateWithFlags(L.stream.out(), hipStreamNonBlocking));
                 // the global overflow area of the traversal stack is sized from the wide tree's depth (2 x depth + 3 entries of 8 B per trace lane): a
                 // pathologically deep device-built tree (depth in the hundreds) would ask for a GB per sub-pipeline -- refuse instead of allocating it
                 const size_t ovf_bytes = size_t(c->trace_grid) * wf_trace_block_threads() * wf_trace_overflow_bytes_per_lane(c->wide_depth);
                 if (ovf_bytes > (size_t(512) << 20)) return fail(MCPT_ERR_BVH_DEPTH, "wide BVH of depth " + std::to_string(c->wide_depth) + " needs a traversal-stack overflow area of " + std::to_string(ovf_bytes >> 20) + " MB per sub-pipeline: build the tree with the host builder (no MCPT_FLAG_GPU_BVH_BUILD)");
-                if ((e = L.ovf_buf.alloc(ovf_bytes)) != hipSuccess)
-                    return bail(e, "alloc stack overflow area");
+                HIP_TRY(L.ovf_buf.alloc(ovf_bytes));
             }
         }
     }
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return bail(e, "sync after upload");
+    HIP_TRY(hipDeviceSynchronize());
     c->accum = static_cast<float4*>(c->accum_own.p);
     DevScene& d = c->dev;
     d.nodes = static_cast<const float4*>(c->nodes.p); d.nodes8 = static_cast<const float4*>(c->nodes8.p);
@@ -259,8 +299,6 @@ static mcpt_status finish_ctx(mcpt_ctx* c) {
     d.tri_shade = static_cast<const float4*>(c->tri_shade.p); d.tri_pos64 = static_cast<const double*>(c->tri_pos64.p);
     d.tri_face = static_cast<const int32_t*>(c->tri_face.p); d.mats = static_cast<const DevMaterial*>(c->mats.p);
     d.lights = static_cast<const DevLight*>(c->lights.p); d.light_pos64 = static_cast<const double*>(c->light_pos64.p); d.texels = static_cast<const float4*>(c->texels.p);
-    c->info.device_bytes = c->nodes.bytes + c->nodes8.bytes + c->tri_isect.bytes + c->tri_shade.bytes + c->tri_pos64.bytes + c->tri_face.bytes +
-                           c->mats.bytes + c->lights.bytes + c->light_pos64.bytes + c->texels.bytes + accum_bytes;
     return MCPT_OK;
 }
 
@@ -277,69 +315,30 @@ static void fill_wide_info(mcpt_scene_info& in, const HostScene& hs) {
 
 
 // ------------------------------------------------------------------------------------------------ live scenes: set-up
-// Sum of the dequantised child-box areas of the context's 8-wide tree, as it is on the device when the stream reaches this point.  Synchronises.
-static mcpt_status rf_wide_area(mcpt_ctx* c, double& out) {
-    const uint32_t n8 = uint32_t(c->dev.n_nodes8), nb = rf_area_blocks(n8);
-    HIP_TRY(launch_rf_wide_area(c->dev.nodes8, n8, static_cast<double*>(c->rf_area.p), c->stream));
-    std::vector<double> part(nb);
-    HIP_TRY(hipMemcpyAsync(part.data(), c->rf_area.p, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+// The per-block partial sums the last launch_rf_wide_area left in rf_area, added up.  The caller has synchronised the stream.
+static mcpt_status rf_read_area(mcpt_ctx* c, double& out) {
+    std::vector<double> part(rf_area_blocks(uint32_t(c->dev.n_nodes8)));
+    HIP_TRY(hipMemcpy(part.data(), c->rf_area.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
     out = 0.0;
     for (double v : part) out += v;
     return MCPT_OK;
 }
-// The level structure of both trees from their host records.  Binary tree: the renumbering puts every parent before its children, so one
-// descending pass gives the heights (0 = both children are leaves); the nodes are then sorted by height.  8-wide tree: build_bvh8 and
-// gpu_collapse_bvh8 number the records breadth-first, level by level -- a level's inner children are the next level, consecutively.
-static bool rf_levels(const std::vector<f4h>& n2, const std::vector<f4h>& n8, std::vector<uint32_t>& bin_order, std::vector<uint32_t>& bin_level,
-                      std::vector<uint32_t>& wide_level, std::string& err) {
-    const size_t N = n2.size() / 4, N8 = n8.size() / 5;
-    auto as_i = [](float f) { int v; std::memcpy(&v, &f, 4); return v; };
-    std::vector<uint32_t> height(N, 0);
-    uint32_t top = 0;
-    for (size_t n = N; n-- > 0;) {
-        uint32_t h = 0;
-        for (int k = 0; k < 2; k++) {
-            const int c = as_i(k == 0 ? n2[4 * n + 3].x : n2[4 * n + 3].y);
-            if (c < 0) continue;
-            if (size_t(c) <= n || size_t(c) >= N) { err = "binary tree is not numbered parents first (internal error)"; return false; }
-            h = std::max(h, height[size_t(c)] + 1);
-        }
-        height[n] = h; top = std::max(top, h);
-    }
-    bin_level.assign(size_t(top) + 2, 0);
-    for (size_t n = 0; n < N; n++) bin_level[height[n] + 1]++;
-    for (size_t k = 1; k < bin_level.size(); k++) bin_level[k] += bin_level[k - 1];
-    bin_order.resize(N);
-    { std::vector<uint32_t> at(bin_level.begin(), bin_level.end() - 1); for (size_t n = 0; n < N; n++) bin_order[at[height[n]]++] = uint32_t(n); }
-    wide_level.clear();
-    size_t begin = 0, end = 1;
-    while (begin < end) {
-        wide_level.push_back(uint32_t(begin));
-        size_t kids = 0;
-        for (size_t r = begin; r < end; r++) {
-            uint32_t masks, base; std::memcpy(&masks, &n8[5 * r + 1].w, 4); std::memcpy(&base, &n8[5 * r + 1].x, 4);
-            const uint32_t ni = uint32_t(__builtin_popcount(masks & 0xffu));
-            if (ni && base != end + kids) { err = "8-wide tree is not numbered level by level (internal error)"; return false; }
-            kids += ni;
-        }
-        begin = end; end += kids;
-        if (end > N8) { err = "8-wide tree: child link out of range (internal error)"; return false; }
-    }
-    wide_level.push_back(uint32_t(begin));
-    if (begin != N8) { err = "8-wide tree: unreachable records (internal error)"; return false; }
-    return true;
+// Sum of the dequantised child-box areas of the context's 8-wide tree, as it is on the device when the stream reaches this point.  Synchronises.
+static mcpt_status rf_wide_area(mcpt_ctx* c, double& out) {
+    HIP_TRY(launch_rf_wide_area(c->dev.nodes8, uint32_t(c->dev.n_nodes8), static_cast<double*>(c->rf_area.p), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return rf_read_area(c, out);
 }
 static mcpt_status rf_alloc(mcpt_ctx* c) {
     const size_t nt = size_t(c->dev.n_tris), n8 = size_t(c->dev.n_nodes8), n2 = size_t(c->dev.n_nodes);
-    HIP_TRY(c->rf_idx.alloc(nt * 6 * sizeof(int32_t))); HIP_TRY(c->rf_vtx.alloc(size_t(c->rf_n_vertex) * 3 * sizeof(double)));
-    HIP_TRY(c->rf_nrm.alloc(size_t(c->rf_n_normal) * 3 * sizeof(double))); HIP_TRY(c->rf_tri_box.alloc(nt * 6 * sizeof(float)));
-    HIP_TRY(c->rf_node_box.alloc(n8 * 6 * sizeof(float))); HIP_TRY(c->rf_bin_order.alloc(n2 * sizeof(uint32_t)));
-    HIP_TRY(c->rf_area.alloc(size_t(rf_area_blocks(uint32_t(n8))) * sizeof(double)));
-    HIP_TRY(hipHostMalloc((void**)&c->rf_stage, (size_t(c->rf_n_vertex) + c->rf_n_normal) * 3 * sizeof(double) + 16, hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(&c->rf_stage_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventCreate(&c->rf_ev0)); HIP_TRY(hipEventCreate(&c->rf_ev1));
-    for (DevBuf* b : {&c->rf_idx, &c->rf_vtx, &c->rf_nrm, &c->rf_tri_box, &c->rf_node_box, &c->rf_bin_order, &c->rf_area}) c->info.device_bytes += b->bytes;
+    uint64_t* tally = &c->info.device_bytes;
+    HIP_TRY(c->rf_idx.alloc(nt * 6 * sizeof(int32_t), tally)); HIP_TRY(c->rf_vtx.alloc(size_t(c->rf_n_vertex) * 3 * sizeof(double), tally));
+    HIP_TRY(c->rf_nrm.alloc(size_t(c->rf_n_normal) * 3 * sizeof(double), tally)); HIP_TRY(c->rf_tri_box.alloc(nt * 6 * sizeof(float), tally));
+    HIP_TRY(c->rf_node_box.alloc(n8 * 6 * sizeof(float), tally)); HIP_TRY(c->rf_bin_order.alloc(n2 * sizeof(uint32_t), tally));
+    HIP_TRY(c->rf_area.alloc(size_t(rf_area_blocks(uint32_t(n8))) * sizeof(double), tally));
+    HIP_TRY(hipHostMalloc((void**)c->rf_stage.out(), (size_t(c->rf_n_vertex) + c->rf_n_normal) * 3 * sizeof(double) + 16, hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(c->rf_stage_ev.out(), hipEventDisableTiming));
+    HIP_TRY(hipEventCreate(c->rf_ev0.out())); HIP_TRY(hipEventCreate(c->rf_ev1.out()));
     c->dynamic = true;
     return MCPT_OK;
 }
@@ -404,18 +403,10 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
     const bool use_wavefront = [&]() { const char* pipe = std::getenv("MCPT_PIPELINE"); return !(pipe && std::string(pipe) == "mega") && o.integrator == MCPT_INTEGRATOR_MIS; }();
     if ((o.flags & MCPT_FLAG_REFERENCE_TIE_ORDER) && !use_wavefront)
         return fail(MCPT_ERR_UNSUPPORTED, "MCPT_FLAG_REFERENCE_TIE_ORDER needs the wavefront pipeline (MCPT_INTEGRATOR_MIS, no MCPT_PIPELINE=mega): the binary-tree kernels have no tie rule");
-    int ndev = 0;
-    hipError_t e = hipSuccess;
-    auto check_device = [&]() -> mcpt_status {
-        e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess || ndev <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-        if (o.device < 0 || o.device >= ndev) return fail(MCPT_ERR_NO_DEVICE, "device ordinal out of range");
-        return MCPT_OK;
-    };
     mcpt_status st;
     if (o.flags & MCPT_FLAG_GPU_BVH_BUILD) {                              // the tree is built on the device the context will render on
-        if ((st = check_device()) != MCPT_OK) return st;
-        if ((e = hipSetDevice(o.device)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+        if ((st = check_device(o.device)) != MCPT_OK) return st;
+        HIP_TRY(hipSetDevice(o.device));
         // An agglomerative (PLOC) tree over millions of triangles can be deeper than the binary-tree kernels' 64-entry stack.  Only the
         // cross-check kernels (megakernel, recursive integrator, mcpt_probe_trace) walk the binary tree; the wavefront pipeline walks
         // the wide collapse of it, whose stack is sized from its own depth -- so a wavefront-only context keeps the deep tree.
@@ -432,28 +423,23 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
     } else {
         st = build_host_scene(scene, hs, err);
         if (st != MCPT_OK) return fail(st, err);
-        if ((st = check_device()) != MCPT_OK) return st;
+        if ((st = check_device(o.device)) != MCPT_OK) return st;
     }
 
     // the 8-wide trace kernel addresses node and triangle records with 32-bit byte offsets
     if ((hs.nodes8.size() * sizeof(f4h) >= (1ull << 32) || hs.tri_isect.size() * sizeof(f4h) >= (1ull << 32)))
         return fail(MCPT_ERR_UNSUPPORTED, "scene too large for the 8-wide traversal kernel (more than 89 M triangles)");
-    mcpt_ctx* c = new mcpt_ctx();
+    std::unique_ptr<mcpt_ctx, void (*)(mcpt_ctx*)> guard(new mcpt_ctx(), destroy_ctx);   // a context that is not handed out is destroyed
+    mcpt_ctx* c = guard.get();
     c->device = o.device; c->opts = o; c->width = scene->camera.width; c->height = scene->camera.height;
     c->wide_depth = hs.bvh8_depth; c->binary_ok = hs.binary_ok; c->use_wavefront = use_wavefront;
-    auto bail = [&](hipError_t he, const char* what) { mcpt_status s = hip_fail(he, what); destroy_ctx(c); return s; };
-    if ((e = hipSetDevice(c->device)) != hipSuccess) return bail(e, "hipSetDevice");
+    HIP_TRY(hipSetDevice(c->device));
     auto t0 = std::chrono::steady_clock::now();
-    if ((e = upload(c->nodes, hs.nodes)) != hipSuccess) return bail(e, "upload nodes");
-    if ((e = upload(c->nodes8, hs.nodes8)) != hipSuccess) return bail(e, "upload nodes8");
-    if ((e = upload(c->tri_isect, hs.tri_isect)) != hipSuccess) return bail(e, "upload tri_isect");
-    if ((e = upload(c->tri_shade, hs.tri_shade)) != hipSuccess) return bail(e, "upload tri_shade");
-    if ((e = upload(c->tri_pos64, hs.tri_pos64)) != hipSuccess) return bail(e, "upload tri_pos64");
-    if ((e = upload(c->tri_face, hs.tri_face)) != hipSuccess) return bail(e, "upload tri_face");
-    if ((e = upload(c->mats, hs.mats)) != hipSuccess) return bail(e, "upload materials");
-    if ((e = upload(c->lights, hs.lights)) != hipSuccess) return bail(e, "upload lights");
-    if ((e = upload(c->light_pos64, hs.light_pos64)) != hipSuccess) return bail(e, "upload light corners");
-    if ((e = upload(c->texels, hs.texels)) != hipSuccess) return bail(e, "upload texels");
+    uint64_t* tally = &c->info.device_bytes;
+    HIP_TRY(upload(c->nodes, hs.nodes, tally)); HIP_TRY(upload(c->nodes8, hs.nodes8, tally)); HIP_TRY(upload(c->tri_isect, hs.tri_isect, tally));
+    HIP_TRY(upload(c->tri_shade, hs.tri_shade, tally)); HIP_TRY(upload(c->tri_pos64, hs.tri_pos64, tally)); HIP_TRY(upload(c->tri_face, hs.tri_face, tally));
+    HIP_TRY(upload(c->mats, hs.mats, tally)); HIP_TRY(upload(c->lights, hs.lights, tally)); HIP_TRY(upload(c->light_pos64, hs.light_pos64, tally));
+    HIP_TRY(upload(c->texels, hs.texels, tally));
     DevScene& d = c->dev;
     d.n_nodes8 = int32_t(hs.nodes8.size() / 5);
     d.cam = hs.cam;
@@ -464,11 +450,10 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
     in.bvh_depth = hs.bvh_depth; in.max_leaf = hs.max_leaf; in.width = uint32_t(c->width); in.height = uint32_t(c->height);
     in.bvh_build_ms = hs.bvh_build_ms;
     fill_wide_info(in, hs);
-    const mcpt_status fs = finish_ctx(c);
-    if (fs != MCPT_OK) { destroy_ctx(c); return fs; }
-    if (o.flags & MCPT_FLAG_DYNAMIC) { const mcpt_status ds = rf_setup(c, hs, scene); if (ds != MCPT_OK) { destroy_ctx(c); return ds; } }
+    if ((st = finish_ctx(c)) != MCPT_OK) return st;
+    if ((o.flags & MCPT_FLAG_DYNAMIC) && (st = rf_setup(c, hs, scene)) != MCPT_OK) return st;
     in.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *out_ctx = c;
+    *out_ctx = guard.release();
     return MCPT_OK;
 }
 
@@ -477,30 +462,26 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
 mcpt_status mcpt_clone_to_device(mcpt_ctx* src, int32_t device, mcpt_ctx** out_ctx) {
     if (!src || !out_ctx) return fail(MCPT_ERR_INVALID_ARG, "mcpt_clone_to_device: null argument");
     *out_ctx = nullptr;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(MCPT_ERR_NO_DEVICE, "device ordinal out of range");
-    mcpt_status st = use(src); if (st != MCPT_OK) return st;
+    mcpt_status st = check_device(device); if (st != MCPT_OK) return st;
+    st = use(src); if (st != MCPT_OK) return st;
     HIP_TRY(hipStreamSynchronize(src->stream));
-    mcpt_ctx* c = new mcpt_ctx();
+    std::unique_ptr<mcpt_ctx, void (*)(mcpt_ctx*)> guard(new mcpt_ctx(), destroy_ctx);
+    mcpt_ctx* c = guard.get();
     c->device = device; c->opts = src->opts; c->opts.device = device; c->width = src->width; c->height = src->height;
     c->wide_depth = src->wide_depth; c->binary_ok = src->binary_ok; c->use_wavefront = src->use_wavefront;
-    c->dev = src->dev; c->info = src->info; c->info.bvh_build_ms = 0.0;
-    auto bail = [&](hipError_t he, const char* what) { mcpt_status s = hip_fail(he, what); destroy_ctx(c); return s; };
-    if ((e = hipSetDevice(device)) != hipSuccess) return bail(e, "hipSetDevice");
+    c->dev = src->dev; c->info = src->info; c->info.bvh_build_ms = 0.0; c->info.device_bytes = 0;   // (counts this context's own allocations)
+    HIP_TRY(hipSetDevice(device));
     auto t0 = std::chrono::steady_clock::now();
     DevBuf* from[10] = {&src->nodes, &src->nodes8, &src->tri_isect, &src->tri_shade, &src->tri_pos64, &src->tri_face, &src->mats, &src->lights, &src->light_pos64, &src->texels};
     DevBuf* to[10] = {&c->nodes, &c->nodes8, &c->tri_isect, &c->tri_shade, &c->tri_pos64, &c->tri_face, &c->mats, &c->lights, &c->light_pos64, &c->texels};
     for (int i = 0; i < 10; i++) {
-        if ((e = to[i]->alloc(from[i]->bytes)) != hipSuccess) return bail(e, "alloc scene stream");
-        if (from[i]->bytes && (e = hipMemcpyPeer(to[i]->p, device, from[i]->p, src->device, from[i]->bytes)) != hipSuccess) return bail(e, "hipMemcpyPeer");
+        HIP_TRY(to[i]->alloc(from[i]->bytes, &c->info.device_bytes));
+        if (from[i]->bytes) HIP_TRY(hipMemcpyPeer(to[i]->p, device, from[i]->p, src->device, from[i]->bytes));
     }
-    const mcpt_status fs = finish_ctx(c);
-    if (fs != MCPT_OK) { destroy_ctx(c); return fs; }
-    if (src->dynamic) { const mcpt_status ds = rf_clone(c, src); if (ds != MCPT_OK) { destroy_ctx(c); return ds; } }
+    if ((st = finish_ctx(c)) != MCPT_OK) return st;
+    if (src->dynamic && (st = rf_clone(c, src)) != MCPT_OK) return st;
     c->info.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *out_ctx = c;
+    *out_ctx = guard.release();
     return MCPT_OK;
 }
 
@@ -524,12 +505,8 @@ static mcpt_status check_pending_jobs(mcpt_ctx* ctx);
 static mcpt_status resolve_timing(mcpt_ctx* c, bool block = true) {
     while (c->timed_tail != c->timed_head) {
         const uint32_t k = c->timed_tail % mcpt_ctx::TIMED;
-        if (block) HIP_TRY(hipEventSynchronize(c->ev1[k]));
-        else {
-            const hipError_t q = hipEventQuery(c->ev1[k]);
-            if (q == hipErrorNotReady) break;
-            if (q != hipSuccess) return hip_fail(q, "hipEventQuery");
-        }
+        bool done; HIP_TRY(event_done(c->ev1[k], block, done));
+        if (!done) break;
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, c->ev0[k], c->ev1[k]));
         c->last_kernel_ms = ms; c->total_kernel_ms += ms; c->timed_tail++;
@@ -560,26 +537,27 @@ static mcpt_status resolve_timing(mcpt_ctx* c, bool block = true) {
 static mcpt_status ensure_pool(mcpt_ctx* ctx, mcpt_ctx::WfLane& L, uint32_t P) {
     if (L.pool.P >= P) return MCPT_OK;
     HIP_TRY(hipStreamSynchronize(L.stream)); HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (auto& b : L.pool_bufs) { ctx->info.device_bytes -= b.bytes; b.free_(); }
+    L.pool_bufs.clear(); L.pool.P = 0;                                   // (the old buffers are freed before the new ones are asked for)
     // the drain compaction's scratch: half a pool of the seven records a live slot carries from one iteration to the next (+ 4096 slots of rounding)
     const bool want_compact = P >= 4 * WF_COMPACT_MIN_SLOTS && !(ctx->opts.flags & MCPT_FLAG_DETERMINISTIC) && env_u32("MCPT_WF_COMPACT", 1) != 0;
     const uint32_t eighths = std::max(1u, std::min(7u, env_u32("MCPT_WF_COMPACT_EIGHTHS", 4)));      // compact when at most this many eighths of the swept slots are alive
-    const uint32_t ccap = want_compact ? uint32_t(uint64_t(P) * eighths / 8) + 4096 : 0;
+    const uint32_t ccap = want_compact ? uint32_t(uint64_t(P) * eighths / 8) + 4096 : 0, nb = P / WF_SHADE_BLOCK;
     L.compact = CompactBufs{}; L.compact.capacity = ccap; L.compact.eighths = eighths;
-    L.pool_bufs.clear(); L.pool_bufs.resize(22);
-    void** dst[22] = {(void**)&L.pool.ray_o, (void**)&L.pool.ray_d, (void**)&L.pool.hit, (void**)&L.pool.sq_d, (void**)&L.pool.nee,
-                      (void**)&L.pool.L, (void**)&L.pool.beta, (void**)&L.pool.sum, (void**)&L.pool.ids, (void**)&L.pool.shadow_queue,
-                      (void**)&L.pool.shadow_count, (void**)&L.pool.sq_o, (void**)&L.pool.block_items, (void**)&L.pool.live_cnt,
-                      (void**)&L.compact.beta, (void**)&L.compact.L, (void**)&L.compact.ray_d, (void**)&L.compact.ray_o, (void**)&L.compact.hit, (void**)&L.compact.nee,
-                      (void**)&L.compact.ids, (void**)&L.compact.dst_off};
-    for (int i = 0; i < 22; i++) {
-        const size_t bytes = i == 9 ? size_t(P) * sizeof(uint32_t) : (i == 10 || i == 13 || i == 21) ? size_t(P / WF_SHADE_BLOCK) * sizeof(uint32_t) : i == 12 ? size_t(P / WF_SHADE_BLOCK) * sizeof(uint2)
-                           : i == 20 ? size_t(ccap) * sizeof(uint2) : (i >= 14 && i <= 19) ? size_t(ccap) * 16 : size_t(P) * 16;
-        hipError_t e = L.pool_bufs[i].alloc(bytes);
-        if (e != hipSuccess) { L.pool.P = 0; return hip_fail(e, "alloc path pool"); }
-        if ((e = hipMemset(L.pool_bufs[i].p, 0, bytes)) != hipSuccess) { L.pool.P = 0; return hip_fail(e, "clear path pool"); }
-        *dst[i] = L.pool_bufs[i].p;
-        ctx->info.device_bytes += bytes;
+    PathPool& pl = L.pool; CompactBufs& cb = L.compact;
+    // one row per buffer: the field it fills (whose type gives the element size) and its element count -- per slot, per shade block or per scratch slot
+    struct Row { void** field; size_t elem; uint32_t count; };
+    auto row = [](auto*& field, uint32_t count) { return Row{(void**)&field, sizeof(*field), count}; };
+    const Row rows[] = {
+        row(pl.ray_o, P), row(pl.ray_d, P), row(pl.hit, P), row(pl.sq_d, P), row(pl.nee, P), row(pl.L, P), row(pl.beta, P), row(pl.sum, P), row(pl.ids, P),
+        row(pl.shadow_queue, P), row(pl.shadow_count, nb), row(pl.sq_o, P), row(pl.block_items, nb), row(pl.live_cnt, nb),
+        row(cb.beta, ccap), row(cb.L, ccap), row(cb.ray_d, ccap), row(cb.ray_o, ccap), row(cb.hit, ccap), row(cb.nee, ccap), row(cb.ids, ccap), row(cb.dst_off, nb)};
+    for (const Row& r : rows) {
+        const size_t bytes = size_t(r.count) * r.elem;
+        DevBuf b;
+        HIP_TRY(b.alloc(bytes, &ctx->info.device_bytes));
+        HIP_TRY(hipMemset(b.p, 0, bytes));
+        *r.field = b.p;
+        L.pool_bufs.push_back(std::move(b));
     }
     HIP_TRY(hipStreamSynchronize(nullptr));                              // (the fills ran on the default stream)
     L.pool.P = P;
@@ -592,18 +570,12 @@ static mcpt_status ensure_pool(mcpt_ctx* ctx, mcpt_ctx::WfLane& L, uint32_t P) {
 static mcpt_status check_lane_verdicts(mcpt_ctx::WfLane& L, bool block) {
     while (!L.verdicts.empty()) {
         const mcpt_ctx::WfLane::Verdict v = L.verdicts.front();
-        if (block) HIP_TRY(hipEventSynchronize(L.chk_ev[v.ring_slot]));
-        else {
-            const hipError_t q = hipEventQuery(L.chk_ev[v.ring_slot]);
-            if (q == hipErrorNotReady) break;
-            if (q != hipSuccess) return hip_fail(q, "hipEventQuery");
-        }
+        bool done; HIP_TRY(event_done(L.chk_ev[v.ring_slot], block, done));
+        if (!done) break;
         L.verdicts.erase(L.verdicts.begin());
-        const IterCtl& s = L.h_ctl[v.ring_slot];
-        if (s.pad[0]) return fail(MCPT_ERR_HIP, "trace kernel watchdog: a wave did not finish its ray list (internal error)");
-        bool items_left = false;
-        for (uint32_t q = 0; q < WF_ITEM_SHARDS; q++) items_left |= s.item_cursor[q].v < wf_shard_capacity(v.n_shared, q);
-        if (s.any_active[v.it & 3] != 0 || items_left) return fail(MCPT_ERR_HIP, "a known-length job did not finish within its iteration bound (internal error)");
+        const JobState js = job_state(L.h_ctl[v.ring_slot], v.it, v.n_shared);
+        if (js == JobState::Watchdog) return fail(MCPT_ERR_HIP, WATCHDOG_MSG);
+        if (js != JobState::Finished) return fail(MCPT_ERR_HIP, "a known-length job did not finish within its iteration bound (internal error)");
     }
     return MCPT_OK;
 }
@@ -701,33 +673,29 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, RenderParams& p0, float4* acc
     }
     auto k_event = [&](mcpt_ctx::WfLane& L, Run& r, bool timed) -> hipError_t {
         if (!timed) return hipSuccess;
-        if (r.kev == L.k_ev.size()) { hipEvent_t ev; hipError_t e = hipEventCreate(&ev); if (e != hipSuccess) return e; L.k_ev.push_back(ev); }
+        if (r.kev == L.k_ev.size()) { Event ev; hipError_t e = hipEventCreate(ev.out()); if (e != hipSuccess) return e; L.k_ev.push_back(std::move(ev)); }
         return hipEventRecord(L.k_ev[r.kev++], L.stream);
     };
     // consume finished control-block snapshots of one sub-pipeline; `block` waits for the oldest one
     auto poll = [&](mcpt_ctx::WfLane& L, Run& r, bool block) -> mcpt_status {
         while (r.seen < r.issued) {
             const uint32_t k = r.seen % RING;
-            if (block) { HIP_TRY(hipEventSynchronize(L.chk_ev[k])); block = false; }
-            else {
-                hipError_t q = hipEventQuery(L.chk_ev[k]);
-                if (q == hipErrorNotReady) break;
-                if (q != hipSuccess) return hip_fail(q, "hipEventQuery");
-            }
+            bool done; HIP_TRY(event_done(L.chk_ev[k], block, done));
+            if (!done) break;
+            block = false;
             const IterCtl& s = L.h_ctl[k];
             const uint32_t it_of = r.snap_it[k];                           // snapshot taken after iteration it_of
             if (debug && (r.seen < 40 || s.pad[WF_CTL_P_ACTIVE]))
                 fprintf(stderr, "[wf] it=%u active=%u head=%u cursor0=%u/%u swept=%u live@compaction=%u compactions=%u\n", it_of, s.any_active[it_of & 3],
                         s.trace_head[it_of & 3], s.item_cursor[0].v, wf_shard_capacity(r.n_shared, 0), s.pad[WF_CTL_P_ACTIVE], s.pad[WF_CTL_LIVE], s.pad[WF_CTL_COMPACTIONS]);
-            if (s.pad[0]) return fail(MCPT_ERR_HIP, "trace kernel watchdog: a wave did not finish its ray list (internal error)");
-            bool items_left = false;
-            for (uint32_t q = 0; q < WF_ITEM_SHARDS; q++) items_left |= s.item_cursor[q].v < wf_shard_capacity(r.n_shared, q);
-            if (s.any_active[it_of & 3] == 0 && !items_left) r.done = true;
+            const JobState js = job_state(s, it_of, r.n_shared);
+            if (js == JobState::Watchdog) return fail(MCPT_ERR_HIP, WATCHDOG_MSG);
+            if (js == JobState::Finished) r.done = true;
             // the compaction launches start as soon as the SHARED cursors move at all: a block turns to them when its private range (90 % of the items) is
             // used up, i.e. in the last tenth of the job -- the host reads snapshots 4 - 8 iterations late, and a drain lasts about ten; the plan kernel
             // itself waits until every item has been handed out
             if (small_job && s.pad[WF_CTL_P_ACTIVE] != 0u && s.pad[WF_CTL_P_ACTIVE] <= small_job) r.grid = shared_grid;   // (the compacted sweep of a draining job)
-            if (!r.drain) { uint64_t moved = 0; for (uint32_t q = 0; q < WF_ITEM_SHARDS; q++) moved += s.item_cursor[q].v; if (moved != 0 || !items_left) r.drain = true; }
+            if (!r.drain) { uint64_t moved = 0; for (uint32_t q = 0; q < WF_ITEM_SHARDS; q++) moved += s.item_cursor[q].v; if (moved != 0) r.drain = true; }   // (a job has at least one shared item: none left => moved)
             r.seen++;
         }
         return MCPT_OK;
@@ -784,6 +752,19 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, RenderParams& p0, float4* acc
     return MCPT_OK;
 }
 
+// The bracket of a timed call: an event pair of the ring around its stream work, and the call counts as a launch.  Durations of earlier calls: read what
+// has finished; wait only when the ring is full -- or when per-kernel timing is on, whose sampled kernel events belong to one call at a time.
+static mcpt_status timed_begin(mcpt_ctx* ctx) {
+    mcpt_status st = resolve_timing(ctx, ctx->time_kernels != 0 || ctx->timed_head - ctx->timed_tail >= mcpt_ctx::TIMED - 1); if (st != MCPT_OK) return st;
+    HIP_TRY(hipEventRecord(ctx->ev0[ctx->timed_head % mcpt_ctx::TIMED], ctx->stream));
+    return MCPT_OK;
+}
+static mcpt_status timed_end(mcpt_ctx* ctx) {
+    HIP_TRY(hipEventRecord(ctx->ev1[ctx->timed_head % mcpt_ctx::TIMED], ctx->stream));
+    ctx->timed_head++; ctx->launches++;
+    return MCPT_OK;
+}
+
 mcpt_status mcpt_render(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample) { return mcpt_render_tiles(ctx, spp, seed, first_sample, 1u, 0u); }
 
 // One render call: `spp` samples of the tiles (tile_mod, tile_rem) selects -- of the tile numbers themselves, or, with a device list `list` of
@@ -794,14 +775,12 @@ static mcpt_status render_call(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint3
     if (spp == 0) return MCPT_OK;
     if (!ctx->use_wavefront && !ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the megakernel's traversal stack");
     mcpt_status st;
-    // durations of earlier calls: read what has finished; wait only when the ring of event pairs is full -- or when per-kernel timing is on,
-    // whose sampled kernel events belong to one call at a time
-    if (timed) { st = resolve_timing(ctx, ctx->time_kernels != 0 || ctx->timed_head - ctx->timed_tail >= mcpt_ctx::TIMED - 1); if (st != MCPT_OK) return st; }
+    if (timed) { st = timed_begin(ctx); if (st != MCPT_OK) return st; }
     RenderParams p; std::memset(&p, 0, sizeof p);
     p.spp = spp; p.first_sample = first_sample;
     p.tiles_x = uint32_t((ctx->width + 7) / 8); p.tiles_y = uint32_t((ctx->height + 7) / 8);
     p.tile_mod = tile_mod; p.tile_rem = tile_rem; p.tile_list = list;
-    {   const uint64_t all = list ? uint64_t(n_list) : uint64_t(p.tiles_x) * p.tiles_y;
+    {   const uint64_t all = list ? uint64_t(n_list) : film_tiles(ctx);
         p.n_owned = all > tile_rem ? uint32_t((all - tile_rem + tile_mod - 1) / tile_mod) : 0u; }
     if (p.n_owned == 0) return MCPT_OK;                                   // more shards than tiles: nothing for this one
     const uint64_t tiles = p.n_owned;
@@ -831,15 +810,12 @@ static mcpt_status render_call(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint3
     p.max_depth = ctx->opts.max_depth; p.flags = ctx->opts.flags; p.integrator = ctx->opts.integrator;
     p.seed_lo = uint32_t(seed); p.seed_hi = uint32_t(seed >> 32);
     if (tiles * p.chunks > 0x3ffffffull) return fail(MCPT_ERR_UNSUPPORTED, "launch too large: lower spp per call or raise samples_per_item");
-    const uint32_t tk = ctx->timed_head % mcpt_ctx::TIMED;
-    if (timed) HIP_TRY(hipEventRecord(ctx->ev0[tk], ctx->stream));
     if (ctx->use_wavefront) {
         st = render_wavefront(ctx, p, accum); if (st != MCPT_OK) return st;
     } else {
         HIP_TRY(launch_render(ctx->dev, p, accum, static_cast<DevCounters*>(ctx->counters.p), ctx->stream));
     }
-    if (timed) { HIP_TRY(hipEventRecord(ctx->ev1[tk], ctx->stream)); ctx->timed_head++; ctx->launches++; }
-    return MCPT_OK;
+    return timed ? timed_end(ctx) : MCPT_OK;
 }
 
 mcpt_status mcpt_render_tiles(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample, uint32_t tile_mod, uint32_t tile_rem) {
@@ -853,7 +829,7 @@ mcpt_status mcpt_render_tile_list(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, ui
     if (n_tiles == 0) return MCPT_OK;
     if (!tiles) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_tile_list: null list");
     // one-sample items write the film with a plain read-modify-write (RenderParams::atomic_accum = 0): a tile listed twice would race with itself
-    const uint64_t all = uint64_t((ctx->width + 7) / 8) * uint64_t((ctx->height + 7) / 8);
+    const uint64_t all = film_tiles(ctx);
     if (n_tiles > all) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_tile_list: more tiles than the image has (a duplicate)");
     std::vector<uint8_t> seen(all, 0);
     for (uint32_t i = 0; i < n_tiles; i++) {
@@ -864,13 +840,11 @@ mcpt_status mcpt_render_tile_list(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, ui
     if (ctx->tl_pending) { HIP_TRY(hipEventSynchronize(ctx->tl_ev)); ctx->tl_pending = false; }   // the staging buffer's last copy has been made
     if (ctx->tl_cap < n_tiles) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));                        // (kernels of earlier calls may still read the device list)
-        ctx->info.device_bytes -= ctx->tl_dev.bytes; ctx->tl_dev.free_();
-        if (ctx->tl_host) { (void)hipHostFree(ctx->tl_host); ctx->tl_host = nullptr; }
-        ctx->tl_cap = 0;
-        HIP_TRY(ctx->tl_dev.alloc(size_t(n_tiles) * sizeof(uint32_t)));
-        HIP_TRY(hipHostMalloc((void**)&ctx->tl_host, size_t(n_tiles) * sizeof(uint32_t), hipHostMallocDefault));
-        ctx->info.device_bytes += ctx->tl_dev.bytes; ctx->tl_cap = n_tiles;
-        if (!ctx->tl_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->tl_ev, hipEventDisableTiming));
+        DevBuf dev; Pinned<uint32_t> host;                                 // the longer pair replaces the old one only when all of it is there
+        HIP_TRY(dev.alloc(size_t(n_tiles) * sizeof(uint32_t), &ctx->info.device_bytes));
+        HIP_TRY(hipHostMalloc((void**)host.out(), size_t(n_tiles) * sizeof(uint32_t), hipHostMallocDefault));
+        if (!ctx->tl_ev) HIP_TRY(hipEventCreateWithFlags(ctx->tl_ev.out(), hipEventDisableTiming));
+        ctx->tl_dev = std::move(dev); ctx->tl_host = std::move(host); ctx->tl_cap = n_tiles;
     }
     std::memcpy(ctx->tl_host, tiles, size_t(n_tiles) * sizeof(uint32_t));
     HIP_TRY(hipMemcpyAsync(ctx->tl_dev.p, ctx->tl_host, size_t(n_tiles) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -884,12 +858,16 @@ mcpt_status mcpt_sync(mcpt_ctx* ctx) {
     return resolve_timing(ctx);
 }
 
+// What the read entry points do once their arguments are checked: drain the stream, copy to the caller, read the finished calls' durations.
+static mcpt_status read_back(mcpt_ctx* ctx, void* host, const void* dev, size_t bytes) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+    return resolve_timing(ctx);
+}
 mcpt_status mcpt_read_accum(mcpt_ctx* ctx, float* rgba_host) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!rgba_host) return fail(MCPT_ERR_INVALID_ARG, "null output");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(rgba_host, ctx->accum, size_t(ctx->width) * ctx->height * sizeof(float4), hipMemcpyDeviceToHost));
-    return resolve_timing(ctx);
+    return read_back(ctx, rgba_host, ctx->accum, size_t(ctx->width) * ctx->height * sizeof(float4));
 }
 mcpt_status mcpt_write_accum(mcpt_ctx* ctx, const float* rgba_host) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
@@ -910,8 +888,10 @@ mcpt_status mcpt_clear_accum(mcpt_ctx* ctx) {
 static mcpt_status tonemap_to_pinned(mcpt_ctx* ctx, const float4* film, int flip_y) {
     const size_t n = size_t(ctx->width) * ctx->height;
     if (!ctx->tone_dev.p) {
-        HIP_TRY(ctx->tone_dev.alloc(3 * n));
-        HIP_TRY(hipHostMalloc((void**)&ctx->tone_host, 3 * n ? 3 * n : 16, hipHostMallocDefault));
+        DevBuf dev; Pinned<uint8_t> host;
+        HIP_TRY(dev.alloc(3 * n));
+        HIP_TRY(hipHostMalloc((void**)host.out(), 3 * n ? 3 * n : 16, hipHostMallocDefault));
+        ctx->tone_dev = std::move(dev); ctx->tone_host = std::move(host);
     }
     HIP_TRY(launch_tonemap(film, static_cast<uint8_t*>(ctx->tone_dev.p), ctx->width, ctx->height, flip_y, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->tone_host, ctx->tone_dev.p, 3 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -956,16 +936,12 @@ mcpt_status mcpt_get_counters(mcpt_ctx* ctx, mcpt_counters* out) {
     st = resolve_timing(ctx); if (st != MCPT_OK) return st;
     std::vector<DevCounters> rep(WF_COUNTER_REPLICAS);               // kernels spread their atomics over replicas; sum them here
     HIP_TRY(hipMemcpy(rep.data(), ctx->counters.p, sizeof(DevCounters) * WF_COUNTER_REPLICAS, hipMemcpyDeviceToHost));
-    DevCounters d; std::memset(&d, 0, sizeof d);
-    for (const DevCounters& r : rep) {
-        d.paths += r.paths; d.rays_primary += r.rays_primary; d.rays_continuation += r.rays_continuation; d.rays_shadow += r.rays_shadow;
-        d.box_tests += r.box_tests; d.tri_tests += r.tri_tests; d.shaded_hits += r.shaded_hits; d.texel_fetches += r.texel_fetches;
-        d.self_shadow_tests += r.self_shadow_tests; d.self_shadow_hits += r.self_shadow_hits; d.stack_spills += r.stack_spills; for (int q = 0; q < 4; q++) d.debug[q] += r.debug[q];
-    }
     std::memset(out, 0, sizeof *out);
-    out->paths = d.paths; out->rays_primary = d.rays_primary; out->rays_continuation = d.rays_continuation; out->rays_shadow = d.rays_shadow;
-    out->box_tests = d.box_tests; out->tri_tests = d.tri_tests; out->shaded_hits = d.shaded_hits; out->texel_fetches = d.texel_fetches;
-    out->self_shadow_tests = d.self_shadow_tests; out->self_shadow_hits = d.self_shadow_hits; out->stack_spills = d.stack_spills; for (int q = 0; q < 4; q++) out->debug[q] = d.debug[q];
+    for (const DevCounters& r : rep) {
+        out->paths += r.paths; out->rays_primary += r.rays_primary; out->rays_continuation += r.rays_continuation; out->rays_shadow += r.rays_shadow;
+        out->box_tests += r.box_tests; out->tri_tests += r.tri_tests; out->shaded_hits += r.shaded_hits; out->texel_fetches += r.texel_fetches;
+        out->self_shadow_tests += r.self_shadow_tests; out->self_shadow_hits += r.self_shadow_hits; out->stack_spills += r.stack_spills; for (int q = 0; q < 4; q++) out->debug[q] += r.debug[q];
+    }
     out->kernel_ms = ctx->last_kernel_ms; out->kernel_ms_total = ctx->total_kernel_ms; out->launches = ctx->launches;
     out->trace_ms_total = ctx->total_trace_ms; out->shade_ms_total = ctx->total_shade_ms; out->iterations = ctx->total_iterations;
     return MCPT_OK;
@@ -1013,10 +989,7 @@ mcpt_status mcpt_render_features(mcpt_ctx* ctx, uint32_t spp, uint64_t seed) {
     if (spp < 1 || spp > DN_MAX_SPP) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_features: need 1 <= spp <= 64");
     if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
     const size_t n = size_t(ctx->width) * ctx->height;
-    if (!ctx->dn_feat.p) {
-        HIP_TRY(ctx->dn_feat.alloc(2 * n * sizeof(float4)));
-        ctx->info.device_bytes += ctx->dn_feat.bytes;
-    }
+    if (!ctx->dn_feat.p) HIP_TRY(ctx->dn_feat.alloc(2 * n * sizeof(float4), &ctx->info.device_bytes));
     HIP_TRY(launch_dn_features(ctx->dev, spp, uint32_t(seed), uint32_t(seed >> 32), static_cast<float4*>(ctx->dn_feat.p), ctx->stream));
     ctx->dn_have_features = true;
     return MCPT_OK;
@@ -1026,25 +999,21 @@ mcpt_status mcpt_read_features(mcpt_ctx* ctx, float* out8) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!out8) return fail(MCPT_ERR_INVALID_ARG, "null output");
     if (!ctx->dn_have_features) return fail(MCPT_ERR_INVALID_ARG, "mcpt_read_features: no features rendered yet (mcpt_render_features)");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out8, ctx->dn_feat.p, ctx->dn_feat.bytes, hipMemcpyDeviceToHost));
-    return resolve_timing(ctx);
+    return read_back(ctx, out8, ctx->dn_feat.p, ctx->dn_feat.bytes);
 }
 
 mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_denoise_opts* opts) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    mcpt_denoise_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o;
-    if (opts) {
-        if (opts->struct_size != sizeof(mcpt_denoise_opts)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: opts->struct_size != sizeof(mcpt_denoise_opts)");
-        o = *opts;
-    }
+    mcpt_denoise_opts o;
+    st = read_opts(opts, o, "mcpt_denoise", "mcpt_denoise_opts"); if (st != MCPT_OK) return st;
     if (o.iterations > DN_MAX_LEVELS) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: at most 10 iterations");
     if (!(o.sigma_color >= 0.f) || !(o.sigma_normal >= 0.f) || !(o.sigma_depth >= 0.f)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be >= 0 (0 = default)");
     if (!ctx->dn_have_features) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: no features rendered yet (mcpt_render_features)");
     const size_t n = size_t(ctx->width) * ctx->height;
     if (!ctx->dn_out.p) {
-        DevBuf* bufs[4] = {&ctx->dn_guide, &ctx->dn_iv0, &ctx->dn_iv1, &ctx->dn_out};
-        for (DevBuf* b : bufs) { HIP_TRY(b->alloc(n * sizeof(float4))); ctx->info.device_bytes += b->bytes; }
+        DevBuf* dst[4] = {&ctx->dn_guide, &ctx->dn_iv0, &ctx->dn_iv1, &ctx->dn_out}; DevBuf fresh[4];
+        for (DevBuf& b : fresh) HIP_TRY(b.alloc(n * sizeof(float4), &ctx->info.device_bytes));
+        for (int i = 0; i < 4; i++) *dst[i] = std::move(fresh[i]);
     }
     DnParams p;
     p.width = ctx->width; p.height = ctx->height;
@@ -1064,9 +1033,7 @@ mcpt_status mcpt_read_denoised(mcpt_ctx* ctx, float* rgba_host) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!rgba_host) return fail(MCPT_ERR_INVALID_ARG, "null output");
     if (!ctx->dn_have_out) return fail(MCPT_ERR_INVALID_ARG, "mcpt_read_denoised: nothing denoised yet (mcpt_denoise)");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(rgba_host, ctx->dn_out.p, ctx->dn_out.bytes, hipMemcpyDeviceToHost));
-    return resolve_timing(ctx);
+    return read_back(ctx, rgba_host, ctx->dn_out.p, ctx->dn_out.bytes);
 }
 
 mcpt_status mcpt_denoised_device_ptr(mcpt_ctx* ctx, void** out_device_rgba) {
@@ -1082,16 +1049,15 @@ mcpt_status mcpt_denoised_device_ptr(mcpt_ctx* ctx, void** out_device_rgba) {
 static mcpt_status ad_ensure(mcpt_ctx* ctx) {
     if (ctx->ad_h.p) return MCPT_OK;
     const size_t n = size_t(ctx->width) * ctx->height;
-    const uint32_t n_tiles = uint32_t(((ctx->width + 7) / 8) * ((ctx->height + 7) / 8)), nb = ad_blocks(n_tiles);
+    const uint32_t n_tiles = uint32_t(film_tiles(ctx)), nb = ad_blocks(n_tiles);
     const size_t bytes[8] = {n * sizeof(float4), n * sizeof(float4), n_tiles * sizeof(float), n_tiles * sizeof(uint32_t), n_tiles * sizeof(uint32_t),
                              nb * sizeof(uint4), nb * sizeof(uint32_t), sizeof(AdTotals)};
-    DevBuf* bufs[8] = {&ctx->ad_h, &ctx->ad_o, &ctx->ad_err, &ctx->ad_list, &ctx->ad_flags, &ctx->ad_counts, &ctx->ad_offs, &ctx->ad_tot};
-    for (int i = 0; i < 8; i++) {
-        const hipError_t e = bufs[i]->alloc(bytes[i]);
-        if (e != hipSuccess) { for (DevBuf* b : bufs) b->free_(); return hip_fail(e, "alloc adaptive buffers"); }
-    }
-    HIP_TRY(hipHostMalloc((void**)&ctx->ad_host, sizeof(AdTotals), hipHostMallocDefault));
-    for (DevBuf* b : bufs) ctx->info.device_bytes += b->bytes;
+    DevBuf* dst[8] = {&ctx->ad_h, &ctx->ad_o, &ctx->ad_err, &ctx->ad_list, &ctx->ad_flags, &ctx->ad_counts, &ctx->ad_offs, &ctx->ad_tot};
+    DevBuf fresh[8]; Pinned<AdTotals> host;                               // committed only when all of it is there
+    for (int i = 0; i < 8; i++) HIP_TRY(fresh[i].alloc(bytes[i], &ctx->info.device_bytes));
+    HIP_TRY(hipHostMalloc((void**)host.out(), sizeof(AdTotals), hipHostMallocDefault));
+    for (int i = 0; i < 8; i++) *dst[i] = std::move(fresh[i]);
+    ctx->ad_host = std::move(host);
     return MCPT_OK;
 }
 static AdScratch ad_scratch(mcpt_ctx* ctx) {
@@ -1103,11 +1069,8 @@ static AdScratch ad_scratch(mcpt_ctx* ctx) {
 
 mcpt_status mcpt_render_adaptive(mcpt_ctx* ctx, uint64_t seed, uint32_t first_sample, const mcpt_adaptive_opts* opts, mcpt_adaptive_stats* out_stats) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    mcpt_adaptive_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o;
-    if (opts) {
-        if (opts->struct_size != sizeof(mcpt_adaptive_opts)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_adaptive: opts->struct_size != sizeof(mcpt_adaptive_opts)");
-        o = *opts;
-    }
+    mcpt_adaptive_opts o;
+    st = read_opts(opts, o, "mcpt_render_adaptive", "mcpt_adaptive_opts"); if (st != MCPT_OK) return st;
     const uint32_t min_spp = o.min_spp ? o.min_spp : 16u, max_spp = o.max_spp ? o.max_spp : 1024u;
     if (min_spp < 2 || (min_spp & 1u)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_adaptive: min_spp must be even and >= 2");
     if (max_spp < min_spp) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_adaptive: max_spp < min_spp");
@@ -1116,15 +1079,13 @@ mcpt_status mcpt_render_adaptive(mcpt_ctx* ctx, uint64_t seed, uint32_t first_sa
     const float thr = o.threshold > 0.f ? o.threshold : MCPT_ADAPTIVE_DEFAULT_THRESHOLD;
     if (!ctx->use_wavefront && !ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the megakernel's traversal stack");
     st = ad_ensure(ctx); if (st != MCPT_OK) return st;
-    st = resolve_timing(ctx, ctx->time_kernels != 0 || ctx->timed_head - ctx->timed_tail >= mcpt_ctx::TIMED - 1); if (st != MCPT_OK) return st;
     const size_t n_px = size_t(ctx->width) * ctx->height;
-    const uint32_t n_tiles = uint32_t(((ctx->width + 7) / 8) * ((ctx->height + 7) / 8));
+    const uint32_t n_tiles = uint32_t(film_tiles(ctx));
     float4* H = static_cast<float4*>(ctx->ad_h.p); float4* O = static_cast<float4*>(ctx->ad_o.p);
     const uint32_t* list = static_cast<const uint32_t*>(ctx->ad_list.p);
     const AdScratch scr = ad_scratch(ctx);
     mcpt_adaptive_stats stats; std::memset(&stats, 0, sizeof stats); stats.struct_size = sizeof stats;
-    const uint32_t tk = ctx->timed_head % mcpt_ctx::TIMED;
-    HIP_TRY(hipEventRecord(ctx->ev0[tk], ctx->stream));
+    st = timed_begin(ctx); if (st != MCPT_OK) return st;
     HIP_TRY(hipMemsetAsync(H, 0, n_px * sizeof(float4), ctx->stream));
     HIP_TRY(hipMemsetAsync(O, 0, n_px * sizeof(float4), ctx->stream));
     ctx->ad_have_err = false;
@@ -1152,8 +1113,7 @@ mcpt_status mcpt_render_adaptive(mcpt_ctx* ctx, uint64_t seed, uint32_t first_sa
         c += n;
     }
     HIP_TRY(launch_ad_merge(ctx->accum, H, O, uint32_t(n_px), ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev1[tk], ctx->stream));
-    ctx->timed_head++; ctx->launches++;
+    st = timed_end(ctx); if (st != MCPT_OK) return st;
     if (out_stats) *out_stats = stats;
     return MCPT_OK;
 }
@@ -1162,9 +1122,7 @@ mcpt_status mcpt_read_tile_error(mcpt_ctx* ctx, float* out) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
     if (!ctx->ad_have_err) return fail(MCPT_ERR_INVALID_ARG, "mcpt_read_tile_error: no adaptive render yet (mcpt_render_adaptive)");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out, ctx->ad_err.p, ctx->ad_err.bytes, hipMemcpyDeviceToHost));
-    return resolve_timing(ctx);
+    return read_back(ctx, out, ctx->ad_err.p, ctx->ad_err.bytes);
 }
 
 mcpt_status mcpt_probe_tile_error(mcpt_ctx* ctx, const float* h_rgba_host, const float* o_rgba_host, float threshold, uint32_t max_spp,
@@ -1173,7 +1131,7 @@ mcpt_status mcpt_probe_tile_error(mcpt_ctx* ctx, const float* h_rgba_host, const
     if (!h_rgba_host || !o_rgba_host || !out_err || !out_list || !out_n) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (!std::isfinite(threshold) || threshold < 0.f) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_tile_error: threshold must be finite and >= 0");
     const size_t n_px = size_t(ctx->width) * ctx->height;
-    const uint32_t n_tiles = uint32_t(((ctx->width + 7) / 8) * ((ctx->height + 7) / 8)), nb = ad_blocks(n_tiles);
+    const uint32_t n_tiles = uint32_t(film_tiles(ctx)), nb = ad_blocks(n_tiles);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     Scratch s; float4 *h, *o; float* err; uint32_t *list, *flags, *offs; uint4* counts; AdTotals* tot;
     HIP_TRY(s.in(reinterpret_cast<const float4*>(h_rgba_host), n_px, &h)); HIP_TRY(s.in(reinterpret_cast<const float4*>(o_rgba_host), n_px, &o));
@@ -1260,9 +1218,8 @@ mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
     std::memset(out, 0, sizeof *out);
     out->struct_size = sizeof *out; out->updates = ctx->rf_updates; out->last_update_ms = ctx->rf_last_ms; out->wide_area_ratio = 1.0;
     if (ctx->rf_updates) {                                                      // the last update left its partial sums behind
-        std::vector<double> part(rf_area_blocks(uint32_t(ctx->dev.n_nodes8)));
-        HIP_TRY(hipMemcpy(part.data(), ctx->rf_area.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
-        double a = 0.0; for (double v : part) a += v;
+        double a = 0.0;
+        st = rf_read_area(ctx, a); if (st != MCPT_OK) return st;
         out->wide_area_ratio = ctx->rf_area0 > 0.0 ? a / ctx->rf_area0 : 1.0;
     }
     return MCPT_OK;
@@ -1351,7 +1308,7 @@ mcpt_status mcpt_probe_trace4(mcpt_ctx* ctx, uint32_t n, const double* origin, c
                             static_cast<int*>(L.ovf_buf.p), ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     {   IterCtl snap; HIP_TRY(hipMemcpy(&snap, L.ctl_buf.p, sizeof snap, hipMemcpyDeviceToHost));
-        if (snap.pad[0]) return fail(MCPT_ERR_HIP, "trace kernel watchdog: a wave did not finish its ray list (internal error)"); }
+        if (job_state(snap, 0u, 0u) == JobState::Watchdog) return fail(MCPT_ERR_HIP, WATCHDOG_MSG); }
     if (any_hit) {
         HIP_TRY(hipMemcpy(hit.data(), pool.nee, hit.size() * 4, hipMemcpyDeviceToHost));     // blocked <=> the trace kernel set nee.w
         for (uint32_t i = 0; i < n; i++) {
@@ -1359,10 +1316,7 @@ mcpt_status mcpt_probe_trace4(mcpt_ctx* ctx, uint32_t n, const double* origin, c
             out_tri[i] = flag ? 1 : 0; out_t[i] = 0.f; out_u[i] = 0.f; out_v[i] = 0.f;
         }
     } else {
-        if (ctx->h_tri_face.empty()) {
-            ctx->h_tri_face.resize(size_t(ctx->dev.n_tris));
-            HIP_TRY(hipMemcpy(ctx->h_tri_face.data(), ctx->dev.tri_face, ctx->h_tri_face.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        }
+        st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
         HIP_TRY(hipMemcpy(hit.data(), pool.hit, hit.size() * 4, hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < n; i++) {
             int32_t tri; std::memcpy(&tri, &hit[4 * size_t(i)], 4);
@@ -1391,10 +1345,7 @@ mcpt_status mcpt_probe_hit_shade(mcpt_ctx* ctx, uint32_t n, const int32_t* face,
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!face || !u || !v || !dir || !out6) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (n == 0) return MCPT_OK;
-    if (ctx->h_tri_face.empty()) {
-        ctx->h_tri_face.resize(size_t(ctx->dev.n_tris));
-        HIP_TRY(hipMemcpy(ctx->h_tri_face.data(), ctx->dev.tri_face, ctx->h_tri_face.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
+    st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
     std::vector<int32_t> leaf_of_face(ctx->h_tri_face.size(), -1), tri(n);
     for (size_t i = 0; i < ctx->h_tri_face.size(); i++) leaf_of_face[size_t(ctx->h_tri_face[i])] = int32_t(i);
     for (uint32_t i = 0; i < n; i++) {

@@ -517,6 +517,48 @@ std::string validate_bvh2(const HostScene& hs) {
     return "";
 }
 
+// The level structure of both trees from their host records.  Binary tree: the renumbering puts every parent before its children, so one
+// descending pass gives the heights (0 = both children are leaves); the nodes are then sorted by height.  8-wide tree: build_bvh8 and
+// gpu_collapse_bvh8 number the records breadth-first, level by level -- a level's inner children are the next level, consecutively.
+bool rf_levels(const std::vector<f4h>& n2, const std::vector<f4h>& n8, std::vector<uint32_t>& bin_order, std::vector<uint32_t>& bin_level,
+               std::vector<uint32_t>& wide_level, std::string& err) {
+    const size_t N = n2.size() / 4, N8 = n8.size() / 5;
+    std::vector<uint32_t> height(N, 0);
+    uint32_t top = 0;
+    for (size_t n = N; n-- > 0;) {
+        uint32_t h = 0;
+        for (int k = 0; k < 2; k++) {
+            const int c = child2(n2, int(n), k);
+            if (c < 0) continue;
+            if (size_t(c) <= n || size_t(c) >= N) { err = "binary tree is not numbered parents first (internal error)"; return false; }
+            h = std::max(h, height[size_t(c)] + 1);
+        }
+        height[n] = h; top = std::max(top, h);
+    }
+    bin_level.assign(size_t(top) + 2, 0);
+    for (size_t n = 0; n < N; n++) bin_level[height[n] + 1]++;
+    for (size_t k = 1; k < bin_level.size(); k++) bin_level[k] += bin_level[k - 1];
+    bin_order.resize(N);
+    { std::vector<uint32_t> at(bin_level.begin(), bin_level.end() - 1); for (size_t n = 0; n < N; n++) bin_order[at[height[n]]++] = uint32_t(n); }
+    wide_level.clear();
+    size_t begin = 0, end = 1;
+    while (begin < end) {
+        wide_level.push_back(uint32_t(begin));
+        size_t kids = 0;
+        for (size_t r = begin; r < end; r++) {
+            uint32_t masks, base; std::memcpy(&masks, &n8[5 * r + 1].w, 4); std::memcpy(&base, &n8[5 * r + 1].x, 4);
+            const uint32_t ni = uint32_t(__builtin_popcount(masks & 0xffu));
+            if (ni && base != end + kids) { err = "8-wide tree is not numbered level by level (internal error)"; return false; }
+            kids += ni;
+        }
+        begin = end; end += kids;
+        if (end > N8) { err = "8-wide tree: child link out of range (internal error)"; return false; }
+    }
+    wide_level.push_back(uint32_t(begin));
+    if (begin != N8) { err = "8-wide tree: unreachable records (internal error)"; return false; }
+    return true;
+}
+
 // MCPT_FLAG_REFERENCE_TIE_ORDER: where every face ends up in the reference's BVH::triangles.  BVH::build (BVH.cpp:15-54) partitions the
 // range [l, r) about the midpoint (narrowed to float, :39) of the CENTROID box's longest axis (AABB::max_axis, AABB.cpp:12-23) with
 // std::partition -- the same libstdc++ algorithm `oracle/_ref` is built with, so the order is the same element for element -- halves the

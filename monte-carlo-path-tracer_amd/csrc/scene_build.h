@@ -53,6 +53,9 @@ std::string validate_bvh8(const HostScene& hs);
 // The same containment walk over the binary tree `nodes`.
 std::string validate_bvh2(const HostScene& hs);
 inline std::string validate_wide_bvh(const HostScene& hs) { return validate_bvh8(hs); }
+// Level structure of both trees, one refit launch per level: the binary nodes sorted by height (bin_order, bin_level), the 8-wide records by depth (wide_level).
+bool rf_levels(const std::vector<f4h>& n2, const std::vector<f4h>& n8, std::vector<uint32_t>& bin_order, std::vector<uint32_t>& bin_level,
+               std::vector<uint32_t>& wide_level, std::string& err);
 
 // DevCamera of `camera` for a scene centred at `centre` (fp64, the reference's operation order): used by mcpt_create and mcpt_set_camera.
 void camera_constants(const mcpt_camera& camera, const double* centre, DevCamera& out);

@@ -83,6 +83,25 @@ int main(int argc, char** argv) {
                 else if (!hs.reference_tie_order && w != i) why = "default tie rank is not the leaf-order index";
             }
         }
+        if (why.empty()) {                                     // the refit's level structure: every binary node once, children below their parent, wide levels tile [0, N8)
+            std::vector<uint32_t> order, bin_level, wide_level;
+            const size_t N = hs.nodes.size() / 4, N8 = hs.nodes8.size() / 5;
+            if (!rf_levels(hs.nodes, hs.nodes8, order, bin_level, wide_level, why)) why = "rf_levels: " + why;
+            else if (order.size() != N || bin_level.empty() || bin_level.front() != 0 || bin_level.back() != N) why = "rf_levels: binary levels do not cover the nodes";
+            else if (wide_level.size() < 2 || wide_level.front() != 0 || wide_level.back() != N8) why = "rf_levels: wide levels do not cover [0, N8)";
+            for (size_t k = 0; k + 1 < wide_level.size() && why.empty(); k++) if (wide_level[k] > wide_level[k + 1]) why = "rf_levels: wide levels are not ascending";
+            std::vector<int64_t> level_of(N, -1);
+            for (size_t k = 0; k + 1 < bin_level.size() && why.empty(); k++)
+                for (uint32_t i = bin_level[k]; i < bin_level[k + 1] && why.empty(); i++) {
+                    if (bin_level[k + 1] > N || order[i] >= N || level_of[order[i]] >= 0) why = "rf_levels: a binary node is missing or listed twice";
+                    else level_of[order[i]] = int64_t(k);
+                }
+            for (size_t n = 0; n < N && why.empty(); n++)
+                for (int k = 0; k < 2; k++) {
+                    int ch; std::memcpy(&ch, k == 0 ? &hs.nodes[4 * n + 3].x : &hs.nodes[4 * n + 3].y, 4);
+                    if (ch >= 0 && level_of[size_t(ch)] >= level_of[n]) why = "rf_levels: a child is not in a lower level than its parent";
+                }
+        }
         if (!why.empty()) { unsound++; std::printf("case %d kind %d: accepted but tree unsound: %s\n", c, kind, why.c_str()); }
     }
     std::printf("%d cases: %d accepted, %d rejected, %d unsound\n", cases, accepted, rejected, unsound);
