@@ -291,6 +291,51 @@ mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out);   /* syn
  * MCPT_OK = sound; otherwise MCPT_ERR_INVALID_ARG with the walk's message in mcpt_last_error(). */
 mcpt_status mcpt_probe_validate_trees(mcpt_ctx* ctx);
 
+/* ---- temporal reprojection: the film carried across a camera move ------------------------------------------------------- */
+/* mcpt_set_camera_reproject is mcpt_set_camera for a caller who wants to keep the film: per pixel of the NEW view the first-hit surface point
+ * (feature depth along the pixel-centre ray) is projected into the OLD view, the old film is gathered bilinearly there -- a tap counts when it
+ * is inside the image, holds samples, is a surface pixel (coverage >= 0.5) and passes a relative depth test and a normal test against the
+ * old view's features; taps of zero weight never count -- and the bound film becomes {mean * n, n} with n = min(rint(weighted mean of the taps'
+ * counts), max_history); {0, 0, 0, 0} where there is no history (background, emitters, disocclusions, less than a quarter of the bilinear
+ * weight left, outside the old image, behind the old eye, or an old view whose front / right / up are linearly dependent).
+ *  - The history cap is the point of the design: reprojected radiance is exact only for view-independent (diffuse) shading.  On glossy and
+ *    mirror surfaces it lags behind the view; max_history bounds how long that stale radiance survives once new samples are added.  Lobes
+ *    are not classified.
+ *  - Asynchronous; all device work is on the context's stream, ordered like mcpt_set_camera.  A film bound with mcpt_bind_accum is the one
+ *    rewritten.  If the context holds no features, those of the CURRENT camera are rendered first (feature_spp, feature_seed).  Afterwards the
+ *    context HOLDS features -- those of the new view, mcpt_render_features(ctx, feature_spp, feature_seed) exactly -- so mcpt_denoise may
+ *    follow at once; the denoised film and the last adaptive tile error are dropped as after mcpt_set_camera; the counters are untouched.
+ *  - Refusals (the camera by mcpt_set_camera's rules, the options by the ranges below, MCPT_ERR_BVH_DEPTH where mcpt_render_features answers
+ *    it) change nothing: not the camera, the film, or the features held.
+ *  - The first call allocates 48 B per pixel (the old view's features and a copy of the old film), counted in device_bytes, plus the 32 B
+ *    per pixel of the feature buffers if the context never had any.  A clone starts without them.
+ *  - Which first_sample / seed to continue with is the caller's business: continuing with sample indices that are already in the history
+ *    correlates the new samples with it (the same paths, seen from the new eye) -- continue past them, or change the seed.
+ *  - mcpt_update_vertices gets no reprojection: moving geometry needs motion vectors. */
+typedef struct mcpt_reproject_opts {
+    uint32_t struct_size;       /* = sizeof(mcpt_reproject_opts) */
+    uint32_t feature_spp;       /* features of the new view (and of the old one if the context holds none): 0 = default 4, max 64 */
+    uint64_t feature_seed;
+    float    max_history;       /* cap on the sample count carried over per pixel; 0 = default 32; finite, >= 1 */
+    float    depth_tolerance;   /* relative; 0 = default 0.05; finite, in (0, 1] */
+    float    normal_threshold;  /* minimum cosine; 0 = default 0.9; in (0, 1] */
+    uint32_t reserved[3];
+} mcpt_reproject_opts;
+typedef struct mcpt_reproject_info {
+    uint32_t struct_size, reprojections;   /* mcpt_set_camera_reproject calls on this context so far */
+    uint64_t pixels_reused;                /* pixels of the last call written with a history of >= 1 sample */
+    double   last_ms;                      /* device time of the last call, first to last operation on the stream (HIP events) */
+    uint32_t reserved[4];
+} mcpt_reproject_info;
+mcpt_status mcpt_set_camera_reproject(mcpt_ctx* ctx, const mcpt_camera* camera, const mcpt_reproject_opts* opts);   /* NULL opts = defaults */
+mcpt_status mcpt_get_reproject_info(mcpt_ctx* ctx, mcpt_reproject_info* out);   /* synchronises */
+/* Probe: the reprojection kernel alone on caller data of the context's film size -- the old film (width * height {sum rgb, count}), the old and
+ * the new view's features (width * height * 8 floats each, mcpt_read_features' layout) and both cameras (mcpt_set_camera's rules).  Touches
+ * neither the context's camera nor its film nor its features.  Synchronous. */
+mcpt_status mcpt_probe_reproject(mcpt_ctx* ctx, const mcpt_camera* old_cam, const mcpt_camera* new_cam, const float* old_film_host,
+                                 const float* old_feat8_host, const float* new_feat8_host, const mcpt_reproject_opts* opts, float* out_film_host,
+                                 uint64_t* out_reused);
+
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that
  * torch.distributed / RCCL all-reduces in place).  NULL re-binds the internal buffer. */

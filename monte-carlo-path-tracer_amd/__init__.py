@@ -113,6 +113,19 @@ class UpdateInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class ReprojectOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("feature_spp", C.c_uint32), ("feature_seed", C.c_uint64), ("max_history", C.c_float),
+                ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class ReprojectInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reprojections", C.c_uint32), ("pixels_reused", C.c_uint64), ("last_ms", C.c_double),
+                ("reserved", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 def texture_to_float(img_u8: np.ndarray) -> np.ndarray:
     """What stbi_loadf gives the reference for an 8-bit image (model.cpp:8-23; stb_image.h:1553,1849):
     (c/255)^2.2 per channel, row 0 = first row of the file."""
@@ -224,6 +237,9 @@ def load_library() -> C.CDLL:
         "mcpt_update_vertices": [vp, vp, C.c_uint32, vp, C.c_uint32],
         "mcpt_get_update_info": [vp, P(UpdateInfo)],
         "mcpt_probe_validate_trees": [vp],
+        "mcpt_set_camera_reproject": [vp, P(CameraC), P(ReprojectOpts)],
+        "mcpt_get_reproject_info": [vp, P(ReprojectInfo)],
+        "mcpt_probe_reproject": [vp, P(CameraC), P(CameraC), vp, vp, vp, P(ReprojectOpts), vp, P(C.c_uint64)],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -246,11 +262,27 @@ EXPORTED_SYMBOLS = [
     "mcpt_render_features", "mcpt_read_features", "mcpt_denoise", "mcpt_read_denoised", "mcpt_denoised_device_ptr",
     "mcpt_render_tile_list", "mcpt_render_adaptive", "mcpt_read_tile_error", "mcpt_probe_tile_error",
     "mcpt_set_camera", "mcpt_update_vertices", "mcpt_get_update_info", "mcpt_probe_validate_trees",
+    "mcpt_set_camera_reproject", "mcpt_get_reproject_info", "mcpt_probe_reproject",
 ]
 
 
 class McptError(RuntimeError):
     pass
+
+
+def _camera_c(camera) -> CameraC:
+    c = CameraC()
+    for k in range(3):
+        c.eye[k] = camera.eye[k]; c.lookat[k] = camera.lookat[k]; c.up[k] = camera.up[k]
+    c.fovy = camera.fovy; c.width = camera.width; c.height = camera.height
+    return c
+
+
+def _reproject_opts(feature_spp=0, feature_seed=0, max_history=0.0, depth_tolerance=0.0, normal_threshold=0.0) -> ReprojectOpts:
+    o = ReprojectOpts()
+    o.struct_size = C.sizeof(ReprojectOpts); o.feature_spp = feature_spp; o.feature_seed = feature_seed
+    o.max_history = max_history; o.depth_tolerance = depth_tolerance; o.normal_threshold = normal_threshold
+    return o
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -348,11 +380,33 @@ class Renderer:
     # ---- live scenes
     def set_camera(self, camera):
         """A new camera (scenes.Camera) for the same film size; free.  The caller clears the film when the old samples no longer belong."""
-        c = CameraC()
-        for k in range(3):
-            c.eye[k] = camera.eye[k]; c.lookat[k] = camera.lookat[k]; c.up[k] = camera.up[k]
-        c.fovy = camera.fovy; c.width = camera.width; c.height = camera.height
+        c = _camera_c(camera)
         self._check(self.lib.mcpt_set_camera(self.ctx, C.byref(c)))
+
+    # ---- temporal reprojection (DESIGN.md §13)
+    def reproject_camera(self, camera, feature_spp=0, feature_seed=0, max_history=0.0, depth_tolerance=0.0, normal_threshold=0.0):
+        """set_camera that carries the film over: the bound film becomes the old film looked up at the new view's surface points, at most
+        max_history samples per pixel (0 = the default of each option).  Asynchronous.  Afterwards the context holds the new view's features."""
+        c = _camera_c(camera)
+        o = _reproject_opts(feature_spp, feature_seed, max_history, depth_tolerance, normal_threshold)
+        self._check(self.lib.mcpt_set_camera_reproject(self.ctx, C.byref(c), C.byref(o)))
+
+    def reproject_info(self) -> ReprojectInfo:
+        i = ReprojectInfo()
+        self._check(self.lib.mcpt_get_reproject_info(self.ctx, C.byref(i)))
+        return i
+
+    def probe_reproject(self, old_camera, new_camera, old_film, old_feat, new_feat, max_history=0.0, depth_tolerance=0.0, normal_threshold=0.0):
+        """The reprojection kernel alone on caller data of this context's film size: ((h, w, 4) film, pixels reused)."""
+        a = np.ascontiguousarray(old_film, np.float32); fo = np.ascontiguousarray(old_feat, np.float32); fn = np.ascontiguousarray(new_feat, np.float32)
+        n = self.width * self.height
+        assert a.size == 4 * n and fo.size == 8 * n and fn.size == 8 * n
+        co, cn = _camera_c(old_camera), _camera_c(new_camera)
+        o = _reproject_opts(0, 0, max_history, depth_tolerance, normal_threshold)
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        reused = C.c_uint64(0)
+        self._check(self.lib.mcpt_probe_reproject(self.ctx, C.byref(co), C.byref(cn), _ptr(a), _ptr(fo), _ptr(fn), C.byref(o), _ptr(out), C.byref(reused)))
+        return out, int(reused.value)
 
     def update_vertices(self, vertex, normal=None):
         """New positions (and optionally normals) for the same faces: refits both trees on the device.  Needs FLAG_DYNAMIC."""

@@ -8,6 +8,7 @@
 #include "denoise.h"
 #include "adaptive.h"
 #include "refit.h"
+#include "reproject.h"
 
 #include <chrono>
 #include <cmath>
@@ -133,6 +134,11 @@ struct mcpt_ctx {
     Pinned<double> rf_stage; Event rf_stage_ev; bool rf_stage_pending = false;
     Event rf_ev0, rf_ev1; bool rf_timed = false;
     uint32_t rf_updates = 0; double rf_last_ms = 0.0, rf_area0 = 0.0;
+    // Temporal reprojection (reproject.hip), allocated by the first mcpt_set_camera_reproject: the old view's features (2 float4 /
+    // pixel, swapped with dn_feat per call) and a copy of the old film (1 float4 / pixel), both counted in device_bytes; the reuse counter
+    DevBuf rp_feat_old, rp_film_old, rp_count;
+    Event rp_ev0, rp_ev1; bool rp_timed = false;
+    uint32_t rp_calls = 0; double rp_last_ms = 0.0;
 };
 
 namespace {
@@ -1151,17 +1157,27 @@ mcpt_status mcpt_probe_tile_error(mcpt_ctx* ctx, const float* h_rgba_host, const
 
 
 // ------------------------------------------------------------------------------------------------ live scenes
-mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* cm) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!cm) return fail(MCPT_ERR_INVALID_ARG, "mcpt_set_camera: null camera");
-    if (cm->width != ctx->width || cm->height != ctx->height) return fail(MCPT_ERR_INVALID_ARG, "mcpt_set_camera: width / height differ from the context's film");
+// What a camera for an existing context must be (mcpt_set_camera's rules); `fn` names the entry point in the message.
+static mcpt_status check_camera(const mcpt_ctx* ctx, const mcpt_camera* cm, const char* fn) {
+    const std::string who = std::string(fn) + ": ";
+    if (!cm) return fail(MCPT_ERR_INVALID_ARG, who + "null camera");
+    if (cm->width != ctx->width || cm->height != ctx->height) return fail(MCPT_ERR_INVALID_ARG, who + "width / height differ from the context's film");
     bool finite = std::isfinite(cm->fovy);
     for (int a = 0; a < 3; a++) finite = finite && std::isfinite(cm->eye[a]) && std::isfinite(cm->lookat[a]) && std::isfinite(cm->up[a]);
-    if (!finite) return fail(MCPT_ERR_INVALID_ARG, "mcpt_set_camera: a camera field is not finite");
-    if (cm->eye[0] == cm->lookat[0] && cm->eye[1] == cm->lookat[1] && cm->eye[2] == cm->lookat[2]) return fail(MCPT_ERR_INVALID_ARG, "mcpt_set_camera: eye == lookat");
-    // the camera travels by value with every launch (DevScene::cam): launches already enqueued keep the old one, later ones get this one
-    camera_constants(*cm, ctx->dev.centre, ctx->dev.cam);
+    if (!finite) return fail(MCPT_ERR_INVALID_ARG, who + "a camera field is not finite");
+    if (cm->eye[0] == cm->lookat[0] && cm->eye[1] == cm->lookat[1] && cm->eye[2] == cm->lookat[2]) return fail(MCPT_ERR_INVALID_ARG, who + "eye == lookat");
+    return MCPT_OK;
+}
+// The camera travels by value with every launch (DevScene::cam): launches already enqueued keep the old one, later ones get this one.
+static void apply_camera(mcpt_ctx* ctx, const mcpt_camera& cm) {
+    camera_constants(cm, ctx->dev.centre, ctx->dev.cam);
     rf_forget_derived(ctx);
+}
+
+mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* cm) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    st = check_camera(ctx, cm, "mcpt_set_camera"); if (st != MCPT_OK) return st;
+    apply_camera(ctx, *cm);
     return MCPT_OK;
 }
 
@@ -1222,6 +1238,118 @@ mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
         st = rf_read_area(ctx, a); if (st != MCPT_OK) return st;
         out->wide_area_ratio = ctx->rf_area0 > 0.0 ? a / ctx->rf_area0 : 1.0;
     }
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ temporal reprojection
+// The options with their defaults filled in, or the refusal.
+static mcpt_status rp_read_opts(const mcpt_reproject_opts* opts, mcpt_reproject_opts& o, const char* fn) {
+    mcpt_status st = read_opts(opts, o, fn, "mcpt_reproject_opts"); if (st != MCPT_OK) return st;
+    const std::string who = std::string(fn) + ": ";
+    if (o.feature_spp > DN_MAX_SPP) return fail(MCPT_ERR_INVALID_ARG, who + "feature_spp must be <= 64 (0 = default 4)");
+    if (o.max_history != 0.f && !(std::isfinite(o.max_history) && o.max_history >= 1.f)) return fail(MCPT_ERR_INVALID_ARG, who + "max_history must be finite and >= 1 (0 = default 32)");
+    if (o.depth_tolerance != 0.f && !(o.depth_tolerance > 0.f && o.depth_tolerance <= 1.f)) return fail(MCPT_ERR_INVALID_ARG, who + "depth_tolerance must be in (0, 1] (0 = default 0.05)");
+    if (o.normal_threshold != 0.f && !(o.normal_threshold > 0.f && o.normal_threshold <= 1.f)) return fail(MCPT_ERR_INVALID_ARG, who + "normal_threshold must be in (0, 1] (0 = default 0.9)");
+    if (o.feature_spp == 0) o.feature_spp = 4u;
+    if (o.max_history == 0.f) o.max_history = 32.f;
+    if (o.depth_tolerance == 0.f) o.depth_tolerance = 0.05f;
+    if (o.normal_threshold == 0.f) o.normal_threshold = 0.9f;
+    return MCPT_OK;
+}
+// rp_reproject_kernel from the view `old_cam` into the view `new_cam` on the context's stream: `out` gets the reprojected film, *count the pixels
+// reused.  An old view whose image basis is singular has no inverse projection: the film is cleared instead (no pixel reused).
+static mcpt_status rp_run(mcpt_ctx* ctx, const DevCamera& old_cam, const DevCamera& new_cam, const mcpt_reproject_opts& o, const float4* old_film,
+                          const float4* old_feat, const float4* new_feat, float4* out, unsigned long long* count) {
+    RpParams p;
+    p.old_cam = old_cam; p.new_cam = new_cam;
+    p.max_history = o.max_history; p.depth_tolerance = o.depth_tolerance; p.normal_threshold = o.normal_threshold;
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned long long), ctx->stream));
+    if (!rp_basis_inverse(old_cam, p.inv)) {
+        HIP_TRY(hipMemsetAsync(out, 0, size_t(ctx->width) * ctx->height * sizeof(float4), ctx->stream));
+        return MCPT_OK;
+    }
+    HIP_TRY(launch_rp_reproject(p, old_film, old_feat, new_feat, out, count, ctx->stream));
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_set_camera_reproject(mcpt_ctx* ctx, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    st = check_camera(ctx, cm, "mcpt_set_camera_reproject"); if (st != MCPT_OK) return st;
+    mcpt_reproject_opts o;
+    st = rp_read_opts(opts, o, "mcpt_set_camera_reproject"); if (st != MCPT_OK) return st;
+    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
+    const size_t n = size_t(ctx->width) * ctx->height;
+    if (!ctx->rp_film_old.p) {                                             // committed only when all of it is there
+        DevBuf feat_old, film_old, count, feat; Event e0, e1;
+        HIP_TRY(feat_old.alloc(2 * n * sizeof(float4), &ctx->info.device_bytes));
+        HIP_TRY(film_old.alloc(n * sizeof(float4), &ctx->info.device_bytes));
+        HIP_TRY(count.alloc(sizeof(unsigned long long)));
+        if (!ctx->dn_feat.p) HIP_TRY(feat.alloc(2 * n * sizeof(float4), &ctx->info.device_bytes));
+        HIP_TRY(hipEventCreate(e0.out())); HIP_TRY(hipEventCreate(e1.out()));
+        ctx->rp_feat_old = std::move(feat_old); ctx->rp_film_old = std::move(film_old); ctx->rp_count = std::move(count);
+        if (!ctx->dn_feat.p) ctx->dn_feat = std::move(feat);
+        ctx->rp_ev0 = std::move(e0); ctx->rp_ev1 = std::move(e1);
+    }
+    // the last call's duration is read before its events are recorded again
+    if (ctx->rp_timed) { HIP_TRY(hipEventSynchronize(ctx->rp_ev1)); float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ctx->rp_ev0, ctx->rp_ev1)); ctx->rp_last_ms = ms; ctx->rp_timed = false; }
+    // Everything below is stream work on the context's stream, ordered like mcpt_set_camera: renders enqueued before it have joined the stream,
+    // the next render's sub-pipelines fork from it after the kernel here.
+    hipStream_t s = ctx->stream;
+    const uint32_t seed_lo = uint32_t(o.feature_seed), seed_hi = uint32_t(o.feature_seed >> 32);
+    HIP_TRY(hipEventRecord(ctx->rp_ev0, s));
+    if (!ctx->dn_have_features) HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, static_cast<float4*>(ctx->dn_feat.p), s));
+    std::swap(ctx->dn_feat, ctx->rp_feat_old);                             // the old view's features are kept where they lie
+    HIP_TRY(hipMemcpyAsync(ctx->rp_film_old.p, ctx->accum, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    const DevCamera old_cam = ctx->dev.cam;
+    apply_camera(ctx, *cm);
+    HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, static_cast<float4*>(ctx->dn_feat.p), s));
+    ctx->dn_have_features = true;                                          // those of the new view: mcpt_denoise may follow at once
+    st = rp_run(ctx, old_cam, ctx->dev.cam, o, static_cast<const float4*>(ctx->rp_film_old.p), static_cast<const float4*>(ctx->rp_feat_old.p),
+                static_cast<const float4*>(ctx->dn_feat.p), ctx->accum, static_cast<unsigned long long*>(ctx->rp_count.p));
+    if (st != MCPT_OK) return st;
+    HIP_TRY(hipEventRecord(ctx->rp_ev1, s)); ctx->rp_timed = true;
+    ctx->rp_calls++;
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_get_reproject_info(mcpt_ctx* ctx, mcpt_reproject_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    if (ctx->rp_timed) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ctx->rp_ev0, ctx->rp_ev1)); ctx->rp_last_ms = ms; ctx->rp_timed = false; }
+    std::memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out; out->reprojections = ctx->rp_calls; out->last_ms = ctx->rp_last_ms;
+    if (ctx->rp_calls) {
+        unsigned long long c = 0;
+        HIP_TRY(hipMemcpy(&c, ctx->rp_count.p, sizeof c, hipMemcpyDeviceToHost));
+        out->pixels_reused = c;
+    }
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_reproject(mcpt_ctx* ctx, const mcpt_camera* old_cam, const mcpt_camera* new_cam, const float* old_film_host, const float* old_feat8_host,
+                                 const float* new_feat8_host, const mcpt_reproject_opts* opts, float* out_film_host, uint64_t* out_reused) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!old_film_host || !old_feat8_host || !new_feat8_host || !out_film_host || !out_reused) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    st = check_camera(ctx, old_cam, "mcpt_probe_reproject (old camera)"); if (st != MCPT_OK) return st;
+    st = check_camera(ctx, new_cam, "mcpt_probe_reproject (new camera)"); if (st != MCPT_OK) return st;
+    mcpt_reproject_opts o;
+    st = rp_read_opts(opts, o, "mcpt_probe_reproject"); if (st != MCPT_OK) return st;
+    const size_t n = size_t(ctx->width) * ctx->height;
+    DevCamera co, cn;
+    camera_constants(*old_cam, ctx->dev.centre, co); camera_constants(*new_cam, ctx->dev.centre, cn);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    Scratch s; float4 *film, *fo, *fn, *out; unsigned long long* count;
+    HIP_TRY(s.in(reinterpret_cast<const float4*>(old_film_host), n, &film));
+    HIP_TRY(s.in(reinterpret_cast<const float4*>(old_feat8_host), 2 * n, &fo)); HIP_TRY(s.in(reinterpret_cast<const float4*>(new_feat8_host), 2 * n, &fn));
+    HIP_TRY(s.out(n, &out)); HIP_TRY(s.out(1, &count));
+    st = rp_run(ctx, co, cn, o, film, fo, fn, out, count); if (st != MCPT_OK) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    unsigned long long c = 0;
+    HIP_TRY(hipMemcpy(&c, count, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_film_host, out, n * sizeof(float4), hipMemcpyDeviceToHost));
+    *out_reused = c;
     return MCPT_OK;
 }
 

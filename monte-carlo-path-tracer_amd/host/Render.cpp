@@ -100,6 +100,28 @@ bool Render::set_camera(Scene& scene, const CameraInfo& camera) {
     if (mcpt_set_camera(ctx, &k) != MCPT_OK) { std::cerr << "Error: mcpt_set_camera: " << mcpt_last_error() << std::endl; return false; }
     return restart(scene);
 }
+bool Render::set_camera_reproject(Scene& scene, const CameraInfo& camera, float max_history) {
+    if (!ctx) return false;
+    if (scene.width() * scene.height() * 4 != int(film.size())) { std::cerr << "Error: Render::set_camera_reproject: the Scene's size differs from the camera's" << std::endl; return false; }
+    if (target && target != &scene) { flush_into(*target); target->detach(this); target = nullptr; }   // another Scene's samples are still that Scene's
+    // the whole film of `scene` on the device: it is there already unless the Scene holds a host part (or another source does)
+    const bool upload = scene.host_samples() || (scene.source() && scene.source() != this);
+    if (upload) {
+        const float* sum = reinterpret_cast<const float*>(scene.pixels());     // (folds whichever source the Scene has; this Render's device film is empty then)
+        if (mcpt_write_accum(ctx, sum) != MCPT_OK) { std::cerr << "Error: mcpt_write_accum: " << mcpt_last_error() << std::endl; return false; }
+    }
+    const mcpt_camera k = to_camera(camera);
+    mcpt_reproject_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.feature_spp = 4; o.feature_seed = seed; o.max_history = max_history;
+    if (mcpt_set_camera_reproject(ctx, &k, &o) != MCPT_OK) {
+        std::cerr << "Error: mcpt_set_camera_reproject: " << mcpt_last_error() << std::endl;
+        if (upload && mcpt_clear_accum(ctx) != MCPT_OK) std::cerr << "Error: mcpt_clear_accum: " << mcpt_last_error() << std::endl;   // the Scene still holds them
+        return false;
+    }
+    if (upload) scene.clear();                        // the samples live on the device now (nothing is held for `scene` at this point: nothing is dropped)
+    target = &scene; scene.attach(this);
+    dirty = true; features = true;                    // the context holds the new view's features (4 samples of `seed`, what denoised() renders)
+    return true;
+}
 bool Render::update(Scene& scene, Model& m) {
     if (!ctx) return false;
     const mcpt_camera k = to_camera(m.camerainfo);

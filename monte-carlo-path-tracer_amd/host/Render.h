@@ -33,6 +33,13 @@ public:
     // picture again: the device film and `scene` are cleared, the sample numbering restarts at 0, the feature buffers are forgotten -- the
     // reference's loop goes on with render(scene) as before.  false (and an unchanged Render and Scene) on failure.
     bool set_camera(Scene& scene, const CameraInfo& camera);
+    // set_camera that carries the picture over instead of starting it again (mcpt_set_camera_reproject): everything `scene` holds
+    // is brought to the device (a host part is uploaded), looked up at the new view's surface points and left on the device as `scene`'s film,
+    // at most max_history samples per pixel (0 = the library's default); pixels without history start empty.  The sample numbering goes ON, so
+    // the next render(scene) adds samples the history has not seen.  Exact for diffuse surfaces only: glossy and mirror radiance lags behind the
+    // view until max_history new samples have diluted it.  Not for update(): moving geometry needs motion vectors.  false on failure (the Render
+    // and the Scene's samples are unchanged, the samples are then all on the host).
+    bool set_camera_reproject(Scene& scene, const CameraInfo& camera, float max_history = 0);
     bool update(Scene& scene, Model& m_model);
     Render(const Render&) = delete;
     Render& operator=(const Render&) = delete;

@@ -26,6 +26,8 @@ static void usage() {
                  "                                        (one GPU; also writes <prefix>_spp.png, a grey map of log2(samples) / log2(spp))\n"
                  "                          [--turntable N]   N frames of --spp samples each, the camera rotated about lookat around up by 360/N degrees per frame\n"
                  "                                        (one GPU; writes <prefix>_turn<frame>.png)\n"
+                 "                          [--reproject H]   with --turntable: frames after the first carry the film over (temporal reprojection, at most H samples\n"
+                 "                                        of history per pixel) instead of starting empty\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -52,6 +54,7 @@ int main(int argc, char** argv) {
     std::string filename = argv[1], out, dump_model;
     uint32_t spp = 64, batch = 0, depth = 0, gpus = 1, save_every = 0; uint64_t seed = 20251004; uint32_t flags = 0, integrator = 0; bool ref_order = false, check_only = false, shard_tiles = false, denoise = false;
     float adaptive = -1.f; uint32_t min_spp = 0, turntable = 0;
+    bool reproject = false; float history = 0.f;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -69,10 +72,12 @@ int main(int argc, char** argv) {
         else if (a == "--adaptive") adaptive = float(std::atof(next()));
         else if (a == "--min-spp") min_spp = uint32_t(std::atoi(next()));
         else if (a == "--turntable") turntable = uint32_t(std::atoi(next()));
+        else if (a == "--reproject") { reproject = true; history = float(std::atof(next())); }
         else { usage(); return 2; }
     }
     if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
     if (turntable && (gpus > 1 || adaptive >= 0.f)) { std::cerr << "Error: --turntable renders on one GPU, without --adaptive" << std::endl; return 2; }
+    if (reproject && (!turntable || !(history >= 1.f))) { std::cerr << "Error: --reproject H needs --turntable N and H >= 1" << std::endl; return 2; }
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
     std::cout << model.face.size() << " " << model.normal.size() << " " << model.vertex.size() << std::endl;   // main.cpp:14
@@ -143,7 +148,8 @@ int main(int argc, char** argv) {
             cam.eye.y = base.lookat.y + v[1] * ca + kx[1] * sa + k[1] * kv * (1.0 - ca);
             cam.eye.z = base.lookat.z + v[2] * ca + kx[2] * sa + k[2] * kv * (1.0 - ca);
             auto t0 = std::chrono::steady_clock::now();
-            if (!renders[0]->set_camera(scene, cam)) return 1;
+            // --reproject H: frames after the first keep what the previous frame saw of the same surfaces
+            if (reproject && f > 0 ? !renders[0]->set_camera_reproject(scene, cam, history) : !renders[0]->set_camera(scene, cam)) return 1;
             renders[0]->render(scene, spp);
             scene.sync();
             std::cout << "frame: " << f << "    frame cost: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << "s\n";
