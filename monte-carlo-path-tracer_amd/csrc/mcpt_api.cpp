@@ -37,6 +37,23 @@ using Event = Owned<hipEvent_t, hipEventDestroy>;
 using Stream = Owned<hipStream_t, hipStreamDestroy>;
 template <class T> using Pinned = Owned<T*, hipHostFree>;
 
+// The duration of the last refit / reprojection call: an event pair around its stream work, read once -- by the next begin() or by whoever asks
+// for last_ms after settle() -- and kept.  (The render calls' ring, mcpt_ctx::ev0 / ev1, is a different thing: many calls outstanding.)
+struct Stopwatch {
+    Event ev0, ev1; bool timed = false; double last_ms = 0.0;
+    hipError_t create() { const hipError_t e = hipEventCreate(ev0.out()); return e != hipSuccess ? e : hipEventCreate(ev1.out()); }
+    hipError_t settle() {                                // waits for the bracketed work
+        if (!timed) return hipSuccess;
+        float ms = 0.f;
+        hipError_t e = hipEventSynchronize(ev1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
+        if (e == hipSuccess) { last_ms = ms; timed = false; }
+        return e;
+    }
+    hipError_t begin(hipStream_t s) { const hipError_t e = settle(); return e != hipSuccess ? e : hipEventRecord(ev0, s); }   // (the last duration is read before the events are recorded again)
+    hipError_t end(hipStream_t s) { const hipError_t e = hipEventRecord(ev1, s); timed = e == hipSuccess; return e; }
+};
+
 // A device buffer.  `tally` (the context's mcpt_scene_info::device_bytes, or null for a buffer that is not counted) follows the allocation:
 // it grows by `bytes` when the buffer is allocated and shrinks when it is released, regrown or destroyed.
 struct DevBuf {
@@ -132,14 +149,16 @@ struct mcpt_ctx {
     std::vector<uint32_t> rf_bin_level, rf_wide_level;      // [k], [k + 1]: the nodes of height k in rf_bin_order / the records of depth k in nodes8
     std::vector<uint8_t> rf_used_vertex;                    // a face uses this vertex: it is validated
     Pinned<double> rf_stage; Event rf_stage_ev; bool rf_stage_pending = false;
-    Event rf_ev0, rf_ev1; bool rf_timed = false;
-    uint32_t rf_updates = 0; double rf_last_ms = 0.0, rf_area0 = 0.0;
+    Stopwatch rf_watch;
+    uint32_t rf_updates = 0; double rf_area0 = 0.0;
     // Temporal reprojection (reproject.hip), allocated by the first mcpt_set_camera_reproject: the old view's features (2 float4 /
     // pixel, swapped with dn_feat per call) and a copy of the old film (1 float4 / pixel), both counted in device_bytes; the reuse counter
     DevBuf rp_feat_old, rp_film_old, rp_count;
-    Event rp_ev0, rp_ev1; bool rp_timed = false;
-    uint32_t rp_calls = 0; double rp_last_ms = 0.0;
+    Stopwatch rp_watch;
+    uint32_t rp_calls = 0;
 };
+
+static mcpt_status read_back(mcpt_ctx* ctx, void* host, const void* dev, size_t bytes, bool timing = true);
 
 namespace {
 
@@ -186,9 +205,9 @@ uint64_t film_tiles(const mcpt_ctx* c) { return uint64_t((c->width + 7) / 8) * u
 mcpt_status fetch_tri_face(mcpt_ctx* c) {
     if (!c->h_tri_face.empty()) return MCPT_OK;
     std::vector<int32_t> f(size_t(c->dev.n_tris));
-    HIP_TRY(hipMemcpy(f.data(), c->dev.tri_face, f.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    c->h_tri_face.swap(f);
-    return MCPT_OK;
+    const mcpt_status st = read_back(c, f.data(), c->dev.tri_face, f.size() * sizeof(int32_t), false);
+    if (st == MCPT_OK) c->h_tri_face.swap(f);
+    return st;
 }
 
 // What a control-block snapshot taken after iteration `it` says about a job with n_shared shared work items.
@@ -219,26 +238,33 @@ std::vector<double> to_local(const mcpt_ctx* c, const double* p, size_t n) {
     return v;
 }
 
-// Device scratch of one probe / tonemap call.  The fills below go through the legacy default stream, the kernels that use the buffers
-// run on the context's stream, which is NON-BLOCKING (no implicit ordering with the default stream): hipMemset on device memory
-// returns before it has executed, so without the explicit wait a kernel could write its results first and have them zeroed afterwards
-// (seen as black regions in `mcpt_cli --save-every` images: the tonemap kernel ran ahead of its buffer's memset).
+// Device scratch and host temporaries of one probe call.  The rule of this file: once a context has been handed out, every copy and fill is an
+// ...Async call on a named stream (ctx->stream, or a sub-pipeline's L.stream for its pool) and is ordered with the kernels around it by that stream alone.
+// Host memory an enqueued copy touches must outlive it: the destructor synchronises the stream before anything here is freed, on every return path.
 struct Scratch {
+    hipStream_t stream;
     std::vector<void*> ptrs;
-    ~Scratch() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t in(const T* host, size_t n, T** dev) {
-        hipError_t e = hipMalloc((void**)dev, (n ? n : 1) * sizeof(T)); if (e != hipSuccess) return e;
-        ptrs.push_back(*dev);
-        if (!n) return hipSuccess;
-        e = hipMemcpy(*dev, host, n * sizeof(T), hipMemcpyHostToDevice); if (e != hipSuccess) return e;
-        return hipStreamSynchronize(nullptr);
+    std::vector<std::shared_ptr<void>> held;
+    explicit Scratch(hipStream_t s) : stream(s) {}
+    Scratch(const Scratch&) = delete;
+    ~Scratch() { (void)finish(); for (void* p : ptrs) (void)hipFree(p); }
+    template <class T> T* keep(std::vector<T> v) {       // a host temporary that lives as long as the copies that use it
+        auto h = std::make_shared<std::vector<T>>(std::move(v));
+        held.push_back(h);
+        return h->data();
     }
-    template <class T> hipError_t out(size_t n, T** dev) {
-        hipError_t e = hipMalloc((void**)dev, (n ? n : 1) * sizeof(T)); if (e != hipSuccess) return e;
-        ptrs.push_back(*dev);
-        e = hipMemset(*dev, 0, (n ? n : 1) * sizeof(T)); if (e != hipSuccess) return e;
-        return hipStreamSynchronize(nullptr);
+    template <class T> hipError_t alloc(size_t n, T** dev) {
+        const hipError_t e = hipMalloc((void**)dev, (n ? n : 1) * sizeof(T));
+        if (e == hipSuccess) ptrs.push_back(*dev);
+        return e;
     }
+    // n counts elements of the host type
+    template <class T> hipError_t put(void* dev, const T* host, size_t n) { return n ? hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, stream) : hipSuccess; }
+    template <class T> hipError_t fetch(T* host, const void* dev, size_t n) { return n ? hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, stream) : hipSuccess; }
+    hipError_t fill(void* dev, int byte, size_t bytes) { return hipMemsetAsync(dev, byte, bytes, stream); }
+    template <class T> hipError_t in(const T* host, size_t n, T** dev) { const hipError_t e = alloc(n, dev); return e != hipSuccess ? e : put(*dev, host, n); }
+    template <class T> hipError_t out(size_t n, T** dev) { const hipError_t e = alloc(n, dev); return e != hipSuccess ? e : fill(*dev, 0, (n ? n : 1) * sizeof(T)); }
+    hipError_t finish() { return hipStreamSynchronize(stream); }
 };
 
 }  // namespace
@@ -321,10 +347,10 @@ static void fill_wide_info(mcpt_scene_info& in, const HostScene& hs) {
 
 
 // ------------------------------------------------------------------------------------------------ live scenes: set-up
-// The per-block partial sums the last launch_rf_wide_area left in rf_area, added up.  The caller has synchronised the stream.
+// The per-block partial sums the last launch_rf_wide_area left in rf_area, added up.  Synchronises.
 static mcpt_status rf_read_area(mcpt_ctx* c, double& out) {
     std::vector<double> part(rf_area_blocks(uint32_t(c->dev.n_nodes8)));
-    HIP_TRY(hipMemcpy(part.data(), c->rf_area.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const mcpt_status st = read_back(c, part.data(), c->rf_area.p, part.size() * sizeof(double), false); if (st != MCPT_OK) return st;
     out = 0.0;
     for (double v : part) out += v;
     return MCPT_OK;
@@ -332,7 +358,6 @@ static mcpt_status rf_read_area(mcpt_ctx* c, double& out) {
 // Sum of the dequantised child-box areas of the context's 8-wide tree, as it is on the device when the stream reaches this point.  Synchronises.
 static mcpt_status rf_wide_area(mcpt_ctx* c, double& out) {
     HIP_TRY(launch_rf_wide_area(c->dev.nodes8, uint32_t(c->dev.n_nodes8), static_cast<double*>(c->rf_area.p), c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
     return rf_read_area(c, out);
 }
 static mcpt_status rf_alloc(mcpt_ctx* c) {
@@ -344,7 +369,7 @@ static mcpt_status rf_alloc(mcpt_ctx* c) {
     HIP_TRY(c->rf_area.alloc(size_t(rf_area_blocks(uint32_t(n8))) * sizeof(double), tally));
     HIP_TRY(hipHostMalloc((void**)c->rf_stage.out(), (size_t(c->rf_n_vertex) + c->rf_n_normal) * 3 * sizeof(double) + 16, hipHostMallocDefault));
     HIP_TRY(hipEventCreateWithFlags(c->rf_stage_ev.out(), hipEventDisableTiming));
-    HIP_TRY(hipEventCreate(c->rf_ev0.out())); HIP_TRY(hipEventCreate(c->rf_ev1.out()));
+    HIP_TRY(c->rf_watch.create());
     c->dynamic = true;
     return MCPT_OK;
 }
@@ -355,9 +380,9 @@ static mcpt_status rf_setup(mcpt_ctx* c, const HostScene& hs, const mcpt_scene_d
     c->rf_used_vertex.assign(scene->n_vertex, 0);
     for (size_t i = 0; i < hs.dyn_idx.size(); i += 6) for (int k = 0; k < 3; k++) c->rf_used_vertex[size_t(hs.dyn_idx[i + k])] = 1;
     mcpt_status st = rf_alloc(c); if (st != MCPT_OK) return st;
-    HIP_TRY(hipMemcpy(c->rf_idx.p, hs.dyn_idx.data(), c->rf_idx.bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->rf_bin_order.p, bin_order.data(), c->rf_bin_order.bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipStreamSynchronize(nullptr));
+    Scratch s(c->stream);                                                 // the uploads and the kernel that follows are ordered by the context's stream
+    HIP_TRY(s.put(c->rf_idx.p, hs.dyn_idx.data(), c->rf_idx.bytes / sizeof(int32_t)));
+    HIP_TRY(s.put(c->rf_bin_order.p, bin_order.data(), c->rf_bin_order.bytes / sizeof(uint32_t)));
     return rf_wide_area(c, c->rf_area0);
 }
 static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
@@ -561,11 +586,11 @@ static mcpt_status ensure_pool(mcpt_ctx* ctx, mcpt_ctx::WfLane& L, uint32_t P) {
         const size_t bytes = size_t(r.count) * r.elem;
         DevBuf b;
         HIP_TRY(b.alloc(bytes, &ctx->info.device_bytes));
-        HIP_TRY(hipMemset(b.p, 0, bytes));
+        HIP_TRY(hipMemsetAsync(b.p, 0, bytes, L.stream));
         *r.field = b.p;
         L.pool_bufs.push_back(std::move(b));
     }
-    HIP_TRY(hipStreamSynchronize(nullptr));                              // (the fills ran on the default stream)
+    HIP_TRY(hipStreamSynchronize(L.stream));                             // (a caller on ctx->stream, mcpt_probe_trace4, sees filled buffers too)
     L.pool.P = P;
     return MCPT_OK;
 }
@@ -864,11 +889,12 @@ mcpt_status mcpt_sync(mcpt_ctx* ctx) {
     return resolve_timing(ctx);
 }
 
-// What the read entry points do once their arguments are checked: drain the stream, copy to the caller, read the finished calls' durations.
-static mcpt_status read_back(mcpt_ctx* ctx, void* host, const void* dev, size_t bytes) {
+// Every device-to-host read of a handed-out context: the copy in stream order, the stream drained (`host` is complete and may be let go), and,
+// with `timing`, the finished calls' durations read -- what the read entry points do once their arguments are checked.
+static mcpt_status read_back(mcpt_ctx* ctx, void* host, const void* dev, size_t bytes, bool timing) {
+    if (bytes) HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
-    return resolve_timing(ctx);
+    return timing ? resolve_timing(ctx) : MCPT_OK;
 }
 mcpt_status mcpt_read_accum(mcpt_ctx* ctx, float* rgba_host) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
@@ -878,9 +904,8 @@ mcpt_status mcpt_read_accum(mcpt_ctx* ctx, float* rgba_host) {
 mcpt_status mcpt_write_accum(mcpt_ctx* ctx, const float* rgba_host) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!rgba_host) return fail(MCPT_ERR_INVALID_ARG, "null input");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(ctx->accum, rgba_host, size_t(ctx->width) * ctx->height * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpyAsync(ctx->accum, rgba_host, size_t(ctx->width) * ctx->height * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                        // (the caller's array is free again)
     return MCPT_OK;
 }
 mcpt_status mcpt_clear_accum(mcpt_ctx* ctx) {
@@ -938,10 +963,8 @@ mcpt_status mcpt_tonemap_buffer(mcpt_ctx* ctx, const void* device_rgba, uint8_t*
 mcpt_status mcpt_get_counters(mcpt_ctx* ctx, mcpt_counters* out) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
     std::vector<DevCounters> rep(WF_COUNTER_REPLICAS);               // kernels spread their atomics over replicas; sum them here
-    HIP_TRY(hipMemcpy(rep.data(), ctx->counters.p, sizeof(DevCounters) * WF_COUNTER_REPLICAS, hipMemcpyDeviceToHost));
+    st = read_back(ctx, rep.data(), ctx->counters.p, sizeof(DevCounters) * WF_COUNTER_REPLICAS); if (st != MCPT_OK) return st;
     std::memset(out, 0, sizeof *out);
     for (const DevCounters& r : rep) {
         out->paths += r.paths; out->rays_primary += r.rays_primary; out->rays_continuation += r.rays_continuation; out->rays_shadow += r.rays_shadow;
@@ -954,9 +977,8 @@ mcpt_status mcpt_get_counters(mcpt_ctx* ctx, mcpt_counters* out) {
 }
 mcpt_status mcpt_reset_counters(mcpt_ctx* ctx) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    HIP_TRY(hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters) * WF_COUNTER_REPLICAS, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemset(ctx->counters.p, 0, sizeof(DevCounters) * WF_COUNTER_REPLICAS));
-    HIP_TRY(hipStreamSynchronize(nullptr));                          // (default-stream fill vs kernels on the non-blocking context stream: see Scratch)
     st = resolve_timing(ctx); if (st != MCPT_OK) return st;
     ctx->total_kernel_ms = 0.0; ctx->launches = 0; ctx->total_trace_ms = 0.0; ctx->total_shade_ms = 0.0; ctx->total_iterations = 0;
     return MCPT_OK;
@@ -1138,19 +1160,16 @@ mcpt_status mcpt_probe_tile_error(mcpt_ctx* ctx, const float* h_rgba_host, const
     if (!std::isfinite(threshold) || threshold < 0.f) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_tile_error: threshold must be finite and >= 0");
     const size_t n_px = size_t(ctx->width) * ctx->height;
     const uint32_t n_tiles = uint32_t(film_tiles(ctx)), nb = ad_blocks(n_tiles);
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    Scratch s; float4 *h, *o; float* err; uint32_t *list, *flags, *offs; uint4* counts; AdTotals* tot;
+    Scratch s(ctx->stream); float4 *h, *o; float* err; uint32_t *list, *flags, *offs; uint4* counts; AdTotals* tot;
     HIP_TRY(s.in(reinterpret_cast<const float4*>(h_rgba_host), n_px, &h)); HIP_TRY(s.in(reinterpret_cast<const float4*>(o_rgba_host), n_px, &o));
     HIP_TRY(s.out(n_tiles, &err)); HIP_TRY(s.out(n_tiles, &list)); HIP_TRY(s.out(n_tiles, &flags));
     HIP_TRY(s.out(nb, &offs)); HIP_TRY(s.out(nb, &counts)); HIP_TRY(s.out(1, &tot));
     AdScratch scr; scr.block_counts = counts; scr.block_offsets = offs; scr.flags = flags; scr.totals = tot;
     HIP_TRY(launch_ad_error_compact(h, o, ctx->width, ctx->height, threshold, max_spp, err, list, scr, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     AdTotals t;
-    HIP_TRY(hipMemcpy(&t, tot, sizeof t, hipMemcpyDeviceToHost));
+    HIP_TRY(s.fetch(&t, tot, 1)); HIP_TRY(s.fetch(out_err, err, n_tiles)); HIP_TRY(s.fetch(out_list, list, n_tiles));   // (entries past the active ones are 0)
+    HIP_TRY(s.finish());
     if (t.n_active > n_tiles) return fail(MCPT_ERR_HIP, "mcpt_probe_tile_error: active count out of range (internal error)");
-    HIP_TRY(hipMemcpy(out_err, err, n_tiles * sizeof(float), hipMemcpyDeviceToHost));
-    if (t.n_active) HIP_TRY(hipMemcpy(out_list, list, t.n_active * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *out_n = t.n_active;
     return MCPT_OK;
 }
@@ -1193,9 +1212,8 @@ mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n
         if (!(std::fabs(x[0]) <= MCPT_MAX_COORD && std::fabs(x[1]) <= MCPT_MAX_COORD && std::fabs(x[2]) <= MCPT_MAX_COORD))
             return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_vertices: vertex " + std::to_string(v) + ": coordinate is not finite or exceeds 1e18");
     }
-    // the staging buffer's last copy has been made; the last update's duration is read before its events are recorded again
+    // the staging buffer's last copy has been made
     if (ctx->rf_stage_pending) { HIP_TRY(hipEventSynchronize(ctx->rf_stage_ev)); ctx->rf_stage_pending = false; }
-    if (ctx->rf_timed) { HIP_TRY(hipEventSynchronize(ctx->rf_ev1)); float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ctx->rf_ev0, ctx->rf_ev1)); ctx->rf_last_ms = ms; ctx->rf_timed = false; }
     const size_t vd = size_t(n_vertex) * 3, nd = size_t(ctx->rf_n_normal) * 3;
     std::memcpy(ctx->rf_stage, vertex, vd * sizeof(double));
     if (normal) std::memcpy(ctx->rf_stage + vd, normal, nd * sizeof(double));
@@ -1203,7 +1221,7 @@ mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n
     // streams joined it at the end of their call, known-length jobs included) and the next render's sub-pipelines fork from it after the last
     // kernel here.
     hipStream_t s = ctx->stream;
-    HIP_TRY(hipEventRecord(ctx->rf_ev0, s));
+    HIP_TRY(ctx->rf_watch.begin(s));
     HIP_TRY(hipMemcpyAsync(ctx->rf_vtx.p, ctx->rf_stage, vd * sizeof(double), hipMemcpyHostToDevice, s));
     if (normal) HIP_TRY(hipMemcpyAsync(ctx->rf_nrm.p, ctx->rf_stage + vd, nd * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(ctx->rf_stage_ev, s)); ctx->rf_stage_pending = true;
@@ -1219,7 +1237,7 @@ mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n
     for (size_t k = ctx->rf_wide_level.size() - 1; k-- > 0;)                     // depths, deepest first
         HIP_TRY(launch_rf_wide_level(static_cast<float4*>(ctx->nodes8.p), ctx->rf_wide_level[k], ctx->rf_wide_level[k + 1], tri_box, static_cast<float*>(ctx->rf_node_box.p), s));
     HIP_TRY(launch_rf_wide_area(d.nodes8, uint32_t(d.n_nodes8), static_cast<double*>(ctx->rf_area.p), s));
-    HIP_TRY(hipEventRecord(ctx->rf_ev1, s)); ctx->rf_timed = true;
+    HIP_TRY(ctx->rf_watch.end(s));
     ctx->rf_updates++;
     rf_forget_derived(ctx);
     return MCPT_OK;
@@ -1230,9 +1248,9 @@ mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
     if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    if (ctx->rf_timed) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ctx->rf_ev0, ctx->rf_ev1)); ctx->rf_last_ms = ms; ctx->rf_timed = false; }
+    HIP_TRY(ctx->rf_watch.settle());
     std::memset(out, 0, sizeof *out);
-    out->struct_size = sizeof *out; out->updates = ctx->rf_updates; out->last_update_ms = ctx->rf_last_ms; out->wide_area_ratio = 1.0;
+    out->struct_size = sizeof *out; out->updates = ctx->rf_updates; out->last_update_ms = ctx->rf_watch.last_ms; out->wide_area_ratio = 1.0;
     if (ctx->rf_updates) {                                                      // the last update left its partial sums behind
         double a = 0.0;
         st = rf_read_area(ctx, a); if (st != MCPT_OK) return st;
@@ -1280,23 +1298,21 @@ mcpt_status mcpt_set_camera_reproject(mcpt_ctx* ctx, const mcpt_camera* cm, cons
     if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
     const size_t n = size_t(ctx->width) * ctx->height;
     if (!ctx->rp_film_old.p) {                                             // committed only when all of it is there
-        DevBuf feat_old, film_old, count, feat; Event e0, e1;
+        DevBuf feat_old, film_old, count, feat; Stopwatch watch;
         HIP_TRY(feat_old.alloc(2 * n * sizeof(float4), &ctx->info.device_bytes));
         HIP_TRY(film_old.alloc(n * sizeof(float4), &ctx->info.device_bytes));
         HIP_TRY(count.alloc(sizeof(unsigned long long)));
         if (!ctx->dn_feat.p) HIP_TRY(feat.alloc(2 * n * sizeof(float4), &ctx->info.device_bytes));
-        HIP_TRY(hipEventCreate(e0.out())); HIP_TRY(hipEventCreate(e1.out()));
+        HIP_TRY(watch.create());
         ctx->rp_feat_old = std::move(feat_old); ctx->rp_film_old = std::move(film_old); ctx->rp_count = std::move(count);
         if (!ctx->dn_feat.p) ctx->dn_feat = std::move(feat);
-        ctx->rp_ev0 = std::move(e0); ctx->rp_ev1 = std::move(e1);
+        ctx->rp_watch = std::move(watch);
     }
-    // the last call's duration is read before its events are recorded again
-    if (ctx->rp_timed) { HIP_TRY(hipEventSynchronize(ctx->rp_ev1)); float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ctx->rp_ev0, ctx->rp_ev1)); ctx->rp_last_ms = ms; ctx->rp_timed = false; }
     // Everything below is stream work on the context's stream, ordered like mcpt_set_camera: renders enqueued before it have joined the stream,
     // the next render's sub-pipelines fork from it after the kernel here.
     hipStream_t s = ctx->stream;
     const uint32_t seed_lo = uint32_t(o.feature_seed), seed_hi = uint32_t(o.feature_seed >> 32);
-    HIP_TRY(hipEventRecord(ctx->rp_ev0, s));
+    HIP_TRY(ctx->rp_watch.begin(s));
     if (!ctx->dn_have_features) HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, static_cast<float4*>(ctx->dn_feat.p), s));
     std::swap(ctx->dn_feat, ctx->rp_feat_old);                             // the old view's features are kept where they lie
     HIP_TRY(hipMemcpyAsync(ctx->rp_film_old.p, ctx->accum, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
@@ -1307,7 +1323,7 @@ mcpt_status mcpt_set_camera_reproject(mcpt_ctx* ctx, const mcpt_camera* cm, cons
     st = rp_run(ctx, old_cam, ctx->dev.cam, o, static_cast<const float4*>(ctx->rp_film_old.p), static_cast<const float4*>(ctx->rp_feat_old.p),
                 static_cast<const float4*>(ctx->dn_feat.p), ctx->accum, static_cast<unsigned long long*>(ctx->rp_count.p));
     if (st != MCPT_OK) return st;
-    HIP_TRY(hipEventRecord(ctx->rp_ev1, s)); ctx->rp_timed = true;
+    HIP_TRY(ctx->rp_watch.end(s));
     ctx->rp_calls++;
     return MCPT_OK;
 }
@@ -1315,16 +1331,11 @@ mcpt_status mcpt_set_camera_reproject(mcpt_ctx* ctx, const mcpt_camera* cm, cons
 mcpt_status mcpt_get_reproject_info(mcpt_ctx* ctx, mcpt_reproject_info* out) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    if (ctx->rp_timed) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ctx->rp_ev0, ctx->rp_ev1)); ctx->rp_last_ms = ms; ctx->rp_timed = false; }
+    unsigned long long c = 0;                                              // (no call yet: no counter to read, the stream is drained all the same)
+    st = read_back(ctx, &c, ctx->rp_count.p, ctx->rp_calls ? sizeof c : 0); if (st != MCPT_OK) return st;
+    HIP_TRY(ctx->rp_watch.settle());
     std::memset(out, 0, sizeof *out);
-    out->struct_size = sizeof *out; out->reprojections = ctx->rp_calls; out->last_ms = ctx->rp_last_ms;
-    if (ctx->rp_calls) {
-        unsigned long long c = 0;
-        HIP_TRY(hipMemcpy(&c, ctx->rp_count.p, sizeof c, hipMemcpyDeviceToHost));
-        out->pixels_reused = c;
-    }
+    out->struct_size = sizeof *out; out->reprojections = ctx->rp_calls; out->last_ms = ctx->rp_watch.last_ms; out->pixels_reused = c;
     return MCPT_OK;
 }
 
@@ -1339,16 +1350,13 @@ mcpt_status mcpt_probe_reproject(mcpt_ctx* ctx, const mcpt_camera* old_cam, cons
     const size_t n = size_t(ctx->width) * ctx->height;
     DevCamera co, cn;
     camera_constants(*old_cam, ctx->dev.centre, co); camera_constants(*new_cam, ctx->dev.centre, cn);
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    Scratch s; float4 *film, *fo, *fn, *out; unsigned long long* count;
+    Scratch s(ctx->stream); float4 *film, *fo, *fn, *out; unsigned long long* count;
     HIP_TRY(s.in(reinterpret_cast<const float4*>(old_film_host), n, &film));
     HIP_TRY(s.in(reinterpret_cast<const float4*>(old_feat8_host), 2 * n, &fo)); HIP_TRY(s.in(reinterpret_cast<const float4*>(new_feat8_host), 2 * n, &fn));
     HIP_TRY(s.out(n, &out)); HIP_TRY(s.out(1, &count));
     st = rp_run(ctx, co, cn, o, film, fo, fn, out, count); if (st != MCPT_OK) return st;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     unsigned long long c = 0;
-    HIP_TRY(hipMemcpy(&c, count, sizeof c, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_film_host, out, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(s.fetch(&c, count, 1)); HIP_TRY(s.fetch(out_film_host, out, 4 * n)); HIP_TRY(s.finish());
     *out_reused = c;
     return MCPT_OK;
 }
@@ -1360,10 +1368,9 @@ mcpt_status mcpt_probe_validate_trees(mcpt_ctx* ctx) {
     HostScene hs;
     hs.nodes.resize(ctx->nodes.bytes / sizeof(f4h)); hs.nodes8.resize(ctx->nodes8.bytes / sizeof(f4h)); hs.tri_isect.resize(ctx->tri_isect.bytes / sizeof(f4h));
     hs.tri_face.resize(size_t(ctx->dev.n_tris));
-    HIP_TRY(hipMemcpy(hs.nodes.data(), ctx->nodes.p, ctx->nodes.bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hs.nodes8.data(), ctx->nodes8.p, ctx->nodes8.bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hs.tri_isect.data(), ctx->tri_isect.p, ctx->tri_isect.bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hs.tri_face.data(), ctx->tri_face.p, ctx->tri_face.bytes, hipMemcpyDeviceToHost));
+    void* const to[4] = {hs.nodes.data(), hs.nodes8.data(), hs.tri_isect.data(), hs.tri_face.data()};
+    const DevBuf* const from[4] = {&ctx->nodes, &ctx->nodes8, &ctx->tri_isect, &ctx->tri_face};
+    for (int i = 0; i < 4; i++) { st = read_back(ctx, to[i], from[i]->p, from[i]->bytes, false); if (st != MCPT_OK) return st; }
     std::string bad = validate_bvh8(hs);
     if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, "8-wide tree: " + bad);
     bad = validate_bvh2(hs);
@@ -1378,14 +1385,11 @@ mcpt_status mcpt_probe_trace(mcpt_ctx* ctx, uint32_t n, const double* origin, co
     if (!origin || !dir || !t1 || !t2 || !out_t || !out_tri || !out_u || !out_v) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary cross-check tree of this (device-built) scene is deeper than its kernels' stack: use mcpt_probe_trace4");
     if (n == 0) return MCPT_OK;
-    Scratch s; double *d_o, *d_d, *d_t1, *d_t2; float *d_t, *d_u, *d_v; int* d_tri;
-    const std::vector<double> lo = to_local(ctx, origin, n);
-    HIP_TRY(s.in(lo.data(), 3 * size_t(n), &d_o)); HIP_TRY(s.in(dir, 3 * size_t(n), &d_d)); HIP_TRY(s.in(t1, n, &d_t1)); HIP_TRY(s.in(t2, n, &d_t2));
+    Scratch s(ctx->stream); double *d_o, *d_d, *d_t1, *d_t2; float *d_t, *d_u, *d_v; int* d_tri;
+    HIP_TRY(s.in(s.keep(to_local(ctx, origin, n)), 3 * size_t(n), &d_o)); HIP_TRY(s.in(dir, 3 * size_t(n), &d_d)); HIP_TRY(s.in(t1, n, &d_t1)); HIP_TRY(s.in(t2, n, &d_t2));
     HIP_TRY(s.out(n, &d_t)); HIP_TRY(s.out(n, &d_tri)); HIP_TRY(s.out(n, &d_u)); HIP_TRY(s.out(n, &d_v));
     HIP_TRY(launch_probe_trace(ctx->dev, n, d_o, d_d, d_t1, d_t2, any_hit, d_t, d_tri, d_u, d_v, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out_t, d_t, n * sizeof(float), hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(out_tri, d_tri, n * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_u, d_u, n * sizeof(float), hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(out_v, d_v, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(s.fetch(out_t, d_t, n)); HIP_TRY(s.fetch(out_tri, d_tri, n)); HIP_TRY(s.fetch(out_u, d_u, n)); HIP_TRY(s.fetch(out_v, d_v, n)); HIP_TRY(s.finish());
     return MCPT_OK;
 }
 
@@ -1404,8 +1408,12 @@ mcpt_status mcpt_probe_trace4(mcpt_ctx* ctx, uint32_t n, const double* origin, c
     st = ensure_pool(ctx, L, P); if (st != MCPT_OK) return st;
     PathPool pool = L.pool;
     pool.P = P;
-    std::vector<float> ro(4 * size_t(P), 0.f), rd(4 * size_t(P), 0.f), sd(4 * size_t(P), 0.f), hit(4 * size_t(P), 0.f);
-    std::vector<uint32_t> queue(P, 0u), qcount(P / WF_SHADE_BLOCK, 0u);
+    Scratch s(ctx->stream);                                           // (holds the host arrays until the stream has used them; the device side is the sub-pipeline's pool)
+    const size_t P4 = 4 * size_t(P), nb = P / WF_SHADE_BLOCK;
+    float *ro = s.keep(std::vector<float>(P4, 0.f)), *rd = s.keep(std::vector<float>(P4, 0.f)), *sd = s.keep(std::vector<float>(P4, 0.f)), *hit = s.keep(std::vector<float>(P4, 0.f));
+    uint32_t *queue = s.keep(std::vector<uint32_t>(P, 0u)), *qcount = s.keep(std::vector<uint32_t>(nb, 0u));
+    IterCtl* ctl0 = s.keep(std::vector<IterCtl>(1));                  // all zero but "iteration 0 left live slots": the trace kernel returns at once otherwise
+    ctl0->any_active[0] = 1u;
     const int32_t no_skip = -1; float no_skip_f; std::memcpy(&no_skip_f, &no_skip, 4);
     for (uint32_t i = 0; i < P; i++) {
         float* o4 = &ro[4 * size_t(i)]; float* d4 = &rd[4 * size_t(i)]; float* s4 = &sd[4 * size_t(i)];
@@ -1421,31 +1429,25 @@ mcpt_status mcpt_probe_trace4(mcpt_ctx* ctx, uint32_t n, const double* origin, c
             qcount[i / WF_SHADE_BLOCK]++;
         } else { const uint32_t one = 1u; std::memcpy(&d4[3], &one, 4); }   // bit 0 of ray_d.w: "an extend ray is pending"
     }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(pool.ray_o, ro.data(), ro.size() * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(pool.ray_d, rd.data(), rd.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pool.sq_d, sd.data(), sd.size() * 4, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(pool.sq_o, ro.data(), ro.size() * 4, hipMemcpyHostToDevice));   // queue entry i = slot i
-    HIP_TRY(hipMemset(pool.hit, 0xff, size_t(P) * 16));
-    HIP_TRY(hipMemset(pool.nee, 0, size_t(P) * 16));                 // nee.w == 0 afterwards <=> the trace kernel did not flag the ray as blocked
-    HIP_TRY(hipMemcpy(pool.shadow_queue, queue.data(), queue.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pool.shadow_count, qcount.data(), qcount.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(L.ctl_buf.p, 0, sizeof(IterCtl)));
-    { const uint32_t one = 1u; HIP_TRY(hipMemcpy(&static_cast<IterCtl*>(L.ctl_buf.p)->any_active[0], &one, 4, hipMemcpyHostToDevice)); }   // "iteration 0 left live slots": the trace kernel returns at once otherwise
-    HIP_TRY(hipStreamSynchronize(nullptr));                          // the fills above ran on the default stream; the kernel below does not wait for it by itself
+    HIP_TRY(s.put(pool.ray_o, ro, P4)); HIP_TRY(s.put(pool.ray_d, rd, P4)); HIP_TRY(s.put(pool.sq_d, sd, P4)); HIP_TRY(s.put(pool.sq_o, ro, P4));   // queue entry i = slot i
+    HIP_TRY(s.fill(pool.hit, 0xff, size_t(P) * 16));
+    HIP_TRY(s.fill(pool.nee, 0, size_t(P) * 16));                    // nee.w == 0 afterwards <=> the trace kernel did not flag the ray as blocked
+    HIP_TRY(s.put(pool.shadow_queue, queue, P)); HIP_TRY(s.put(pool.shadow_count, qcount, nb));
+    HIP_TRY(s.put(L.ctl_buf.p, ctl0, 1));
     const bool count = (ctx->opts.flags & MCPT_FLAG_COUNT_TRAVERSAL) != 0;
     HIP_TRY(launch_wf_trace(ctx->dev, pool, static_cast<IterCtl*>(L.ctl_buf.p), 0u, ctx->tune, count, static_cast<DevCounters*>(ctx->counters.p), ctx->trace_grid,
                             static_cast<int*>(L.ovf_buf.p), ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    {   IterCtl snap; HIP_TRY(hipMemcpy(&snap, L.ctl_buf.p, sizeof snap, hipMemcpyDeviceToHost));
+    {   IterCtl snap; st = read_back(ctx, &snap, L.ctl_buf.p, sizeof snap, false); if (st != MCPT_OK) return st;
         if (job_state(snap, 0u, 0u) == JobState::Watchdog) return fail(MCPT_ERR_HIP, WATCHDOG_MSG); }
     if (any_hit) {
-        HIP_TRY(hipMemcpy(hit.data(), pool.nee, hit.size() * 4, hipMemcpyDeviceToHost));     // blocked <=> the trace kernel set nee.w
+        st = read_back(ctx, hit, pool.nee, P4 * 4, false); if (st != MCPT_OK) return st;     // blocked <=> the trace kernel set nee.w
         for (uint32_t i = 0; i < n; i++) {
             uint32_t flag; std::memcpy(&flag, &hit[4 * size_t(i) + 3], 4);
             out_tri[i] = flag ? 1 : 0; out_t[i] = 0.f; out_u[i] = 0.f; out_v[i] = 0.f;
         }
     } else {
         st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
-        HIP_TRY(hipMemcpy(hit.data(), pool.hit, hit.size() * 4, hipMemcpyDeviceToHost));
+        st = read_back(ctx, hit, pool.hit, P4 * 4, false); if (st != MCPT_OK) return st;
         for (uint32_t i = 0; i < n; i++) {
             int32_t tri; std::memcpy(&tri, &hit[4 * size_t(i)], 4);
             if (tri >= 0) tri &= HIT_TRI_MASK;                          // the upper bits carry the hit's lobe class for the shade kernel
@@ -1461,11 +1463,10 @@ mcpt_status mcpt_probe_cast_ray(mcpt_ctx* ctx, uint32_t n, const int32_t* xy, co
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!xy || !xi || !out6) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (n == 0) return MCPT_OK;
-    Scratch s; int* d_xy; float *d_xi, *d_out;
+    Scratch s(ctx->stream); int* d_xy; float *d_xi, *d_out;
     HIP_TRY(s.in(xy, 2 * size_t(n), &d_xy)); HIP_TRY(s.in(xi, 2 * size_t(n), &d_xi)); HIP_TRY(s.out(6 * size_t(n), &d_out));
     HIP_TRY(launch_probe_cast_ray(ctx->dev, n, d_xy, d_xi, d_out, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out6, d_out, 6 * size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(s.fetch(out6, d_out, 6 * size_t(n))); HIP_TRY(s.finish());
     return MCPT_OK;
 }
 
@@ -1480,11 +1481,10 @@ mcpt_status mcpt_probe_hit_shade(mcpt_ctx* ctx, uint32_t n, const int32_t* face,
         if (face[i] < 0 || size_t(face[i]) >= leaf_of_face.size()) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_hit_shade: face index out of range");
         tri[i] = leaf_of_face[size_t(face[i])];
     }
-    Scratch s; int* d_tri; float *d_u, *d_v, *d_out; double* d_d;
-    HIP_TRY(s.in(tri.data(), n, &d_tri)); HIP_TRY(s.in(u, n, &d_u)); HIP_TRY(s.in(v, n, &d_v)); HIP_TRY(s.in(dir, 3 * size_t(n), &d_d)); HIP_TRY(s.out(6 * size_t(n), &d_out));
+    Scratch s(ctx->stream); int* d_tri; float *d_u, *d_v, *d_out; double* d_d;
+    HIP_TRY(s.in(s.keep(std::move(tri)), n, &d_tri)); HIP_TRY(s.in(u, n, &d_u)); HIP_TRY(s.in(v, n, &d_v)); HIP_TRY(s.in(dir, 3 * size_t(n), &d_d)); HIP_TRY(s.out(6 * size_t(n), &d_out));
     HIP_TRY(launch_probe_hit_shade(ctx->dev, n, d_tri, d_u, d_v, d_d, d_out, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out6, d_out, 6 * size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(s.fetch(out6, d_out, 6 * size_t(n))); HIP_TRY(s.finish());
     return MCPT_OK;
 }
 
@@ -1493,13 +1493,12 @@ mcpt_status mcpt_probe_bsdf(mcpt_ctx* ctx, uint32_t n, const float* normal, cons
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!normal || !wi || !kd || !ks || !ns || !wo || !xi || !out12) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (n == 0) return MCPT_OK;
-    Scratch s; float *d_n, *d_wi, *d_kd, *d_ks, *d_ns, *d_wo, *d_xi, *d_out;
+    Scratch s(ctx->stream); float *d_n, *d_wi, *d_kd, *d_ks, *d_ns, *d_wo, *d_xi, *d_out;
     HIP_TRY(s.in(normal, 3 * size_t(n), &d_n)); HIP_TRY(s.in(wi, 3 * size_t(n), &d_wi)); HIP_TRY(s.in(kd, 3 * size_t(n), &d_kd));
     HIP_TRY(s.in(ks, 3 * size_t(n), &d_ks)); HIP_TRY(s.in(ns, n, &d_ns)); HIP_TRY(s.in(wo, 3 * size_t(n), &d_wo)); HIP_TRY(s.in(xi, 3 * size_t(n), &d_xi));
     HIP_TRY(s.out(12 * size_t(n), &d_out));
     HIP_TRY(launch_probe_bsdf(n, d_n, d_wi, d_kd, d_ks, d_ns, d_wo, d_xi, d_out, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out12, d_out, 12 * size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(s.fetch(out12, d_out, 12 * size_t(n))); HIP_TRY(s.finish());
     return MCPT_OK;
 }
 
@@ -1507,12 +1506,10 @@ mcpt_status mcpt_probe_sample_light(mcpt_ctx* ctx, uint32_t n, const double* poi
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!point || !xi || !out10) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (n == 0) return MCPT_OK;
-    Scratch s; double* d_p; float *d_xi, *d_out;
-    const std::vector<double> lp = to_local(ctx, point, n);
-    HIP_TRY(s.in(lp.data(), 3 * size_t(n), &d_p)); HIP_TRY(s.in(xi, 3 * size_t(n), &d_xi)); HIP_TRY(s.out(10 * size_t(n), &d_out));
+    Scratch s(ctx->stream); double* d_p; float *d_xi, *d_out;
+    HIP_TRY(s.in(s.keep(to_local(ctx, point, n)), 3 * size_t(n), &d_p)); HIP_TRY(s.in(xi, 3 * size_t(n), &d_xi)); HIP_TRY(s.out(10 * size_t(n), &d_out));
     HIP_TRY(launch_probe_sample_light(ctx->dev, n, d_p, d_xi, d_out, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out10, d_out, 10 * size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(s.fetch(out10, d_out, 10 * size_t(n))); HIP_TRY(s.finish());
     return MCPT_OK;
 }
 
@@ -1521,9 +1518,8 @@ mcpt_status mcpt_probe_paths(mcpt_ctx* ctx, uint32_t n, const double* origin, co
     if (!origin || !dir || !out_L3) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (n == 0) return MCPT_OK;
     if (ctx->opts.integrator != MCPT_INTEGRATOR_MIS) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_probe_paths drives the MIS integrator only");
-    Scratch s; double *d_o, *d_d; float* d_out; DevCounters* d_cnt;
-    const std::vector<double> lo = to_local(ctx, origin, n);
-    HIP_TRY(s.in(lo.data(), 3 * size_t(n), &d_o)); HIP_TRY(s.in(dir, 3 * size_t(n), &d_d)); HIP_TRY(s.out(3 * size_t(n), &d_out)); HIP_TRY(s.out(1, &d_cnt));
+    Scratch s(ctx->stream); double *d_o, *d_d; float* d_out; DevCounters* d_cnt;
+    HIP_TRY(s.in(s.keep(to_local(ctx, origin, n)), 3 * size_t(n), &d_o)); HIP_TRY(s.in(dir, 3 * size_t(n), &d_d)); HIP_TRY(s.out(3 * size_t(n), &d_out)); HIP_TRY(s.out(1, &d_cnt));
     RenderParams p; std::memset(&p, 0, sizeof p);
     p.spp = 1; p.first_sample = 0; p.samples_per_item = 1; p.chunks = 1; p.tiles_x = 0x7fffffffu; p.tiles_y = 1; p.tile_mod = 1; p.tile_rem = 0; p.n_owned = 0x7fffffffu;
     p.max_depth = ctx->opts.max_depth; p.flags = ctx->opts.flags & ~MCPT_FLAG_COUNT_TRAVERSAL; p.integrator = MCPT_INTEGRATOR_MIS;
@@ -1535,10 +1531,10 @@ mcpt_status mcpt_probe_paths(mcpt_ctx* ctx, uint32_t n, const double* origin, co
         HIP_TRY(s.out(size_t(n), &d_film));
         p.probe_n = n; p.probe_o = d_o; p.probe_d = d_d;
         st = render_wavefront(ctx, p, d_film); if (st != MCPT_OK) return st;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        float* film = s.keep(std::vector<float>(4 * size_t(n)));
+        HIP_TRY(s.fetch(film, d_film, 4 * size_t(n)));
+        HIP_TRY(s.finish());
         for (auto& L : ctx->lanes) { L.last_iterations = 0; L.last_timed = 0; }
-        std::vector<float> film(4 * size_t(n));
-        HIP_TRY(hipMemcpy(film.data(), d_film, film.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < n; i++) {
             if (film[4 * size_t(i) + 3] != 1.f) return fail(MCPT_ERR_HIP, "mcpt_probe_paths: a probe path did not finish exactly once");
             for (int k = 0; k < 3; k++) out_L3[3 * size_t(i) + k] = film[4 * size_t(i) + k];
@@ -1547,8 +1543,7 @@ mcpt_status mcpt_probe_paths(mcpt_ctx* ctx, uint32_t n, const double* origin, co
     }
     if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the megakernel's traversal stack");
     HIP_TRY(launch_probe_paths(ctx->dev, p, n, d_o, d_d, d_out, d_cnt, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out_L3, d_out, 3 * size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(s.fetch(out_L3, d_out, 3 * size_t(n))); HIP_TRY(s.finish());
     return MCPT_OK;
 }
 
@@ -1557,11 +1552,10 @@ mcpt_status mcpt_probe_texture(mcpt_ctx* ctx, uint32_t material, uint32_t n, con
     if (!uv2 || !out_rgb3) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (material >= uint32_t(ctx->dev.n_mats)) return fail(MCPT_ERR_INVALID_ARG, "material index out of range");
     if (n == 0) return MCPT_OK;
-    Scratch s; float *d_uv, *d_out;
+    Scratch s(ctx->stream); float *d_uv, *d_out;
     HIP_TRY(s.in(uv2, 2 * size_t(n), &d_uv)); HIP_TRY(s.out(3 * size_t(n), &d_out));
     HIP_TRY(launch_probe_texture(ctx->dev, int(material), n, d_uv, d_out, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out_rgb3, d_out, 3 * size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(s.fetch(out_rgb3, d_out, 3 * size_t(n))); HIP_TRY(s.finish());
     return MCPT_OK;
 }
 
@@ -1569,11 +1563,10 @@ mcpt_status mcpt_probe_rng(mcpt_ctx* ctx, uint32_t n, const uint32_t* key3, uint
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!key3 || !out4) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (n == 0) return MCPT_OK;
-    Scratch s; uint32_t* d_k; float* d_out;
+    Scratch s(ctx->stream); uint32_t* d_k; float* d_out;
     HIP_TRY(s.in(key3, 3 * size_t(n), &d_k)); HIP_TRY(s.out(4 * size_t(n), &d_out));
     HIP_TRY(launch_probe_rng(n, d_k, uint32_t(seed), uint32_t(seed >> 32), d_out, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out4, d_out, 4 * size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(s.fetch(out4, d_out, 4 * size_t(n))); HIP_TRY(s.finish());
     return MCPT_OK;
 }
 

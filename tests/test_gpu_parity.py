@@ -590,6 +590,135 @@ def test_render_is_stream_ordered_with_the_callers_stream(pkg, which):
     r.bind_accum(0); r.set_stream(0); r.close()
 
 
+# Every copy and fill the library issues is ordered on the context's stream: the sequences below run on a caller stream with ~100 ms of queued
+# work in front and nothing waited for between the calls, and must give, bit for bit (FLAG_DETERMINISTIC), what the same calls give on an idle
+# context that is synchronised after every step.
+def _box(pkg):
+    return pkg.Renderer(pkg.scenes.open_box(64, 64), max_depth=4, flags=pkg.FLAG_DETERMINISTIC)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32) if a.dtype.itemsize == 4 else np.ascontiguousarray(a)
+
+
+class _BusyStream:
+    """The caller stream `which` ("side": a torch side stream, "null": torch's default = the legacy null stream), bound to `r`."""
+
+    def __init__(self, r, which):
+        import torch
+        self.torch = torch
+        self.s = torch.cuda.Stream() if which == "side" else torch.cuda.default_stream()
+        r.set_torch_stream(self.s)
+        self.big = torch.randn(4096, 4096, device="cuda")
+        torch.cuda.synchronize()
+
+    def queue_work(self):
+        big = self.big
+        with self.torch.cuda.stream(self.s):
+            for _ in range(30):
+                big = (big @ big) * 1e-3             # ~100 ms in front of whatever the library enqueues next
+
+
+@pytest.fixture(scope="module")
+def idle_box(pkg):
+    """What the synchronised sequences give on an idle context; computed once."""
+    rng = np.random.default_rng(11)
+    A = rng.random((64, 64, 4), dtype=np.float32); A[..., 3] = 3.0
+    keys = rng.integers(0, 1 << 20, (256, 3), dtype=np.uint32)
+    xy = rng.integers(0, 64, (512, 2), dtype=np.int32); xi = rng.random((512, 2), dtype=np.float32)
+    r = _box(pkg)
+    r.render(4, seed=1); r.sync()
+    film4 = r.read_accum(); tone4 = r.tonemap()
+    r.write_accum(A); r.sync(); r.render(4, seed=1); r.sync()
+    on_A = r.read_accum()
+    r.close()
+    r = _box(pkg)                                    # the probes: a fresh idle context
+    rays = r.probe_cast_ray(xy, xi)
+    d = rays[:, 3:].astype(np.float64); d[77] = 0.0  # one slot without a pending ray
+    want = {"rng": r.probe_rng(keys, 9), "cast": r.probe_cast_ray(xy[:256], xi[:256]), "trace4": r.probe_trace4(rays[:, :3], d)}
+    r.close()
+    assert want["trace4"][1][77] == -1 and (want["trace4"][1] >= 0).mean() > 0.9
+    return {"A": A, "keys": keys, "xy": xy, "xi": xi, "o": rays[:, :3].copy(), "d": d, "film4": film4, "tone4": tone4, "on_A": on_A, "probes": want}
+
+
+@pytest.mark.parametrize("which", ["side", "null"])
+def test_film_upload_render_and_read_are_stream_ordered(pkg, idle_box, which):
+    r = _box(pkg); b = _BusyStream(r, which)
+    b.queue_work()
+    r.write_accum(idle_box["A"]); r.render(4, seed=1); got = r.read_accum()
+    r.set_stream(0); r.close()
+    assert np.array_equal(got[..., 3], np.full((64, 64), 7.0))
+    assert np.array_equal(_bits(got), _bits(idle_box["on_A"]))
+
+
+@pytest.mark.parametrize("which", ["side", "null"])
+def test_counter_reset_is_stream_ordered(pkg, which):
+    r = _box(pkg); b = _BusyStream(r, which)
+    b.queue_work()
+    r.render(4, seed=1); r.reset_counters(); r.render(4, seed=1); c = r.counters()
+    r.set_stream(0); r.close()
+    assert c.paths == 64 * 64 * 4 and c.launches == 1
+
+
+@pytest.mark.parametrize("which", ["side", "null"])
+def test_probes_behind_a_render_are_stream_ordered(pkg, idle_box, which):
+    """mcpt_probe_trace4 fills the first sub-pipeline's pool, which the render before it is still using."""
+    q = idle_box
+    r = _box(pkg); b = _BusyStream(r, which)
+    b.queue_work()
+    r.render(4, seed=1)
+    rng_ = r.probe_rng(q["keys"], 9)
+    b.queue_work(); cast = r.probe_cast_ray(q["xy"][:256], q["xi"][:256])
+    b.queue_work(); t4 = r.probe_trace4(q["o"], q["d"])
+    film = r.read_accum()
+    r.set_stream(0); r.close()
+    assert np.array_equal(_bits(rng_), _bits(q["probes"]["rng"])) and np.array_equal(_bits(cast), _bits(q["probes"]["cast"]))
+    for got, want in zip(t4, q["probes"]["trace4"]):
+        assert np.array_equal(_bits(got), _bits(want))
+    assert np.array_equal(_bits(film), _bits(q["film4"]))
+
+
+@pytest.mark.parametrize("which", ["side", "null"])
+def test_tonemap_behind_a_render_is_stream_ordered(pkg, idle_box, which):
+    r = _box(pkg); b = _BusyStream(r, which)
+    b.queue_work()
+    r.render(4, seed=1); u8 = r.tonemap()
+    r.set_stream(0); r.close()
+    assert np.array_equal(u8, idle_box["tone4"])
+
+
+@pytest.mark.parametrize("which", ["side", "null"])
+def test_update_and_reprojection_durations_are_read_once_and_kept(pkg, which):
+    scene = pkg.scenes.cornell_box_small(48, 48)
+    r = pkg.Renderer(scene, max_depth=4, flags=pkg.FLAG_DETERMINISTIC | pkg.FLAG_DYNAMIC); b = _BusyStream(r, which)
+    for k in (1, 2):
+        b.queue_work()
+        r.update_vertices(scene.vertex); i = r.update_info()
+        assert i.updates == k and i.wide_area_ratio == 1.0 and i.last_update_ms > 0
+    assert r.update_info().last_update_ms == i.last_update_ms
+    for k in (1, 2):
+        b.queue_work()
+        r.reproject_camera(scene.camera); j = r.reproject_info()
+        assert j.reprojections == k and j.last_ms > 0
+    assert r.reproject_info().last_ms == j.last_ms
+    r.set_stream(0); r.close()
+
+
+def test_refused_probes_leave_nothing_enqueued(pkg, idle_box):
+    """A probe that refuses its arguments returns before it has enqueued a copy of a buffer that dies with the call."""
+    import ctypes as C
+    ERR_INVALID_ARG = 1                              # include/mcpt.h
+    r = _box(pkg)
+    h = np.zeros((64, 64, 4), np.float32); err = np.zeros(64, np.float32); lst = np.zeros(64, np.uint32); n = C.c_uint32(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert r.lib.mcpt_probe_tile_error(r.ctx, vp(h), vp(h), float("nan"), 64, vp(err), vp(lst), C.byref(n)) == ERR_INVALID_ARG
+    face = np.array([0, 10 ** 6], np.int32); uv = np.zeros(2, np.float32); d = np.ones((2, 3), np.float64); out = np.zeros((2, 6), np.float32)
+    assert r.lib.mcpt_probe_hit_shade(r.ctx, 2, vp(face), vp(uv), vp(uv), vp(d), vp(out)) == ERR_INVALID_ARG
+    r.render(4, seed=1); film = r.read_accum()
+    r.close()
+    assert np.array_equal(_bits(film), _bits(idle_box["film4"]))
+
+
 # ------------------------------------------------------------------------------------------------ BASELINE.json sizes: properties
 def test_full_size_properties_cornell_800(pkg):
     """configs[1] geometry (800x800, depth 8, 39 612 triangles) at reduced spp: sample-count plane, linearity of the film in
