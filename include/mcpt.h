@@ -279,7 +279,7 @@ mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* camera);
 mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal);
 
 typedef struct mcpt_update_info {
-    uint32_t struct_size, updates;      /* mcpt_update_vertices calls on this context so far */
+    uint32_t struct_size, updates;      /* mcpt_update_vertices (+ _reproject) calls on this context so far */
     double   last_update_ms;            /* device time of the last one, first to last operation on the stream (HIP events) */
     double   wide_area_ratio;           /* sum of the child-box areas of the 8-wide tree now / at creation (dequantised boxes; 1.0 before any update) */
     uint32_t reserved[4];
@@ -311,7 +311,7 @@ mcpt_status mcpt_probe_validate_trees(mcpt_ctx* ctx);
  *    per pixel of the feature buffers if the context never had any.  A clone starts without them.
  *  - Which first_sample / seed to continue with is the caller's business: continuing with sample indices that are already in the history
  *    correlates the new samples with it (the same paths, seen from the new eye) -- continue past them, or change the seed.
- *  - mcpt_update_vertices gets no reprojection: moving geometry needs motion vectors. */
+ *  - A camera move only: the film is carried across a vertex update by mcpt_update_vertices_reproject below, which follows the surfaces. */
 typedef struct mcpt_reproject_opts {
     uint32_t struct_size;       /* = sizeof(mcpt_reproject_opts) */
     uint32_t feature_spp;       /* features of the new view (and of the old one if the context holds none): 0 = default 4, max 64 */
@@ -322,7 +322,7 @@ typedef struct mcpt_reproject_opts {
     uint32_t reserved[3];
 } mcpt_reproject_opts;
 typedef struct mcpt_reproject_info {
-    uint32_t struct_size, reprojections;   /* mcpt_set_camera_reproject calls on this context so far */
+    uint32_t struct_size, reprojections;   /* mcpt_set_camera_reproject + mcpt_update_vertices_reproject calls on this context so far */
     uint64_t pixels_reused;                /* pixels of the last call written with a history of >= 1 sample */
     double   last_ms;                      /* device time of the last call, first to last operation on the stream (HIP events) */
     uint32_t reserved[4];
@@ -335,6 +335,42 @@ mcpt_status mcpt_get_reproject_info(mcpt_ctx* ctx, mcpt_reproject_info* out);   
 mcpt_status mcpt_probe_reproject(mcpt_ctx* ctx, const mcpt_camera* old_cam, const mcpt_camera* new_cam, const float* old_film_host,
                                  const float* old_feat8_host, const float* new_feat8_host, const mcpt_reproject_opts* opts, float* out_film_host,
                                  uint64_t* out_reused);
+
+/* ---- motion-vector reprojection: the film carried across a vertex update ------------------------------------------------ */
+/* mcpt_update_vertices_reproject is mcpt_update_vertices for a caller who wants to keep the film (needs MCPT_FLAG_DYNAMIC), optionally with a
+ * camera move in the same call (camera NULL = keep).  Per pixel of the NEW view the first hit of the pixel-centre ray in the NEW scene names a
+ * triangle and barycentrics; the vertices the scene had BEFORE the call say where that surface point was, the normals it had before say which
+ * way it faced (turned towards the old eye), and from there on it is mcpt_set_camera_reproject's projection, bilinear gather and tap rules --
+ * except that a tap's normal is compared with that OLD shading normal of the point, not with the new view's normal, so a rotating object keeps
+ * its history.  No history where mcpt_set_camera_reproject has none, nor where the centre ray misses or meets an emitter.
+ *  - Validation, in this order and all before any device work: the vertices by mcpt_update_vertices' rules, the camera (when given) by
+ *    mcpt_set_camera's, the options by the ranges above, MCPT_ERR_BVH_DEPTH where mcpt_render_features answers it.  A refusal changes nothing: not
+ *    the geometry, the camera, the film or the features held.
+ *  - Asynchronous; all device work is on the context's stream, ordered like mcpt_update_vertices: features of the current scene if none are
+ *    held, the old features / film / vertices / normals set aside, the update exactly as mcpt_update_vertices does it, the camera, the new
+ *    features, the first hits, the gather into the bound film.  Afterwards the context holds the features of the new scene and view
+ *    (mcpt_denoise may follow at once); the denoised film and the adaptive tile error are dropped; the counters are untouched.
+ *  - mcpt_get_update_info and mcpt_get_reproject_info count the call as one update and one reprojection; pixels_reused and last_ms describe it
+ *    (last_ms spans the whole call, last_update_ms its refit).
+ *  - The first call allocates 16 B per pixel (the first hits) and 24 B x (n_vertex + n_normal) (the old arrays) on top of
+ *    mcpt_set_camera_reproject's 48 B per pixel (+ 32 B per pixel if the context never had features), all counted in device_bytes.  A clone
+ *    starts without them.
+ *  - The radiance carried over is the old scene's: shadows and indirect light of what moved lag behind like glossy radiance behind the view,
+ *    and max_history bounds for how long. */
+mcpt_status mcpt_update_vertices_reproject(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal,
+                                           const mcpt_camera* camera /* NULL = keep */, const mcpt_reproject_opts* opts /* NULL = defaults */);
+/* Probes, both synchronous; neither touches the context's film, features, camera or geometry.
+ * mcpt_probe_first_hits: the first-hit kernel on the current scene and camera -- per pixel the face (Model::face order, -1 = miss) and
+ * {u, v, t} of the closest hit of the pixel-centre ray (0, 0, 0 for a miss); MCPT_ERR_BVH_DEPTH where mcpt_render_features answers it.
+ * mcpt_probe_reproject_motion: the motion kernel alone on caller data of the context's film size (a MCPT_FLAG_DYNAMIC context: the faces' vertex
+ * and normal indices and materials are the context's).  old_vertex / old_normal: n_vertex / n_normal records of the scene description, NULL =
+ * the context's current ones.  hit_face / hit_uv2: per pixel of the new view a face (Model::face order, -1 = miss) and its {u, v}, the way
+ * mcpt_probe_hit_shade takes hits; a face outside [-1, n_face) or a non-finite u or v is refused on the host.  The rest as mcpt_probe_reproject. */
+mcpt_status mcpt_probe_first_hits(mcpt_ctx* ctx, int32_t* out_face, float* out_uvt3);
+mcpt_status mcpt_probe_reproject_motion(mcpt_ctx* ctx, const mcpt_camera* old_cam, const mcpt_camera* new_cam, const double* old_vertex,
+                                        const double* old_normal, const float* old_film_host, const float* old_feat8_host, const float* new_feat8_host,
+                                        const int32_t* hit_face_host, const float* hit_uv2_host, const mcpt_reproject_opts* opts,
+                                        float* out_film_host, uint64_t* out_reused);
 
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that

@@ -240,6 +240,9 @@ def load_library() -> C.CDLL:
         "mcpt_set_camera_reproject": [vp, P(CameraC), P(ReprojectOpts)],
         "mcpt_get_reproject_info": [vp, P(ReprojectInfo)],
         "mcpt_probe_reproject": [vp, P(CameraC), P(CameraC), vp, vp, vp, P(ReprojectOpts), vp, P(C.c_uint64)],
+        "mcpt_update_vertices_reproject": [vp, vp, C.c_uint32, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
+        "mcpt_probe_first_hits": [vp, vp, vp],
+        "mcpt_probe_reproject_motion": [vp, P(CameraC), P(CameraC), vp, vp, vp, vp, vp, vp, vp, P(ReprojectOpts), vp, P(C.c_uint64)],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -263,6 +266,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_render_tile_list", "mcpt_render_adaptive", "mcpt_read_tile_error", "mcpt_probe_tile_error",
     "mcpt_set_camera", "mcpt_update_vertices", "mcpt_get_update_info", "mcpt_probe_validate_trees",
     "mcpt_set_camera_reproject", "mcpt_get_reproject_info", "mcpt_probe_reproject",
+    "mcpt_update_vertices_reproject", "mcpt_probe_first_hits", "mcpt_probe_reproject_motion",
 ]
 
 
@@ -406,6 +410,43 @@ class Renderer:
         out = np.zeros((self.height, self.width, 4), np.float32)
         reused = C.c_uint64(0)
         self._check(self.lib.mcpt_probe_reproject(self.ctx, C.byref(co), C.byref(cn), _ptr(a), _ptr(fo), _ptr(fn), C.byref(o), _ptr(out), C.byref(reused)))
+        return out, int(reused.value)
+
+    # ---- motion-vector reprojection
+    def update_vertices_reproject(self, vertex, normal=None, camera=None, **opts):
+        """update_vertices that carries the film over (optionally with a camera move in the same call): the bound film becomes the old film looked
+        up where the new view's surface points were before the update.  opts: reproject_camera's.  Needs FLAG_DYNAMIC.  Asynchronous."""
+        v = np.ascontiguousarray(vertex, np.float64).reshape(-1, 3)
+        n = None if normal is None else np.ascontiguousarray(normal, np.float64).reshape(-1, 3)
+        c = None if camera is None else C.byref(_camera_c(camera))
+        o = _reproject_opts(**opts)
+        self._check(self.lib.mcpt_update_vertices_reproject(self.ctx, _ptr(v), v.shape[0], _ptr(n), 0 if n is None else n.shape[0], c, C.byref(o)))
+
+    def probe_first_hits(self):
+        """The first-hit kernel on the current scene and camera: ((h, w) face, -1 = miss; (h, w, 3) {u, v, t})."""
+        face = np.zeros((self.height, self.width), np.int32); uvt = np.zeros((self.height, self.width, 3), np.float32)
+        self._check(self.lib.mcpt_probe_first_hits(self.ctx, _ptr(face), _ptr(uvt)))
+        return face, uvt
+
+    def probe_reproject_motion(self, old_camera, new_camera, old_film, old_feat, new_feat, hit_face, hit_uv, old_vertex=None, old_normal=None,
+                               max_history=0.0, depth_tolerance=0.0, normal_threshold=0.0):
+        """The motion kernel alone on caller data of this context's film size: ((h, w, 4) film, pixels reused).  hit_face / hit_uv: per pixel
+        of the new view a face (-1 = miss) and its (u, v); old_vertex / old_normal: None = the context's current arrays."""
+        a = np.ascontiguousarray(old_film, np.float32); fo = np.ascontiguousarray(old_feat, np.float32); fn = np.ascontiguousarray(new_feat, np.float32)
+        hf = np.ascontiguousarray(hit_face, np.int32); uv = np.ascontiguousarray(hit_uv, np.float32)
+        n = self.width * self.height
+        assert a.size == 4 * n and fo.size == 8 * n and fn.size == 8 * n and hf.size == n and uv.size == 2 * n
+        info = self.holder
+        ov = None if old_vertex is None else np.ascontiguousarray(old_vertex, np.float64).reshape(-1, 3)
+        on = None if old_normal is None else np.ascontiguousarray(old_normal, np.float64).reshape(-1, 3)
+        assert ov is None or ov.shape == info.vertex.shape
+        assert on is None or on.shape == info.normal.shape
+        co, cn = _camera_c(old_camera), _camera_c(new_camera)
+        o = _reproject_opts(0, 0, max_history, depth_tolerance, normal_threshold)
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        reused = C.c_uint64(0)
+        self._check(self.lib.mcpt_probe_reproject_motion(self.ctx, C.byref(co), C.byref(cn), _ptr(ov), _ptr(on), _ptr(a), _ptr(fo), _ptr(fn), _ptr(hf), _ptr(uv),
+                                                         C.byref(o), _ptr(out), C.byref(reused)))
         return out, int(reused.value)
 
     def update_vertices(self, vertex, normal=None):

@@ -143,6 +143,7 @@ struct mcpt_ctx {
     // Live scenes (refit.hip).  MCPT_FLAG_DYNAMIC only: per triangle its vertex and normal indices (leaf order), the device copy of
     // the caller's vertices / normals and its pinned staging, per triangle and per 8-wide node an fp32 box (refit scratch), the binary nodes sorted
     // by height and the level boundaries of both trees (one launch per level), the per-block partial sums of the wide tree's box areas.
+    // rf_vtx / rf_nrm hold the scene's CURRENT vertices and normals from creation on (§14 reads them as "the scene before this update").
     bool dynamic = false;
     uint32_t rf_n_vertex = 0, rf_n_normal = 0;
     DevBuf rf_idx, rf_vtx, rf_nrm, rf_tri_box, rf_node_box, rf_bin_order, rf_area;
@@ -153,7 +154,9 @@ struct mcpt_ctx {
     uint32_t rf_updates = 0; double rf_area0 = 0.0;
     // Temporal reprojection (reproject.hip), allocated by the first mcpt_set_camera_reproject: the old view's features (2 float4 /
     // pixel, swapped with dn_feat per call) and a copy of the old film (1 float4 / pixel), both counted in device_bytes; the reuse counter
-    DevBuf rp_feat_old, rp_film_old, rp_count;
+    // Motion-vector reprojection, allocated by the first mcpt_update_vertices_reproject and counted too: the first hit of every
+    // pixel-centre ray (1 float4 / pixel) and the vertices and normals as they were before the update (rf_vtx's and rf_nrm's sizes)
+    DevBuf rp_feat_old, rp_film_old, rp_count, rp_hits, rp_vtx_old, rp_nrm_old;
     Stopwatch rp_watch;
     uint32_t rp_calls = 0;
 };
@@ -383,7 +386,8 @@ static mcpt_status rf_setup(mcpt_ctx* c, const HostScene& hs, const mcpt_scene_d
     Scratch s(c->stream);                                                 // the uploads and the kernel that follows are ordered by the context's stream
     HIP_TRY(s.put(c->rf_idx.p, hs.dyn_idx.data(), c->rf_idx.bytes / sizeof(int32_t)));
     HIP_TRY(s.put(c->rf_bin_order.p, bin_order.data(), c->rf_bin_order.bytes / sizeof(uint32_t)));
-    return rf_wide_area(c, c->rf_area0);
+    HIP_TRY(s.put(c->rf_vtx.p, scene->vertex, size_t(scene->n_vertex) * 3)); HIP_TRY(s.put(c->rf_nrm.p, scene->normal, size_t(scene->n_normal) * 3));
+    return rf_wide_area(c, c->rf_area0);                                  // (synchronises: the caller's arrays have been read)
 }
 static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     c->rf_n_vertex = src->rf_n_vertex; c->rf_n_normal = src->rf_n_normal; c->rf_used_vertex = src->rf_used_vertex;
@@ -391,6 +395,8 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     mcpt_status st = rf_alloc(c); if (st != MCPT_OK) return st;
     HIP_TRY(hipMemcpyPeer(c->rf_idx.p, c->device, src->rf_idx.p, src->device, c->rf_idx.bytes));
     HIP_TRY(hipMemcpyPeer(c->rf_bin_order.p, c->device, src->rf_bin_order.p, src->device, c->rf_bin_order.bytes));
+    if (c->rf_vtx.bytes) HIP_TRY(hipMemcpyPeer(c->rf_vtx.p, c->device, src->rf_vtx.p, src->device, c->rf_vtx.bytes));
+    if (c->rf_nrm.bytes) HIP_TRY(hipMemcpyPeer(c->rf_nrm.p, c->device, src->rf_nrm.p, src->device, c->rf_nrm.bytes));
     HIP_TRY(hipDeviceSynchronize());
     return MCPT_OK;
 }
@@ -1200,18 +1206,23 @@ mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* cm) {
     return MCPT_OK;
 }
 
-mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_update_vertices: the context was created without MCPT_FLAG_DYNAMIC");
-    if (!vertex) return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_vertices: null vertex array");
-    if (n_vertex != ctx->rf_n_vertex) return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_vertices: n_vertex differs from the scene's");
-    if (normal && n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_vertices: n_normal differs from the scene's");
+// mcpt_update_vertices' rules for its arrays, host only; `fn` names the entry point in the message.
+static mcpt_status rf_check_update(const mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal, const char* fn) {
+    const std::string who = std::string(fn) + ": ";
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if (!vertex) return fail(MCPT_ERR_INVALID_ARG, who + "null vertex array");
+    if (n_vertex != ctx->rf_n_vertex) return fail(MCPT_ERR_INVALID_ARG, who + "n_vertex differs from the scene's");
+    if (normal && n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_normal differs from the scene's");
     for (uint32_t v = 0; v < n_vertex; v++) {
         if (!ctx->rf_used_vertex[v]) continue;
         const double* x = vertex + 3 * size_t(v);
         if (!(std::fabs(x[0]) <= MCPT_MAX_COORD && std::fabs(x[1]) <= MCPT_MAX_COORD && std::fabs(x[2]) <= MCPT_MAX_COORD))
-            return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_vertices: vertex " + std::to_string(v) + ": coordinate is not finite or exceeds 1e18");
+            return fail(MCPT_ERR_INVALID_ARG, who + "vertex " + std::to_string(v) + ": coordinate is not finite or exceeds 1e18");
     }
+    return MCPT_OK;
+}
+// The update itself, for arrays rf_check_update has passed: staged, copied and refitted on the context's stream.
+static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal) {
     // the staging buffer's last copy has been made
     if (ctx->rf_stage_pending) { HIP_TRY(hipEventSynchronize(ctx->rf_stage_ev)); ctx->rf_stage_pending = false; }
     const size_t vd = size_t(n_vertex) * 3, nd = size_t(ctx->rf_n_normal) * 3;
@@ -1241,6 +1252,12 @@ mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n
     ctx->rf_updates++;
     rf_forget_derived(ctx);
     return MCPT_OK;
+}
+
+mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    st = rf_check_update(ctx, vertex, n_vertex, normal, n_normal, "mcpt_update_vertices"); if (st != MCPT_OK) return st;
+    return rf_enqueue_update(ctx, vertex, n_vertex, normal);
 }
 
 mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
@@ -1290,6 +1307,32 @@ static mcpt_status rp_run(mcpt_ctx* ctx, const DevCamera& old_cam, const DevCame
     return MCPT_OK;
 }
 
+// The buffers of a reprojection call, allocated by the first one and committed only when all of them are there.  `motion`: also those of §14.
+static mcpt_status rp_ensure(mcpt_ctx* ctx, bool motion) {
+    const size_t n = size_t(ctx->width) * ctx->height;
+    uint64_t* tally = &ctx->info.device_bytes;
+    const bool base = !ctx->rp_film_old.p, more = motion && !ctx->rp_hits.p;
+    DevBuf feat_old, film_old, count, feat, hits, vtx_old, nrm_old; Stopwatch watch;
+    if (base) {
+        HIP_TRY(feat_old.alloc(2 * n * sizeof(float4), tally));
+        HIP_TRY(film_old.alloc(n * sizeof(float4), tally));
+        HIP_TRY(count.alloc(sizeof(unsigned long long)));
+        if (!ctx->dn_feat.p) HIP_TRY(feat.alloc(2 * n * sizeof(float4), tally));
+        HIP_TRY(watch.create());
+    }
+    if (more) {
+        HIP_TRY(hits.alloc(n * sizeof(float4), tally));
+        HIP_TRY(vtx_old.alloc(ctx->rf_vtx.bytes, tally)); HIP_TRY(nrm_old.alloc(ctx->rf_nrm.bytes, tally));
+    }
+    if (base) {
+        ctx->rp_feat_old = std::move(feat_old); ctx->rp_film_old = std::move(film_old); ctx->rp_count = std::move(count);
+        if (!ctx->dn_feat.p) ctx->dn_feat = std::move(feat);
+        ctx->rp_watch = std::move(watch);
+    }
+    if (more) { ctx->rp_hits = std::move(hits); ctx->rp_vtx_old = std::move(vtx_old); ctx->rp_nrm_old = std::move(nrm_old); }
+    return MCPT_OK;
+}
+
 mcpt_status mcpt_set_camera_reproject(mcpt_ctx* ctx, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     st = check_camera(ctx, cm, "mcpt_set_camera_reproject"); if (st != MCPT_OK) return st;
@@ -1297,17 +1340,7 @@ mcpt_status mcpt_set_camera_reproject(mcpt_ctx* ctx, const mcpt_camera* cm, cons
     st = rp_read_opts(opts, o, "mcpt_set_camera_reproject"); if (st != MCPT_OK) return st;
     if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
     const size_t n = size_t(ctx->width) * ctx->height;
-    if (!ctx->rp_film_old.p) {                                             // committed only when all of it is there
-        DevBuf feat_old, film_old, count, feat; Stopwatch watch;
-        HIP_TRY(feat_old.alloc(2 * n * sizeof(float4), &ctx->info.device_bytes));
-        HIP_TRY(film_old.alloc(n * sizeof(float4), &ctx->info.device_bytes));
-        HIP_TRY(count.alloc(sizeof(unsigned long long)));
-        if (!ctx->dn_feat.p) HIP_TRY(feat.alloc(2 * n * sizeof(float4), &ctx->info.device_bytes));
-        HIP_TRY(watch.create());
-        ctx->rp_feat_old = std::move(feat_old); ctx->rp_film_old = std::move(film_old); ctx->rp_count = std::move(count);
-        if (!ctx->dn_feat.p) ctx->dn_feat = std::move(feat);
-        ctx->rp_watch = std::move(watch);
-    }
+    st = rp_ensure(ctx, false); if (st != MCPT_OK) return st;
     // Everything below is stream work on the context's stream, ordered like mcpt_set_camera: renders enqueued before it have joined the stream,
     // the next render's sub-pipelines fork from it after the kernel here.
     hipStream_t s = ctx->stream;
@@ -1355,6 +1388,126 @@ mcpt_status mcpt_probe_reproject(mcpt_ctx* ctx, const mcpt_camera* old_cam, cons
     HIP_TRY(s.in(reinterpret_cast<const float4*>(old_feat8_host), 2 * n, &fo)); HIP_TRY(s.in(reinterpret_cast<const float4*>(new_feat8_host), 2 * n, &fn));
     HIP_TRY(s.out(n, &out)); HIP_TRY(s.out(1, &count));
     st = rp_run(ctx, co, cn, o, film, fo, fn, out, count); if (st != MCPT_OK) return st;
+    unsigned long long c = 0;
+    HIP_TRY(s.fetch(&c, count, 1)); HIP_TRY(s.fetch(out_film_host, out, 4 * n)); HIP_TRY(s.finish());
+    *out_reused = c;
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ motion-vector reprojection
+// rp_reproject_motion_kernel on the context's stream, with rp_run's contract.  `hits`: first-hit records of the new scene and view; old_vtx /
+// old_nrm: rf_n_vertex / rf_n_normal device records of the scene before the update.
+static mcpt_status rp_run_motion(mcpt_ctx* ctx, const DevCamera& old_cam, const DevCamera& new_cam, const mcpt_reproject_opts& o, const float4* hits,
+                                 const double* old_vtx, const double* old_nrm, const float4* old_film, const float4* old_feat, const float4* new_feat,
+                                 float4* out, unsigned long long* count) {
+    RpParams p;
+    p.old_cam = old_cam; p.new_cam = new_cam;
+    p.max_history = o.max_history; p.depth_tolerance = o.depth_tolerance; p.normal_threshold = o.normal_threshold;
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned long long), ctx->stream));
+    if (!rp_basis_inverse(old_cam, p.inv)) {
+        HIP_TRY(hipMemsetAsync(out, 0, size_t(ctx->width) * ctx->height * sizeof(float4), ctx->stream));
+        return MCPT_OK;
+    }
+    RpMotion m;
+    m.hits = hits; m.idx6 = static_cast<const int32_t*>(ctx->rf_idx.p); m.old_vtx = old_vtx; m.old_nrm = old_nrm;
+    m.tri_shade = ctx->dev.tri_shade; m.mats = ctx->dev.mats;
+    for (int a = 0; a < 3; a++) m.centre[a] = ctx->dev.centre[a];
+    m.n_tris = uint32_t(ctx->dev.n_tris); m.n_vertex = ctx->rf_n_vertex; m.n_normal = ctx->rf_n_normal; m.n_mats = uint32_t(ctx->dev.n_mats);
+    HIP_TRY(launch_rp_reproject_motion(p, m, old_film, old_feat, new_feat, out, count, ctx->stream));
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_update_vertices_reproject(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal,
+                                           const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
+    const char* const fn = "mcpt_update_vertices_reproject";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    st = rf_check_update(ctx, vertex, n_vertex, normal, n_normal, fn); if (st != MCPT_OK) return st;
+    if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
+    mcpt_reproject_opts o;
+    st = rp_read_opts(opts, o, fn); if (st != MCPT_OK) return st;
+    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
+    st = rp_ensure(ctx, true); if (st != MCPT_OK) return st;
+    // Everything below is stream work on the context's stream, ordered like mcpt_update_vertices.
+    const size_t n = size_t(ctx->width) * ctx->height;
+    hipStream_t s = ctx->stream;
+    const uint32_t seed_lo = uint32_t(o.feature_seed), seed_hi = uint32_t(o.feature_seed >> 32);
+    HIP_TRY(ctx->rp_watch.begin(s));
+    if (!ctx->dn_have_features) HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, static_cast<float4*>(ctx->dn_feat.p), s));
+    std::swap(ctx->dn_feat, ctx->rp_feat_old);                             // the old scene's features are kept where they lie
+    HIP_TRY(hipMemcpyAsync(ctx->rp_film_old.p, ctx->accum, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->rp_vtx_old.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, s));
+    if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->rp_nrm_old.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, s));
+    const DevCamera old_cam = ctx->dev.cam;
+    st = rf_enqueue_update(ctx, vertex, n_vertex, normal); if (st != MCPT_OK) return st;
+    if (cm) apply_camera(ctx, *cm);
+    HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, static_cast<float4*>(ctx->dn_feat.p), s));
+    ctx->dn_have_features = true;                                          // those of the new scene and view: mcpt_denoise may follow at once
+    HIP_TRY(launch_rp_first_hit(ctx->dev, static_cast<float4*>(ctx->rp_hits.p), s));
+    st = rp_run_motion(ctx, old_cam, ctx->dev.cam, o, static_cast<const float4*>(ctx->rp_hits.p), static_cast<const double*>(ctx->rp_vtx_old.p),
+                       static_cast<const double*>(ctx->rp_nrm_old.p), static_cast<const float4*>(ctx->rp_film_old.p),
+                       static_cast<const float4*>(ctx->rp_feat_old.p), static_cast<const float4*>(ctx->dn_feat.p), ctx->accum,
+                       static_cast<unsigned long long*>(ctx->rp_count.p));
+    if (st != MCPT_OK) return st;
+    HIP_TRY(ctx->rp_watch.end(s));
+    ctx->rp_calls++;
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_first_hits(mcpt_ctx* ctx, int32_t* out_face, float* out_uvt3) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out_face || !out_uvt3) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the first-hit kernel's traversal stack");
+    st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
+    const size_t n = size_t(ctx->width) * ctx->height;
+    std::vector<float> rec(4 * n);
+    {   Scratch s(ctx->stream); float4* hits;
+        HIP_TRY(s.out(n, &hits));
+        HIP_TRY(launch_rp_first_hit(ctx->dev, hits, ctx->stream));
+        HIP_TRY(s.fetch(rec.data(), hits, 4 * n)); HIP_TRY(s.finish()); }
+    for (size_t i = 0; i < n; i++) {
+        int32_t tri; std::memcpy(&tri, &rec[4 * i], 4);
+        if (tri >= ctx->dev.n_tris) return fail(MCPT_ERR_HIP, "mcpt_probe_first_hits: the kernel returned an out-of-range triangle");
+        out_face[i] = tri < 0 ? -1 : ctx->h_tri_face[size_t(tri)];
+        for (int k = 0; k < 3; k++) out_uvt3[3 * i + k] = tri < 0 ? 0.f : rec[4 * i + 1 + k];
+    }
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_reproject_motion(mcpt_ctx* ctx, const mcpt_camera* old_cam, const mcpt_camera* new_cam, const double* old_vertex, const double* old_normal,
+                                        const float* old_film_host, const float* old_feat8_host, const float* new_feat8_host, const int32_t* hit_face_host,
+                                        const float* hit_uv2_host, const mcpt_reproject_opts* opts, float* out_film_host, uint64_t* out_reused) {
+    const char* const fn = "mcpt_probe_reproject_motion";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!old_film_host || !old_feat8_host || !new_feat8_host || !hit_face_host || !hit_uv2_host || !out_film_host || !out_reused) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, std::string(fn) + ": the context was created without MCPT_FLAG_DYNAMIC");
+    st = check_camera(ctx, old_cam, "mcpt_probe_reproject_motion (old camera)"); if (st != MCPT_OK) return st;
+    st = check_camera(ctx, new_cam, "mcpt_probe_reproject_motion (new camera)"); if (st != MCPT_OK) return st;
+    mcpt_reproject_opts o;
+    st = rp_read_opts(opts, o, fn); if (st != MCPT_OK) return st;
+    st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
+    const size_t n = size_t(ctx->width) * ctx->height, nf = ctx->h_tri_face.size();
+    // hits the way mcpt_probe_hit_shade takes them (Model::face indices), turned into the kernel's records on the host; nothing out of range leaves it
+    std::vector<int32_t> leaf_of_face(nf, -1);
+    for (size_t i = 0; i < nf; i++) leaf_of_face[size_t(ctx->h_tri_face[i])] = int32_t(i);
+    std::vector<float> rec(4 * n, 0.f);
+    for (size_t i = 0; i < n; i++) {
+        const int32_t f = hit_face_host[i]; const float u = hit_uv2_host[2 * i], v = hit_uv2_host[2 * i + 1];
+        if (f < -1 || (f >= 0 && size_t(f) >= nf)) return fail(MCPT_ERR_INVALID_ARG, std::string(fn) + ": face index out of range");
+        if (!std::isfinite(u) || !std::isfinite(v)) return fail(MCPT_ERR_INVALID_ARG, std::string(fn) + ": a hit's u or v is not finite");
+        const int32_t tri = f < 0 ? -1 : leaf_of_face[size_t(f)];
+        std::memcpy(&rec[4 * i], &tri, 4); rec[4 * i + 1] = u; rec[4 * i + 2] = v;
+    }
+    DevCamera co, cn;
+    camera_constants(*old_cam, ctx->dev.centre, co); camera_constants(*new_cam, ctx->dev.centre, cn);
+    Scratch s(ctx->stream); float4 *hits, *film, *fo, *fnew, *out; unsigned long long* count;
+    const double* d_vtx = static_cast<const double*>(ctx->rf_vtx.p); const double* d_nrm = static_cast<const double*>(ctx->rf_nrm.p);
+    if (old_vertex) { double* d; HIP_TRY(s.in(old_vertex, size_t(ctx->rf_n_vertex) * 3, &d)); d_vtx = d; }
+    if (old_normal) { double* d; HIP_TRY(s.in(old_normal, size_t(ctx->rf_n_normal) * 3, &d)); d_nrm = d; }
+    HIP_TRY(s.in(reinterpret_cast<const float4*>(s.keep(std::move(rec))), n, &hits));
+    HIP_TRY(s.in(reinterpret_cast<const float4*>(old_film_host), n, &film));
+    HIP_TRY(s.in(reinterpret_cast<const float4*>(old_feat8_host), 2 * n, &fo)); HIP_TRY(s.in(reinterpret_cast<const float4*>(new_feat8_host), 2 * n, &fnew));
+    HIP_TRY(s.out(n, &out)); HIP_TRY(s.out(1, &count));
+    st = rp_run_motion(ctx, co, cn, o, hits, d_vtx, d_nrm, film, fo, fnew, out, count); if (st != MCPT_OK) return st;
     unsigned long long c = 0;
     HIP_TRY(s.fetch(&c, count, 1)); HIP_TRY(s.fetch(out_film_host, out, 4 * n)); HIP_TRY(s.finish());
     *out_reused = c;

@@ -5,7 +5,8 @@
 // and a normal test against the old view's features.  What comes over is a mean and a sample count, the count capped at max_history.
 // The cap is the point of the design: reprojected radiance is exact only for view-independent (diffuse) shading; on glossy and mirror
 // surfaces it lags behind the view, and the cap bounds how long that stale radiance survives once new samples are added.  Nothing here
-// classifies lobes, and nothing follows moving geometry (that needs motion vectors).
+// classifies lobes.  Moving geometry is followed by rp_reproject_motion_kernel: the first hit of the new pixel's centre ray names a
+// triangle and barycentrics, the vertices the scene had BEFORE the update say where that surface point was, and from there on it is the same gather.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -43,3 +44,20 @@ inline bool rp_basis_inverse(const DevCamera& c, double inv[9]) {
 // *reused (zeroed by the caller, in stream order) += the pixels written with n_hist >= 1.
 hipError_t launch_rp_reproject(const RpParams& p, const float4* old_film, const float4* old_feat, const float4* new_feat, float4* out,
                                unsigned long long* reused, hipStream_t stream);
+
+// What rp_reproject_motion_kernel needs beside RpParams.  The lengths bound every index the kernel reads from memory.
+struct RpMotion {
+    const float4* hits;            // width * height {leaf-order triangle or -1, u, v, t} of the NEW scene and view (rp_first_hit_kernel's output)
+    const int32_t* idx6;           // 6 per triangle (leaf order): its three vertex indices, then its three normal indices (the refit's rf_idx)
+    const double* old_vtx;         // the vertices before the update, WORLD coordinates, 3 per vertex
+    const double* old_nrm;         // the normals before the update, 3 per normal
+    const float4* tri_shade;       // record [3].w: the triangle's material
+    const DevMaterial* mats;
+    double centre[3];              // DevScene::centre
+    uint32_t n_tris, n_vertex, n_normal, n_mats;
+};
+// The closest hit of every pixel-centre ray of sc.cam over the binary tree (the caller has checked that the tree fits the traversal stack).
+hipError_t launch_rp_first_hit(const DevScene& sc, float4* hits, hipStream_t stream);
+// launch_rp_reproject for a scene whose vertices moved: same buffers, same `reused` contract.
+hipError_t launch_rp_reproject_motion(const RpParams& p, const RpMotion& m, const float4* old_film, const float4* old_feat, const float4* new_feat,
+                                      float4* out, unsigned long long* reused, hipStream_t stream);

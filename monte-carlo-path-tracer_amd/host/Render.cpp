@@ -102,14 +102,9 @@ bool Render::set_camera(Scene& scene, const CameraInfo& camera) {
 }
 bool Render::set_camera_reproject(Scene& scene, const CameraInfo& camera, float max_history) {
     if (!ctx) return false;
-    if (scene.width() * scene.height() * 4 != int(film.size())) { std::cerr << "Error: Render::set_camera_reproject: the Scene's size differs from the camera's" << std::endl; return false; }
-    if (target && target != &scene) { flush_into(*target); target->detach(this); target = nullptr; }   // another Scene's samples are still that Scene's
-    // the whole film of `scene` on the device: it is there already unless the Scene holds a host part (or another source does)
-    const bool upload = scene.host_samples() || (scene.source() && scene.source() != this);
-    if (upload) {
-        const float* sum = reinterpret_cast<const float*>(scene.pixels());     // (folds whichever source the Scene has; this Render's device film is empty then)
-        if (mcpt_write_accum(ctx, sum) != MCPT_OK) { std::cerr << "Error: mcpt_write_accum: " << mcpt_last_error() << std::endl; return false; }
-    }
+    bool ok = false;
+    const bool upload = film_to_device(scene, "set_camera_reproject", ok);
+    if (!ok) return false;
     const mcpt_camera k = to_camera(camera);
     mcpt_reproject_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.feature_spp = 4; o.feature_seed = seed; o.max_history = max_history;
     if (mcpt_set_camera_reproject(ctx, &k, &o) != MCPT_OK) {
@@ -120,6 +115,40 @@ bool Render::set_camera_reproject(Scene& scene, const CameraInfo& camera, float 
     if (upload) scene.clear();                        // the samples live on the device now (nothing is held for `scene` at this point: nothing is dropped)
     target = &scene; scene.attach(this);
     dirty = true; features = true;                    // the context holds the new view's features (4 samples of `seed`, what denoised() renders)
+    return true;
+}
+// The whole film of `scene` on the device, as set_camera_reproject needs it: true when a host part had to be uploaded.  `ok` false on failure.
+bool Render::film_to_device(Scene& scene, const char* who, bool& ok) {
+    ok = false;
+    if (scene.width() * scene.height() * 4 != int(film.size())) { std::cerr << "Error: Render::" << who << ": the Scene's size differs from the camera's" << std::endl; return false; }
+    if (target && target != &scene) { flush_into(*target); target->detach(this); target = nullptr; }   // another Scene's samples are still that Scene's
+    // it is there already unless the Scene holds a host part (or another source does)
+    const bool upload = scene.host_samples() || (scene.source() && scene.source() != this);
+    if (upload) {
+        const float* sum = reinterpret_cast<const float*>(scene.pixels());     // (folds whichever source the Scene has; this Render's device film is empty then)
+        if (mcpt_write_accum(ctx, sum) != MCPT_OK) { std::cerr << "Error: mcpt_write_accum: " << mcpt_last_error() << std::endl; return upload; }
+    }
+    ok = true;
+    return upload;
+}
+bool Render::update_reproject(Scene& scene, Model& m, float max_history) { return update_reproject(scene, m, nullptr, max_history); }
+bool Render::update_reproject(Scene& scene, Model& m, const CameraInfo& camera, float max_history) { return update_reproject(scene, m, &camera, max_history); }
+bool Render::update_reproject(Scene& scene, Model& m, const CameraInfo* camera, float max_history) {
+    if (!ctx) return false;
+    bool ok = false;
+    const bool upload = film_to_device(scene, "update_reproject", ok);
+    if (!ok) return false;
+    mcpt_camera k; if (camera) k = to_camera(*camera);
+    mcpt_reproject_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.feature_spp = 4; o.feature_seed = seed; o.max_history = max_history;
+    if (mcpt_update_vertices_reproject(ctx, reinterpret_cast<const double*>(m.vertex.data()), uint32_t(m.vertex.size()), reinterpret_cast<const double*>(m.normal.data()),
+                                       uint32_t(m.normal.size()), camera ? &k : nullptr, &o) != MCPT_OK) {
+        std::cerr << "Error: mcpt_update_vertices_reproject: " << mcpt_last_error() << std::endl;
+        if (upload && mcpt_clear_accum(ctx) != MCPT_OK) std::cerr << "Error: mcpt_clear_accum: " << mcpt_last_error() << std::endl;   // the Scene still holds them
+        return false;
+    }
+    if (upload) scene.clear();                        // the samples live on the device now
+    target = &scene; scene.attach(this);
+    dirty = true; features = true;                    // the context holds the new scene's features (4 samples of `seed`, what denoised() renders)
     return true;
 }
 bool Render::update(Scene& scene, Model& m) {

@@ -37,10 +37,17 @@ public:
     // is brought to the device (a host part is uploaded), looked up at the new view's surface points and left on the device as `scene`'s film,
     // at most max_history samples per pixel (0 = the library's default); pixels without history start empty.  The sample numbering goes ON, so
     // the next render(scene) adds samples the history has not seen.  Exact for diffuse surfaces only: glossy and mirror radiance lags behind the
-    // view until max_history new samples have diluted it.  Not for update(): moving geometry needs motion vectors.  false on failure (the Render
+    // view until max_history new samples have diluted it.  For update() there is update_reproject below.  false on failure (the Render
     // and the Scene's samples are unchanged, the samples are then all on the host).
     bool set_camera_reproject(Scene& scene, const CameraInfo& camera, float max_history = 0);
     bool update(Scene& scene, Model& m_model);
+    // update that carries the picture over (mcpt_update_vertices_reproject): positions and normals re-read from `m_model`, the
+    // camera kept -- or, second form, replaced by `camera` in the same call (Model::camerainfo is not read).  `scene`'s film is treated as by
+    // set_camera_reproject: brought to the device, looked up where the new view's surface points WERE, left there as `scene`'s film with at most
+    // max_history samples per pixel; the sample numbering goes on.  The radiance carried over is the old scene's: what moved drags its shadows
+    // and reflections along until max_history new samples have diluted them.  false on failure (Render and the Scene's samples unchanged).
+    bool update_reproject(Scene& scene, Model& m_model, float max_history = 0);
+    bool update_reproject(Scene& scene, Model& m_model, const CameraInfo& camera, float max_history = 0);
     Render(const Render&) = delete;
     Render& operator=(const Render&) = delete;
     bool ok() const { return ctx != nullptr; }
@@ -56,6 +63,8 @@ private:
     std::vector<Color3b> denoised_rgb;
     void create(Model& m, const mcpt_opts& opts);
     bool restart(Scene& scene);
+    bool film_to_device(Scene& scene, const char* who, bool& ok);
+    bool update_reproject(Scene& scene, Model& m_model, const CameraInfo* camera, float max_history);
 };
 // Fills an mcpt_scene_desc that points INTO `m` (and into the two scratch vectors); valid while all three live.
 void model_to_desc(Model& m, std::vector<mcpt_material>& mats, std::vector<mcpt_texture>& texs, mcpt_scene_desc& d);

@@ -28,6 +28,8 @@ static void usage() {
                  "                                        (one GPU; writes <prefix>_turn<frame>.png)\n"
                  "                          [--reproject H]   with --turntable: frames after the first carry the film over (temporal reprojection, at most H samples\n"
                  "                                        of history per pixel) instead of starting empty\n"
+                 "                          [--wobble A]   with --turntable: every frame after the first also displaces the vertices by\n"
+                 "                                        A sin(2 pi frame / N) (sin 9y, sin 7z, sin 8x) (device-side refit; with --reproject the film follows the surfaces)\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -55,6 +57,7 @@ int main(int argc, char** argv) {
     uint32_t spp = 64, batch = 0, depth = 0, gpus = 1, save_every = 0; uint64_t seed = 20251004; uint32_t flags = 0, integrator = 0; bool ref_order = false, check_only = false, shard_tiles = false, denoise = false;
     float adaptive = -1.f; uint32_t min_spp = 0, turntable = 0;
     bool reproject = false; float history = 0.f;
+    bool wobble = false; double wobble_a = 0.0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -73,11 +76,14 @@ int main(int argc, char** argv) {
         else if (a == "--min-spp") min_spp = uint32_t(std::atoi(next()));
         else if (a == "--turntable") turntable = uint32_t(std::atoi(next()));
         else if (a == "--reproject") { reproject = true; history = float(std::atof(next())); }
+        else if (a == "--wobble") { wobble = true; wobble_a = std::atof(next()); }
         else { usage(); return 2; }
     }
     if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
     if (turntable && (gpus > 1 || adaptive >= 0.f)) { std::cerr << "Error: --turntable renders on one GPU, without --adaptive" << std::endl; return 2; }
     if (reproject && (!turntable || !(history >= 1.f))) { std::cerr << "Error: --reproject H needs --turntable N and H >= 1" << std::endl; return 2; }
+    if (wobble && (!turntable || !(std::fabs(wobble_a) <= 1e6))) { std::cerr << "Error: --wobble A needs --turntable N and a finite A" << std::endl; return 2; }
+    if (wobble) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
     std::cout << model.face.size() << " " << model.normal.size() << " " << model.vertex.size() << std::endl;   // main.cpp:14
@@ -137,6 +143,7 @@ int main(int argc, char** argv) {
     // --turntable N: the camera moves, the scene stays -- Render::set_camera per frame, no rebuild, no upload
     if (turntable) {
         const CameraInfo base = model.camerainfo;
+        const std::vector<dvec3> rest = model.vertex;                        // --wobble displaces from these
         const double ul = std::sqrt(base.up.x * base.up.x + base.up.y * base.up.y + base.up.z * base.up.z);
         if (!(ul > 0.0)) { std::cerr << "Error: --turntable needs a camera with an up vector" << std::endl; return 1; }
         const double k[3] = {base.up.x / ul, base.up.y / ul, base.up.z / ul}, v[3] = {base.eye.x - base.lookat.x, base.eye.y - base.lookat.y, base.eye.z - base.lookat.z};
@@ -149,6 +156,15 @@ int main(int argc, char** argv) {
             cam.eye.z = base.lookat.z + v[2] * ca + kx[2] * sa + k[2] * kv * (1.0 - ca);
             auto t0 = std::chrono::steady_clock::now();
             // --reproject H: frames after the first keep what the previous frame saw of the same surfaces
+            if (wobble && f > 0) {                                           // --wobble A: the vertices move too, and with --reproject the film follows them (§14)
+                const double s = wobble_a * std::sin(2.0 * 3.14159265358979323846 * double(f) / double(turntable));
+                for (size_t i = 0; i < rest.size(); i++) {
+                    const dvec3& p = rest[i];
+                    model.vertex[i] = dvec3{p.x + s * std::sin(9.0 * p.y), p.y + s * std::sin(7.0 * p.z), p.z + s * std::sin(8.0 * p.x)};
+                }
+                model.camerainfo = cam;
+                if (reproject ? !renders[0]->update_reproject(scene, model, cam, history) : !renders[0]->update(scene, model)) return 1;
+            } else
             if (reproject && f > 0 ? !renders[0]->set_camera_reproject(scene, cam, history) : !renders[0]->set_camera(scene, cam)) return 1;
             renders[0]->render(scene, spp);
             scene.sync();
