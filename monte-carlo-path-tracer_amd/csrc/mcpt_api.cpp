@@ -17,6 +17,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 
 namespace {
@@ -54,22 +55,67 @@ struct Stopwatch {
     hipError_t end(hipStream_t s) { const hipError_t e = hipEventRecord(ev1, s); timed = e == hipSuccess; return e; }
 };
 
-// A device buffer.  `tally` (the context's mcpt_scene_info::device_bytes, or null for a buffer that is not counted) follows the allocation:
+// A pinned host buffer that is filled by the host, copied to the device in stream order and filled again by the next call.  `copied`: the last
+// copy out of it has been made, it may be written again.
+template <class T> struct Staging {
+    Pinned<T> host; size_t cap = 0; Event copied; bool pending = false;
+    hipError_t wait() {                                  // until the buffer may be written
+        const hipError_t e = pending ? hipEventSynchronize(copied) : hipSuccess;
+        if (e == hipSuccess) pending = false;
+        return e;
+    }
+    // elements [at, at + n) to `dev` on `s`; `last`: no further copy of this filling follows -- the event is recorded
+    hipError_t send(T* dev, size_t at, size_t n, hipStream_t s, bool last = true) {
+        hipError_t e = hipMemcpyAsync(dev, host + at, n * sizeof(T), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && last) { e = hipEventRecord(copied, s); pending = e == hipSuccess; }
+        return e;
+    }
+    hipError_t grow(size_t n) {                          // to n elements, after wait(); the contents are not kept, and nothing changes on failure
+        if (n <= cap) return hipSuccess;
+        Pinned<T> h;
+        hipError_t e = hipHostMalloc(h.out(), n * sizeof(T), hipHostMallocDefault);
+        if (e == hipSuccess && !copied) e = hipEventCreateWithFlags(copied.out(), hipEventDisableTiming);
+        if (e == hipSuccess) { host = std::move(h); cap = n; }
+        return e;
+    }
+};
+
+// A device buffer of `T`s.  `tally` (the context's mcpt_scene_info::device_bytes, or null for a buffer that is not counted) follows the allocation:
 // it grows by `bytes` when the buffer is allocated and shrinks when it is released, regrown or destroyed.
-struct DevBuf {
-    void* p = nullptr; size_t bytes = 0; uint64_t* tally = nullptr;
+template <class T> struct DevBuf {
+    T* p = nullptr; size_t bytes = 0; uint64_t* tally = nullptr;
     DevBuf() = default;
     DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes), tally(o.tally) { o.p = nullptr; o.bytes = 0; }
     DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); std::swap(tally, o.tally); return *this; }
     ~DevBuf() { release(); }
+    size_t count() const { return bytes / sizeof(T); }
     void release() { if (p) { (void)hipFree(p); if (tally) *tally -= bytes; } p = nullptr; bytes = 0; }
-    hipError_t alloc(size_t n, uint64_t* count = nullptr) {
+    hipError_t alloc(size_t n, uint64_t* counted = nullptr) {             // n elements
         release();
-        const hipError_t e = hipMalloc(&p, n ? n : 16);
-        if (e == hipSuccess) { bytes = n; tally = count; if (tally) *tally += n; } else p = nullptr;
+        const hipError_t e = hipMalloc(&p, n ? n * sizeof(T) : 16);
+        if (e == hipSuccess) { bytes = n * sizeof(T); tally = counted; if (tally) *tally += bytes; } else p = nullptr;
         return e;
     }
 };
+using DevBytes = DevBuf<unsigned char>;                // the rows of ensure_pool's table: element sizes differ from row to row
+
+// "Allocate a group into locals, commit all or none": every wanted owner (`on`) is allocated afresh, in the order given, and only when all of
+// them are there do they replace their destinations.  On a failure the fresh ones die and the context is as it was, its tally included.
+template <class O> struct Want {
+    O& dst; size_t n; uint64_t* tally; bool on;
+    Want(O& d, size_t n_ = 1, uint64_t* t = nullptr, bool on_ = true) : dst(d), n(n_), tally(t), on(on_) {}
+};
+template <class T> hipError_t alloc_fresh(DevBuf<T>& b, size_t n, uint64_t* tally) { return b.alloc(n, tally); }
+template <class T> hipError_t alloc_fresh(Pinned<T>& h, size_t n, uint64_t*) { return hipHostMalloc(h.out(), n ? n * sizeof(T) : 16, hipHostMallocDefault); }
+template <class T> hipError_t alloc_fresh(Staging<T>& s, size_t n, uint64_t*) { return s.grow(n); }
+inline hipError_t alloc_fresh(Stopwatch& w, size_t, uint64_t*) { return w.create(); }
+template <class... O> hipError_t alloc_all(Want<O>... w) {
+    std::tuple<O...> fresh;
+    hipError_t e = hipSuccess;
+    std::apply([&](O&... f) { ((e = e != hipSuccess || !w.on ? e : alloc_fresh(f, w.n, w.tally)), ...); }, fresh);
+    if (e == hipSuccess) std::apply([&](O&... f) { ((w.on ? void(w.dst = std::move(f)) : void()), ...); }, fresh);
+    return e;
+}
 
 }  // namespace
 
@@ -77,7 +123,9 @@ struct mcpt_ctx {
     int device = 0;
     mcpt_opts opts{};
     DevScene dev{};
-    DevBuf nodes, nodes8, tri_isect, tri_shade, tri_pos64, tri_face, mats, lights, light_pos64, texels, accum_own, counters;
+    DevBuf<float4> nodes, nodes8, tri_isect, tri_shade, texels, accum_own;
+    DevBuf<double> tri_pos64, light_pos64;
+    DevBuf<int32_t> tri_face; DevBuf<DevMaterial> mats; DevBuf<DevLight> lights; DevBuf<DevCounters> counters;   // (counters: WF_COUNTER_REPLICAS of them)
     float4* accum = nullptr;           // bound accumulator (own or external)
     Stream own_stream; hipStream_t stream = nullptr;   // the stream in use: own_stream, the caller's (mcpt_set_stream) or the default stream
     // HIP-event brackets of the render calls whose duration has not been read yet: a ring, so that a call does not have to wait for the one
@@ -97,8 +145,8 @@ struct mcpt_ctx {
     struct WfLane {
         PathPool pool{};
         CompactBufs compact{};             // scratch of the end-of-job drain compaction (wavefront.h); capacity 0 = none (small pools)
-        std::vector<DevBuf> pool_bufs;
-        DevBuf ctl_buf, ovf_buf;
+        std::vector<DevBytes> pool_bufs;
+        DevBuf<IterCtl> ctl_buf; DevBuf<int> ovf_buf;
         Pinned<IterCtl> h_ctl;             // pinned ring of control-block snapshots (termination check)
         std::vector<Event> chk_ev;
         std::vector<Event> k_ev;           // per-kernel event chain (only with detailed timing)
@@ -127,17 +175,16 @@ struct mcpt_ctx {
     std::vector<int32_t> h_tri_face;      // leaf order -> face index, fetched on first use by mcpt_probe_trace4
     // Scene::getPixelsColor every frame (main.cpp:26-33): the tonemapped film's device buffer and its pinned host image live as long as the
     // context (allocated by the first tonemap call) -- nothing is allocated, cleared or released per frame
-    DevBuf tone_dev; Pinned<uint8_t> tone_host;
+    DevBuf<uint8_t> tone_dev; Pinned<uint8_t> tone_host;
     // Denoised preview (denoise.hip): first-hit features (2 float4 / pixel), allocated by the first mcpt_render_features; the filter's guide,
     // two ping-pong {irr, var} buffers and the denoised film (1 float4 / pixel each), allocated by the first mcpt_denoise
-    DevBuf dn_feat, dn_guide, dn_iv0, dn_iv1, dn_out;
+    DevBuf<float4> dn_feat, dn_guide, dn_iv0, dn_iv1, dn_out;
     bool dn_have_features = false, dn_have_out = false;
-    // mcpt_render_tile_list: the caller's list, staged in pinned memory and copied to the device in stream order (tl_ev: that copy has been made,
-    // the staging buffer may be written again); both grow to the longest list seen
-    DevBuf tl_dev; Pinned<uint32_t> tl_host; size_t tl_cap = 0; Event tl_ev; bool tl_pending = false;
+    // mcpt_render_tile_list: the caller's list, staged in pinned memory and copied to the device in stream order; both grow to the longest list seen
+    DevBuf<uint32_t> tl_dev; Staging<uint32_t> tl_stage;
     // Adaptive sampling (adaptive.hip), allocated by the first mcpt_render_adaptive: the half films H and O (1 float4 / pixel each), per tile
     // E_t, the active list and its flags, per error block counts and offsets, the totals and their pinned read-back
-    DevBuf ad_h, ad_o, ad_err, ad_list, ad_flags, ad_counts, ad_offs, ad_tot;
+    DevBuf<float4> ad_h, ad_o; DevBuf<float> ad_err; DevBuf<uint32_t> ad_list, ad_flags, ad_offs; DevBuf<uint4> ad_counts; DevBuf<AdTotals> ad_tot;
     Pinned<AdTotals> ad_host;
     bool ad_have_err = false;
     // Live scenes (refit.hip).  MCPT_FLAG_DYNAMIC only: per triangle its vertex and normal indices (leaf order), the device copy of
@@ -146,17 +193,17 @@ struct mcpt_ctx {
     // rf_vtx / rf_nrm hold the scene's CURRENT vertices and normals from creation on (§14 reads them as "the scene before this update").
     bool dynamic = false;
     uint32_t rf_n_vertex = 0, rf_n_normal = 0;
-    DevBuf rf_idx, rf_vtx, rf_nrm, rf_tri_box, rf_node_box, rf_bin_order, rf_area;
+    DevBuf<int32_t> rf_idx; DevBuf<double> rf_vtx, rf_nrm, rf_area; DevBuf<float> rf_tri_box, rf_node_box; DevBuf<uint32_t> rf_bin_order;
     std::vector<uint32_t> rf_bin_level, rf_wide_level;      // [k], [k + 1]: the nodes of height k in rf_bin_order / the records of depth k in nodes8
     std::vector<uint8_t> rf_used_vertex;                    // a face uses this vertex: it is validated
-    Pinned<double> rf_stage; Event rf_stage_ev; bool rf_stage_pending = false;
+    Staging<double> rf_stage;                               // the vertices, then the normals
     Stopwatch rf_watch;
     uint32_t rf_updates = 0; double rf_area0 = 0.0;
-    // Temporal reprojection (reproject.hip), allocated by the first mcpt_set_camera_reproject: the old view's features (2 float4 /
-    // pixel, swapped with dn_feat per call) and a copy of the old film (1 float4 / pixel), both counted in device_bytes; the reuse counter
-    // Motion-vector reprojection, allocated by the first mcpt_update_vertices_reproject and counted too: the first hit of every
-    // pixel-centre ray (1 float4 / pixel) and the vertices and normals as they were before the update (rf_vtx's and rf_nrm's sizes)
-    DevBuf rp_feat_old, rp_film_old, rp_count, rp_hits, rp_vtx_old, rp_nrm_old;
+    // Temporal reprojection (reproject.hip), allocated by the first reprojection call: the old view's features (2 per pixel, swapped
+    // with dn_feat per call), a copy of the old film and the reuse counter.
+    // Motion-vector reprojection adds, on the first mcpt_update_vertices_reproject: the first hit of every pixel-centre ray and
+    // the vertices and normals as they were before the update (rf_vtx's and rf_nrm's sizes).  All but the counter are counted in device_bytes.
+    DevBuf<float4> rp_feat_old, rp_film_old, rp_hits; DevBuf<unsigned long long> rp_count; DevBuf<double> rp_vtx_old, rp_nrm_old;
     Stopwatch rp_watch;
     uint32_t rp_calls = 0;
 };
@@ -169,9 +216,10 @@ mcpt_status fail(mcpt_status s, const std::string& msg) { g_err = msg; return s;
 mcpt_status hip_fail(hipError_t e, const char* what) { g_err = std::string(what) + ": " + hipGetErrorString(e); return MCPT_ERR_HIP; }
 #define HIP_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, #call); } while (0)
 
-template <class T> hipError_t upload(DevBuf& b, const std::vector<T>& v, uint64_t* tally) {
-    const hipError_t e = b.alloc(v.size() * sizeof(T), tally);
-    return e != hipSuccess || v.empty() ? e : hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+template <class T, class H> hipError_t upload(DevBuf<T>& b, const std::vector<H>& v, uint64_t* tally) {
+    static_assert(sizeof(H) == sizeof(T), "the host mirror of a device element has its size (f4h / float4)");
+    const hipError_t e = b.alloc(v.size(), tally);
+    return e != hipSuccess || v.empty() ? e : hipMemcpy(b.p, v.data(), b.bytes, hipMemcpyHostToDevice);
 }
 
 // The device must be current while the members give their handles back.
@@ -278,11 +326,10 @@ static mcpt_status finish_ctx(mcpt_ctx* c) {
     HIP_TRY(hipStreamCreateWithFlags(c->own_stream.out(), hipStreamNonBlocking));
     c->stream = c->own_stream;
     for (uint32_t i = 0; i < mcpt_ctx::TIMED; i++) { HIP_TRY(hipEventCreate(c->ev0[i].out())); HIP_TRY(hipEventCreate(c->ev1[i].out())); }
-    const size_t accum_bytes = size_t(c->width) * c->height * sizeof(float4);
-    HIP_TRY(c->accum_own.alloc(accum_bytes, &c->info.device_bytes));
-    HIP_TRY(hipMemset(c->accum_own.p, 0, accum_bytes));
-    HIP_TRY(c->counters.alloc(sizeof(DevCounters) * WF_COUNTER_REPLICAS));
-    HIP_TRY(hipMemset(c->counters.p, 0, sizeof(DevCounters) * WF_COUNTER_REPLICAS));
+    HIP_TRY(c->accum_own.alloc(size_t(c->width) * c->height, &c->info.device_bytes));
+    HIP_TRY(hipMemset(c->accum_own.p, 0, c->accum_own.bytes));
+    HIP_TRY(c->counters.alloc(WF_COUNTER_REPLICAS));
+    HIP_TRY(hipMemset(c->counters.p, 0, c->counters.bytes));
     {   // ---- wavefront pool.  Tunables are developer knobs (environment), not part of the ABI.
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, c->device));
@@ -312,8 +359,8 @@ static mcpt_status finish_ctx(mcpt_ctx* c) {
             c->lanes.resize(n_lanes);
             for (auto& L : c->lanes) {
                 L.pool.P = 0;                                             // allocated by ensure_pool() when the first job arrives
-                HIP_TRY(L.ctl_buf.alloc(sizeof(IterCtl)));
-                HIP_TRY(hipHostMalloc((void**)L.h_ctl.out(), 8 * sizeof(IterCtl), hipHostMallocDefault));
+                HIP_TRY(L.ctl_buf.alloc(1));
+                HIP_TRY(hipHostMalloc(L.h_ctl.out(), 8 * sizeof(IterCtl), hipHostMallocDefault));
                 L.chk_ev.resize(8);
                 for (auto& ev : L.chk_ev) HIP_TRY(hipEventCreateWithFlags(ev.out(), hipEventDisableTiming));
                 HIP_TRY(hipEventCreateWithFlags(L.done_ev.out(), hipEventDisableTiming));
@@ -322,18 +369,15 @@ static mcpt_status finish_ctx(mcpt_ctx* c) {
                 // pathologically deep device-built tree (depth in the hundreds) would ask for a GB per sub-pipeline -- refuse instead of allocating it
                 const size_t ovf_bytes = size_t(c->trace_grid) * wf_trace_block_threads() * wf_trace_overflow_bytes_per_lane(c->wide_depth);
                 if (ovf_bytes > (size_t(512) << 20)) return fail(MCPT_ERR_BVH_DEPTH, "wide BVH of depth " + std::to_string(c->wide_depth) + " needs a traversal-stack overflow area of " + std::to_string(ovf_bytes >> 20) + " MB per sub-pipeline: build the tree with the host builder (no MCPT_FLAG_GPU_BVH_BUILD)");
-                HIP_TRY(L.ovf_buf.alloc(ovf_bytes));
+                HIP_TRY(L.ovf_buf.alloc(ovf_bytes / sizeof(int)));
             }
         }
     }
     HIP_TRY(hipDeviceSynchronize());
-    c->accum = static_cast<float4*>(c->accum_own.p);
+    c->accum = c->accum_own.p;
     DevScene& d = c->dev;
-    d.nodes = static_cast<const float4*>(c->nodes.p); d.nodes8 = static_cast<const float4*>(c->nodes8.p);
-    d.tri_isect = static_cast<const float4*>(c->tri_isect.p);
-    d.tri_shade = static_cast<const float4*>(c->tri_shade.p); d.tri_pos64 = static_cast<const double*>(c->tri_pos64.p);
-    d.tri_face = static_cast<const int32_t*>(c->tri_face.p); d.mats = static_cast<const DevMaterial*>(c->mats.p);
-    d.lights = static_cast<const DevLight*>(c->lights.p); d.light_pos64 = static_cast<const double*>(c->light_pos64.p); d.texels = static_cast<const float4*>(c->texels.p);
+    d.nodes = c->nodes.p; d.nodes8 = c->nodes8.p; d.tri_isect = c->tri_isect.p; d.tri_shade = c->tri_shade.p; d.tri_pos64 = c->tri_pos64.p;
+    d.tri_face = c->tri_face.p; d.mats = c->mats.p; d.lights = c->lights.p; d.light_pos64 = c->light_pos64.p; d.texels = c->texels.p;
     return MCPT_OK;
 }
 
@@ -360,18 +404,17 @@ static mcpt_status rf_read_area(mcpt_ctx* c, double& out) {
 }
 // Sum of the dequantised child-box areas of the context's 8-wide tree, as it is on the device when the stream reaches this point.  Synchronises.
 static mcpt_status rf_wide_area(mcpt_ctx* c, double& out) {
-    HIP_TRY(launch_rf_wide_area(c->dev.nodes8, uint32_t(c->dev.n_nodes8), static_cast<double*>(c->rf_area.p), c->stream));
+    HIP_TRY(launch_rf_wide_area(c->dev.nodes8, uint32_t(c->dev.n_nodes8), c->rf_area.p, c->stream));
     return rf_read_area(c, out);
 }
 static mcpt_status rf_alloc(mcpt_ctx* c) {
     const size_t nt = size_t(c->dev.n_tris), n8 = size_t(c->dev.n_nodes8), n2 = size_t(c->dev.n_nodes);
     uint64_t* tally = &c->info.device_bytes;
-    HIP_TRY(c->rf_idx.alloc(nt * 6 * sizeof(int32_t), tally)); HIP_TRY(c->rf_vtx.alloc(size_t(c->rf_n_vertex) * 3 * sizeof(double), tally));
-    HIP_TRY(c->rf_nrm.alloc(size_t(c->rf_n_normal) * 3 * sizeof(double), tally)); HIP_TRY(c->rf_tri_box.alloc(nt * 6 * sizeof(float), tally));
-    HIP_TRY(c->rf_node_box.alloc(n8 * 6 * sizeof(float), tally)); HIP_TRY(c->rf_bin_order.alloc(n2 * sizeof(uint32_t), tally));
-    HIP_TRY(c->rf_area.alloc(size_t(rf_area_blocks(uint32_t(n8))) * sizeof(double), tally));
-    HIP_TRY(hipHostMalloc((void**)c->rf_stage.out(), (size_t(c->rf_n_vertex) + c->rf_n_normal) * 3 * sizeof(double) + 16, hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(c->rf_stage_ev.out(), hipEventDisableTiming));
+    HIP_TRY(c->rf_idx.alloc(nt * 6, tally)); HIP_TRY(c->rf_vtx.alloc(size_t(c->rf_n_vertex) * 3, tally));
+    HIP_TRY(c->rf_nrm.alloc(size_t(c->rf_n_normal) * 3, tally)); HIP_TRY(c->rf_tri_box.alloc(nt * 6, tally));
+    HIP_TRY(c->rf_node_box.alloc(n8 * 6, tally)); HIP_TRY(c->rf_bin_order.alloc(n2, tally));
+    HIP_TRY(c->rf_area.alloc(rf_area_blocks(uint32_t(n8)), tally));
+    HIP_TRY(c->rf_stage.grow(c->rf_vtx.count() + c->rf_nrm.count() + 2));         // (+ 2: never empty)
     HIP_TRY(c->rf_watch.create());
     c->dynamic = true;
     return MCPT_OK;
@@ -384,9 +427,8 @@ static mcpt_status rf_setup(mcpt_ctx* c, const HostScene& hs, const mcpt_scene_d
     for (size_t i = 0; i < hs.dyn_idx.size(); i += 6) for (int k = 0; k < 3; k++) c->rf_used_vertex[size_t(hs.dyn_idx[i + k])] = 1;
     mcpt_status st = rf_alloc(c); if (st != MCPT_OK) return st;
     Scratch s(c->stream);                                                 // the uploads and the kernel that follows are ordered by the context's stream
-    HIP_TRY(s.put(c->rf_idx.p, hs.dyn_idx.data(), c->rf_idx.bytes / sizeof(int32_t)));
-    HIP_TRY(s.put(c->rf_bin_order.p, bin_order.data(), c->rf_bin_order.bytes / sizeof(uint32_t)));
-    HIP_TRY(s.put(c->rf_vtx.p, scene->vertex, size_t(scene->n_vertex) * 3)); HIP_TRY(s.put(c->rf_nrm.p, scene->normal, size_t(scene->n_normal) * 3));
+    HIP_TRY(s.put(c->rf_idx.p, hs.dyn_idx.data(), c->rf_idx.count())); HIP_TRY(s.put(c->rf_bin_order.p, bin_order.data(), c->rf_bin_order.count()));
+    HIP_TRY(s.put(c->rf_vtx.p, scene->vertex, c->rf_vtx.count())); HIP_TRY(s.put(c->rf_nrm.p, scene->normal, c->rf_nrm.count()));
     return rf_wide_area(c, c->rf_area0);                                  // (synchronises: the caller's arrays have been read)
 }
 static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
@@ -509,12 +551,13 @@ mcpt_status mcpt_clone_to_device(mcpt_ctx* src, int32_t device, mcpt_ctx** out_c
     c->dev = src->dev; c->info = src->info; c->info.bvh_build_ms = 0.0; c->info.device_bytes = 0;   // (counts this context's own allocations)
     HIP_TRY(hipSetDevice(device));
     auto t0 = std::chrono::steady_clock::now();
-    DevBuf* from[10] = {&src->nodes, &src->nodes8, &src->tri_isect, &src->tri_shade, &src->tri_pos64, &src->tri_face, &src->mats, &src->lights, &src->light_pos64, &src->texels};
-    DevBuf* to[10] = {&c->nodes, &c->nodes8, &c->tri_isect, &c->tri_shade, &c->tri_pos64, &c->tri_face, &c->mats, &c->lights, &c->light_pos64, &c->texels};
-    for (int i = 0; i < 10; i++) {
-        HIP_TRY(to[i]->alloc(from[i]->bytes, &c->info.device_bytes));
-        if (from[i]->bytes) HIP_TRY(hipMemcpyPeer(to[i]->p, device, from[i]->p, src->device, from[i]->bytes));
-    }
+    auto copy = [&](auto mcpt_ctx::* m) {                                  // one scene stream: the types of the two ends agree by construction
+        const hipError_t e = (c->*m).alloc((src->*m).count(), &c->info.device_bytes);
+        return e != hipSuccess || !(src->*m).bytes ? e : hipMemcpyPeer((c->*m).p, device, (src->*m).p, src->device, (src->*m).bytes);
+    };
+    HIP_TRY(copy(&mcpt_ctx::nodes)); HIP_TRY(copy(&mcpt_ctx::nodes8)); HIP_TRY(copy(&mcpt_ctx::tri_isect)); HIP_TRY(copy(&mcpt_ctx::tri_shade));
+    HIP_TRY(copy(&mcpt_ctx::tri_pos64)); HIP_TRY(copy(&mcpt_ctx::tri_face)); HIP_TRY(copy(&mcpt_ctx::mats)); HIP_TRY(copy(&mcpt_ctx::lights));
+    HIP_TRY(copy(&mcpt_ctx::light_pos64)); HIP_TRY(copy(&mcpt_ctx::texels));
     if ((st = finish_ctx(c)) != MCPT_OK) return st;
     if (src->dynamic && (st = rf_clone(c, src)) != MCPT_OK) return st;
     c->info.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -590,7 +633,7 @@ static mcpt_status ensure_pool(mcpt_ctx* ctx, mcpt_ctx::WfLane& L, uint32_t P) {
         row(cb.beta, ccap), row(cb.L, ccap), row(cb.ray_d, ccap), row(cb.ray_o, ccap), row(cb.hit, ccap), row(cb.nee, ccap), row(cb.ids, ccap), row(cb.dst_off, nb)};
     for (const Row& r : rows) {
         const size_t bytes = size_t(r.count) * r.elem;
-        DevBuf b;
+        DevBytes b;
         HIP_TRY(b.alloc(bytes, &ctx->info.device_bytes));
         HIP_TRY(hipMemsetAsync(b.p, 0, bytes, L.stream));
         *r.field = b.p;
@@ -630,7 +673,7 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, RenderParams& p0, float4* acc
     constexpr uint32_t CHECK = 4, RING = 8;
     const bool debug = env_u32("MCPT_WF_DEBUG", 0) != 0;
     const uint32_t max_it = env_u32("MCPT_WF_MAXIT", 1u << 20);
-    DevCounters* cnt = static_cast<DevCounters*>(ctx->counters.p);
+    DevCounters* cnt = ctx->counters.p;
     struct Run { RenderParams p; PathPool pool; uint32_t n_items = 0, n_shared = 0, it = 0, issued = 0, seen = 0, bound = 0, snap_it[RING] = {0}; size_t kev = 0; bool active = false, done = false;
                  uint32_t grid = 0;         // blocks of this sub-pipeline's trace launches (below: small jobs share the CUs instead of queueing for them)
                  bool drain = false; };     // drain: a snapshot showed the shared work-item cursors exhausted -> the compaction launches follow every trace launch from here on
@@ -706,12 +749,17 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, RenderParams& p0, float4* acc
         if (!runs[k].active) continue;
         mcpt_ctx::WfLane& L = ctx->lanes[k]; Run& r = runs[k];
         HIP_TRY(hipStreamWaitEvent(L.stream, ctx->fork_ev, 0));
-        HIP_TRY(launch_wf_pool_reset(r.pool, static_cast<IterCtl*>(L.ctl_buf.p), L.stream));    // every slot DEAD, control block zeroed
+        HIP_TRY(launch_wf_pool_reset(r.pool, L.ctl_buf.p, L.stream));    // every slot DEAD, control block zeroed
     }
     auto k_event = [&](mcpt_ctx::WfLane& L, Run& r, bool timed) -> hipError_t {
         if (!timed) return hipSuccess;
         if (r.kev == L.k_ev.size()) { Event ev; hipError_t e = hipEventCreate(ev.out()); if (e != hipSuccess) return e; L.k_ev.push_back(std::move(ev)); }
         return hipEventRecord(L.k_ev[r.kev++], L.stream);
+    };
+    // the control block as it is after the launches enqueued so far, copied to slot q of the sub-pipeline's ring, and the event that says it has arrived
+    auto snapshot = [](mcpt_ctx::WfLane& L, uint32_t q) -> hipError_t {
+        const hipError_t e = hipMemcpyAsync(&L.h_ctl[q], L.ctl_buf.p, sizeof(IterCtl), hipMemcpyDeviceToHost, L.stream);
+        return e != hipSuccess ? e : hipEventRecord(L.chk_ev[q], L.stream);
     };
     // consume finished control-block snapshots of one sub-pipeline; `block` waits for the oldest one
     auto poll = [&](mcpt_ctx::WfLane& L, Run& r, bool block) -> mcpt_status {
@@ -744,12 +792,12 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, RenderParams& p0, float4* acc
             Run& r = runs[k];
             if (!r.active || r.done) continue;
             mcpt_ctx::WfLane& L = ctx->lanes[k];
-            IterCtl* ctl = static_cast<IterCtl*>(L.ctl_buf.p);
+            IterCtl* ctl = L.ctl_buf.p;
             const bool timed = ctx->time_kernels && r.it % ctx->time_kernels == 0;
             HIP_TRY(k_event(L, r, timed));
             HIP_TRY(launch_wf_shade(ctx->dev, r.p, r.pool, ctl, r.it, r.n_shared, accum, cnt, L.stream));
             HIP_TRY(k_event(L, r, timed));
-            HIP_TRY(launch_wf_trace(ctx->dev, r.pool, ctl, r.it, ctx->tune, count, cnt, r.grid, static_cast<int*>(L.ovf_buf.p), L.stream));
+            HIP_TRY(launch_wf_trace(ctx->dev, r.pool, ctl, r.it, ctx->tune, count, cnt, r.grid, L.ovf_buf.p, L.stream));
             HIP_TRY(k_event(L, r, timed));
             // end-of-job drain: move the live slots to the front of the pool once at most half of the swept ones are alive (decided on the device)
             if (r.drain && !r.bound && L.compact.capacity && r.p.samples_per_item == 1 && !p0.probe_n)
@@ -757,8 +805,7 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, RenderParams& p0, float4* acc
             r.it++;
             if (r.bound && r.it == r.bound) {                               // known-length job: all of it is enqueued; its verdict is read later
                 const uint32_t q = L.ring_next++ % RING;
-                HIP_TRY(hipMemcpyAsync(&L.h_ctl[q], ctl, sizeof(IterCtl), hipMemcpyDeviceToHost, L.stream));
-                HIP_TRY(hipEventRecord(L.chk_ev[q], L.stream));
+                HIP_TRY(snapshot(L, q));
                 L.verdicts.push_back({q, r.it - 1, r.n_shared});
                 r.done = true;
                 continue;
@@ -767,8 +814,7 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, RenderParams& p0, float4* acc
                 mcpt_status ps = poll(L, r, r.issued - r.seen >= 2); if (ps != MCPT_OK) return ps;   // at most 2 checks (8 iterations) ahead
                 if (!r.done) {
                     const uint32_t q = r.issued % RING;
-                    HIP_TRY(hipMemcpyAsync(&L.h_ctl[q], ctl, sizeof(IterCtl), hipMemcpyDeviceToHost, L.stream));
-                    HIP_TRY(hipEventRecord(L.chk_ev[q], L.stream));
+                    HIP_TRY(snapshot(L, q));
                     r.snap_it[q] = r.it - 1;
                     r.issued++;
                 }
@@ -850,7 +896,7 @@ static mcpt_status render_call(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint3
     if (ctx->use_wavefront) {
         st = render_wavefront(ctx, p, accum); if (st != MCPT_OK) return st;
     } else {
-        HIP_TRY(launch_render(ctx->dev, p, accum, static_cast<DevCounters*>(ctx->counters.p), ctx->stream));
+        HIP_TRY(launch_render(ctx->dev, p, accum, ctx->counters.p, ctx->stream));
     }
     return timed ? timed_end(ctx) : MCPT_OK;
 }
@@ -874,26 +920,23 @@ mcpt_status mcpt_render_tile_list(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, ui
         if (seen[tiles[i]]++) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_tile_list: tile " + std::to_string(tiles[i]) + " listed twice");
     }
     if (spp == 0) return MCPT_OK;
-    if (ctx->tl_pending) { HIP_TRY(hipEventSynchronize(ctx->tl_ev)); ctx->tl_pending = false; }   // the staging buffer's last copy has been made
-    if (ctx->tl_cap < n_tiles) {
+    HIP_TRY(ctx->tl_stage.wait());
+    if (ctx->tl_stage.cap < n_tiles) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));                        // (kernels of earlier calls may still read the device list)
-        DevBuf dev; Pinned<uint32_t> host;                                 // the longer pair replaces the old one only when all of it is there
-        HIP_TRY(dev.alloc(size_t(n_tiles) * sizeof(uint32_t), &ctx->info.device_bytes));
-        HIP_TRY(hipHostMalloc((void**)host.out(), size_t(n_tiles) * sizeof(uint32_t), hipHostMallocDefault));
-        if (!ctx->tl_ev) HIP_TRY(hipEventCreateWithFlags(ctx->tl_ev.out(), hipEventDisableTiming));
-        ctx->tl_dev = std::move(dev); ctx->tl_host = std::move(host); ctx->tl_cap = n_tiles;
+        HIP_TRY(alloc_all(Want(ctx->tl_dev, n_tiles, &ctx->info.device_bytes), Want(ctx->tl_stage, n_tiles)));   // the longer pair replaces the old one
     }
-    std::memcpy(ctx->tl_host, tiles, size_t(n_tiles) * sizeof(uint32_t));
-    HIP_TRY(hipMemcpyAsync(ctx->tl_dev.p, ctx->tl_host, size_t(n_tiles) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->tl_ev, ctx->stream)); ctx->tl_pending = true;
-    return render_call(ctx, spp, seed, first_sample, 1u, 0u, static_cast<const uint32_t*>(ctx->tl_dev.p), n_tiles, ctx->accum, true);
+    std::memcpy(ctx->tl_stage.host, tiles, size_t(n_tiles) * sizeof(uint32_t));
+    HIP_TRY(ctx->tl_stage.send(ctx->tl_dev.p, 0, n_tiles, ctx->stream));
+    return render_call(ctx, spp, seed, first_sample, 1u, 0u, ctx->tl_dev.p, n_tiles, ctx->accum, true);
 }
 
-mcpt_status mcpt_sync(mcpt_ctx* ctx) {
+// Make the context's device current, drain its stream and read the finished calls' durations.
+static mcpt_status use_drained(mcpt_ctx* ctx) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return resolve_timing(ctx);
 }
+mcpt_status mcpt_sync(mcpt_ctx* ctx) { return use_drained(ctx); }
 
 // Every device-to-host read of a handed-out context: the copy in stream order, the stream drained (`host` is complete and may be let go), and,
 // with `timing`, the finished calls' durations read -- what the read entry points do once their arguments are checked.
@@ -924,24 +967,23 @@ mcpt_status mcpt_clear_accum(mcpt_ctx* ctx) {
 // the stream has drained (the image is complete).  The kernel writes every byte: nothing to clear.
 static mcpt_status tonemap_to_pinned(mcpt_ctx* ctx, const float4* film, int flip_y) {
     const size_t n = size_t(ctx->width) * ctx->height;
-    if (!ctx->tone_dev.p) {
-        DevBuf dev; Pinned<uint8_t> host;
-        HIP_TRY(dev.alloc(3 * n));
-        HIP_TRY(hipHostMalloc((void**)host.out(), 3 * n ? 3 * n : 16, hipHostMallocDefault));
-        ctx->tone_dev = std::move(dev); ctx->tone_host = std::move(host);
-    }
-    HIP_TRY(launch_tonemap(film, static_cast<uint8_t*>(ctx->tone_dev.p), ctx->width, ctx->height, flip_y, ctx->stream));
+    if (!ctx->tone_dev.p) HIP_TRY(alloc_all(Want(ctx->tone_dev, 3 * n), Want(ctx->tone_host, 3 * n)));
+    HIP_TRY(launch_tonemap(film, ctx->tone_dev.p, ctx->width, ctx->height, flip_y, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->tone_host, ctx->tone_dev.p, 3 * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return resolve_timing(ctx);
+}
+// ... and copied on into the caller's image
+static mcpt_status tonemap_to_host(mcpt_ctx* ctx, const float4* film, uint8_t* rgb_host, int flip_y) {
+    const mcpt_status st = tonemap_to_pinned(ctx, film, flip_y);
+    if (st == MCPT_OK) std::memcpy(rgb_host, ctx->tone_host, 3 * size_t(ctx->width) * ctx->height);
+    return st;
 }
 
 mcpt_status mcpt_tonemap(mcpt_ctx* ctx, uint8_t* rgb_host, int flip_y) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!rgb_host) return fail(MCPT_ERR_INVALID_ARG, "null output");
-    st = tonemap_to_pinned(ctx, ctx->accum, flip_y); if (st != MCPT_OK) return st;
-    std::memcpy(rgb_host, ctx->tone_host, 3 * size_t(ctx->width) * ctx->height);
-    return MCPT_OK;
+    return tonemap_to_host(ctx, ctx->accum, rgb_host, flip_y);
 }
 
 /* The same without the last copy: *out_rgb points at the context's own pinned host image (width * height * 3 bytes), valid until the next
@@ -961,16 +1003,14 @@ mcpt_status mcpt_tonemap_map(mcpt_ctx* ctx, int flip_y, const uint8_t** out_rgb)
 mcpt_status mcpt_tonemap_buffer(mcpt_ctx* ctx, const void* device_rgba, uint8_t* rgb_host, int flip_y) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!rgb_host || !device_rgba) return fail(MCPT_ERR_INVALID_ARG, "null argument");
-    st = tonemap_to_pinned(ctx, static_cast<const float4*>(device_rgba), flip_y); if (st != MCPT_OK) return st;
-    std::memcpy(rgb_host, ctx->tone_host, 3 * size_t(ctx->width) * ctx->height);
-    return MCPT_OK;
+    return tonemap_to_host(ctx, static_cast<const float4*>(device_rgba), rgb_host, flip_y);
 }
 
 mcpt_status mcpt_get_counters(mcpt_ctx* ctx, mcpt_counters* out) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
     std::vector<DevCounters> rep(WF_COUNTER_REPLICAS);               // kernels spread their atomics over replicas; sum them here
-    st = read_back(ctx, rep.data(), ctx->counters.p, sizeof(DevCounters) * WF_COUNTER_REPLICAS); if (st != MCPT_OK) return st;
+    st = read_back(ctx, rep.data(), ctx->counters.p, ctx->counters.bytes); if (st != MCPT_OK) return st;
     std::memset(out, 0, sizeof *out);
     for (const DevCounters& r : rep) {
         out->paths += r.paths; out->rays_primary += r.rays_primary; out->rays_continuation += r.rays_continuation; out->rays_shadow += r.rays_shadow;
@@ -983,7 +1023,7 @@ mcpt_status mcpt_get_counters(mcpt_ctx* ctx, mcpt_counters* out) {
 }
 mcpt_status mcpt_reset_counters(mcpt_ctx* ctx) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    HIP_TRY(hipMemsetAsync(ctx->counters.p, 0, sizeof(DevCounters) * WF_COUNTER_REPLICAS, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->counters.p, 0, ctx->counters.bytes, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     st = resolve_timing(ctx); if (st != MCPT_OK) return st;
     ctx->total_kernel_ms = 0.0; ctx->launches = 0; ctx->total_trace_ms = 0.0; ctx->total_shade_ms = 0.0; ctx->total_iterations = 0;
@@ -993,7 +1033,7 @@ mcpt_status mcpt_reset_counters(mcpt_ctx* ctx) {
 mcpt_status mcpt_bind_accum(mcpt_ctx* ctx, void* device_rgba) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->accum = device_rgba ? static_cast<float4*>(device_rgba) : static_cast<float4*>(ctx->accum_own.p);
+    ctx->accum = device_rgba ? static_cast<float4*>(device_rgba) : ctx->accum_own.p;
     return MCPT_OK;
 }
 mcpt_status mcpt_accum_device_ptr(mcpt_ctx* ctx, void** out_device_rgba) {
@@ -1002,17 +1042,13 @@ mcpt_status mcpt_accum_device_ptr(mcpt_ctx* ctx, void** out_device_rgba) {
     return MCPT_OK;
 }
 mcpt_status mcpt_set_stream(mcpt_ctx* ctx, void* hip_stream) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    mcpt_status st = use_drained(ctx); if (st != MCPT_OK) return st;
     ctx->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream;
     return MCPT_OK;
 }
 
 mcpt_status mcpt_set_null_stream(mcpt_ctx* ctx) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    mcpt_status st = use_drained(ctx); if (st != MCPT_OK) return st;
     ctx->stream = nullptr;                                             // the device's legacy default stream
     return MCPT_OK;
 }
@@ -1023,8 +1059,8 @@ mcpt_status mcpt_render_features(mcpt_ctx* ctx, uint32_t spp, uint64_t seed) {
     if (spp < 1 || spp > DN_MAX_SPP) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_features: need 1 <= spp <= 64");
     if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
     const size_t n = size_t(ctx->width) * ctx->height;
-    if (!ctx->dn_feat.p) HIP_TRY(ctx->dn_feat.alloc(2 * n * sizeof(float4), &ctx->info.device_bytes));
-    HIP_TRY(launch_dn_features(ctx->dev, spp, uint32_t(seed), uint32_t(seed >> 32), static_cast<float4*>(ctx->dn_feat.p), ctx->stream));
+    if (!ctx->dn_feat.p) HIP_TRY(ctx->dn_feat.alloc(2 * n, &ctx->info.device_bytes));
+    HIP_TRY(launch_dn_features(ctx->dev, spp, uint32_t(seed), uint32_t(seed >> 32), ctx->dn_feat.p, ctx->stream));
     ctx->dn_have_features = true;
     return MCPT_OK;
 }
@@ -1044,11 +1080,8 @@ mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_deno
     if (!(o.sigma_color >= 0.f) || !(o.sigma_normal >= 0.f) || !(o.sigma_depth >= 0.f)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be >= 0 (0 = default)");
     if (!ctx->dn_have_features) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: no features rendered yet (mcpt_render_features)");
     const size_t n = size_t(ctx->width) * ctx->height;
-    if (!ctx->dn_out.p) {
-        DevBuf* dst[4] = {&ctx->dn_guide, &ctx->dn_iv0, &ctx->dn_iv1, &ctx->dn_out}; DevBuf fresh[4];
-        for (DevBuf& b : fresh) HIP_TRY(b.alloc(n * sizeof(float4), &ctx->info.device_bytes));
-        for (int i = 0; i < 4; i++) *dst[i] = std::move(fresh[i]);
-    }
+    uint64_t* tally = &ctx->info.device_bytes;
+    if (!ctx->dn_out.p) HIP_TRY(alloc_all(Want(ctx->dn_guide, n, tally), Want(ctx->dn_iv0, n, tally), Want(ctx->dn_iv1, n, tally), Want(ctx->dn_out, n, tally)));
     DnParams p;
     p.width = ctx->width; p.height = ctx->height;
     p.sigma_c = o.sigma_color > 0.f ? o.sigma_color : 4.f;
@@ -1057,8 +1090,7 @@ mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_deno
     p.theta = float(ctx->dev.cam.h / double(ctx->height));
     const uint32_t levels = o.iterations ? o.iterations : 5u;
     const float4* film = device_rgba ? static_cast<const float4*>(device_rgba) : ctx->accum;
-    HIP_TRY(launch_dn_filter(p, levels, film, static_cast<const float4*>(ctx->dn_feat.p), static_cast<float4*>(ctx->dn_guide.p),
-                             static_cast<float4*>(ctx->dn_iv0.p), static_cast<float4*>(ctx->dn_iv1.p), static_cast<float4*>(ctx->dn_out.p), ctx->stream));
+    HIP_TRY(launch_dn_filter(p, levels, film, ctx->dn_feat.p, ctx->dn_guide.p, ctx->dn_iv0.p, ctx->dn_iv1.p, ctx->dn_out.p, ctx->stream));
     ctx->dn_have_out = true;
     return MCPT_OK;
 }
@@ -1084,20 +1116,15 @@ static mcpt_status ad_ensure(mcpt_ctx* ctx) {
     if (ctx->ad_h.p) return MCPT_OK;
     const size_t n = size_t(ctx->width) * ctx->height;
     const uint32_t n_tiles = uint32_t(film_tiles(ctx)), nb = ad_blocks(n_tiles);
-    const size_t bytes[8] = {n * sizeof(float4), n * sizeof(float4), n_tiles * sizeof(float), n_tiles * sizeof(uint32_t), n_tiles * sizeof(uint32_t),
-                             nb * sizeof(uint4), nb * sizeof(uint32_t), sizeof(AdTotals)};
-    DevBuf* dst[8] = {&ctx->ad_h, &ctx->ad_o, &ctx->ad_err, &ctx->ad_list, &ctx->ad_flags, &ctx->ad_counts, &ctx->ad_offs, &ctx->ad_tot};
-    DevBuf fresh[8]; Pinned<AdTotals> host;                               // committed only when all of it is there
-    for (int i = 0; i < 8; i++) HIP_TRY(fresh[i].alloc(bytes[i], &ctx->info.device_bytes));
-    HIP_TRY(hipHostMalloc((void**)host.out(), sizeof(AdTotals), hipHostMallocDefault));
-    for (int i = 0; i < 8; i++) *dst[i] = std::move(fresh[i]);
-    ctx->ad_host = std::move(host);
+    uint64_t* tally = &ctx->info.device_bytes;
+    HIP_TRY(alloc_all(Want(ctx->ad_h, n, tally), Want(ctx->ad_o, n, tally), Want(ctx->ad_err, n_tiles, tally), Want(ctx->ad_list, n_tiles, tally),
+                      Want(ctx->ad_flags, n_tiles, tally), Want(ctx->ad_counts, nb, tally), Want(ctx->ad_offs, nb, tally), Want(ctx->ad_tot, 1, tally),
+                      Want(ctx->ad_host, 1)));
     return MCPT_OK;
 }
 static AdScratch ad_scratch(mcpt_ctx* ctx) {
     AdScratch s;
-    s.block_counts = static_cast<uint4*>(ctx->ad_counts.p); s.block_offsets = static_cast<uint32_t*>(ctx->ad_offs.p);
-    s.flags = static_cast<uint32_t*>(ctx->ad_flags.p); s.totals = static_cast<AdTotals*>(ctx->ad_tot.p);
+    s.block_counts = ctx->ad_counts.p; s.block_offsets = ctx->ad_offs.p; s.flags = ctx->ad_flags.p; s.totals = ctx->ad_tot.p;
     return s;
 }
 
@@ -1115,22 +1142,20 @@ mcpt_status mcpt_render_adaptive(mcpt_ctx* ctx, uint64_t seed, uint32_t first_sa
     st = ad_ensure(ctx); if (st != MCPT_OK) return st;
     const size_t n_px = size_t(ctx->width) * ctx->height;
     const uint32_t n_tiles = uint32_t(film_tiles(ctx));
-    float4* H = static_cast<float4*>(ctx->ad_h.p); float4* O = static_cast<float4*>(ctx->ad_o.p);
-    const uint32_t* list = static_cast<const uint32_t*>(ctx->ad_list.p);
     const AdScratch scr = ad_scratch(ctx);
     mcpt_adaptive_stats stats; std::memset(&stats, 0, sizeof stats); stats.struct_size = sizeof stats;
     st = timed_begin(ctx); if (st != MCPT_OK) return st;
-    HIP_TRY(hipMemsetAsync(H, 0, n_px * sizeof(float4), ctx->stream));
-    HIP_TRY(hipMemsetAsync(O, 0, n_px * sizeof(float4), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->ad_h.p, 0, ctx->ad_h.bytes, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->ad_o.p, 0, ctx->ad_o.bytes, ctx->stream));
     ctx->ad_have_err = false;
     // pass 0: every tile, samples [fs, fs + min/2) into H and [fs + min/2, fs + min) into O
     const uint32_t half = min_spp / 2;
-    st = render_call(ctx, half, seed, first_sample, 1u, 0u, nullptr, 0u, H, false); if (st != MCPT_OK) return st;
-    st = render_call(ctx, half, seed, first_sample + half, 1u, 0u, nullptr, 0u, O, false); if (st != MCPT_OK) return st;
+    st = render_call(ctx, half, seed, first_sample, 1u, 0u, nullptr, 0u, ctx->ad_h.p, false); if (st != MCPT_OK) return st;
+    st = render_call(ctx, half, seed, first_sample + half, 1u, 0u, nullptr, 0u, ctx->ad_o.p, false); if (st != MCPT_OK) return st;
     stats.passes = 1; stats.pixel_samples = uint64_t(min_spp) * n_px;
     uint32_t c = min_spp;                                                  // the count every active tile has
     for (;;) {
-        HIP_TRY(launch_ad_error_compact(H, O, ctx->width, ctx->height, thr, max_spp, static_cast<float*>(ctx->ad_err.p), static_cast<uint32_t*>(ctx->ad_list.p), scr, ctx->stream));
+        HIP_TRY(launch_ad_error_compact(ctx->ad_h.p, ctx->ad_o.p, ctx->width, ctx->height, thr, max_spp, ctx->ad_err.p, ctx->ad_list.p, scr, ctx->stream));
         HIP_TRY(hipMemcpyAsync(ctx->ad_host, ctx->ad_tot.p, sizeof(AdTotals), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         ctx->ad_have_err = true;
@@ -1141,12 +1166,12 @@ mcpt_status mcpt_render_adaptive(mcpt_ctx* ctx, uint64_t seed, uint32_t first_sa
         }
         // the next pass doubles the active tiles' count, or brings it to max_spp: n samples [fs + c, fs + c + n), the first floor(n/2) into H
         const uint32_t n = std::min(c, max_spp - c), nh = n / 2;
-        st = render_call(ctx, nh, seed, first_sample + c, 1u, 0u, list, t.n_active, H, false); if (st != MCPT_OK) return st;
-        st = render_call(ctx, n - nh, seed, first_sample + c + nh, 1u, 0u, list, t.n_active, O, false); if (st != MCPT_OK) return st;
+        st = render_call(ctx, nh, seed, first_sample + c, 1u, 0u, ctx->ad_list.p, t.n_active, ctx->ad_h.p, false); if (st != MCPT_OK) return st;
+        st = render_call(ctx, n - nh, seed, first_sample + c + nh, 1u, 0u, ctx->ad_list.p, t.n_active, ctx->ad_o.p, false); if (st != MCPT_OK) return st;
         stats.passes++; stats.pixel_samples += uint64_t(n) * t.active_pixels;
         c += n;
     }
-    HIP_TRY(launch_ad_merge(ctx->accum, H, O, uint32_t(n_px), ctx->stream));
+    HIP_TRY(launch_ad_merge(ctx->accum, ctx->ad_h.p, ctx->ad_o.p, uint32_t(n_px), ctx->stream));
     st = timed_end(ctx); if (st != MCPT_OK) return st;
     if (out_stats) *out_stats = stats;
     return MCPT_OK;
@@ -1222,32 +1247,28 @@ static mcpt_status rf_check_update(const mcpt_ctx* ctx, const double* vertex, ui
     return MCPT_OK;
 }
 // The update itself, for arrays rf_check_update has passed: staged, copied and refitted on the context's stream.
-static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal) {
-    // the staging buffer's last copy has been made
-    if (ctx->rf_stage_pending) { HIP_TRY(hipEventSynchronize(ctx->rf_stage_ev)); ctx->rf_stage_pending = false; }
-    const size_t vd = size_t(n_vertex) * 3, nd = size_t(ctx->rf_n_normal) * 3;
-    std::memcpy(ctx->rf_stage, vertex, vd * sizeof(double));
-    if (normal) std::memcpy(ctx->rf_stage + vd, normal, nd * sizeof(double));
+static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const double* vertex, const double* normal) {
+    HIP_TRY(ctx->rf_stage.wait());
+    const size_t vd = ctx->rf_vtx.count(), nd = ctx->rf_nrm.count();
+    std::memcpy(ctx->rf_stage.host, vertex, vd * sizeof(double));
+    if (normal) std::memcpy(ctx->rf_stage.host + vd, normal, nd * sizeof(double));
     // Everything below is stream work on the context's stream: it starts after every render enqueued so far has finished (the sub-pipelines'
     // streams joined it at the end of their call, known-length jobs included) and the next render's sub-pipelines fork from it after the last
     // kernel here.
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx->rf_watch.begin(s));
-    HIP_TRY(hipMemcpyAsync(ctx->rf_vtx.p, ctx->rf_stage, vd * sizeof(double), hipMemcpyHostToDevice, s));
-    if (normal) HIP_TRY(hipMemcpyAsync(ctx->rf_nrm.p, ctx->rf_stage + vd, nd * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(ctx->rf_stage_ev, s)); ctx->rf_stage_pending = true;
-    const double* d_nrm = normal ? static_cast<const double*>(ctx->rf_nrm.p) : nullptr;
-    const int32_t* idx = static_cast<const int32_t*>(ctx->rf_idx.p);
-    float* tri_box = static_cast<float*>(ctx->rf_tri_box.p);
+    HIP_TRY(ctx->rf_stage.send(ctx->rf_vtx.p, 0, vd, s, !normal));
+    if (normal) HIP_TRY(ctx->rf_stage.send(ctx->rf_nrm.p, vd, nd, s));
+    const double* d_nrm = normal ? ctx->rf_nrm.p : nullptr;
     const DevScene& d = ctx->dev;
-    HIP_TRY(launch_rf_triangles(static_cast<const double*>(ctx->rf_vtx.p), d_nrm, idx, RfCentre{d.centre[0], d.centre[1], d.centre[2]}, static_cast<float4*>(ctx->tri_isect.p),
-                                static_cast<float4*>(ctx->tri_shade.p), static_cast<double*>(ctx->tri_pos64.p), tri_box, uint32_t(d.n_tris), s));
-    HIP_TRY(launch_rf_lights(static_cast<DevLight*>(ctx->lights.p), static_cast<double*>(ctx->light_pos64.p), d.tri_isect, d.tri_pos64, d_nrm, idx, uint32_t(d.n_lights), s));
+    HIP_TRY(launch_rf_triangles(ctx->rf_vtx.p, d_nrm, ctx->rf_idx.p, RfCentre{d.centre[0], d.centre[1], d.centre[2]}, ctx->tri_isect.p, ctx->tri_shade.p,
+                                ctx->tri_pos64.p, ctx->rf_tri_box.p, uint32_t(d.n_tris), s));
+    HIP_TRY(launch_rf_lights(ctx->lights.p, ctx->light_pos64.p, d.tri_isect, d.tri_pos64, d_nrm, ctx->rf_idx.p, uint32_t(d.n_lights), s));
     for (size_t k = 0; k + 1 < ctx->rf_bin_level.size(); k++)                    // heights, lowest first
-        HIP_TRY(launch_rf_binary_level(static_cast<float4*>(ctx->nodes.p), static_cast<const uint32_t*>(ctx->rf_bin_order.p), ctx->rf_bin_level[k], ctx->rf_bin_level[k + 1], tri_box, s));
+        HIP_TRY(launch_rf_binary_level(ctx->nodes.p, ctx->rf_bin_order.p, ctx->rf_bin_level[k], ctx->rf_bin_level[k + 1], ctx->rf_tri_box.p, s));
     for (size_t k = ctx->rf_wide_level.size() - 1; k-- > 0;)                     // depths, deepest first
-        HIP_TRY(launch_rf_wide_level(static_cast<float4*>(ctx->nodes8.p), ctx->rf_wide_level[k], ctx->rf_wide_level[k + 1], tri_box, static_cast<float*>(ctx->rf_node_box.p), s));
-    HIP_TRY(launch_rf_wide_area(d.nodes8, uint32_t(d.n_nodes8), static_cast<double*>(ctx->rf_area.p), s));
+        HIP_TRY(launch_rf_wide_level(ctx->nodes8.p, ctx->rf_wide_level[k], ctx->rf_wide_level[k + 1], ctx->rf_tri_box.p, ctx->rf_node_box.p, s));
+    HIP_TRY(launch_rf_wide_area(d.nodes8, uint32_t(d.n_nodes8), ctx->rf_area.p, s));
     HIP_TRY(ctx->rf_watch.end(s));
     ctx->rf_updates++;
     rf_forget_derived(ctx);
@@ -1257,7 +1278,7 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const double* vertex, uint32
 mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     st = rf_check_update(ctx, vertex, n_vertex, normal, n_normal, "mcpt_update_vertices"); if (st != MCPT_OK) return st;
-    return rf_enqueue_update(ctx, vertex, n_vertex, normal);
+    return rf_enqueue_update(ctx, vertex, normal);
 }
 
 mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
@@ -1291,10 +1312,14 @@ static mcpt_status rp_read_opts(const mcpt_reproject_opts* opts, mcpt_reproject_
     if (o.normal_threshold == 0.f) o.normal_threshold = 0.9f;
     return MCPT_OK;
 }
-// rp_reproject_kernel from the view `old_cam` into the view `new_cam` on the context's stream: `out` gets the reprojected film, *count the pixels
-// reused.  An old view whose image basis is singular has no inverse projection: the film is cleared instead (no pixel reused).
-static mcpt_status rp_run(mcpt_ctx* ctx, const DevCamera& old_cam, const DevCamera& new_cam, const mcpt_reproject_opts& o, const float4* old_film,
-                          const float4* old_feat, const float4* new_feat, float4* out, unsigned long long* count) {
+// What motion-vector reprojection (§14) reads besides: the first-hit records of the new scene and view, and rf_n_vertex / rf_n_normal device
+// records of the scene before the update.
+struct RpOldScene { const float4* hits; const double* vtx; const double* nrm; };
+// rp_reproject_kernel -- with `motion`, rp_reproject_motion_kernel -- from the view `old_cam` into the view `new_cam` on the context's stream: `out`
+// gets the reprojected film, *count the pixels reused.  An old view whose image basis is singular has no inverse projection: the film is cleared
+// instead (no pixel reused).
+static mcpt_status rp_run(mcpt_ctx* ctx, const DevCamera& old_cam, const DevCamera& new_cam, const mcpt_reproject_opts& o, const RpOldScene* motion,
+                          const float4* old_film, const float4* old_feat, const float4* new_feat, float4* out, unsigned long long* count) {
     RpParams p;
     p.old_cam = old_cam; p.new_cam = new_cam;
     p.max_history = o.max_history; p.depth_tolerance = o.depth_tolerance; p.normal_threshold = o.normal_threshold;
@@ -1303,7 +1328,16 @@ static mcpt_status rp_run(mcpt_ctx* ctx, const DevCamera& old_cam, const DevCame
         HIP_TRY(hipMemsetAsync(out, 0, size_t(ctx->width) * ctx->height * sizeof(float4), ctx->stream));
         return MCPT_OK;
     }
-    HIP_TRY(launch_rp_reproject(p, old_film, old_feat, new_feat, out, count, ctx->stream));
+    if (!motion) {
+        HIP_TRY(launch_rp_reproject(p, old_film, old_feat, new_feat, out, count, ctx->stream));
+        return MCPT_OK;
+    }
+    RpMotion m;
+    m.hits = motion->hits; m.idx6 = ctx->rf_idx.p; m.old_vtx = motion->vtx; m.old_nrm = motion->nrm;
+    m.tri_shade = ctx->dev.tri_shade; m.mats = ctx->dev.mats;
+    for (int a = 0; a < 3; a++) m.centre[a] = ctx->dev.centre[a];
+    m.n_tris = uint32_t(ctx->dev.n_tris); m.n_vertex = ctx->rf_n_vertex; m.n_normal = ctx->rf_n_normal; m.n_mats = uint32_t(ctx->dev.n_mats);
+    HIP_TRY(launch_rp_reproject_motion(p, m, old_film, old_feat, new_feat, out, count, ctx->stream));
     return MCPT_OK;
 }
 
@@ -1312,53 +1346,49 @@ static mcpt_status rp_ensure(mcpt_ctx* ctx, bool motion) {
     const size_t n = size_t(ctx->width) * ctx->height;
     uint64_t* tally = &ctx->info.device_bytes;
     const bool base = !ctx->rp_film_old.p, more = motion && !ctx->rp_hits.p;
-    DevBuf feat_old, film_old, count, feat, hits, vtx_old, nrm_old; Stopwatch watch;
-    if (base) {
-        HIP_TRY(feat_old.alloc(2 * n * sizeof(float4), tally));
-        HIP_TRY(film_old.alloc(n * sizeof(float4), tally));
-        HIP_TRY(count.alloc(sizeof(unsigned long long)));
-        if (!ctx->dn_feat.p) HIP_TRY(feat.alloc(2 * n * sizeof(float4), tally));
-        HIP_TRY(watch.create());
-    }
-    if (more) {
-        HIP_TRY(hits.alloc(n * sizeof(float4), tally));
-        HIP_TRY(vtx_old.alloc(ctx->rf_vtx.bytes, tally)); HIP_TRY(nrm_old.alloc(ctx->rf_nrm.bytes, tally));
-    }
-    if (base) {
-        ctx->rp_feat_old = std::move(feat_old); ctx->rp_film_old = std::move(film_old); ctx->rp_count = std::move(count);
-        if (!ctx->dn_feat.p) ctx->dn_feat = std::move(feat);
-        ctx->rp_watch = std::move(watch);
-    }
-    if (more) { ctx->rp_hits = std::move(hits); ctx->rp_vtx_old = std::move(vtx_old); ctx->rp_nrm_old = std::move(nrm_old); }
+    HIP_TRY(alloc_all(Want(ctx->rp_feat_old, 2 * n, tally, base), Want(ctx->rp_film_old, n, tally, base), Want(ctx->rp_count, 1, nullptr, base),
+                      Want(ctx->dn_feat, 2 * n, tally, base && !ctx->dn_feat.p), Want(ctx->rp_watch, 1, nullptr, base), Want(ctx->rp_hits, n, tally, more),
+                      Want(ctx->rp_vtx_old, ctx->rf_vtx.count(), tally, more), Want(ctx->rp_nrm_old, ctx->rf_nrm.count(), tally, more)));
+    return MCPT_OK;
+}
+
+// A vertex update for rf_enqueue_update, checked by rf_check_update.
+struct RfUpdate { const double* vertex; const double* normal; };
+// The frame of a reprojection entry point whose own arguments have been checked: the film is carried from the scene and view as they are to the
+// scene after `update` (null: unchanged, §13) seen from `cm` (null: the same camera).  `fn` names the entry point in the message.
+static mcpt_status rp_frame(mcpt_ctx* ctx, const RfUpdate* update, const mcpt_camera* cm, const mcpt_reproject_opts* opts, const char* fn) {
+    mcpt_reproject_opts o;
+    mcpt_status st = rp_read_opts(opts, o, fn); if (st != MCPT_OK) return st;
+    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
+    st = rp_ensure(ctx, update != nullptr); if (st != MCPT_OK) return st;
+    // Everything below is stream work on the context's stream, ordered like mcpt_set_camera / mcpt_update_vertices: renders enqueued before it have
+    // joined the stream, the next render's sub-pipelines fork from it after the last kernel here.
+    hipStream_t s = ctx->stream;
+    const uint32_t seed_lo = uint32_t(o.feature_seed), seed_hi = uint32_t(o.feature_seed >> 32);
+    HIP_TRY(ctx->rp_watch.begin(s));
+    if (!ctx->dn_have_features) HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, ctx->dn_feat.p, s));
+    std::swap(ctx->dn_feat, ctx->rp_feat_old);                             // the old scene's and view's features are kept where they lie
+    HIP_TRY(hipMemcpyAsync(ctx->rp_film_old.p, ctx->accum, ctx->rp_film_old.bytes, hipMemcpyDeviceToDevice, s));
+    if (update && ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->rp_vtx_old.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, s));
+    if (update && ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->rp_nrm_old.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, s));
+    const DevCamera old_cam = ctx->dev.cam;
+    if (update) { st = rf_enqueue_update(ctx, update->vertex, update->normal); if (st != MCPT_OK) return st; }
+    if (cm) apply_camera(ctx, *cm);
+    HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, ctx->dn_feat.p, s));
+    ctx->dn_have_features = true;                                          // those of the new scene and view: mcpt_denoise may follow at once
+    if (update) HIP_TRY(launch_rp_first_hit(ctx->dev, ctx->rp_hits.p, s));
+    const RpOldScene old{ctx->rp_hits.p, ctx->rp_vtx_old.p, ctx->rp_nrm_old.p};
+    st = rp_run(ctx, old_cam, ctx->dev.cam, o, update ? &old : nullptr, ctx->rp_film_old.p, ctx->rp_feat_old.p, ctx->dn_feat.p, ctx->accum, ctx->rp_count.p);
+    if (st != MCPT_OK) return st;
+    HIP_TRY(ctx->rp_watch.end(s));
+    ctx->rp_calls++;
     return MCPT_OK;
 }
 
 mcpt_status mcpt_set_camera_reproject(mcpt_ctx* ctx, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     st = check_camera(ctx, cm, "mcpt_set_camera_reproject"); if (st != MCPT_OK) return st;
-    mcpt_reproject_opts o;
-    st = rp_read_opts(opts, o, "mcpt_set_camera_reproject"); if (st != MCPT_OK) return st;
-    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
-    const size_t n = size_t(ctx->width) * ctx->height;
-    st = rp_ensure(ctx, false); if (st != MCPT_OK) return st;
-    // Everything below is stream work on the context's stream, ordered like mcpt_set_camera: renders enqueued before it have joined the stream,
-    // the next render's sub-pipelines fork from it after the kernel here.
-    hipStream_t s = ctx->stream;
-    const uint32_t seed_lo = uint32_t(o.feature_seed), seed_hi = uint32_t(o.feature_seed >> 32);
-    HIP_TRY(ctx->rp_watch.begin(s));
-    if (!ctx->dn_have_features) HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, static_cast<float4*>(ctx->dn_feat.p), s));
-    std::swap(ctx->dn_feat, ctx->rp_feat_old);                             // the old view's features are kept where they lie
-    HIP_TRY(hipMemcpyAsync(ctx->rp_film_old.p, ctx->accum, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
-    const DevCamera old_cam = ctx->dev.cam;
-    apply_camera(ctx, *cm);
-    HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, static_cast<float4*>(ctx->dn_feat.p), s));
-    ctx->dn_have_features = true;                                          // those of the new view: mcpt_denoise may follow at once
-    st = rp_run(ctx, old_cam, ctx->dev.cam, o, static_cast<const float4*>(ctx->rp_film_old.p), static_cast<const float4*>(ctx->rp_feat_old.p),
-                static_cast<const float4*>(ctx->dn_feat.p), ctx->accum, static_cast<unsigned long long*>(ctx->rp_count.p));
-    if (st != MCPT_OK) return st;
-    HIP_TRY(ctx->rp_watch.end(s));
-    ctx->rp_calls++;
-    return MCPT_OK;
+    return rp_frame(ctx, nullptr, cm, opts, "mcpt_set_camera_reproject");
 }
 
 mcpt_status mcpt_get_reproject_info(mcpt_ctx* ctx, mcpt_reproject_info* out) {
@@ -1372,85 +1402,47 @@ mcpt_status mcpt_get_reproject_info(mcpt_ctx* ctx, mcpt_reproject_info* out) {
     return MCPT_OK;
 }
 
-mcpt_status mcpt_probe_reproject(mcpt_ctx* ctx, const mcpt_camera* old_cam, const mcpt_camera* new_cam, const float* old_film_host, const float* old_feat8_host,
-                                 const float* new_feat8_host, const mcpt_reproject_opts* opts, float* out_film_host, uint64_t* out_reused) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!old_film_host || !old_feat8_host || !new_feat8_host || !out_film_host || !out_reused) return fail(MCPT_ERR_INVALID_ARG, "null argument");
-    st = check_camera(ctx, old_cam, "mcpt_probe_reproject (old camera)"); if (st != MCPT_OK) return st;
-    st = check_camera(ctx, new_cam, "mcpt_probe_reproject (new camera)"); if (st != MCPT_OK) return st;
+// What the two reprojection probes share once their own arguments are checked: the two cameras, the options, the three films staged, rp_run into a
+// scratch film and counter, both fetched.  `stage_motion` (§14; may refuse) stages its inputs first and says where they are.
+using RpStageMotion = std::function<mcpt_status(Scratch&, RpOldScene&)>;
+static mcpt_status rp_probe(mcpt_ctx* ctx, const char* fn, const mcpt_camera* old_cam, const mcpt_camera* new_cam, const float* old_film_host,
+                            const float* old_feat8_host, const float* new_feat8_host, const mcpt_reproject_opts* opts, const RpStageMotion& stage_motion,
+                            float* out_film_host, uint64_t* out_reused) {
+    mcpt_status st = check_camera(ctx, old_cam, (std::string(fn) + " (old camera)").c_str()); if (st != MCPT_OK) return st;
+    st = check_camera(ctx, new_cam, (std::string(fn) + " (new camera)").c_str()); if (st != MCPT_OK) return st;
     mcpt_reproject_opts o;
-    st = rp_read_opts(opts, o, "mcpt_probe_reproject"); if (st != MCPT_OK) return st;
+    st = rp_read_opts(opts, o, fn); if (st != MCPT_OK) return st;
     const size_t n = size_t(ctx->width) * ctx->height;
     DevCamera co, cn;
     camera_constants(*old_cam, ctx->dev.centre, co); camera_constants(*new_cam, ctx->dev.centre, cn);
-    Scratch s(ctx->stream); float4 *film, *fo, *fn, *out; unsigned long long* count;
+    Scratch s(ctx->stream); RpOldScene old{}; float4 *film, *fo, *fnew, *out; unsigned long long* count;
+    if (stage_motion) { st = stage_motion(s, old); if (st != MCPT_OK) return st; }
     HIP_TRY(s.in(reinterpret_cast<const float4*>(old_film_host), n, &film));
-    HIP_TRY(s.in(reinterpret_cast<const float4*>(old_feat8_host), 2 * n, &fo)); HIP_TRY(s.in(reinterpret_cast<const float4*>(new_feat8_host), 2 * n, &fn));
+    HIP_TRY(s.in(reinterpret_cast<const float4*>(old_feat8_host), 2 * n, &fo)); HIP_TRY(s.in(reinterpret_cast<const float4*>(new_feat8_host), 2 * n, &fnew));
     HIP_TRY(s.out(n, &out)); HIP_TRY(s.out(1, &count));
-    st = rp_run(ctx, co, cn, o, film, fo, fn, out, count); if (st != MCPT_OK) return st;
+    st = rp_run(ctx, co, cn, o, stage_motion ? &old : nullptr, film, fo, fnew, out, count); if (st != MCPT_OK) return st;
     unsigned long long c = 0;
     HIP_TRY(s.fetch(&c, count, 1)); HIP_TRY(s.fetch(out_film_host, out, 4 * n)); HIP_TRY(s.finish());
     *out_reused = c;
     return MCPT_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ motion-vector reprojection (DESIGN.md §14)
-// rp_reproject_motion_kernel on the context's stream, with rp_run's contract.  `hits`: first-hit records of the new scene and view; old_vtx /
-// old_nrm: rf_n_vertex / rf_n_normal device records of the scene before the update.
-static mcpt_status rp_run_motion(mcpt_ctx* ctx, const DevCamera& old_cam, const DevCamera& new_cam, const mcpt_reproject_opts& o, const float4* hits,
-                                 const double* old_vtx, const double* old_nrm, const float4* old_film, const float4* old_feat, const float4* new_feat,
-                                 float4* out, unsigned long long* count) {
-    RpParams p;
-    p.old_cam = old_cam; p.new_cam = new_cam;
-    p.max_history = o.max_history; p.depth_tolerance = o.depth_tolerance; p.normal_threshold = o.normal_threshold;
-    HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned long long), ctx->stream));
-    if (!rp_basis_inverse(old_cam, p.inv)) {
-        HIP_TRY(hipMemsetAsync(out, 0, size_t(ctx->width) * ctx->height * sizeof(float4), ctx->stream));
-        return MCPT_OK;
-    }
-    RpMotion m;
-    m.hits = hits; m.idx6 = static_cast<const int32_t*>(ctx->rf_idx.p); m.old_vtx = old_vtx; m.old_nrm = old_nrm;
-    m.tri_shade = ctx->dev.tri_shade; m.mats = ctx->dev.mats;
-    for (int a = 0; a < 3; a++) m.centre[a] = ctx->dev.centre[a];
-    m.n_tris = uint32_t(ctx->dev.n_tris); m.n_vertex = ctx->rf_n_vertex; m.n_normal = ctx->rf_n_normal; m.n_mats = uint32_t(ctx->dev.n_mats);
-    HIP_TRY(launch_rp_reproject_motion(p, m, old_film, old_feat, new_feat, out, count, ctx->stream));
-    return MCPT_OK;
+mcpt_status mcpt_probe_reproject(mcpt_ctx* ctx, const mcpt_camera* old_cam, const mcpt_camera* new_cam, const float* old_film_host, const float* old_feat8_host,
+                                 const float* new_feat8_host, const mcpt_reproject_opts* opts, float* out_film_host, uint64_t* out_reused) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!old_film_host || !old_feat8_host || !new_feat8_host || !out_film_host || !out_reused) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    return rp_probe(ctx, "mcpt_probe_reproject", old_cam, new_cam, old_film_host, old_feat8_host, new_feat8_host, opts, nullptr, out_film_host, out_reused);
 }
 
+// ------------------------------------------------------------------------------------------------ motion-vector reprojection (DESIGN.md §14)
 mcpt_status mcpt_update_vertices_reproject(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal,
                                            const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
     const char* const fn = "mcpt_update_vertices_reproject";
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     st = rf_check_update(ctx, vertex, n_vertex, normal, n_normal, fn); if (st != MCPT_OK) return st;
     if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
-    mcpt_reproject_opts o;
-    st = rp_read_opts(opts, o, fn); if (st != MCPT_OK) return st;
-    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
-    st = rp_ensure(ctx, true); if (st != MCPT_OK) return st;
-    // Everything below is stream work on the context's stream, ordered like mcpt_update_vertices.
-    const size_t n = size_t(ctx->width) * ctx->height;
-    hipStream_t s = ctx->stream;
-    const uint32_t seed_lo = uint32_t(o.feature_seed), seed_hi = uint32_t(o.feature_seed >> 32);
-    HIP_TRY(ctx->rp_watch.begin(s));
-    if (!ctx->dn_have_features) HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, static_cast<float4*>(ctx->dn_feat.p), s));
-    std::swap(ctx->dn_feat, ctx->rp_feat_old);                             // the old scene's features are kept where they lie
-    HIP_TRY(hipMemcpyAsync(ctx->rp_film_old.p, ctx->accum, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
-    if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->rp_vtx_old.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, s));
-    if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->rp_nrm_old.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, s));
-    const DevCamera old_cam = ctx->dev.cam;
-    st = rf_enqueue_update(ctx, vertex, n_vertex, normal); if (st != MCPT_OK) return st;
-    if (cm) apply_camera(ctx, *cm);
-    HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, static_cast<float4*>(ctx->dn_feat.p), s));
-    ctx->dn_have_features = true;                                          // those of the new scene and view: mcpt_denoise may follow at once
-    HIP_TRY(launch_rp_first_hit(ctx->dev, static_cast<float4*>(ctx->rp_hits.p), s));
-    st = rp_run_motion(ctx, old_cam, ctx->dev.cam, o, static_cast<const float4*>(ctx->rp_hits.p), static_cast<const double*>(ctx->rp_vtx_old.p),
-                       static_cast<const double*>(ctx->rp_nrm_old.p), static_cast<const float4*>(ctx->rp_film_old.p),
-                       static_cast<const float4*>(ctx->rp_feat_old.p), static_cast<const float4*>(ctx->dn_feat.p), ctx->accum,
-                       static_cast<unsigned long long*>(ctx->rp_count.p));
-    if (st != MCPT_OK) return st;
-    HIP_TRY(ctx->rp_watch.end(s));
-    ctx->rp_calls++;
-    return MCPT_OK;
+    const RfUpdate update{vertex, normal};
+    return rp_frame(ctx, &update, cm, opts, fn);
 }
 
 mcpt_status mcpt_probe_first_hits(mcpt_ctx* ctx, int32_t* out_face, float* out_uvt3) {
@@ -1480,50 +1472,40 @@ mcpt_status mcpt_probe_reproject_motion(mcpt_ctx* ctx, const mcpt_camera* old_ca
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!old_film_host || !old_feat8_host || !new_feat8_host || !hit_face_host || !hit_uv2_host || !out_film_host || !out_reused) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, std::string(fn) + ": the context was created without MCPT_FLAG_DYNAMIC");
-    st = check_camera(ctx, old_cam, "mcpt_probe_reproject_motion (old camera)"); if (st != MCPT_OK) return st;
-    st = check_camera(ctx, new_cam, "mcpt_probe_reproject_motion (new camera)"); if (st != MCPT_OK) return st;
-    mcpt_reproject_opts o;
-    st = rp_read_opts(opts, o, fn); if (st != MCPT_OK) return st;
-    st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
-    const size_t n = size_t(ctx->width) * ctx->height, nf = ctx->h_tri_face.size();
-    // hits the way mcpt_probe_hit_shade takes them (Model::face indices), turned into the kernel's records on the host; nothing out of range leaves it
-    std::vector<int32_t> leaf_of_face(nf, -1);
-    for (size_t i = 0; i < nf; i++) leaf_of_face[size_t(ctx->h_tri_face[i])] = int32_t(i);
-    std::vector<float> rec(4 * n, 0.f);
-    for (size_t i = 0; i < n; i++) {
-        const int32_t f = hit_face_host[i]; const float u = hit_uv2_host[2 * i], v = hit_uv2_host[2 * i + 1];
-        if (f < -1 || (f >= 0 && size_t(f) >= nf)) return fail(MCPT_ERR_INVALID_ARG, std::string(fn) + ": face index out of range");
-        if (!std::isfinite(u) || !std::isfinite(v)) return fail(MCPT_ERR_INVALID_ARG, std::string(fn) + ": a hit's u or v is not finite");
-        const int32_t tri = f < 0 ? -1 : leaf_of_face[size_t(f)];
-        std::memcpy(&rec[4 * i], &tri, 4); rec[4 * i + 1] = u; rec[4 * i + 2] = v;
-    }
-    DevCamera co, cn;
-    camera_constants(*old_cam, ctx->dev.centre, co); camera_constants(*new_cam, ctx->dev.centre, cn);
-    Scratch s(ctx->stream); float4 *hits, *film, *fo, *fnew, *out; unsigned long long* count;
-    const double* d_vtx = static_cast<const double*>(ctx->rf_vtx.p); const double* d_nrm = static_cast<const double*>(ctx->rf_nrm.p);
-    if (old_vertex) { double* d; HIP_TRY(s.in(old_vertex, size_t(ctx->rf_n_vertex) * 3, &d)); d_vtx = d; }
-    if (old_normal) { double* d; HIP_TRY(s.in(old_normal, size_t(ctx->rf_n_normal) * 3, &d)); d_nrm = d; }
-    HIP_TRY(s.in(reinterpret_cast<const float4*>(s.keep(std::move(rec))), n, &hits));
-    HIP_TRY(s.in(reinterpret_cast<const float4*>(old_film_host), n, &film));
-    HIP_TRY(s.in(reinterpret_cast<const float4*>(old_feat8_host), 2 * n, &fo)); HIP_TRY(s.in(reinterpret_cast<const float4*>(new_feat8_host), 2 * n, &fnew));
-    HIP_TRY(s.out(n, &out)); HIP_TRY(s.out(1, &count));
-    st = rp_run_motion(ctx, co, cn, o, hits, d_vtx, d_nrm, film, fo, fnew, out, count); if (st != MCPT_OK) return st;
-    unsigned long long c = 0;
-    HIP_TRY(s.fetch(&c, count, 1)); HIP_TRY(s.fetch(out_film_host, out, 4 * n)); HIP_TRY(s.finish());
-    *out_reused = c;
-    return MCPT_OK;
+    const auto stage_motion = [&](Scratch& s, RpOldScene& old) -> mcpt_status {
+        mcpt_status st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
+        const size_t n = size_t(ctx->width) * ctx->height, nf = ctx->h_tri_face.size();
+        // hits the way mcpt_probe_hit_shade takes them (Model::face indices), turned into the kernel's records on the host; nothing out of range leaves it
+        std::vector<int32_t> leaf_of_face(nf, -1);
+        for (size_t i = 0; i < nf; i++) leaf_of_face[size_t(ctx->h_tri_face[i])] = int32_t(i);
+        std::vector<float> rec(4 * n, 0.f);
+        for (size_t i = 0; i < n; i++) {
+            const int32_t f = hit_face_host[i]; const float u = hit_uv2_host[2 * i], v = hit_uv2_host[2 * i + 1];
+            if (f < -1 || (f >= 0 && size_t(f) >= nf)) return fail(MCPT_ERR_INVALID_ARG, std::string(fn) + ": face index out of range");
+            if (!std::isfinite(u) || !std::isfinite(v)) return fail(MCPT_ERR_INVALID_ARG, std::string(fn) + ": a hit's u or v is not finite");
+            const int32_t tri = f < 0 ? -1 : leaf_of_face[size_t(f)];
+            std::memcpy(&rec[4 * i], &tri, 4); rec[4 * i + 1] = u; rec[4 * i + 2] = v;
+        }
+        double *d_vtx = ctx->rf_vtx.p, *d_nrm = ctx->rf_nrm.p; float4* hits;   // the old scene: the caller's arrays, or the context's current ones
+        if (old_vertex) HIP_TRY(s.in(old_vertex, ctx->rf_vtx.count(), &d_vtx));
+        if (old_normal) HIP_TRY(s.in(old_normal, ctx->rf_nrm.count(), &d_nrm));
+        HIP_TRY(s.in(reinterpret_cast<const float4*>(s.keep(std::move(rec))), n, &hits));
+        old = RpOldScene{hits, d_vtx, d_nrm};
+        return MCPT_OK;
+    };
+    return rp_probe(ctx, fn, old_cam, new_cam, old_film_host, old_feat8_host, new_feat8_host, opts, stage_motion, out_film_host, out_reused);
 }
 
 mcpt_status mcpt_probe_validate_trees(mcpt_ctx* ctx) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    mcpt_status st = use_drained(ctx); if (st != MCPT_OK) return st;
     HostScene hs;
-    hs.nodes.resize(ctx->nodes.bytes / sizeof(f4h)); hs.nodes8.resize(ctx->nodes8.bytes / sizeof(f4h)); hs.tri_isect.resize(ctx->tri_isect.bytes / sizeof(f4h));
-    hs.tri_face.resize(size_t(ctx->dev.n_tris));
-    void* const to[4] = {hs.nodes.data(), hs.nodes8.data(), hs.tri_isect.data(), hs.tri_face.data()};
-    const DevBuf* const from[4] = {&ctx->nodes, &ctx->nodes8, &ctx->tri_isect, &ctx->tri_face};
-    for (int i = 0; i < 4; i++) { st = read_back(ctx, to[i], from[i]->p, from[i]->bytes, false); if (st != MCPT_OK) return st; }
+    auto get = [&](auto& host, const auto& dev) {
+        static_assert(sizeof(host[0]) == sizeof(*dev.p), "the host mirror of a device element has its size (f4h / float4)");
+        host.resize(dev.count());
+        return read_back(ctx, host.data(), dev.p, dev.bytes, false);
+    };
+    if ((st = get(hs.nodes, ctx->nodes)) != MCPT_OK || (st = get(hs.nodes8, ctx->nodes8)) != MCPT_OK || (st = get(hs.tri_isect, ctx->tri_isect)) != MCPT_OK ||
+        (st = get(hs.tri_face, ctx->tri_face)) != MCPT_OK) return st;
     std::string bad = validate_bvh8(hs);
     if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, "8-wide tree: " + bad);
     bad = validate_bvh2(hs);
@@ -1588,8 +1570,7 @@ mcpt_status mcpt_probe_trace4(mcpt_ctx* ctx, uint32_t n, const double* origin, c
     HIP_TRY(s.put(pool.shadow_queue, queue, P)); HIP_TRY(s.put(pool.shadow_count, qcount, nb));
     HIP_TRY(s.put(L.ctl_buf.p, ctl0, 1));
     const bool count = (ctx->opts.flags & MCPT_FLAG_COUNT_TRAVERSAL) != 0;
-    HIP_TRY(launch_wf_trace(ctx->dev, pool, static_cast<IterCtl*>(L.ctl_buf.p), 0u, ctx->tune, count, static_cast<DevCounters*>(ctx->counters.p), ctx->trace_grid,
-                            static_cast<int*>(L.ovf_buf.p), ctx->stream));
+    HIP_TRY(launch_wf_trace(ctx->dev, pool, L.ctl_buf.p, 0u, ctx->tune, count, ctx->counters.p, ctx->trace_grid, L.ovf_buf.p, ctx->stream));
     {   IterCtl snap; st = read_back(ctx, &snap, L.ctl_buf.p, sizeof snap, false); if (st != MCPT_OK) return st;
         if (job_state(snap, 0u, 0u) == JobState::Watchdog) return fail(MCPT_ERR_HIP, WATCHDOG_MSG); }
     if (any_hit) {

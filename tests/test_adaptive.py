@@ -168,6 +168,27 @@ def test_tile_list_subset_equals_the_full_render(pkg, which, monkeypatch):
 
 
 @pytest.mark.gpu
+def test_a_list_that_grows_between_unsynchronised_calls(pkg):
+    """The longer second list replaces the device list and its staging buffer while the first call may still be reading them: the pair equals the
+    same two calls with a synchronisation between them, bit for bit.  24 x 16 pixels = six tiles, lists of two and then five, one sample."""
+    w, h = 24, 16
+    scene = pkg.scenes.cornell_box_small(w, h)
+    first, second = np.asarray([4, 1], np.uint32), np.asarray([0, 1, 2, 3, 5], np.uint32)
+    films = []
+    for synchronised in (False, True):
+        r = pkg.Renderer(scene, max_depth=4)
+        r.render_tile_list(1, 9, 0, first)
+        if synchronised:
+            r.sync()
+        r.render_tile_list(1, 9, 1, second)
+        films.append(r.read_accum())
+        r.close()
+    assert np.array_equal(_bits(films[0]), _bits(films[1]))
+    count = _tile_mask(first, w, h).astype(np.float32) + _tile_mask(second, w, h)      # each call sampled its own tiles, once
+    assert np.array_equal(films[0][..., 3], count)
+
+
+@pytest.mark.gpu
 def test_bad_tile_lists_are_refused(pkg):
     r = pkg.Renderer(pkg.scenes.cornell_box_small(W, H), max_depth=4)
     prior = np.random.default_rng(2).uniform(0, 2, (H, W, 4)).astype(np.float32)
