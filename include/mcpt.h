@@ -372,6 +372,42 @@ mcpt_status mcpt_probe_reproject_motion(mcpt_ctx* ctx, const mcpt_camera* old_ca
                                         const int32_t* hit_face_host, const float* hit_uv2_host, const mcpt_reproject_opts* opts,
                                         float* out_film_host, uint64_t* out_reused);
 
+/* ---- material, light and texture edits of a live context -------------------------------------------------------------------- */
+/* What a surface looks like, edited without rebuilding anything: ks, ns, radiance and map_kd of every material (mcpt_update_materials) and the
+ * texels of one texture (mcpt_update_texture).  Both work on every context (MCPT_FLAG_DYNAMIC or not, either builder, both integrators) and are
+ * ordered like mcpt_update_vertices: asynchronous, all device work on the context's stream, so renders enqueued before the call see the old look
+ * and renders after it the new one.  Host data is staged through pinned memory and copied in stream order: the caller may reuse its arrays when
+ * the call returns.  Neither touches the film or the counters (the caller clears the film); the feature buffers, the denoised film and the
+ * adaptive tile error are dropped as after mcpt_set_camera.  A clone taken afterwards is a clone of the edited state, and a later
+ * mcpt_update_vertices works on the new light list.
+ *
+ * mcpt_update_materials: n_materials must equal creation's, and every map_kd must name one of the textures the context was created with
+ * (re-pointing a material at another of them is allowed).  Validated on the host before any device work; a refusal changes nothing:
+ * MCPT_ERR_INVALID_ARG for NULL, a wrong count, a map_kd out of range or a non-finite ks / ns / radiance; MCPT_ERR_NO_LIGHTS when no face would
+ * be left with |radiance| > 0.01.  The material records are formed by the function mcpt_create uses; the lobe class of every triangle and the
+ * light list -- membership by |radiance| > 0.01, in Model::face order -- are rebuilt on the device, bit for bit what mcpt_create of the edited
+ * scene uploads.  mcpt_scene_info::n_lights and device_bytes follow.  The first call allocates 4 B per face of scratch; the light buffers grow
+ * when the list outgrows them (one stream synchronisation then) and never shrink.
+ *
+ * mcpt_update_texture: new texels for texture `index`; width and height must equal creation's (else MCPT_ERR_INVALID_ARG).  A 1x1 texture is a
+ * constant Kd colour: its new value also reaches every material that maps it.  The light list is not touched. */
+mcpt_status mcpt_update_materials(mcpt_ctx* ctx, const mcpt_material* materials, uint32_t n_materials);
+mcpt_status mcpt_update_texture(mcpt_ctx* ctx, uint32_t index, const mcpt_texture* tex);
+typedef struct mcpt_material_info {
+    uint32_t struct_size, updates;      /* mcpt_update_materials calls on this context so far */
+    uint32_t n_lights, reserved0;       /* entries of the light list now */
+    double   last_ms;                   /* device time of the last mcpt_update_materials, first to last operation on the stream (HIP events) */
+    uint32_t reserved[4];
+} mcpt_material_info;
+mcpt_status mcpt_get_material_info(mcpt_ctx* ctx, mcpt_material_info* out);   /* synchronises */
+/* Probes, synchronous, touch nothing; both work on any context, so an edited context can be compared with a fresh one record for record.
+ * mcpt_probe_lights: per light in list order its face (Model::face order), out13 = {area, radiance[3], n0[3], n1[3], n2[3]} and the nine fp64
+ * corner coordinates the device samples it from (relative to mcpt_scene_info::centre).  *out_n = n_lights; capacity < n_lights is
+ * MCPT_ERR_INVALID_ARG with *out_n set.  mcpt_probe_face_classes: per face (n_face, Model::face order) the lobe set its hits are shaded with:
+ * 0 diffuse, 1 Blinn-Phong + diffuse, 2 mirror + diffuse. */
+mcpt_status mcpt_probe_lights(mcpt_ctx* ctx, uint32_t capacity, int32_t* out_face, float* out13, double* out_pos9, uint32_t* out_n);
+mcpt_status mcpt_probe_face_classes(mcpt_ctx* ctx, uint8_t* out_class);
+
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that
  * torch.distributed / RCCL all-reduces in place).  NULL re-binds the internal buffer. */

@@ -126,11 +126,39 @@ class ReprojectInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class MaterialInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("updates", C.c_uint32), ("n_lights", C.c_uint32), ("reserved0", C.c_uint32), ("last_ms", C.c_double),
+                ("reserved", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 def texture_to_float(img_u8: np.ndarray) -> np.ndarray:
     """What stbi_loadf gives the reference for an 8-bit image (model.cpp:8-23; stb_image.h:1553,1849):
     (c/255)^2.2 per channel, row 0 = first row of the file."""
     x = img_u8.astype(np.float32) / np.float32(255.0)
     return np.power(x, np.float32(2.2)).astype(np.float32)
+
+
+def material_texels(m: "scenes.Material") -> np.ndarray:
+    """The (h, w, 3) fp32 texels mcpt_create gets for a scenes.Material: its image, or its constant Kd as a 1x1 texture."""
+    if m.texture is not None and m.texture.dtype == np.float32:
+        return np.ascontiguousarray(m.texture)                    # already what stbi_loadf would return (tests feed reference texels)
+    if m.texture is not None:
+        return np.ascontiguousarray(texture_to_float(m.texture))
+    return np.asarray(m.kd, np.float32).reshape(1, 1, 3).copy()   # Texture(Color3f kd): kd parsed with stof (model.cpp:189-193)
+
+
+def _materials_c(materials, map_kd=None):
+    out = (MaterialC * len(materials))()
+    for i, m in enumerate(materials):
+        mc = out[i]
+        for k in range(3):
+            mc.ks[k] = float(m.ks[k]); mc.radiance[k] = float(m.radiance[k])
+        mc.ns = float(m.ns)
+        mc.map_kd = i if map_kd is None else int(map_kd[i])
+    return out
 
 
 class DescHolder:
@@ -143,24 +171,14 @@ class DescHolder:
         self.face = np.ascontiguousarray(scene.face, np.int32)
         self.tex_arrays = []
         n = len(scene.materials)
-        self.materials = (MaterialC * n)()
+        self.materials = _materials_c(scene.materials)
         self.textures = (Texture * n)()
         for i, m in enumerate(scene.materials):
-            if m.texture is not None and m.texture.dtype == np.float32:
-                t = np.ascontiguousarray(m.texture)               # already what stbi_loadf would return (tests feed reference texels)
-            elif m.texture is not None:
-                t = np.ascontiguousarray(texture_to_float(m.texture))
-            else:  # Texture(Color3f kd): kd parsed with stof (model.cpp:189-193)
-                t = np.asarray(m.kd, np.float32).reshape(1, 1, 3).copy()
+            t = material_texels(m)
             self.tex_arrays.append(t)
             self.textures[i].width = t.shape[1]
             self.textures[i].height = t.shape[0]
             self.textures[i].rgb = t.ctypes.data_as(C.POINTER(C.c_float))
-            mc = self.materials[i]
-            for k in range(3):
-                mc.ks[k] = float(m.ks[k]); mc.radiance[k] = float(m.radiance[k])
-            mc.ns = float(m.ns)
-            mc.map_kd = i
         d = SceneDesc()
         d.vertex = self.vertex.ctypes.data_as(C.POINTER(C.c_double)); d.n_vertex = self.vertex.shape[0]
         d.normal = self.normal.ctypes.data_as(C.POINTER(C.c_double)); d.n_normal = self.normal.shape[0]
@@ -243,6 +261,11 @@ def load_library() -> C.CDLL:
         "mcpt_update_vertices_reproject": [vp, vp, C.c_uint32, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
         "mcpt_probe_first_hits": [vp, vp, vp],
         "mcpt_probe_reproject_motion": [vp, P(CameraC), P(CameraC), vp, vp, vp, vp, vp, vp, vp, P(ReprojectOpts), vp, P(C.c_uint64)],
+        "mcpt_update_materials": [vp, P(MaterialC), C.c_uint32],
+        "mcpt_update_texture": [vp, C.c_uint32, P(Texture)],
+        "mcpt_get_material_info": [vp, P(MaterialInfo)],
+        "mcpt_probe_lights": [vp, C.c_uint32, vp, vp, vp, P(C.c_uint32)],
+        "mcpt_probe_face_classes": [vp, vp],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -267,6 +290,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_camera", "mcpt_update_vertices", "mcpt_get_update_info", "mcpt_probe_validate_trees",
     "mcpt_set_camera_reproject", "mcpt_get_reproject_info", "mcpt_probe_reproject",
     "mcpt_update_vertices_reproject", "mcpt_probe_first_hits", "mcpt_probe_reproject_motion",
+    "mcpt_update_materials", "mcpt_update_texture", "mcpt_get_material_info", "mcpt_probe_lights", "mcpt_probe_face_classes",
 ]
 
 
@@ -309,6 +333,7 @@ class Renderer:
                  samples_per_item=0):
         self.lib = load_library()
         self.holder = DescHolder(scene)
+        self.tex_arrays = list(self.holder.tex_arrays)            # the texels the context holds now (update_materials / update_texture replace entries)
         self.width, self.height = scene.camera.width, scene.camera.height
         o = Opts()
         o.struct_size = C.sizeof(Opts); o.device = device; o.max_depth = max_depth
@@ -320,6 +345,7 @@ class Renderer:
         """A second Renderer for the same scene (mcpt_clone_to_device): no flatten, no BVH build."""
         other = Renderer.__new__(Renderer)
         other.lib = self.lib; other.holder = self.holder; other.width, other.height = self.width, self.height
+        other.tex_arrays = list(self.tex_arrays)
         other.ctx = C.c_void_p()
         self._check(self.lib.mcpt_clone_to_device(self.ctx, int(device), C.byref(other.ctx)))
         return other
@@ -454,6 +480,48 @@ class Renderer:
         v = np.ascontiguousarray(vertex, np.float64).reshape(-1, 3)
         n = None if normal is None else np.ascontiguousarray(normal, np.float64).reshape(-1, 3)
         self._check(self.lib.mcpt_update_vertices(self.ctx, _ptr(v), v.shape[0], _ptr(n), 0 if n is None else n.shape[0]))
+
+    # ---- material, light and texture edits
+    def update_materials(self, materials, map_kd=None):
+        """New ks / ns / radiance for the same number of materials (a list of scenes.Material); map_kd: per material the index of the creation
+        texture it maps, None = its own.  Every material whose texels (built as DescHolder builds them) differ from the ones held gets them
+        replaced (update_texture; same size only).  Asynchronous; the caller clears the film."""
+        mats = _materials_c(materials, map_kd)
+        self._check(self.lib.mcpt_update_materials(self.ctx, mats, len(materials)))
+        for i, m in enumerate(materials[:len(self.tex_arrays)]):
+            t = material_texels(m)
+            if t.shape != self.tex_arrays[i].shape or not np.array_equal(t, self.tex_arrays[i]):
+                self.update_texture(i, t)
+
+    def update_texture(self, index: int, array):
+        """New (h, w, 3) fp32 texels for texture `index`, of the size it was created with; a 1x1 texture is a constant Kd colour."""
+        t = np.ascontiguousarray(array, np.float32)
+        if t.ndim != 3 or t.shape[2] != 3:
+            raise ValueError("update_texture: need an (h, w, 3) array")
+        tex = Texture()
+        tex.width = t.shape[1]; tex.height = t.shape[0]; tex.rgb = t.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(self.lib.mcpt_update_texture(self.ctx, int(index), C.byref(tex)))
+        if 0 <= index < len(self.tex_arrays):
+            self.tex_arrays[index] = t.copy()
+
+    def material_info(self) -> MaterialInfo:
+        i = MaterialInfo()
+        self._check(self.lib.mcpt_get_material_info(self.ctx, C.byref(i)))
+        return i
+
+    def probe_lights(self):
+        """The light list as the device holds it: ((n,) face in Model::face order, (n, 13) {area, radiance, n0, n1, n2}, (n, 9) fp64 corners)."""
+        cap = max(1, int(self.info().n_lights))
+        face = np.zeros(cap, np.int32); rec = np.zeros((cap, 13), np.float32); pos = np.zeros((cap, 9), np.float64)
+        n = C.c_uint32(0)
+        self._check(self.lib.mcpt_probe_lights(self.ctx, cap, _ptr(face), _ptr(rec), _ptr(pos), C.byref(n)))
+        return face[:n.value].copy(), rec[:n.value].copy(), pos[:n.value].copy()
+
+    def probe_face_classes(self) -> np.ndarray:
+        """(n_face,) uint8: the lobe class (0 diffuse, 1 Blinn-Phong, 2 mirror) every face's hits are shaded with."""
+        out = np.zeros(self.holder.face.shape[0], np.uint8)
+        self._check(self.lib.mcpt_probe_face_classes(self.ctx, _ptr(out)))
+        return out
 
     def update_info(self) -> UpdateInfo:
         i = UpdateInfo()

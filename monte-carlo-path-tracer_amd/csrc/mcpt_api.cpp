@@ -9,6 +9,7 @@
 #include "adaptive.h"
 #include "refit.h"
 #include "reproject.h"
+#include "materials.h"
 
 #include <chrono>
 #include <cmath>
@@ -206,6 +207,15 @@ struct mcpt_ctx {
     DevBuf<float4> rp_feat_old, rp_film_old, rp_hits; DevBuf<unsigned long long> rp_count; DevBuf<double> rp_vtx_old, rp_nrm_old;
     Stopwatch rp_watch;
     uint32_t rp_calls = 0;
+    // Material edits (materials.hip).  From creation on, on the host: the description's materials as they are now, per texture its
+    // place in `texels`, size and first texel, per material the faces that use it (the new light count is known before any device work).
+    // Allocated by the first mcpt_update_materials and counted in device_bytes: one word per face (light flag, then its prefix sum) and one per
+    // scan block.  `lights` / `light_pos64` only grow: their capacity is their buffers' count().
+    std::vector<mcpt_material> mt_mats; std::vector<TexInfo> mt_tex; std::vector<uint32_t> mt_faces;
+    DevBuf<uint32_t> mt_flag, mt_sums;
+    Staging<DevMaterial> mt_stage; Staging<float4> mt_tex_stage;
+    Stopwatch mt_watch; bool mt_have_watch = false;
+    uint32_t mt_updates = 0;
 };
 
 static mcpt_status read_back(mcpt_ctx* ctx, void* host, const void* dev, size_t bytes, bool timing = true);
@@ -529,6 +539,7 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
     in.bvh_depth = hs.bvh_depth; in.max_leaf = hs.max_leaf; in.width = uint32_t(c->width); in.height = uint32_t(c->height);
     in.bvh_build_ms = hs.bvh_build_ms;
     fill_wide_info(in, hs);
+    c->mt_mats.assign(scene->materials, scene->materials + scene->n_materials); c->mt_tex = hs.tex_info; c->mt_faces = hs.mat_faces;
     if ((st = finish_ctx(c)) != MCPT_OK) return st;
     if ((o.flags & MCPT_FLAG_DYNAMIC) && (st = rf_setup(c, hs, scene)) != MCPT_OK) return st;
     in.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -558,6 +569,7 @@ mcpt_status mcpt_clone_to_device(mcpt_ctx* src, int32_t device, mcpt_ctx** out_c
     HIP_TRY(copy(&mcpt_ctx::nodes)); HIP_TRY(copy(&mcpt_ctx::nodes8)); HIP_TRY(copy(&mcpt_ctx::tri_isect)); HIP_TRY(copy(&mcpt_ctx::tri_shade));
     HIP_TRY(copy(&mcpt_ctx::tri_pos64)); HIP_TRY(copy(&mcpt_ctx::tri_face)); HIP_TRY(copy(&mcpt_ctx::mats)); HIP_TRY(copy(&mcpt_ctx::lights));
     HIP_TRY(copy(&mcpt_ctx::light_pos64)); HIP_TRY(copy(&mcpt_ctx::texels));
+    c->mt_mats = src->mt_mats; c->mt_tex = src->mt_tex; c->mt_faces = src->mt_faces;
     if ((st = finish_ctx(c)) != MCPT_OK) return st;
     if (src->dynamic && (st = rf_clone(c, src)) != MCPT_OK) return st;
     c->info.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1293,6 +1305,132 @@ mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
         double a = 0.0;
         st = rf_read_area(ctx, a); if (st != MCPT_OK) return st;
         out->wide_area_ratio = ctx->rf_area0 > 0.0 ? a / ctx->rf_area0 : 1.0;
+    }
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ material edits
+// The device records of `mats` over the context's textures, into `out` (n_mats of them).
+static void mt_records(const mcpt_ctx* ctx, const std::vector<mcpt_material>& mats, DevMaterial* out) {
+    for (size_t i = 0; i < mats.size(); i++) out[i] = device_material(mats[i], ctx->mt_tex[size_t(mats[i].map_kd)]);
+}
+// `mats` staged and copied over the device records in stream order (`last`: the staging buffer's only copy of this filling).
+static mcpt_status mt_send_records(mcpt_ctx* ctx, const std::vector<mcpt_material>& mats) {
+    HIP_TRY(ctx->mt_stage.wait());
+    HIP_TRY(ctx->mt_stage.grow(mats.size()));
+    mt_records(ctx, mats, ctx->mt_stage.host);
+    HIP_TRY(ctx->mt_stage.send(ctx->mats.p, 0, mats.size(), ctx->stream));
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_update_materials(mcpt_ctx* ctx, const mcpt_material* materials, uint32_t n_materials) {
+    const std::string who = "mcpt_update_materials: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!materials) return fail(MCPT_ERR_INVALID_ARG, who + "null materials");
+    if (n_materials != uint32_t(ctx->dev.n_mats)) return fail(MCPT_ERR_INVALID_ARG, who + "n_materials differs from the scene's");
+    uint64_t n_lights = 0;
+    for (uint32_t i = 0; i < n_materials; i++) {
+        const mcpt_material& m = materials[i];
+        if (m.map_kd < 0 || size_t(m.map_kd) >= ctx->mt_tex.size()) return fail(MCPT_ERR_INVALID_ARG, who + "material " + std::to_string(i) + ": map_kd out of range");
+        bool finite = std::isfinite(m.ns);
+        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(m.ks[k]) && std::isfinite(m.radiance[k]);
+        if (!finite) return fail(MCPT_ERR_INVALID_ARG, who + "material " + std::to_string(i) + ": ks, ns or radiance is not finite");
+        if (device_material(m, ctx->mt_tex[size_t(m.map_kd)]).flags & MAT_EMIT_REC) n_lights += ctx->mt_faces[i];
+    }
+    if (n_lights == 0) return fail(MCPT_ERR_NO_LIGHTS, who + "no face would be left with |radiance| > 0.01");
+    const uint32_t nt = uint32_t(ctx->dev.n_tris);
+    uint64_t* tally = &ctx->info.device_bytes;
+    if (!ctx->mt_flag.p) HIP_TRY(alloc_all(Want(ctx->mt_flag, nt, tally), Want(ctx->mt_sums, mt_blocks(nt), tally)));
+    if (!ctx->mt_have_watch) { HIP_TRY(ctx->mt_watch.create()); ctx->mt_have_watch = true; }
+    HIP_TRY(ctx->mt_stage.wait());
+    HIP_TRY(ctx->mt_stage.grow(n_materials));
+    if (n_lights > ctx->lights.count()) {
+        // the list grows (rare): kernels enqueued earlier may still read the old buffers, which die when the new ones replace them
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(alloc_all(Want(ctx->lights, size_t(n_lights), tally), Want(ctx->light_pos64, 9 * size_t(n_lights), tally)));
+        ctx->dev.lights = ctx->lights.p; ctx->dev.light_pos64 = ctx->light_pos64.p;
+    }
+    // Everything below is stream work on the context's stream, ordered like mcpt_update_vertices: renders enqueued so far have joined it, the
+    // next render's sub-pipelines fork from it after the last kernel here.
+    hipStream_t s = ctx->stream;
+    const std::vector<mcpt_material> mats(materials, materials + n_materials);
+    HIP_TRY(ctx->mt_watch.begin(s));
+    st = mt_send_records(ctx, mats); if (st != MCPT_OK) return st;
+    HIP_TRY(launch_mt_classes(ctx->tri_isect.p, ctx->dev.tri_shade, ctx->dev.tri_face, ctx->dev.mats, n_materials, ctx->mt_flag.p, nt, s));
+    HIP_TRY(launch_mt_scan(ctx->mt_flag.p, ctx->mt_sums.p, nt, s));
+    HIP_TRY(launch_mt_emit(ctx->dev.tri_isect, ctx->dev.tri_shade, ctx->dev.tri_pos64, ctx->dev.tri_face, ctx->dev.mats, n_materials, ctx->mt_flag.p,
+                           ctx->lights.p, ctx->light_pos64.p, uint32_t(ctx->lights.count()), nt, s));
+    HIP_TRY(ctx->mt_watch.end(s));
+    ctx->mt_mats = mats;
+    ctx->dev.n_lights = int32_t(n_lights); ctx->info.n_lights = uint32_t(n_lights);
+    ctx->mt_updates++;
+    rf_forget_derived(ctx);
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_update_texture(mcpt_ctx* ctx, uint32_t index, const mcpt_texture* tex) {
+    const std::string who = "mcpt_update_texture: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!tex || !tex->rgb) return fail(MCPT_ERR_INVALID_ARG, who + "null texture");
+    if (size_t(index) >= ctx->mt_tex.size()) return fail(MCPT_ERR_INVALID_ARG, who + "texture index out of range");
+    TexInfo& t = ctx->mt_tex[index];
+    if (tex->width != t.w || tex->height != t.h) return fail(MCPT_ERR_INVALID_ARG, who + "width / height differ from the texture's at creation");
+    const size_t n = size_t(t.w) * size_t(t.h);
+    HIP_TRY(ctx->mt_tex_stage.wait());
+    HIP_TRY(ctx->mt_tex_stage.grow(n));
+    if (n == 1) { HIP_TRY(ctx->mt_stage.wait()); HIP_TRY(ctx->mt_stage.grow(ctx->mt_mats.size())); }   // (what can fail comes before anything changes)
+    float4* h = ctx->mt_tex_stage.host;
+    for (size_t k = 0; k < n; k++) h[k] = make_float4(tex->rgb[3 * k], tex->rgb[3 * k + 1], tex->rgb[3 * k + 2], 0.f);
+    HIP_TRY(ctx->mt_tex_stage.send(ctx->texels.p + t.off, 0, n, ctx->stream));
+    for (int k = 0; k < 3; k++) t.rgb[k] = tex->rgb[k];
+    if (n == 1) { st = mt_send_records(ctx, ctx->mt_mats); if (st != MCPT_OK) return st; }   // a constant colour lives in the material records too
+    rf_forget_derived(ctx);
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_get_material_info(mcpt_ctx* ctx, mcpt_material_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    if (ctx->mt_have_watch) HIP_TRY(ctx->mt_watch.settle());
+    std::memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out; out->updates = ctx->mt_updates; out->n_lights = uint32_t(ctx->dev.n_lights); out->last_ms = ctx->mt_watch.last_ms;
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_lights(mcpt_ctx* ctx, uint32_t capacity, int32_t* out_face, float* out13, double* out_pos9, uint32_t* out_n) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out_n) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    const uint32_t n = uint32_t(ctx->dev.n_lights);
+    *out_n = n;
+    if (capacity < n) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_lights: capacity < n_lights");
+    if (!out_face || !out13 || !out_pos9) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
+    std::vector<DevLight> rec(n);
+    st = read_back(ctx, rec.data(), ctx->lights.p, size_t(n) * sizeof(DevLight), false); if (st != MCPT_OK) return st;
+    st = read_back(ctx, out_pos9, ctx->light_pos64.p, 9 * size_t(n) * sizeof(double), false); if (st != MCPT_OK) return st;
+    for (uint32_t i = 0; i < n; i++) {
+        const DevLight& L = rec[i];
+        if (L.tri < 0 || L.tri >= ctx->dev.n_tris) return fail(MCPT_ERR_HIP, "mcpt_probe_lights: a light names an out-of-range triangle");
+        out_face[i] = ctx->h_tri_face[size_t(L.tri)];
+        float* o = out13 + 13 * size_t(i);
+        o[0] = L.area;
+        for (int k = 0; k < 3; k++) { o[1 + k] = L.radiance[k]; o[4 + k] = L.n0[k]; o[7 + k] = L.n1[k]; o[10 + k] = L.n2[k]; }
+    }
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_face_classes(mcpt_ctx* ctx, uint8_t* out_class) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out_class) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
+    const size_t nt = size_t(ctx->dev.n_tris);
+    std::vector<f4h> isect(3 * nt);
+    st = read_back(ctx, isect.data(), ctx->tri_isect.p, isect.size() * sizeof(f4h), false); if (st != MCPT_OK) return st;
+    for (size_t i = 0; i < nt; i++) {
+        uint32_t w; std::memcpy(&w, &isect[3 * i].w, 4);
+        out_class[size_t(ctx->h_tri_face[i])] = uint8_t(w >> HIT_CLASS_SHIFT);
     }
     return MCPT_OK;
 }

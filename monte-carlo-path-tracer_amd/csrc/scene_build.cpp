@@ -594,6 +594,22 @@ static void reference_triangle_order(const mcpt_scene_desc* d, std::vector<uint3
     for (uint32_t i = 0; i < nf; i++) rank[size_t(ord[i])] = i;
 }
 
+// The device record of a material whose Map_Kd is the texture `t`: what mcpt_create uploads and what mcpt_update_materials / mcpt_update_texture
+// rewrite.  The flags, their fp64 thresholds and the constant-kd copy have this one source.
+DevMaterial device_material(const mcpt_material& m, const TexInfo& t) {
+    DevMaterial dm; std::memset(&dm, 0, sizeof dm);
+    for (int k = 0; k < 3; k++) { dm.ks[k] = float(m.ks[k]); dm.radiance[k] = float(m.radiance[k]); }
+    dm.ns = float(m.ns);
+    if (len3(m.ks) != 0.0) { dm.flags |= MAT_HAS_SPEC; if (m.ns >= 10000) dm.flags |= MAT_MIRROR; }   // BSDF.cpp:96-98
+    const double rl = len3(m.radiance);
+    if (rl != 0.0) dm.flags |= MAT_EMISSIVE;
+    if (rl > 0.0001) dm.flags |= MAT_EMIT_0;
+    if (rl > 0.01) dm.flags |= MAT_EMIT_REC;
+    dm.tex_off = t.off; dm.tex_w = t.w; dm.tex_h = t.h;
+    if (dm.tex_w * dm.tex_h == 1) { dm.flags |= MAT_CONST_KD; for (int k = 0; k < 3; k++) dm.kd[k] = t.rgb[k]; }
+    return dm;
+}
+
 mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::string& err, const BvhBuildFn& custom_bvh, const Collapse8Fn& custom_collapse8) {
     if (!d || !d->vertex || !d->normal || !d->texcoord || !d->face || !d->materials || !d->textures) { err = "null pointer in mcpt_scene_desc"; return MCPT_ERR_INVALID_ARG; }
     if (d->n_face == 0 || d->n_materials == 0 || d->n_textures == 0) { err = "empty scene"; return MCPT_ERR_INVALID_ARG; }
@@ -604,28 +620,18 @@ mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::stri
 
     // ---- materials + textures
     out.texels.clear(); out.mats.clear();
-    std::vector<int32_t> tex_off(d->n_textures);
+    out.tex_info.assign(d->n_textures, TexInfo{});
     for (uint32_t i = 0; i < d->n_textures; i++) {
         const mcpt_texture& t = d->textures[i];
         if (t.width <= 0 || t.height <= 0 || !t.rgb) { err = "bad texture " + std::to_string(i); return MCPT_ERR_INVALID_ARG; }
-        tex_off[i] = int32_t(out.texels.size());
+        out.tex_info[i] = TexInfo{int32_t(out.texels.size()), t.width, t.height, {t.rgb[0], t.rgb[1], t.rgb[2]}};
         const size_t n = size_t(t.width) * t.height;
         for (size_t k = 0; k < n; k++) out.texels.push_back({t.rgb[3 * k], t.rgb[3 * k + 1], t.rgb[3 * k + 2], 0.f});
     }
     for (uint32_t i = 0; i < d->n_materials; i++) {
         const mcpt_material& m = d->materials[i];
         if (m.map_kd < 0 || uint32_t(m.map_kd) >= d->n_textures) { err = "material " + std::to_string(i) + ": map_kd out of range (the reference dereferences a null Map_Kd here)"; return MCPT_ERR_INVALID_ARG; }
-        DevMaterial dm; std::memset(&dm, 0, sizeof dm);
-        for (int k = 0; k < 3; k++) { dm.ks[k] = float(m.ks[k]); dm.radiance[k] = float(m.radiance[k]); }
-        dm.ns = float(m.ns);
-        if (len3(m.ks) != 0.0) { dm.flags |= MAT_HAS_SPEC; if (m.ns >= 10000) dm.flags |= MAT_MIRROR; }   // BSDF.cpp:96-98
-        const double rl = len3(m.radiance);
-        if (rl != 0.0) dm.flags |= MAT_EMISSIVE;
-        if (rl > 0.0001) dm.flags |= MAT_EMIT_0;
-        if (rl > 0.01) dm.flags |= MAT_EMIT_REC;
-        dm.tex_off = tex_off[m.map_kd]; dm.tex_w = d->textures[m.map_kd].width; dm.tex_h = d->textures[m.map_kd].height;
-        if (dm.tex_w * dm.tex_h == 1) { dm.flags |= MAT_CONST_KD; for (int k = 0; k < 3; k++) dm.kd[k] = d->textures[m.map_kd].rgb[k]; }
-        out.mats.push_back(dm);
+        out.mats.push_back(device_material(m, out.tex_info[size_t(m.map_kd)]));
     }
 
     // ---- flatten faces (Render.cpp:12-44).  Coordinates are taken relative to the fp64 centre of the scene's bounding box (DevScene::centre):
@@ -771,9 +777,11 @@ mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::stri
 
     // ---- lights in face order (Render.cpp:41-42)
     out.lights.clear(); out.light_pos64.clear();
+    out.mat_faces.assign(d->n_materials, 0u);                              // what mcpt_update_materials knows the new light count from
     for (uint32_t f = 0; f < nf; f++) {
         const int32_t* c = d->face + 12 * size_t(f);
         const mcpt_material& m = d->materials[c[3]];
+        out.mat_faces[size_t(c[3])]++;
         if (!(len3(m.radiance) > 0.01)) continue;
         DevLight L; std::memset(&L, 0, sizeof L);
         L.tri = pos_of_face[f];

@@ -10,6 +10,10 @@
 
 struct f4h { float x, y, z, w; };   // host mirror of float4 (16 B)
 
+// What a material record needs of its texture: where its texels start in DevScene::texels, its size, and its first texel (the constant colour of a
+// 1x1 texture).  mcpt_create keeps the table, mcpt_update_texture edits it.
+struct TexInfo { int32_t off, w, h; float rgb[3]; };
+
 struct HostScene {
     std::vector<f4h> nodes;          // 4 per inner node (binary tree: megakernel + probes)
     std::vector<f4h> nodes8;         // 5 per node of the 8-wide compressed tree (wavefront trace kernel)
@@ -21,6 +25,8 @@ struct HostScene {
     std::vector<DevLight> lights;
     std::vector<double> light_pos64; // 9 per light
     std::vector<f4h> texels;
+    std::vector<TexInfo> tex_info;   // per texture of the description
+    std::vector<uint32_t> mat_faces; // per material: the faces that use it
     DevCamera cam;
     double centre[3] = {0.0, 0.0, 0.0};   // the point every coordinate above is relative to (device_scene.h: DevScene::centre)
     uint32_t bvh_depth = 0, max_leaf = 0, bvh8_depth = 0;
@@ -57,6 +63,9 @@ inline std::string validate_wide_bvh(const HostScene& hs) { return validate_bvh8
 bool rf_levels(const std::vector<f4h>& n2, const std::vector<f4h>& n8, std::vector<uint32_t>& bin_order, std::vector<uint32_t>& bin_level,
                std::vector<uint32_t>& wide_level, std::string& err);
 
+// The DevMaterial of `m` over its texture `t` (t = tex_info[m.map_kd], range-checked by the caller): used by mcpt_create, mcpt_update_materials and
+// mcpt_update_texture.
+DevMaterial device_material(const mcpt_material& m, const TexInfo& t);
 // DevCamera of `camera` for a scene centred at `centre` (fp64, the reference's operation order): used by mcpt_create and mcpt_set_camera.
 void camera_constants(const mcpt_camera& camera, const double* centre, DevCamera& out);
 // The coordinate bound build_host_scene enforces on every vertex a face uses.

@@ -35,13 +35,14 @@ void Render::create(Model& m, const mcpt_opts& opts) {
     model_to_desc(m, mats, texs, d);
     if (mcpt_create(&d, &opts, &ctx) != MCPT_OK) { std::cerr << "Error: mcpt_create: " << mcpt_last_error() << std::endl; ctx = nullptr; return; }
     film.resize(size_t(d.camera.width) * d.camera.height * 4);
+    for (const mcpt_texture& t : texs) { tex_size.push_back(t.width); tex_size.push_back(t.height); }
 }
 Render::Render(Model& m) { mcpt_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; create(m, o); }
 Render::Render(Model& m, const mcpt_opts& opts) { create(m, opts); }
 Render::Render(Render& other, int device) {
     seed = other.seed;
     if (!other.ctx || mcpt_clone_to_device(other.ctx, device, &ctx) != MCPT_OK) { std::cerr << "Error: mcpt_clone_to_device: " << mcpt_last_error() << std::endl; ctx = nullptr; return; }
-    film.resize(other.film.size());
+    film.resize(other.film.size()); tex_size = other.tex_size;
 }
 Render::~Render() {
     if (target) { flush_into(*target); target->detach(this); }
@@ -157,6 +158,21 @@ bool Render::update(Scene& scene, Model& m) {
     if (mcpt_update_vertices(ctx, reinterpret_cast<const double*>(m.vertex.data()), uint32_t(m.vertex.size()), reinterpret_cast<const double*>(m.normal.data()),
                              uint32_t(m.normal.size())) != MCPT_OK) { std::cerr << "Error: mcpt_update_vertices: " << mcpt_last_error() << std::endl; return false; }
     if (mcpt_set_camera(ctx, &k) != MCPT_OK) { std::cerr << "Error: mcpt_set_camera: " << mcpt_last_error() << std::endl; return false; }
+    return restart(scene);
+}
+bool Render::update_materials(Scene& scene, Model& m) {
+    if (!ctx) return false;
+    std::vector<mcpt_material> mats; std::vector<mcpt_texture> texs; mcpt_scene_desc d;
+    model_to_desc(m, mats, texs, d);
+    // everything that can be refused is checked before anything changes: the texture sizes here, the rest by mcpt_update_materials itself
+    if (2 * texs.size() != tex_size.size()) { std::cerr << "Error: Render::update_materials: the number of materials changed" << std::endl; return false; }
+    for (size_t i = 0; i < texs.size(); i++)
+        if (texs[i].width != tex_size[2 * i] || texs[i].height != tex_size[2 * i + 1]) {
+            std::cerr << "Error: Render::update_materials: the image of material " << i << " changed its size" << std::endl; return false;
+        }
+    if (mcpt_update_materials(ctx, mats.data(), uint32_t(mats.size())) != MCPT_OK) { std::cerr << "Error: mcpt_update_materials: " << mcpt_last_error() << std::endl; return false; }
+    for (size_t i = 0; i < texs.size(); i++)
+        if (mcpt_update_texture(ctx, uint32_t(i), &texs[i]) != MCPT_OK) { std::cerr << "Error: mcpt_update_texture: " << mcpt_last_error() << std::endl; return false; }
     return restart(scene);
 }
 void Render::flush_into(Scene& scene) {

@@ -41,6 +41,10 @@ public:
     // and the Scene's samples are unchanged, the samples are then all on the host).
     bool set_camera_reproject(Scene& scene, const CameraInfo& camera, float max_history = 0);
     bool update(Scene& scene, Model& m_model);
+    // Materials, lights and textures re-read from `m_model` (mcpt_update_materials / mcpt_update_texture) after the caller edited
+    // Model::materials in place: Ks, Ns, radiance and the Map_Kd images, each of the size it had when this Render was made; same number of
+    // materials.  Works on every Render.  Starts the picture again like update().  false (and an unchanged Render and Scene) on failure.
+    bool update_materials(Scene& scene, Model& m_model);
     // update that carries the picture over (mcpt_update_vertices_reproject): positions and normals re-read from `m_model`, the
     // camera kept -- or, second form, replaced by `camera` in the same call (Model::camerainfo is not read).  `scene`'s film is treated as by
     // set_camera_reproject: brought to the device, looked up where the new view's surface points WERE, left there as `scene`'s film with at most
@@ -61,6 +65,7 @@ private:
     bool dirty = false;                               // the device film holds samples `target` has not seen
     bool features = false;                            // mcpt_render_features has run for this context
     std::vector<Color3b> denoised_rgb;
+    std::vector<int32_t> tex_size;                    // width, height of every material's Map_Kd at creation
     void create(Model& m, const mcpt_opts& opts);
     bool restart(Scene& scene);
     bool film_to_device(Scene& scene, const char* who, bool& ok);

@@ -30,6 +30,8 @@ static void usage() {
                  "                                        of history per pixel) instead of starting empty\n"
                  "                          [--wobble A]   with --turntable: every frame after the first also displaces the vertices by\n"
                  "                                        A sin(2 pi frame / N) (sin 9y, sin 7z, sin 8x) (device-side refit; with --reproject the film follows the surfaces)\n"
+                 "                          [--light-pulse A]   with --turntable: frame k scales the radiance of every emissive material by 1 + A sin(2 pi k / N)\n"
+                 "                                        (materials and light list edited on the device, the film restarts every frame; not with --reproject)\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -58,6 +60,7 @@ int main(int argc, char** argv) {
     float adaptive = -1.f; uint32_t min_spp = 0, turntable = 0;
     bool reproject = false; float history = 0.f;
     bool wobble = false; double wobble_a = 0.0;
+    bool pulse = false; double pulse_a = 0.0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -77,12 +80,15 @@ int main(int argc, char** argv) {
         else if (a == "--turntable") turntable = uint32_t(std::atoi(next()));
         else if (a == "--reproject") { reproject = true; history = float(std::atof(next())); }
         else if (a == "--wobble") { wobble = true; wobble_a = std::atof(next()); }
+        else if (a == "--light-pulse") { pulse = true; pulse_a = std::atof(next()); }
         else { usage(); return 2; }
     }
     if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
     if (turntable && (gpus > 1 || adaptive >= 0.f)) { std::cerr << "Error: --turntable renders on one GPU, without --adaptive" << std::endl; return 2; }
     if (reproject && (!turntable || !(history >= 1.f))) { std::cerr << "Error: --reproject H needs --turntable N and H >= 1" << std::endl; return 2; }
     if (wobble && (!turntable || !(std::fabs(wobble_a) <= 1e6))) { std::cerr << "Error: --wobble A needs --turntable N and a finite A" << std::endl; return 2; }
+    if (pulse && (!turntable || !(std::fabs(pulse_a) <= 1e6))) { std::cerr << "Error: --light-pulse A needs --turntable N and a finite A" << std::endl; return 2; }
+    if (pulse && reproject) { std::cerr << "Error: --light-pulse restarts the film every frame: radiance reprojected across it would be the old light's (drop --reproject)" << std::endl; return 2; }
     if (wobble) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
@@ -144,6 +150,7 @@ int main(int argc, char** argv) {
     if (turntable) {
         const CameraInfo base = model.camerainfo;
         const std::vector<dvec3> rest = model.vertex;                        // --wobble displaces from these
+        const std::vector<Material> lit = model.materials;                   // --light-pulse scales these
         const double ul = std::sqrt(base.up.x * base.up.x + base.up.y * base.up.y + base.up.z * base.up.z);
         if (!(ul > 0.0)) { std::cerr << "Error: --turntable needs a camera with an up vector" << std::endl; return 1; }
         const double k[3] = {base.up.x / ul, base.up.y / ul, base.up.z / ul}, v[3] = {base.eye.x - base.lookat.x, base.eye.y - base.lookat.y, base.eye.z - base.lookat.z};
@@ -155,6 +162,14 @@ int main(int argc, char** argv) {
             cam.eye.y = base.lookat.y + v[1] * ca + kx[1] * sa + k[1] * kv * (1.0 - ca);
             cam.eye.z = base.lookat.z + v[2] * ca + kx[2] * sa + k[2] * kv * (1.0 - ca);
             auto t0 = std::chrono::steady_clock::now();
+            if (pulse) {                                                     // --light-pulse A: the lamps breathe; the camera call below restarts the film
+                const double g = 1.0 + pulse_a * std::sin(2.0 * 3.14159265358979323846 * double(f) / double(turntable));
+                for (size_t i = 0; i < lit.size(); i++) {
+                    model.materials[i].radiance.x = lit[i].radiance.x * g; model.materials[i].radiance.y = lit[i].radiance.y * g;
+                    model.materials[i].radiance.z = lit[i].radiance.z * g;
+                }
+                if (!renders[0]->update_materials(scene, model)) return 1;
+            }
             // --reproject H: frames after the first keep what the previous frame saw of the same surfaces
             if (wobble && f > 0) {                                           // --wobble A: the vertices move too, and with --reproject the film follows them (§14)
                 const double s = wobble_a * std::sin(2.0 * 3.14159265358979323846 * double(f) / double(turntable));
