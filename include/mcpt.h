@@ -279,7 +279,7 @@ mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* camera);
 mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal);
 
 typedef struct mcpt_update_info {
-    uint32_t struct_size, updates;      /* mcpt_update_vertices (+ _reproject) calls on this context so far */
+    uint32_t struct_size, updates;      /* mcpt_update_vertices / mcpt_update_transforms (+ _reproject) calls on this context so far */
     double   last_update_ms;            /* device time of the last one, first to last operation on the stream (HIP events) */
     double   wide_area_ratio;           /* sum of the child-box areas of the 8-wide tree now / at creation (dequantised boxes; 1.0 before any update) */
     uint32_t reserved[4];
@@ -322,7 +322,7 @@ typedef struct mcpt_reproject_opts {
     uint32_t reserved[3];
 } mcpt_reproject_opts;
 typedef struct mcpt_reproject_info {
-    uint32_t struct_size, reprojections;   /* mcpt_set_camera_reproject + mcpt_update_vertices_reproject calls on this context so far */
+    uint32_t struct_size, reprojections;   /* mcpt_set_camera_reproject + mcpt_update_{vertices,transforms}_reproject calls so far */
     uint64_t pixels_reused;                /* pixels of the last call written with a history of >= 1 sample */
     double   last_ms;                      /* device time of the last call, first to last operation on the stream (HIP events) */
     uint32_t reserved[4];
@@ -407,6 +407,56 @@ mcpt_status mcpt_get_material_info(mcpt_ctx* ctx, mcpt_material_info* out);   /*
  * 0 diffuse, 1 Blinn-Phong + diffuse, 2 mirror + diffuse. */
 mcpt_status mcpt_probe_lights(mcpt_ctx* ctx, uint32_t capacity, int32_t* out_face, float* out13, double* out_pos9, uint32_t* out_n);
 mcpt_status mcpt_probe_face_classes(mcpt_ctx* ctx, uint8_t* out_class);
+
+/* ---- rigid parts moved by per-group transforms on the device ----------------------------------------------------------------- */
+/* The usual animation moves a few rigid parts.  Instead of computing every vertex on the host and sending all of them (mcpt_update_vertices), the
+ * caller names a group per vertex and per normal once and then sends one 3x4 matrix per group and frame: the device keeps a REST POSE and writes
+ * the current vertices and normals from it.  All three calls need MCPT_FLAG_DYNAMIC (else MCPT_ERR_UNSUPPORTED).
+ *
+ * mcpt_set_vertex_groups: set-up, synchronous.  n_vertex / n_normal must equal the scene's, 1 <= n_groups <= n_vertex + n_normal, every id
+ * < n_groups (normal_group may be NULL when n_normal is 0); a violation is MCPT_ERR_INVALID_ARG with nothing changed.  Groups are per vertex and
+ * per normal, not per face (the context keeps no host copy of the faces): a vertex or normal shared by two parts is the caller's to duplicate.
+ * The context's CURRENT vertices and normals become the rest pose (copied device to device), the ids are uploaded, and per group R_g -- the
+ * largest |coordinate| among its vertices that a face uses, 0 without any -- is kept for the validation below (one read-back of the vertices).
+ * Calling it again replaces the groups and takes the rest pose anew.  Allocates, counted in device_bytes, 24 B x (n_vertex + n_normal) for the
+ * rest pose, 4 B x (n_vertex + n_normal) for the ids and 168 B x n_groups for the table (per group the 12 doubles of its matrix and the 9 of its
+ * cofactor matrix), plus a pinned stage of the table's size.  mcpt_clone_to_device carries the groups, the rest pose and R_g.
+ *
+ * mcpt_update_transforms: m3x4 holds n_groups row-major 3x4 matrices [A | t] in world space.  Every vertex becomes A rest + t of its group -- per
+ * row ((a0 x + a1 y) + a2 z) + t in fp64, in that association -- and every normal cof(A) rest_normal, normalised (cof(A) = det(A) A^-T, so
+ * nothing is divided by the determinant; a result of length 0 or not finite is left as it is).
+ *  - MIRRORING (det A < 0): cof(A) carries a normal the way it carries the cross product of a triangle's edges, so the normals of a mirrored
+ *    part come out on the side its stored winding faces -- for a closed part that is INTO the object.  This renderer orients a surface by its
+ *    vertex normals alone (front = dot(normal, direction) < 0; an emitter radiates to its normals' side), never by the winding: a mirrored
+ *    sphere is shaded as seen from inside and a mirrored lamp radiates to its other side.  A caller who mirrors a part and wants it to look
+ *    mirrored, not turned inside out, negates that part's normals as well: mcpt_update_vertices with the normals negated BEFORE
+ *    mcpt_set_vertex_groups, so that the rest pose holds them.
+ * From there on the call IS mcpt_update_vertices after its upload: the same refit, ordering, bookkeeping (mcpt_get_update_info counts it, and
+ * last_update_ms spans the transform kernels and the refit) and what it leaves untouched (film, counters) or drops (features, denoised film,
+ * tile error).
+ *  - Transforms apply to the rest pose and never accumulate: the same matrices twice give the same scene, identities give the rest pose back.  A
+ *    later mcpt_update_vertices moves the scene and leaves the rest pose alone; the next mcpt_update_transforms overwrites what it wrote.
+ *  - Validated on the host before any device work, a refusal changes nothing; in this order: MCPT_ERR_UNSUPPORTED without MCPT_FLAG_DYNAMIC;
+ *    MCPT_ERR_INVALID_ARG when no groups are set, for NULL or another n_groups, for an entry that is not finite, for det A zero or not finite,
+ *    and when for some row (|a0| + |a1| + |a2|) R_g + |t| exceeds 1e18 or is not finite.  That row bound is CONSERVATIVE: it may refuse a
+ *    transform whose vertices mcpt_update_vertices would accept just under 1e18; in exchange validation needs no device round trip.
+ *  - Asynchronous on the context's stream.  The matrices are staged through pinned memory and copied in stream order: the caller may reuse its
+ *    array when the call returns, and back-to-back calls cannot overtake each other.
+ *
+ * mcpt_update_transforms_reproject is mcpt_update_vertices_reproject with the transform in place of the upload; validation order: the matrices,
+ * the camera (when given), the options, MCPT_ERR_BVH_DEPTH. */
+mcpt_status mcpt_set_vertex_groups(mcpt_ctx* ctx, const uint32_t* vertex_group, uint32_t n_vertex, const uint32_t* normal_group, uint32_t n_normal,
+                                   uint32_t n_groups);
+mcpt_status mcpt_update_transforms(mcpt_ctx* ctx, const double* m3x4, uint32_t n_groups);
+mcpt_status mcpt_update_transforms_reproject(mcpt_ctx* ctx, const double* m3x4, uint32_t n_groups, const mcpt_camera* camera /* NULL = keep */,
+                                             const mcpt_reproject_opts* opts /* NULL = defaults */);
+typedef struct mcpt_transform_info {
+    uint32_t struct_size, n_groups;     /* groups set now (0 = none) */
+    uint32_t updates, reserved0;        /* mcpt_update_transforms (+ _reproject) calls on this context so far */
+    double   last_ms;                   /* device time of the last one's transform part: the table's copy and the two kernels (HIP events) */
+    uint32_t reserved[4];
+} mcpt_transform_info;
+mcpt_status mcpt_get_transform_info(mcpt_ctx* ctx, mcpt_transform_info* out);   /* synchronises */
 
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that

@@ -134,6 +134,14 @@ class MaterialInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class TransformInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_groups", C.c_uint32), ("updates", C.c_uint32), ("reserved0", C.c_uint32), ("last_ms", C.c_double),
+                ("reserved", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 def texture_to_float(img_u8: np.ndarray) -> np.ndarray:
     """What stbi_loadf gives the reference for an 8-bit image (model.cpp:8-23; stb_image.h:1553,1849):
     (c/255)^2.2 per channel, row 0 = first row of the file."""
@@ -266,6 +274,10 @@ def load_library() -> C.CDLL:
         "mcpt_get_material_info": [vp, P(MaterialInfo)],
         "mcpt_probe_lights": [vp, C.c_uint32, vp, vp, vp, P(C.c_uint32)],
         "mcpt_probe_face_classes": [vp, vp],
+        "mcpt_set_vertex_groups": [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32],
+        "mcpt_update_transforms": [vp, vp, C.c_uint32],
+        "mcpt_update_transforms_reproject": [vp, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
+        "mcpt_get_transform_info": [vp, P(TransformInfo)],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -291,6 +303,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_camera_reproject", "mcpt_get_reproject_info", "mcpt_probe_reproject",
     "mcpt_update_vertices_reproject", "mcpt_probe_first_hits", "mcpt_probe_reproject_motion",
     "mcpt_update_materials", "mcpt_update_texture", "mcpt_get_material_info", "mcpt_probe_lights", "mcpt_probe_face_classes",
+    "mcpt_set_vertex_groups", "mcpt_update_transforms", "mcpt_update_transforms_reproject", "mcpt_get_transform_info",
 ]
 
 
@@ -315,6 +328,25 @@ def _reproject_opts(feature_spp=0, feature_seed=0, max_history=0.0, depth_tolera
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def groups_from_faces(scene: "scenes.SceneData", face_group):
+    """Per-vertex and per-normal group ids (two uint32 arrays, for Renderer.set_vertex_groups) from one id per face: a vertex or normal takes
+    the group of the faces that use it, one no face uses gets group 0.  Raises ValueError when faces of two groups share a vertex or a normal --
+    the caller duplicates it then."""
+    fg = np.ascontiguousarray(face_group, np.int64).reshape(-1)
+    if fg.shape[0] != scene.face.shape[0] or (fg.size and fg.min() < 0):
+        raise ValueError("groups_from_faces: need one group id >= 0 per face")
+    out = []
+    for what, col, n in (("vertex", 0, scene.vertex.shape[0]), ("normal", 1, scene.normal.shape[0])):
+        idx = scene.face[:, :, col].astype(np.int64).reshape(-1); g = np.repeat(fg, 3)
+        lo = np.full(n, np.iinfo(np.int64).max, np.int64); hi = np.full(n, -1, np.int64)
+        np.minimum.at(lo, idx, g); np.maximum.at(hi, idx, g)
+        shared = np.flatnonzero((hi >= 0) & (lo != hi))
+        if shared.size:
+            raise ValueError("groups_from_faces: %s %d is used by faces of groups %d and %d" % (what, shared[0], lo[shared[0]], hi[shared[0]]))
+        out.append(np.where(hi >= 0, hi, 0).astype(np.uint32))
+    return out[0], out[1]
 
 
 def check_scene(scene: "scenes.SceneData"):
@@ -480,6 +512,38 @@ class Renderer:
         v = np.ascontiguousarray(vertex, np.float64).reshape(-1, 3)
         n = None if normal is None else np.ascontiguousarray(normal, np.float64).reshape(-1, 3)
         self._check(self.lib.mcpt_update_vertices(self.ctx, _ptr(v), v.shape[0], _ptr(n), 0 if n is None else n.shape[0]))
+
+    # ---- rigid parts moved by per-group transforms
+    def set_vertex_groups(self, vertex_group, normal_group, n_groups: int):
+        """A group id per vertex and per normal (groups_from_faces derives them from faces); the scene as it is now becomes the rest pose
+        update_transforms moves.  Needs FLAG_DYNAMIC.  Synchronous."""
+        vg = np.ascontiguousarray(vertex_group, np.uint32).reshape(-1); ng = np.ascontiguousarray(normal_group, np.uint32).reshape(-1)
+        self._check(self.lib.mcpt_set_vertex_groups(self.ctx, _ptr(vg), vg.size, _ptr(ng) if ng.size else None, ng.size, int(n_groups)))
+
+    @staticmethod
+    def _matrices(matrices) -> np.ndarray:
+        m = np.ascontiguousarray(matrices, np.float64)
+        if m.size % 12:
+            raise ValueError("need (n_groups, 3, 4) matrices")
+        return m.reshape(-1, 3, 4)
+
+    def update_transforms(self, matrices):
+        """One row-major 3x4 matrix [A | t] per group, applied to the REST pose on the device (never accumulated), then update_vertices' refit:
+        only the matrices cross the bus.  Asynchronous; the caller clears the film."""
+        m = self._matrices(matrices)
+        self._check(self.lib.mcpt_update_transforms(self.ctx, _ptr(m), m.shape[0]))
+
+    def update_transforms_reproject(self, matrices, camera=None, **opts):
+        """update_transforms that carries the film over, as update_vertices_reproject does; opts: reproject_camera's."""
+        m = self._matrices(matrices)
+        c = None if camera is None else C.byref(_camera_c(camera))
+        o = _reproject_opts(**opts)
+        self._check(self.lib.mcpt_update_transforms_reproject(self.ctx, _ptr(m), m.shape[0], c, C.byref(o)))
+
+    def transform_info(self) -> TransformInfo:
+        i = TransformInfo()
+        self._check(self.lib.mcpt_get_transform_info(self.ctx, C.byref(i)))
+        return i
 
     # ---- material, light and texture edits (DESIGN.md §15)
     def update_materials(self, materials, map_kd=None):

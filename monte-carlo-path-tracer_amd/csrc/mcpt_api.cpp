@@ -8,6 +8,7 @@
 #include "denoise.h"
 #include "adaptive.h"
 #include "refit.h"
+#include "transform.h"
 #include "reproject.h"
 #include "materials.h"
 
@@ -200,6 +201,13 @@ struct mcpt_ctx {
     Staging<double> rf_stage;                               // the vertices, then the normals
     Stopwatch rf_watch;
     uint32_t rf_updates = 0; double rf_area0 = 0.0;
+    // Rigid parts (transform.hip), allocated by mcpt_set_vertex_groups and counted in device_bytes: the rest pose (rf_vtx's and
+    // rf_nrm's sizes), a group id per vertex and per normal, the table of XF_RECORD doubles per group and its pinned staging.  On the host per
+    // group R_g, the largest |coordinate| among its vertices that a face uses (what mcpt_update_transforms validates against).
+    DevBuf<double> xf_rest_vtx, xf_rest_nrm, xf_table; DevBuf<uint32_t> xf_vgroup, xf_ngroup;
+    Staging<double> xf_stage; std::vector<double> xf_radius;
+    Stopwatch xf_watch;
+    uint32_t xf_n_groups = 0, xf_updates = 0;
     // Temporal reprojection (reproject.hip), allocated by the first reprojection call: the old view's features (2 per pixel, swapped
     // with dn_feat per call), a copy of the old film and the reuse counter.
     // Motion-vector reprojection adds, on the first mcpt_update_vertices_reproject: the first hit of every pixel-centre ray and
@@ -441,6 +449,15 @@ static mcpt_status rf_setup(mcpt_ctx* c, const HostScene& hs, const mcpt_scene_d
     HIP_TRY(s.put(c->rf_vtx.p, scene->vertex, c->rf_vtx.count())); HIP_TRY(s.put(c->rf_nrm.p, scene->normal, c->rf_nrm.count()));
     return rf_wide_area(c, c->rf_area0);                                  // (synchronises: the caller's arrays have been read)
 }
+// The buffers of §16 for n_groups groups, all or none: a context that had groups keeps them when an allocation fails.
+static mcpt_status xf_alloc(mcpt_ctx* c, uint32_t n_groups) {
+    uint64_t* tally = &c->info.device_bytes;
+    const size_t nt = size_t(n_groups) * XF_RECORD;
+    HIP_TRY(alloc_all(Want(c->xf_rest_vtx, c->rf_vtx.count(), tally), Want(c->xf_rest_nrm, c->rf_nrm.count(), tally), Want(c->xf_vgroup, c->rf_n_vertex, tally),
+                      Want(c->xf_ngroup, c->rf_n_normal, tally), Want(c->xf_table, nt, tally), Want(c->xf_stage, nt), Want(c->xf_watch, 1, nullptr, !c->xf_watch.ev0)));
+    c->xf_n_groups = n_groups; c->xf_radius.assign(n_groups, 0.0);
+    return MCPT_OK;
+}
 static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     c->rf_n_vertex = src->rf_n_vertex; c->rf_n_normal = src->rf_n_normal; c->rf_used_vertex = src->rf_used_vertex;
     c->rf_bin_level = src->rf_bin_level; c->rf_wide_level = src->rf_wide_level; c->rf_area0 = src->rf_area0;
@@ -449,6 +466,13 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     HIP_TRY(hipMemcpyPeer(c->rf_bin_order.p, c->device, src->rf_bin_order.p, src->device, c->rf_bin_order.bytes));
     if (c->rf_vtx.bytes) HIP_TRY(hipMemcpyPeer(c->rf_vtx.p, c->device, src->rf_vtx.p, src->device, c->rf_vtx.bytes));
     if (c->rf_nrm.bytes) HIP_TRY(hipMemcpyPeer(c->rf_nrm.p, c->device, src->rf_nrm.p, src->device, c->rf_nrm.bytes));
+    if (src->xf_n_groups) {                                                // the groups, the rest pose and R_g travel with the clone (§16)
+        mcpt_status xs = xf_alloc(c, src->xf_n_groups); if (xs != MCPT_OK) return xs;
+        c->xf_radius = src->xf_radius;
+        auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
+        HIP_TRY(copy(c->xf_rest_vtx, src->xf_rest_vtx)); HIP_TRY(copy(c->xf_rest_nrm, src->xf_rest_nrm));
+        HIP_TRY(copy(c->xf_vgroup, src->xf_vgroup)); HIP_TRY(copy(c->xf_ngroup, src->xf_ngroup));
+    }
     HIP_TRY(hipDeviceSynchronize());
     return MCPT_OK;
 }
@@ -1258,19 +1282,59 @@ static mcpt_status rf_check_update(const mcpt_ctx* ctx, const double* vertex, ui
     }
     return MCPT_OK;
 }
-// The update itself, for arrays rf_check_update has passed: staged, copied and refitted on the context's stream.
-static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const double* vertex, const double* normal) {
-    HIP_TRY(ctx->rf_stage.wait());
+// mcpt_update_transforms' rules for its matrices (§16), host only: no device round trip, hence the conservative row bound against R_g.
+static mcpt_status xf_check_update(const mcpt_ctx* ctx, const double* m3x4, uint32_t n_groups, const char* fn) {
+    const std::string who = std::string(fn) + ": ";
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if (!ctx->xf_n_groups) return fail(MCPT_ERR_INVALID_ARG, who + "no groups are set (mcpt_set_vertex_groups)");
+    if (!m3x4) return fail(MCPT_ERR_INVALID_ARG, who + "null matrices");
+    if (n_groups != ctx->xf_n_groups) return fail(MCPT_ERR_INVALID_ARG, who + "n_groups differs from the groups set");
+    for (size_t k = 0; k < size_t(n_groups) * 12; k++)
+        if (!std::isfinite(m3x4[k])) return fail(MCPT_ERR_INVALID_ARG, who + "group " + std::to_string(k / 12) + ": a matrix entry is not finite");
+    for (uint32_t g = 0; g < n_groups; g++) {
+        double rec[XF_RECORD];
+        xf_group_record(m3x4 + 12 * size_t(g), rec);
+        const double det = xf_record_det(rec);
+        if (!(std::isfinite(det) && det != 0.0)) return fail(MCPT_ERR_INVALID_ARG, who + "group " + std::to_string(g) + ": det A is zero or not finite");
+    }
+    for (uint32_t g = 0; g < n_groups; g++)
+        for (int r = 0; r < 3; r++) {
+            const double reach = xf_row_reach(m3x4 + 12 * size_t(g) + 4 * r, ctx->xf_radius[g]);
+            if (!(reach <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "group " + std::to_string(g) + ": a vertex could leave |coordinate| <= 1e18 (conservative bound)");
+        }
+    return MCPT_OK;
+}
+// A scene update that has been checked: the caller's arrays (rf_check_update), or one matrix per group (xf_check_update).
+struct RfUpdate { const double* vertex; const double* normal; const double* m3x4; };
+// The update itself: the new vertices and normals reach rf_vtx / rf_nrm -- arrays staged and copied, or the staged table of matrices applied to the
+// rest pose on the device -- and both trees are refitted, all on the context's stream.
+static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     const size_t vd = ctx->rf_vtx.count(), nd = ctx->rf_nrm.count();
-    std::memcpy(ctx->rf_stage.host, vertex, vd * sizeof(double));
-    if (normal) std::memcpy(ctx->rf_stage.host + vd, normal, nd * sizeof(double));
+    const bool normal = u.m3x4 ? nd != 0 : u.normal != nullptr;                  // are there new normals
+    if (u.m3x4) {
+        HIP_TRY(ctx->xf_stage.wait());
+        for (uint32_t g = 0; g < ctx->xf_n_groups; g++) xf_group_record(u.m3x4 + 12 * size_t(g), ctx->xf_stage.host + XF_RECORD * size_t(g));
+    } else {
+        HIP_TRY(ctx->rf_stage.wait());
+        std::memcpy(ctx->rf_stage.host, u.vertex, vd * sizeof(double));
+        if (normal) std::memcpy(ctx->rf_stage.host + vd, u.normal, nd * sizeof(double));
+    }
     // Everything below is stream work on the context's stream: it starts after every render enqueued so far has finished (the sub-pipelines'
     // streams joined it at the end of their call, known-length jobs included) and the next render's sub-pipelines fork from it after the last
     // kernel here.
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx->rf_watch.begin(s));
-    HIP_TRY(ctx->rf_stage.send(ctx->rf_vtx.p, 0, vd, s, !normal));
-    if (normal) HIP_TRY(ctx->rf_stage.send(ctx->rf_nrm.p, vd, nd, s));
+    if (u.m3x4) {
+        HIP_TRY(ctx->xf_watch.begin(s));
+        HIP_TRY(ctx->xf_stage.send(ctx->xf_table.p, 0, ctx->xf_table.count(), s));
+        HIP_TRY(launch_xf_vertices(ctx->xf_rest_vtx.p, ctx->xf_vgroup.p, ctx->xf_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
+        HIP_TRY(launch_xf_normals(ctx->xf_rest_nrm.p, ctx->xf_ngroup.p, ctx->xf_table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+        HIP_TRY(ctx->xf_watch.end(s));
+        ctx->xf_updates++;
+    } else {
+        HIP_TRY(ctx->rf_stage.send(ctx->rf_vtx.p, 0, vd, s, !normal));
+        if (normal) HIP_TRY(ctx->rf_stage.send(ctx->rf_nrm.p, vd, nd, s));
+    }
     const double* d_nrm = normal ? ctx->rf_nrm.p : nullptr;
     const DevScene& d = ctx->dev;
     HIP_TRY(launch_rf_triangles(ctx->rf_vtx.p, d_nrm, ctx->rf_idx.p, RfCentre{d.centre[0], d.centre[1], d.centre[2]}, ctx->tri_isect.p, ctx->tri_shade.p,
@@ -1290,7 +1354,51 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const double* vertex, const 
 mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     st = rf_check_update(ctx, vertex, n_vertex, normal, n_normal, "mcpt_update_vertices"); if (st != MCPT_OK) return st;
-    return rf_enqueue_update(ctx, vertex, normal);
+    return rf_enqueue_update(ctx, RfUpdate{vertex, normal, nullptr});
+}
+
+// ------------------------------------------------------------------------------------------------ rigid parts
+mcpt_status mcpt_set_vertex_groups(mcpt_ctx* ctx, const uint32_t* vertex_group, uint32_t n_vertex, const uint32_t* normal_group, uint32_t n_normal, uint32_t n_groups) {
+    const std::string who = "mcpt_set_vertex_groups: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if (n_vertex != ctx->rf_n_vertex || n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_vertex / n_normal differ from the scene's");
+    if (!vertex_group || (n_normal && !normal_group)) return fail(MCPT_ERR_INVALID_ARG, who + "null group array");
+    if (n_groups < 1 || uint64_t(n_groups) > uint64_t(n_vertex) + n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_groups must be in [1, n_vertex + n_normal]");
+    for (uint32_t v = 0; v < n_vertex; v++) if (vertex_group[v] >= n_groups) return fail(MCPT_ERR_INVALID_ARG, who + "vertex " + std::to_string(v) + ": group id >= n_groups");
+    for (uint32_t v = 0; v < n_normal; v++) if (normal_group[v] >= n_groups) return fail(MCPT_ERR_INVALID_ARG, who + "normal " + std::to_string(v) + ": group id >= n_groups");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // rf_vtx / rf_nrm are final, and no copy out of the old stage is under way
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    st = xf_alloc(ctx, n_groups); if (st != MCPT_OK) return st;
+    std::vector<double> vtx(ctx->rf_vtx.count());
+    {   Scratch s(ctx->stream);
+        if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->xf_rest_vtx.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->xf_rest_nrm.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(s.put(ctx->xf_vgroup.p, vertex_group, n_vertex)); HIP_TRY(s.put(ctx->xf_ngroup.p, normal_group, n_normal));
+        HIP_TRY(s.fetch(vtx.data(), ctx->rf_vtx.p, vtx.size())); HIP_TRY(s.finish()); }
+    for (uint32_t v = 0; v < n_vertex; v++) {
+        if (!ctx->rf_used_vertex[v]) continue;
+        double& r = ctx->xf_radius[vertex_group[v]];
+        for (int a = 0; a < 3; a++) r = std::max(r, std::fabs(vtx[3 * size_t(v) + a]));
+    }
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_update_transforms(mcpt_ctx* ctx, const double* m3x4, uint32_t n_groups) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    st = xf_check_update(ctx, m3x4, n_groups, "mcpt_update_transforms"); if (st != MCPT_OK) return st;
+    return rf_enqueue_update(ctx, RfUpdate{nullptr, nullptr, m3x4});
+}
+
+mcpt_status mcpt_get_transform_info(mcpt_ctx* ctx, mcpt_transform_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    HIP_TRY(ctx->xf_watch.settle());
+    std::memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out; out->n_groups = ctx->xf_n_groups; out->updates = ctx->xf_updates; out->last_ms = ctx->xf_watch.last_ms;
+    return MCPT_OK;
 }
 
 mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
@@ -1490,8 +1598,6 @@ static mcpt_status rp_ensure(mcpt_ctx* ctx, bool motion) {
     return MCPT_OK;
 }
 
-// A vertex update for rf_enqueue_update, checked by rf_check_update.
-struct RfUpdate { const double* vertex; const double* normal; };
 // The frame of a reprojection entry point whose own arguments have been checked: the film is carried from the scene and view as they are to the
 // scene after `update` (null: unchanged, §13) seen from `cm` (null: the same camera).  `fn` names the entry point in the message.
 static mcpt_status rp_frame(mcpt_ctx* ctx, const RfUpdate* update, const mcpt_camera* cm, const mcpt_reproject_opts* opts, const char* fn) {
@@ -1510,7 +1616,7 @@ static mcpt_status rp_frame(mcpt_ctx* ctx, const RfUpdate* update, const mcpt_ca
     if (update && ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->rp_vtx_old.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, s));
     if (update && ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->rp_nrm_old.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, s));
     const DevCamera old_cam = ctx->dev.cam;
-    if (update) { st = rf_enqueue_update(ctx, update->vertex, update->normal); if (st != MCPT_OK) return st; }
+    if (update) { st = rf_enqueue_update(ctx, *update); if (st != MCPT_OK) return st; }
     if (cm) apply_camera(ctx, *cm);
     HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, ctx->dn_feat.p, s));
     ctx->dn_have_features = true;                                          // those of the new scene and view: mcpt_denoise may follow at once
@@ -1579,7 +1685,16 @@ mcpt_status mcpt_update_vertices_reproject(mcpt_ctx* ctx, const double* vertex, 
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     st = rf_check_update(ctx, vertex, n_vertex, normal, n_normal, fn); if (st != MCPT_OK) return st;
     if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
-    const RfUpdate update{vertex, normal};
+    const RfUpdate update{vertex, normal, nullptr};
+    return rp_frame(ctx, &update, cm, opts, fn);
+}
+
+mcpt_status mcpt_update_transforms_reproject(mcpt_ctx* ctx, const double* m3x4, uint32_t n_groups, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
+    const char* const fn = "mcpt_update_transforms_reproject";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    st = xf_check_update(ctx, m3x4, n_groups, fn); if (st != MCPT_OK) return st;
+    if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
+    const RfUpdate update{nullptr, nullptr, m3x4};                               // §16: the matrices in place of the arrays, the same frame
     return rp_frame(ctx, &update, cm, opts, fn);
 }
 

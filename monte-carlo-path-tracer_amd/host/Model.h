@@ -52,6 +52,10 @@ public:
     CameraInfo camerainfo;
     explicit Model(const std::string& filename, bool reference_index_order = false);
     bool ok = false;                                  // the reference only prints to cerr on failure; this also records it
+    int material_index(const std::string& name) const {   // the index `usemtl name` gives a face, -1 for a name no .mtl defines
+        const auto it = material_map.find(name);
+        return it == material_map.end() ? -1 : it->second;
+    }
 private:
     std::map<std::string, int> material_map;
     void load_material(const std::string& filename);

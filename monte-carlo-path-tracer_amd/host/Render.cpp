@@ -132,18 +132,27 @@ bool Render::film_to_device(Scene& scene, const char* who, bool& ok) {
     ok = true;
     return upload;
 }
-bool Render::update_reproject(Scene& scene, Model& m, float max_history) { return update_reproject(scene, m, nullptr, max_history); }
-bool Render::update_reproject(Scene& scene, Model& m, const CameraInfo& camera, float max_history) { return update_reproject(scene, m, &camera, max_history); }
-bool Render::update_reproject(Scene& scene, Model& m, const CameraInfo* camera, float max_history) {
+bool Render::update_reproject(Scene& scene, Model& m, float max_history) { return update_reproject(scene, &m, nullptr, nullptr, max_history); }
+bool Render::update_reproject(Scene& scene, Model& m, const CameraInfo& camera, float max_history) { return update_reproject(scene, &m, nullptr, &camera, max_history); }
+bool Render::update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, float max_history) { return update_reproject(scene, nullptr, &matrices, nullptr, max_history); }
+bool Render::update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history) {
+    return update_reproject(scene, nullptr, &matrices, &camera, max_history);
+}
+// The geometry comes from `m` (its arrays) or from `matrices` (one 3x4 per group, §16): the rest is the same.
+bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>* matrices, const CameraInfo* camera, float max_history) {
     if (!ctx) return false;
+    const char* const who = m ? "update_reproject" : "update_transforms_reproject";
+    if (!m && matrices->size() % 12) { std::cerr << "Error: Render::" << who << ": need 12 doubles per group" << std::endl; return false; }
     bool ok = false;
-    const bool upload = film_to_device(scene, "update_reproject", ok);
+    const bool upload = film_to_device(scene, who, ok);
     if (!ok) return false;
     mcpt_camera k; if (camera) k = to_camera(*camera);
     mcpt_reproject_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.feature_spp = 4; o.feature_seed = seed; o.max_history = max_history;
-    if (mcpt_update_vertices_reproject(ctx, reinterpret_cast<const double*>(m.vertex.data()), uint32_t(m.vertex.size()), reinterpret_cast<const double*>(m.normal.data()),
-                                       uint32_t(m.normal.size()), camera ? &k : nullptr, &o) != MCPT_OK) {
-        std::cerr << "Error: mcpt_update_vertices_reproject: " << mcpt_last_error() << std::endl;
+    const mcpt_status st = m ? mcpt_update_vertices_reproject(ctx, reinterpret_cast<const double*>(m->vertex.data()), uint32_t(m->vertex.size()),
+                                                              reinterpret_cast<const double*>(m->normal.data()), uint32_t(m->normal.size()), camera ? &k : nullptr, &o)
+                             : mcpt_update_transforms_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o);
+    if (st != MCPT_OK) {
+        std::cerr << "Error: mcpt_" << (m ? "update_vertices_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
         if (upload && mcpt_clear_accum(ctx) != MCPT_OK) std::cerr << "Error: mcpt_clear_accum: " << mcpt_last_error() << std::endl;   // the Scene still holds them
         return false;
     }
@@ -158,6 +167,41 @@ bool Render::update(Scene& scene, Model& m) {
     if (mcpt_update_vertices(ctx, reinterpret_cast<const double*>(m.vertex.data()), uint32_t(m.vertex.size()), reinterpret_cast<const double*>(m.normal.data()),
                              uint32_t(m.normal.size())) != MCPT_OK) { std::cerr << "Error: mcpt_update_vertices: " << mcpt_last_error() << std::endl; return false; }
     if (mcpt_set_camera(ctx, &k) != MCPT_OK) { std::cerr << "Error: mcpt_set_camera: " << mcpt_last_error() << std::endl; return false; }
+    return restart(scene);
+}
+// One group per vertex and per normal from one per face: whatever a face of group g uses belongs to g; what no face uses, to group 0.
+static bool groups_of(const std::vector<imat3x4>& face, const std::vector<uint32_t>& face_group, int column, size_t n, const char* what, std::vector<uint32_t>& out) {
+    const uint32_t none = ~0u;
+    out.assign(n, none);
+    for (size_t f = 0; f < face.size(); f++)
+        for (int c = 0; c < 3; c++) {
+            const int i = face[f][c][column];
+            if (i < 0 || size_t(i) >= n) { std::cerr << "Error: Render::set_groups: face " << f << " names a " << what << " out of range" << std::endl; return false; }
+            if (out[size_t(i)] != none && out[size_t(i)] != face_group[f]) {
+                std::cerr << "Error: Render::set_groups: " << what << " " << i << " is used by faces of groups " << out[size_t(i)] << " and " << face_group[f]
+                          << " (duplicate it in the file)" << std::endl;
+                return false;
+            }
+            out[size_t(i)] = face_group[f];
+        }
+    for (uint32_t& g : out) if (g == none) g = 0;
+    return true;
+}
+bool Render::set_groups(Scene&, Model& m, const std::vector<uint32_t>& face_group) {
+    if (!ctx) return false;
+    if (face_group.size() != m.face.size() || face_group.empty()) { std::cerr << "Error: Render::set_groups: need one group per face" << std::endl; return false; }
+    std::vector<uint32_t> vg, ng;
+    if (!groups_of(m.face, face_group, 0, m.vertex.size(), "vertex", vg) || !groups_of(m.face, face_group, 1, m.normal.size(), "normal", ng)) return false;
+    const uint32_t n_groups = *std::max_element(face_group.begin(), face_group.end()) + 1;
+    if (mcpt_set_vertex_groups(ctx, vg.data(), uint32_t(vg.size()), ng.data(), uint32_t(ng.size()), n_groups) != MCPT_OK) {
+        std::cerr << "Error: mcpt_set_vertex_groups: " << mcpt_last_error() << std::endl; return false;
+    }
+    return true;
+}
+bool Render::update_transforms(Scene& scene, const std::vector<double>& matrices) {
+    if (!ctx) return false;
+    if (matrices.size() % 12) { std::cerr << "Error: Render::update_transforms: need 12 doubles per group" << std::endl; return false; }
+    if (mcpt_update_transforms(ctx, matrices.data(), uint32_t(matrices.size() / 12)) != MCPT_OK) { std::cerr << "Error: mcpt_update_transforms: " << mcpt_last_error() << std::endl; return false; }
     return restart(scene);
 }
 bool Render::update_materials(Scene& scene, Model& m) {

@@ -52,6 +52,15 @@ public:
     // and reflections along until max_history new samples have diluted them.  false on failure (Render and the Scene's samples unchanged).
     bool update_reproject(Scene& scene, Model& m_model, float max_history = 0);
     bool update_reproject(Scene& scene, Model& m_model, const CameraInfo& camera, float max_history = 0);
+    // Rigid parts.  set_groups: one group id per face of `m_model`, the Model this Render was made from (MCPT_FLAG_DYNAMIC); the
+    // scene as it is now becomes the rest pose; false when faces of two groups share a vertex or a normal.  The film is not touched.
+    // update_transforms: one row-major 3x4 matrix [A | t] per group (12 doubles each), applied to the rest pose on the device
+    // (mcpt_update_transforms) -- only the matrices cross the bus, Model::vertex is neither read nor written.  Starts the picture again like
+    // update(); update_transforms_reproject carries it over like update_reproject.  false (Render and Scene unchanged) on failure.
+    bool set_groups(Scene& scene, Model& m_model, const std::vector<uint32_t>& face_group);
+    bool update_transforms(Scene& scene, const std::vector<double>& matrices);
+    bool update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, float max_history = 0);
+    bool update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history = 0);
     Render(const Render&) = delete;
     Render& operator=(const Render&) = delete;
     bool ok() const { return ctx != nullptr; }
@@ -69,7 +78,7 @@ private:
     void create(Model& m, const mcpt_opts& opts);
     bool restart(Scene& scene);
     bool film_to_device(Scene& scene, const char* who, bool& ok);
-    bool update_reproject(Scene& scene, Model& m_model, const CameraInfo* camera, float max_history);
+    bool update_reproject(Scene& scene, Model* m_model, const std::vector<double>* matrices, const CameraInfo* camera, float max_history);
 };
 // Fills an mcpt_scene_desc that points INTO `m` (and into the two scratch vectors); valid while all three live.
 void model_to_desc(Model& m, std::vector<mcpt_material>& mats, std::vector<mcpt_texture>& texs, mcpt_scene_desc& d);

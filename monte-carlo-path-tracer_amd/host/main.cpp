@@ -32,6 +32,9 @@ static void usage() {
                  "                                        A sin(2 pi frame / N) (sin 9y, sin 7z, sin 8x) (device-side refit; with --reproject the film follows the surfaces)\n"
                  "                          [--light-pulse A]   with --turntable: frame k scales the radiance of every emissive material by 1 + A sin(2 pi k / N)\n"
                  "                                        (materials and light list edited on the device, the film restarts every frame; not with --reproject)\n"
+                 "                          [--spin MTLNAME]   with --turntable: the faces of that material turn as one rigid part, by 360 k / N degrees in frame k about\n"
+                 "                                        the camera's up axis through their bounding box's centre (one 3x4 matrix per frame, applied on the device;\n"
+                 "                                        honours --reproject; not with --wobble)\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -61,6 +64,7 @@ int main(int argc, char** argv) {
     bool reproject = false; float history = 0.f;
     bool wobble = false; double wobble_a = 0.0;
     bool pulse = false; double pulse_a = 0.0;
+    std::string spin;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -81,6 +85,7 @@ int main(int argc, char** argv) {
         else if (a == "--reproject") { reproject = true; history = float(std::atof(next())); }
         else if (a == "--wobble") { wobble = true; wobble_a = std::atof(next()); }
         else if (a == "--light-pulse") { pulse = true; pulse_a = std::atof(next()); }
+        else if (a == "--spin") spin = next();
         else { usage(); return 2; }
     }
     if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
@@ -89,7 +94,8 @@ int main(int argc, char** argv) {
     if (wobble && (!turntable || !(std::fabs(wobble_a) <= 1e6))) { std::cerr << "Error: --wobble A needs --turntable N and a finite A" << std::endl; return 2; }
     if (pulse && (!turntable || !(std::fabs(pulse_a) <= 1e6))) { std::cerr << "Error: --light-pulse A needs --turntable N and a finite A" << std::endl; return 2; }
     if (pulse && reproject) { std::cerr << "Error: --light-pulse restarts the film every frame: radiance reprojected across it would be the old light's (drop --reproject)" << std::endl; return 2; }
-    if (wobble) flags |= MCPT_FLAG_DYNAMIC;
+    if (!spin.empty() && (!turntable || wobble)) { std::cerr << "Error: --spin MTLNAME needs --turntable N and no --wobble (both write the vertices)" << std::endl; return 2; }
+    if (wobble || !spin.empty()) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
     std::cout << model.face.size() << " " << model.normal.size() << " " << model.vertex.size() << std::endl;   // main.cpp:14
@@ -154,6 +160,28 @@ int main(int argc, char** argv) {
         const double ul = std::sqrt(base.up.x * base.up.x + base.up.y * base.up.y + base.up.z * base.up.z);
         if (!(ul > 0.0)) { std::cerr << "Error: --turntable needs a camera with an up vector" << std::endl; return 1; }
         const double k[3] = {base.up.x / ul, base.up.y / ul, base.up.z / ul}, v[3] = {base.eye.x - base.lookat.x, base.eye.y - base.lookat.y, base.eye.z - base.lookat.z};
+        // --spin MTLNAME: that material's faces are group 1, everything else group 0
+        double pivot[3] = {0.0, 0.0, 0.0};
+        if (!spin.empty()) {
+            const int mtl = model.material_index(spin);
+            if (mtl < 0) { std::cerr << "Error: --spin: no material named " << spin << std::endl; return 1; }
+            std::vector<uint32_t> face_group(model.face.size(), 0u);
+            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+            size_t n_spin = 0;
+            for (size_t i = 0; i < model.face.size(); i++) {
+                if (model.face[i][0][3] != mtl) continue;
+                face_group[i] = 1u; n_spin++;
+                for (int c = 0; c < 3; c++) {
+                    const int vi = model.face[i][c][0];
+                    if (vi < 0 || size_t(vi) >= model.vertex.size()) continue;   // (mcpt_create has refused such a face already)
+                    const dvec3& p = model.vertex[size_t(vi)]; const double q[3] = {p.x, p.y, p.z};
+                    for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], q[a]); hi[a] = std::max(hi[a], q[a]); }
+                }
+            }
+            if (!n_spin) { std::cerr << "Error: --spin: no face uses material " << spin << std::endl; return 1; }
+            for (int a = 0; a < 3; a++) pivot[a] = 0.5 * (lo[a] + hi[a]);
+            if (!renders[0]->set_groups(scene, model, face_group)) return 1;
+        }
         for (uint32_t f = 0; f < turntable; f++) {
             const double a = 2.0 * 3.14159265358979323846 * double(f) / double(turntable), ca = std::cos(a), sa = std::sin(a);
             const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2], kx[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
@@ -179,6 +207,18 @@ int main(int argc, char** argv) {
                 }
                 model.camerainfo = cam;
                 if (reproject ? !renders[0]->update_reproject(scene, model, cam, history) : !renders[0]->update(scene, model)) return 1;
+            } else if (!spin.empty()) {                                      // Rodrigues as a matrix: R = cos a I + sin a [k]x + (1 - cos a) k k^T, about the pivot
+                const double R[3][3] = {{ca + k[0] * k[0] * (1.0 - ca), k[0] * k[1] * (1.0 - ca) - k[2] * sa, k[0] * k[2] * (1.0 - ca) + k[1] * sa},
+                                        {k[1] * k[0] * (1.0 - ca) + k[2] * sa, ca + k[1] * k[1] * (1.0 - ca), k[1] * k[2] * (1.0 - ca) - k[0] * sa},
+                                        {k[2] * k[0] * (1.0 - ca) - k[1] * sa, k[2] * k[1] * (1.0 - ca) + k[0] * sa, ca + k[2] * k[2] * (1.0 - ca)}};
+                std::vector<double> m(24, 0.0);
+                m[0] = m[5] = m[10] = 1.0;                                   // group 0 stays
+                for (int r = 0; r < 3; r++) {
+                    for (int c = 0; c < 3; c++) m[12 + 4 * r + c] = R[r][c];
+                    m[12 + 4 * r + 3] = pivot[r] - (R[r][0] * pivot[0] + R[r][1] * pivot[1] + R[r][2] * pivot[2]);
+                }
+                if (reproject && f > 0 ? !renders[0]->update_transforms_reproject(scene, m, cam, history)
+                                       : !(renders[0]->update_transforms(scene, m) && renders[0]->set_camera(scene, cam))) return 1;
             } else
             if (reproject && f > 0 ? !renders[0]->set_camera_reproject(scene, cam, history) : !renders[0]->set_camera(scene, cam)) return 1;
             renders[0]->render(scene, spp);
