@@ -1,0 +1,163 @@
+"""The one copy of what the per-feature suites share: the bitwise view behind every "bit for bit" assertion, live-scene scaffolding (films, rays,
+the moved sphere), the reprojection suites' synthetic inputs and comparison, and the drivers of the C++ façade programs and mcpt_cli.
+
+A plain module, imported like tests/reproject_ref.py.  Where the suites' copies differed in a default or in the order of their arguments the
+function here takes the argument explicitly and every call site passes the value it always used.
+"""
+from __future__ import annotations
+
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc")
+HOST = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "host")
+CLI = os.path.join(CSRC, "mcpt_cli")
+F32 = np.float32
+
+
+# ------------------------------------------------------------------------------------------------------------------------ comparisons
+def bits(a):
+    """`a` as the unsigned integers of its bit patterns (fp32 -> u32, fp64 -> u64; anything else as it is): equal exactly when the arrays are
+    the same bit for bit, so 0.0 differs from -0.0 and a NaN equals only the NaN of its own payload."""
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
+
+
+def compare_with_ref(got, reused, want, marg, rtol=1e-3, atol=1e-6):
+    """A reprojected film and the kernel's count of reused pixels against the numpy restatement: off the restatement's marginal pixels the
+    sample counts are equal and every colour sum is within rtol |want| + atol; the counts of reused pixels differ by at most the number of
+    marginal pixels."""
+    ok = ~marg
+    assert np.array_equal(got[ok][:, 3], want[ok][:, 3])
+    g, w = got[ok][:, :3].astype(np.float64), want[ok][:, :3].astype(np.float64)
+    assert np.all(np.abs(g - w) <= rtol * np.abs(w) + atol), float(np.max(np.abs(g - w) / np.maximum(np.abs(w), 1e-3)))
+    assert abs(int(reused) - int((want[..., 3] > 0).sum())) <= int(marg.sum())
+
+
+def assert_exports(pkg, symbols, renderer_methods=()):
+    """The library exports `symbols`, the ctypes plumbing binds them, the ABI is version 4 and Renderer has `renderer_methods`."""
+    lib = pkg.load_library()
+    assert [s for s in symbols if not hasattr(lib, s)] == []
+    assert set(symbols) <= set(pkg.EXPORTED_SYMBOLS)
+    assert lib.mcpt_abi_version() == 4
+    for name in renderer_methods:
+        assert callable(getattr(pkg.Renderer, name))
+
+
+# ------------------------------------------------------------------------------------------------------------------------ live scenes
+def render_film(r, spp, seed):
+    """The film of `spp` samples from an empty one."""
+    r.clear(); r.render(spp, seed=seed)
+    return r.read_accum()
+
+
+def with_arrays(pkg, scene, vertex=None, normal=None, camera=None):
+    return pkg.scenes.SceneData(scene.name, scene.vertex if vertex is None else vertex, scene.normal if normal is None else normal, scene.texcoord,
+                                scene.face, scene.materials, scene.camera if camera is None else camera, dict(scene.meta))
+
+
+def moved_sphere(pkg, scene, shift=(0.12, 0.25, -0.1), squash=0.6):
+    """S-cornell with its sphere (material 4) translated and squashed along y inside the room, walls and light fixed: the bounding box -- and
+    with it the centre every device coordinate is relative to -- stays.  Normals recomputed (inverse transpose of the squash)."""
+    sphere = scene.face[:, 0, 3] == 4
+    vi = np.unique(scene.face[sphere][:, :, 0]); ni = np.unique(scene.face[sphere][:, :, 1])
+    c = np.array([0.5, 0.3, 0.5]); s = np.array([1.0, squash, 1.0])
+    v = scene.vertex.copy(); n = scene.normal.copy()
+    v[vi] = (v[vi] - c) * s + c + np.asarray(shift)
+    n[ni] = n[ni] / s; n[ni] /= np.linalg.norm(n[ni], axis=1, keepdims=True)
+    assert v[vi].min() > 0.0 and v[vi].max() < 0.999
+    return with_arrays(pkg, scene, v, n)
+
+
+def used_bounds(scene):
+    """(lo, hi) of the vertices a face uses."""
+    used = scene.vertex[np.unique(scene.face[:, :, 0])]
+    return used.min(0), used.max(0)
+
+
+def camera_rays(r, w, h, seed):
+    """One ray per pixel of a w x h film through a random point of the pixel: (xy, xi, rays as fp64 (n, 6): origin, direction)."""
+    ys, xs = np.mgrid[0:h, 0:w]
+    xy = np.stack([xs.ravel(), ys.ravel()], -1).astype(np.int32)
+    xi = np.random.default_rng(seed).uniform(0, 1, (xy.shape[0], 2)).astype(np.float32)
+    return xy, xi, r.probe_cast_ray(xy, xi).astype(np.float64)
+
+
+def box_rays(lo, hi, n, seed):
+    """`n` rays between random points of the box [lo, hi]: (origins, unit directions)."""
+    rng = np.random.default_rng(seed)
+    o = rng.uniform(lo, hi, (n, 3)); t = rng.uniform(lo, hi, (n, 3))
+    d = t - o; d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return o, d
+
+
+def light_points(lo, hi, n, seed):
+    """`n` shading points in the box [lo, hi] and the random numbers to sample a light with: (points, xi)."""
+    rng = np.random.default_rng(seed)
+    return rng.uniform(lo, hi, (n, 3)), rng.uniform(0, 1, (n, 3)).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------------------ reprojection
+class Cam:
+    """What the reprojection restatements and Renderer read of a camera (scenes.Camera's fields)."""
+
+    def __init__(self, eye, lookat, up, fovy, width, height):
+        self.eye, self.lookat, self.up, self.fovy, self.width, self.height = tuple(eye), tuple(lookat), tuple(up), float(fovy), int(width), int(height)
+
+
+# translation + rotation between two orthonormal cameras
+CAM_A = dict(eye=(0.1, 0.2, 4.0), lookat=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fovy=40.0)
+CAM_B = dict(eye=(0.37, 0.11, 3.8), lookat=(0.1, 0.05, 0.0), up=(0.0, 1.0, 0.0), fovy=40.0)
+SIZES = [(37, 23), (1, 1), (130, 9)]                        # the last crosses the 64-wide and the 4-high block edges
+OPTS = {"default": {}, "other": dict(max_history=10.0, depth_tolerance=0.2, normal_threshold=0.8)}
+CORNELL_SIZE = 64                                           # film width and height of the scene tests
+SEED_F = 5                                                  # feature seed of the scene tests
+
+
+def synthetic_film(h, w, seed, zero_share=0.1, max_count=40, nan=0):
+    """A film of random means and sample counts 1 .. max_count, a share of the pixels never sampled and `nan` channels not a number."""
+    rng = np.random.default_rng(seed)
+    cnt = rng.integers(1, max_count + 1, (h, w)).astype(F32)
+    cnt[rng.uniform(size=(h, w)) < zero_share] = 0
+    film = np.zeros((h, w, 4), F32)
+    film[..., :3] = rng.uniform(0.1, 2.0, (h, w, 3)).astype(F32) * cnt[..., None]; film[..., 3] = cnt
+    for _ in range(nan):
+        film[rng.integers(h), rng.integers(w), rng.integers(3)] = np.nan
+    return film
+
+
+def cornell(pkg, dynamic, scene=None):
+    """(scene, deterministic depth-8 context) of S-cornell-small at CORNELL_SIZE, or of `scene`."""
+    scene = scene or pkg.scenes.cornell_box_small(CORNELL_SIZE, CORNELL_SIZE)
+    return scene, pkg.Renderer(scene, max_depth=8, flags=pkg.FLAG_DETERMINISTIC | (pkg.FLAG_DYNAMIC if dynamic else 0))
+
+
+# ------------------------------------------------------------------------------------------------------------------------ programs
+def build_facade(source_name, tmp_path, extra_flags=()):
+    """Compile tests/<source_name> against the C++ host classes (libmcpt_host.a) and the library; returns the executable."""
+    exe = str(tmp_path / os.path.splitext(source_name)[0])
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + HOST, os.path.join(ROOT, "tests", source_name), os.path.join(CSRC, "libmcpt_host.a"),
+                           "-o", exe, "-L" + CSRC, "-lmcpt_hip", "-lz", "-lpthread", "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"] + list(extra_flags))
+    return exe
+
+
+def run_facade(exe, args):
+    """Run a façade program; the words of its last line (the loader prints "[Model] <path>" lines first)."""
+    return subprocess.check_output([exe] + list(args), timeout=300).decode().split("\n")[-2].split()
+
+
+def run_cli(args):
+    return subprocess.run([CLI] + list(args), capture_output=True, text=True, timeout=300)
+
+
+def turntable_frames(prefix, n=3):
+    """The bytes of <prefix>_turn0.png .. _turn<n-1>.png, each checked for the PNG signature."""
+    out = []
+    for f in range(n):
+        with open("%s_turn%d.png" % (prefix, f), "rb") as fh:
+            out.append(fh.read())
+        assert out[-1][:8] == b"\x89PNG\r\n\x1a\n"
+    return out

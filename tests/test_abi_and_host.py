@@ -1,5 +1,6 @@
 """CPU tests of the drop-in boundary and the host-side logic of libmcpt_hip.so (no compute call needs a GPU here)."""
 import ctypes as C
+import functools
 import os
 import re
 import shutil
@@ -9,7 +10,8 @@ import tempfile
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.kit import CLI, CSRC, ROOT
+
 HEADER = os.path.join(ROOT, "include", "mcpt.h")
 
 
@@ -29,25 +31,56 @@ def test_library_exports_every_declared_symbol(pkg):
     assert lib.mcpt_abi_version() == 4
 
 
-def test_ctypes_structs_match_the_header_layout(pkg):
-    """Compile a 20-line C program against include/mcpt.h and compare sizeof/offsetof with the ctypes mirrors."""
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "mcpt.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(mcpt_texture), sizeof(mcpt_material), sizeof(mcpt_camera), sizeof(mcpt_scene_desc),
-         sizeof(mcpt_opts), sizeof(mcpt_counters), sizeof(mcpt_scene_info), offsetof(mcpt_scene_desc, camera));
-  return 0; }
-'''
+# every ctypes.Structure of the package and the struct of include/mcpt.h it mirrors
+STRUCTS = {
+    "Texture": "mcpt_texture", "MaterialC": "mcpt_material", "CameraC": "mcpt_camera", "SceneDesc": "mcpt_scene_desc", "Opts": "mcpt_opts",
+    "Counters": "mcpt_counters", "SceneInfo": "mcpt_scene_info", "DenoiseOpts": "mcpt_denoise_opts", "AdaptiveOpts": "mcpt_adaptive_opts",
+    "AdaptiveStats": "mcpt_adaptive_stats", "UpdateInfo": "mcpt_update_info", "ReprojectOpts": "mcpt_reproject_opts",
+    "ReprojectInfo": "mcpt_reproject_info", "MaterialInfo": "mcpt_material_info", "TransformInfo": "mcpt_transform_info",
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _header_layout(pkg):
+    """What a C compiler makes of include/mcpt.h, from one program generated from the ctypes classes' own _fields_ and compiled once:
+    {class name: [sizeof, offsetof of every field in _fields_ order]}, plus "abi" (MCPT_ABI_VERSION) and "flags" ({FLAG_x: MCPT_FLAG_x})."""
+    flags = sorted(n for n in dir(pkg) if n.startswith("FLAG_"))
+    lines = []
+    for name, struct in STRUCTS.items():
+        fields = [f[0] for f in getattr(pkg, name)._fields_]
+        lines.append('  printf("%s %%zu%s\\n", sizeof(%s)%s);' % (name, " %zu" * len(fields), struct, "".join(", offsetof(%s, %s)" % (struct, f) for f in fields)))
+    lines.append('  printf("abi %d\\n", MCPT_ABI_VERSION);')
+    lines.append('  printf("flags%s\\n"%s);' % (" %u" * len(flags), "".join(", (unsigned)MCPT_%s" % f for f in flags)))
+    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "mcpt.h"\nint main(void) {\n%s\n  return 0; }\n' % "\n".join(lines)
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "t.c"); exe = os.path.join(d, "t")
         open(src, "w").write(prog)
         subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), src, "-o", exe])   # the header is plain C
-        got = [int(x) for x in subprocess.check_output([exe]).split()]
-    want = [C.sizeof(pkg.Texture), C.sizeof(pkg.MaterialC), C.sizeof(pkg.CameraC), C.sizeof(pkg.SceneDesc), C.sizeof(pkg.Opts),
-            C.sizeof(pkg.Counters), C.sizeof(pkg.SceneInfo), pkg.SceneDesc.camera.offset]
-    assert got == want
+        out = {l.split()[0]: [int(x) for x in l.split()[1:]] for l in subprocess.check_output([exe]).decode().splitlines()}
+    out["abi"] = out["abi"][0]; out["flags"] = dict(zip(flags, out["flags"]))
+    return out
+
+
+def test_ctypes_structs_match_the_header_layout(pkg):
+    """STRUCTS names every ctypes.Structure the package declares, so that test_struct_layout_matches_the_header leaves none out; the sizes,
+    the ABI version and the flag values of the header are the package's."""
+    declared = sorted(n for n, v in vars(pkg).items() if isinstance(v, type) and issubclass(v, C.Structure) and v.__module__ == pkg.__name__)
+    assert declared == sorted(STRUCTS) and len(set(STRUCTS.values())) == len(STRUCTS)
+    got = _header_layout(pkg)
+    assert [got[n][0] for n in STRUCTS] == [C.sizeof(getattr(pkg, n)) for n in STRUCTS]
+    assert got["abi"] == 4
+    assert len(got["flags"]) >= 6 and got["flags"] == {f: getattr(pkg, f) for f in got["flags"]}
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
+@pytest.mark.parametrize("name", sorted(STRUCTS))
+def test_struct_layout_matches_the_header(pkg, name):
+    """sizeof and the offsetof of EVERY field of the class's _fields_ against the header's struct, and MCPT_ABI_VERSION == 4."""
+    cls = getattr(pkg, name)
+    got = _header_layout(pkg)
+    assert len(cls._fields_) >= 1
+    assert got[name] == [C.sizeof(cls)] + [getattr(cls, f[0]).offset for f in cls._fields_]
+    assert got["abi"] == 4
 
 
 def test_no_cpu_fallback(pkg):
@@ -115,10 +148,9 @@ def test_work_item_decode_divisions_are_exact(pkg, tmp_path):
     """The shade kernel decodes a work item with three divisions by run-time values (tiles of the call, tiles per row, film width) done as
     multiply + shift with constants the host computes per launch (wavefront.hip: wf_make_fastdiv): tests/fastdiv_check.cpp links the
     library and checks x / d for 26 000 divisors against 4 million dividends below the 2^30 bound, multiples and their neighbours first."""
-    csrc = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc")
     exe = str(tmp_path / "fastdiv_check")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "fastdiv_check.cpp"), "-o", exe, "-L" + csrc, "-lmcpt_hip",
-                           "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
+    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "fastdiv_check.cpp"), "-o", exe, "-L" + CSRC, "-lmcpt_hip",
+                           "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
     # and the film-size bound the scheme rests on is enforced where scenes come in
@@ -212,7 +244,7 @@ def test_cpp_host_loader_reads_the_reference_file_formats(pkg, tmp_path):
     """host/Model.cpp (own OBJ + MTL + XML + PPM reader behind the reference's `Model(filename)`) against the generator's
     arrays, through `mcpt_cli --check` (host-only: loader -> model_to_desc -> mcpt_check_scene)."""
     import json
-    cli = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc", "mcpt_cli")
+    cli = CLI
     assert os.path.exists(cli), "build() compiles mcpt_cli"
     s = pkg.scenes.bathroom_stress(64, 36, detail=8, tex_size=16)
     obj = s.write(str(tmp_path))
@@ -236,7 +268,7 @@ def test_cpp_host_loader_decodes_jpeg_textures(pkg, tmp_path):
     grey, restart intervals, optimised Huffman tables; progressive files (spectral selection + successive approximation, the scan script
     libjpeg writes) with and without restart intervals.  `mcpt_cli --decode-image` is host-only."""
     Image = pytest.importorskip("PIL.Image")
-    cli = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc", "mcpt_cli")
+    cli = CLI
     rng = np.random.RandomState(3)
 
     def picture(w, h):
@@ -291,7 +323,7 @@ def test_cpp_host_loader_decodes_jpeg_textures(pkg, tmp_path):
 def test_cpp_host_loader_decodes_every_png_flavour(pkg, tmp_path):
     """PNG colour types 0/2/3/4/6, bit depths 1-16 (host/Model.cpp, zlib inflate + own unfiltering) -- exact against Pillow."""
     Image = pytest.importorskip("PIL.Image")
-    cli = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc", "mcpt_cli")
+    cli = CLI
     rng = np.random.RandomState(5)
     a = rng.randint(0, 256, (37, 53, 3)).astype(np.uint8)
     cases = {"rgb": Image.fromarray(a), "rgba": Image.fromarray(np.dstack([a, rng.randint(0, 256, (37, 53, 1)).astype(np.uint8)])),
@@ -332,7 +364,7 @@ def test_cpp_host_loader_decodes_interlaced_png_bmp_and_tga(pkg, tmp_path):
     (RGB, RGBA, grey, 16-bit, 4-bit grey; odd sizes down to 1 x 1 so that some passes are empty), BMP (24-bit, 8-bit palettised) and TGA
     (true colour and grey, raw and run-length coded) -- exact against Pillow's decode of the same files."""
     Image = pytest.importorskip("PIL.Image")
-    cli = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc", "mcpt_cli")
+    cli = CLI
     rng = np.random.RandomState(9)
 
     def decoded(path):
@@ -395,7 +427,7 @@ def test_cpp_host_loader_decodes_radiance_hdr_rle_bmp_and_mapped_tga(pkg, tmp_pa
     per-scanline run-length form, and stb's fall-back when the first scanline carries no RLE marker; fixtures written here, expected
     values from that formula (parity unpinned against a third decoder: none is installed).  RLE8 BMP and colour-mapped TGA: exact against
     Pillow's decode of the same files."""
-    cli = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc", "mcpt_cli")
+    cli = CLI
     rng = np.random.RandomState(5)
 
     def decoded_hdr(path):

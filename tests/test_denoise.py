@@ -8,46 +8,19 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+from tests import kit
 from tests.denoise_ref import denoise_ref, pixel_angle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["mcpt_render_features", "mcpt_read_features", "mcpt_denoise", "mcpt_read_denoised", "mcpt_denoised_device_ptr"]
 
 
 # ------------------------------------------------------------------------------------------------------------------------ CPU
 def test_library_exports_the_denoise_entry_points(pkg):
-    lib = pkg.load_library()
-    assert [s for s in NEW_SYMBOLS if not hasattr(lib, s)] == []
-    assert set(NEW_SYMBOLS) <= set(pkg.EXPORTED_SYMBOLS)
-
-
-@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
-def test_denoise_opts_layout_matches_the_header(pkg):
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "mcpt.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(mcpt_denoise_opts), offsetof(mcpt_denoise_opts, struct_size), offsetof(mcpt_denoise_opts, iterations),
-         offsetof(mcpt_denoise_opts, sigma_color), offsetof(mcpt_denoise_opts, sigma_normal), offsetof(mcpt_denoise_opts, sigma_depth),
-         offsetof(mcpt_denoise_opts, reserved));
-  return 0; }
-'''
-    with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, "t.c"); exe = os.path.join(d, "t")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        got = [int(x) for x in subprocess.check_output([exe]).split()]
-    D = pkg.DenoiseOpts
-    assert got == [C.sizeof(D), D.struct_size.offset, D.iterations.offset, D.sigma_color.offset, D.sigma_normal.offset,
-                   D.sigma_depth.offset, D.reserved.offset]
+    kit.assert_exports(pkg, NEW_SYMBOLS)
 
 
 def test_null_context_is_an_invalid_argument(pkg):
@@ -363,14 +336,11 @@ def _tonemap(film):
 
 @pytest.mark.gpu
 def test_facade_denoised_matches_the_reference_filter(pkg, tmp_path):
-    csrc = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc"); host = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "host")
-    exe = str(tmp_path / "facade_denoise")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + host, os.path.join(ROOT, "tests", "facade_denoise.cpp"), os.path.join(csrc, "libmcpt_host.a"),
-                           "-o", exe, "-L" + csrc, "-lmcpt_hip", "-lz", "-lpthread", "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
+    exe = kit.build_facade("facade_denoise.cpp", tmp_path)
     scene = pkg.scenes.cornell_box_small(48, 32)
     obj = scene.write(str(tmp_path / "scene"))
     outs = [str(tmp_path / n) for n in ("dev.rgb", "host.rgb", "film.bin", "feat.bin")]
-    line = subprocess.check_output([exe, obj, "8", "6"] + outs, timeout=300).decode().split("\n")[-2].split()
+    line = kit.run_facade(exe, [obj, "8", "6"] + outs)
     assert line == ["48", "32", "8"]
     dev = np.fromfile(outs[0], np.uint8).reshape(32, 48, 3).astype(int); hst = np.fromfile(outs[1], np.uint8).reshape(32, 48, 3).astype(int)
     film = np.fromfile(outs[2], np.float32).reshape(32, 48, 4); feat = np.fromfile(outs[3], np.float32).reshape(32, 48, 8)
@@ -382,11 +352,9 @@ def test_facade_denoised_matches_the_reference_filter(pkg, tmp_path):
 
 @pytest.mark.gpu
 def test_cli_writes_the_denoised_image(pkg, tmp_path):
-    cli = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc", "mcpt_cli")
     obj = pkg.scenes.cornell_box_small(40, 32).write(str(tmp_path / "scene"))
     out = str(tmp_path / "img")
-    p = subprocess.run([cli, obj, "--spp", "8", "--batch", "2", "--depth", "6", "--denoise", "--save-every", "2", "--out", out],
-                       capture_output=True, text=True, timeout=300)
+    p = kit.run_cli([obj, "--spp", "8", "--batch", "2", "--depth", "6", "--denoise", "--save-every", "2", "--out", out])
     assert p.returncode == 0, p.stderr[-2000:]
     for name in ("img8.png", "img8_denoised.png", "img4_denoised.png"):
         assert os.path.getsize(str(tmp_path / name)) > 100, name

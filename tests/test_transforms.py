@@ -12,14 +12,13 @@ import functools
 import os
 import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from tests import transform_ref as T
+from tests import kit, transform_ref as T
+from tests.kit import ROOT, bits, render_film
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["mcpt_set_vertex_groups", "mcpt_update_transforms", "mcpt_update_transforms_reproject", "mcpt_get_transform_info"]
 INVALID, UNSUPPORTED = 1, 6
 W, H = 64, 64
@@ -62,33 +61,7 @@ M_LAMP = T.about(T.rotation((0, 1, 0), 25.0), (0.5, 0.999, 0.5), (0.1, -0.2, 0.0
 
 # ------------------------------------------------------------------------------------------------------------------------ CPU
 def test_library_exports_the_transform_entry_points(pkg):
-    lib = pkg.load_library()
-    assert [s for s in NEW_SYMBOLS if not hasattr(lib, s)] == []
-    assert set(NEW_SYMBOLS) <= set(pkg.EXPORTED_SYMBOLS)
-    assert lib.mcpt_abi_version() == 4
-    for name in ("set_vertex_groups", "update_transforms", "update_transforms_reproject", "transform_info"):
-        assert callable(getattr(pkg.Renderer, name))
-
-
-@pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
-def test_transform_info_layout_matches_the_header(pkg):
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "mcpt.h"
-#define I(f) offsetof(mcpt_transform_info, f)
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %d\n", sizeof(mcpt_transform_info), I(struct_size), I(n_groups), I(updates), I(reserved0), I(last_ms), I(reserved),
-         MCPT_ABI_VERSION);
-  return 0; }
-'''
-    with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, "t.c"); exe = os.path.join(d, "t")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        got = [int(x) for x in subprocess.check_output([exe]).split()]
-    I = pkg.TransformInfo
-    assert got == [C.sizeof(I), I.struct_size.offset, I.n_groups.offset, I.updates.offset, I.reserved0.offset, I.last_ms.offset, I.reserved.offset, 4]
+    kit.assert_exports(pkg, NEW_SYMBOLS, ("set_vertex_groups", "update_transforms", "update_transforms_reproject", "transform_info"))
 
 
 def test_null_context_is_an_invalid_argument_for_the_transform_calls(pkg):
@@ -236,16 +209,6 @@ def test_host_cofactors_and_validation_are_the_restatement_bit_for_bit(pkg, tmp_
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU helpers
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def _film(r, spp=4, seed=5):
-    r.clear(); r.render(spp, seed=seed)
-    return r.read_accum()
-
-
 @functools.lru_cache(maxsize=None)
 def _rays(pkg):
     """The camera rays of S-cornell (one per pixel, fixed xi) and random rays through its box: computed once, never changed."""
@@ -270,14 +233,14 @@ def _state(pkg, r, film=True):
     lf, lrec, lpos = r.probe_lights()
     out = {"t": t, "face": f, "u": u, "v": v, "shade": shade, "light_face": lf, "light_rec": lrec, "light_pos": lpos}
     if film:
-        out["film"] = _film(r)
+        out["film"] = render_film(r, 4, 5)
     return out
 
 
 def _assert_same(a, b, skip=()):
     for k in a:
         if k not in skip:
-            assert np.array_equal(_bits(a[k]), _bits(b[k])), k
+            assert np.array_equal(bits(a[k]), bits(b[k])), k
 
 
 @functools.lru_cache(maxsize=None)
@@ -390,7 +353,7 @@ def test_moved_lamp_moves_the_light_records(pkg):
     # light_pos64 is the moved corners relative to the creation centre
     s = _scene(pkg); v, _ = _ref(pkg, _mats(lamp=M_LAMP))
     want = (v[s.face[a["light_face"], :, 0]] - np.array(list(R.info().centre))).reshape(-1, 9)
-    assert np.array_equal(_bits(want), _bits(a["light_pos"]))
+    assert np.array_equal(bits(want), bits(a["light_pos"]))
     R.close(); O.close()
 
 
@@ -474,7 +437,7 @@ def test_update_between_renders_without_a_sync(pkg, which):
     O.render(4, seed=9, first_sample=0); O.sync(); O.update_transforms(m); O.sync(); O.render(4, seed=9, first_sample=4); O.sync()
     O.update_transforms(_mats(sphere=M_OTHER)); O.sync(); O.update_transforms(m); O.sync()
     O.render(2, seed=9, first_sample=8); O.sync()
-    assert np.array_equal(_bits(got), _bits(O.read_accum())) and np.all(got[..., 3] == 10)
+    assert np.array_equal(bits(got), bits(O.read_accum())) and np.all(got[..., 3] == 10)
     if which == "side":
         R.set_stream(0)
     R.close(); O.close()
@@ -494,10 +457,10 @@ def test_reprojection_follows_the_transform(pkg, with_camera):
     R.update_transforms_reproject(m, camera=cam, **opts)
     O.update_vertices_reproject(v, n, camera=cam, **opts)
     a, b = R.read_accum(), O.read_accum()
-    assert np.array_equal(_bits(a), _bits(b))
+    assert np.array_equal(bits(a), bits(b))
     ia, ib = R.reproject_info(), O.reproject_info()
     assert (ia.reprojections, ia.pixels_reused) == (ib.reprojections, ib.pixels_reused) == (1, ib.pixels_reused) and ia.pixels_reused > 0.5 * W * H
-    assert np.array_equal(_bits(R.features()), _bits(O.features()))          # the context holds the new scene's features
+    assert np.array_equal(bits(R.features()), bits(O.features()))          # the context holds the new scene's features
     assert R.update_info().updates == 1 and R.transform_info().updates == 1
     _assert_same(_state(pkg, R, film=False), _state(pkg, O, film=False))
     R.close(); O.close()
@@ -516,13 +479,13 @@ def test_transform_refusals(pkg):
     plain.close()
     R = pkg.Renderer(s, max_depth=6, flags=FLAGS(pkg))
     o, d = _rays(pkg)
-    film = _film(R); trace = R.probe_trace4(o, d); bytes0 = R.info().device_bytes
+    film = render_film(R, 4, 5); trace = R.probe_trace4(o, d); bytes0 = R.info().device_bytes
 
     def unchanged():
         assert R.update_info().updates == 0 and R.transform_info().updates == 0
-        assert np.array_equal(_bits(_film(R)), _bits(film))
+        assert np.array_equal(bits(render_film(R, 4, 5)), bits(film))
         for x, y in zip(trace, R.probe_trace4(o, d)):
-            assert np.array_equal(_bits(x), _bits(y))
+            assert np.array_equal(bits(x), bits(y))
 
     def refused(call, status=INVALID):
         with pytest.raises(pkg.McptError) as e:
@@ -616,10 +579,7 @@ def test_clone_and_bookkeeping(pkg):
 
 @pytest.mark.gpu
 def test_facade_transforms(pkg, tmp_path):
-    csrc = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc"); host = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "host")
-    exe = str(tmp_path / "facade_transforms")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + host, os.path.join(ROOT, "tests", "facade_transforms.cpp"), os.path.join(csrc, "libmcpt_host.a"),
-                           "-o", exe, "-L" + csrc, "-lmcpt_hip", "-lz", "-lpthread", "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
+    exe = kit.build_facade("facade_transforms.cpp", tmp_path)
     a = pkg.scenes.cornell_box(44, 30, sphere_lon=24, sphere_lat=12)
     obj = a.write(str(tmp_path / "a"))
     # the program reads the 9-digit text of the file: the same numbers scenes.py keeps (SceneData is rounded through that text form)
@@ -629,31 +589,24 @@ def test_facade_transforms(pkg, tmp_path):
     M_RIGID.tofile(str(tmp_path / "m.bin"))
     outs = [str(tmp_path / n) for n in ("xf.bin", "upd.bin", "rp.bin")]
     k = 4
-    line = subprocess.check_output([exe, obj, "glossy", str(k), str(tmp_path / "m.bin"), str(tmp_path / "v.bin"), str(tmp_path / "n.bin")] + outs,
-                                   timeout=300).decode().split("\n")[-2].split()
+    line = kit.run_facade(exe, [obj, "glossy", str(k), str(tmp_path / "m.bin"), str(tmp_path / "v.bin"), str(tmp_path / "n.bin")] + outs)
     w, h = int(line[0]), int(line[1])
     assert (w, h, int(line[2])) == (44, 30, k)
     xf, upd, rp = [np.fromfile(p, np.float32).reshape(h, w, 4) for p in outs]
     assert np.all(xf[..., 3] == k) and xf[..., :3].sum() > 0                 # the picture started again and ends at k samples
-    assert np.array_equal(_bits(xf), _bits(upd))                             # matrices on the device = the restated arrays through update()
+    assert np.array_equal(bits(xf), bits(upd))                             # matrices on the device = the restated arrays through update()
     assert np.all(rp[..., 3] >= 1) and np.all(rp[..., 3] <= 5) and (rp[..., 3] > 1).mean() > 0.5   # history capped at 4, plus the new frame
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("reproject", [False, True])
 def test_cli_spin(pkg, tmp_path, reproject):
-    cli = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc", "mcpt_cli")
     obj = pkg.scenes.cornell_box_small(40, 32).write(str(tmp_path / "scene"))
     out = str(tmp_path / "img")
-    base = [cli, obj, "--turntable", "3", "--spp", "4", "--depth", "5", "--out", out]
-    p = subprocess.run(base + ["--spin", "glossy"] + (["--reproject", "8"] if reproject else []), capture_output=True, text=True, timeout=300)
+    base = [obj, "--turntable", "3", "--spp", "4", "--depth", "5", "--out", out]
+    p = kit.run_cli(base + ["--spin", "glossy"] + (["--reproject", "8"] if reproject else []))
     assert p.returncode == 0, p.stderr[-2000:]
-    imgs = []
-    for f in range(3):
-        with open("%s_turn%d.png" % (out, f), "rb") as fh:
-            data = fh.read()
-        assert data[:8] == b"\x89PNG\r\n\x1a\n"
-        imgs.append(data)
+    imgs = kit.turntable_frames(out)
     assert imgs[0] != imgs[1] and imgs[1] != imgs[2]
     if not reproject:                                                        # clean errors: an unknown material, --spin without --turntable, a shared vertex
         S = pkg.scenes
@@ -664,12 +617,11 @@ def test_cli_spin(pkg, tmp_path, reproject):
         m.add_tri(i[0], i[1], i[2], 2); m.add_tri(i[0], i[2], i[3], 0)       # one quad, two materials: its diagonal's vertices belong to both
         shared = m.finish("shared", [S.Material("floor", kd=(0.5, 0.5, 0.5)), S.Material("lamp", kd=(0.5, 0.5, 0.5), radiance=(5, 5, 5)),
                                      S.Material("part", kd=(0.6, 0.2, 0.2))], S.Camera((0.5, 0.5, 2.5), (0.5, 0.4, 0.0), (0, 1, 0), 40.0, 24, 16))
-        q = subprocess.run([cli, shared.write(str(tmp_path / "shared")), "--turntable", "2", "--spp", "1", "--out", out, "--spin", "part"],
-                           capture_output=True, text=True, timeout=300)
+        q = kit.run_cli([shared.write(str(tmp_path / "shared")), "--turntable", "2", "--spp", "1", "--out", out, "--spin", "part"])
         assert q.returncode == 1 and "is used by faces of groups" in q.stderr, q.stderr[-2000:]
-        q = subprocess.run(base + ["--spin", "no-such-material"], capture_output=True, text=True, timeout=300)
+        q = kit.run_cli(base + ["--spin", "no-such-material"])
         assert q.returncode == 1 and "no material named" in q.stderr
-        q = subprocess.run([cli, obj, "--spin", "glossy"], capture_output=True, text=True, timeout=300)
+        q = kit.run_cli([obj, "--spin", "glossy"])
         assert q.returncode == 2 and "--turntable" in q.stderr
 
 
