@@ -5,6 +5,7 @@
 #include "scene_build.h"
 #include "bvh_gpu.h"
 #include "wavefront.h"
+#include "wf_plan.h"
 #include "denoise.h"
 #include "adaptive.h"
 #include "refit.h"
@@ -155,7 +156,7 @@ struct mcpt_ctx {
         Stream stream;
         Event done_ev;
         uint64_t last_iterations = 0, last_timed = 0;
-        // Known-length jobs (every item has its own slot and one sample, depth-limited: render_wavefront) are enqueued whole and NOT waited for:
+        // Known-length jobs (every item has its own slot and one sample, depth-limited: wf_plan_call) are enqueued whole and NOT waited for:
         // the control-block snapshot taken after their last iteration is looked at later -- by the next call that drains the stream, or when the
         // ring of snapshots is full -- so consecutive one-sample calls (the reference's loop, main.cpp:26-33) cost the host only their launches.
         struct Verdict { uint32_t ring_slot, it, n_shared; };
@@ -166,10 +167,8 @@ struct mcpt_ctx {
     Event fork_ev;
     WaveTuning tune{};
     uint32_t trace_grid = 0;
-    uint32_t pool_cap = 1u << 23;       // most slots a sub-pipeline's pool may have (MCPT_WF_POOL_LOG2); pools are allocated on first use, sized to the job
-    uint32_t items_per_slot = 1;        // pool sizing knob: a job of n work items gets n / items_per_slot slots, at most pool_cap (MCPT_WF_ITEMS_PER_SLOT), see render_wavefront
+    WfKnobs knobs{};                    // the scheduler's environment knobs, read by finish_ctx and by nobody after it (wf_plan.h)
     int n_cus = 0;
-    uint32_t time_kernels = 0;          // MCPT_TIME_KERNELS=N: bracket the two kernels of every Nth iteration with HIP events (0 = off)
     double last_trace_ms = 0.0, total_trace_ms = 0.0, last_shade_ms = 0.0, total_shade_ms = 0.0;
     uint64_t total_iterations = 0;
     bool binary_ok = true;                // the binary cross-check tree fits its kernels' stack (false: a deep device-built tree)
@@ -348,17 +347,14 @@ static mcpt_status finish_ctx(mcpt_ctx* c) {
     HIP_TRY(hipMemset(c->accum_own.p, 0, c->accum_own.bytes));
     HIP_TRY(c->counters.alloc(WF_COUNTER_REPLICAS));
     HIP_TRY(hipMemset(c->counters.p, 0, c->counters.bytes));
-    {   // ---- wavefront pool.  Tunables are developer knobs (environment), not part of the ABI.
+    {   // ---- wavefront pool.  Tunables are developer knobs (environment), not part of the ABI; every one of them is decided ONCE, here: no
+        // render call reads the environment.
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, c->device));
         c->n_cus = prop.multiProcessorCount;
-        c->pool_cap = 1u << std::min(26u, env_u32("MCPT_WF_POOL_LOG2", 23));
-        c->pool_cap = env_u32("MCPT_WF_POOL_SLOTS", c->pool_cap) & ~uint32_t(16 * WF_SHADE_BLOCK - 1);   // (developer knob: any multiple of 4096 slots)
-        if (c->pool_cap < 4096) c->pool_cap = 4096;
-        c->items_per_slot = std::max(1u, env_u32("MCPT_WF_ITEMS_PER_SLOT", 1));
+        c->knobs = wf_read_knobs(env_u32);
         c->tune.refill_at = env_u32("MCPT_WF_REFILL", 28); c->tune.leaf_at = env_u32("MCPT_WF_LEAF", 16);
         c->tune.inner_keep = env_u32("MCPT_WF_INNER", 24); c->tune.policy = env_u32("MCPT_WF_POLICY", 0); c->tune.pend_cap = 48;      // speculative traversal: refined below once the scene's size is known
-        c->time_kernels = env_u32("MCPT_TIME_KERNELS", 0);
         if (c->use_wavefront) {
             uint32_t n_lanes = env_u32("MCPT_WF_LANES", 2);
             if (n_lanes < 1) n_lanes = 1;
@@ -626,7 +622,7 @@ static mcpt_status resolve_timing(mcpt_ctx* c, bool block = true) {
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, c->ev0[k], c->ev1[k]));
         c->last_kernel_ms = ms; c->total_kernel_ms += ms; c->timed_tail++;
-        if (c->use_wavefront && c->time_kernels && c->timed_tail == c->timed_head) {   // (per-kernel timing: calls are resolved one at a time, see mcpt_render_tiles)
+        if (c->use_wavefront && c->knobs.time_kernels && c->timed_tail == c->timed_head) {   // (per-kernel timing: calls are resolved one at a time, see mcpt_render_tiles)
             double sh = 0.0, tr = 0.0;
             for (auto& L : c->lanes) {
                 if (L.last_timed) {                                          // sampled iterations stand for all of them
@@ -655,8 +651,8 @@ static mcpt_status ensure_pool(mcpt_ctx* ctx, mcpt_ctx::WfLane& L, uint32_t P) {
     HIP_TRY(hipStreamSynchronize(L.stream)); HIP_TRY(hipStreamSynchronize(ctx->stream));
     L.pool_bufs.clear(); L.pool.P = 0;                                   // (the old buffers are freed before the new ones are asked for)
     // the drain compaction's scratch: half a pool of the seven records a live slot carries from one iteration to the next (+ 4096 slots of rounding)
-    const bool want_compact = P >= 4 * WF_COMPACT_MIN_SLOTS && !(ctx->opts.flags & MCPT_FLAG_DETERMINISTIC) && env_u32("MCPT_WF_COMPACT", 1) != 0;
-    const uint32_t eighths = std::max(1u, std::min(7u, env_u32("MCPT_WF_COMPACT_EIGHTHS", 4)));      // compact when at most this many eighths of the swept slots are alive
+    const bool want_compact = P >= 4 * WF_COMPACT_MIN_SLOTS && !(ctx->opts.flags & MCPT_FLAG_DETERMINISTIC) && ctx->knobs.compact;
+    const uint32_t eighths = ctx->knobs.compact_eighths;                 // compact when at most this many eighths of the swept slots are alive
     const uint32_t ccap = want_compact ? uint32_t(uint64_t(P) * eighths / 8) + 4096 : 0, nb = P / WF_SHADE_BLOCK;
     L.compact = CompactBufs{}; L.compact.capacity = ccap; L.compact.eighths = eighths;
     PathPool& pl = L.pool; CompactBufs& cb = L.compact;
@@ -700,168 +696,117 @@ static mcpt_status check_pending_jobs(mcpt_ctx* ctx) {
     return MCPT_OK;
 }
 
-static mcpt_status render_wavefront(mcpt_ctx* ctx, RenderParams& p0, float4* accum) {
-    // One mcpt_render call = per sub-pipeline a loop of [shade, trace] launches over its slot pool until its work items are done.
-    // The sample range is split contiguously over the sub-pipelines; their streams fork from and join the context's stream.
-    const uint64_t tiles = p0.n_owned;
-    const uint32_t n_lanes = p0.probe_n ? 1u : uint32_t(ctx->lanes.size());    // a probe (mcpt_probe_paths) runs on one sub-pipeline
-    const bool count = (p0.flags & MCPT_FLAG_COUNT_TRAVERSAL) != 0;
-    constexpr uint32_t CHECK = 4, RING = 8;
-    const bool debug = env_u32("MCPT_WF_DEBUG", 0) != 0;
-    const uint32_t max_it = env_u32("MCPT_WF_MAXIT", 1u << 20);
-    DevCounters* cnt = ctx->counters.p;
-    struct Run { RenderParams p; PathPool pool; uint32_t n_items = 0, n_shared = 0, it = 0, issued = 0, seen = 0, bound = 0, snap_it[RING] = {0}; size_t kev = 0; bool active = false, done = false;
-                 uint32_t grid = 0;         // blocks of this sub-pipeline's trace launches (below: small jobs share the CUs instead of queueing for them)
-                 bool drain = false; };     // drain: a snapshot showed the shared work-item cursors exhausted -> the compaction launches follow every trace launch from here on
-    std::vector<Run> runs(n_lanes);
-    uint32_t n_active = 0;
-    // A call with fewer samples than sub-pipelines (the reference's one-sample-per-call loop, Render.cpp:56-69) splits its TILES over them
-    // instead of its samples -- pipeline k takes every n_lanes-th tile of this call's share -- so that the shade of one still runs
-    // beside the trace of the other.  Their pixel sets are disjoint.
-    const bool split_tiles = !p0.probe_n && p0.spp < n_lanes && tiles >= n_lanes;
-    for (uint32_t k = 0; k < n_lanes; k++) {
-        Run& r = runs[k];
-        r.p = p0;
-        uint64_t my_tiles = tiles;
-        if (split_tiles) {
-            r.p.tile_mod = p0.tile_mod * n_lanes; r.p.tile_rem = p0.tile_rem + k * p0.tile_mod;
-            my_tiles = (tiles - k + n_lanes - 1) / n_lanes; r.p.n_owned = uint32_t(my_tiles);
-        } else {
-            const uint32_t lo = uint32_t(uint64_t(p0.spp) * k / n_lanes), hi = uint32_t(uint64_t(p0.spp) * (k + 1) / n_lanes);   // (equal shares: 40 / 60 and 35 / 65 splits, so that the two pools do not drain together, were 6 - 10 % slower)
-            if (hi == lo) { r.done = true; ctx->lanes[k].last_iterations = 0; ctx->lanes[k].last_timed = 0; continue; }
-            r.p.spp = hi - lo; r.p.first_sample = p0.first_sample + lo;
-        }
-        if (r.p.samples_per_item > r.p.spp) r.p.samples_per_item = r.p.spp;
-        r.p.chunks = (r.p.spp + r.p.samples_per_item - 1) / r.p.samples_per_item;
-        r.n_items = p0.probe_n ? p0.probe_n : uint32_t(my_tiles * 64 * r.p.chunks);
-        // Pool slots for this job: one per work item, at most pool_cap (2^23 by default).  (items_per_slot, a developer knob, default 1: a job of more
-        // than 2^20 items gets items / items_per_slot slots, at least 2^20 -- what a slot costs is the end-of-job drain, the last ~8 iterations sweep a
-        // pool that is emptying; measured in round 3, fewer slots than the job can fill lose more in short launches than they save in the drain.)
-        {
-            const uint64_t want64 = ((uint64_t(r.n_items) + WF_SHADE_BLOCK - 1) / WF_SHADE_BLOCK) * WF_SHADE_BLOCK;
-            uint64_t P = std::min<uint64_t>(want64, ctx->pool_cap);
-            if (want64 > (1ull << 20)) {
-                const uint64_t by_items = ((uint64_t(r.n_items) / ctx->items_per_slot) + 16 * WF_SHADE_BLOCK - 1) & ~uint64_t(16 * WF_SHADE_BLOCK - 1);   // (rounded UP: a job just over 2^20 items keeps one slot per item and its known length)
-                P = std::min<uint64_t>(P, std::max<uint64_t>(by_items, 1ull << 20));
-            }
-            mcpt_status ps = ensure_pool(ctx, ctx->lanes[k], uint32_t(P)); if (ps != MCPT_OK) return ps;
-            r.pool = ctx->lanes[k].pool;
-            r.pool.P = uint32_t(P);                                        // (a smaller job sweeps only the slots it needs)
-        }
-        // Every item has a slot of its own and one sample: all paths start in iteration 0, vertex b is shaded in iteration b + 1, the
-        // depth limit ends the path by iteration max_depth + 1 and a parked NEE term (SLOT_DRAIN) costs one more.  The loop then runs
-        // exactly that many iterations before it looks at the control block for the first time -- no launches past the end of the job.
-        if (r.n_items <= r.pool.P && r.p.chunks == 1 && r.p.samples_per_item == 1 && p0.max_depth != 0 && !p0.probe_n) r.bound = p0.max_depth + 3;
-        // Work items: 90 % are split evenly into one private range per shade block -- the block advances a cursor only it touches, so
-        // the returning atomic that used to sit between two barriers of every block is gone from the steady state -- and the last
-        // 10 % still come from the shared cursors, which is what balances the blocks at the end of the call.
-        r.p.priv_items = 0; r.p.shared_base = 0; r.n_shared = r.n_items;
-        const uint32_t n_blocks = r.pool.P / WF_SHADE_BLOCK;
-        if (!p0.probe_n && uint64_t(r.n_items) >= 4ull * r.pool.P && env_u32("MCPT_WF_PRIVATE_ITEMS", 1)) {
-            r.p.priv_items = uint32_t(0.9 * double(r.n_items) / double(n_blocks)) & ~63u;   // whole 64-item units (block b owns unit k * n_blocks + b)
-            r.p.shared_base = n_blocks * r.p.priv_items;
-            r.n_shared = r.n_items - r.p.shared_base;
-        }
-        {   // snapshots of earlier known-length jobs on this sub-pipeline: a polled job starts with none outstanding (it takes the ring's slots
-            // in turn from 0), a known-length one needs a free slot for its own
-            mcpt_ctx::WfLane& L = ctx->lanes[k];
-            mcpt_status vs = check_lane_verdicts(L, r.bound == 0); if (vs != MCPT_OK) return vs;
-            if (L.verdicts.size() > RING - 2) { vs = check_lane_verdicts(L, true); if (vs != MCPT_OK) return vs; }
-        }
-        r.active = true; n_active++;
+// ---- The executor of a WfPlan: wf_plan.h decides what a call's shape makes of it, everything from here to render_wavefront's end launches it.
+constexpr uint32_t WF_CHECK = 4, WF_RING = 8;     // a polled job snapshots its control block every WF_CHECK iterations, into a ring of WF_RING slots
+// What changes while a sub-pipeline's loop runs; the rest is its WfLanePlan.
+struct Run { const WfLanePlan* plan = nullptr; PathPool pool; uint32_t it = 0, issued = 0, seen = 0, snap_it[WF_RING] = {0}; size_t kev = 0; bool done = false;
+             uint32_t grid = 0;         // blocks of this sub-pipeline's trace launches (WfLanePlan::grid, until wf_poll sees a compacted sweep)
+             bool drain = false; };     // drain: a snapshot showed the shared work-item cursors moving -> the compaction launches follow every trace launch from here on
+static hipError_t wf_k_event(mcpt_ctx::WfLane& L, Run& r, bool timed) {
+    if (!timed) return hipSuccess;
+    if (r.kev == L.k_ev.size()) { Event ev; hipError_t e = hipEventCreate(ev.out()); if (e != hipSuccess) return e; L.k_ev.push_back(std::move(ev)); }
+    return hipEventRecord(L.k_ev[r.kev++], L.stream);
+}
+// the control block as it is after the launches enqueued so far, copied to slot q of the sub-pipeline's ring, and the event that says it has arrived
+static hipError_t wf_snapshot(mcpt_ctx::WfLane& L, uint32_t q) {
+    const hipError_t e = hipMemcpyAsync(&L.h_ctl[q], L.ctl_buf.p, sizeof(IterCtl), hipMemcpyDeviceToHost, L.stream);
+    return e != hipSuccess ? e : hipEventRecord(L.chk_ev[q], L.stream);
+}
+// consume finished control-block snapshots of one sub-pipeline; `block` waits for the oldest one
+static mcpt_status wf_poll(mcpt_ctx::WfLane& L, Run& r, const WfPlan& plan, bool debug, bool block) {
+    const uint32_t n_shared = r.plan->n_shared;
+    while (r.seen < r.issued) {
+        const uint32_t k = r.seen % WF_RING;
+        bool done; HIP_TRY(event_done(L.chk_ev[k], block, done));
+        if (!done) break;
+        block = false;
+        const IterCtl& s = L.h_ctl[k];
+        const uint32_t it_of = r.snap_it[k];                           // snapshot taken after iteration it_of
+        if (debug && (r.seen < 40 || s.pad[WF_CTL_P_ACTIVE]))
+            fprintf(stderr, "[wf] it=%u active=%u head=%u cursor0=%u/%u swept=%u live@compaction=%u compactions=%u\n", it_of, s.any_active[it_of & 3],
+                    s.trace_head[it_of & 3], s.item_cursor[0].v, wf_shard_capacity(n_shared, 0), s.pad[WF_CTL_P_ACTIVE], s.pad[WF_CTL_LIVE], s.pad[WF_CTL_COMPACTIONS]);
+        const JobState js = job_state(s, it_of, n_shared);
+        if (js == JobState::Watchdog) return fail(MCPT_ERR_HIP, WATCHDOG_MSG);
+        if (js == JobState::Finished) r.done = true;
+        // the compaction launches start as soon as the SHARED cursors move at all: a block turns to them when its private range (90 % of the items) is
+        // used up, i.e. in the last tenth of the job -- the host reads snapshots 4 - 8 iterations late, and a drain lasts about ten; the plan kernel
+        // itself waits until every item has been handed out
+        if (plan.small_job && s.pad[WF_CTL_P_ACTIVE] != 0u && s.pad[WF_CTL_P_ACTIVE] <= plan.small_job) r.grid = plan.shared_grid;   // (the compacted sweep of a draining job)
+        if (!r.drain) { uint64_t moved = 0; for (uint32_t q = 0; q < WF_ITEM_SHARDS; q++) moved += s.item_cursor[q].v; if (moved != 0) r.drain = true; }   // (a job has at least one shared item: none left => moved)
+        r.seen++;
     }
-    for (Run& r : runs) if (r.active) r.p.atomic_accum = ((n_active > 1 && !split_tiles) || r.p.chunks > 1) ? 1u : 0u;
-    // Trace grid.  A CU holds ONE trace block (registers), so the trace launches of two sub-pipelines queue for each other's CUs.  That is what the steady
-    // state wants (the other pipeline's SHADE runs beside a trace launch); a job with about a ray per trace lane -- the one-sample frame of the reference's
-    // display loop: 320 k paths per sub-pipeline, 262 k trace lanes -- has nothing to hide and is a chain of 2 x (depth + 3) dependent launches: there each
-    // sub-pipeline's launch takes its share of the CUs and the chains run side by side.  S-cornell 800x800, render + tonemapped read per frame: 2.43 -> 2.06 ms;
-    // two samples per call 2.83 -> 2.76, four 3.95 -> 4.73 (profiles/r04_frame_knobs.txt): the split applies up to 2.5 paths per trace lane.  The same holds
-    // at the end of a long job once the drain compaction has shrunk the sweep that far (poll, below).
-    const uint32_t small_job = env_u32("MCPT_WF_SMALL_JOB_SPLIT", 1) && n_active > 1 ? uint32_t(std::min<uint64_t>(0xffffffffull, uint64_t(ctx->trace_grid) * wf_trace_block_threads() * 5 / 2)) : 0u;
-    const uint32_t shared_grid = std::max(1u, ctx->trace_grid / std::max(1u, n_active));
-    for (Run& r : runs) if (r.active) r.grid = (small_job && !p0.probe_n && r.n_items <= small_job) ? shared_grid : ctx->trace_grid;
+    return MCPT_OK;
+}
+
+// One mcpt_render call: plan it; per active sub-pipeline, in their order, grow its pool and look at the verdicts of its earlier jobs; then
+// their streams fork from the context's stream, run their [shade, trace] loops and join it.
+static mcpt_status render_wavefront(mcpt_ctx* ctx, const RenderParams& p0, float4* accum) {
+    const WfKnobs& knobs = ctx->knobs;
+    const WfPlan plan = wf_plan_call(p0, uint32_t(ctx->lanes.size()), knobs, ctx->trace_grid, wf_trace_block_threads());
+    const uint32_t n_lanes = uint32_t(plan.lanes.size());
+    const bool count = (p0.flags & MCPT_FLAG_COUNT_TRAVERSAL) != 0;
+    DevCounters* cnt = ctx->counters.p;
+    std::vector<Run> runs(n_lanes);
+    for (uint32_t k = 0; k < n_lanes; k++) {
+        const WfLanePlan& lp = plan.lanes[k]; mcpt_ctx::WfLane& L = ctx->lanes[k]; Run& r = runs[k];
+        r.plan = &lp; r.done = !lp.active; r.grid = lp.grid;
+        if (!lp.active) { L.last_iterations = 0; L.last_timed = 0; continue; }
+        mcpt_status st = ensure_pool(ctx, L, lp.P); if (st != MCPT_OK) return st;
+        r.pool = L.pool;
+        r.pool.P = lp.P;                                                  // (a smaller job sweeps only the slots it needs)
+        // snapshots of earlier known-length jobs on this sub-pipeline: a polled job starts with none outstanding (it takes the ring's slots
+        // in turn from 0), a known-length one needs a free slot for its own
+        st = check_lane_verdicts(L, lp.bound == 0); if (st != MCPT_OK) return st;
+        if (L.verdicts.size() > WF_RING - 2) { st = check_lane_verdicts(L, true); if (st != MCPT_OK) return st; }
+    }
     HIP_TRY(hipEventRecord(ctx->fork_ev, ctx->stream));
     for (uint32_t k = 0; k < n_lanes; k++) {
-        if (!runs[k].active) continue;
-        mcpt_ctx::WfLane& L = ctx->lanes[k]; Run& r = runs[k];
+        if (!plan.lanes[k].active) continue;
+        mcpt_ctx::WfLane& L = ctx->lanes[k];
         HIP_TRY(hipStreamWaitEvent(L.stream, ctx->fork_ev, 0));
-        HIP_TRY(launch_wf_pool_reset(r.pool, L.ctl_buf.p, L.stream));    // every slot DEAD, control block zeroed
+        HIP_TRY(launch_wf_pool_reset(runs[k].pool, L.ctl_buf.p, L.stream));   // every slot DEAD, control block zeroed
     }
-    auto k_event = [&](mcpt_ctx::WfLane& L, Run& r, bool timed) -> hipError_t {
-        if (!timed) return hipSuccess;
-        if (r.kev == L.k_ev.size()) { Event ev; hipError_t e = hipEventCreate(ev.out()); if (e != hipSuccess) return e; L.k_ev.push_back(std::move(ev)); }
-        return hipEventRecord(L.k_ev[r.kev++], L.stream);
-    };
-    // the control block as it is after the launches enqueued so far, copied to slot q of the sub-pipeline's ring, and the event that says it has arrived
-    auto snapshot = [](mcpt_ctx::WfLane& L, uint32_t q) -> hipError_t {
-        const hipError_t e = hipMemcpyAsync(&L.h_ctl[q], L.ctl_buf.p, sizeof(IterCtl), hipMemcpyDeviceToHost, L.stream);
-        return e != hipSuccess ? e : hipEventRecord(L.chk_ev[q], L.stream);
-    };
-    // consume finished control-block snapshots of one sub-pipeline; `block` waits for the oldest one
-    auto poll = [&](mcpt_ctx::WfLane& L, Run& r, bool block) -> mcpt_status {
-        while (r.seen < r.issued) {
-            const uint32_t k = r.seen % RING;
-            bool done; HIP_TRY(event_done(L.chk_ev[k], block, done));
-            if (!done) break;
-            block = false;
-            const IterCtl& s = L.h_ctl[k];
-            const uint32_t it_of = r.snap_it[k];                           // snapshot taken after iteration it_of
-            if (debug && (r.seen < 40 || s.pad[WF_CTL_P_ACTIVE]))
-                fprintf(stderr, "[wf] it=%u active=%u head=%u cursor0=%u/%u swept=%u live@compaction=%u compactions=%u\n", it_of, s.any_active[it_of & 3],
-                        s.trace_head[it_of & 3], s.item_cursor[0].v, wf_shard_capacity(r.n_shared, 0), s.pad[WF_CTL_P_ACTIVE], s.pad[WF_CTL_LIVE], s.pad[WF_CTL_COMPACTIONS]);
-            const JobState js = job_state(s, it_of, r.n_shared);
-            if (js == JobState::Watchdog) return fail(MCPT_ERR_HIP, WATCHDOG_MSG);
-            if (js == JobState::Finished) r.done = true;
-            // the compaction launches start as soon as the SHARED cursors move at all: a block turns to them when its private range (90 % of the items) is
-            // used up, i.e. in the last tenth of the job -- the host reads snapshots 4 - 8 iterations late, and a drain lasts about ten; the plan kernel
-            // itself waits until every item has been handed out
-            if (small_job && s.pad[WF_CTL_P_ACTIVE] != 0u && s.pad[WF_CTL_P_ACTIVE] <= small_job) r.grid = shared_grid;   // (the compacted sweep of a draining job)
-            if (!r.drain) { uint64_t moved = 0; for (uint32_t q = 0; q < WF_ITEM_SHARDS; q++) moved += s.item_cursor[q].v; if (moved != 0) r.drain = true; }   // (a job has at least one shared item: none left => moved)
-            r.seen++;
-        }
-        return MCPT_OK;
-    };
-    bool all_done = n_active == 0;
+    bool all_done = plan.n_active == 0;
     while (!all_done) {
         all_done = true;
         for (uint32_t k = 0; k < n_lanes; k++) {                            // one iteration of every live sub-pipeline per round
             Run& r = runs[k];
-            if (!r.active || r.done) continue;
-            mcpt_ctx::WfLane& L = ctx->lanes[k];
+            if (r.done) continue;
+            const WfLanePlan& lp = plan.lanes[k]; mcpt_ctx::WfLane& L = ctx->lanes[k];
             IterCtl* ctl = L.ctl_buf.p;
-            const bool timed = ctx->time_kernels && r.it % ctx->time_kernels == 0;
-            HIP_TRY(k_event(L, r, timed));
-            HIP_TRY(launch_wf_shade(ctx->dev, r.p, r.pool, ctl, r.it, r.n_shared, accum, cnt, L.stream));
-            HIP_TRY(k_event(L, r, timed));
+            const bool timed = knobs.time_kernels && r.it % knobs.time_kernels == 0;
+            HIP_TRY(wf_k_event(L, r, timed));
+            HIP_TRY(launch_wf_shade(ctx->dev, lp.p, r.pool, ctl, r.it, lp.n_shared, accum, cnt, L.stream));
+            HIP_TRY(wf_k_event(L, r, timed));
             HIP_TRY(launch_wf_trace(ctx->dev, r.pool, ctl, r.it, ctx->tune, count, cnt, r.grid, L.ovf_buf.p, L.stream));
-            HIP_TRY(k_event(L, r, timed));
+            HIP_TRY(wf_k_event(L, r, timed));
             // end-of-job drain: move the live slots to the front of the pool once at most half of the swept ones are alive (decided on the device)
-            if (r.drain && !r.bound && L.compact.capacity && r.p.samples_per_item == 1 && !p0.probe_n)
-                HIP_TRY(launch_wf_compact(r.pool, L.compact, ctl, r.it, r.n_shared, r.p.priv_items, L.stream));
+            if (r.drain && !lp.bound && L.compact.capacity && lp.p.samples_per_item == 1 && !p0.probe_n)
+                HIP_TRY(launch_wf_compact(r.pool, L.compact, ctl, r.it, lp.n_shared, lp.p.priv_items, L.stream));
             r.it++;
-            if (r.bound && r.it == r.bound) {                               // known-length job: all of it is enqueued; its verdict is read later
-                const uint32_t q = L.ring_next++ % RING;
-                HIP_TRY(snapshot(L, q));
-                L.verdicts.push_back({q, r.it - 1, r.n_shared});
+            if (lp.bound && r.it == lp.bound) {                             // known-length job: all of it is enqueued; its verdict is read later
+                const uint32_t q = L.ring_next++ % WF_RING;
+                HIP_TRY(wf_snapshot(L, q));
+                L.verdicts.push_back({q, r.it - 1, lp.n_shared});
                 r.done = true;
                 continue;
             }
-            if (!r.bound && r.it % CHECK == 0) {
-                mcpt_status ps = poll(L, r, r.issued - r.seen >= 2); if (ps != MCPT_OK) return ps;   // at most 2 checks (8 iterations) ahead
+            if (!lp.bound && r.it % WF_CHECK == 0) {
+                mcpt_status ps = wf_poll(L, r, plan, knobs.debug, r.issued - r.seen >= 2); if (ps != MCPT_OK) return ps;   // at most 2 checks (8 iterations) ahead
                 if (!r.done) {
-                    const uint32_t q = r.issued % RING;
-                    HIP_TRY(snapshot(L, q));
+                    const uint32_t q = r.issued % WF_RING;
+                    HIP_TRY(wf_snapshot(L, q));
                     r.snap_it[q] = r.it - 1;
                     r.issued++;
                 }
             }
-            if (!r.done) { mcpt_status ps = poll(L, r, false); if (ps != MCPT_OK) return ps; }
-            if (r.it > max_it) return fail(MCPT_ERR_HIP, "wavefront loop did not terminate within MCPT_WF_MAXIT iterations");
+            if (!r.done) { mcpt_status ps = wf_poll(L, r, plan, knobs.debug, false); if (ps != MCPT_OK) return ps; }
+            if (r.it > knobs.max_it) return fail(MCPT_ERR_HIP, "wavefront loop did not terminate within MCPT_WF_MAXIT iterations");
             if (!r.done) all_done = false;
         }
     }
     for (uint32_t k = 0; k < n_lanes; k++) {
-        if (!runs[k].active) continue;
+        if (!plan.lanes[k].active) continue;
         mcpt_ctx::WfLane& L = ctx->lanes[k];
         L.last_iterations = runs[k].it; L.last_timed = runs[k].kev / 3;
         ctx->total_iterations += runs[k].it;
@@ -874,7 +819,7 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, RenderParams& p0, float4* acc
 // The bracket of a timed call: an event pair of the ring around its stream work, and the call counts as a launch.  Durations of earlier calls: read what
 // has finished; wait only when the ring is full -- or when per-kernel timing is on, whose sampled kernel events belong to one call at a time.
 static mcpt_status timed_begin(mcpt_ctx* ctx) {
-    mcpt_status st = resolve_timing(ctx, ctx->time_kernels != 0 || ctx->timed_head - ctx->timed_tail >= mcpt_ctx::TIMED - 1); if (st != MCPT_OK) return st;
+    mcpt_status st = resolve_timing(ctx, ctx->knobs.time_kernels != 0 || ctx->timed_head - ctx->timed_tail >= mcpt_ctx::TIMED - 1); if (st != MCPT_OK) return st;
     HIP_TRY(hipEventRecord(ctx->ev0[ctx->timed_head % mcpt_ctx::TIMED], ctx->stream));
     return MCPT_OK;
 }
@@ -895,40 +840,11 @@ static mcpt_status render_call(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint3
     if (!ctx->use_wavefront && !ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the megakernel's traversal stack");
     mcpt_status st;
     if (timed) { st = timed_begin(ctx); if (st != MCPT_OK) return st; }
-    RenderParams p; std::memset(&p, 0, sizeof p);
-    p.spp = spp; p.first_sample = first_sample;
-    p.tiles_x = uint32_t((ctx->width + 7) / 8); p.tiles_y = uint32_t((ctx->height + 7) / 8);
-    p.tile_mod = tile_mod; p.tile_rem = tile_rem; p.tile_list = list;
-    {   const uint64_t all = list ? uint64_t(n_list) : film_tiles(ctx);
-        p.n_owned = all > tile_rem ? uint32_t((all - tile_rem + tile_mod - 1) / tile_mod) : 0u; }
-    if (p.n_owned == 0) return MCPT_OK;                                   // more shards than tiles: nothing for this one
-    const uint64_t tiles = p.n_owned;
-    uint32_t spi = ctx->opts.samples_per_item;
-    if (ctx->opts.flags & MCPT_FLAG_DETERMINISTIC) spi = spp;               // one lane owns a pixel for the whole call
-    else if (spi == 0) {
-        if (ctx->use_wavefront) {
-            // auto: one sample per item, longer ones only to keep the item count in the cursors' range.  Short items keep the end-of-render
-            // drain short (a slot works its item off sample after sample: 8-sample items cost 2.7 % at 1024 spp on the bench workload).
-            // Rounds 1-2 also grew the items when many pool slots would share a film pixel (more than 32 per pixel), for fear of the film's
-            // float atomics; measured in round 3 that rule was the problem, not the atomics: 64 x 64 x 4096 spp 88 -> 17 ms without it
-            // (4 096 slots per pixel), 16 x 16 x 16 384 spp 49 -> 9 ms, 256 x 256 x 1024 spp 60 -> 51 ms, and an interleaved-tile share of
-            // the bench job (1/8 of the pixels) 72 -> 58 ms -- the atomics execute at the memory side and 10^4 adders per address are fine.
-            spi = 1;
-            while (tiles * ((spp + spi - 1) / spi) > 0x3ffffffull && spi < spp) spi <<= 1;
-        } else {
-            // megakernel: long enough that per-item overheads vanish, short enough that the work balances across the chip
-            spi = 64;
-            const uint64_t want_items = 256ull * 16 * 16;
-            while (spi > 8 && tiles * ((spp + spi - 1) / spi) < want_items) spi >>= 1;
-        }
-        if (spi > spp) spi = spp;
-    }
-    if (spi > spp) spi = spp;
-    p.samples_per_item = spi; p.chunks = (spp + spi - 1) / spi;
-    p.atomic_accum = p.chunks > 1 ? 1u : 0u;
-    p.max_depth = ctx->opts.max_depth; p.flags = ctx->opts.flags; p.integrator = ctx->opts.integrator;
-    p.seed_lo = uint32_t(seed); p.seed_hi = uint32_t(seed >> 32);
-    if (tiles * p.chunks > 0x3ffffffull) return fail(MCPT_ERR_UNSUPPORTED, "launch too large: lower spp per call or raise samples_per_item");
+    RenderParams p;
+    const WfCall verdict = wf_plan_params(p, list ? uint64_t(n_list) : film_tiles(ctx), tile_mod, tile_rem, spp, first_sample, seed, ctx->opts, ctx->use_wavefront);
+    if (verdict == WfCall::Nothing) return MCPT_OK;                       // more shards than tiles: nothing for this one
+    if (verdict == WfCall::TooLarge) return fail(MCPT_ERR_UNSUPPORTED, "launch too large: lower spp per call or raise samples_per_item");
+    p.tiles_x = uint32_t((ctx->width + 7) / 8); p.tiles_y = uint32_t((ctx->height + 7) / 8); p.tile_list = list;
     if (ctx->use_wavefront) {
         st = render_wavefront(ctx, p, accum); if (st != MCPT_OK) return st;
     } else {
@@ -1792,7 +1708,7 @@ mcpt_status mcpt_probe_trace4(mcpt_ctx* ctx, uint32_t n, const double* origin, c
     if (n == 0) return MCPT_OK;
     mcpt_ctx::WfLane& L = ctx->lanes[0];
     const uint32_t P = uint32_t(((uint64_t(n) + WF_SHADE_BLOCK - 1) / WF_SHADE_BLOCK) * WF_SHADE_BLOCK);
-    if (P > ctx->pool_cap) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_probe_trace4: more rays than pool slots");
+    if (P > ctx->knobs.pool_cap) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_probe_trace4: more rays than pool slots");
     st = ensure_pool(ctx, L, P); if (st != MCPT_OK) return st;
     PathPool pool = L.pool;
     pool.P = P;

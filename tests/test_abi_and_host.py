@@ -159,6 +159,20 @@ def test_work_item_decode_divisions_are_exact(pkg, tmp_path):
     assert st != 0 and "film too large" in msg, (st, msg)
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_wavefront_plans_keep_the_kernels_invariants(tmp_path):
+    """What a render call's shape makes of it -- tile or sample split over the sub-pipelines, pool size, known length, private / shared work
+    items, film atomics, trace grid, and the environment knobs' clamps -- is pure host arithmetic (csrc/wf_plan.h): tests/wf_plan_check.cpp
+    plans a quarter of a million call shapes with the host compiler and checks on each that every (tile, sample) is rendered exactly once
+    and that the other invariants the kernels rely on hold."""
+    exe = str(tmp_path / "wf_plan_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                           os.path.join(ROOT, "tests", "wf_plan_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
+    assert int(out.stdout.split()[1]) >= 100000
+
+
 def test_reference_undefined_behaviour_becomes_error_codes(pkg):
     s = pkg.scenes.open_box(8, 8)
     # no emissive triangle: the reference indexes lights[-1] (Render.cpp:204-206)

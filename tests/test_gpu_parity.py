@@ -974,7 +974,7 @@ def test_frame_by_frame_equals_one_call(pkg):
 
 def test_small_jobs_share_the_trace_grid_without_changing_the_film(pkg, monkeypatch):
     """A job of about a path per trace lane (the one-sample frame of the reference's display loop, main.cpp:26-33) gives each sub-pipeline half of the
-    CUs for its trace launches (mcpt_api.cpp: Run::grid; DESIGN 6).  The grid is scheduling only: one sample per pixel, disjoint tile sets per
+    CUs for its trace launches (wf_plan.h: WfLanePlan::grid; DESIGN 6).  The grid is scheduling only: one sample per pixel, disjoint tile sets per
     sub-pipeline -> the film is the same bit for bit with the split on and off, at the bounded depth (a job of known length) and at the
     reference's unbounded depth (a polled job), and the next multi-sample call on the same context is untouched by it."""
     scene = pkg.scenes.cornell_box_small(200, 120)

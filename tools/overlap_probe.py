@@ -19,4 +19,4 @@ dt = time.perf_counter() - t0
 rays = sum(r.counters().rays for r in rs) - sum(0 for _ in rs)
 c = [r.counters() for r in rs]
 rays = sum(x.rays for x in c)
-print("contexts=%d pool_log2=%s  wall %.1f ms  %.1f Mray/s (incl. warm-up rays in counter: ignore ~1%%)" % (n, os.environ.get("MCPT_WF_POOL_LOG2", "22"), dt * 1e3, (rays * spp / (spp + 8)) / dt / 1e6))
+print("contexts=%d pool_log2=%s  wall %.1f ms  %.1f Mray/s (incl. warm-up rays in counter: ignore ~1%%)" % (n, os.environ.get("MCPT_WF_POOL_LOG2", "23"), dt * 1e3, (rays * spp / (spp + 8)) / dt / 1e6))
