@@ -134,7 +134,12 @@ typedef struct mcpt_scene_info {
     uint64_t device_bytes;      /* HBM held by the scene (nodes + triangle streams + textures + accumulator + path pools allocated so far) */
     double   bvh_build_ms, upload_ms;
     /* ABI 3: the wide tree the wavefront trace kernel walks (8 children per node; wide_width is always 8 since round 4, when the round-2 4-wide kernel was removed) */
-    uint32_t wide_width, wide_nodes, wide_depth, reserved0;
+    uint32_t wide_width, wide_nodes, wide_depth;
+    uint32_t bvh_builder;       /* who made the tree in use (this word was reserved0, always 0, so 0 keeps its meaning): 0 = the host SAH builder (always so for
+                                   mcpt_check_scene and for scenes of at most 2 triangles); 1 = the device PLOC builder of MCPT_FLAG_GPU_BVH_BUILD, its
+                                   tree kept; 2 = the device builder ran and its result was discarded -- the tree came out deeper than the context's
+                                   kernels can walk (63 levels, 255 on a wavefront-only context), or the builder gave up (more than 4096 rounds) --
+                                   and the host SAH tree is in use.  A clone reports its source's value. */
     uint64_t traversal_bytes;   /* wide nodes + triangle intersection records: what a ray's traversal can touch */
     double   centre[3];         /* device coordinates are relative to this point (the fp64 centre of the scene's bounding box) */
     uint64_t wide_tree_hash;    /* FNV-1a over the wide tree's records and the leaf order: equal hashes = the same tree and triangle order

@@ -5,6 +5,7 @@
 //   2. rocprim radix sort of (code, triangle) pairs -- the initial order of the clusters
 //   3. per round:        ploc_nn_kernel (nearest neighbour by merged surface area), ploc_merge_kernel (mutual pairs become inner
 //                        nodes), rocprim exclusive scan + ploc_compact_kernel (the surviving clusters), until one cluster is left
+//                        (more than 4096 rounds, or a round without a merge: the builder gives up and the caller builds on the host)
 //   4. host emission     depth-first: subtrees of <= MCPT_LEAF_MAX triangles become leaves, inner nodes are written in the host
 //                        builder's 64-B node format (both child boxes in the parent, child codes)
 //
@@ -96,7 +97,11 @@ __global__ void __launch_bounds__(256) ploc_nn_kernel(const Box6* __restrict__ c
         const int g = (int)i + o;
         if (o == 0 || g < 0 || g >= (int)nc) continue;
         const float a = half_area(merge(me, tile[threadIdx.x + PLOC_RADIUS + o]));
-        if (a < best) { best = a; bj = (uint32_t)g; }                 // ties: the lower index, on both sides of a pair -> mutual
+        // ties: the even-odd partner i ^ 1, else the lower index.  The lower index alone makes only the FIRST pair of a run of equal areas
+        // mutual (i picks i - 16, which picks its own lower neighbour): one merge per round, a chain for a tree.  With i ^ 1 such a run pairs
+        // up in one round, and some pair among the globally smallest areas is always mutual -- the lowest cluster i0 that has such a partner
+        // picks i0 ^ 1 (which picks it back) or its lowest partner j, and j picks i0 back unless (j, j ^ 1) is itself such a pair, then mutual.
+        if (a < best || (a == best && (uint32_t)g == (i ^ 1u))) { best = a; bj = (uint32_t)g; }
     }
     nn[i] = bj;
 }
@@ -174,9 +179,9 @@ bool gpu_build_ploc(const float* tri_boxes, uint32_t n, GpuBvh& out, std::string
         CK(hipGetLastError());
         uint32_t next = 0;
         CK(hipMemcpy(&next, d_next.p, 4, hipMemcpyDeviceToHost));
-        if (next >= nc) { err = "gpu_build_ploc: no pair merged (internal error)"; return false; }
+        if (next >= nc) { err = "gpu_build_ploc: no pair merged"; out.gave_up = true; return false; }
         nc = next;
-        if (++iterations > 4096) { err = "gpu_build_ploc: did not converge"; return false; }
+        if (++iterations > 4096) { err = "gpu_build_ploc: did not converge"; out.gave_up = true; return false; }
     }
     uint32_t made = 0, root_ref = 0;
     CK(hipMemcpy(&made, d_cnt.p, 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(&root_ref, d_cr0.p, 4, hipMemcpyDeviceToHost));

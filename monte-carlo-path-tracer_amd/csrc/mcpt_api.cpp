@@ -523,7 +523,12 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
         st = build_host_scene(scene, hs, err, [&](const float* boxes, uint32_t n, std::vector<f4h>& nodes, std::vector<int>& order, uint32_t& depth,
                                                    uint32_t& max_leaf, std::string& berr) {
             GpuBvh g;
-            if (!gpu_build_ploc(boxes, n, g, berr)) return false;
+            if (!gpu_build_ploc(boxes, n, g, berr)) {
+                if (!g.gave_up) return false;
+                if (std::getenv("MCPT_BUILD_DEBUG")) fprintf(stderr, "[build] %s: building on the host\n", berr.c_str());
+                nodes.clear(); order.clear(); berr.clear();              // gave up: no tree, no error -- the host builder takes over (bvh_builder = 2)
+                return true;
+            }
             nodes.swap(g.nodes); order.assign(g.order.begin(), g.order.end()); depth = g.depth; max_leaf = g.max_leaf;
             return true;
         }, env_u32("MCPT_HOST_COLLAPSE", 0) ? Collapse8Fn(nullptr) : Collapse8Fn(gpu_collapse_bvh8));
@@ -557,7 +562,7 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
     mcpt_scene_info& in = c->info;
     in.n_tris = uint32_t(d.n_tris); in.n_lights = uint32_t(d.n_lights); in.n_nodes = uint32_t(d.n_nodes);
     in.bvh_depth = hs.bvh_depth; in.max_leaf = hs.max_leaf; in.width = uint32_t(c->width); in.height = uint32_t(c->height);
-    in.bvh_build_ms = hs.bvh_build_ms;
+    in.bvh_build_ms = hs.bvh_build_ms; in.bvh_builder = hs.bvh_builder;
     fill_wide_info(in, hs);
     c->mt_mats.assign(scene->materials, scene->materials + scene->n_materials); c->mt_tex = hs.tex_info; c->mt_faces = hs.mat_faces;
     if ((st = finish_ctx(c)) != MCPT_OK) return st;

@@ -682,11 +682,13 @@ mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::stri
         for (uint32_t f = 0; f < nf; f++)
             for (int a = 0; a < 3; a++) { boxes[6 * size_t(f) + a] = round_down(bt[f].lo[a], 0.f); boxes[6 * size_t(f) + 3 + a] = round_up(bt[f].hi[a], 0.f); }
         if (!custom_bvh(boxes.data(), nf, out.nodes, order, out.bvh_depth, out.max_leaf, err)) return MCPT_ERR_HIP;
-        if (order.size() != nf || out.nodes.empty() || out.nodes.size() % 4 != 0) { err = "custom BVH builder returned inconsistent arrays"; return MCPT_ERR_HIP; }
-        // A Morton-code tree over many coincident centroids can come out deeper than the binary-tree kernels' stack: such a scene
-        // is rebuilt by the depth-capped host builder instead of being refused.
-        built = out.bvh_depth <= uint32_t(MCPT_STACK_DEPTH - 1) || (out.allow_deep_binary && out.bvh_depth <= 255u);
+        if (!out.nodes.empty() && (order.size() != nf || out.nodes.size() % 4 != 0)) { err = "custom BVH builder returned inconsistent arrays"; return MCPT_ERR_HIP; }
+        // An agglomerative tree over nested boxes (every merge with a smaller box gives the same box: a chain) can come out deeper than the
+        // binary-tree kernels' stack, and the builder gives up (no nodes) when its rounds do not converge: such a scene is rebuilt by the
+        // depth-capped host builder instead of being refused.
+        built = !out.nodes.empty() && (out.bvh_depth <= uint32_t(MCPT_STACK_DEPTH - 1) || (out.allow_deep_binary && out.bvh_depth <= 255u));
         if (!built) { out.nodes.clear(); order.clear(); }
+        out.bvh_builder = built ? 1u : 2u;
     }
     if (!built) {
         Builder b(bt, out.nodes);

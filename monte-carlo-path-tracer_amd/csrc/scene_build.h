@@ -30,6 +30,7 @@ struct HostScene {
     DevCamera cam;
     double centre[3] = {0.0, 0.0, 0.0};   // the point every coordinate above is relative to (device_scene.h: DevScene::centre)
     uint32_t bvh_depth = 0, max_leaf = 0, bvh8_depth = 0;
+    uint32_t bvh_builder = 0;        // out: mcpt_scene_info::bvh_builder (0 host SAH, 1 custom builder's tree kept, 2 custom builder's result discarded)
     std::vector<int> subtree_begin;  // binary nodes: first index of every depth-first-numbered subtree below the breadth-first top levels (ascending)
     bool reference_tie_order = false; // in: MCPT_FLAG_REFERENCE_TIE_ORDER -- the tie rank of a triangle (low 28 bits of tri_isect[3 i].w) is its position in the
                                      //     reference's BVH::triangles after BVH::build instead of its position in this library's leaf order
@@ -41,7 +42,8 @@ struct HostScene {
 };
 
 // Optional replacement for the host SAH builder (bvh_gpu.hip): gets one fp32 box per face (lo xyz, hi xyz, rounded outward) and
-// fills the binary tree in the host builder's node layout, the leaf order, the depth in inner levels and the largest leaf.
+// fills the binary tree in the host builder's node layout, the leaf order, the depth in inner levels and the largest leaf.  false = an error
+// (build_host_scene fails with it); true with `nodes` left empty = the builder gave up on this input and the host builder takes over.
 using BvhBuildFn = std::function<bool(const float* boxes, uint32_t n, std::vector<f4h>& nodes, std::vector<int>& order, uint32_t& depth,
                                       uint32_t& max_leaf, std::string& err)>;
 

@@ -1,5 +1,6 @@
 """The one copy of what the per-feature suites share: the bitwise view behind every "bit for bit" assertion, live-scene scaffolding (films, rays,
-the moved sphere), the reprojection suites' synthetic inputs and comparison, and the drivers of the C++ façade programs and mcpt_cli.
+the moved sphere), the reprojection suites' synthetic inputs and comparison, the drivers of the C++ façade programs and mcpt_cli, and the
+brute-force ray tracer the tree-builder suites hold the kernels to.
 
 A plain module, imported like tests/reproject_ref.py.  Where the suites' copies differed in a default or in the order of their arguments the
 function here takes the argument explicitly and every call site passes the value it always used.
@@ -161,3 +162,33 @@ def turntable_frames(prefix, n=3):
             out.append(fh.read())
         assert out[-1][:8] == b"\x89PNG\r\n\x1a\n"
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------ brute force
+def brute_force_trace(scene, origin, direction, dtype=np.float64, t1=1e-4, chunk=None):
+    """Closest hit of every ray against EVERY triangle of `scene`, Moeller-Trumbore with the acceptance rule of tri_accept_closest (pt_device.h):
+    |det| >= 1e-5, t1 <= t, u >= 0, v >= 0, 1 - u - v >= 0; among equal t the lowest face index.  (t, face or -1, u, v).  dtype=np.float32 works on
+    the records the device holds (first corner and ray origin less the fp64 centre of the used vertices, edges from the world coordinates, all
+    rounded to fp32) in fp32 arithmetic: what any fp32 kernel can be asked to agree with."""
+    p = scene.vertex[scene.face[:, :, 0]].astype(np.float64)
+    used = p.reshape(-1, 3); ctr = 0.5 * used.min(0) + 0.5 * used.max(0)
+    T = np.dtype(dtype).type
+    v0 = (p[:, 0] - ctr).astype(dtype); e1 = (p[:, 1] - p[:, 0]).astype(dtype); e2 = (p[:, 2] - p[:, 0]).astype(dtype)
+    o = (np.asarray(origin, np.float64).reshape(-1, 3) - ctr).astype(dtype); d = np.asarray(direction, np.float64).reshape(-1, 3).astype(dtype)
+    n = o.shape[0]
+    chunk = chunk or max(1, 2_000_000 // max(1, v0.shape[0]))
+    t_out = np.full(n, np.inf, dtype); f_out = np.full(n, -1, np.int32); u_out = np.zeros(n, dtype); v_out = np.zeros(n, dtype)
+    for b in range(0, n, chunk):
+        oo, dd = o[b:b + chunk, None, :], d[b:b + chunk, None, :]
+        h = np.cross(dd, e2[None]); a = (e1[None] * h).sum(-1)
+        s = oo - v0[None]; q = np.cross(s, e1[None])
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            inv = T(1.0) / a
+            u = (s * h).sum(-1) * inv; v = (dd * q).sum(-1) * inv; t = (e2[None] * q).sum(-1) * inv
+            ok = (np.abs(a) >= T(1e-5)) & (t >= T(t1)) & (u >= 0) & (v >= 0) & (T(1.0) - u - v >= 0)
+        t = np.where(ok, t, np.inf).astype(dtype)
+        k = np.argmin(t, 1)                                                  # first minimum: the lowest face among exact ties
+        rows = np.arange(t.shape[0]); tt = t[rows, k]; hit = np.isfinite(tt)
+        t_out[b:b + chunk] = tt; f_out[b:b + chunk] = np.where(hit, k, -1)
+        u_out[b:b + chunk] = np.where(hit, u[rows, k], 0); v_out[b:b + chunk] = np.where(hit, v[rows, k], 0)
+    return t_out, f_out, u_out, v_out

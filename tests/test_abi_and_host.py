@@ -83,6 +83,17 @@ def test_struct_layout_matches_the_header(pkg, name):
     assert got["abi"] == 4
 
 
+def test_bvh_builder_took_the_place_of_a_reserved_word(pkg):
+    """mcpt_scene_info.bvh_builder is the former reserved0: same offset (68) and size, same struct size, ABI still 4 -- and 0, what old readers saw
+    there, still means the host builder, which is all mcpt_check_scene ever runs."""
+    f = pkg.SceneInfo.bvh_builder
+    assert (f.offset, f.size) == (68, 4) and pkg.SceneInfo.wide_depth.offset == 64 and pkg.SceneInfo.traversal_bytes.offset == 72
+    assert C.sizeof(pkg.SceneInfo) == 112 and not hasattr(pkg.SceneInfo, "reserved0")
+    scene = pkg.scenes.open_box(8, 8)
+    st, info, msg = pkg.check_scene(scene)
+    assert st == 0 and info.bvh_builder == 0 and info.n_tris == scene.n_faces, msg
+
+
 def test_no_cpu_fallback(pkg):
     """Without a HIP device mcpt_create must fail loudly (MCPT_ERR_NO_DEVICE) -- there is no CPU path to fall back to."""
     import torch

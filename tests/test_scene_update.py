@@ -7,11 +7,12 @@ bit for bit where both round about the same centre, within the device-builder te
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 
-from tests import kit
+from tests import kit, ploc_ref
 from tests.kit import bits, render_film
 
 NEW_SYMBOLS = ["mcpt_set_camera", "mcpt_update_vertices", "mcpt_get_update_info", "mcpt_probe_validate_trees"]
@@ -60,8 +61,8 @@ def _tri_t64(scene, face, o, d):
     return float(e2 @ qv / det)
 
 
-def _compare_traces(pkg, R, F, moved, probe="probe_trace4", exact=True):
-    o, d = _rays(pkg, F, moved)
+def _compare_traces(pkg, R, F, moved, probe="probe_trace4", exact=True, rays=None):
+    o, d = rays or _rays(pkg, F, moved)
     tr, fr, _, _ = getattr(R, probe)(o, d); tf, ff, _, _ = getattr(F, probe)(o, d)
     assert (ff >= 0).mean() > 0.3
     hit = ff >= 0
@@ -369,3 +370,38 @@ def test_refit_is_faster_than_the_rebuild_it_replaces(pkg):
         fi.n_tris, refit, min(ms[3:]), max(ms[3:]), fi.bvh_build_ms, fi.upload_ms, rebuild, refit / rebuild, ratio))
     assert np.isfinite(a).all() and abs(a[..., :3].mean() - b[..., :3].mean()) <= 0.05 * b[..., :3].mean()
     assert refit > 0 and refit < rebuild
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("maker,args", [("lattice_soup", (3,)), ("lattice_soup", (9,)), ("lattice_soup", (257,)), ("coincident", (300,)), ("shells", (150, 1.2))])
+def test_refit_of_small_tied_and_deep_device_built_trees(pkg, maker, args):
+    """The refit on device-BUILT trees at the sizes no other scene has (tests/ploc_ref.py makes them): one-node levels and a single wide record
+    (3 and 9 triangles), a block edge (257), a run of exact ties (300 copies) and a chain 148 deep, kept by this wavefront context.  An update
+    with the creation vertices changes no traced bit; after every vertex is scaled by 1.25 about the centre the context equals a fresh one of the
+    scaled scene by _compare_traces' criteria for contexts that round on their own."""
+    scene = getattr(ploc_ref, maker)(pkg, *args)
+    fl = pkg.FLAG_DYNAMIC | pkg.FLAG_GPU_BVH_BUILD
+    os.environ["MCPT_VALIDATE_BVH"] = "1"
+    try:
+        R = pkg.Renderer(scene, flags=fl)
+    finally:
+        os.environ.pop("MCPT_VALIDATE_BVH", None)
+    assert R.info().bvh_builder == 1
+    o, d = ploc_ref.interior_rays(scene, 1500, seed=9)[:2]
+    before = R.probe_trace4(o, d)
+    R.update_vertices(scene.vertex); R.validate_trees()
+    after = R.probe_trace4(o, d)
+    assert (before[1] >= 0).mean() > 0.3
+    for a, b in zip(before, after):
+        assert np.array_equal(bits(a), bits(b))
+    lo, hi = kit.used_bounds(scene); c = 0.5 * lo + 0.5 * hi
+    moved = kit.with_arrays(pkg, scene, vertex=(scene.vertex - c) * 1.25 + c)
+    R.update_vertices(moved.vertex); R.validate_trees()
+    os.environ["MCPT_VALIDATE_BVH"] = "1"
+    try:
+        F = pkg.Renderer(moved, flags=fl)
+    finally:
+        os.environ.pop("MCPT_VALIDATE_BVH", None)
+    assert F.info().bvh_builder == 1
+    _compare_traces(pkg, R, F, moved, "probe_trace4", exact=False, rays=ploc_ref.interior_rays(moved, 1500, seed=10)[:2])
+    R.close(); F.close()
