@@ -714,6 +714,10 @@ int oracle_sample_light(void* h, const double* p3, const float* xi, int n, doubl
     out14[6] = ls.pdf; out14[7] = ls.ray.t2; put3(out14 + 8, ls.ray.start); put3(out14 + 11, ls.ray.direction);
     return r.pos;
 }
+int oracle_sample_light_tri(void* h, const double* p3, const float* xi, int n) {   // the triangle (= face) that oracle_sample_light sampled
+    Scene* s = static_cast<Scene*>(h); Hit info; info.point = P3(p3); Rng r = seq_rng(xi, n);
+    return sample_light_point(*s, info, r, 0, true).tri;
+}
 int oracle_trace_path(void* h, const double* o, const double* d, const float* xi, int n, float* L3) {
     Scene* s = static_cast<Scene*>(h); Rng r = seq_rng(xi, n); Counters c;
     Ray ray; ray.start = P3(o); ray.direction = P3(d);

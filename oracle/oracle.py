@@ -86,6 +86,7 @@ class Oracle:
             L.oracle_clamp01.argtypes = [C.c_float]; L.oracle_clamp01.restype = C.c_double
             L.oracle_texture_get_color.argtypes = [C.c_int, C.c_int, vp, C.c_double, C.c_double, vp]
             L.oracle_sample_light.argtypes = [vp, vp, vp, C.c_int, vp]
+            L.oracle_sample_light_tri.argtypes = [vp, vp, vp, C.c_int]
             L.oracle_trace_path.argtypes = [vp, vp, vp, vp, C.c_int, vp]
             L.oracle_trace_path_recursive.argtypes = [vp, vp, vp, vp, C.c_int, vp]
             L.oracle_trace_pixel.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp]
@@ -192,6 +193,9 @@ class Oracle:
 
     def sample_light(self, p, xi):
         xi = _f(xi); out = np.zeros(14); c = self.L.oracle_sample_light(self.h, _p(_d3(p)), _p(xi), xi.size, _p(out)); return out, c
+
+    def sample_light_tri(self, p, xi):
+        xi = _f(xi); return self.L.oracle_sample_light_tri(self.h, _p(_d3(p)), _p(xi), xi.size)
 
     def trace_path(self, o, d, xi, recursive=False):
         xi = _f(xi); L3 = np.zeros(3, np.float32)

@@ -466,6 +466,15 @@ def test_probe_bsdf_vs_reference(pkg, kats):
     assert lo.sum() > 200 and hi.sum() > 100
     assert np.allclose(out[lo, 7:11], smp[lo, 3:7], rtol=2e-3, atol=1e-5)
     assert np.allclose(out[hi, 7:11], smp[hi, 3:7], rtol=2e-2, atol=1e-4)
+    # Kd = Ks = 0 (kind 3): the reference reads uninitialised lobe weights there (SURVEY A-12), so its recorded answers say nothing; this build defines
+    # the weights as 0 -- the path ends.  Sample pdf and evaluation pdf exactly 0, fx and f finite.
+    blk = k["bsdf_kind"] == 3
+    assert blk.sum() > 300
+    r = pkg.Renderer(pkg.scenes.open_box(8, 8))
+    ob = r.probe_bsdf(k["bsdf_n"][blk], k["bsdf_wi"][blk], k["bsdf_kd"][blk], k["bsdf_ks"][blk], k["bsdf_ns"][blk], k["bsdf_wo"][blk], k["bsdf_xi"][blk])
+    r.close()
+    assert (ob[:, 10] == 0).all() and (ob[:, 3] == 0).all() and (ob[:, 11] == 0).all()
+    assert np.isfinite(ob[:, 0:3]).all() and np.isfinite(ob[:, 7:10]).all()
 
 
 def test_probe_texture_vs_reference(pkg, kats):
