@@ -278,7 +278,7 @@ mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* camera);
  *  - Tie ranks, leaf order, lobe classes, materials, textures and the light list's membership and order are those of creation; with
  *    MCPT_FLAG_REFERENCE_TIE_ORDER the ranks are the creation geometry's.
  *  - Topology and octant slots are kept, so a large deformation makes traversal slower, never wrong; mcpt_update_info::wide_area_ratio tells
- *    the caller when a fresh mcpt_create is due.
+ *    the caller when mcpt_rebuild_trees (below) is due: new trees for the moved geometry in this context, everything else kept.
  *  - mcpt_clone_to_device of a dynamic context gives a dynamic context.  Works with either builder, with deep device-built binary trees and
  *    with both integrators. */
 mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal);
@@ -286,7 +286,8 @@ mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n
 typedef struct mcpt_update_info {
     uint32_t struct_size, updates;      /* mcpt_update_vertices / mcpt_update_transforms (+ _reproject) calls on this context so far */
     double   last_update_ms;            /* device time of the last one, first to last operation on the stream (HIP events) */
-    double   wide_area_ratio;           /* sum of the child-box areas of the 8-wide tree now / at creation (dequantised boxes; 1.0 before any update) */
+    double   wide_area_ratio;           /* sum of the child-box areas of the 8-wide tree now / when it was built, by mcpt_create or by the last
+                                           mcpt_rebuild_trees (dequantised boxes; 1.0 before any update and right after a rebuild) */
     uint32_t reserved[4];
 } mcpt_update_info;
 mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out);   /* synchronises */
@@ -462,6 +463,46 @@ typedef struct mcpt_transform_info {
     uint32_t reserved[4];
 } mcpt_transform_info;
 mcpt_status mcpt_get_transform_info(mcpt_ctx* ctx, mcpt_transform_info* out);   /* synchronises */
+
+/* ---- live scenes: new trees for the geometry as it is now -------------------------------------------------------------- */
+/* mcpt_update_vertices and mcpt_update_transforms refit: after a large deformation the trees are sound and slow.  mcpt_rebuild_trees builds BOTH
+ * trees (binary and 8-wide) anew for the context's current vertices -- whatever the last update or transform wrote -- and keeps everything else.
+ *  - Needs MCPT_FLAG_DYNAMIC (else MCPT_ERR_UNSUPPORTED).  Works with both integrators and with MCPT_PIPELINE=mega.  `builder` chooses the host
+ *    binned-SAH builder or the device PLOC builder; the device builder has mcpt_create's fallbacks (gave up, or too deep for the context's
+ *    kernels: the host builder's tree, bvh_builder = 2) and mcpt_create's depth rule: a wavefront-only context may keep a deep device tree.
+ *  - SYNCHRONOUS, and ordered like every call: it drains the context first, so renders enqueued before it walked the old trees; when it returns
+ *    the new ones are in place.
+ *  - Coordinates stay relative to the CREATION-time centre: mcpt_scene_info::centre and the camera constants do not change.  The builders see
+ *    the faces in Model::face order with the bounds mcpt_create would form for them, so whenever a fresh mcpt_create of the same geometry would
+ *    choose the same centre the rebuilt context IS that fresh context: wide_tree_hash, the leaf order, every triangle stream bit for bit, the
+ *    deterministic film.
+ *  - A triangle's tie rank becomes its new leaf position, as mcpt_create gives it; with MCPT_FLAG_REFERENCE_TIE_ORDER every triangle keeps the
+ *    rank it has (the creation geometry's, as mcpt_update_vertices documents).
+ *  - KEPT, because the scene looks the same from every pixel: the film or a bound accumulator, the counters, the stream binding, the camera, the
+ *    feature buffers and the denoised film, the adaptive tile error, the reprojection buffers, the vertex groups with their rest pose and R_g,
+ *    the materials, the textures, and the light list's membership and order (only the lights' leaf-order triangle index is renumbered).
+ *  - Afterwards mcpt_update_info::wide_area_ratio is 1.0 (its base is the new tree) and `updates` is unchanged; mcpt_scene_info follows the new
+ *    trees: n_nodes, bvh_depth, max_leaf, wide_nodes, wide_depth, traversal_bytes, wide_tree_hash, bvh_builder, and device_bytes counts what is
+ *    allocated now; bvh_build_ms and upload_ms stay creation's.
+ *  - A refusal changes NOTHING, not a buffer and not a field of an info: MCPT_ERR_INVALID_ARG for a NULL context, a struct_size that is not this
+ *    library's or an unknown builder; MCPT_ERR_BVH_DEPTH where mcpt_create would answer it for the new tree (binary depth; the 512-MB cap of the
+ *    traversal stack's overflow area, which is sized from the new wide_depth before anything walks the tree); MCPT_ERR_HIP for an allocation or
+ *    builder failure.  Needs room for a second copy of the triangle streams while it runs.
+ *  - A clone taken afterwards is a clone of the rebuilt context; clones taken earlier keep their own trees. */
+#define MCPT_REBUILD_SAME   0u   /* the builder the context was created with (MCPT_FLAG_GPU_BVH_BUILD or not) */
+#define MCPT_REBUILD_HOST   1u   /* host binned-SAH builder */
+#define MCPT_REBUILD_DEVICE 2u   /* device PLOC builder, with create's fallbacks (gave up / too deep -> host, bvh_builder = 2) */
+typedef struct mcpt_rebuild_opts { uint32_t struct_size, builder; uint32_t reserved[4]; } mcpt_rebuild_opts;
+typedef struct mcpt_rebuild_info {
+    uint32_t struct_size, rebuilds;     /* successful mcpt_rebuild_trees calls on this context */
+    double   last_ms;                   /* wall time of the last call, entry to return */
+    double   last_build_ms;             /* its tree construction (what bvh_build_ms is for mcpt_create) */
+    double   last_device_ms;            /* HIP events: the bounds kernel + the permutation and light kernels */
+    double   area_ratio_before;         /* wide_area_ratio just before the last call */
+    uint32_t reserved[4];
+} mcpt_rebuild_info;
+mcpt_status mcpt_rebuild_trees(mcpt_ctx* ctx, const mcpt_rebuild_opts* opts /* NULL = defaults */);
+mcpt_status mcpt_get_rebuild_info(mcpt_ctx* ctx, mcpt_rebuild_info* out);
 
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that

@@ -17,6 +17,8 @@ from typing import Optional
 import numpy as np
 
 from . import scenes  # noqa: F401  (re-export)
+# mcpt_rebuild_trees' options, info and builder constants; tests/test_rebuild.py holds their layout to the header
+from .rebuild_abi import REBUILD_DEVICE, REBUILD_HOST, REBUILD_SAME, RebuildInfo, RebuildOpts  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmcpt_hip.so")
@@ -278,6 +280,8 @@ def load_library() -> C.CDLL:
         "mcpt_update_transforms": [vp, vp, C.c_uint32],
         "mcpt_update_transforms_reproject": [vp, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
         "mcpt_get_transform_info": [vp, P(TransformInfo)],
+        "mcpt_rebuild_trees": [vp, P(RebuildOpts)],
+        "mcpt_get_rebuild_info": [vp, P(RebuildInfo)],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -304,6 +308,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_update_vertices_reproject", "mcpt_probe_first_hits", "mcpt_probe_reproject_motion",
     "mcpt_update_materials", "mcpt_update_texture", "mcpt_get_material_info", "mcpt_probe_lights", "mcpt_probe_face_classes",
     "mcpt_set_vertex_groups", "mcpt_update_transforms", "mcpt_update_transforms_reproject", "mcpt_get_transform_info",
+    "mcpt_rebuild_trees", "mcpt_get_rebuild_info",
 ]
 
 
@@ -590,6 +595,19 @@ class Renderer:
     def update_info(self) -> UpdateInfo:
         i = UpdateInfo()
         self._check(self.lib.mcpt_get_update_info(self.ctx, C.byref(i)))
+        return i
+
+    # ---- new trees for the geometry as it is now
+    def rebuild(self, builder: int = REBUILD_SAME):
+        """Both trees built anew for the context's current vertices, in place; film, counters, features, groups, materials and lights stay.
+        builder: REBUILD_SAME (the one the context was created with), REBUILD_HOST or REBUILD_DEVICE.  Needs FLAG_DYNAMIC.  Synchronous."""
+        o = RebuildOpts()
+        o.struct_size = C.sizeof(RebuildOpts); o.builder = int(builder)
+        self._check(self.lib.mcpt_rebuild_trees(self.ctx, C.byref(o)))
+
+    def rebuild_info(self) -> RebuildInfo:
+        i = RebuildInfo()
+        self._check(self.lib.mcpt_get_rebuild_info(self.ctx, C.byref(i)))
         return i
 
     def validate_trees(self):

@@ -9,6 +9,8 @@
 #include "denoise.h"
 #include "adaptive.h"
 #include "refit.h"
+#include "rebuild.h"
+#include "rebuild_plan.h"
 #include "transform.h"
 #include "reproject.h"
 #include "materials.h"
@@ -200,6 +202,8 @@ struct mcpt_ctx {
     Staging<double> rf_stage;                               // the vertices, then the normals
     Stopwatch rf_watch;
     uint32_t rf_updates = 0; double rf_area0 = 0.0;
+    // Tree rebuilds (rebuild.hip): what mcpt_get_rebuild_info reports.  The call owns its temporaries; nothing of it stays allocated.
+    uint32_t rb_rebuilds = 0; double rb_last_ms = 0.0, rb_last_build_ms = 0.0, rb_last_device_ms = 0.0, rb_area_before = 1.0;
     // Rigid parts (transform.hip), allocated by mcpt_set_vertex_groups and counted in device_bytes: the rest pose (rf_vtx's and
     // rf_nrm's sizes), a group id per vertex and per normal, the table of XF_RECORD doubles per group and its pinned staging.  On the host per
     // group R_g, the largest |coordinate| among its vertices that a face uses (what mcpt_update_transforms validates against).
@@ -337,6 +341,14 @@ struct Scratch {
 
 }  // namespace
 
+// The traversal-stack overflow area one sub-pipeline needs under a wide tree of depth `wide_depth`, from the context's trace grid; host arithmetic
+// only.  mcpt_create and mcpt_rebuild_trees size (and refuse) by it.
+static mcpt_status overflow_bytes(const mcpt_ctx* c, uint32_t wide_depth, size_t& out) {
+    out = size_t(c->trace_grid) * wf_trace_block_threads() * wf_trace_overflow_bytes_per_lane(wide_depth);
+    if (out > (size_t(512) << 20)) return fail(MCPT_ERR_BVH_DEPTH, "wide BVH of depth " + std::to_string(wide_depth) + " needs a traversal-stack overflow area of " + std::to_string(out >> 20) + " MB per sub-pipeline: build the tree with the host builder (no MCPT_FLAG_GPU_BVH_BUILD)");
+    return MCPT_OK;
+}
+
 // Everything of a context that is not the scene: streams, events, film, counters, the wavefront sub-pipelines, and the device pointers of
 // c->dev (the scene streams c->nodes ... c->texels are on the device already: uploaded by mcpt_create or copied by mcpt_clone_to_device).
 static mcpt_status finish_ctx(mcpt_ctx* c) {
@@ -381,8 +393,8 @@ static mcpt_status finish_ctx(mcpt_ctx* c) {
                 HIP_TRY(hipStreamCreateWithFlags(L.stream.out(), hipStreamNonBlocking));
                 // the global overflow area of the traversal stack is sized from the wide tree's depth (2 x depth + 3 entries of 8 B per trace lane): a
                 // pathologically deep device-built tree (depth in the hundreds) would ask for a GB per sub-pipeline -- refuse instead of allocating it
-                const size_t ovf_bytes = size_t(c->trace_grid) * wf_trace_block_threads() * wf_trace_overflow_bytes_per_lane(c->wide_depth);
-                if (ovf_bytes > (size_t(512) << 20)) return fail(MCPT_ERR_BVH_DEPTH, "wide BVH of depth " + std::to_string(c->wide_depth) + " needs a traversal-stack overflow area of " + std::to_string(ovf_bytes >> 20) + " MB per sub-pipeline: build the tree with the host builder (no MCPT_FLAG_GPU_BVH_BUILD)");
+                size_t ovf_bytes = 0;
+                const mcpt_status os = overflow_bytes(c, c->wide_depth, ovf_bytes); if (os != MCPT_OK) return os;
                 HIP_TRY(L.ovf_buf.alloc(ovf_bytes / sizeof(int)));
             }
         }
@@ -395,16 +407,37 @@ static mcpt_status finish_ctx(mcpt_ctx* c) {
     return MCPT_OK;
 }
 
-static void fill_wide_info(mcpt_scene_info& in, const HostScene& hs) {
+// The wide tree's part of the info: hs.nodes8 and its depth, the leaf order `tri_face` (n_tris entries), the tri_isect stream's 3 n_tris + 3 records.
+static void fill_tree_info(mcpt_scene_info& in, const HostScene& hs, const int32_t* tri_face, size_t n_tris) {
     in.wide_width = 8; in.wide_nodes = uint32_t(hs.nodes8.size() / 5);
     in.wide_depth = hs.bvh8_depth;
-    in.traversal_bytes = (hs.nodes8.size() + hs.tri_isect.size()) * sizeof(f4h);
-    for (int a = 0; a < 3; a++) in.centre[a] = hs.centre[a];
+    in.traversal_bytes = (hs.nodes8.size() + 3 * n_tris + 3) * sizeof(f4h);
     uint64_t h = 1469598103934665603ull;                                  // FNV-1a, 4 bytes at a time
     auto mix = [&](const void* p, size_t bytes) { const uint32_t* w = static_cast<const uint32_t*>(p); for (size_t i = 0; i < bytes / 4; i++) { h ^= w[i]; h *= 1099511628211ull; } };
-    mix(hs.nodes8.data(), hs.nodes8.size() * sizeof(f4h)); mix(hs.tri_face.data(), hs.tri_face.size() * 4);
+    mix(hs.nodes8.data(), hs.nodes8.size() * sizeof(f4h)); mix(tri_face, n_tris * 4);
     in.wide_tree_hash = h;
 }
+static void fill_wide_info(mcpt_scene_info& in, const HostScene& hs) {
+    fill_tree_info(in, hs, hs.tri_face.data(), hs.tri_face.size());
+    for (int a = 0; a < 3; a++) in.centre[a] = hs.centre[a];
+}
+
+// The device builders mcpt_create and mcpt_rebuild_trees hand to build_trees: PLOC on the current device (gave up: no tree, no error -- the host
+// builder takes over, bvh_builder = 2) and the device collapse (MCPT_HOST_COLLAPSE=1: the host's).
+static BvhBuildFn device_bvh_builder() {
+    return [](const float* boxes, uint32_t n, std::vector<f4h>& nodes, std::vector<int>& order, uint32_t& depth, uint32_t& max_leaf, std::string& berr) {
+        GpuBvh g;
+        if (!gpu_build_ploc(boxes, n, g, berr)) {
+            if (!g.gave_up) return false;
+            if (std::getenv("MCPT_BUILD_DEBUG")) fprintf(stderr, "[build] %s: building on the host\n", berr.c_str());
+            nodes.clear(); order.clear(); berr.clear();              // gave up: no tree, no error -- the host builder takes over (bvh_builder = 2)
+            return true;
+        }
+        nodes.swap(g.nodes); order.assign(g.order.begin(), g.order.end()); depth = g.depth; max_leaf = g.max_leaf;
+        return true;
+    };
+}
+static Collapse8Fn device_collapse8() { return env_u32("MCPT_HOST_COLLAPSE", 0) ? Collapse8Fn(nullptr) : Collapse8Fn(gpu_collapse_bvh8); }
 
 
 // ------------------------------------------------------------------------------------------------ live scenes: set-up
@@ -520,18 +553,7 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
         // cross-check kernels (megakernel, recursive integrator, mcpt_probe_trace) walk the binary tree; the wavefront pipeline walks
         // the wide collapse of it, whose stack is sized from its own depth -- so a wavefront-only context keeps the deep tree.
         hs.allow_deep_binary = use_wavefront;
-        st = build_host_scene(scene, hs, err, [&](const float* boxes, uint32_t n, std::vector<f4h>& nodes, std::vector<int>& order, uint32_t& depth,
-                                                   uint32_t& max_leaf, std::string& berr) {
-            GpuBvh g;
-            if (!gpu_build_ploc(boxes, n, g, berr)) {
-                if (!g.gave_up) return false;
-                if (std::getenv("MCPT_BUILD_DEBUG")) fprintf(stderr, "[build] %s: building on the host\n", berr.c_str());
-                nodes.clear(); order.clear(); berr.clear();              // gave up: no tree, no error -- the host builder takes over (bvh_builder = 2)
-                return true;
-            }
-            nodes.swap(g.nodes); order.assign(g.order.begin(), g.order.end()); depth = g.depth; max_leaf = g.max_leaf;
-            return true;
-        }, env_u32("MCPT_HOST_COLLAPSE", 0) ? Collapse8Fn(nullptr) : Collapse8Fn(gpu_collapse_bvh8));
+        st = build_host_scene(scene, hs, err, device_bvh_builder(), device_collapse8());
         if (st != MCPT_OK) return fail(st, err);
         if (env_u32("MCPT_VALIDATE_BVH", 0)) { const std::string bad = validate_wide_bvh(hs); if (!bad.empty()) return fail(MCPT_ERR_HIP, "device-built BVH failed validation: " + bad); }
     } else {
@@ -1335,6 +1357,131 @@ mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
         st = rf_read_area(ctx, a); if (st != MCPT_OK) return st;
         out->wide_area_ratio = ctx->rf_area0 > 0.0 ? a / ctx->rf_area0 : 1.0;
     }
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ tree rebuild
+// New trees for the vertices the context holds, everything else kept.  Every step that can fail works on temporaries -- the builders' input and
+// output, the new node buffers, the permuted streams, the renumbered lights, the level tables, a larger overflow area -- and the last block swaps
+// them in; a refusal returns before it and the temporaries die with their owners (the tally follows them back).
+mcpt_status mcpt_rebuild_trees(mcpt_ctx* ctx, const mcpt_rebuild_opts* opts) {
+    const std::string who = "mcpt_rebuild_trees: ";
+    const auto t_entry = std::chrono::steady_clock::now();
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    mcpt_rebuild_opts o;
+    st = read_opts(opts, o, "mcpt_rebuild_trees", "mcpt_rebuild_opts"); if (st != MCPT_OK) return st;
+    if (o.builder > MCPT_REBUILD_DEVICE) return fail(MCPT_ERR_INVALID_ARG, who + "unknown builder");
+    const bool device_builder = o.builder == MCPT_REBUILD_DEVICE || (o.builder == MCPT_REBUILD_SAME && (ctx->opts.flags & MCPT_FLAG_GPU_BVH_BUILD));
+    st = use_drained(ctx); if (st != MCPT_OK) return st;                          // renders enqueued so far have walked the old tree
+    HIP_TRY(ctx->rf_watch.settle());
+    double area_before = 1.0;
+    if (ctx->rf_updates) {
+        double a = 0.0;
+        st = rf_read_area(ctx, a); if (st != MCPT_OK) return st;
+        if (ctx->rf_area0 > 0.0) area_before = a / ctx->rf_area0;
+    }
+    const uint32_t nt = uint32_t(ctx->dev.n_tris);
+    hipStream_t s = ctx->stream;
+    st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
+    RebuildPlan plan;
+    {   // the bounds kernel scatters by the old order: it is a permutation, or nothing is launched
+        const std::string bad = rb_plan(ctx->h_tri_face.data(), ctx->h_tri_face.size(), ctx->h_tri_face.data(), ctx->h_tri_face.size(), plan);
+        if (!bad.empty() || ctx->h_tri_face.size() != nt) return fail(MCPT_ERR_HIP, who + "the context's leaf order is damaged: " + bad);
+    }
+
+    // ---- the builders' input, from rf_vtx, in face order; fetched when a builder asks for it
+    Event ev[4];                                                                  // [0, 1] the bounds kernel, [2, 3] the permutation and the lights
+    for (Event& e : ev) HIP_TRY(hipEventCreate(e.out()));
+    double device_ms = 0.0;
+    DevBuf<float> d_box32; DevBuf<double> d_bound64; Pinned<float> h_box32; Pinned<double> h_bound64;
+    static_assert(sizeof(BTri) == 9 * sizeof(double), "rb_face_bounds_kernel writes scene_build.h's BTri: lo, hi, centroid");
+    std::string err;
+    auto bounds = [&](bool want64) -> bool {
+        auto hip_ok = [&](hipError_t e, const char* what) { if (e != hipSuccess) err = who + what + ": " + hipGetErrorString(e); return e == hipSuccess; };
+        if (!d_box32.p && !(hip_ok(d_box32.alloc(6 * size_t(nt)), "hipMalloc") && hip_ok(hipHostMalloc(h_box32.out(), 6 * size_t(nt) * sizeof(float), hipHostMallocDefault), "hipHostMalloc"))) return false;
+        if (want64 && !(hip_ok(d_bound64.alloc(9 * size_t(nt)), "hipMalloc") && hip_ok(hipHostMalloc(h_bound64.out(), 9 * size_t(nt) * sizeof(double), hipHostMallocDefault), "hipHostMalloc"))) return false;
+        const DevScene& d = ctx->dev;
+        float ms = 0.f;
+        return hip_ok(hipEventRecord(ev[0], s), "hipEventRecord") &&
+               hip_ok(launch_rb_face_bounds(ctx->rf_vtx.p, ctx->rf_idx.p, ctx->tri_face.p, RfCentre{d.centre[0], d.centre[1], d.centre[2]}, d_box32.p, want64 ? d_bound64.p : nullptr, nt, s), "rb_face_bounds_kernel") &&
+               hip_ok(hipEventRecord(ev[1], s), "hipEventRecord") &&
+               hip_ok(hipMemcpyAsync(h_box32, d_box32.p, d_box32.bytes, hipMemcpyDeviceToHost, s), "hipMemcpyAsync") &&
+               (!want64 || hip_ok(hipMemcpyAsync(h_bound64, d_bound64.p, d_bound64.bytes, hipMemcpyDeviceToHost, s), "hipMemcpyAsync")) &&
+               hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") && hip_ok(hipEventElapsedTime(&ms, ev[0], ev[1]), "hipEventElapsedTime") && ((device_ms += ms), true);
+    };
+    const TreeInput in{nt, [&]() -> const BTri* { return bounds(true) ? reinterpret_cast<const BTri*>(h_bound64.h) : nullptr; },
+                       [&]() -> const float* { return bounds(false) ? h_box32.h : nullptr; }};
+
+    // ---- the trees: mcpt_create's path, builders and depth rule
+    HostScene hs; std::vector<int> order;
+    hs.allow_deep_binary = device_builder && ctx->use_wavefront;
+    st = device_builder ? build_trees(in, hs, order, err, device_bvh_builder(), device_collapse8()) : build_trees(in, hs, order, err);
+    if (st != MCPT_OK) return fail(st, who + err);
+    if (hs.nodes8.size() * sizeof(f4h) >= (1ull << 32)) return fail(MCPT_ERR_UNSUPPORTED, who + "tree too large for the 8-wide traversal kernel");
+    {   const std::string bad = rb_plan(ctx->h_tri_face.data(), ctx->h_tri_face.size(), order.data(), order.size(), plan);
+        if (!bad.empty()) return fail(MCPT_ERR_HIP, who + "the builder's leaf order is no permutation of the faces: " + bad); }
+    std::vector<uint32_t> bin_order, bin_level, wide_level;
+    if (!rf_levels(hs.nodes, hs.nodes8, bin_order, bin_level, wide_level, err)) return fail(MCPT_ERR_HIP, who + err);
+    // the overflow area follows the NEW wide depth, known here on the host: a deeper tree gets its larger area before any kernel walks it
+    size_t ovf_bytes = 0;
+    if (ctx->use_wavefront && (st = overflow_bytes(ctx, hs.bvh8_depth, ovf_bytes)) != MCPT_OK) return st;
+    std::vector<DevBuf<int>> ovf(ctx->lanes.size());
+    for (size_t l = 0; l < ovf.size(); l++) if (ctx->lanes[l].ovf_buf.bytes != ovf_bytes) HIP_TRY(ovf[l].alloc(ovf_bytes / sizeof(int)));
+
+    // ---- new buffers: the nodes uploaded, the streams permuted, the lights renumbered in a copy, the new tree's area
+    uint64_t* tally = &ctx->info.device_bytes;
+    const size_t n2 = hs.nodes.size() / 4, n8 = hs.nodes8.size() / 5;
+    DevBuf<float4> nodes, nodes8, tri_isect, tri_shade; DevBuf<double> tri_pos64, rf_area; DevBuf<int32_t> rf_idx, tri_face; DevBuf<DevLight> lights;
+    DevBuf<float> rf_node_box; DevBuf<uint32_t> rf_bin_order, d_src, d_dst;
+    HIP_TRY(nodes.alloc(hs.nodes.size(), tally)); HIP_TRY(nodes8.alloc(hs.nodes8.size(), tally)); HIP_TRY(tri_isect.alloc(ctx->tri_isect.count(), tally));
+    HIP_TRY(tri_shade.alloc(ctx->tri_shade.count(), tally)); HIP_TRY(tri_pos64.alloc(ctx->tri_pos64.count(), tally)); HIP_TRY(tri_face.alloc(ctx->tri_face.count(), tally));
+    HIP_TRY(rf_idx.alloc(ctx->rf_idx.count(), tally)); HIP_TRY(lights.alloc(ctx->lights.count(), tally)); HIP_TRY(rf_node_box.alloc(n8 * 6, tally));
+    HIP_TRY(rf_bin_order.alloc(n2, tally)); HIP_TRY(rf_area.alloc(rf_area_blocks(uint32_t(n8)), tally));
+    HIP_TRY(d_src.alloc(nt)); HIP_TRY(d_dst.alloc(nt));
+    HIP_TRY(hipMemcpyAsync(nodes.p, hs.nodes.data(), nodes.bytes, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(nodes8.p, hs.nodes8.data(), nodes8.bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(rf_bin_order.p, bin_order.data(), rf_bin_order.bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_src.p, plan.src_of_dst.data(), d_src.bytes, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(d_dst.p, plan.dst_of_src.data(), d_dst.bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(tri_isect.p + 3 * size_t(nt), 0, 3 * sizeof(float4), s));                     // the spare record
+    if (lights.bytes) HIP_TRY(hipMemcpyAsync(lights.p, ctx->lights.p, lights.bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipEventRecord(ev[2], s));
+    HIP_TRY(launch_rb_permute(RbStreams{ctx->tri_isect.p, ctx->tri_shade.p, ctx->tri_pos64.p, ctx->rf_idx.p, ctx->tri_face.p},
+                              RbStreams{tri_isect.p, tri_shade.p, tri_pos64.p, rf_idx.p, tri_face.p}, d_src.p, nt, (ctx->opts.flags & MCPT_FLAG_REFERENCE_TIE_ORDER) != 0, s));
+    HIP_TRY(launch_rb_lights(lights.p, d_dst.p, uint32_t(ctx->dev.n_lights), nt, s));
+    HIP_TRY(hipEventRecord(ev[3], s));
+    HIP_TRY(launch_rf_wide_area(nodes8.p, uint32_t(n8), rf_area.p, s));
+    std::vector<double> part(rf_area.count());
+    HIP_TRY(hipMemcpyAsync(part.data(), rf_area.p, rf_area.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));                                             // (the host vectors above have been read)
+    {   float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ev[2], ev[3])); device_ms += ms; }
+    double area0 = 0.0;
+    for (double v : part) area0 += v;
+
+    // ---- commit: moves and assignments only
+    ctx->nodes = std::move(nodes); ctx->nodes8 = std::move(nodes8); ctx->tri_isect = std::move(tri_isect); ctx->tri_shade = std::move(tri_shade);
+    ctx->tri_pos64 = std::move(tri_pos64); ctx->tri_face = std::move(tri_face); ctx->rf_idx = std::move(rf_idx); ctx->lights = std::move(lights);
+    ctx->rf_node_box = std::move(rf_node_box); ctx->rf_bin_order = std::move(rf_bin_order); ctx->rf_area = std::move(rf_area);
+    for (size_t l = 0; l < ovf.size(); l++) if (ovf[l].p) ctx->lanes[l].ovf_buf = std::move(ovf[l]);
+    ctx->rf_bin_level.swap(bin_level); ctx->rf_wide_level.swap(wide_level); ctx->rf_area0 = area0;
+    ctx->h_tri_face.assign(order.begin(), order.end());
+    ctx->wide_depth = hs.bvh8_depth; ctx->binary_ok = hs.binary_ok;
+    DevScene& d = ctx->dev;
+    d.nodes = ctx->nodes.p; d.nodes8 = ctx->nodes8.p; d.tri_isect = ctx->tri_isect.p; d.tri_shade = ctx->tri_shade.p; d.tri_pos64 = ctx->tri_pos64.p;
+    d.tri_face = ctx->tri_face.p; d.lights = ctx->lights.p; d.n_nodes = int32_t(n2); d.n_nodes8 = int32_t(n8);
+    mcpt_scene_info& info = ctx->info;
+    info.n_nodes = uint32_t(n2); info.bvh_depth = hs.bvh_depth; info.max_leaf = hs.max_leaf; info.bvh_builder = hs.bvh_builder;
+    fill_tree_info(info, hs, ctx->h_tri_face.data(), ctx->h_tri_face.size());
+    ctx->rb_rebuilds++; ctx->rb_area_before = area_before; ctx->rb_last_build_ms = hs.bvh_build_ms; ctx->rb_last_device_ms = device_ms;
+    ctx->rb_last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_get_rebuild_info(mcpt_ctx* ctx, mcpt_rebuild_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    std::memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out; out->rebuilds = ctx->rb_rebuilds; out->last_ms = ctx->rb_last_ms; out->last_build_ms = ctx->rb_last_build_ms;
+    out->last_device_ms = ctx->rb_last_device_ms; out->area_ratio_before = ctx->rb_area_before;
     return MCPT_OK;
 }
 

@@ -27,7 +27,6 @@ static constexpr double kMaxCoord = MCPT_MAX_COORD;
 
 namespace {
 
-struct BTri { double lo[3], hi[3], c[3]; };
 struct Box {
     double lo[3], hi[3];
     Box() { for (int a = 0; a < 3; a++) { lo[a] = std::numeric_limits<double>::max(); hi[a] = std::numeric_limits<double>::lowest(); } }
@@ -49,11 +48,11 @@ inline float round_up(double v, float pad) { float f = float(v); if (double(f) <
 
 class Builder {
 public:
-    Builder(const std::vector<BTri>& t, std::vector<f4h>& nodes) : t_(t), nodes_(nodes), order_(t.size()) {
+    Builder(const BTri* t, size_t n, std::vector<f4h>& nodes) : t_(t), n_(n), nodes_(nodes), order_(n) {
         for (size_t i = 0; i < order_.size(); i++) order_[i] = int(i);
     }
     void run() {
-        const int n = int(t_.size());
+        const int n = int(n_);
         Box rb;
         if (n <= MCPT_LEAF_MAX) {            // keep the invariant "node 0 is an inner node"
             nodes_.resize(4);
@@ -169,7 +168,7 @@ private:
     std::atomic<int> next_node_{0};
     std::atomic<uint32_t> depth_{0}, max_leaf_{0};
 
-    const std::vector<BTri>& t_;
+    const BTri* t_; size_t n_;
     std::vector<f4h>& nodes_;
     std::vector<int> order_;
 };
@@ -610,6 +609,78 @@ DevMaterial device_material(const mcpt_material& m, const TexInfo& t) {
     return dm;
 }
 
+// The trees of `in.n_face` faces given by their bounds in face order: the custom or the host builder with its fallbacks, the breadth-first /
+// depth-first renumbering and the 8-wide collapse.  One path for mcpt_create (build_host_scene) and mcpt_rebuild_trees.
+mcpt_status build_trees(const TreeInput& in, HostScene& out, std::vector<int>& order, std::string& err, const BvhBuildFn& custom_bvh, const Collapse8Fn& custom_collapse8) {
+    const uint32_t nf = in.n_face;
+    auto t0 = std::chrono::steady_clock::now();
+    out.nodes.clear();
+    order.clear();
+    bool built = false;
+    if (custom_bvh && nf > uint32_t(MCPT_LEAF_MAX)) {
+        const float* boxes = in.boxes32();
+        if (!boxes) return MCPT_ERR_HIP;                                  // (the provider has filled `err`)
+        if (!custom_bvh(boxes, nf, out.nodes, order, out.bvh_depth, out.max_leaf, err)) return MCPT_ERR_HIP;
+        if (!out.nodes.empty() && (order.size() != nf || out.nodes.size() % 4 != 0)) { err = "custom BVH builder returned inconsistent arrays"; return MCPT_ERR_HIP; }
+        // An agglomerative tree over nested boxes (every merge with a smaller box gives the same box: a chain) can come out deeper than the
+        // binary-tree kernels' stack, and the builder gives up (no nodes) when its rounds do not converge: such a scene is rebuilt by the
+        // depth-capped host builder instead of being refused.
+        built = !out.nodes.empty() && (out.bvh_depth <= uint32_t(MCPT_STACK_DEPTH - 1) || (out.allow_deep_binary && out.bvh_depth <= 255u));
+        if (!built) { out.nodes.clear(); order.clear(); }
+        out.bvh_builder = built ? 1u : 2u;
+    }
+    if (!built) {
+        const BTri* bt = in.bounds64();
+        if (!bt) return MCPT_ERR_HIP;
+        Builder b(bt, nf, out.nodes);
+        b.run();
+        if (std::getenv("MCPT_BUILD_DEBUG")) fprintf(stderr, "[build] SAH %.0f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        out.bvh_depth = b.depth; out.max_leaf = b.max_leaf;
+        order = b.order();
+    }
+    {   // Renumber: the first MCPT_TOP_NODES nodes in breadth-first order (= the top ~10 levels, which the trace kernel keeps in
+        // LDS), every subtree below them in depth-first order (children next to parents -> cache-line locality in L1/L2).
+        const int n_nodes = int(out.nodes.size() / 4);
+        std::vector<int> new_id(n_nodes, -1), order_new; order_new.reserve(n_nodes);
+        auto child = [&](int n, int k) { int c; std::memcpy(&c, k == 0 ? &out.nodes[4 * size_t(n) + 3].x : &out.nodes[4 * size_t(n) + 3].y, 4); return c; };
+        std::vector<int> queue{0}; size_t qh = 0;
+        while (qh < queue.size() && int(order_new.size()) + int(queue.size() - qh) <= MCPT_TOP_NODES) {
+            const int n = queue[qh++]; new_id[n] = int(order_new.size()); order_new.push_back(n);
+            for (int k = 0; k < 2; k++) { const int c = child(n, k); if (c >= 0) queue.push_back(c); }
+        }
+        std::vector<int> stack;
+        for (size_t i = queue.size(); i-- > qh;) stack.push_back(queue[i]);           // remaining frontier, in BFS order
+        const size_t frontier_left = stack.size();
+        out.subtree_begin.clear();
+        while (!stack.empty()) {
+            const int n = stack.back(); stack.pop_back();
+            if (stack.size() < frontier_left - out.subtree_begin.size()) out.subtree_begin.push_back(int(order_new.size()));   // a frontier node: its whole subtree follows, contiguously
+            new_id[n] = int(order_new.size()); order_new.push_back(n);
+            const int c0 = child(n, 0), c1 = child(n, 1);
+            if (c1 >= 0) stack.push_back(c1);
+            if (c0 >= 0) stack.push_back(c0);
+        }
+        std::vector<f4h> renum(out.nodes.size());
+        for (int i = 0; i < n_nodes; i++) {
+            const int o = order_new[i];
+            for (int q = 0; q < 4; q++) renum[4 * size_t(i) + q] = out.nodes[4 * size_t(o) + q];
+            const int c0 = child(o, 0), c1 = child(o, 1);
+            renum[4 * size_t(i) + 3].x = as_float(c0 >= 0 ? new_id[c0] : c0);
+            renum[4 * size_t(i) + 3].y = as_float(c1 >= 0 ? new_id[c1] : c1);
+        }
+        out.nodes.swap(renum);
+    }
+    out.bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    out.binary_ok = out.bvh_depth <= uint32_t(MCPT_STACK_DEPTH - 1);
+    if (!out.binary_ok && !out.allow_deep_binary) { err = "BVH depth exceeds traversal stack"; return MCPT_ERR_BVH_DEPTH; }
+    out.nodes8.clear(); out.bvh8_depth = 0;
+    if (custom_collapse8) { if (!custom_collapse8(out.nodes, order, out.nodes8, out.bvh8_depth, err)) return MCPT_ERR_HIP; }
+    else build_bvh8(out, order);                                          // (defines the leaf order: `order` and the binary leaf codes are rewritten)
+    if (std::getenv("MCPT_BUILD_DEBUG")) fprintf(stderr, "[build] 8-wide collapse done at %.0f ms (%zu nodes, depth %u)\n",
+                                                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), out.nodes8.size() / 5, out.bvh8_depth);
+    return MCPT_OK;
+}
+
 mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::string& err, const BvhBuildFn& custom_bvh, const Collapse8Fn& custom_collapse8) {
     if (!d || !d->vertex || !d->normal || !d->texcoord || !d->face || !d->materials || !d->textures) { err = "null pointer in mcpt_scene_desc"; return MCPT_ERR_INVALID_ARG; }
     if (d->n_face == 0 || d->n_materials == 0 || d->n_textures == 0) { err = "empty scene"; return MCPT_ERR_INVALID_ARG; }
@@ -673,70 +744,15 @@ mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::stri
     }
 
     // ---- BVH
-    auto t0 = std::chrono::steady_clock::now();
-    out.nodes.clear();
     std::vector<int> order;
-    bool built = false;
-    if (custom_bvh && nf > uint32_t(MCPT_LEAF_MAX)) {
-        std::vector<float> boxes(6 * size_t(nf));
+    std::vector<float> boxes;
+    const TreeInput in{nf, [&]() { return bt.data(); }, [&]() {
+        boxes.resize(6 * size_t(nf));
         for (uint32_t f = 0; f < nf; f++)
             for (int a = 0; a < 3; a++) { boxes[6 * size_t(f) + a] = round_down(bt[f].lo[a], 0.f); boxes[6 * size_t(f) + 3 + a] = round_up(bt[f].hi[a], 0.f); }
-        if (!custom_bvh(boxes.data(), nf, out.nodes, order, out.bvh_depth, out.max_leaf, err)) return MCPT_ERR_HIP;
-        if (!out.nodes.empty() && (order.size() != nf || out.nodes.size() % 4 != 0)) { err = "custom BVH builder returned inconsistent arrays"; return MCPT_ERR_HIP; }
-        // An agglomerative tree over nested boxes (every merge with a smaller box gives the same box: a chain) can come out deeper than the
-        // binary-tree kernels' stack, and the builder gives up (no nodes) when its rounds do not converge: such a scene is rebuilt by the
-        // depth-capped host builder instead of being refused.
-        built = !out.nodes.empty() && (out.bvh_depth <= uint32_t(MCPT_STACK_DEPTH - 1) || (out.allow_deep_binary && out.bvh_depth <= 255u));
-        if (!built) { out.nodes.clear(); order.clear(); }
-        out.bvh_builder = built ? 1u : 2u;
-    }
-    if (!built) {
-        Builder b(bt, out.nodes);
-        b.run();
-        if (std::getenv("MCPT_BUILD_DEBUG")) fprintf(stderr, "[build] SAH %.0f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        out.bvh_depth = b.depth; out.max_leaf = b.max_leaf;
-        order = b.order();
-    }
-    {   // Renumber: the first MCPT_TOP_NODES nodes in breadth-first order (= the top ~10 levels, which the trace kernel keeps in
-        // LDS), every subtree below them in depth-first order (children next to parents -> cache-line locality in L1/L2).
-        const int n_nodes = int(out.nodes.size() / 4);
-        std::vector<int> new_id(n_nodes, -1), order_new; order_new.reserve(n_nodes);
-        auto child = [&](int n, int k) { int c; std::memcpy(&c, k == 0 ? &out.nodes[4 * size_t(n) + 3].x : &out.nodes[4 * size_t(n) + 3].y, 4); return c; };
-        std::vector<int> queue{0}; size_t qh = 0;
-        while (qh < queue.size() && int(order_new.size()) + int(queue.size() - qh) <= MCPT_TOP_NODES) {
-            const int n = queue[qh++]; new_id[n] = int(order_new.size()); order_new.push_back(n);
-            for (int k = 0; k < 2; k++) { const int c = child(n, k); if (c >= 0) queue.push_back(c); }
-        }
-        std::vector<int> stack;
-        for (size_t i = queue.size(); i-- > qh;) stack.push_back(queue[i]);           // remaining frontier, in BFS order
-        const size_t frontier_left = stack.size();
-        out.subtree_begin.clear();
-        while (!stack.empty()) {
-            const int n = stack.back(); stack.pop_back();
-            if (stack.size() < frontier_left - out.subtree_begin.size()) out.subtree_begin.push_back(int(order_new.size()));   // a frontier node: its whole subtree follows, contiguously
-            new_id[n] = int(order_new.size()); order_new.push_back(n);
-            const int c0 = child(n, 0), c1 = child(n, 1);
-            if (c1 >= 0) stack.push_back(c1);
-            if (c0 >= 0) stack.push_back(c0);
-        }
-        std::vector<f4h> renum(out.nodes.size());
-        for (int i = 0; i < n_nodes; i++) {
-            const int o = order_new[i];
-            for (int q = 0; q < 4; q++) renum[4 * size_t(i) + q] = out.nodes[4 * size_t(o) + q];
-            const int c0 = child(o, 0), c1 = child(o, 1);
-            renum[4 * size_t(i) + 3].x = as_float(c0 >= 0 ? new_id[c0] : c0);
-            renum[4 * size_t(i) + 3].y = as_float(c1 >= 0 ? new_id[c1] : c1);
-        }
-        out.nodes.swap(renum);
-    }
-    out.bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    out.binary_ok = out.bvh_depth <= uint32_t(MCPT_STACK_DEPTH - 1);
-    if (!out.binary_ok && !out.allow_deep_binary) { err = "BVH depth exceeds traversal stack"; return MCPT_ERR_BVH_DEPTH; }
-    out.nodes8.clear(); out.bvh8_depth = 0;
-    if (custom_collapse8) { if (!custom_collapse8(out.nodes, order, out.nodes8, out.bvh8_depth, err)) return MCPT_ERR_HIP; }
-    else build_bvh8(out, order);                                          // (defines the leaf order: `order` and the binary leaf codes are rewritten)
-    if (std::getenv("MCPT_BUILD_DEBUG")) fprintf(stderr, "[build] 8-wide collapse done at %.0f ms (%zu nodes, depth %u)\n",
-                                                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), out.nodes8.size() / 5, out.bvh8_depth);
+        return static_cast<const float*>(boxes.data());
+    }};
+    { const mcpt_status st = build_trees(in, out, order, err, custom_bvh, custom_collapse8); if (st != MCPT_OK) return st; }
     std::vector<int> pos_of_face(nf);
     for (uint32_t i = 0; i < nf; i++) pos_of_face[order[i]] = int(i);
 

@@ -51,6 +51,21 @@ using BvhBuildFn = std::function<bool(const float* boxes, uint32_t n, std::vecto
 // out; rewrites the binary tree's leaf codes and the leaf order like build_bvh8 does.
 using Collapse8Fn = std::function<bool(std::vector<f4h>& nodes2, std::vector<int>& order, std::vector<f4h>& nodes8, uint32_t& depth8, std::string& err)>;
 
+// What the builders see of a face, in centred coordinates: its fp64 bound and centroid (host builder) ...
+struct BTri { double lo[3], hi[3], c[3]; };
+// ... given in Model::face order by two providers that are asked only when their builder runs (mcpt_rebuild_trees fetches them from the device):
+// bounds64 for the host builder, boxes32 -- lo xyz, hi xyz, the fp64 bound rounded outward -- for the custom one.  nullptr = failed, `err` filled.
+struct TreeInput {
+    uint32_t n_face;
+    std::function<const BTri*()> bounds64;
+    std::function<const float*()> boxes32;
+};
+// Both trees of a scene: the custom builder (when given and the scene has more than one leaf) with its fallbacks or the host builder, the
+// renumbering, the 8-wide collapse.  Reads out.allow_deep_binary; fills out.nodes, nodes8, bvh_depth, max_leaf, bvh8_depth, subtree_begin,
+// bvh_builder, binary_ok, bvh_build_ms and `order` (leaf position -> face).  build_host_scene and mcpt_rebuild_trees both build through it.
+mcpt_status build_trees(const TreeInput& in, HostScene& out, std::vector<int>& order, std::string& err, const BvhBuildFn& custom_bvh = nullptr,
+                        const Collapse8Fn& custom_collapse8 = nullptr);
+
 // Validates the description (indices in range, sizes non-zero), flattens faces, collects lights, builds the BVH.
 // Returns MCPT_OK or an error code with `err` filled.
 mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::string& err, const BvhBuildFn& custom_bvh = nullptr,

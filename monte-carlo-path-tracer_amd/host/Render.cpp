@@ -169,6 +169,12 @@ bool Render::update(Scene& scene, Model& m) {
     if (mcpt_set_camera(ctx, &k) != MCPT_OK) { std::cerr << "Error: mcpt_set_camera: " << mcpt_last_error() << std::endl; return false; }
     return restart(scene);
 }
+bool Render::rebuild(Scene&, uint32_t builder) {
+    if (!ctx) return false;
+    mcpt_rebuild_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.builder = builder;
+    if (mcpt_rebuild_trees(ctx, &o) != MCPT_OK) { std::cerr << "Error: mcpt_rebuild_trees: " << mcpt_last_error() << std::endl; return false; }
+    return true;
+}
 // One group per vertex and per normal from one per face: whatever a face of group g uses belongs to g; what no face uses, to group 0.
 static bool groups_of(const std::vector<imat3x4>& face, const std::vector<uint32_t>& face_group, int column, size_t n, const char* what, std::vector<uint32_t>& out) {
     const uint32_t none = ~0u;

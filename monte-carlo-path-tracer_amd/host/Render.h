@@ -61,6 +61,11 @@ public:
     bool update_transforms(Scene& scene, const std::vector<double>& matrices);
     bool update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, float max_history = 0);
     bool update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history = 0);
+    // New trees for the geometry as it is now (mcpt_rebuild_trees): after update() / update_transforms() have moved the scene far
+    // (mcpt_update_info::wide_area_ratio says how far) the refitted trees are sound and slow; this builds them anew on the context.  The picture
+    // goes ON: `scene`'s film, the sample numbering and the feature buffers stay, the scene looks the same from every pixel.  Synchronous.  false
+    // (and an unchanged Render) on failure.
+    bool rebuild(Scene& scene, uint32_t builder = MCPT_REBUILD_SAME);
     Render(const Render&) = delete;
     Render& operator=(const Render&) = delete;
     bool ok() const { return ctx != nullptr; }

@@ -35,6 +35,8 @@ static void usage() {
                  "                          [--spin MTLNAME]   with --turntable: the faces of that material turn as one rigid part, by 360 k / N degrees in frame k about\n"
                  "                                        the camera's up axis through their bounding box's centre (one 3x4 matrix per frame, applied on the device;\n"
                  "                                        honours --reproject; not with --wobble)\n"
+                 "                          [--rebuild-above R]   with --turntable and --wobble or --spin: after a frame's update the trees are built anew\n"
+                 "                                        (mcpt_rebuild_trees, film kept) when wide_area_ratio exceeds R; prints frame, ratio and cost per rebuild\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -65,6 +67,7 @@ int main(int argc, char** argv) {
     bool wobble = false; double wobble_a = 0.0;
     bool pulse = false; double pulse_a = 0.0;
     std::string spin;
+    bool rebuild = false; double rebuild_above = 0.0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -86,6 +89,7 @@ int main(int argc, char** argv) {
         else if (a == "--wobble") { wobble = true; wobble_a = std::atof(next()); }
         else if (a == "--light-pulse") { pulse = true; pulse_a = std::atof(next()); }
         else if (a == "--spin") spin = next();
+        else if (a == "--rebuild-above") { rebuild = true; rebuild_above = std::atof(next()); }
         else { usage(); return 2; }
     }
     if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
@@ -95,6 +99,7 @@ int main(int argc, char** argv) {
     if (pulse && (!turntable || !(std::fabs(pulse_a) <= 1e6))) { std::cerr << "Error: --light-pulse A needs --turntable N and a finite A" << std::endl; return 2; }
     if (pulse && reproject) { std::cerr << "Error: --light-pulse restarts the film every frame: radiance reprojected across it would be the old light's (drop --reproject)" << std::endl; return 2; }
     if (!spin.empty() && (!turntable || wobble)) { std::cerr << "Error: --spin MTLNAME needs --turntable N and no --wobble (both write the vertices)" << std::endl; return 2; }
+    if (rebuild && (!turntable || !(wobble || !spin.empty()) || !(rebuild_above >= 0.0))) { std::cerr << "Error: --rebuild-above R needs --turntable N with --wobble or --spin, and R >= 0" << std::endl; return 2; }
     if (wobble || !spin.empty()) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
@@ -221,6 +226,14 @@ int main(int argc, char** argv) {
                                        : !(renders[0]->update_transforms(scene, m) && renders[0]->set_camera(scene, cam))) return 1;
             } else
             if (reproject && f > 0 ? !renders[0]->set_camera_reproject(scene, cam, history) : !renders[0]->set_camera(scene, cam)) return 1;
+            if (rebuild) {                                                   // --rebuild-above R: the refitted trees have grown past R times their built size
+                mcpt_update_info ui; mcpt_rebuild_info ri;
+                if (mcpt_get_update_info(renders[0]->handle(), &ui) != MCPT_OK) { std::cerr << "Error: mcpt_get_update_info: " << mcpt_last_error() << std::endl; return 1; }
+                if (ui.wide_area_ratio > rebuild_above) {
+                    if (!renders[0]->rebuild(scene) || mcpt_get_rebuild_info(renders[0]->handle(), &ri) != MCPT_OK) return 1;
+                    std::cout << "rebuild: frame " << f << "    wide_area_ratio before: " << ri.area_ratio_before << "    cost: " << ri.last_ms << " ms\n";
+                }
+            }
             renders[0]->render(scene, spp);
             scene.sync();
             std::cout << "frame: " << f << "    frame cost: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << "s\n";
