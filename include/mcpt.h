@@ -284,7 +284,7 @@ mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* camera);
 mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal);
 
 typedef struct mcpt_update_info {
-    uint32_t struct_size, updates;      /* mcpt_update_vertices / mcpt_update_transforms (+ _reproject) calls on this context so far */
+    uint32_t struct_size, updates;      /* mcpt_update_vertices / _transforms / _skin (+ _reproject) calls on this context so far */
     double   last_update_ms;            /* device time of the last one, first to last operation on the stream (HIP events) */
     double   wide_area_ratio;           /* sum of the child-box areas of the 8-wide tree now / when it was built, by mcpt_create or by the last
                                            mcpt_rebuild_trees (dequantised boxes; 1.0 before any update and right after a rebuild) */
@@ -328,7 +328,7 @@ typedef struct mcpt_reproject_opts {
     uint32_t reserved[3];
 } mcpt_reproject_opts;
 typedef struct mcpt_reproject_info {
-    uint32_t struct_size, reprojections;   /* mcpt_set_camera_reproject + mcpt_update_{vertices,transforms}_reproject calls so far */
+    uint32_t struct_size, reprojections;   /* mcpt_set_camera_reproject + mcpt_update_{vertices,transforms,skin}_reproject calls */
     uint64_t pixels_reused;                /* pixels of the last call written with a history of >= 1 sample */
     double   last_ms;                      /* device time of the last call, first to last operation on the stream (HIP events) */
     uint32_t reserved[4];
@@ -464,6 +464,60 @@ typedef struct mcpt_transform_info {
 } mcpt_transform_info;
 mcpt_status mcpt_get_transform_info(mcpt_ctx* ctx, mcpt_transform_info* out);   /* synchronises */
 
+/* ---- deforming parts: linear-blend skinning on the device --------------------------------------------------------------------- */
+/* A bending arm, a swaying plant or a character has vertices that follow several bones with weights: mcpt_update_transforms cannot express it (a
+ * vertex belongs to one group).  The caller names MCPT_SKIN_INFLUENCES bone ids and weights per vertex and per normal once and then sends one 3x4
+ * matrix per bone and frame: the device keeps the skin's REST POSE and writes the current vertices and normals from it.  All calls need
+ * MCPT_FLAG_DYNAMIC (else MCPT_ERR_UNSUPPORTED).
+ *
+ * mcpt_set_vertex_skin: set-up, synchronous, the twin of mcpt_set_vertex_groups.  vertex_bone / vertex_weight hold 4 ids / 4 doubles per vertex,
+ * normal_bone / normal_weight 4 per normal (both may be NULL only when n_normal is 0).  The context's CURRENT vertices and normals become the skin's
+ * OWN rest pose (copied device to device) -- independent of the groups' rest pose; both features may be set on one context.  Per bone R_b -- the
+ * largest |coordinate| among the vertices that a face uses and that give the bone a weight > 0, 0 without any -- is kept for the validation below
+ * (one read-back of the vertices).  Calling it again replaces the skin and takes the rest pose anew.  Allocates, counted in device_bytes, 24 B
+ * (rest pose) + 16 B (ids) + 32 B (weights) per vertex and per normal and 96 B per bone (the table), plus a pinned stage of the table's size.
+ * mcpt_clone_to_device carries skin, rest pose and R_b; mcpt_rebuild_trees keeps them (they are per vertex, not per leaf: nothing is permuted).
+ *  - Refused with nothing changed, MCPT_ERR_INVALID_ARG: counts that differ from the scene's; a NULL array; n_bones outside
+ *    [1, 4 (n_vertex + n_normal)]; an id >= n_bones in ANY slot, zero-weight slots included; a weight that is not finite or is outside [0, 1]; a
+ *    record whose sum S = ((w0 + w1) + w2) + w3 has |S - 1| > 1e-6.
+ *  - Weights are USED AS GIVEN and never renormalised: what the caller sends is what every frame is blended with.  (fp32 weights normalised by the
+ *    caller sum to 1 within about 1e-7 and pass.)
+ *
+ * mcpt_update_skin: m3x4 holds n_bones row-major 3x4 matrices [A | t] in world space.  Per record the blended matrix is, entrywise,
+ * B = ((w0 M0 + w1 M1) + w2 M2) + w3 M3 -- all four slots in that order, none skipped because its weight is 0.  A vertex becomes per row
+ * ((B0 x + B1 y) + B2 z) + B3; a normal, with its own influences, cof(A_B) rest_normal per row (C0 x + C1 y) + C2 z, divided by its length when
+ * that is finite and > 0 and left as it is otherwise (mcpt_update_transforms' rule).  Everything in fp64, one rounding per operation.
+ *  - Blends that come out (nearly) SINGULAR give meaningless normals: two opposed rotations blended half and half are the classic case (the
+ *    "candy wrapper").  Only the bones themselves are validated, not their blends.
+ * From there on the call IS mcpt_update_vertices after its upload: the same refit, ordering, bookkeeping (mcpt_get_update_info counts it, and
+ * last_update_ms spans the table's copy, the two kernels and the refit) and what it leaves untouched (film, counters) or drops (features, denoised
+ * film, tile error).
+ *  - Bones apply to the skin's rest pose and never accumulate.  A later mcpt_update_vertices or mcpt_update_transforms overwrites what the call
+ *    wrote and leaves the skin's rest pose alone; the next mcpt_update_skin overwrites what they wrote and leaves the groups' rest pose alone.
+ *  - Validated on the host before any device work, a refusal changes nothing; in this order: MCPT_ERR_UNSUPPORTED without MCPT_FLAG_DYNAMIC;
+ *    MCPT_ERR_INVALID_ARG when no skin is set, for NULL or another n_bones, for an entry that is not finite, for a bone whose det A is zero or not
+ *    finite, and when for some bone and row (1 + 2^-16) ((|a0| + |a1| + |a2|) R_b + |t|) exceeds 1e18 or is not finite.  That row bound is
+ *    CONSERVATIVE: a vertex's result is bounded by S times the largest reach of its bones, and the factor covers S <= 1 + 1e-6 and the rounding;
+ *    it may refuse bones whose vertices mcpt_update_vertices would accept just under 1e18; in exchange validation needs no device round trip.
+ *  - Asynchronous on the context's stream.  The matrices are staged through pinned memory and copied in stream order: the caller may reuse its
+ *    array when the call returns, and back-to-back calls cannot overtake each other.
+ *
+ * mcpt_update_skin_reproject is mcpt_update_vertices_reproject with the bones in place of the upload; validation order: the matrices, the camera
+ * (when given), the options, MCPT_ERR_BVH_DEPTH. */
+#define MCPT_SKIN_INFLUENCES 4
+mcpt_status mcpt_set_vertex_skin(mcpt_ctx* ctx, const uint32_t* vertex_bone /* 4 per vertex */, const double* vertex_weight /* 4 per vertex */,
+                                 uint32_t n_vertex, const uint32_t* normal_bone, const double* normal_weight, uint32_t n_normal, uint32_t n_bones);
+mcpt_status mcpt_update_skin(mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones);
+mcpt_status mcpt_update_skin_reproject(mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones, const mcpt_camera* camera /* NULL = keep */,
+                                       const mcpt_reproject_opts* opts /* NULL = defaults */);
+typedef struct mcpt_skin_info {
+    uint32_t struct_size, n_bones;      /* bones of the skin set now (0 = none) */
+    uint32_t updates, reserved0;        /* mcpt_update_skin (+ _reproject) calls on this context so far */
+    double   last_ms;                   /* device time of the last one's skinning part: the table's copy and the two kernels (HIP events) */
+    uint32_t reserved[4];
+} mcpt_skin_info;
+mcpt_status mcpt_get_skin_info(mcpt_ctx* ctx, mcpt_skin_info* out);   /* synchronises */
+
 /* ---- live scenes: new trees for the geometry as it is now -------------------------------------------------------------- */
 /* mcpt_update_vertices and mcpt_update_transforms refit: after a large deformation the trees are sound and slow.  mcpt_rebuild_trees builds BOTH
  * trees (binary and 8-wide) anew for the context's current vertices -- whatever the last update or transform wrote -- and keeps everything else.
@@ -480,7 +534,8 @@ mcpt_status mcpt_get_transform_info(mcpt_ctx* ctx, mcpt_transform_info* out);   
  *    rank it has (the creation geometry's, as mcpt_update_vertices documents).
  *  - KEPT, because the scene looks the same from every pixel: the film or a bound accumulator, the counters, the stream binding, the camera, the
  *    feature buffers and the denoised film, the adaptive tile error, the reprojection buffers, the vertex groups with their rest pose and R_g,
- *    the materials, the textures, and the light list's membership and order (only the lights' leaf-order triangle index is renumbered).
+ *    the skin with its rest pose and R_b, the materials, the textures, and the light list's membership and order (only the lights' leaf-order
+ *    triangle index is renumbered).
  *  - Afterwards mcpt_update_info::wide_area_ratio is 1.0 (its base is the new tree) and `updates` is unchanged; mcpt_scene_info follows the new
  *    trees: n_nodes, bvh_depth, max_leaf, wide_nodes, wide_depth, traversal_bytes, wide_tree_hash, bvh_builder, and device_bytes counts what is
  *    allocated now; bvh_build_ms and upload_ms stay creation's.

@@ -19,6 +19,8 @@ import numpy as np
 from . import scenes  # noqa: F401  (re-export)
 # mcpt_rebuild_trees' options, info and builder constants; tests/test_rebuild.py holds their layout to the header
 from .rebuild_abi import REBUILD_DEVICE, REBUILD_HOST, REBUILD_SAME, RebuildInfo, RebuildOpts  # noqa: F401
+# mcpt_get_skin_info's struct and the influence count; tests/test_skin.py holds the layout to the header
+from .skin_abi import SKIN_INFLUENCES, SkinInfo  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmcpt_hip.so")
@@ -280,6 +282,10 @@ def load_library() -> C.CDLL:
         "mcpt_update_transforms": [vp, vp, C.c_uint32],
         "mcpt_update_transforms_reproject": [vp, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
         "mcpt_get_transform_info": [vp, P(TransformInfo)],
+        "mcpt_set_vertex_skin": [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32],
+        "mcpt_update_skin": [vp, vp, C.c_uint32],
+        "mcpt_update_skin_reproject": [vp, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
+        "mcpt_get_skin_info": [vp, P(SkinInfo)],
         "mcpt_rebuild_trees": [vp, P(RebuildOpts)],
         "mcpt_get_rebuild_info": [vp, P(RebuildInfo)],
     }
@@ -308,6 +314,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_update_vertices_reproject", "mcpt_probe_first_hits", "mcpt_probe_reproject_motion",
     "mcpt_update_materials", "mcpt_update_texture", "mcpt_get_material_info", "mcpt_probe_lights", "mcpt_probe_face_classes",
     "mcpt_set_vertex_groups", "mcpt_update_transforms", "mcpt_update_transforms_reproject", "mcpt_get_transform_info",
+    "mcpt_set_vertex_skin", "mcpt_update_skin", "mcpt_update_skin_reproject", "mcpt_get_skin_info",
     "mcpt_rebuild_trees", "mcpt_get_rebuild_info",
 ]
 
@@ -352,6 +359,28 @@ def groups_from_faces(scene: "scenes.SceneData", face_group):
             raise ValueError("groups_from_faces: %s %d is used by faces of groups %d and %d" % (what, shared[0], lo[shared[0]], hi[shared[0]]))
         out.append(np.where(hi >= 0, hi, 0).astype(np.uint32))
     return out[0], out[1]
+
+
+def skin_normals_from_faces(scene: "scenes.SceneData", vertex_bone, vertex_weight):
+    """Per-normal bone ids and weights ((n_normal, 4) uint32 and float64, for Renderer.set_vertex_skin) from the per-vertex ones: a normal takes
+    the influences of the vertex it is paired with in a face corner, one no face uses gets bone 0 with weight 1.  Raises ValueError naming the
+    normal when two corners pair it with vertices whose influence records differ -- the caller duplicates it then."""
+    nv, nn = scene.vertex.shape[0], scene.normal.shape[0]
+    vb = np.ascontiguousarray(vertex_bone, np.uint32).reshape(-1, SKIN_INFLUENCES); vw = np.ascontiguousarray(vertex_weight, np.float64).reshape(-1, SKIN_INFLUENCES)
+    if vb.shape[0] != nv or vw.shape[0] != nv:
+        raise ValueError("skin_normals_from_faces: need %d bone ids and weights per vertex" % SKIN_INFLUENCES)
+    vi = scene.face[:, :, 0].astype(np.int64).reshape(-1); ni = scene.face[:, :, 1].astype(np.int64).reshape(-1)
+    first = np.full(nn, -1, np.int64)
+    first[ni[::-1]] = vi[::-1]                                    # per normal the vertex of its first corner
+    mine = first[ni]
+    differ = np.any(vb[vi] != vb[mine], axis=1) | np.any(vw[vi].view(np.uint64) != vw[mine].view(np.uint64), axis=1)
+    if differ.any():
+        k = int(np.flatnonzero(differ)[0])
+        raise ValueError("skin_normals_from_faces: normal %d is paired with vertices %d and %d, whose influences differ" % (ni[k], mine[k], vi[k]))
+    nb = np.zeros((nn, SKIN_INFLUENCES), np.uint32); nw = np.zeros((nn, SKIN_INFLUENCES), np.float64); nw[:, 0] = 1.0
+    used = first >= 0
+    nb[used] = vb[first[used]]; nw[used] = vw[first[used]]
+    return nb, nw
 
 
 def check_scene(scene: "scenes.SceneData"):
@@ -550,6 +579,35 @@ class Renderer:
         self._check(self.lib.mcpt_get_transform_info(self.ctx, C.byref(i)))
         return i
 
+    # ---- deforming parts: linear-blend skinning
+    def set_vertex_skin(self, vertex_bone, vertex_weight, normal_bone, normal_weight, n_bones: int):
+        """Four bone ids and weights per vertex and per normal (skin_normals_from_faces derives the normals' from the vertices'); the scene as it
+        is now becomes the rest pose update_skin deforms.  Weights are used as given.  Needs FLAG_DYNAMIC.  Synchronous."""
+        vb = np.ascontiguousarray(vertex_bone, np.uint32).reshape(-1, SKIN_INFLUENCES); vw = np.ascontiguousarray(vertex_weight, np.float64).reshape(-1, SKIN_INFLUENCES)
+        nb = np.ascontiguousarray(normal_bone, np.uint32).reshape(-1, SKIN_INFLUENCES); nw = np.ascontiguousarray(normal_weight, np.float64).reshape(-1, SKIN_INFLUENCES)
+        if vb.shape != vw.shape or nb.shape != nw.shape:
+            raise ValueError("need as many weights as bone ids")
+        self._check(self.lib.mcpt_set_vertex_skin(self.ctx, _ptr(vb), _ptr(vw), vb.shape[0], _ptr(nb) if nb.size else None, _ptr(nw) if nw.size else None,
+                                                  nb.shape[0], int(n_bones)))
+
+    def update_skin(self, matrices):
+        """One row-major 3x4 matrix [A | t] per bone, blended per record by its four weights and applied to the skin's REST pose on the device
+        (never accumulated), then update_vertices' refit: only the matrices cross the bus.  Asynchronous; the caller clears the film."""
+        m = self._matrices(matrices)
+        self._check(self.lib.mcpt_update_skin(self.ctx, _ptr(m), m.shape[0]))
+
+    def update_skin_reproject(self, matrices, camera=None, **opts):
+        """update_skin that carries the film over, as update_vertices_reproject does; opts: reproject_camera's."""
+        m = self._matrices(matrices)
+        c = None if camera is None else C.byref(_camera_c(camera))
+        o = _reproject_opts(**opts)
+        self._check(self.lib.mcpt_update_skin_reproject(self.ctx, _ptr(m), m.shape[0], c, C.byref(o)))
+
+    def skin_info(self) -> SkinInfo:
+        i = SkinInfo()
+        self._check(self.lib.mcpt_get_skin_info(self.ctx, C.byref(i)))
+        return i
+
     # ---- material, light and texture edits (DESIGN.md §15)
     def update_materials(self, materials, map_kd=None):
         """New ks / ns / radiance for the same number of materials (a list of scenes.Material); map_kd: per material the index of the creation
@@ -599,7 +657,7 @@ class Renderer:
 
     # ---- new trees for the geometry as it is now
     def rebuild(self, builder: int = REBUILD_SAME):
-        """Both trees built anew for the context's current vertices, in place; film, counters, features, groups, materials and lights stay.
+        """Both trees built anew for the context's current vertices, in place; film, counters, features, groups, skin, materials and lights stay.
         builder: REBUILD_SAME (the one the context was created with), REBUILD_HOST or REBUILD_DEVICE.  Needs FLAG_DYNAMIC.  Synchronous."""
         o = RebuildOpts()
         o.struct_size = C.sizeof(RebuildOpts); o.builder = int(builder)

@@ -12,6 +12,7 @@
 #include "rebuild.h"
 #include "rebuild_plan.h"
 #include "transform.h"
+#include "skin.h"
 #include "reproject.h"
 #include "materials.h"
 
@@ -211,6 +212,14 @@ struct mcpt_ctx {
     Staging<double> xf_stage; std::vector<double> xf_radius;
     Stopwatch xf_watch;
     uint32_t xf_n_groups = 0, xf_updates = 0;
+    // Linear-blend skinning (skin.hip), allocated by mcpt_set_vertex_skin and counted in device_bytes: the skin's OWN rest pose
+    // (rf_vtx's and rf_nrm's sizes; independent of the groups'), SK_INFLUENCES bone ids and weights per vertex and per normal, the table of
+    // SK_RECORD doubles per bone and its pinned staging.  On the host per bone R_b, the largest |coordinate| among the vertices that a face uses
+    // and that give the bone a weight > 0 (what mcpt_update_skin validates against).
+    DevBuf<double> sk_rest_vtx, sk_rest_nrm, sk_table, sk_vweight, sk_nweight; DevBuf<uint32_t> sk_vbone, sk_nbone;
+    Staging<double> sk_stage; std::vector<double> sk_radius;
+    Stopwatch sk_watch;
+    uint32_t sk_n_bones = 0, sk_updates = 0;
     // Temporal reprojection (reproject.hip), allocated by the first reprojection call: the old view's features (2 per pixel, swapped
     // with dn_feat per call), a copy of the old film and the reuse counter.
     // Motion-vector reprojection adds, on the first mcpt_update_vertices_reproject: the first hit of every pixel-centre ray and
@@ -487,6 +496,16 @@ static mcpt_status xf_alloc(mcpt_ctx* c, uint32_t n_groups) {
     c->xf_n_groups = n_groups; c->xf_radius.assign(n_groups, 0.0);
     return MCPT_OK;
 }
+// The buffers of §18 for n_bones bones, all or none: a context that had a skin keeps it when an allocation fails.
+static mcpt_status sk_alloc(mcpt_ctx* c, uint32_t n_bones) {
+    uint64_t* tally = &c->info.device_bytes;
+    const size_t nt = size_t(n_bones) * SK_RECORD, nv = size_t(c->rf_n_vertex) * SK_INFLUENCES, nn = size_t(c->rf_n_normal) * SK_INFLUENCES;
+    HIP_TRY(alloc_all(Want(c->sk_rest_vtx, c->rf_vtx.count(), tally), Want(c->sk_rest_nrm, c->rf_nrm.count(), tally), Want(c->sk_vbone, nv, tally),
+                      Want(c->sk_nbone, nn, tally), Want(c->sk_vweight, nv, tally), Want(c->sk_nweight, nn, tally), Want(c->sk_table, nt, tally),
+                      Want(c->sk_stage, nt), Want(c->sk_watch, 1, nullptr, !c->sk_watch.ev0)));
+    c->sk_n_bones = n_bones; c->sk_radius.assign(n_bones, 0.0);
+    return MCPT_OK;
+}
 static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     c->rf_n_vertex = src->rf_n_vertex; c->rf_n_normal = src->rf_n_normal; c->rf_used_vertex = src->rf_used_vertex;
     c->rf_bin_level = src->rf_bin_level; c->rf_wide_level = src->rf_wide_level; c->rf_area0 = src->rf_area0;
@@ -501,6 +520,14 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
         auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
         HIP_TRY(copy(c->xf_rest_vtx, src->xf_rest_vtx)); HIP_TRY(copy(c->xf_rest_nrm, src->xf_rest_nrm));
         HIP_TRY(copy(c->xf_vgroup, src->xf_vgroup)); HIP_TRY(copy(c->xf_ngroup, src->xf_ngroup));
+    }
+    if (src->sk_n_bones) {                                                 // the skin, its rest pose and R_b travel with the clone (§18)
+        mcpt_status ks = sk_alloc(c, src->sk_n_bones); if (ks != MCPT_OK) return ks;
+        c->sk_radius = src->sk_radius;
+        auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
+        HIP_TRY(copy(c->sk_rest_vtx, src->sk_rest_vtx)); HIP_TRY(copy(c->sk_rest_nrm, src->sk_rest_nrm));
+        HIP_TRY(copy(c->sk_vbone, src->sk_vbone)); HIP_TRY(copy(c->sk_nbone, src->sk_nbone));
+        HIP_TRY(copy(c->sk_vweight, src->sk_vweight)); HIP_TRY(copy(c->sk_nweight, src->sk_nweight));
     }
     HIP_TRY(hipDeviceSynchronize());
     return MCPT_OK;
@@ -1247,14 +1274,37 @@ static mcpt_status xf_check_update(const mcpt_ctx* ctx, const double* m3x4, uint
         }
     return MCPT_OK;
 }
-// A scene update that has been checked: the caller's arrays (rf_check_update), or one matrix per group (xf_check_update).
-struct RfUpdate { const double* vertex; const double* normal; const double* m3x4; };
+// mcpt_update_skin's rules for its matrices (§18), host only, as xf_check_update: the conservative row bound against R_b carries a slack factor.
+static mcpt_status sk_check_update(const mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones, const char* fn) {
+    const std::string who = std::string(fn) + ": ";
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if (!ctx->sk_n_bones) return fail(MCPT_ERR_INVALID_ARG, who + "no skin is set (mcpt_set_vertex_skin)");
+    if (!m3x4) return fail(MCPT_ERR_INVALID_ARG, who + "null matrices");
+    if (n_bones != ctx->sk_n_bones) return fail(MCPT_ERR_INVALID_ARG, who + "n_bones differs from the skin set");
+    for (size_t k = 0; k < size_t(n_bones) * 12; k++)
+        if (!std::isfinite(m3x4[k])) return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(k / 12) + ": a matrix entry is not finite");
+    for (uint32_t b = 0; b < n_bones; b++) {
+        const double det = sk_bone_det(m3x4 + 12 * size_t(b));
+        if (!(std::isfinite(det) && det != 0.0)) return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": det A is zero or not finite");
+    }
+    for (uint32_t b = 0; b < n_bones; b++)
+        for (int r = 0; r < 3; r++) {
+            const double reach = sk_row_reach(m3x4 + 12 * size_t(b) + 4 * r, ctx->sk_radius[b]);
+            if (!(reach <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": a vertex could leave |coordinate| <= 1e18 (conservative bound)");
+        }
+    return MCPT_OK;
+}
+// A scene update that has been checked: the caller's arrays (rf_check_update), one matrix per group (xf_check_update) or one per bone (sk_check_update).
+struct RfUpdate { const double* vertex; const double* normal; const double* m3x4; const double* bones; };
 // The update itself: the new vertices and normals reach rf_vtx / rf_nrm -- arrays staged and copied, or the staged table of matrices applied to the
-// rest pose on the device -- and both trees are refitted, all on the context's stream.
+// groups' or the skin's rest pose on the device -- and both trees are refitted, all on the context's stream.
 static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     const size_t vd = ctx->rf_vtx.count(), nd = ctx->rf_nrm.count();
-    const bool normal = u.m3x4 ? nd != 0 : u.normal != nullptr;                  // are there new normals
-    if (u.m3x4) {
+    const bool normal = u.m3x4 || u.bones ? nd != 0 : u.normal != nullptr;       // are there new normals
+    if (u.bones) {
+        HIP_TRY(ctx->sk_stage.wait());
+        std::memcpy(ctx->sk_stage.host, u.bones, ctx->sk_table.bytes);
+    } else if (u.m3x4) {
         HIP_TRY(ctx->xf_stage.wait());
         for (uint32_t g = 0; g < ctx->xf_n_groups; g++) xf_group_record(u.m3x4 + 12 * size_t(g), ctx->xf_stage.host + XF_RECORD * size_t(g));
     } else {
@@ -1267,7 +1317,14 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     // kernel here.
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx->rf_watch.begin(s));
-    if (u.m3x4) {
+    if (u.bones) {
+        HIP_TRY(ctx->sk_watch.begin(s));
+        HIP_TRY(ctx->sk_stage.send(ctx->sk_table.p, 0, ctx->sk_table.count(), s));
+        HIP_TRY(launch_sk_vertices(ctx->sk_rest_vtx.p, ctx->sk_vbone.p, ctx->sk_vweight.p, ctx->sk_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
+        HIP_TRY(launch_sk_normals(ctx->sk_rest_nrm.p, ctx->sk_nbone.p, ctx->sk_nweight.p, ctx->sk_table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+        HIP_TRY(ctx->sk_watch.end(s));
+        ctx->sk_updates++;
+    } else if (u.m3x4) {
         HIP_TRY(ctx->xf_watch.begin(s));
         HIP_TRY(ctx->xf_stage.send(ctx->xf_table.p, 0, ctx->xf_table.count(), s));
         HIP_TRY(launch_xf_vertices(ctx->xf_rest_vtx.p, ctx->xf_vgroup.p, ctx->xf_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
@@ -1341,6 +1398,69 @@ mcpt_status mcpt_get_transform_info(mcpt_ctx* ctx, mcpt_transform_info* out) {
     HIP_TRY(ctx->xf_watch.settle());
     std::memset(out, 0, sizeof *out);
     out->struct_size = sizeof *out; out->n_groups = ctx->xf_n_groups; out->updates = ctx->xf_updates; out->last_ms = ctx->xf_watch.last_ms;
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ linear-blend skinning
+// One array of influence records (SK_INFLUENCES ids and weights each) against mcpt_set_vertex_skin's rules; `what` names the record in the message.
+static mcpt_status sk_check_records(const uint32_t* bone, const double* weight, uint32_t n, uint32_t n_bones, const std::string& who, const char* what) {
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* b = bone + SK_INFLUENCES * size_t(i); const double* w = weight + SK_INFLUENCES * size_t(i);
+        const std::string rec = who + what + " " + std::to_string(i);
+        for (int k = 0; k < SK_INFLUENCES; k++) {
+            if (b[k] >= n_bones) return fail(MCPT_ERR_INVALID_ARG, rec + ": bone id >= n_bones");
+            if (!(w[k] >= 0.0 && w[k] <= 1.0)) return fail(MCPT_ERR_INVALID_ARG, rec + ": a weight is not finite or outside [0, 1]");
+        }
+        const double sum = ((w[0] + w[1]) + w[2]) + w[3];
+        if (!(std::fabs(sum - 1.0) <= 1e-6)) return fail(MCPT_ERR_INVALID_ARG, rec + ": the weights do not sum to 1 within 1e-6");
+    }
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_set_vertex_skin(mcpt_ctx* ctx, const uint32_t* vertex_bone, const double* vertex_weight, uint32_t n_vertex, const uint32_t* normal_bone,
+                                 const double* normal_weight, uint32_t n_normal, uint32_t n_bones) {
+    const std::string who = "mcpt_set_vertex_skin: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if (n_vertex != ctx->rf_n_vertex || n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_vertex / n_normal differ from the scene's");
+    if (!vertex_bone || !vertex_weight || (n_normal && (!normal_bone || !normal_weight))) return fail(MCPT_ERR_INVALID_ARG, who + "null bone or weight array");
+    if (n_bones < 1 || uint64_t(n_bones) > SK_INFLUENCES * (uint64_t(n_vertex) + n_normal)) return fail(MCPT_ERR_INVALID_ARG, who + "n_bones must be in [1, 4 (n_vertex + n_normal)]");
+    st = sk_check_records(vertex_bone, vertex_weight, n_vertex, n_bones, who, "vertex"); if (st != MCPT_OK) return st;
+    st = sk_check_records(normal_bone, normal_weight, n_normal, n_bones, who, "normal"); if (st != MCPT_OK) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // rf_vtx / rf_nrm are final, and no copy out of the old stage is under way
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    st = sk_alloc(ctx, n_bones); if (st != MCPT_OK) return st;
+    std::vector<double> vtx(ctx->rf_vtx.count());
+    {   Scratch s(ctx->stream);
+        if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->sk_rest_vtx.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->sk_rest_nrm.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(s.put(ctx->sk_vbone.p, vertex_bone, ctx->sk_vbone.count())); HIP_TRY(s.put(ctx->sk_vweight.p, vertex_weight, ctx->sk_vweight.count()));
+        HIP_TRY(s.put(ctx->sk_nbone.p, normal_bone, ctx->sk_nbone.count())); HIP_TRY(s.put(ctx->sk_nweight.p, normal_weight, ctx->sk_nweight.count()));
+        HIP_TRY(s.fetch(vtx.data(), ctx->rf_vtx.p, vtx.size())); HIP_TRY(s.finish()); }
+    for (uint32_t v = 0; v < n_vertex; v++) {
+        if (!ctx->rf_used_vertex[v]) continue;
+        double far = 0.0;
+        for (int a = 0; a < 3; a++) far = std::max(far, std::fabs(vtx[3 * size_t(v) + a]));
+        for (int k = 0; k < SK_INFLUENCES; k++)
+            if (vertex_weight[SK_INFLUENCES * size_t(v) + k] > 0.0) { double& r = ctx->sk_radius[vertex_bone[SK_INFLUENCES * size_t(v) + k]]; r = std::max(r, far); }
+    }
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_update_skin(mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    st = sk_check_update(ctx, m3x4, n_bones, "mcpt_update_skin"); if (st != MCPT_OK) return st;
+    return rf_enqueue_update(ctx, RfUpdate{nullptr, nullptr, nullptr, m3x4});
+}
+
+mcpt_status mcpt_get_skin_info(mcpt_ctx* ctx, mcpt_skin_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    HIP_TRY(ctx->sk_watch.settle());
+    std::memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out; out->n_bones = ctx->sk_n_bones; out->updates = ctx->sk_updates; out->last_ms = ctx->sk_watch.last_ms;
     return MCPT_OK;
 }
 
@@ -1763,6 +1883,15 @@ mcpt_status mcpt_update_transforms_reproject(mcpt_ctx* ctx, const double* m3x4, 
     st = xf_check_update(ctx, m3x4, n_groups, fn); if (st != MCPT_OK) return st;
     if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
     const RfUpdate update{nullptr, nullptr, m3x4};                               // §16: the matrices in place of the arrays, the same frame
+    return rp_frame(ctx, &update, cm, opts, fn);
+}
+
+mcpt_status mcpt_update_skin_reproject(mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
+    const char* const fn = "mcpt_update_skin_reproject";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    st = sk_check_update(ctx, m3x4, n_bones, fn); if (st != MCPT_OK) return st;
+    if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
+    const RfUpdate update{nullptr, nullptr, nullptr, m3x4};                      // §18: the bones in place of the arrays, the same frame
     return rp_frame(ctx, &update, cm, opts, fn);
 }
 

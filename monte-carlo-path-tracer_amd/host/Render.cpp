@@ -132,17 +132,21 @@ bool Render::film_to_device(Scene& scene, const char* who, bool& ok) {
     ok = true;
     return upload;
 }
-bool Render::update_reproject(Scene& scene, Model& m, float max_history) { return update_reproject(scene, &m, nullptr, nullptr, max_history); }
-bool Render::update_reproject(Scene& scene, Model& m, const CameraInfo& camera, float max_history) { return update_reproject(scene, &m, nullptr, &camera, max_history); }
-bool Render::update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, float max_history) { return update_reproject(scene, nullptr, &matrices, nullptr, max_history); }
+bool Render::update_reproject(Scene& scene, Model& m, float max_history) { return update_reproject(scene, &m, nullptr, false, nullptr, max_history); }
+bool Render::update_reproject(Scene& scene, Model& m, const CameraInfo& camera, float max_history) { return update_reproject(scene, &m, nullptr, false, &camera, max_history); }
+bool Render::update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, float max_history) { return update_reproject(scene, nullptr, &matrices, false, nullptr, max_history); }
 bool Render::update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history) {
-    return update_reproject(scene, nullptr, &matrices, &camera, max_history);
+    return update_reproject(scene, nullptr, &matrices, false, &camera, max_history);
 }
-// The geometry comes from `m` (its arrays) or from `matrices` (one 3x4 per group, §16): the rest is the same.
-bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>* matrices, const CameraInfo* camera, float max_history) {
+bool Render::update_skin_reproject(Scene& scene, const std::vector<double>& matrices, float max_history) { return update_reproject(scene, nullptr, &matrices, true, nullptr, max_history); }
+bool Render::update_skin_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history) {
+    return update_reproject(scene, nullptr, &matrices, true, &camera, max_history);
+}
+// The geometry comes from `m` (its arrays) or from `matrices` (one 3x4 per group, §16, or per bone, §18): the rest is the same.
+bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>* matrices, bool bones, const CameraInfo* camera, float max_history) {
     if (!ctx) return false;
-    const char* const who = m ? "update_reproject" : "update_transforms_reproject";
-    if (!m && matrices->size() % 12) { std::cerr << "Error: Render::" << who << ": need 12 doubles per group" << std::endl; return false; }
+    const char* const who = m ? "update_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject";
+    if (!m && matrices->size() % 12) { std::cerr << "Error: Render::" << who << ": need 12 doubles per " << (bones ? "bone" : "group") << std::endl; return false; }
     bool ok = false;
     const bool upload = film_to_device(scene, who, ok);
     if (!ok) return false;
@@ -150,9 +154,10 @@ bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>*
     mcpt_reproject_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.feature_spp = 4; o.feature_seed = seed; o.max_history = max_history;
     const mcpt_status st = m ? mcpt_update_vertices_reproject(ctx, reinterpret_cast<const double*>(m->vertex.data()), uint32_t(m->vertex.size()),
                                                               reinterpret_cast<const double*>(m->normal.data()), uint32_t(m->normal.size()), camera ? &k : nullptr, &o)
+                     : bones ? mcpt_update_skin_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o)
                              : mcpt_update_transforms_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o);
     if (st != MCPT_OK) {
-        std::cerr << "Error: mcpt_" << (m ? "update_vertices_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
+        std::cerr << "Error: mcpt_" << (m ? "update_vertices_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
         if (upload && mcpt_clear_accum(ctx) != MCPT_OK) std::cerr << "Error: mcpt_clear_accum: " << mcpt_last_error() << std::endl;   // the Scene still holds them
         return false;
     }
@@ -208,6 +213,40 @@ bool Render::update_transforms(Scene& scene, const std::vector<double>& matrices
     if (!ctx) return false;
     if (matrices.size() % 12) { std::cerr << "Error: Render::update_transforms: need 12 doubles per group" << std::endl; return false; }
     if (mcpt_update_transforms(ctx, matrices.data(), uint32_t(matrices.size() / 12)) != MCPT_OK) { std::cerr << "Error: mcpt_update_transforms: " << mcpt_last_error() << std::endl; return false; }
+    return restart(scene);
+}
+bool Render::set_skin(Scene&, Model& m, const std::vector<uint32_t>& vertex_bone, const std::vector<double>& vertex_weight, uint32_t n_bones) {
+    if (!ctx) return false;
+    const size_t K = MCPT_SKIN_INFLUENCES, nv = m.vertex.size(), nn = m.normal.size();
+    if (vertex_bone.size() != K * nv || vertex_weight.size() != K * nv) { std::cerr << "Error: Render::set_skin: need 4 bone ids and 4 weights per vertex" << std::endl; return false; }
+    // every normal takes the influences of the vertex it is paired with in a face corner; bone 0 with weight 1 where no face uses it
+    const size_t none = ~size_t(0);
+    std::vector<size_t> first(nn, none);
+    for (size_t f = 0; f < m.face.size(); f++)
+        for (int c = 0; c < 3; c++) {
+            const int vi = m.face[f][c][0], ni = m.face[f][c][1];
+            if (vi < 0 || size_t(vi) >= nv || ni < 0 || size_t(ni) >= nn) { std::cerr << "Error: Render::set_skin: face " << f << " names a vertex or normal out of range" << std::endl; return false; }
+            size_t& v0 = first[size_t(ni)];
+            if (v0 == none) { v0 = size_t(vi); continue; }
+            if (std::memcmp(&vertex_bone[K * v0], &vertex_bone[K * size_t(vi)], K * sizeof(uint32_t)) || std::memcmp(&vertex_weight[K * v0], &vertex_weight[K * size_t(vi)], K * sizeof(double))) {
+                std::cerr << "Error: Render::set_skin: normal " << ni << " is paired with vertices " << v0 << " and " << vi << ", whose influences differ (duplicate it in the file)" << std::endl;
+                return false;
+            }
+        }
+    std::vector<uint32_t> nb(K * nn, 0u); std::vector<double> nw(K * nn, 0.0);
+    for (size_t i = 0; i < nn; i++) {
+        if (first[i] == none) { nw[K * i] = 1.0; continue; }
+        std::copy_n(&vertex_bone[K * first[i]], K, &nb[K * i]); std::copy_n(&vertex_weight[K * first[i]], K, &nw[K * i]);
+    }
+    if (mcpt_set_vertex_skin(ctx, vertex_bone.data(), vertex_weight.data(), uint32_t(nv), nn ? nb.data() : nullptr, nn ? nw.data() : nullptr, uint32_t(nn), n_bones) != MCPT_OK) {
+        std::cerr << "Error: mcpt_set_vertex_skin: " << mcpt_last_error() << std::endl; return false;
+    }
+    return true;
+}
+bool Render::update_skin(Scene& scene, const std::vector<double>& matrices) {
+    if (!ctx) return false;
+    if (matrices.size() % 12) { std::cerr << "Error: Render::update_skin: need 12 doubles per bone" << std::endl; return false; }
+    if (mcpt_update_skin(ctx, matrices.data(), uint32_t(matrices.size() / 12)) != MCPT_OK) { std::cerr << "Error: mcpt_update_skin: " << mcpt_last_error() << std::endl; return false; }
     return restart(scene);
 }
 bool Render::update_materials(Scene& scene, Model& m) {

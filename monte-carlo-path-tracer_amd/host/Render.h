@@ -61,6 +61,16 @@ public:
     bool update_transforms(Scene& scene, const std::vector<double>& matrices);
     bool update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, float max_history = 0);
     bool update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history = 0);
+    // Deforming parts.  set_skin: four bone ids and four weights per vertex of `m_model`, the Model this Render was made from
+    // (MCPT_FLAG_DYNAMIC); every normal takes the influences of the vertex it is paired with in a face corner (bone 0 with weight 1 when no
+    // face uses it); the scene as it is now becomes the skin's rest pose; false when two corners pair a normal with vertices whose influences
+    // differ.  The film is not touched.  update_skin: one row-major 3x4 matrix [A | t] per bone (12 doubles each), blended per vertex and
+    // applied to the rest pose on the device (mcpt_update_skin) -- only the matrices cross the bus.  Starts the picture again like update();
+    // update_skin_reproject carries it over like update_reproject.  false (Render and Scene unchanged) on failure.
+    bool set_skin(Scene& scene, Model& m_model, const std::vector<uint32_t>& vertex_bone, const std::vector<double>& vertex_weight, uint32_t n_bones);
+    bool update_skin(Scene& scene, const std::vector<double>& matrices);
+    bool update_skin_reproject(Scene& scene, const std::vector<double>& matrices, float max_history = 0);
+    bool update_skin_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history = 0);
     // New trees for the geometry as it is now (mcpt_rebuild_trees): after update() / update_transforms() have moved the scene far
     // (mcpt_update_info::wide_area_ratio says how far) the refitted trees are sound and slow; this builds them anew on the context.  The picture
     // goes ON: `scene`'s film, the sample numbering and the feature buffers stay, the scene looks the same from every pixel.  Synchronous.  false
@@ -83,7 +93,7 @@ private:
     void create(Model& m, const mcpt_opts& opts);
     bool restart(Scene& scene);
     bool film_to_device(Scene& scene, const char* who, bool& ok);
-    bool update_reproject(Scene& scene, Model* m_model, const std::vector<double>* matrices, const CameraInfo* camera, float max_history);
+    bool update_reproject(Scene& scene, Model* m_model, const std::vector<double>* matrices, bool bones, const CameraInfo* camera, float max_history);
 };
 // Fills an mcpt_scene_desc that points INTO `m` (and into the two scratch vectors); valid while all three live.
 void model_to_desc(Model& m, std::vector<mcpt_material>& mats, std::vector<mcpt_texture>& texs, mcpt_scene_desc& d);

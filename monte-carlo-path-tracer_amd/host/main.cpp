@@ -35,7 +35,11 @@ static void usage() {
                  "                          [--spin MTLNAME]   with --turntable: the faces of that material turn as one rigid part, by 360 k / N degrees in frame k about\n"
                  "                                        the camera's up axis through their bounding box's centre (one 3x4 matrix per frame, applied on the device;\n"
                  "                                        honours --reproject; not with --wobble)\n"
-                 "                          [--rebuild-above R]   with --turntable and --wobble or --spin: after a frame's update the trees are built anew\n"
+                 "                          [--bend MTLNAME DEG]   with --turntable: the faces of that material bend as a two-bone part (linear-blend skinning on the\n"
+                 "                                        device): a vertex follows the upper bone by its height inside the part's y-extent, the lower bone stays,\n"
+                 "                                        the upper one turns by DEG sin(2 pi k / N) about z through the part's centre in frame k (honours --reproject;\n"
+                 "                                        not with --wobble or --spin)\n"
+                 "                          [--rebuild-above R]   with --turntable and --wobble, --spin or --bend: after a frame's update the trees are built anew\n"
                  "                                        (mcpt_rebuild_trees, film kept) when wide_area_ratio exceeds R; prints frame, ratio and cost per rebuild\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
@@ -66,7 +70,7 @@ int main(int argc, char** argv) {
     bool reproject = false; float history = 0.f;
     bool wobble = false; double wobble_a = 0.0;
     bool pulse = false; double pulse_a = 0.0;
-    std::string spin;
+    std::string spin, bend; double bend_deg = 0.0;
     bool rebuild = false; double rebuild_above = 0.0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
@@ -89,6 +93,7 @@ int main(int argc, char** argv) {
         else if (a == "--wobble") { wobble = true; wobble_a = std::atof(next()); }
         else if (a == "--light-pulse") { pulse = true; pulse_a = std::atof(next()); }
         else if (a == "--spin") spin = next();
+        else if (a == "--bend") { bend = next(); bend_deg = std::atof(next()); }
         else if (a == "--rebuild-above") { rebuild = true; rebuild_above = std::atof(next()); }
         else { usage(); return 2; }
     }
@@ -99,8 +104,11 @@ int main(int argc, char** argv) {
     if (pulse && (!turntable || !(std::fabs(pulse_a) <= 1e6))) { std::cerr << "Error: --light-pulse A needs --turntable N and a finite A" << std::endl; return 2; }
     if (pulse && reproject) { std::cerr << "Error: --light-pulse restarts the film every frame: radiance reprojected across it would be the old light's (drop --reproject)" << std::endl; return 2; }
     if (!spin.empty() && (!turntable || wobble)) { std::cerr << "Error: --spin MTLNAME needs --turntable N and no --wobble (both write the vertices)" << std::endl; return 2; }
-    if (rebuild && (!turntable || !(wobble || !spin.empty()) || !(rebuild_above >= 0.0))) { std::cerr << "Error: --rebuild-above R needs --turntable N with --wobble or --spin, and R >= 0" << std::endl; return 2; }
-    if (wobble || !spin.empty()) flags |= MCPT_FLAG_DYNAMIC;
+    if (!bend.empty() && (!turntable || wobble || !spin.empty() || !(std::fabs(bend_deg) <= 1e6))) {
+        std::cerr << "Error: --bend MTLNAME DEG needs --turntable N, a finite DEG and neither --wobble nor --spin (all three write the vertices)" << std::endl; return 2;
+    }
+    if (rebuild && (!turntable || !(wobble || !spin.empty() || !bend.empty()) || !(rebuild_above >= 0.0))) { std::cerr << "Error: --rebuild-above R needs --turntable N with --wobble, --spin or --bend, and R >= 0" << std::endl; return 2; }
+    if (wobble || !spin.empty() || !bend.empty()) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
     std::cout << model.face.size() << " " << model.normal.size() << " " << model.vertex.size() << std::endl;   // main.cpp:14
@@ -187,6 +195,34 @@ int main(int argc, char** argv) {
             for (int a = 0; a < 3; a++) pivot[a] = 0.5 * (lo[a] + hi[a]);
             if (!renders[0]->set_groups(scene, model, face_group)) return 1;
         }
+        // --bend MTLNAME DEG: that material's faces follow bones 1 and 2 by height, everything else bone 0
+        if (!bend.empty()) {
+            const int mtl = model.material_index(bend);
+            if (mtl < 0) { std::cerr << "Error: --bend: no material named " << bend << std::endl; return 1; }
+            std::vector<uint8_t> part(model.vertex.size(), 0);
+            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+            size_t n_bend = 0;
+            for (size_t i = 0; i < model.face.size(); i++) {
+                if (model.face[i][0][3] != mtl) continue;
+                n_bend++;
+                for (int c = 0; c < 3; c++) {
+                    const int vi = model.face[i][c][0];
+                    if (vi < 0 || size_t(vi) >= model.vertex.size()) continue;   // (mcpt_create has refused such a face already)
+                    part[size_t(vi)] = 1;
+                    const dvec3& p = model.vertex[size_t(vi)]; const double q[3] = {p.x, p.y, p.z};
+                    for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], q[a]); hi[a] = std::max(hi[a], q[a]); }
+                }
+            }
+            if (!n_bend) { std::cerr << "Error: --bend: no face uses material " << bend << std::endl; return 1; }
+            for (int a = 0; a < 3; a++) pivot[a] = 0.5 * (lo[a] + hi[a]);
+            std::vector<uint32_t> bone(4 * model.vertex.size(), 0u); std::vector<double> weight(4 * model.vertex.size(), 0.0);
+            for (size_t i = 0; i < model.vertex.size(); i++) {
+                if (!part[i]) { weight[4 * i] = 1.0; continue; }             // bone 0
+                const double t = hi[1] > lo[1] ? std::min(1.0, std::max(0.0, (model.vertex[i].y - lo[1]) / (hi[1] - lo[1]))) : 0.0;
+                bone[4 * i] = 1u; weight[4 * i] = 1.0 - t; bone[4 * i + 1] = 2u; weight[4 * i + 1] = t;
+            }
+            if (!renders[0]->set_skin(scene, model, bone, weight, 3u)) return 1;
+        }
         for (uint32_t f = 0; f < turntable; f++) {
             const double a = 2.0 * 3.14159265358979323846 * double(f) / double(turntable), ca = std::cos(a), sa = std::sin(a);
             const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2], kx[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
@@ -224,6 +260,15 @@ int main(int argc, char** argv) {
                 }
                 if (reproject && f > 0 ? !renders[0]->update_transforms_reproject(scene, m, cam, history)
                                        : !(renders[0]->update_transforms(scene, m) && renders[0]->set_camera(scene, cam))) return 1;
+            } else if (!bend.empty()) {                                      // bones 0 and 1 stay; bone 2 turns about z through the part's centre
+                const double b = bend_deg * 3.14159265358979323846 / 180.0 * sa, cb = std::cos(b), sb = std::sin(b);
+                std::vector<double> m(36, 0.0);
+                for (int g = 0; g < 3; g++) m[12 * g] = m[12 * g + 5] = m[12 * g + 10] = 1.0;
+                double* u = m.data() + 24;
+                u[0] = cb; u[1] = -sb; u[3] = pivot[0] - (cb * pivot[0] - sb * pivot[1]);
+                u[4] = sb; u[5] = cb; u[7] = pivot[1] - (sb * pivot[0] + cb * pivot[1]);
+                if (reproject && f > 0 ? !renders[0]->update_skin_reproject(scene, m, cam, history)
+                                       : !(renders[0]->update_skin(scene, m) && renders[0]->set_camera(scene, cam))) return 1;
             } else
             if (reproject && f > 0 ? !renders[0]->set_camera_reproject(scene, cam, history) : !renders[0]->set_camera(scene, cam)) return 1;
             if (rebuild) {                                                   // --rebuild-above R: the refitted trees have grown past R times their built size
