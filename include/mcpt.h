@@ -284,7 +284,7 @@ mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* camera);
 mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal);
 
 typedef struct mcpt_update_info {
-    uint32_t struct_size, updates;      /* mcpt_update_vertices / _transforms / _skin (+ _reproject) calls on this context so far */
+    uint32_t struct_size, updates;      /* mcpt_update_vertices / _transforms / _skin / _morph (+ _reproject) calls on this context so far */
     double   last_update_ms;            /* device time of the last one, first to last operation on the stream (HIP events) */
     double   wide_area_ratio;           /* sum of the child-box areas of the 8-wide tree now / when it was built, by mcpt_create or by the last
                                            mcpt_rebuild_trees (dequantised boxes; 1.0 before any update and right after a rebuild) */
@@ -328,7 +328,7 @@ typedef struct mcpt_reproject_opts {
     uint32_t reserved[3];
 } mcpt_reproject_opts;
 typedef struct mcpt_reproject_info {
-    uint32_t struct_size, reprojections;   /* mcpt_set_camera_reproject + mcpt_update_{vertices,transforms,skin}_reproject calls */
+    uint32_t struct_size, reprojections;   /* mcpt_set_camera_reproject + mcpt_update_{vertices,transforms,skin,morph}_reproject calls */
     uint64_t pixels_reused;                /* pixels of the last call written with a history of >= 1 sample */
     double   last_ms;                      /* device time of the last call, first to last operation on the stream (HIP events) */
     uint32_t reserved[4];
@@ -518,6 +518,80 @@ typedef struct mcpt_skin_info {
 } mcpt_skin_info;
 mcpt_status mcpt_get_skin_info(mcpt_ctx* ctx, mcpt_skin_info* out);   /* synchronises */
 
+/* ---- deforming parts: morph targets (blend shapes) on the device -------------------------------------------------------------- */
+/* A facial expression, a bulging muscle or a breathing chest is a weighted sum of per-vertex displacement sets, not a matrix per bone.  The caller
+ * names the targets once -- each a sparse list of records and their displacements -- and then sends ONE WEIGHT PER TARGET and frame: the device
+ * keeps the morph's REST POSE and writes the current vertices and normals from it.  All calls need MCPT_FLAG_DYNAMIC (else MCPT_ERR_UNSUPPORTED).
+ *
+ * mcpt_set_vertex_morph: set-up, synchronous, the twin of mcpt_set_vertex_skin.  `vertex` holds the targets over the vertices, `normal` (NULL =
+ * normals are not morphed: every call writes the rest pose's normals) the targets over the normals; normal->n_targets must equal
+ * vertex->n_targets, one weight drives both.  A target may have no entries, and so may all of them.  The context's CURRENT vertices and normals
+ * become the morph's OWN rest pose (copied device to device) -- independent of the groups' and the skin's; all three may be set on one context.
+ * The host turns the per-target lists into one list per record (a counting sort; inside a record the entries are ordered by ascending target id)
+ * and keeps R, the largest |coordinate| among the rest-pose vertices that a face uses (one read-back of the vertices), and per target D_k, the
+ * largest |delta component| among its vertex entries whose vertex a face uses (0 without any).  Calling it again replaces the targets and takes
+ * the rest pose anew.  Allocates, counted in device_bytes: 24 B per vertex and per normal (rest pose), 4 B (n_vertex + 1) + 4 B (n_normal + 1)
+ * (list offsets), 32 B per entry and 8 B per target (the weights), plus a pinned stage of the weights' size.  mcpt_clone_to_device carries all of
+ * it with R and D_k; mcpt_rebuild_trees keeps it (it is per vertex, not per leaf: nothing is permuted).
+ *  - Refused with nothing changed, MCPT_ERR_INVALID_ARG: counts that differ from the scene's; NULL `vertex`; a wrong struct_size; n_targets
+ *    outside [1, 65536]; NULL target_offset, or NULL index / delta where entries exist; offsets that decrease or do not start at 0; an index >=
+ *    the record count; indices not STRICTLY ascending inside a target (so no record twice in one target); a delta component that is not finite
+ *    or has |d| > 1e18.
+ *
+ * mcpt_update_morph: `weight` holds n_targets doubles; they may be negative or exceed 1 (extrapolation) and are never renormalised.  Everything
+ * in fp64, one correctly rounded operation each.  A vertex with >= 1 entry: p = rest, then per entry in stored order (ascending target) and per
+ * component p = p + weight[target] * d -- EVERY entry, one whose weight is 0 included (skipping it could change the sign of a zero).  A vertex
+ * without entries: the rest pose's, bit for bit.  A normal with >= 1 entry: the same sum, then divided by its length sqrt((x x + y y) + z z)
+ * when that is finite and > 0 and left as it is otherwise (mcpt_update_transforms' rule).  A normal without entries: copied, NOT normalised.
+ * Every record is written on every call.
+ *  - bones_m3x4 == NULL: the morphed arrays ARE the context's new vertices and normals.
+ *  - bones_m3x4 != NULL: MORPH, THEN SKIN, the order glTF prescribes.  Needs mcpt_set_vertex_skin on this context; m3x4 and n_bones are
+ *    mcpt_update_skin's.  The morphed arrays go to two scratch arrays (24 B per vertex and per normal, allocated by the first such call, counted
+ *    in device_bytes, carried by a clone) and mcpt_update_skin's kernels, with the skin's influences, read THEM as their rest pose: in this call
+ *    the skin's own rest pose is not read (and not changed) -- the morph's rest pose is the base.  mcpt_skin_info::updates advances too (its
+ *    last_ms does not: this call's time is mcpt_morph_info::last_ms).
+ * From there on the call IS mcpt_update_vertices after its upload: the same refit, ordering, bookkeeping (mcpt_get_update_info counts it, and
+ * last_update_ms spans the weights' copy, the kernels and the refit) and what it leaves untouched (film, counters) or drops (features, denoised
+ * film, tile error).
+ *  - Morphs apply to the morph's rest pose and never accumulate.  A later mcpt_update_vertices / _transforms / _skin overwrites what the call
+ *    wrote and leaves the morph's rest pose alone; the next mcpt_update_morph overwrites what they wrote and leaves their rest poses alone.
+ *  - Validated on the host before any device work, a refusal changes nothing; in this order: MCPT_ERR_UNSUPPORTED without MCPT_FLAG_DYNAMIC;
+ *    MCPT_ERR_INVALID_ARG when no morph is set, for NULL weights or another n_targets, for a weight that is not finite or has |w| > 1e18; when the
+ *    reach E = (1 + 2^-16) (R + sum_k |w_k| D_k) (summed in the order of k, starting from R) exceeds 1e18 or is not finite; with bones: when no
+ *    skin is set or for another n_bones, then mcpt_update_skin's matrix checks (finite entries, det A finite and non-zero), then its row bound
+ *    with E in place of EVERY bone's R_b.  Both bounds are CONSERVATIVE; the second may refuse a far-away bone without members that
+ *    mcpt_update_skin accepts; in exchange validation needs no device round trip.
+ *  - Asynchronous on the context's stream.  Weights (and bones) are staged through pinned memory and copied in stream order: the caller may reuse
+ *    its arrays when the call returns, and back-to-back calls cannot overtake each other.
+ *
+ * mcpt_update_morph_reproject is mcpt_update_vertices_reproject with the weights (and bones) in place of the upload; validation order: the above,
+ * the camera (when given), the options, MCPT_ERR_BVH_DEPTH.
+ *
+ * mcpt_probe_vertices (for tests and debugging; synchronous, needs MCPT_FLAG_DYNAMIC): the context's current vertices and normals as the device
+ * holds them now, whatever call wrote them.  Either output may be NULL.  Touches nothing. */
+typedef struct mcpt_morph_targets {      /* one set of sparse targets over an array of records (vertices, or normals) */
+    uint32_t        struct_size;
+    uint32_t        n_targets;
+    const uint32_t* target_offset;       /* n_targets + 1 entries, non-decreasing, [0] = 0: target k owns entries [off[k], off[k+1]) */
+    const uint32_t* index;               /* per entry the record it displaces; STRICTLY ascending inside a target (so: no duplicates) */
+    const double*   delta;               /* 3 doubles per entry */
+    uint32_t        reserved[4];
+} mcpt_morph_targets;
+mcpt_status mcpt_set_vertex_morph(mcpt_ctx* ctx, const mcpt_morph_targets* vertex, uint32_t n_vertex,
+                                  const mcpt_morph_targets* normal /* NULL = normals are not morphed */, uint32_t n_normal);
+mcpt_status mcpt_update_morph(mcpt_ctx* ctx, const double* weight, uint32_t n_targets, const double* bones_m3x4 /* NULL = no skinning */, uint32_t n_bones);
+mcpt_status mcpt_update_morph_reproject(mcpt_ctx* ctx, const double* weight, uint32_t n_targets, const double* bones_m3x4, uint32_t n_bones,
+                                        const mcpt_camera* camera /* NULL = keep */, const mcpt_reproject_opts* opts /* NULL = defaults */);
+typedef struct mcpt_morph_info {
+    uint32_t struct_size, n_targets;    /* targets of the morph set now (0 = none) */
+    uint32_t updates, reserved0;        /* mcpt_update_morph (+ _reproject) calls on this context so far */
+    uint64_t vertex_entries, normal_entries;   /* entries of the per-record lists */
+    double   last_ms;                   /* device time of the last one's deforming part: the weights' (and bones') copy and the morph (and skin) kernels */
+    uint32_t reserved[4];
+} mcpt_morph_info;
+mcpt_status mcpt_get_morph_info(mcpt_ctx* ctx, mcpt_morph_info* out);   /* synchronises */
+mcpt_status mcpt_probe_vertices(mcpt_ctx* ctx, double* out_vertex /* 3 n_vertex, may be NULL */, double* out_normal /* 3 n_normal, may be NULL */);
+
 /* ---- live scenes: new trees for the geometry as it is now -------------------------------------------------------------- */
 /* mcpt_update_vertices and mcpt_update_transforms refit: after a large deformation the trees are sound and slow.  mcpt_rebuild_trees builds BOTH
  * trees (binary and 8-wide) anew for the context's current vertices -- whatever the last update or transform wrote -- and keeps everything else.
@@ -534,7 +608,7 @@ mcpt_status mcpt_get_skin_info(mcpt_ctx* ctx, mcpt_skin_info* out);   /* synchro
  *    rank it has (the creation geometry's, as mcpt_update_vertices documents).
  *  - KEPT, because the scene looks the same from every pixel: the film or a bound accumulator, the counters, the stream binding, the camera, the
  *    feature buffers and the denoised film, the adaptive tile error, the reprojection buffers, the vertex groups with their rest pose and R_g,
- *    the skin with its rest pose and R_b, the materials, the textures, and the light list's membership and order (only the lights' leaf-order
+ *    the skin with its rest pose and R_b, the morph targets with their rest pose, R and D_k (and the morph-then-skin scratch), the materials, the textures, and the light list's membership and order (only the lights' leaf-order
  *    triangle index is renumbered).
  *  - Afterwards mcpt_update_info::wide_area_ratio is 1.0 (its base is the new tree) and `updates` is unchanged; mcpt_scene_info follows the new
  *    trees: n_nodes, bvh_depth, max_leaf, wide_nodes, wide_depth, traversal_bytes, wide_tree_hash, bvh_builder, and device_bytes counts what is

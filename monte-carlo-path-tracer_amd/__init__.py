@@ -21,6 +21,8 @@ from . import scenes  # noqa: F401  (re-export)
 from .rebuild_abi import REBUILD_DEVICE, REBUILD_HOST, REBUILD_SAME, RebuildInfo, RebuildOpts  # noqa: F401
 # mcpt_get_skin_info's struct and the influence count; tests/test_skin.py holds the layout to the header
 from .skin_abi import SKIN_INFLUENCES, SkinInfo  # noqa: F401
+# mcpt_set_vertex_morph's and mcpt_get_morph_info's structs and the flattening of a target list; tests/test_morph.py holds the layouts to the header
+from .morph_abi import MORPH_MAX_TARGETS, MorphInfo, MorphTargets, flatten_targets, targets_struct  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmcpt_hip.so")
@@ -286,6 +288,11 @@ def load_library() -> C.CDLL:
         "mcpt_update_skin": [vp, vp, C.c_uint32],
         "mcpt_update_skin_reproject": [vp, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
         "mcpt_get_skin_info": [vp, P(SkinInfo)],
+        "mcpt_set_vertex_morph": [vp, P(MorphTargets), C.c_uint32, P(MorphTargets), C.c_uint32],
+        "mcpt_update_morph": [vp, vp, C.c_uint32, vp, C.c_uint32],
+        "mcpt_update_morph_reproject": [vp, vp, C.c_uint32, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
+        "mcpt_get_morph_info": [vp, P(MorphInfo)],
+        "mcpt_probe_vertices": [vp, vp, vp],
         "mcpt_rebuild_trees": [vp, P(RebuildOpts)],
         "mcpt_get_rebuild_info": [vp, P(RebuildInfo)],
     }
@@ -315,6 +322,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_update_materials", "mcpt_update_texture", "mcpt_get_material_info", "mcpt_probe_lights", "mcpt_probe_face_classes",
     "mcpt_set_vertex_groups", "mcpt_update_transforms", "mcpt_update_transforms_reproject", "mcpt_get_transform_info",
     "mcpt_set_vertex_skin", "mcpt_update_skin", "mcpt_update_skin_reproject", "mcpt_get_skin_info",
+    "mcpt_set_vertex_morph", "mcpt_update_morph", "mcpt_update_morph_reproject", "mcpt_get_morph_info", "mcpt_probe_vertices",
     "mcpt_rebuild_trees", "mcpt_get_rebuild_info",
 ]
 
@@ -608,6 +616,48 @@ class Renderer:
         self._check(self.lib.mcpt_get_skin_info(self.ctx, C.byref(i)))
         return i
 
+    # ---- deforming parts: morph targets
+    def set_vertex_morph(self, vertex_targets, normal_targets=None):
+        """Morph targets (blend shapes): each argument a list with one (index array, (n, 3) delta array) pair per target -- the records the target
+        displaces, strictly ascending, and their displacements; normal_targets=None leaves the normals unmorphed, otherwise it has as many
+        targets as vertex_targets (one weight drives both).  The scene as it is now becomes the rest pose update_morph deforms.  Needs
+        FLAG_DYNAMIC.  Synchronous."""
+        v, keep_v = targets_struct(vertex_targets)
+        n, keep_n = (None, None) if normal_targets is None else targets_struct(normal_targets)
+        self._check(self.lib.mcpt_set_vertex_morph(self.ctx, C.byref(v), self.holder.desc.n_vertex, None if n is None else C.byref(n), self.holder.desc.n_normal))
+
+    @staticmethod
+    def _weights_and_bones(weights, bones):
+        w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+        m = None if bones is None else Renderer._matrices(bones)
+        return w, m
+
+    def update_morph(self, weights, bones=None):
+        """One weight per target: every vertex and normal becomes its REST pose plus the weighted displacements of its entries, summed on the
+        device in a fixed order (never accumulated over calls), then update_vertices' refit: only the weights cross the bus.  bones: one 3x4
+        matrix per bone of the skin set with set_vertex_skin -- morph, then skin, in one call.  Asynchronous; the caller clears the film."""
+        w, m = self._weights_and_bones(weights, bones)
+        self._check(self.lib.mcpt_update_morph(self.ctx, _ptr(w), w.shape[0], _ptr(m), 0 if m is None else m.shape[0]))
+
+    def update_morph_reproject(self, weights, bones=None, camera=None, **opts):
+        """update_morph that carries the film over, as update_vertices_reproject does; opts: reproject_camera's."""
+        w, m = self._weights_and_bones(weights, bones)
+        c = None if camera is None else C.byref(_camera_c(camera))
+        o = _reproject_opts(**opts)
+        self._check(self.lib.mcpt_update_morph_reproject(self.ctx, _ptr(w), w.shape[0], _ptr(m), 0 if m is None else m.shape[0], c, C.byref(o)))
+
+    def morph_info(self) -> MorphInfo:
+        i = MorphInfo()
+        self._check(self.lib.mcpt_get_morph_info(self.ctx, C.byref(i)))
+        return i
+
+    def vertices(self):
+        """(vertex, normal): the context's current vertices and normals as the device holds them, (n, 3) float64 each -- whatever update call
+        wrote them.  Needs FLAG_DYNAMIC.  Synchronous; touches nothing."""
+        v = np.empty((self.holder.desc.n_vertex, 3), np.float64); n = np.empty((self.holder.desc.n_normal, 3), np.float64)
+        self._check(self.lib.mcpt_probe_vertices(self.ctx, _ptr(v), _ptr(n)))
+        return v, n
+
     # ---- material, light and texture edits (DESIGN.md §15)
     def update_materials(self, materials, map_kd=None):
         """New ks / ns / radiance for the same number of materials (a list of scenes.Material); map_kd: per material the index of the creation
@@ -657,7 +707,7 @@ class Renderer:
 
     # ---- new trees for the geometry as it is now
     def rebuild(self, builder: int = REBUILD_SAME):
-        """Both trees built anew for the context's current vertices, in place; film, counters, features, groups, skin, materials and lights stay.
+        """Both trees built anew for the context's current vertices, in place; film, counters, features, groups, skin, morph targets, materials and lights stay.
         builder: REBUILD_SAME (the one the context was created with), REBUILD_HOST or REBUILD_DEVICE.  Needs FLAG_DYNAMIC.  Synchronous."""
         o = RebuildOpts()
         o.struct_size = C.sizeof(RebuildOpts); o.builder = int(builder)

@@ -13,6 +13,7 @@
 #include "rebuild_plan.h"
 #include "transform.h"
 #include "skin.h"
+#include "morph.h"
 #include "reproject.h"
 #include "materials.h"
 
@@ -220,6 +221,16 @@ struct mcpt_ctx {
     Staging<double> sk_stage; std::vector<double> sk_radius;
     Stopwatch sk_watch;
     uint32_t sk_n_bones = 0, sk_updates = 0;
+    // Morph targets (morph.hip), allocated by mcpt_set_vertex_morph and counted in device_bytes: the morph's OWN rest pose (rf_vtx's
+    // and rf_nrm's sizes; independent of the groups' and the skin's), per array of records its n + 1 list offsets and its 32-byte entries, the
+    // table of one weight per target and its pinned staging.  mo_tmp_vtx / mo_tmp_nrm (rf_vtx's and rf_nrm's sizes, counted too) are allocated by
+    // the first mcpt_update_morph WITH bones: the morphed arrays that skin.hip's kernels then read as their rest pose (those kernels' `rest` and
+    // `out` are __restrict__: they cannot work in place).  On the host R, the largest |coordinate| among the rest-pose vertices that a face uses,
+    // and per target D_k, the largest |delta component| among its entries on such vertices (what mcpt_update_morph validates against).
+    DevBuf<double> mo_rest_vtx, mo_rest_nrm, mo_weight, mo_tmp_vtx, mo_tmp_nrm; DevBuf<uint32_t> mo_voffset, mo_noffset; DevBuf<MoEntry> mo_ventry, mo_nentry;
+    Staging<double> mo_stage; std::vector<double> mo_delta; double mo_radius = 0.0;
+    Stopwatch mo_watch;
+    uint32_t mo_n_targets = 0, mo_updates = 0;
     // Temporal reprojection (reproject.hip), allocated by the first reprojection call: the old view's features (2 per pixel, swapped
     // with dn_feat per call), a copy of the old film and the reuse counter.
     // Motion-vector reprojection adds, on the first mcpt_update_vertices_reproject: the first hit of every pixel-centre ray and
@@ -506,6 +517,23 @@ static mcpt_status sk_alloc(mcpt_ctx* c, uint32_t n_bones) {
     c->sk_n_bones = n_bones; c->sk_radius.assign(n_bones, 0.0);
     return MCPT_OK;
 }
+// The buffers of §19 for n_targets targets with the given entry counts, all or none: a context that had a morph keeps it when an allocation fails.
+static mcpt_status mo_alloc(mcpt_ctx* c, uint32_t n_targets, size_t vertex_entries, size_t normal_entries) {
+    uint64_t* tally = &c->info.device_bytes;
+    HIP_TRY(alloc_all(Want(c->mo_rest_vtx, c->rf_vtx.count(), tally), Want(c->mo_rest_nrm, c->rf_nrm.count(), tally),
+                      Want(c->mo_voffset, size_t(c->rf_n_vertex) + 1, tally), Want(c->mo_noffset, size_t(c->rf_n_normal) + 1, tally),
+                      Want(c->mo_ventry, vertex_entries, tally), Want(c->mo_nentry, normal_entries, tally), Want(c->mo_weight, n_targets, tally),
+                      Want(c->mo_stage, n_targets), Want(c->mo_watch, 1, nullptr, !c->mo_watch.ev0)));
+    c->mo_n_targets = n_targets; c->mo_delta.assign(n_targets, 0.0); c->mo_radius = 0.0;
+    return MCPT_OK;
+}
+// The scratch arrays of "morph, then skin" (§19), allocated once.
+static mcpt_status mo_ensure_scratch(mcpt_ctx* c) {
+    if (c->mo_tmp_vtx.p) return MCPT_OK;
+    uint64_t* tally = &c->info.device_bytes;
+    HIP_TRY(alloc_all(Want(c->mo_tmp_vtx, c->rf_vtx.count(), tally), Want(c->mo_tmp_nrm, c->rf_nrm.count(), tally)));
+    return MCPT_OK;
+}
 static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     c->rf_n_vertex = src->rf_n_vertex; c->rf_n_normal = src->rf_n_normal; c->rf_used_vertex = src->rf_used_vertex;
     c->rf_bin_level = src->rf_bin_level; c->rf_wide_level = src->rf_wide_level; c->rf_area0 = src->rf_area0;
@@ -528,6 +556,15 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
         HIP_TRY(copy(c->sk_rest_vtx, src->sk_rest_vtx)); HIP_TRY(copy(c->sk_rest_nrm, src->sk_rest_nrm));
         HIP_TRY(copy(c->sk_vbone, src->sk_vbone)); HIP_TRY(copy(c->sk_nbone, src->sk_nbone));
         HIP_TRY(copy(c->sk_vweight, src->sk_vweight)); HIP_TRY(copy(c->sk_nweight, src->sk_nweight));
+    }
+    if (src->mo_n_targets) {                                               // the morph, its rest pose, R and D_k travel with the clone (§19)
+        mcpt_status ms = mo_alloc(c, src->mo_n_targets, src->mo_ventry.count(), src->mo_nentry.count()); if (ms != MCPT_OK) return ms;
+        c->mo_delta = src->mo_delta; c->mo_radius = src->mo_radius;
+        auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
+        HIP_TRY(copy(c->mo_rest_vtx, src->mo_rest_vtx)); HIP_TRY(copy(c->mo_rest_nrm, src->mo_rest_nrm));
+        HIP_TRY(copy(c->mo_voffset, src->mo_voffset)); HIP_TRY(copy(c->mo_noffset, src->mo_noffset));
+        HIP_TRY(copy(c->mo_ventry, src->mo_ventry)); HIP_TRY(copy(c->mo_nentry, src->mo_nentry));
+        if (src->mo_tmp_vtx.p) { ms = mo_ensure_scratch(c); if (ms != MCPT_OK) return ms; }   // (scratch: its contents are not carried)
     }
     HIP_TRY(hipDeviceSynchronize());
     return MCPT_OK;
@@ -1275,7 +1312,8 @@ static mcpt_status xf_check_update(const mcpt_ctx* ctx, const double* m3x4, uint
     return MCPT_OK;
 }
 // mcpt_update_skin's rules for its matrices (§18), host only, as xf_check_update: the conservative row bound against R_b carries a slack factor.
-static mcpt_status sk_check_update(const mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones, const char* fn) {
+// `every_radius` (§19, morph then skin): the radius that stands for EVERY bone's R_b -- the morphed pose's reach, not the skin's rest pose.
+static mcpt_status sk_check_update(const mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones, const char* fn, const double* every_radius = nullptr) {
     const std::string who = std::string(fn) + ": ";
     if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
     if (!ctx->sk_n_bones) return fail(MCPT_ERR_INVALID_ARG, who + "no skin is set (mcpt_set_vertex_skin)");
@@ -1289,19 +1327,41 @@ static mcpt_status sk_check_update(const mcpt_ctx* ctx, const double* m3x4, uint
     }
     for (uint32_t b = 0; b < n_bones; b++)
         for (int r = 0; r < 3; r++) {
-            const double reach = sk_row_reach(m3x4 + 12 * size_t(b) + 4 * r, ctx->sk_radius[b]);
+            const double reach = sk_row_reach(m3x4 + 12 * size_t(b) + 4 * r, every_radius ? *every_radius : ctx->sk_radius[b]);
             if (!(reach <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": a vertex could leave |coordinate| <= 1e18 (conservative bound)");
         }
     return MCPT_OK;
 }
-// A scene update that has been checked: the caller's arrays (rf_check_update), one matrix per group (xf_check_update) or one per bone (sk_check_update).
-struct RfUpdate { const double* vertex; const double* normal; const double* m3x4; const double* bones; };
+// mcpt_update_morph's rules for its weights and, when given, its bones (§19), host only: the reach E of the morphed pose bounds the vertices, and
+// stands for every bone's radius in the skin's row bound.
+static mcpt_status mo_check_update(const mcpt_ctx* ctx, const double* weight, uint32_t n_targets, const double* bones, uint32_t n_bones, const char* fn) {
+    const std::string who = std::string(fn) + ": ";
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if (!ctx->mo_n_targets) return fail(MCPT_ERR_INVALID_ARG, who + "no morph is set (mcpt_set_vertex_morph)");
+    if (!weight) return fail(MCPT_ERR_INVALID_ARG, who + "null weights");
+    if (n_targets != ctx->mo_n_targets) return fail(MCPT_ERR_INVALID_ARG, who + "n_targets differs from the morph set");
+    for (uint32_t k = 0; k < n_targets; k++)
+        if (!(std::fabs(weight[k]) <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "target " + std::to_string(k) + ": the weight is not finite or exceeds 1e18");
+    const double reach = mo_reach(ctx->mo_radius, weight, ctx->mo_delta.data(), n_targets);
+    if (!(reach <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "a vertex could leave |coordinate| <= 1e18 (conservative bound)");
+    return bones ? sk_check_update(ctx, bones, n_bones, fn, &reach) : MCPT_OK;
+}
+// A scene update that has been checked: the caller's arrays (rf_check_update), one matrix per group (xf_check_update), one per bone
+// (sk_check_update), or one weight per morph target -- the one source that combines with another, `bones` (mo_check_update).
+struct RfUpdate { const double* vertex; const double* normal; const double* m3x4; const double* bones; const double* morph; };
 // The update itself: the new vertices and normals reach rf_vtx / rf_nrm -- arrays staged and copied, or the staged table of matrices applied to the
 // groups' or the skin's rest pose on the device -- and both trees are refitted, all on the context's stream.
 static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     const size_t vd = ctx->rf_vtx.count(), nd = ctx->rf_nrm.count();
-    const bool normal = u.m3x4 || u.bones ? nd != 0 : u.normal != nullptr;       // are there new normals
-    if (u.bones) {
+    const bool normal = u.m3x4 || u.bones || u.morph ? nd != 0 : u.normal != nullptr;   // are there new normals
+    if (u.morph) {
+        HIP_TRY(ctx->mo_stage.wait());
+        std::memcpy(ctx->mo_stage.host, u.morph, ctx->mo_weight.bytes);
+        if (u.bones) {
+            HIP_TRY(ctx->sk_stage.wait());
+            std::memcpy(ctx->sk_stage.host, u.bones, ctx->sk_table.bytes);
+        }
+    } else if (u.bones) {
         HIP_TRY(ctx->sk_stage.wait());
         std::memcpy(ctx->sk_stage.host, u.bones, ctx->sk_table.bytes);
     } else if (u.m3x4) {
@@ -1317,7 +1377,21 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     // kernel here.
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx->rf_watch.begin(s));
-    if (u.bones) {
+    if (u.morph) {                                                               // morph, then skin: the morphed arrays are the skin kernels' rest pose
+        double* const mv = u.bones ? ctx->mo_tmp_vtx.p : ctx->rf_vtx.p; double* const mn = u.bones ? ctx->mo_tmp_nrm.p : ctx->rf_nrm.p;
+        HIP_TRY(ctx->mo_watch.begin(s));
+        HIP_TRY(ctx->mo_stage.send(ctx->mo_weight.p, 0, ctx->mo_weight.count(), s));
+        if (u.bones) HIP_TRY(ctx->sk_stage.send(ctx->sk_table.p, 0, ctx->sk_table.count(), s));
+        HIP_TRY(launch_mo_vertices(ctx->mo_rest_vtx.p, ctx->mo_voffset.p, ctx->mo_ventry.p, ctx->mo_weight.p, mv, ctx->rf_n_vertex, s));
+        HIP_TRY(launch_mo_normals(ctx->mo_rest_nrm.p, ctx->mo_noffset.p, ctx->mo_nentry.p, ctx->mo_weight.p, mn, ctx->rf_n_normal, s));
+        if (u.bones) {
+            HIP_TRY(launch_sk_vertices(mv, ctx->sk_vbone.p, ctx->sk_vweight.p, ctx->sk_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
+            HIP_TRY(launch_sk_normals(mn, ctx->sk_nbone.p, ctx->sk_nweight.p, ctx->sk_table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+            ctx->sk_updates++;
+        }
+        HIP_TRY(ctx->mo_watch.end(s));
+        ctx->mo_updates++;
+    } else if (u.bones) {
         HIP_TRY(ctx->sk_watch.begin(s));
         HIP_TRY(ctx->sk_stage.send(ctx->sk_table.p, 0, ctx->sk_table.count(), s));
         HIP_TRY(launch_sk_vertices(ctx->sk_rest_vtx.p, ctx->sk_vbone.p, ctx->sk_vweight.p, ctx->sk_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
@@ -1462,6 +1536,93 @@ mcpt_status mcpt_get_skin_info(mcpt_ctx* ctx, mcpt_skin_info* out) {
     std::memset(out, 0, sizeof *out);
     out->struct_size = sizeof *out; out->n_bones = ctx->sk_n_bones; out->updates = ctx->sk_updates; out->last_ms = ctx->sk_watch.last_ms;
     return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ morph targets
+// One set of targets against mcpt_set_vertex_morph's rules; `what` names the array in the message.  (null: no targets for this array.)
+static mcpt_status mo_check_targets(const mcpt_morph_targets* t, uint32_t n_records, uint32_t n_targets, const std::string& who, const char* what) {
+    if (!t) return MCPT_OK;
+    const std::string set = who + what + " targets: ";
+    if (t->struct_size != sizeof(mcpt_morph_targets)) return fail(MCPT_ERR_INVALID_ARG, set + "struct_size != sizeof(mcpt_morph_targets)");
+    if (t->n_targets < 1 || t->n_targets > 65536) return fail(MCPT_ERR_INVALID_ARG, set + "n_targets must be in [1, 65536]");
+    if (t->n_targets != n_targets) return fail(MCPT_ERR_INVALID_ARG, set + "n_targets differs from the vertex targets' (one weight drives both)");
+    if (!t->target_offset) return fail(MCPT_ERR_INVALID_ARG, set + "null target_offset");
+    if (t->target_offset[0] != 0) return fail(MCPT_ERR_INVALID_ARG, set + "target_offset[0] is not 0");
+    for (uint32_t k = 0; k < n_targets; k++)
+        if (t->target_offset[k + 1] < t->target_offset[k]) return fail(MCPT_ERR_INVALID_ARG, set + "target_offset decreases at target " + std::to_string(k));
+    const uint32_t total = t->target_offset[n_targets];
+    if (total && (!t->index || !t->delta)) return fail(MCPT_ERR_INVALID_ARG, set + "null index or delta array");
+    for (uint32_t k = 0; k < n_targets; k++)
+        for (uint32_t e = t->target_offset[k]; e < t->target_offset[k + 1]; e++) {
+            const std::string at = set + "target " + std::to_string(k) + ", entry " + std::to_string(e);
+            if (t->index[e] >= n_records) return fail(MCPT_ERR_INVALID_ARG, at + ": index >= the record count");
+            if (e > t->target_offset[k] && t->index[e] <= t->index[e - 1]) return fail(MCPT_ERR_INVALID_ARG, at + ": indices are not strictly ascending inside the target");
+            const double* d = t->delta + 3 * size_t(e);
+            if (!(std::fabs(d[0]) <= MCPT_MAX_COORD && std::fabs(d[1]) <= MCPT_MAX_COORD && std::fabs(d[2]) <= MCPT_MAX_COORD))
+                return fail(MCPT_ERR_INVALID_ARG, at + ": a delta component is not finite or exceeds 1e18");
+        }
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_set_vertex_morph(mcpt_ctx* ctx, const mcpt_morph_targets* vertex, uint32_t n_vertex, const mcpt_morph_targets* normal, uint32_t n_normal) {
+    const std::string who = "mcpt_set_vertex_morph: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if (n_vertex != ctx->rf_n_vertex || n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_vertex / n_normal differ from the scene's");
+    if (!vertex) return fail(MCPT_ERR_INVALID_ARG, who + "null vertex targets");
+    st = mo_check_targets(vertex, n_vertex, vertex->n_targets, who, "vertex"); if (st != MCPT_OK) return st;
+    st = mo_check_targets(normal, n_normal, vertex->n_targets, who, "normal"); if (st != MCPT_OK) return st;
+    const uint32_t n_targets = vertex->n_targets;
+    std::vector<uint32_t> voff, noff; std::vector<MoEntry> vent, nent;
+    mo_per_record(vertex->target_offset, vertex->index, vertex->delta, n_targets, n_vertex, voff, vent);
+    if (normal) mo_per_record(normal->target_offset, normal->index, normal->delta, n_targets, n_normal, noff, nent);
+    else noff.assign(size_t(n_normal) + 1, 0);                                   // normals are not morphed: every list is empty, every record is copied
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // rf_vtx / rf_nrm are final, and no copy out of the old stage is under way
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    st = mo_alloc(ctx, n_targets, vent.size(), nent.size()); if (st != MCPT_OK) return st;
+    std::vector<double> vtx(ctx->rf_vtx.count());
+    {   Scratch s(ctx->stream);
+        if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->mo_rest_vtx.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->mo_rest_nrm.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(s.put(ctx->mo_voffset.p, voff.data(), voff.size())); HIP_TRY(s.put(ctx->mo_noffset.p, noff.data(), noff.size()));
+        HIP_TRY(s.put(ctx->mo_ventry.p, vent.data(), vent.size())); HIP_TRY(s.put(ctx->mo_nentry.p, nent.data(), nent.size()));
+        HIP_TRY(s.fetch(vtx.data(), ctx->rf_vtx.p, vtx.size())); HIP_TRY(s.finish()); }
+    for (uint32_t v = 0; v < n_vertex; v++) {
+        if (!ctx->rf_used_vertex[v]) continue;
+        for (int a = 0; a < 3; a++) ctx->mo_radius = std::max(ctx->mo_radius, std::fabs(vtx[3 * size_t(v) + a]));
+    }
+    for (uint32_t k = 0; k < n_targets; k++)
+        for (uint32_t e = vertex->target_offset[k]; e < vertex->target_offset[k + 1]; e++) {
+            if (!ctx->rf_used_vertex[vertex->index[e]]) continue;
+            for (int a = 0; a < 3; a++) ctx->mo_delta[k] = std::max(ctx->mo_delta[k], std::fabs(vertex->delta[3 * size_t(e) + a]));
+        }
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_update_morph(mcpt_ctx* ctx, const double* weight, uint32_t n_targets, const double* bones_m3x4, uint32_t n_bones) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    st = mo_check_update(ctx, weight, n_targets, bones_m3x4, n_bones, "mcpt_update_morph"); if (st != MCPT_OK) return st;
+    if (bones_m3x4) { st = mo_ensure_scratch(ctx); if (st != MCPT_OK) return st; }
+    return rf_enqueue_update(ctx, RfUpdate{nullptr, nullptr, nullptr, bones_m3x4, weight});
+}
+
+mcpt_status mcpt_get_morph_info(mcpt_ctx* ctx, mcpt_morph_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    HIP_TRY(ctx->mo_watch.settle());
+    std::memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out; out->n_targets = ctx->mo_n_targets; out->updates = ctx->mo_updates; out->last_ms = ctx->mo_watch.last_ms;
+    out->vertex_entries = ctx->mo_ventry.count(); out->normal_entries = ctx->mo_nentry.count();
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_vertices(mcpt_ctx* ctx, double* out_vertex, double* out_normal) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_probe_vertices: the context was created without MCPT_FLAG_DYNAMIC");
+    st = read_back(ctx, out_vertex, ctx->rf_vtx.p, out_vertex ? ctx->rf_vtx.bytes : 0); if (st != MCPT_OK) return st;
+    return read_back(ctx, out_normal, ctx->rf_nrm.p, out_normal ? ctx->rf_nrm.bytes : 0);
 }
 
 mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
@@ -1892,6 +2053,21 @@ mcpt_status mcpt_update_skin_reproject(mcpt_ctx* ctx, const double* m3x4, uint32
     st = sk_check_update(ctx, m3x4, n_bones, fn); if (st != MCPT_OK) return st;
     if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
     const RfUpdate update{nullptr, nullptr, nullptr, m3x4};                      // §18: the bones in place of the arrays, the same frame
+    return rp_frame(ctx, &update, cm, opts, fn);
+}
+
+mcpt_status mcpt_update_morph_reproject(mcpt_ctx* ctx, const double* weight, uint32_t n_targets, const double* bones_m3x4, uint32_t n_bones,
+                                        const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
+    const char* const fn = "mcpt_update_morph_reproject";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    st = mo_check_update(ctx, weight, n_targets, bones_m3x4, n_bones, fn); if (st != MCPT_OK) return st;
+    if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
+    if (bones_m3x4 && ctx->binary_ok) {                                          // the scratch is allocated only by a call that rp_frame will not refuse
+        mcpt_reproject_opts o;
+        st = rp_read_opts(opts, o, fn); if (st != MCPT_OK) return st;
+        st = mo_ensure_scratch(ctx); if (st != MCPT_OK) return st;
+    }
+    const RfUpdate update{nullptr, nullptr, nullptr, bones_m3x4, weight};        // §19: the weights (and bones) in place of the arrays, the same frame
     return rp_frame(ctx, &update, cm, opts, fn);
 }
 

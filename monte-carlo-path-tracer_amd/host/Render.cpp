@@ -132,32 +132,46 @@ bool Render::film_to_device(Scene& scene, const char* who, bool& ok) {
     ok = true;
     return upload;
 }
-bool Render::update_reproject(Scene& scene, Model& m, float max_history) { return update_reproject(scene, &m, nullptr, false, nullptr, max_history); }
-bool Render::update_reproject(Scene& scene, Model& m, const CameraInfo& camera, float max_history) { return update_reproject(scene, &m, nullptr, false, &camera, max_history); }
-bool Render::update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, float max_history) { return update_reproject(scene, nullptr, &matrices, false, nullptr, max_history); }
+bool Render::update_reproject(Scene& scene, Model& m, float max_history) { return update_reproject(scene, &m, nullptr, false, nullptr, nullptr, max_history); }
+bool Render::update_reproject(Scene& scene, Model& m, const CameraInfo& camera, float max_history) { return update_reproject(scene, &m, nullptr, false, nullptr, &camera, max_history); }
+bool Render::update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, float max_history) { return update_reproject(scene, nullptr, &matrices, false, nullptr, nullptr, max_history); }
 bool Render::update_transforms_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history) {
-    return update_reproject(scene, nullptr, &matrices, false, &camera, max_history);
+    return update_reproject(scene, nullptr, &matrices, false, nullptr, &camera, max_history);
 }
-bool Render::update_skin_reproject(Scene& scene, const std::vector<double>& matrices, float max_history) { return update_reproject(scene, nullptr, &matrices, true, nullptr, max_history); }
+bool Render::update_skin_reproject(Scene& scene, const std::vector<double>& matrices, float max_history) { return update_reproject(scene, nullptr, &matrices, true, nullptr, nullptr, max_history); }
 bool Render::update_skin_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history) {
-    return update_reproject(scene, nullptr, &matrices, true, &camera, max_history);
+    return update_reproject(scene, nullptr, &matrices, true, nullptr, &camera, max_history);
 }
-// The geometry comes from `m` (its arrays) or from `matrices` (one 3x4 per group, §16, or per bone, §18): the rest is the same.
-bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>* matrices, bool bones, const CameraInfo* camera, float max_history) {
+bool Render::update_morph_reproject(Scene& scene, const std::vector<double>& weights, float max_history) { return update_reproject(scene, nullptr, nullptr, false, &weights, nullptr, max_history); }
+bool Render::update_morph_reproject(Scene& scene, const std::vector<double>& weights, const CameraInfo& camera, float max_history) {
+    return update_reproject(scene, nullptr, nullptr, false, &weights, &camera, max_history);
+}
+bool Render::update_morph_reproject(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices, float max_history) {
+    return update_reproject(scene, nullptr, &bone_matrices, true, &weights, nullptr, max_history);
+}
+bool Render::update_morph_reproject(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices, const CameraInfo& camera, float max_history) {
+    return update_reproject(scene, nullptr, &bone_matrices, true, &weights, &camera, max_history);
+}
+// The geometry comes from `m` (its arrays), from `matrices` (one 3x4 per group, §16, or per bone, §18) or from `weights` (one per morph target,
+// §19, with or without the bones' matrices): the rest is the same.
+bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>* matrices, bool bones, const std::vector<double>* weights, const CameraInfo* camera,
+                              float max_history) {
     if (!ctx) return false;
-    const char* const who = m ? "update_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject";
-    if (!m && matrices->size() % 12) { std::cerr << "Error: Render::" << who << ": need 12 doubles per " << (bones ? "bone" : "group") << std::endl; return false; }
+    const char* const who = m ? "update_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject";
+    if (!m && matrices && (matrices->size() % 12 || matrices->empty())) { std::cerr << "Error: Render::" << who << ": need 12 doubles per " << (bones ? "bone" : "group") << std::endl; return false; }
     bool ok = false;
     const bool upload = film_to_device(scene, who, ok);
     if (!ok) return false;
     mcpt_camera k; if (camera) k = to_camera(*camera);
     mcpt_reproject_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.feature_spp = 4; o.feature_seed = seed; o.max_history = max_history;
-    const mcpt_status st = m ? mcpt_update_vertices_reproject(ctx, reinterpret_cast<const double*>(m->vertex.data()), uint32_t(m->vertex.size()),
+    const mcpt_status st = weights ? mcpt_update_morph_reproject(ctx, weights->data(), uint32_t(weights->size()), matrices ? matrices->data() : nullptr,
+                                                                 matrices ? uint32_t(matrices->size() / 12) : 0u, camera ? &k : nullptr, &o)
+                         : m ? mcpt_update_vertices_reproject(ctx, reinterpret_cast<const double*>(m->vertex.data()), uint32_t(m->vertex.size()),
                                                               reinterpret_cast<const double*>(m->normal.data()), uint32_t(m->normal.size()), camera ? &k : nullptr, &o)
                      : bones ? mcpt_update_skin_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o)
                              : mcpt_update_transforms_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o);
     if (st != MCPT_OK) {
-        std::cerr << "Error: mcpt_" << (m ? "update_vertices_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
+        std::cerr << "Error: mcpt_" << (m ? "update_vertices_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
         if (upload && mcpt_clear_accum(ctx) != MCPT_OK) std::cerr << "Error: mcpt_clear_accum: " << mcpt_last_error() << std::endl;   // the Scene still holds them
         return false;
     }
@@ -247,6 +261,42 @@ bool Render::update_skin(Scene& scene, const std::vector<double>& matrices) {
     if (!ctx) return false;
     if (matrices.size() % 12) { std::cerr << "Error: Render::update_skin: need 12 doubles per bone" << std::endl; return false; }
     if (mcpt_update_skin(ctx, matrices.data(), uint32_t(matrices.size() / 12)) != MCPT_OK) { std::cerr << "Error: mcpt_update_skin: " << mcpt_last_error() << std::endl; return false; }
+    return restart(scene);
+}
+// One set of targets flattened into what mcpt_morph_targets points to; false when a target's delta count is not 3 per index.
+static bool flatten_targets(const std::vector<MorphTarget>& targets, std::vector<uint32_t>& offset, std::vector<uint32_t>& index, std::vector<double>& delta, mcpt_morph_targets& t) {
+    offset.assign(1, 0u);
+    for (const MorphTarget& g : targets) {
+        if (g.delta.size() != 3 * g.index.size()) return false;
+        index.insert(index.end(), g.index.begin(), g.index.end()); delta.insert(delta.end(), g.delta.begin(), g.delta.end());
+        offset.push_back(uint32_t(index.size()));
+    }
+    std::memset(&t, 0, sizeof t); t.struct_size = sizeof t; t.n_targets = uint32_t(targets.size());
+    t.target_offset = offset.data(); t.index = index.empty() ? nullptr : index.data(); t.delta = delta.empty() ? nullptr : delta.data();
+    return true;
+}
+bool Render::set_morph(Scene&, Model& m, const std::vector<MorphTarget>& vertex_targets, const std::vector<MorphTarget>& normal_targets) {
+    if (!ctx) return false;
+    std::vector<uint32_t> vo, vi, no, ni; std::vector<double> vd, nd; mcpt_morph_targets vt, nt;
+    if (!flatten_targets(vertex_targets, vo, vi, vd, vt) || !flatten_targets(normal_targets, no, ni, nd, nt)) {
+        std::cerr << "Error: Render::set_morph: need 3 doubles of displacement per index" << std::endl; return false;
+    }
+    if (mcpt_set_vertex_morph(ctx, &vt, uint32_t(m.vertex.size()), normal_targets.empty() ? nullptr : &nt, uint32_t(m.normal.size())) != MCPT_OK) {
+        std::cerr << "Error: mcpt_set_vertex_morph: " << mcpt_last_error() << std::endl; return false;
+    }
+    return true;
+}
+bool Render::update_morph(Scene& scene, const std::vector<double>& weights) {
+    if (!ctx) return false;
+    if (mcpt_update_morph(ctx, weights.data(), uint32_t(weights.size()), nullptr, 0u) != MCPT_OK) { std::cerr << "Error: mcpt_update_morph: " << mcpt_last_error() << std::endl; return false; }
+    return restart(scene);
+}
+bool Render::update_morph(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices) {
+    if (!ctx) return false;
+    if (bone_matrices.empty() || bone_matrices.size() % 12) { std::cerr << "Error: Render::update_morph: need 12 doubles per bone" << std::endl; return false; }
+    if (mcpt_update_morph(ctx, weights.data(), uint32_t(weights.size()), bone_matrices.data(), uint32_t(bone_matrices.size() / 12)) != MCPT_OK) {
+        std::cerr << "Error: mcpt_update_morph: " << mcpt_last_error() << std::endl; return false;
+    }
     return restart(scene);
 }
 bool Render::update_materials(Scene& scene, Model& m) {

@@ -6,6 +6,9 @@
 #include "Model.h"
 #include "Scene.h"
 
+// One morph target: the records it displaces, strictly ascending, and 3 doubles of displacement per record.
+struct MorphTarget { std::vector<uint32_t> index; std::vector<double> delta; };
+
 class Render : public FilmSource {
 public:
     explicit Render(Model& m_model);                  // Render.cpp:5-10: flatten + BVH + upload (inside mcpt_create)
@@ -71,6 +74,19 @@ public:
     bool update_skin(Scene& scene, const std::vector<double>& matrices);
     bool update_skin_reproject(Scene& scene, const std::vector<double>& matrices, float max_history = 0);
     bool update_skin_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history = 0);
+    // Morph targets.  set_morph: one MorphTarget per target over the vertices of `m_model`, the Model this Render was made from
+    // (MCPT_FLAG_DYNAMIC), and -- optionally, as many -- over its normals (none: the normals are not morphed); the scene as it is now becomes
+    // the morph's rest pose.  The film is not touched.  update_morph: one weight per target, the weighted displacements added to the rest pose
+    // on the device (mcpt_update_morph) -- only the weights cross the bus; with bone_matrices (12 doubles per bone of the skin set with
+    // set_skin) the morphed pose is skinned in the same call: morph, then skin.  Starts the picture again like update();
+    // update_morph_reproject carries it over like update_reproject.  false (Render and Scene unchanged) on failure.
+    bool set_morph(Scene& scene, Model& m_model, const std::vector<MorphTarget>& vertex_targets, const std::vector<MorphTarget>& normal_targets = {});
+    bool update_morph(Scene& scene, const std::vector<double>& weights);
+    bool update_morph(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices);
+    bool update_morph_reproject(Scene& scene, const std::vector<double>& weights, float max_history = 0);
+    bool update_morph_reproject(Scene& scene, const std::vector<double>& weights, const CameraInfo& camera, float max_history = 0);
+    bool update_morph_reproject(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices, float max_history = 0);
+    bool update_morph_reproject(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices, const CameraInfo& camera, float max_history = 0);
     // New trees for the geometry as it is now (mcpt_rebuild_trees): after update() / update_transforms() have moved the scene far
     // (mcpt_update_info::wide_area_ratio says how far) the refitted trees are sound and slow; this builds them anew on the context.  The picture
     // goes ON: `scene`'s film, the sample numbering and the feature buffers stay, the scene looks the same from every pixel.  Synchronous.  false
@@ -93,7 +109,8 @@ private:
     void create(Model& m, const mcpt_opts& opts);
     bool restart(Scene& scene);
     bool film_to_device(Scene& scene, const char* who, bool& ok);
-    bool update_reproject(Scene& scene, Model* m_model, const std::vector<double>* matrices, bool bones, const CameraInfo* camera, float max_history);
+    bool update_reproject(Scene& scene, Model* m_model, const std::vector<double>* matrices, bool bones, const std::vector<double>* weights, const CameraInfo* camera,
+                          float max_history);
 };
 // Fills an mcpt_scene_desc that points INTO `m` (and into the two scratch vectors); valid while all three live.
 void model_to_desc(Model& m, std::vector<mcpt_material>& mats, std::vector<mcpt_texture>& texs, mcpt_scene_desc& d);

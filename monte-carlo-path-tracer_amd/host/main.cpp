@@ -39,7 +39,11 @@ static void usage() {
                  "                                        device): a vertex follows the upper bone by its height inside the part's y-extent, the lower bone stays,\n"
                  "                                        the upper one turns by DEG sin(2 pi k / N) about z through the part's centre in frame k (honours --reproject;\n"
                  "                                        not with --wobble or --spin)\n"
-                 "                          [--rebuild-above R]   with --turntable and --wobble, --spin or --bend: after a frame's update the trees are built anew\n"
+                 "                          [--swell MTLNAME AMOUNT]   with --turntable: the faces of that material swell and shrink about the centroid of their\n"
+                 "                                        vertices (one morph target on the device, delta = vertex - centroid, weight AMOUNT sin(2 pi k / N) in frame k:\n"
+                 "                                        a uniform scaling, so the normals stay); combines with --bend (morph, then skin, one call per frame);\n"
+                 "                                        honours --reproject; not with --wobble or --spin\n"
+                 "                          [--rebuild-above R]   with --turntable and --wobble, --spin, --bend or --swell: after a frame's update the trees are built anew\n"
                  "                                        (mcpt_rebuild_trees, film kept) when wide_area_ratio exceeds R; prints frame, ratio and cost per rebuild\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
@@ -70,7 +74,7 @@ int main(int argc, char** argv) {
     bool reproject = false; float history = 0.f;
     bool wobble = false; double wobble_a = 0.0;
     bool pulse = false; double pulse_a = 0.0;
-    std::string spin, bend; double bend_deg = 0.0;
+    std::string spin, bend, swell; double bend_deg = 0.0, swell_a = 0.0;
     bool rebuild = false; double rebuild_above = 0.0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
@@ -94,6 +98,7 @@ int main(int argc, char** argv) {
         else if (a == "--light-pulse") { pulse = true; pulse_a = std::atof(next()); }
         else if (a == "--spin") spin = next();
         else if (a == "--bend") { bend = next(); bend_deg = std::atof(next()); }
+        else if (a == "--swell") { swell = next(); swell_a = std::atof(next()); }
         else if (a == "--rebuild-above") { rebuild = true; rebuild_above = std::atof(next()); }
         else { usage(); return 2; }
     }
@@ -107,8 +112,13 @@ int main(int argc, char** argv) {
     if (!bend.empty() && (!turntable || wobble || !spin.empty() || !(std::fabs(bend_deg) <= 1e6))) {
         std::cerr << "Error: --bend MTLNAME DEG needs --turntable N, a finite DEG and neither --wobble nor --spin (all three write the vertices)" << std::endl; return 2;
     }
-    if (rebuild && (!turntable || !(wobble || !spin.empty() || !bend.empty()) || !(rebuild_above >= 0.0))) { std::cerr << "Error: --rebuild-above R needs --turntable N with --wobble, --spin or --bend, and R >= 0" << std::endl; return 2; }
-    if (wobble || !spin.empty() || !bend.empty()) flags |= MCPT_FLAG_DYNAMIC;
+    if (!swell.empty() && (!turntable || wobble || !spin.empty() || !(std::fabs(swell_a) <= 1e6))) {
+        std::cerr << "Error: --swell MTLNAME AMOUNT needs --turntable N, a finite AMOUNT and neither --wobble nor --spin (all three write the vertices)" << std::endl; return 2;
+    }
+    if (rebuild && (!turntable || !(wobble || !spin.empty() || !bend.empty() || !swell.empty()) || !(rebuild_above >= 0.0))) {
+        std::cerr << "Error: --rebuild-above R needs --turntable N with --wobble, --spin, --bend or --swell, and R >= 0" << std::endl; return 2;
+    }
+    if (wobble || !spin.empty() || !bend.empty() || !swell.empty()) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
     std::cout << model.face.size() << " " << model.normal.size() << " " << model.vertex.size() << std::endl;   // main.cpp:14
@@ -223,6 +233,33 @@ int main(int argc, char** argv) {
             }
             if (!renders[0]->set_skin(scene, model, bone, weight, 3u)) return 1;
         }
+        // --swell MTLNAME AMOUNT: ONE morph target over that material's vertices, delta = vertex - centroid: a uniform scaling about a
+        // point leaves every normal as it is, so there is no normal target
+        if (!swell.empty()) {
+            const int mtl = model.material_index(swell);
+            if (mtl < 0) { std::cerr << "Error: --swell: no material named " << swell << std::endl; return 1; }
+            std::vector<uint8_t> part(model.vertex.size(), 0);
+            size_t n_swell = 0;
+            for (size_t i = 0; i < model.face.size(); i++) {
+                if (model.face[i][0][3] != mtl) continue;
+                n_swell++;
+                for (int c = 0; c < 3; c++) {
+                    const int vi = model.face[i][c][0];
+                    if (vi >= 0 && size_t(vi) < model.vertex.size()) part[size_t(vi)] = 1;   // (mcpt_create has refused any other face already)
+                }
+            }
+            if (!n_swell) { std::cerr << "Error: --swell: no face uses material " << swell << std::endl; return 1; }
+            double centre[3] = {0.0, 0.0, 0.0}; size_t n_part = 0;
+            for (size_t i = 0; i < model.vertex.size(); i++) if (part[i]) { centre[0] += model.vertex[i].x; centre[1] += model.vertex[i].y; centre[2] += model.vertex[i].z; n_part++; }
+            for (int a = 0; a < 3; a++) centre[a] /= double(n_part);
+            std::vector<MorphTarget> target(1);
+            for (size_t i = 0; i < model.vertex.size(); i++) {               // ascending, as the library asks
+                if (!part[i]) continue;
+                target[0].index.push_back(uint32_t(i));
+                target[0].delta.push_back(model.vertex[i].x - centre[0]); target[0].delta.push_back(model.vertex[i].y - centre[1]); target[0].delta.push_back(model.vertex[i].z - centre[2]);
+            }
+            if (!renders[0]->set_morph(scene, model, target)) return 1;
+        }
         for (uint32_t f = 0; f < turntable; f++) {
             const double a = 2.0 * 3.14159265358979323846 * double(f) / double(turntable), ca = std::cos(a), sa = std::sin(a);
             const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2], kx[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
@@ -260,13 +297,20 @@ int main(int argc, char** argv) {
                 }
                 if (reproject && f > 0 ? !renders[0]->update_transforms_reproject(scene, m, cam, history)
                                        : !(renders[0]->update_transforms(scene, m) && renders[0]->set_camera(scene, cam))) return 1;
-            } else if (!bend.empty()) {                                      // bones 0 and 1 stay; bone 2 turns about z through the part's centre
+            } else if (!bend.empty() || !swell.empty()) {                    // bones 0 and 1 stay; bone 2 turns about z through the part's centre
                 const double b = bend_deg * 3.14159265358979323846 / 180.0 * sa, cb = std::cos(b), sb = std::sin(b);
                 std::vector<double> m(36, 0.0);
                 for (int g = 0; g < 3; g++) m[12 * g] = m[12 * g + 5] = m[12 * g + 10] = 1.0;
                 double* u = m.data() + 24;
                 u[0] = cb; u[1] = -sb; u[3] = pivot[0] - (cb * pivot[0] - sb * pivot[1]);
                 u[4] = sb; u[5] = cb; u[7] = pivot[1] - (sb * pivot[0] + cb * pivot[1]);
+                const std::vector<double> weights{swell_a * sa};             // --swell: the one target's weight (with --bend: morph, then skin, in one call)
+                Render& r0 = *renders[0];
+                if (!swell.empty() && !bend.empty()) {
+                    if (reproject && f > 0 ? !r0.update_morph_reproject(scene, weights, m, cam, history) : !(r0.update_morph(scene, weights, m) && r0.set_camera(scene, cam))) return 1;
+                } else if (!swell.empty()) {
+                    if (reproject && f > 0 ? !r0.update_morph_reproject(scene, weights, cam, history) : !(r0.update_morph(scene, weights) && r0.set_camera(scene, cam))) return 1;
+                } else
                 if (reproject && f > 0 ? !renders[0]->update_skin_reproject(scene, m, cam, history)
                                        : !(renders[0]->update_skin(scene, m) && renders[0]->set_camera(scene, cam))) return 1;
             } else
