@@ -284,7 +284,7 @@ mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* camera);
 mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal);
 
 typedef struct mcpt_update_info {
-    uint32_t struct_size, updates;      /* mcpt_update_vertices / _transforms / _skin / _morph (+ _reproject) calls on this context so far */
+    uint32_t struct_size, updates;      /* mcpt_update_vertices / _transforms / _skin / _morph (+ _reproject) / _normals calls on this context so far */
     double   last_update_ms;            /* device time of the last one, first to last operation on the stream (HIP events) */
     double   wide_area_ratio;           /* sum of the child-box areas of the 8-wide tree now / when it was built, by mcpt_create or by the last
                                            mcpt_rebuild_trees (dequantised boxes; 1.0 before any update and right after a rebuild) */
@@ -592,6 +592,59 @@ typedef struct mcpt_morph_info {
 mcpt_status mcpt_get_morph_info(mcpt_ctx* ctx, mcpt_morph_info* out);   /* synchronises */
 mcpt_status mcpt_probe_vertices(mcpt_ctx* ctx, double* out_vertex /* 3 n_vertex, may be NULL */, double* out_normal /* 3 n_normal, may be NULL */);
 
+/* ---- live scenes: smooth normals recomputed on the device after every update -------------------------------------------------- */
+/* None of the update routes yields normals of the DEFORMED surface: mcpt_update_vertices(normal = NULL) keeps the old ones, mcpt_update_morph
+ * without normal targets writes the rest pose's, mcpt_update_skin pushes rest normals through a blended matrix.  The tracer orients a surface by
+ * its vertex normals alone, so stale normals also give wrong front/back decisions and emission sides.  With auto normals on, every scene update
+ * -- mcpt_update_vertices / _transforms / _skin / _morph and their _reproject forms -- runs one extra kernel after the route has written the
+ * vertices and normals and in front of the refit: each chosen normal record becomes the normalised sum of the area-weighted normals of the faces
+ * that use it, computed from the vertices as they are now.  All calls need MCPT_FLAG_DYNAMIC (else MCPT_ERR_UNSUPPORTED).
+ *
+ * mcpt_set_auto_normals: set-up, synchronous, the twin of mcpt_set_vertex_morph.  normal_mask: n_normal bytes, != 0 = recompute this record,
+ * NULL = all.  It reads back the faces and the context's CURRENT vertices and normals, the REFERENCE POSE, and builds on the host, per normal
+ * record, the list of the faces that name the record in any corner: one entry per face (also when two or three corners name it), ordered by
+ * ascending face index of the description (never by leaf order: mcpt_rebuild_trees keeps the lists untouched, mcpt_clone_to_device carries them).
+ * An entry is 16 bytes: the face's three vertex indices in corner order and `flip`.  With g = cross(v1 - v0, v2 - v0) at the reference pose and
+ * n the record's reference normal, flip = ((g.x n.x + g.y n.y) + g.z n.z) < 0 (a zero or NaN dot: 0): a face whose winding disagrees with its
+ * normal record at the reference pose goes on disagreeing, so the renderer's orientation rule holds.  Hard edges keep working: they are
+ * separate normal records, and each record gathers only its own faces.  A record that is masked out or that no face uses has no entries and is
+ * never written by the pass.  Allocates, counted in device_bytes: 4 B (n_normal + 1) (list offsets) + 16 B per entry (at most 3 per face).
+ * Calling it again replaces the lists and takes the reference pose anew; mode MCPT_NORMALS_OFF frees them, and every update is again exactly
+ * what it is without this section.
+ *  - Refused with nothing changed: MCPT_ERR_INVALID_ARG for a NULL context, n_normal that differs from the scene's, a wrong struct_size, an
+ *    unknown mode; MCPT_ERR_HIP when an allocation fails.
+ *
+ * The pass, per record with >= 1 entry, everything in fp64 and one correctly rounded operation each: s = +0; per entry in stored order
+ * a = V[v1] - V[v0], b = V[v2] - V[v0], c = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), s = s + sigma c (sigma = -1 when flip,
+ * else +1); len = sqrt((s.x s.x + s.y s.y) + s.z s.z); the record becomes s / len when len is finite and > 0 and is otherwise NOT written (it
+ * keeps what the route wrote).  Area weighting is the only weighting: angle weighting needs acos, which is not correctly rounded.
+ *  - For the records that have entries the pass OVERRIDES what the route wrote -- normals that the caller handed to mcpt_update_vertices
+ *    included.  Mask out what the caller wants to supply itself.
+ *  - The refit is handed the context's normals on every update, also after mcpt_update_vertices(normal = NULL).
+ *  - mcpt_update_info::last_update_ms spans the pass; mcpt_normals_info::last_ms is the pass alone.
+ *
+ * mcpt_update_normals: the same update with no source -- nothing is staged, no vertex moves; the pass, then the usual refit (which reproduces
+ * the trees: the call is idempotent).  Counted as one update; asynchronous on the context's stream; drops what mcpt_update_vertices drops.
+ * MCPT_ERR_INVALID_ARG when auto normals are not set. */
+#define MCPT_NORMALS_OFF  0u
+#define MCPT_NORMALS_AREA 1u           /* area-weighted face normals, the only weighting */
+typedef struct mcpt_normals_opts {
+    uint32_t struct_size, mode;         /* MCPT_NORMALS_* */
+    uint32_t reserved[4];
+} mcpt_normals_opts;
+mcpt_status mcpt_set_auto_normals(mcpt_ctx* ctx, const uint8_t* normal_mask /* n_normal bytes, != 0 = recompute; NULL = all */, uint32_t n_normal,
+                                  const mcpt_normals_opts* opts /* NULL = MCPT_NORMALS_AREA */);
+mcpt_status mcpt_update_normals(mcpt_ctx* ctx);   /* recompute now; nothing moves */
+typedef struct mcpt_normals_info {
+    uint32_t struct_size, mode;         /* MCPT_NORMALS_* in force now */
+    uint32_t records, max_valence;      /* normal records with >= 1 entry; the largest number of entries of one record */
+    uint64_t entries;                   /* entries of the per-record lists */
+    uint32_t updates, reserved0;        /* passes run on this context so far: one per scene update while the mode was on */
+    double   last_ms;                   /* device time of the last pass (HIP events) */
+    uint32_t reserved[4];
+} mcpt_normals_info;
+mcpt_status mcpt_get_normals_info(mcpt_ctx* ctx, mcpt_normals_info* out);   /* synchronises */
+
 /* ---- live scenes: new trees for the geometry as it is now -------------------------------------------------------------- */
 /* mcpt_update_vertices and mcpt_update_transforms refit: after a large deformation the trees are sound and slow.  mcpt_rebuild_trees builds BOTH
  * trees (binary and 8-wide) anew for the context's current vertices -- whatever the last update or transform wrote -- and keeps everything else.
@@ -608,7 +661,7 @@ mcpt_status mcpt_probe_vertices(mcpt_ctx* ctx, double* out_vertex /* 3 n_vertex,
  *    rank it has (the creation geometry's, as mcpt_update_vertices documents).
  *  - KEPT, because the scene looks the same from every pixel: the film or a bound accumulator, the counters, the stream binding, the camera, the
  *    feature buffers and the denoised film, the adaptive tile error, the reprojection buffers, the vertex groups with their rest pose and R_g,
- *    the skin with its rest pose and R_b, the morph targets with their rest pose, R and D_k (and the morph-then-skin scratch), the materials, the textures, and the light list's membership and order (only the lights' leaf-order
+ *    the skin with its rest pose and R_b, the morph targets with their rest pose, R and D_k (and the morph-then-skin scratch), the auto-normals lists (§20: they are per face of the description, not per leaf), the materials, the textures, and the light list's membership and order (only the lights' leaf-order
  *    triangle index is renumbered).
  *  - Afterwards mcpt_update_info::wide_area_ratio is 1.0 (its base is the new tree) and `updates` is unchanged; mcpt_scene_info follows the new
  *    trees: n_nodes, bvh_depth, max_leaf, wide_nodes, wide_depth, traversal_bytes, wide_tree_hash, bvh_builder, and device_bytes counts what is

@@ -23,6 +23,8 @@ from .rebuild_abi import REBUILD_DEVICE, REBUILD_HOST, REBUILD_SAME, RebuildInfo
 from .skin_abi import SKIN_INFLUENCES, SkinInfo  # noqa: F401
 # mcpt_set_vertex_morph's and mcpt_get_morph_info's structs and the flattening of a target list; tests/test_morph.py holds the layouts to the header
 from .morph_abi import MORPH_MAX_TARGETS, MorphInfo, MorphTargets, flatten_targets, targets_struct  # noqa: F401
+# mcpt_set_auto_normals' and mcpt_get_normals_info's structs and the mask of the normals a set of faces uses; tests/test_normals.py holds the layouts to the header
+from .normals_abi import NORMALS_AREA, NORMALS_OFF, NormalsInfo, NormalsOpts, normal_mask_from_faces  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmcpt_hip.so")
@@ -293,6 +295,9 @@ def load_library() -> C.CDLL:
         "mcpt_update_morph_reproject": [vp, vp, C.c_uint32, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
         "mcpt_get_morph_info": [vp, P(MorphInfo)],
         "mcpt_probe_vertices": [vp, vp, vp],
+        "mcpt_set_auto_normals": [vp, vp, C.c_uint32, P(NormalsOpts)],
+        "mcpt_update_normals": [vp],
+        "mcpt_get_normals_info": [vp, P(NormalsInfo)],
         "mcpt_rebuild_trees": [vp, P(RebuildOpts)],
         "mcpt_get_rebuild_info": [vp, P(RebuildInfo)],
     }
@@ -323,6 +328,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_vertex_groups", "mcpt_update_transforms", "mcpt_update_transforms_reproject", "mcpt_get_transform_info",
     "mcpt_set_vertex_skin", "mcpt_update_skin", "mcpt_update_skin_reproject", "mcpt_get_skin_info",
     "mcpt_set_vertex_morph", "mcpt_update_morph", "mcpt_update_morph_reproject", "mcpt_get_morph_info", "mcpt_probe_vertices",
+    "mcpt_set_auto_normals", "mcpt_update_normals", "mcpt_get_normals_info",
     "mcpt_rebuild_trees", "mcpt_get_rebuild_info",
 ]
 
@@ -657,6 +663,27 @@ class Renderer:
         v = np.empty((self.holder.desc.n_vertex, 3), np.float64); n = np.empty((self.holder.desc.n_normal, 3), np.float64)
         self._check(self.lib.mcpt_probe_vertices(self.ctx, _ptr(v), _ptr(n)))
         return v, n
+
+    # ---- smooth normals recomputed on the device after every update
+    def set_auto_normals(self, mask=None, mode: int = NORMALS_AREA):
+        """From now on every scene update (update_vertices / _transforms / _skin / _morph and their _reproject forms) recomputes the normal
+        records chosen by `mask` (one byte per normal, != 0 = recompute; None = all) from the deformed faces: the normalised sum of the
+        area-weighted face normals, in a fixed order.  The scene as it is now is the reference pose that fixes each face's side.  For the
+        chosen records this OVERRIDES what the update wrote, caller-supplied normals included.  mode=NORMALS_OFF frees the lists.  Needs
+        FLAG_DYNAMIC.  Synchronous."""
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        o = NormalsOpts()
+        o.struct_size = C.sizeof(NormalsOpts); o.mode = int(mode)
+        self._check(self.lib.mcpt_set_auto_normals(self.ctx, _ptr(m), self.holder.desc.n_normal if m is None else m.shape[0], C.byref(o)))
+
+    def update_normals(self):
+        """The normals pass and the refit on the scene as it is: nothing moves.  Needs set_auto_normals.  Asynchronous; the caller clears the film."""
+        self._check(self.lib.mcpt_update_normals(self.ctx))
+
+    def normals_info(self) -> NormalsInfo:
+        i = NormalsInfo()
+        self._check(self.lib.mcpt_get_normals_info(self.ctx, C.byref(i)))
+        return i
 
     # ---- material, light and texture edits (DESIGN.md §15)
     def update_materials(self, materials, map_kd=None):

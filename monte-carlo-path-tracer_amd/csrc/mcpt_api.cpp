@@ -14,6 +14,7 @@
 #include "transform.h"
 #include "skin.h"
 #include "morph.h"
+#include "normals.h"
 #include "reproject.h"
 #include "materials.h"
 
@@ -231,6 +232,12 @@ struct mcpt_ctx {
     Staging<double> mo_stage; std::vector<double> mo_delta; double mo_radius = 0.0;
     Stopwatch mo_watch;
     uint32_t mo_n_targets = 0, mo_updates = 0;
+    // Automatic normals (normals.hip), allocated by mcpt_set_auto_normals and counted in device_bytes: per normal record its list
+    // offset (rf_n_normal + 1) and the 16-byte entries, one per face that names the record.  The lists follow the description's face order, not
+    // the leaf order: a rebuild keeps them, a clone carries them.  nr_mode == MCPT_NORMALS_OFF: nothing is allocated, no update runs the pass.
+    DevBuf<uint32_t> nr_offset; DevBuf<NrEntry> nr_entry;
+    Stopwatch nr_watch;
+    uint32_t nr_mode = 0, nr_updates = 0, nr_records = 0, nr_max_valence = 0;
     // Temporal reprojection (reproject.hip), allocated by the first reprojection call: the old view's features (2 per pixel, swapped
     // with dn_feat per call), a copy of the old film and the reuse counter.
     // Motion-vector reprojection adds, on the first mcpt_update_vertices_reproject: the first hit of every pixel-centre ray and
@@ -534,6 +541,12 @@ static mcpt_status mo_ensure_scratch(mcpt_ctx* c) {
     HIP_TRY(alloc_all(Want(c->mo_tmp_vtx, c->rf_vtx.count(), tally), Want(c->mo_tmp_nrm, c->rf_nrm.count(), tally)));
     return MCPT_OK;
 }
+// The buffers of §20 for the given entry count, all or none: a context that had lists keeps them when an allocation fails.
+static mcpt_status nr_alloc(mcpt_ctx* c, size_t entries) {
+    uint64_t* tally = &c->info.device_bytes;
+    HIP_TRY(alloc_all(Want(c->nr_offset, size_t(c->rf_n_normal) + 1, tally), Want(c->nr_entry, entries, tally), Want(c->nr_watch, 1, nullptr, !c->nr_watch.ev0)));
+    return MCPT_OK;
+}
 static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     c->rf_n_vertex = src->rf_n_vertex; c->rf_n_normal = src->rf_n_normal; c->rf_used_vertex = src->rf_used_vertex;
     c->rf_bin_level = src->rf_bin_level; c->rf_wide_level = src->rf_wide_level; c->rf_area0 = src->rf_area0;
@@ -565,6 +578,12 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
         HIP_TRY(copy(c->mo_voffset, src->mo_voffset)); HIP_TRY(copy(c->mo_noffset, src->mo_noffset));
         HIP_TRY(copy(c->mo_ventry, src->mo_ventry)); HIP_TRY(copy(c->mo_nentry, src->mo_nentry));
         if (src->mo_tmp_vtx.p) { ms = mo_ensure_scratch(c); if (ms != MCPT_OK) return ms; }   // (scratch: its contents are not carried)
+    }
+    if (src->nr_mode != MCPT_NORMALS_OFF) {                                // the auto-normals lists travel with the clone (§20)
+        mcpt_status ns = nr_alloc(c, src->nr_entry.count()); if (ns != MCPT_OK) return ns;
+        c->nr_mode = src->nr_mode; c->nr_records = src->nr_records; c->nr_max_valence = src->nr_max_valence;
+        auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
+        HIP_TRY(copy(c->nr_offset, src->nr_offset)); HIP_TRY(copy(c->nr_entry, src->nr_entry));
     }
     HIP_TRY(hipDeviceSynchronize());
     return MCPT_OK;
@@ -1347,14 +1366,19 @@ static mcpt_status mo_check_update(const mcpt_ctx* ctx, const double* weight, ui
     return bones ? sk_check_update(ctx, bones, n_bones, fn, &reach) : MCPT_OK;
 }
 // A scene update that has been checked: the caller's arrays (rf_check_update), one matrix per group (xf_check_update), one per bone
-// (sk_check_update), or one weight per morph target -- the one source that combines with another, `bones` (mo_check_update).
-struct RfUpdate { const double* vertex; const double* normal; const double* m3x4; const double* bones; const double* morph; };
+// (sk_check_update), or one weight per morph target -- the one source that combines with another, `bones` (mo_check_update).  `no_source`
+// (§20, mcpt_update_normals): nothing is staged and no vertex moves; the normals pass and the refit run on the arrays as they are.
+struct RfUpdate { const double* vertex; const double* normal; const double* m3x4; const double* bones; const double* morph; bool no_source; };
 // The update itself: the new vertices and normals reach rf_vtx / rf_nrm -- arrays staged and copied, or the staged table of matrices applied to the
-// groups' or the skin's rest pose on the device -- and both trees are refitted, all on the context's stream.
+// groups' or the skin's rest pose on the device --, with auto normals on the chosen normal records are recomputed from them (§20), and both trees
+// are refitted, all on the context's stream.
 static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     const size_t vd = ctx->rf_vtx.count(), nd = ctx->rf_nrm.count();
-    const bool normal = u.m3x4 || u.bones || u.morph ? nd != 0 : u.normal != nullptr;   // are there new normals
-    if (u.morph) {
+    const bool auto_normals = ctx->nr_mode != MCPT_NORMALS_OFF;                  // §20: the pass below rewrites rf_nrm, so the refit always reads it
+    const bool upload_normal = u.normal != nullptr;                              // the arrays' route: the caller's normals are copied too
+    const bool normal = u.m3x4 || u.bones || u.morph || auto_normals ? nd != 0 : upload_normal;   // are there new normals
+    if (u.no_source) {                                                           // §20, mcpt_update_normals: nothing to stage
+    } else if (u.morph) {
         HIP_TRY(ctx->mo_stage.wait());
         std::memcpy(ctx->mo_stage.host, u.morph, ctx->mo_weight.bytes);
         if (u.bones) {
@@ -1370,14 +1394,15 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     } else {
         HIP_TRY(ctx->rf_stage.wait());
         std::memcpy(ctx->rf_stage.host, u.vertex, vd * sizeof(double));
-        if (normal) std::memcpy(ctx->rf_stage.host + vd, u.normal, nd * sizeof(double));
+        if (upload_normal) std::memcpy(ctx->rf_stage.host + vd, u.normal, nd * sizeof(double));
     }
     // Everything below is stream work on the context's stream: it starts after every render enqueued so far has finished (the sub-pipelines'
     // streams joined it at the end of their call, known-length jobs included) and the next render's sub-pipelines fork from it after the last
     // kernel here.
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx->rf_watch.begin(s));
-    if (u.morph) {                                                               // morph, then skin: the morphed arrays are the skin kernels' rest pose
+    if (u.no_source) {                                                           // ... and nothing to write
+    } else if (u.morph) {                                                        // morph, then skin: the morphed arrays are the skin kernels' rest pose
         double* const mv = u.bones ? ctx->mo_tmp_vtx.p : ctx->rf_vtx.p; double* const mn = u.bones ? ctx->mo_tmp_nrm.p : ctx->rf_nrm.p;
         HIP_TRY(ctx->mo_watch.begin(s));
         HIP_TRY(ctx->mo_stage.send(ctx->mo_weight.p, 0, ctx->mo_weight.count(), s));
@@ -1406,8 +1431,14 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
         HIP_TRY(ctx->xf_watch.end(s));
         ctx->xf_updates++;
     } else {
-        HIP_TRY(ctx->rf_stage.send(ctx->rf_vtx.p, 0, vd, s, !normal));
-        if (normal) HIP_TRY(ctx->rf_stage.send(ctx->rf_nrm.p, vd, nd, s));
+        HIP_TRY(ctx->rf_stage.send(ctx->rf_vtx.p, 0, vd, s, !upload_normal));
+        if (upload_normal) HIP_TRY(ctx->rf_stage.send(ctx->rf_nrm.p, vd, nd, s));
+    }
+    if (auto_normals) {                                                          // §20: the chosen records from the faces as they are now, in place
+        HIP_TRY(ctx->nr_watch.begin(s));
+        HIP_TRY(launch_nr_normals(ctx->rf_vtx.p, ctx->nr_offset.p, ctx->nr_entry.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+        HIP_TRY(ctx->nr_watch.end(s));
+        ctx->nr_updates++;
     }
     const double* d_nrm = normal ? ctx->rf_nrm.p : nullptr;
     const DevScene& d = ctx->dev;
@@ -1623,6 +1654,65 @@ mcpt_status mcpt_probe_vertices(mcpt_ctx* ctx, double* out_vertex, double* out_n
     if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_probe_vertices: the context was created without MCPT_FLAG_DYNAMIC");
     st = read_back(ctx, out_vertex, ctx->rf_vtx.p, out_vertex ? ctx->rf_vtx.bytes : 0); if (st != MCPT_OK) return st;
     return read_back(ctx, out_normal, ctx->rf_nrm.p, out_normal ? ctx->rf_nrm.bytes : 0);
+}
+
+// ------------------------------------------------------------------------------------------------ automatic normals
+mcpt_status mcpt_set_auto_normals(mcpt_ctx* ctx, const uint8_t* normal_mask, uint32_t n_normal, const mcpt_normals_opts* opts) {
+    const char* const fn = "mcpt_set_auto_normals";
+    const std::string who = std::string(fn) + ": ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if (n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_normal differs from the scene's");
+    mcpt_normals_opts o;
+    st = read_opts(opts, o, fn, "mcpt_normals_opts"); if (st != MCPT_OK) return st;
+    if (!opts) o.mode = MCPT_NORMALS_AREA;
+    if (o.mode != MCPT_NORMALS_OFF && o.mode != MCPT_NORMALS_AREA) return fail(MCPT_ERR_INVALID_ARG, who + "unknown mode");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // rf_vtx / rf_nrm are final, and no kernel reads the old lists any more
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    if (o.mode == MCPT_NORMALS_OFF) {
+        ctx->nr_offset.release(); ctx->nr_entry.release();
+        ctx->nr_mode = MCPT_NORMALS_OFF; ctx->nr_records = 0; ctx->nr_max_valence = 0;
+        return MCPT_OK;
+    }
+    // the faces in the description's order, from the leaf-order index arrays and the leaf order itself; the reference pose
+    const size_t nt = size_t(ctx->dev.n_tris);
+    std::vector<int32_t> idx6(ctx->rf_idx.count()), leaf_face(nt), fv(3 * nt), fnm(3 * nt);
+    std::vector<double> vtx(ctx->rf_vtx.count()), nrm(ctx->rf_nrm.count());
+    {   Scratch s(ctx->stream);
+        HIP_TRY(s.fetch(idx6.data(), ctx->rf_idx.p, idx6.size())); HIP_TRY(s.fetch(leaf_face.data(), ctx->tri_face.p, leaf_face.size()));
+        HIP_TRY(s.fetch(vtx.data(), ctx->rf_vtx.p, vtx.size())); HIP_TRY(s.fetch(nrm.data(), ctx->rf_nrm.p, nrm.size())); HIP_TRY(s.finish()); }
+    for (size_t i = 0; i < nt; i++) {
+        const size_t f = size_t(leaf_face[i]);
+        if (f >= nt) return fail(MCPT_ERR_HIP, who + "the context's leaf order is damaged");
+        for (int k = 0; k < 3; k++) { fv[3 * f + k] = idx6[6 * i + k]; fnm[3 * f + k] = idx6[6 * i + 3 + k]; }
+    }
+    std::vector<uint32_t> offset; std::vector<NrEntry> entry;
+    const uint32_t max_valence = nr_per_record(fv.data(), fnm.data(), uint32_t(nt), n_normal, normal_mask, vtx.data(), nrm.data(), offset, entry);
+    st = nr_alloc(ctx, entry.size()); if (st != MCPT_OK) return st;
+    {   Scratch s(ctx->stream);
+        HIP_TRY(s.put(ctx->nr_offset.p, offset.data(), offset.size())); HIP_TRY(s.put(ctx->nr_entry.p, entry.data(), entry.size())); HIP_TRY(s.finish()); }
+    ctx->nr_mode = o.mode; ctx->nr_max_valence = max_valence; ctx->nr_records = 0;
+    for (uint32_t i = 0; i < n_normal; i++) ctx->nr_records += offset[size_t(i) + 1] > offset[i];
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_update_normals(mcpt_ctx* ctx) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_update_normals: the context was created without MCPT_FLAG_DYNAMIC");
+    if (ctx->nr_mode == MCPT_NORMALS_OFF) return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_normals: auto normals are not set (mcpt_set_auto_normals)");
+    return rf_enqueue_update(ctx, RfUpdate{nullptr, nullptr, nullptr, nullptr, nullptr, true});
+}
+
+mcpt_status mcpt_get_normals_info(mcpt_ctx* ctx, mcpt_normals_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    HIP_TRY(ctx->nr_watch.settle());
+    std::memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out; out->mode = ctx->nr_mode; out->records = ctx->nr_records; out->max_valence = ctx->nr_max_valence;
+    out->entries = ctx->nr_entry.count(); out->updates = ctx->nr_updates; out->last_ms = ctx->nr_watch.last_ms;
+    return MCPT_OK;
 }
 
 mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {

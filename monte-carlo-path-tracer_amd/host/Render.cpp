@@ -299,6 +299,26 @@ bool Render::update_morph(Scene& scene, const std::vector<double>& weights, cons
     }
     return restart(scene);
 }
+bool Render::set_auto_normals(Scene&, Model& m, const std::vector<uint8_t>& face_mask) {
+    if (!ctx) return false;
+    const size_t nn = m.normal.size();
+    if (!face_mask.empty() && face_mask.size() != m.face.size()) { std::cerr << "Error: Render::set_auto_normals: need one flag per face (or none)" << std::endl; return false; }
+    std::vector<uint8_t> mask(nn, face_mask.empty() ? 1 : 0);                // the normal records that the chosen faces name
+    for (size_t f = 0; f < m.face.size() && !face_mask.empty(); f++)
+        for (int c = 0; c < 3 && face_mask[f]; c++) {
+            const int ni = m.face[f][c][1];
+            if (ni < 0 || size_t(ni) >= nn) { std::cerr << "Error: Render::set_auto_normals: face " << f << " names a normal out of range" << std::endl; return false; }
+            mask[size_t(ni)] = 1;
+        }
+    mcpt_normals_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.mode = MCPT_NORMALS_AREA;
+    if (mcpt_set_auto_normals(ctx, mask.data(), uint32_t(nn), &o) != MCPT_OK) { std::cerr << "Error: mcpt_set_auto_normals: " << mcpt_last_error() << std::endl; return false; }
+    return true;
+}
+bool Render::update_normals(Scene& scene) {
+    if (!ctx) return false;
+    if (mcpt_update_normals(ctx) != MCPT_OK) { std::cerr << "Error: mcpt_update_normals: " << mcpt_last_error() << std::endl; return false; }
+    return restart(scene);
+}
 bool Render::update_materials(Scene& scene, Model& m) {
     if (!ctx) return false;
     std::vector<mcpt_material> mats; std::vector<mcpt_texture> texs; mcpt_scene_desc d;

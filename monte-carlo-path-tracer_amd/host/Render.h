@@ -87,6 +87,13 @@ public:
     bool update_morph_reproject(Scene& scene, const std::vector<double>& weights, const CameraInfo& camera, float max_history = 0);
     bool update_morph_reproject(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices, float max_history = 0);
     bool update_morph_reproject(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices, const CameraInfo& camera, float max_history = 0);
+    // Smooth normals recomputed on the device after every update.  set_auto_normals: one flag per face of `m_model`, the Model this
+    // Render was made from (MCPT_FLAG_DYNAMIC); the normal records that the flagged faces name (an empty face_mask: all records) are from now
+    // on recomputed from the deformed faces by every update*() call -- area-weighted, overriding what the call itself wrote for them, Model::normal
+    // included; the scene as it is now is the reference pose that fixes each face's side.  The film is not touched.  update_normals: the pass
+    // now, nothing moves; starts the picture again like update().  false (Render and Scene unchanged) on failure.
+    bool set_auto_normals(Scene& scene, Model& m_model, const std::vector<uint8_t>& face_mask = {});
+    bool update_normals(Scene& scene);
     // New trees for the geometry as it is now (mcpt_rebuild_trees): after update() / update_transforms() have moved the scene far
     // (mcpt_update_info::wide_area_ratio says how far) the refitted trees are sound and slow; this builds them anew on the context.  The picture
     // goes ON: `scene`'s film, the sample numbering and the feature buffers stay, the scene looks the same from every pixel.  Synchronous.  false

@@ -43,6 +43,9 @@ static void usage() {
                  "                                        vertices (one morph target on the device, delta = vertex - centroid, weight AMOUNT sin(2 pi k / N) in frame k:\n"
                  "                                        a uniform scaling, so the normals stay); combines with --bend (morph, then skin, one call per frame);\n"
                  "                                        honours --reproject; not with --wobble or --spin\n"
+                 "                          [--auto-normals]   with --turntable and --wobble, --bend or --swell: the smooth normals are recomputed on the device after\n"
+                 "                                        every frame's update, area-weighted, from the deformed faces -- all normals with --wobble, otherwise those\n"
+                 "                                        of the named material's faces (honours --reproject and --rebuild-above)\n"
                  "                          [--rebuild-above R]   with --turntable and --wobble, --spin, --bend or --swell: after a frame's update the trees are built anew\n"
                  "                                        (mcpt_rebuild_trees, film kept) when wide_area_ratio exceeds R; prints frame, ratio and cost per rebuild\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
@@ -76,6 +79,7 @@ int main(int argc, char** argv) {
     bool pulse = false; double pulse_a = 0.0;
     std::string spin, bend, swell; double bend_deg = 0.0, swell_a = 0.0;
     bool rebuild = false; double rebuild_above = 0.0;
+    bool auto_normals = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -99,6 +103,7 @@ int main(int argc, char** argv) {
         else if (a == "--spin") spin = next();
         else if (a == "--bend") { bend = next(); bend_deg = std::atof(next()); }
         else if (a == "--swell") { swell = next(); swell_a = std::atof(next()); }
+        else if (a == "--auto-normals") auto_normals = true;
         else if (a == "--rebuild-above") { rebuild = true; rebuild_above = std::atof(next()); }
         else { usage(); return 2; }
     }
@@ -117,6 +122,9 @@ int main(int argc, char** argv) {
     }
     if (rebuild && (!turntable || !(wobble || !spin.empty() || !bend.empty() || !swell.empty()) || !(rebuild_above >= 0.0))) {
         std::cerr << "Error: --rebuild-above R needs --turntable N with --wobble, --spin, --bend or --swell, and R >= 0" << std::endl; return 2;
+    }
+    if (auto_normals && (!turntable || !(wobble || !bend.empty() || !swell.empty()))) {
+        std::cerr << "Error: --auto-normals needs --turntable N with --wobble, --bend or --swell (the updates whose normals it recomputes)" << std::endl; return 2;
     }
     if (wobble || !spin.empty() || !bend.empty() || !swell.empty()) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
@@ -259,6 +267,20 @@ int main(int argc, char** argv) {
                 target[0].delta.push_back(model.vertex[i].x - centre[0]); target[0].delta.push_back(model.vertex[i].y - centre[1]); target[0].delta.push_back(model.vertex[i].z - centre[2]);
             }
             if (!renders[0]->set_morph(scene, model, target)) return 1;
+        }
+        // --auto-normals: every update below is followed by the normals pass -- over all normals with --wobble, which moves every
+        // vertex, otherwise over the normals of the faces of --bend's and --swell's materials
+        if (auto_normals) {
+            std::vector<uint8_t> face_mask;                                  // empty: all
+            if (!wobble) {
+                const int bend_mtl = bend.empty() ? -1 : model.material_index(bend), swell_mtl = swell.empty() ? -1 : model.material_index(swell);
+                face_mask.assign(model.face.size(), 0);
+                for (size_t i = 0; i < model.face.size(); i++) {
+                    const int mtl = model.face[i][0][3];
+                    face_mask[i] = mtl >= 0 && (mtl == bend_mtl || mtl == swell_mtl);
+                }
+            }
+            if (!renders[0]->set_auto_normals(scene, model, face_mask)) return 1;
         }
         for (uint32_t f = 0; f < turntable; f++) {
             const double a = 2.0 * 3.14159265358979323846 * double(f) / double(turntable), ca = std::cos(a), sa = std::sin(a);
