@@ -518,6 +518,43 @@ typedef struct mcpt_skin_info {
 } mcpt_skin_info;
 mcpt_status mcpt_get_skin_info(mcpt_ctx* ctx, mcpt_skin_info* out);   /* synchronises */
 
+/* ---- deforming parts: dual-quaternion skinning -------------------------------------------------------------------------------- */
+/* Blending the bones' MATRICES shrinks a twisted part: two bones that differ by a rotation of 170 degrees, blended half and half, leave a ring of
+ * vertices at 0.087 of its radius, and at 180 degrees the surface collapses onto the axis (the "candy wrapper" above).  The second skinning mode
+ * blends the bones as unit DUAL QUATERNIONS (Kavan et al. 2008): the blend of rigid motions is again a rigid motion, the ring keeps its radius and
+ * turns by half the angle.
+ *
+ * mcpt_set_skin_mode: MCPT_SKIN_LINEAR (the default: everything above, bit for bit) or MCPT_SKIN_DUAL_QUATERNION.  A sticky property of the
+ * context: it may be set before or after mcpt_set_vertex_skin, survives another mcpt_set_vertex_skin, travels with mcpt_clone_to_device and is
+ * kept by mcpt_rebuild_trees.  Synchronous.  MCPT_ERR_UNSUPPORTED without MCPT_FLAG_DYNAMIC; MCPT_ERR_INVALID_ARG for an unknown mode, with nothing
+ * changed.  While the mode is MCPT_SKIN_DUAL_QUATERNION and a skin is set the context holds a second table of 8 doubles per bone (64 B x n_bones,
+ * counted in device_bytes) and a pinned stage of that size; both are released when the mode goes back to MCPT_SKIN_LINEAR.
+ *
+ * Every call that takes bones -- mcpt_update_skin, mcpt_update_skin_reproject, mcpt_update_morph and mcpt_update_morph_reproject with bones --
+ * follows the mode.  The bones are given as before, one row-major 3x4 matrix [A | t] each.  In MCPT_SKIN_DUAL_QUATERNION mode:
+ *  - Every bone must be RIGID: det A > 0 and |(A^T A)ij - delta_ij| <= 1e-6 for every entry, each entry computed as (a0i a0j + a1i a1j) + a2i a2j
+ *    (rotations built in fp32 pass).  A scaled, sheared or mirrored bone is MCPT_ERR_INVALID_ARG: such bones need MCPT_SKIN_LINEAR.  The checks run
+ *    in mcpt_update_skin's order, after its own matrix checks; the reach bound (1 + 2^-16) (2 R_b + 16 ((|tx| + |ty|) + |tz|)) <= 1e18 per bone
+ *    replaces the row bound (with a morph in the same call its reach E stands for every R_b).  It is conservative too: a rotation carries
+ *    |p|inf <= R_b to at most sqrt(3) R_b, and the blended translation is at most 16 S times the longest of the blended bones' translations.
+ *  - The host turns each bone into the unit dual quaternion {w, x, y, z, dw, dx, dy, dz}: the rotation by Shepperd's method (the largest of
+ *    trace, a00, a11, a22 decides the branch, the first wins a tie), divided by its length, negated when w < 0; the dual part is 1/2 (0, t) q.
+ *    Only these 8 doubles per bone cross the bus.
+ *  - Per record SLOT 0 IS THE PIVOT, whatever its weight (put the main bone first): slot k = 1..3 enters with the sign s_k = -1 when the dot
+ *    product of its rotation quaternion with slot 0's is < 0, else +1 -- q and -q are the same rotation, and the blend goes the short way round.
+ *    All eight components are blended as ((w0 q0 + (w1 s1) q1) + (w2 s2) q2) + (w3 s3) q3, all four slots in that order.  With n2 the squared
+ *    length of the blended rotation part: when !(n2 >= 2^-8 && n2 < inf) the blend is DEGENERATE and the record keeps its rest pose, bit for bit
+ *    (this needs three or four wildly opposed bones: two bones in slots 0 and 1 give n2 >= 1/2).  Otherwise both parts are divided by sqrt(n2), R is the rotation
+ *    matrix of the real part r, t = 2 (r.w d_v - d.w r_v + r_v x d_v), and a vertex becomes per row ((R0 x + R1 y) + R2 z) + t.
+ *  - A normal, with its own influences, blends the rotation parts only, by the same signs and the same degenerate rule (a degenerate normal is
+ *    copied as it is, not normalised); otherwise R rest_normal per row (R0 x + R1 y) + R2 z, divided by its length when that is finite and > 0.
+ *  - Everything in fp64, one rounding per operation; DESIGN.md §21 fixes the association of every expression.
+ * Refit, automatic normals, ordering, bookkeeping (mcpt_skin_info, mcpt_update_info) and the reprojection are the same in both modes. */
+#define MCPT_SKIN_LINEAR          0u   /* blend the bones' matrices (the default) */
+#define MCPT_SKIN_DUAL_QUATERNION 1u   /* blend the bones as unit dual quaternions: rigid bones only */
+mcpt_status mcpt_set_skin_mode(mcpt_ctx* ctx, uint32_t mode);
+mcpt_status mcpt_get_skin_mode(mcpt_ctx* ctx, uint32_t* out_mode);
+
 /* ---- deforming parts: morph targets (blend shapes) on the device -------------------------------------------------------------- */
 /* A facial expression, a bulging muscle or a breathing chest is a weighted sum of per-vertex displacement sets, not a matrix per bone.  The caller
  * names the targets once -- each a sparse list of records and their displacements -- and then sends ONE WEIGHT PER TARGET and frame: the device

@@ -20,7 +20,7 @@ from . import scenes  # noqa: F401  (re-export)
 # mcpt_rebuild_trees' options, info and builder constants; tests/test_rebuild.py holds their layout to the header
 from .rebuild_abi import REBUILD_DEVICE, REBUILD_HOST, REBUILD_SAME, RebuildInfo, RebuildOpts  # noqa: F401
 # mcpt_get_skin_info's struct and the influence count; tests/test_skin.py holds the layout to the header
-from .skin_abi import SKIN_INFLUENCES, SkinInfo  # noqa: F401
+from .skin_abi import SKIN_DUAL_QUATERNION, SKIN_INFLUENCES, SKIN_LINEAR, SkinInfo  # noqa: F401
 # mcpt_set_vertex_morph's and mcpt_get_morph_info's structs and the flattening of a target list; tests/test_morph.py holds the layouts to the header
 from .morph_abi import MORPH_MAX_TARGETS, MorphInfo, MorphTargets, flatten_targets, targets_struct  # noqa: F401
 # mcpt_set_auto_normals' and mcpt_get_normals_info's structs and the mask of the normals a set of faces uses; tests/test_normals.py holds the layouts to the header
@@ -290,6 +290,8 @@ def load_library() -> C.CDLL:
         "mcpt_update_skin": [vp, vp, C.c_uint32],
         "mcpt_update_skin_reproject": [vp, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
         "mcpt_get_skin_info": [vp, P(SkinInfo)],
+        "mcpt_set_skin_mode": [vp, C.c_uint32],
+        "mcpt_get_skin_mode": [vp, P(C.c_uint32)],
         "mcpt_set_vertex_morph": [vp, P(MorphTargets), C.c_uint32, P(MorphTargets), C.c_uint32],
         "mcpt_update_morph": [vp, vp, C.c_uint32, vp, C.c_uint32],
         "mcpt_update_morph_reproject": [vp, vp, C.c_uint32, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
@@ -327,6 +329,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_update_materials", "mcpt_update_texture", "mcpt_get_material_info", "mcpt_probe_lights", "mcpt_probe_face_classes",
     "mcpt_set_vertex_groups", "mcpt_update_transforms", "mcpt_update_transforms_reproject", "mcpt_get_transform_info",
     "mcpt_set_vertex_skin", "mcpt_update_skin", "mcpt_update_skin_reproject", "mcpt_get_skin_info",
+    "mcpt_set_skin_mode", "mcpt_get_skin_mode",
     "mcpt_set_vertex_morph", "mcpt_update_morph", "mcpt_update_morph_reproject", "mcpt_get_morph_info", "mcpt_probe_vertices",
     "mcpt_set_auto_normals", "mcpt_update_normals", "mcpt_get_normals_info",
     "mcpt_rebuild_trees", "mcpt_get_rebuild_info",
@@ -621,6 +624,18 @@ class Renderer:
         i = SkinInfo()
         self._check(self.lib.mcpt_get_skin_info(self.ctx, C.byref(i)))
         return i
+
+    # ---- deforming parts: dual-quaternion skinning
+    def set_skin_mode(self, mode: int):
+        """SKIN_LINEAR (the default) or SKIN_DUAL_QUATERNION: how update_skin, update_skin_reproject and update_morph with bones blend a record's
+        bones from now on.  Dual-quaternion mode keeps the volume of a twisted part and takes rigid bones only (rotation and translation); slot 0
+        of a record is its pivot.  Sticky: survives set_vertex_skin, clone and rebuild.  Needs FLAG_DYNAMIC.  Synchronous."""
+        self._check(self.lib.mcpt_set_skin_mode(self.ctx, int(mode)))
+
+    def skin_mode(self) -> int:
+        m = C.c_uint32()
+        self._check(self.lib.mcpt_get_skin_mode(self.ctx, C.byref(m)))
+        return int(m.value)
 
     # ---- deforming parts: morph targets (DESIGN.md §19)
     def set_vertex_morph(self, vertex_targets, normal_targets=None):

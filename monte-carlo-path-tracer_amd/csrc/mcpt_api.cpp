@@ -222,6 +222,10 @@ struct mcpt_ctx {
     Staging<double> sk_stage; std::vector<double> sk_radius;
     Stopwatch sk_watch;
     uint32_t sk_n_bones = 0, sk_updates = 0;
+    // Dual-quaternion mode: the mode is sticky and lives as long as the context; the table of SK_DQ_RECORD doubles per bone
+    // (counted in device_bytes) and its pinned staging exist exactly while the mode is MCPT_SKIN_DUAL_QUATERNION AND a skin is set.
+    uint32_t sk_mode = MCPT_SKIN_LINEAR;
+    DevBuf<double> sk_dq_table; Staging<double> sk_dq_stage;
     // Morph targets (morph.hip), allocated by mcpt_set_vertex_morph and counted in device_bytes: the morph's OWN rest pose (rf_vtx's
     // and rf_nrm's sizes; independent of the groups' and the skin's), per array of records its n + 1 list offsets and its 32-byte entries, the
     // table of one weight per target and its pinned staging.  mo_tmp_vtx / mo_tmp_nrm (rf_vtx's and rf_nrm's sizes, counted too) are allocated by
@@ -518,9 +522,11 @@ static mcpt_status xf_alloc(mcpt_ctx* c, uint32_t n_groups) {
 static mcpt_status sk_alloc(mcpt_ctx* c, uint32_t n_bones) {
     uint64_t* tally = &c->info.device_bytes;
     const size_t nt = size_t(n_bones) * SK_RECORD, nv = size_t(c->rf_n_vertex) * SK_INFLUENCES, nn = size_t(c->rf_n_normal) * SK_INFLUENCES;
+    const size_t nq = size_t(n_bones) * SK_DQ_RECORD; const bool dq = c->sk_mode == MCPT_SKIN_DUAL_QUATERNION;   // §21: the second table follows n_bones
     HIP_TRY(alloc_all(Want(c->sk_rest_vtx, c->rf_vtx.count(), tally), Want(c->sk_rest_nrm, c->rf_nrm.count(), tally), Want(c->sk_vbone, nv, tally),
                       Want(c->sk_nbone, nn, tally), Want(c->sk_vweight, nv, tally), Want(c->sk_nweight, nn, tally), Want(c->sk_table, nt, tally),
-                      Want(c->sk_stage, nt), Want(c->sk_watch, 1, nullptr, !c->sk_watch.ev0)));
+                      Want(c->sk_stage, nt), Want(c->sk_watch, 1, nullptr, !c->sk_watch.ev0), Want(c->sk_dq_table, nq, tally, dq),
+                      Want(c->sk_dq_stage, nq, nullptr, dq)));
     c->sk_n_bones = n_bones; c->sk_radius.assign(n_bones, 0.0);
     return MCPT_OK;
 }
@@ -562,6 +568,7 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
         HIP_TRY(copy(c->xf_rest_vtx, src->xf_rest_vtx)); HIP_TRY(copy(c->xf_rest_nrm, src->xf_rest_nrm));
         HIP_TRY(copy(c->xf_vgroup, src->xf_vgroup)); HIP_TRY(copy(c->xf_ngroup, src->xf_ngroup));
     }
+    c->sk_mode = src->sk_mode;                                             // the skinning mode travels too, with or without a skin (§21)
     if (src->sk_n_bones) {                                                 // the skin, its rest pose and R_b travel with the clone (§18)
         mcpt_status ks = sk_alloc(c, src->sk_n_bones); if (ks != MCPT_OK) return ks;
         c->sk_radius = src->sk_radius;
@@ -569,6 +576,7 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
         HIP_TRY(copy(c->sk_rest_vtx, src->sk_rest_vtx)); HIP_TRY(copy(c->sk_rest_nrm, src->sk_rest_nrm));
         HIP_TRY(copy(c->sk_vbone, src->sk_vbone)); HIP_TRY(copy(c->sk_nbone, src->sk_nbone));
         HIP_TRY(copy(c->sk_vweight, src->sk_vweight)); HIP_TRY(copy(c->sk_nweight, src->sk_nweight));
+        HIP_TRY(copy(c->sk_dq_table, src->sk_dq_table));                     // (§21; empty in MCPT_SKIN_LINEAR mode)
     }
     if (src->mo_n_targets) {                                               // the morph, its rest pose, R and D_k travel with the clone (§19)
         mcpt_status ms = mo_alloc(c, src->mo_n_targets, src->mo_ventry.count(), src->mo_nentry.count()); if (ms != MCPT_OK) return ms;
@@ -1344,6 +1352,17 @@ static mcpt_status sk_check_update(const mcpt_ctx* ctx, const double* m3x4, uint
         const double det = sk_bone_det(m3x4 + 12 * size_t(b));
         if (!(std::isfinite(det) && det != 0.0)) return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": det A is zero or not finite");
     }
+    if (ctx->sk_mode == MCPT_SKIN_DUAL_QUATERNION) {                             // §21: rigid bones only, and the reach bound in place of the row bound
+        for (uint32_t b = 0; b < n_bones; b++)
+            if (!sk_bone_rigid(m3x4 + 12 * size_t(b)))
+                return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": not a rigid transform (det A <= 0, or A^T A differs from the identity by more than 1e-6): "
+                                                        "dual-quaternion skinning takes rotations and translations only; scaled, sheared or mirrored bones need MCPT_SKIN_LINEAR");
+        for (uint32_t b = 0; b < n_bones; b++) {
+            const double reach = sk_dq_reach(m3x4 + 12 * size_t(b), every_radius ? *every_radius : ctx->sk_radius[b]);
+            if (!(reach <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": a vertex could leave |coordinate| <= 1e18 (conservative bound)");
+        }
+        return MCPT_OK;
+    }
     for (uint32_t b = 0; b < n_bones; b++)
         for (int r = 0; r < 3; r++) {
             const double reach = sk_row_reach(m3x4 + 12 * size_t(b) + 4 * r, every_radius ? *every_radius : ctx->sk_radius[b]);
@@ -1369,6 +1388,35 @@ static mcpt_status mo_check_update(const mcpt_ctx* ctx, const double* weight, ui
 // (sk_check_update), or one weight per morph target -- the one source that combines with another, `bones` (mo_check_update).  `no_source`
 // (§20, mcpt_update_normals): nothing is staged and no vertex moves; the normals pass and the refit run on the arrays as they are.
 struct RfUpdate { const double* vertex; const double* normal; const double* m3x4; const double* bones; const double* morph; bool no_source; };
+// The bones of a checked update into the pinned stage of the context's skinning mode: the 3x4 matrices as they are (§18), or one unit dual
+// quaternion per bone (§21).
+static mcpt_status sk_stage_bones(mcpt_ctx* ctx, const double* bones) {
+    if (ctx->sk_mode == MCPT_SKIN_DUAL_QUATERNION) {
+        HIP_TRY(ctx->sk_dq_stage.wait());
+        for (uint32_t b = 0; b < ctx->sk_n_bones; b++) sk_bone_dualquat(bones + 12 * size_t(b), ctx->sk_dq_stage.host + SK_DQ_RECORD * size_t(b));
+    } else {
+        HIP_TRY(ctx->sk_stage.wait());
+        std::memcpy(ctx->sk_stage.host, bones, ctx->sk_table.bytes);
+    }
+    return MCPT_OK;
+}
+// The staged table to the device, in stream order.
+static mcpt_status sk_send_bones(mcpt_ctx* ctx, hipStream_t s) {
+    if (ctx->sk_mode == MCPT_SKIN_DUAL_QUATERNION) HIP_TRY(ctx->sk_dq_stage.send(ctx->sk_dq_table.p, 0, ctx->sk_dq_table.count(), s));
+    else HIP_TRY(ctx->sk_stage.send(ctx->sk_table.p, 0, ctx->sk_table.count(), s));
+    return MCPT_OK;
+}
+// The two skinning kernels of the context's mode: rf_vtx / rf_nrm from the given rest pose.
+static mcpt_status sk_launch(mcpt_ctx* ctx, const double* rest_vtx, const double* rest_nrm, hipStream_t s) {
+    if (ctx->sk_mode == MCPT_SKIN_DUAL_QUATERNION) {
+        HIP_TRY(launch_sk_dq_vertices(rest_vtx, ctx->sk_vbone.p, ctx->sk_vweight.p, ctx->sk_dq_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
+        HIP_TRY(launch_sk_dq_normals(rest_nrm, ctx->sk_nbone.p, ctx->sk_nweight.p, ctx->sk_dq_table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+    } else {
+        HIP_TRY(launch_sk_vertices(rest_vtx, ctx->sk_vbone.p, ctx->sk_vweight.p, ctx->sk_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
+        HIP_TRY(launch_sk_normals(rest_nrm, ctx->sk_nbone.p, ctx->sk_nweight.p, ctx->sk_table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+    }
+    return MCPT_OK;
+}
 // The update itself: the new vertices and normals reach rf_vtx / rf_nrm -- arrays staged and copied, or the staged table of matrices applied to the
 // groups' or the skin's rest pose on the device --, with auto normals on the chosen normal records are recomputed from them (§20), and both trees
 // are refitted, all on the context's stream.
@@ -1381,13 +1429,9 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     } else if (u.morph) {
         HIP_TRY(ctx->mo_stage.wait());
         std::memcpy(ctx->mo_stage.host, u.morph, ctx->mo_weight.bytes);
-        if (u.bones) {
-            HIP_TRY(ctx->sk_stage.wait());
-            std::memcpy(ctx->sk_stage.host, u.bones, ctx->sk_table.bytes);
-        }
+        if (u.bones) { const mcpt_status st = sk_stage_bones(ctx, u.bones); if (st != MCPT_OK) return st; }
     } else if (u.bones) {
-        HIP_TRY(ctx->sk_stage.wait());
-        std::memcpy(ctx->sk_stage.host, u.bones, ctx->sk_table.bytes);
+        const mcpt_status st = sk_stage_bones(ctx, u.bones); if (st != MCPT_OK) return st;
     } else if (u.m3x4) {
         HIP_TRY(ctx->xf_stage.wait());
         for (uint32_t g = 0; g < ctx->xf_n_groups; g++) xf_group_record(u.m3x4 + 12 * size_t(g), ctx->xf_stage.host + XF_RECORD * size_t(g));
@@ -1406,21 +1450,19 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
         double* const mv = u.bones ? ctx->mo_tmp_vtx.p : ctx->rf_vtx.p; double* const mn = u.bones ? ctx->mo_tmp_nrm.p : ctx->rf_nrm.p;
         HIP_TRY(ctx->mo_watch.begin(s));
         HIP_TRY(ctx->mo_stage.send(ctx->mo_weight.p, 0, ctx->mo_weight.count(), s));
-        if (u.bones) HIP_TRY(ctx->sk_stage.send(ctx->sk_table.p, 0, ctx->sk_table.count(), s));
+        if (u.bones) { const mcpt_status st = sk_send_bones(ctx, s); if (st != MCPT_OK) return st; }
         HIP_TRY(launch_mo_vertices(ctx->mo_rest_vtx.p, ctx->mo_voffset.p, ctx->mo_ventry.p, ctx->mo_weight.p, mv, ctx->rf_n_vertex, s));
         HIP_TRY(launch_mo_normals(ctx->mo_rest_nrm.p, ctx->mo_noffset.p, ctx->mo_nentry.p, ctx->mo_weight.p, mn, ctx->rf_n_normal, s));
         if (u.bones) {
-            HIP_TRY(launch_sk_vertices(mv, ctx->sk_vbone.p, ctx->sk_vweight.p, ctx->sk_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
-            HIP_TRY(launch_sk_normals(mn, ctx->sk_nbone.p, ctx->sk_nweight.p, ctx->sk_table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+            const mcpt_status st = sk_launch(ctx, mv, mn, s); if (st != MCPT_OK) return st;   // in the context's skinning mode (§21)
             ctx->sk_updates++;
         }
         HIP_TRY(ctx->mo_watch.end(s));
         ctx->mo_updates++;
     } else if (u.bones) {
         HIP_TRY(ctx->sk_watch.begin(s));
-        HIP_TRY(ctx->sk_stage.send(ctx->sk_table.p, 0, ctx->sk_table.count(), s));
-        HIP_TRY(launch_sk_vertices(ctx->sk_rest_vtx.p, ctx->sk_vbone.p, ctx->sk_vweight.p, ctx->sk_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
-        HIP_TRY(launch_sk_normals(ctx->sk_rest_nrm.p, ctx->sk_nbone.p, ctx->sk_nweight.p, ctx->sk_table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+        mcpt_status st = sk_send_bones(ctx, s); if (st != MCPT_OK) return st;
+        st = sk_launch(ctx, ctx->sk_rest_vtx.p, ctx->sk_rest_nrm.p, s); if (st != MCPT_OK) return st;   // in the context's skinning mode (§21)
         HIP_TRY(ctx->sk_watch.end(s));
         ctx->sk_updates++;
     } else if (u.m3x4) {
@@ -1556,6 +1598,32 @@ mcpt_status mcpt_update_skin(mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     st = sk_check_update(ctx, m3x4, n_bones, "mcpt_update_skin"); if (st != MCPT_OK) return st;
     return rf_enqueue_update(ctx, RfUpdate{nullptr, nullptr, nullptr, m3x4});
+}
+
+// ------------------------------------------------------------------------------------------------ dual-quaternion skinning
+mcpt_status mcpt_set_skin_mode(mcpt_ctx* ctx, uint32_t mode) {
+    const std::string who = "mcpt_set_skin_mode: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if (mode != MCPT_SKIN_LINEAR && mode != MCPT_SKIN_DUAL_QUATERNION) return fail(MCPT_ERR_INVALID_ARG, who + "unknown mode");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // no kernel reads the table and no copy out of its stage is under way
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    if (mode == ctx->sk_mode) return MCPT_OK;
+    if (mode == MCPT_SKIN_DUAL_QUATERNION && ctx->sk_n_bones) {                  // the table exists while the mode AND a skin are known; all or none
+        const size_t nq = size_t(ctx->sk_n_bones) * SK_DQ_RECORD;
+        HIP_TRY(alloc_all(Want(ctx->sk_dq_table, nq, &ctx->info.device_bytes), Want(ctx->sk_dq_stage, nq)));
+    } else if (mode == MCPT_SKIN_LINEAR) {
+        ctx->sk_dq_table.release(); ctx->sk_dq_stage = Staging<double>{};
+    }
+    ctx->sk_mode = mode;
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_get_skin_mode(mcpt_ctx* ctx, uint32_t* out_mode) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out_mode) return fail(MCPT_ERR_INVALID_ARG, "mcpt_get_skin_mode: null output");
+    *out_mode = ctx->sk_mode;
+    return MCPT_OK;
 }
 
 mcpt_status mcpt_get_skin_info(mcpt_ctx* ctx, mcpt_skin_info* out) {

@@ -263,6 +263,11 @@ bool Render::update_skin(Scene& scene, const std::vector<double>& matrices) {
     if (mcpt_update_skin(ctx, matrices.data(), uint32_t(matrices.size() / 12)) != MCPT_OK) { std::cerr << "Error: mcpt_update_skin: " << mcpt_last_error() << std::endl; return false; }
     return restart(scene);
 }
+bool Render::set_skin_mode(Scene&, uint32_t mode) {
+    if (!ctx) return false;
+    if (mcpt_set_skin_mode(ctx, mode) != MCPT_OK) { std::cerr << "Error: mcpt_set_skin_mode: " << mcpt_last_error() << std::endl; return false; }
+    return true;
+}
 // One set of targets flattened into what mcpt_morph_targets points to; false when a target's delta count is not 3 per index.
 static bool flatten_targets(const std::vector<MorphTarget>& targets, std::vector<uint32_t>& offset, std::vector<uint32_t>& index, std::vector<double>& delta, mcpt_morph_targets& t) {
     offset.assign(1, 0u);

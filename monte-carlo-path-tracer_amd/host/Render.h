@@ -74,6 +74,11 @@ public:
     bool update_skin(Scene& scene, const std::vector<double>& matrices);
     bool update_skin_reproject(Scene& scene, const std::vector<double>& matrices, float max_history = 0);
     bool update_skin_reproject(Scene& scene, const std::vector<double>& matrices, const CameraInfo& camera, float max_history = 0);
+    // Dual-quaternion skinning.  set_skin_mode: MCPT_SKIN_LINEAR (the default) or MCPT_SKIN_DUAL_QUATERNION -- how update_skin,
+    // update_skin_reproject and update_morph with bones blend a vertex's bones from now on (mcpt_set_skin_mode; before or after set_skin).  In
+    // dual-quaternion mode a twisted part keeps its volume; the bones must be rigid (rotation and translation) and the first of a vertex's four
+    // bones is its pivot.  Neither film nor scene is touched.  false (nothing changed) on failure.
+    bool set_skin_mode(Scene& scene, uint32_t mode);
     // Morph targets.  set_morph: one MorphTarget per target over the vertices of `m_model`, the Model this Render was made from
     // (MCPT_FLAG_DYNAMIC), and -- optionally, as many -- over its normals (none: the normals are not morphed); the scene as it is now becomes
     // the morph's rest pose.  The film is not touched.  update_morph: one weight per target, the weighted displacements added to the rest pose

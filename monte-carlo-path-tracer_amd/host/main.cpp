@@ -39,6 +39,8 @@ static void usage() {
                  "                                        device): a vertex follows the upper bone by its height inside the part's y-extent, the lower bone stays,\n"
                  "                                        the upper one turns by DEG sin(2 pi k / N) about z through the part's centre in frame k (honours --reproject;\n"
                  "                                        not with --wobble or --spin)\n"
+                 "                          [--dual-quat]   with --bend: the bones are blended as unit dual quaternions instead of matrices (DESIGN.md 21): the bent\n"
+                 "                                        part keeps its volume however far it turns; the bones must be rigid, as --bend's are\n"
                  "                          [--swell MTLNAME AMOUNT]   with --turntable: the faces of that material swell and shrink about the centroid of their\n"
                  "                                        vertices (one morph target on the device, delta = vertex - centroid, weight AMOUNT sin(2 pi k / N) in frame k:\n"
                  "                                        a uniform scaling, so the normals stay); combines with --bend (morph, then skin, one call per frame);\n"
@@ -79,7 +81,7 @@ int main(int argc, char** argv) {
     bool pulse = false; double pulse_a = 0.0;
     std::string spin, bend, swell; double bend_deg = 0.0, swell_a = 0.0;
     bool rebuild = false; double rebuild_above = 0.0;
-    bool auto_normals = false;
+    bool auto_normals = false, dual_quat = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -102,6 +104,7 @@ int main(int argc, char** argv) {
         else if (a == "--light-pulse") { pulse = true; pulse_a = std::atof(next()); }
         else if (a == "--spin") spin = next();
         else if (a == "--bend") { bend = next(); bend_deg = std::atof(next()); }
+        else if (a == "--dual-quat") dual_quat = true;
         else if (a == "--swell") { swell = next(); swell_a = std::atof(next()); }
         else if (a == "--auto-normals") auto_normals = true;
         else if (a == "--rebuild-above") { rebuild = true; rebuild_above = std::atof(next()); }
@@ -117,6 +120,7 @@ int main(int argc, char** argv) {
     if (!bend.empty() && (!turntable || wobble || !spin.empty() || !(std::fabs(bend_deg) <= 1e6))) {
         std::cerr << "Error: --bend MTLNAME DEG needs --turntable N, a finite DEG and neither --wobble nor --spin (all three write the vertices)" << std::endl; return 2;
     }
+    if (dual_quat && bend.empty()) { std::cerr << "Error: --dual-quat needs --bend MTLNAME DEG (it chooses how --bend's bones are blended)" << std::endl; return 2; }
     if (!swell.empty() && (!turntable || wobble || !spin.empty() || !(std::fabs(swell_a) <= 1e6))) {
         std::cerr << "Error: --swell MTLNAME AMOUNT needs --turntable N, a finite AMOUNT and neither --wobble nor --spin (all three write the vertices)" << std::endl; return 2;
     }
@@ -240,6 +244,9 @@ int main(int argc, char** argv) {
                 bone[4 * i] = 1u; weight[4 * i] = 1.0 - t; bone[4 * i + 1] = 2u; weight[4 * i + 1] = t;
             }
             if (!renders[0]->set_skin(scene, model, bone, weight, 3u)) return 1;
+            // --dual-quat: before the first frame.  The bones below are rotations about z through the pivot: rigid, as the mode asks; were they not,
+            // the library's refusal names the bone and the rule, and it is printed as it is -- the bones are never changed to fit
+            if (dual_quat && !renders[0]->set_skin_mode(scene, MCPT_SKIN_DUAL_QUATERNION)) return 1;
         }
         // --swell MTLNAME AMOUNT: ONE morph target over that material's vertices, delta = vertex - centroid: a uniform scaling about a
         // point leaves every normal as it is, so there is no normal target

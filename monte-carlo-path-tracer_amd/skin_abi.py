@@ -1,8 +1,9 @@
-"""ctypes mirror of include/mcpt.h's skinning section: mcpt_skin_info and MCPT_SKIN_INFLUENCES.  Re-exported by the package;
-tests/test_skin.py holds the struct's size and offsets to the header."""
+"""ctypes mirror of include/mcpt.h's skinning sections: mcpt_skin_info, MCPT_SKIN_INFLUENCES and the skinning modes.
+Re-exported by the package; tests/test_skin.py holds the struct's size and offsets to the header, tests/test_skin_dq.py the modes' values."""
 import ctypes as C
 
 SKIN_INFLUENCES = 4
+SKIN_LINEAR, SKIN_DUAL_QUATERNION = 0, 1                 # mcpt_set_skin_mode
 
 
 class SkinInfo(C.Structure):
