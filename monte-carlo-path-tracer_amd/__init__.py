@@ -355,6 +355,11 @@ def _reproject_opts(feature_spp=0, feature_seed=0, max_history=0.0, depth_tolera
     return o
 
 
+def _camera_and_opts(camera, opts):
+    """The last two arguments of an update_*_reproject call: the camera (None: the view stays) and reproject_camera's options, both by reference."""
+    return None if camera is None else C.byref(_camera_c(camera)), C.byref(_reproject_opts(**opts))
+
+
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -527,9 +532,8 @@ class Renderer:
         up where the new view's surface points were before the update.  opts: reproject_camera's.  Needs FLAG_DYNAMIC.  Asynchronous."""
         v = np.ascontiguousarray(vertex, np.float64).reshape(-1, 3)
         n = None if normal is None else np.ascontiguousarray(normal, np.float64).reshape(-1, 3)
-        c = None if camera is None else C.byref(_camera_c(camera))
-        o = _reproject_opts(**opts)
-        self._check(self.lib.mcpt_update_vertices_reproject(self.ctx, _ptr(v), v.shape[0], _ptr(n), 0 if n is None else n.shape[0], c, C.byref(o)))
+        c, o = _camera_and_opts(camera, opts)
+        self._check(self.lib.mcpt_update_vertices_reproject(self.ctx, _ptr(v), v.shape[0], _ptr(n), 0 if n is None else n.shape[0], c, o))
 
     def probe_first_hits(self):
         """The first-hit kernel on the current scene and camera: ((h, w) face, -1 = miss; (h, w, 3) {u, v, t})."""
@@ -587,9 +591,8 @@ class Renderer:
     def update_transforms_reproject(self, matrices, camera=None, **opts):
         """update_transforms that carries the film over, as update_vertices_reproject does; opts: reproject_camera's."""
         m = self._matrices(matrices)
-        c = None if camera is None else C.byref(_camera_c(camera))
-        o = _reproject_opts(**opts)
-        self._check(self.lib.mcpt_update_transforms_reproject(self.ctx, _ptr(m), m.shape[0], c, C.byref(o)))
+        c, o = _camera_and_opts(camera, opts)
+        self._check(self.lib.mcpt_update_transforms_reproject(self.ctx, _ptr(m), m.shape[0], c, o))
 
     def transform_info(self) -> TransformInfo:
         i = TransformInfo()
@@ -616,9 +619,8 @@ class Renderer:
     def update_skin_reproject(self, matrices, camera=None, **opts):
         """update_skin that carries the film over, as update_vertices_reproject does; opts: reproject_camera's."""
         m = self._matrices(matrices)
-        c = None if camera is None else C.byref(_camera_c(camera))
-        o = _reproject_opts(**opts)
-        self._check(self.lib.mcpt_update_skin_reproject(self.ctx, _ptr(m), m.shape[0], c, C.byref(o)))
+        c, o = _camera_and_opts(camera, opts)
+        self._check(self.lib.mcpt_update_skin_reproject(self.ctx, _ptr(m), m.shape[0], c, o))
 
     def skin_info(self) -> SkinInfo:
         i = SkinInfo()
@@ -663,9 +665,8 @@ class Renderer:
     def update_morph_reproject(self, weights, bones=None, camera=None, **opts):
         """update_morph that carries the film over, as update_vertices_reproject does; opts: reproject_camera's."""
         w, m = self._weights_and_bones(weights, bones)
-        c = None if camera is None else C.byref(_camera_c(camera))
-        o = _reproject_opts(**opts)
-        self._check(self.lib.mcpt_update_morph_reproject(self.ctx, _ptr(w), w.shape[0], _ptr(m), 0 if m is None else m.shape[0], c, C.byref(o)))
+        c, o = _camera_and_opts(camera, opts)
+        self._check(self.lib.mcpt_update_morph_reproject(self.ctx, _ptr(w), w.shape[0], _ptr(m), 0 if m is None else m.shape[0], c, o))
 
     def morph_info(self) -> MorphInfo:
         i = MorphInfo()

@@ -125,6 +125,10 @@ template <class... O> hipError_t alloc_all(Want<O>... w) {
     return e;
 }
 
+mcpt_status fail(mcpt_status s, const std::string& msg) { g_err = msg; return s; }
+mcpt_status hip_fail(hipError_t e, const char* what) { g_err = std::string(what) + ": " + hipGetErrorString(e); return MCPT_ERR_HIP; }
+#define HIP_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, #call); } while (0)
+
 }  // namespace
 
 struct mcpt_ctx {
@@ -207,41 +211,112 @@ struct mcpt_ctx {
     uint32_t rf_updates = 0; double rf_area0 = 0.0;
     // Tree rebuilds (rebuild.hip): what mcpt_get_rebuild_info reports.  The call owns its temporaries; nothing of it stays allocated.
     uint32_t rb_rebuilds = 0; double rb_last_ms = 0.0, rb_last_build_ms = 0.0, rb_last_device_ms = 0.0, rb_area_before = 1.0;
-    // Rigid parts (transform.hip), allocated by mcpt_set_vertex_groups and counted in device_bytes: the rest pose (rf_vtx's and
-    // rf_nrm's sizes), a group id per vertex and per normal, the table of XF_RECORD doubles per group and its pinned staging.  On the host per
-    // group R_g, the largest |coordinate| among its vertices that a face uses (what mcpt_update_transforms validates against).
-    DevBuf<double> xf_rest_vtx, xf_rest_nrm, xf_table; DevBuf<uint32_t> xf_vgroup, xf_ngroup;
-    Staging<double> xf_stage; std::vector<double> xf_radius;
-    Stopwatch xf_watch;
-    uint32_t xf_n_groups = 0, xf_updates = 0;
-    // Linear-blend skinning (skin.hip), allocated by mcpt_set_vertex_skin and counted in device_bytes: the skin's OWN rest pose
-    // (rf_vtx's and rf_nrm's sizes; independent of the groups'), SK_INFLUENCES bone ids and weights per vertex and per normal, the table of
-    // SK_RECORD doubles per bone and its pinned staging.  On the host per bone R_b, the largest |coordinate| among the vertices that a face uses
-    // and that give the bone a weight > 0 (what mcpt_update_skin validates against).
-    DevBuf<double> sk_rest_vtx, sk_rest_nrm, sk_table, sk_vweight, sk_nweight; DevBuf<uint32_t> sk_vbone, sk_nbone;
-    Staging<double> sk_stage; std::vector<double> sk_radius;
-    Stopwatch sk_watch;
-    uint32_t sk_n_bones = 0, sk_updates = 0;
-    // Dual-quaternion mode: the mode is sticky and lives as long as the context; the table of SK_DQ_RECORD doubles per bone
-    // (counted in device_bytes) and its pinned staging exist exactly while the mode is MCPT_SKIN_DUAL_QUATERNION AND a skin is set.
-    uint32_t sk_mode = MCPT_SKIN_LINEAR;
-    DevBuf<double> sk_dq_table; Staging<double> sk_dq_stage;
-    // Morph targets (morph.hip), allocated by mcpt_set_vertex_morph and counted in device_bytes: the morph's OWN rest pose (rf_vtx's
-    // and rf_nrm's sizes; independent of the groups' and the skin's), per array of records its n + 1 list offsets and its 32-byte entries, the
-    // table of one weight per target and its pinned staging.  mo_tmp_vtx / mo_tmp_nrm (rf_vtx's and rf_nrm's sizes, counted too) are allocated by
-    // the first mcpt_update_morph WITH bones: the morphed arrays that skin.hip's kernels then read as their rest pose (those kernels' `rest` and
-    // `out` are __restrict__: they cannot work in place).  On the host R, the largest |coordinate| among the rest-pose vertices that a face uses,
-    // and per target D_k, the largest |delta component| among its entries on such vertices (what mcpt_update_morph validates against).
-    DevBuf<double> mo_rest_vtx, mo_rest_nrm, mo_weight, mo_tmp_vtx, mo_tmp_nrm; DevBuf<uint32_t> mo_voffset, mo_noffset; DevBuf<MoEntry> mo_ventry, mo_nentry;
-    Staging<double> mo_stage; std::vector<double> mo_delta; double mo_radius = 0.0;
-    Stopwatch mo_watch;
-    uint32_t mo_n_targets = 0, mo_updates = 0;
-    // Automatic normals (normals.hip), allocated by mcpt_set_auto_normals and counted in device_bytes: per normal record its list
-    // offset (rf_n_normal + 1) and the 16-byte entries, one per face that names the record.  The lists follow the description's face order, not
-    // the leaf order: a rebuild keeps them, a clone carries them.  nr_mode == MCPT_NORMALS_OFF: nothing is allocated, no update runs the pass.
-    DevBuf<uint32_t> nr_offset; DevBuf<NrEntry> nr_entry;
-    Stopwatch nr_watch;
-    uint32_t nr_mode = 0, nr_updates = 0, nr_records = 0, nr_max_valence = 0;
+    // One record per deformer that feeds the refit (Groups, Skin, Morph) and one for the normals pass: its device buffers (counted in device_bytes),
+    // pinned stage, host radii, the Stopwatch of its stream work and its `updates` counter.  alloc(): the buffers afresh, all or none -- a context
+    // that had the record keeps it when an allocation fails.  clone_from(): what travels with mcpt_clone_to_device, each buffer named once.
+    struct RestPose { DevBuf<double> vtx, nrm; };             // the scene as the record's set call found it: rf_vtx's and rf_nrm's sizes
+    // Rigid parts (transform.hip), allocated by mcpt_set_vertex_groups: the rest pose, a group id per vertex and per normal, the
+    // table of XF_RECORD doubles per group and its pinned staging.  On the host per group R_g, the largest |coordinate| among its vertices that a
+    // face uses (what mcpt_update_transforms validates against).
+    struct Groups {
+        RestPose rest; DevBuf<double> table; DevBuf<uint32_t> vgroup, ngroup;
+        Staging<double> stage; std::vector<double> radius; Stopwatch watch; uint32_t n_groups = 0, updates = 0;
+        mcpt_status alloc(mcpt_ctx* c, uint32_t n) {
+            uint64_t* tally = &c->info.device_bytes; const size_t nt = size_t(n) * XF_RECORD;
+            HIP_TRY(alloc_all(Want(rest.vtx, c->rf_vtx.count(), tally), Want(rest.nrm, c->rf_nrm.count(), tally), Want(vgroup, c->rf_n_vertex, tally),
+                              Want(ngroup, c->rf_n_normal, tally), Want(table, nt, tally), Want(stage, nt), Want(watch, 1, nullptr, !watch.ev0)));
+            n_groups = n; radius.assign(n, 0.0);
+            return MCPT_OK;
+        }
+        template <class Copy> mcpt_status clone_from(mcpt_ctx* c, const Groups& src, Copy copy) {       // the groups, the rest pose and R_g
+            if (!src.n_groups) return MCPT_OK;
+            const mcpt_status st = alloc(c, src.n_groups); if (st != MCPT_OK) return st;
+            radius = src.radius;
+            HIP_TRY(copy(rest.vtx, src.rest.vtx)); HIP_TRY(copy(rest.nrm, src.rest.nrm)); HIP_TRY(copy(vgroup, src.vgroup)); HIP_TRY(copy(ngroup, src.ngroup));
+            return MCPT_OK;
+        }
+    } xf;
+    // Linear-blend skinning (skin.hip), allocated by mcpt_set_vertex_skin: the skin's OWN rest pose (independent of the groups'),
+    // SK_INFLUENCES bone ids and weights per vertex and per normal, the table of SK_RECORD doubles per bone and its pinned staging.  On the host
+    // per bone R_b, the largest |coordinate| among the vertices that a face uses and that give the bone a weight > 0 (what mcpt_update_skin
+    // validates against).  Dual-quaternion mode: the mode is sticky and lives as long as the context; the table of SK_DQ_RECORD
+    // doubles per bone (counted in device_bytes) and its pinned staging exist exactly while the mode is MCPT_SKIN_DUAL_QUATERNION AND a skin is set.
+    struct Skin {
+        RestPose rest; DevBuf<double> table, vweight, nweight, dq_table; DevBuf<uint32_t> vbone, nbone;
+        Staging<double> stage, dq_stage; std::vector<double> radius; Stopwatch watch; uint32_t n_bones = 0, updates = 0, mode = MCPT_SKIN_LINEAR;
+        bool dq() const { return mode == MCPT_SKIN_DUAL_QUATERNION; }
+        Staging<double>& bone_stage() { return dq() ? dq_stage : stage; }         // the pinned stage and the table that the mode in force uses
+        DevBuf<double>& bone_table() { return dq() ? dq_table : table; }
+        mcpt_status alloc(mcpt_ctx* c, uint32_t n) {
+            uint64_t* tally = &c->info.device_bytes;
+            const size_t nt = size_t(n) * SK_RECORD, nv = size_t(c->rf_n_vertex) * SK_INFLUENCES, nn = size_t(c->rf_n_normal) * SK_INFLUENCES;
+            const size_t nq = size_t(n) * SK_DQ_RECORD;                          // §21: the second table follows n_bones
+            HIP_TRY(alloc_all(Want(rest.vtx, c->rf_vtx.count(), tally), Want(rest.nrm, c->rf_nrm.count(), tally), Want(vbone, nv, tally), Want(nbone, nn, tally),
+                              Want(vweight, nv, tally), Want(nweight, nn, tally), Want(table, nt, tally), Want(stage, nt), Want(watch, 1, nullptr, !watch.ev0),
+                              Want(dq_table, nq, tally, dq()), Want(dq_stage, nq, nullptr, dq())));
+            n_bones = n; radius.assign(n, 0.0);
+            return MCPT_OK;
+        }
+        template <class Copy> mcpt_status clone_from(mcpt_ctx* c, const Skin& src, Copy copy) {         // the skin, its rest pose and R_b
+            mode = src.mode;                                                     // the skinning mode travels too, with or without a skin (§21)
+            if (!src.n_bones) return MCPT_OK;
+            const mcpt_status st = alloc(c, src.n_bones); if (st != MCPT_OK) return st;
+            radius = src.radius;
+            HIP_TRY(copy(rest.vtx, src.rest.vtx)); HIP_TRY(copy(rest.nrm, src.rest.nrm)); HIP_TRY(copy(vbone, src.vbone)); HIP_TRY(copy(nbone, src.nbone));
+            HIP_TRY(copy(vweight, src.vweight)); HIP_TRY(copy(nweight, src.nweight)); HIP_TRY(copy(dq_table, src.dq_table));   // (§21: empty in MCPT_SKIN_LINEAR mode)
+            return MCPT_OK;
+        }
+    } sk;
+    // Morph targets (morph.hip), allocated by mcpt_set_vertex_morph: the morph's OWN rest pose (independent of the groups' and the
+    // skin's), per array of records its n + 1 list offsets and its 32-byte entries, the table of one weight per target and its pinned staging.
+    // `tmp` (rf_vtx's and rf_nrm's sizes, counted too) is allocated by the first mcpt_update_morph WITH bones: the morphed arrays that skin.hip's
+    // kernels then read as their rest pose (those kernels' `rest` and `out` are __restrict__: they cannot work in place).  On the host R, the
+    // largest |coordinate| among the rest-pose vertices that a face uses, and per target D_k, the largest |delta component| among its entries on
+    // such vertices (what mcpt_update_morph validates against).
+    struct Morph {
+        RestPose rest, tmp; DevBuf<double> weight; DevBuf<uint32_t> voffset, noffset; DevBuf<MoEntry> ventry, nentry;
+        Staging<double> stage; std::vector<double> delta; double radius = 0.0; Stopwatch watch; uint32_t n_targets = 0, updates = 0;
+        mcpt_status alloc(mcpt_ctx* c, uint32_t n, size_t vertex_entries, size_t normal_entries) {
+            uint64_t* tally = &c->info.device_bytes;
+            HIP_TRY(alloc_all(Want(rest.vtx, c->rf_vtx.count(), tally), Want(rest.nrm, c->rf_nrm.count(), tally),
+                              Want(voffset, size_t(c->rf_n_vertex) + 1, tally), Want(noffset, size_t(c->rf_n_normal) + 1, tally),
+                              Want(ventry, vertex_entries, tally), Want(nentry, normal_entries, tally), Want(weight, n, tally),
+                              Want(stage, n), Want(watch, 1, nullptr, !watch.ev0)));
+            n_targets = n; delta.assign(n, 0.0); radius = 0.0;
+            return MCPT_OK;
+        }
+        mcpt_status ensure_scratch(mcpt_ctx* c) {                                // the scratch arrays of "morph, then skin", allocated once
+            if (tmp.vtx.p) return MCPT_OK;
+            HIP_TRY(alloc_all(Want(tmp.vtx, c->rf_vtx.count(), &c->info.device_bytes), Want(tmp.nrm, c->rf_nrm.count(), &c->info.device_bytes)));
+            return MCPT_OK;
+        }
+        template <class Copy> mcpt_status clone_from(mcpt_ctx* c, const Morph& src, Copy copy) {        // the morph, its rest pose, R and D_k
+            if (!src.n_targets) return MCPT_OK;
+            const mcpt_status st = alloc(c, src.n_targets, src.ventry.count(), src.nentry.count()); if (st != MCPT_OK) return st;
+            delta = src.delta; radius = src.radius;
+            HIP_TRY(copy(rest.vtx, src.rest.vtx)); HIP_TRY(copy(rest.nrm, src.rest.nrm)); HIP_TRY(copy(voffset, src.voffset)); HIP_TRY(copy(noffset, src.noffset));
+            HIP_TRY(copy(ventry, src.ventry)); HIP_TRY(copy(nentry, src.nentry));
+            return src.tmp.vtx.p ? ensure_scratch(c) : MCPT_OK;                   // (scratch: its contents are not carried)
+        }
+    } mo;
+    // Automatic normals (normals.hip), allocated by mcpt_set_auto_normals: per normal record its list offset (rf_n_normal + 1) and
+    // the 16-byte entries, one per face that names the record.  The lists follow the description's face order, not the leaf order: a rebuild
+    // keeps them, a clone carries them.  mode == MCPT_NORMALS_OFF: nothing is allocated, no update runs the pass.
+    struct Normals {
+        DevBuf<uint32_t> offset; DevBuf<NrEntry> entry; Stopwatch watch; uint32_t mode = 0, updates = 0, records = 0, max_valence = 0;
+        mcpt_status alloc(mcpt_ctx* c, size_t entries) {
+            uint64_t* tally = &c->info.device_bytes;
+            HIP_TRY(alloc_all(Want(offset, size_t(c->rf_n_normal) + 1, tally), Want(entry, entries, tally), Want(watch, 1, nullptr, !watch.ev0)));
+            return MCPT_OK;
+        }
+        template <class Copy> mcpt_status clone_from(mcpt_ctx* c, const Normals& src, Copy copy) {      // the lists
+            if (src.mode == MCPT_NORMALS_OFF) return MCPT_OK;
+            const mcpt_status st = alloc(c, src.entry.count()); if (st != MCPT_OK) return st;
+            mode = src.mode; records = src.records; max_valence = src.max_valence;
+            HIP_TRY(copy(offset, src.offset)); HIP_TRY(copy(entry, src.entry));
+            return MCPT_OK;
+        }
+    } nr;
     // Temporal reprojection (reproject.hip), allocated by the first reprojection call: the old view's features (2 per pixel, swapped
     // with dn_feat per call), a copy of the old film and the reuse counter.
     // Motion-vector reprojection adds, on the first mcpt_update_vertices_reproject: the first hit of every pixel-centre ray and
@@ -261,12 +336,9 @@ struct mcpt_ctx {
 };
 
 static mcpt_status read_back(mcpt_ctx* ctx, void* host, const void* dev, size_t bytes, bool timing = true);
+static mcpt_status resolve_timing(mcpt_ctx* c, bool block = true);
 
 namespace {
-
-mcpt_status fail(mcpt_status s, const std::string& msg) { g_err = msg; return s; }
-mcpt_status hip_fail(hipError_t e, const char* what) { g_err = std::string(what) + ": " + hipGetErrorString(e); return MCPT_ERR_HIP; }
-#define HIP_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, #call); } while (0)
 
 template <class T, class H> hipError_t upload(DevBuf<T>& b, const std::vector<H>& v, uint64_t* tally) {
     static_assert(sizeof(H) == sizeof(T), "the host mirror of a device element has its size (f4h / float4)");
@@ -286,6 +358,9 @@ mcpt_status use(mcpt_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     return MCPT_OK;
 }
+
+// Live scenes need what MCPT_FLAG_DYNAMIC keeps; `who` opens the message ("<entry point>: ").
+mcpt_status require_dynamic(const mcpt_ctx* c, const std::string& who) { return c->dynamic ? MCPT_OK : fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC"); }
 
 mcpt_status check_device(int device) {
     int ndev = 0;
@@ -509,95 +584,49 @@ static mcpt_status rf_setup(mcpt_ctx* c, const HostScene& hs, const mcpt_scene_d
     HIP_TRY(s.put(c->rf_vtx.p, scene->vertex, c->rf_vtx.count())); HIP_TRY(s.put(c->rf_nrm.p, scene->normal, c->rf_nrm.count()));
     return rf_wide_area(c, c->rf_area0);                                  // (synchronises: the caller's arrays have been read)
 }
-// The buffers of §16 for n_groups groups, all or none: a context that had groups keeps them when an allocation fails.
-static mcpt_status xf_alloc(mcpt_ctx* c, uint32_t n_groups) {
-    uint64_t* tally = &c->info.device_bytes;
-    const size_t nt = size_t(n_groups) * XF_RECORD;
-    HIP_TRY(alloc_all(Want(c->xf_rest_vtx, c->rf_vtx.count(), tally), Want(c->xf_rest_nrm, c->rf_nrm.count(), tally), Want(c->xf_vgroup, c->rf_n_vertex, tally),
-                      Want(c->xf_ngroup, c->rf_n_normal, tally), Want(c->xf_table, nt, tally), Want(c->xf_stage, nt), Want(c->xf_watch, 1, nullptr, !c->xf_watch.ev0)));
-    c->xf_n_groups = n_groups; c->xf_radius.assign(n_groups, 0.0);
-    return MCPT_OK;
-}
-// The buffers of §18 for n_bones bones, all or none: a context that had a skin keeps it when an allocation fails.
-static mcpt_status sk_alloc(mcpt_ctx* c, uint32_t n_bones) {
-    uint64_t* tally = &c->info.device_bytes;
-    const size_t nt = size_t(n_bones) * SK_RECORD, nv = size_t(c->rf_n_vertex) * SK_INFLUENCES, nn = size_t(c->rf_n_normal) * SK_INFLUENCES;
-    const size_t nq = size_t(n_bones) * SK_DQ_RECORD; const bool dq = c->sk_mode == MCPT_SKIN_DUAL_QUATERNION;   // §21: the second table follows n_bones
-    HIP_TRY(alloc_all(Want(c->sk_rest_vtx, c->rf_vtx.count(), tally), Want(c->sk_rest_nrm, c->rf_nrm.count(), tally), Want(c->sk_vbone, nv, tally),
-                      Want(c->sk_nbone, nn, tally), Want(c->sk_vweight, nv, tally), Want(c->sk_nweight, nn, tally), Want(c->sk_table, nt, tally),
-                      Want(c->sk_stage, nt), Want(c->sk_watch, 1, nullptr, !c->sk_watch.ev0), Want(c->sk_dq_table, nq, tally, dq),
-                      Want(c->sk_dq_stage, nq, nullptr, dq)));
-    c->sk_n_bones = n_bones; c->sk_radius.assign(n_bones, 0.0);
-    return MCPT_OK;
-}
-// The buffers of §19 for n_targets targets with the given entry counts, all or none: a context that had a morph keeps it when an allocation fails.
-static mcpt_status mo_alloc(mcpt_ctx* c, uint32_t n_targets, size_t vertex_entries, size_t normal_entries) {
-    uint64_t* tally = &c->info.device_bytes;
-    HIP_TRY(alloc_all(Want(c->mo_rest_vtx, c->rf_vtx.count(), tally), Want(c->mo_rest_nrm, c->rf_nrm.count(), tally),
-                      Want(c->mo_voffset, size_t(c->rf_n_vertex) + 1, tally), Want(c->mo_noffset, size_t(c->rf_n_normal) + 1, tally),
-                      Want(c->mo_ventry, vertex_entries, tally), Want(c->mo_nentry, normal_entries, tally), Want(c->mo_weight, n_targets, tally),
-                      Want(c->mo_stage, n_targets), Want(c->mo_watch, 1, nullptr, !c->mo_watch.ev0)));
-    c->mo_n_targets = n_targets; c->mo_delta.assign(n_targets, 0.0); c->mo_radius = 0.0;
-    return MCPT_OK;
-}
-// The scratch arrays of "morph, then skin" (§19), allocated once.
-static mcpt_status mo_ensure_scratch(mcpt_ctx* c) {
-    if (c->mo_tmp_vtx.p) return MCPT_OK;
-    uint64_t* tally = &c->info.device_bytes;
-    HIP_TRY(alloc_all(Want(c->mo_tmp_vtx, c->rf_vtx.count(), tally), Want(c->mo_tmp_nrm, c->rf_nrm.count(), tally)));
-    return MCPT_OK;
-}
-// The buffers of §20 for the given entry count, all or none: a context that had lists keeps them when an allocation fails.
-static mcpt_status nr_alloc(mcpt_ctx* c, size_t entries) {
-    uint64_t* tally = &c->info.device_bytes;
-    HIP_TRY(alloc_all(Want(c->nr_offset, size_t(c->rf_n_normal) + 1, tally), Want(c->nr_entry, entries, tally), Want(c->nr_watch, 1, nullptr, !c->nr_watch.ev0)));
-    return MCPT_OK;
-}
 static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     c->rf_n_vertex = src->rf_n_vertex; c->rf_n_normal = src->rf_n_normal; c->rf_used_vertex = src->rf_used_vertex;
     c->rf_bin_level = src->rf_bin_level; c->rf_wide_level = src->rf_wide_level; c->rf_area0 = src->rf_area0;
     mcpt_status st = rf_alloc(c); if (st != MCPT_OK) return st;
-    HIP_TRY(hipMemcpyPeer(c->rf_idx.p, c->device, src->rf_idx.p, src->device, c->rf_idx.bytes));
-    HIP_TRY(hipMemcpyPeer(c->rf_bin_order.p, c->device, src->rf_bin_order.p, src->device, c->rf_bin_order.bytes));
-    if (c->rf_vtx.bytes) HIP_TRY(hipMemcpyPeer(c->rf_vtx.p, c->device, src->rf_vtx.p, src->device, c->rf_vtx.bytes));
-    if (c->rf_nrm.bytes) HIP_TRY(hipMemcpyPeer(c->rf_nrm.p, c->device, src->rf_nrm.p, src->device, c->rf_nrm.bytes));
-    if (src->xf_n_groups) {                                                // the groups, the rest pose and R_g travel with the clone (§16)
-        mcpt_status xs = xf_alloc(c, src->xf_n_groups); if (xs != MCPT_OK) return xs;
-        c->xf_radius = src->xf_radius;
-        auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
-        HIP_TRY(copy(c->xf_rest_vtx, src->xf_rest_vtx)); HIP_TRY(copy(c->xf_rest_nrm, src->xf_rest_nrm));
-        HIP_TRY(copy(c->xf_vgroup, src->xf_vgroup)); HIP_TRY(copy(c->xf_ngroup, src->xf_ngroup));
-    }
-    c->sk_mode = src->sk_mode;                                             // the skinning mode travels too, with or without a skin (§21)
-    if (src->sk_n_bones) {                                                 // the skin, its rest pose and R_b travel with the clone (§18)
-        mcpt_status ks = sk_alloc(c, src->sk_n_bones); if (ks != MCPT_OK) return ks;
-        c->sk_radius = src->sk_radius;
-        auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
-        HIP_TRY(copy(c->sk_rest_vtx, src->sk_rest_vtx)); HIP_TRY(copy(c->sk_rest_nrm, src->sk_rest_nrm));
-        HIP_TRY(copy(c->sk_vbone, src->sk_vbone)); HIP_TRY(copy(c->sk_nbone, src->sk_nbone));
-        HIP_TRY(copy(c->sk_vweight, src->sk_vweight)); HIP_TRY(copy(c->sk_nweight, src->sk_nweight));
-        HIP_TRY(copy(c->sk_dq_table, src->sk_dq_table));                     // (§21; empty in MCPT_SKIN_LINEAR mode)
-    }
-    if (src->mo_n_targets) {                                               // the morph, its rest pose, R and D_k travel with the clone (§19)
-        mcpt_status ms = mo_alloc(c, src->mo_n_targets, src->mo_ventry.count(), src->mo_nentry.count()); if (ms != MCPT_OK) return ms;
-        c->mo_delta = src->mo_delta; c->mo_radius = src->mo_radius;
-        auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
-        HIP_TRY(copy(c->mo_rest_vtx, src->mo_rest_vtx)); HIP_TRY(copy(c->mo_rest_nrm, src->mo_rest_nrm));
-        HIP_TRY(copy(c->mo_voffset, src->mo_voffset)); HIP_TRY(copy(c->mo_noffset, src->mo_noffset));
-        HIP_TRY(copy(c->mo_ventry, src->mo_ventry)); HIP_TRY(copy(c->mo_nentry, src->mo_nentry));
-        if (src->mo_tmp_vtx.p) { ms = mo_ensure_scratch(c); if (ms != MCPT_OK) return ms; }   // (scratch: its contents are not carried)
-    }
-    if (src->nr_mode != MCPT_NORMALS_OFF) {                                // the auto-normals lists travel with the clone (§20)
-        mcpt_status ns = nr_alloc(c, src->nr_entry.count()); if (ns != MCPT_OK) return ns;
-        c->nr_mode = src->nr_mode; c->nr_records = src->nr_records; c->nr_max_valence = src->nr_max_valence;
-        auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
-        HIP_TRY(copy(c->nr_offset, src->nr_offset)); HIP_TRY(copy(c->nr_entry, src->nr_entry));
-    }
+    auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
+    HIP_TRY(copy(c->rf_idx, src->rf_idx)); HIP_TRY(copy(c->rf_bin_order, src->rf_bin_order)); HIP_TRY(copy(c->rf_vtx, src->rf_vtx)); HIP_TRY(copy(c->rf_nrm, src->rf_nrm));
+    if ((st = c->xf.clone_from(c, src->xf, copy)) != MCPT_OK || (st = c->sk.clone_from(c, src->sk, copy)) != MCPT_OK ||
+        (st = c->mo.clone_from(c, src->mo, copy)) != MCPT_OK || (st = c->nr.clone_from(c, src->nr, copy)) != MCPT_OK) return st;
     HIP_TRY(hipDeviceSynchronize());
     return MCPT_OK;
 }
 // The first-hit features and the last adaptive call's tile error describe the scene as it was.
 static void rf_forget_derived(mcpt_ctx* c) { c->dn_have_features = false; c->dn_have_out = false; c->ad_have_err = false; }
+
+// What mcpt_set_vertex_groups / _skin / _morph do once their arguments are checked, in this order: the stream drained (rf_vtx / rf_nrm are final,
+// and no copy out of the old stage is under way), the record's `alloc`, rf_vtx / rf_nrm copied into `rest` on the device, the caller's per-record
+// arrays `put` through the same Scratch, the vertices fetched: `used(v, far)` sees each one that a face uses and its largest |coordinate|.
+template <class Alloc, class Put, class Used> static mcpt_status rf_capture_rest(mcpt_ctx* ctx, mcpt_ctx::RestPose& rest, Alloc alloc, Put put, Used used) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    mcpt_status st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    st = alloc(); if (st != MCPT_OK) return st;
+    std::vector<double> vtx(ctx->rf_vtx.count());
+    {   Scratch s(ctx->stream);
+        if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(rest.vtx.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(rest.nrm.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        st = put(s); if (st != MCPT_OK) return st;
+        HIP_TRY(s.fetch(vtx.data(), ctx->rf_vtx.p, vtx.size())); HIP_TRY(s.finish()); }
+    for (uint32_t v = 0; v < ctx->rf_n_vertex; v++) {
+        const double* x = vtx.data() + 3 * size_t(v);
+        if (ctx->rf_used_vertex[v]) used(v, std::max({std::fabs(x[0]), std::fabs(x[1]), std::fabs(x[2])}));
+    }
+    return MCPT_OK;
+}
+// The shared opening of the info getters; `watch` is the context's (null with a null context, which is refused before it is looked at).
+template <class Info> static mcpt_status info_begin(mcpt_ctx* ctx, Info* out, Stopwatch* watch) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    HIP_TRY(watch->settle());
+    std::memset(out, 0, sizeof *out); out->struct_size = sizeof *out;
+    return MCPT_OK;
+}
 
 extern "C" {
 
@@ -732,7 +761,7 @@ mcpt_status mcpt_get_scene_info(const mcpt_ctx* ctx, mcpt_scene_info* out) {
 static mcpt_status check_pending_jobs(mcpt_ctx* ctx);
 // Reads the durations of finished render calls (oldest first).  `block`: wait for all of them -- every entry point that drains the stream
 // anyway, and a render call when per-kernel timing is on (its sampled kernel events are per call).  Otherwise only what has finished.
-static mcpt_status resolve_timing(mcpt_ctx* c, bool block = true) {
+static mcpt_status resolve_timing(mcpt_ctx* c, bool block) {
     while (c->timed_tail != c->timed_head) {
         const uint32_t k = c->timed_tail % mcpt_ctx::TIMED;
         bool done; HIP_TRY(event_done(c->ev1[k], block, done));
@@ -1304,7 +1333,6 @@ mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* cm) {
 // mcpt_update_vertices' rules for its arrays, host only; `fn` names the entry point in the message.
 static mcpt_status rf_check_update(const mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal, const char* fn) {
     const std::string who = std::string(fn) + ": ";
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
     if (!vertex) return fail(MCPT_ERR_INVALID_ARG, who + "null vertex array");
     if (n_vertex != ctx->rf_n_vertex) return fail(MCPT_ERR_INVALID_ARG, who + "n_vertex differs from the scene's");
     if (normal && n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_normal differs from the scene's");
@@ -1319,10 +1347,9 @@ static mcpt_status rf_check_update(const mcpt_ctx* ctx, const double* vertex, ui
 // mcpt_update_transforms' rules for its matrices (§16), host only: no device round trip, hence the conservative row bound against R_g.
 static mcpt_status xf_check_update(const mcpt_ctx* ctx, const double* m3x4, uint32_t n_groups, const char* fn) {
     const std::string who = std::string(fn) + ": ";
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
-    if (!ctx->xf_n_groups) return fail(MCPT_ERR_INVALID_ARG, who + "no groups are set (mcpt_set_vertex_groups)");
+    if (!ctx->xf.n_groups) return fail(MCPT_ERR_INVALID_ARG, who + "no groups are set (mcpt_set_vertex_groups)");
     if (!m3x4) return fail(MCPT_ERR_INVALID_ARG, who + "null matrices");
-    if (n_groups != ctx->xf_n_groups) return fail(MCPT_ERR_INVALID_ARG, who + "n_groups differs from the groups set");
+    if (n_groups != ctx->xf.n_groups) return fail(MCPT_ERR_INVALID_ARG, who + "n_groups differs from the groups set");
     for (size_t k = 0; k < size_t(n_groups) * 12; k++)
         if (!std::isfinite(m3x4[k])) return fail(MCPT_ERR_INVALID_ARG, who + "group " + std::to_string(k / 12) + ": a matrix entry is not finite");
     for (uint32_t g = 0; g < n_groups; g++) {
@@ -1333,7 +1360,7 @@ static mcpt_status xf_check_update(const mcpt_ctx* ctx, const double* m3x4, uint
     }
     for (uint32_t g = 0; g < n_groups; g++)
         for (int r = 0; r < 3; r++) {
-            const double reach = xf_row_reach(m3x4 + 12 * size_t(g) + 4 * r, ctx->xf_radius[g]);
+            const double reach = xf_row_reach(m3x4 + 12 * size_t(g) + 4 * r, ctx->xf.radius[g]);
             if (!(reach <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "group " + std::to_string(g) + ": a vertex could leave |coordinate| <= 1e18 (conservative bound)");
         }
     return MCPT_OK;
@@ -1342,147 +1369,180 @@ static mcpt_status xf_check_update(const mcpt_ctx* ctx, const double* m3x4, uint
 // `every_radius` (§19, morph then skin): the radius that stands for EVERY bone's R_b -- the morphed pose's reach, not the skin's rest pose.
 static mcpt_status sk_check_update(const mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones, const char* fn, const double* every_radius = nullptr) {
     const std::string who = std::string(fn) + ": ";
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
-    if (!ctx->sk_n_bones) return fail(MCPT_ERR_INVALID_ARG, who + "no skin is set (mcpt_set_vertex_skin)");
+    if (!ctx->sk.n_bones) return fail(MCPT_ERR_INVALID_ARG, who + "no skin is set (mcpt_set_vertex_skin)");
     if (!m3x4) return fail(MCPT_ERR_INVALID_ARG, who + "null matrices");
-    if (n_bones != ctx->sk_n_bones) return fail(MCPT_ERR_INVALID_ARG, who + "n_bones differs from the skin set");
+    if (n_bones != ctx->sk.n_bones) return fail(MCPT_ERR_INVALID_ARG, who + "n_bones differs from the skin set");
     for (size_t k = 0; k < size_t(n_bones) * 12; k++)
         if (!std::isfinite(m3x4[k])) return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(k / 12) + ": a matrix entry is not finite");
     for (uint32_t b = 0; b < n_bones; b++) {
         const double det = sk_bone_det(m3x4 + 12 * size_t(b));
         if (!(std::isfinite(det) && det != 0.0)) return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": det A is zero or not finite");
     }
-    if (ctx->sk_mode == MCPT_SKIN_DUAL_QUATERNION) {                             // §21: rigid bones only, and the reach bound in place of the row bound
-        for (uint32_t b = 0; b < n_bones; b++)
-            if (!sk_bone_rigid(m3x4 + 12 * size_t(b)))
-                return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": not a rigid transform (det A <= 0, or A^T A differs from the identity by more than 1e-6): "
-                                                        "dual-quaternion skinning takes rotations and translations only; scaled, sheared or mirrored bones need MCPT_SKIN_LINEAR");
-        for (uint32_t b = 0; b < n_bones; b++) {
-            const double reach = sk_dq_reach(m3x4 + 12 * size_t(b), every_radius ? *every_radius : ctx->sk_radius[b]);
-            if (!(reach <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": a vertex could leave |coordinate| <= 1e18 (conservative bound)");
-        }
-        return MCPT_OK;
-    }
+    const bool dq = ctx->sk.dq();                                                // §21: rigid bones only, and the reach bound in place of the row bound
+    for (uint32_t b = 0; dq && b < n_bones; b++)
+        if (!sk_bone_rigid(m3x4 + 12 * size_t(b)))
+            return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": not a rigid transform (det A <= 0, or A^T A differs from the identity by more than 1e-6): "
+                                                    "dual-quaternion skinning takes rotations and translations only; scaled, sheared or mirrored bones need MCPT_SKIN_LINEAR");
+    const auto within = [dq](const double* m, double radius) {                   // the mode's bound on where a bone can take a vertex of that radius
+        if (dq) return sk_dq_reach(m, radius) <= MCPT_MAX_COORD;
+        return sk_row_reach(m, radius) <= MCPT_MAX_COORD && sk_row_reach(m + 4, radius) <= MCPT_MAX_COORD && sk_row_reach(m + 8, radius) <= MCPT_MAX_COORD;
+    };
     for (uint32_t b = 0; b < n_bones; b++)
-        for (int r = 0; r < 3; r++) {
-            const double reach = sk_row_reach(m3x4 + 12 * size_t(b) + 4 * r, every_radius ? *every_radius : ctx->sk_radius[b]);
-            if (!(reach <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": a vertex could leave |coordinate| <= 1e18 (conservative bound)");
-        }
+        if (!within(m3x4 + 12 * size_t(b), every_radius ? *every_radius : ctx->sk.radius[b]))
+            return fail(MCPT_ERR_INVALID_ARG, who + "bone " + std::to_string(b) + ": a vertex could leave |coordinate| <= 1e18 (conservative bound)");
     return MCPT_OK;
 }
 // mcpt_update_morph's rules for its weights and, when given, its bones (§19), host only: the reach E of the morphed pose bounds the vertices, and
 // stands for every bone's radius in the skin's row bound.
 static mcpt_status mo_check_update(const mcpt_ctx* ctx, const double* weight, uint32_t n_targets, const double* bones, uint32_t n_bones, const char* fn) {
     const std::string who = std::string(fn) + ": ";
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
-    if (!ctx->mo_n_targets) return fail(MCPT_ERR_INVALID_ARG, who + "no morph is set (mcpt_set_vertex_morph)");
+    if (!ctx->mo.n_targets) return fail(MCPT_ERR_INVALID_ARG, who + "no morph is set (mcpt_set_vertex_morph)");
     if (!weight) return fail(MCPT_ERR_INVALID_ARG, who + "null weights");
-    if (n_targets != ctx->mo_n_targets) return fail(MCPT_ERR_INVALID_ARG, who + "n_targets differs from the morph set");
+    if (n_targets != ctx->mo.n_targets) return fail(MCPT_ERR_INVALID_ARG, who + "n_targets differs from the morph set");
     for (uint32_t k = 0; k < n_targets; k++)
         if (!(std::fabs(weight[k]) <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "target " + std::to_string(k) + ": the weight is not finite or exceeds 1e18");
-    const double reach = mo_reach(ctx->mo_radius, weight, ctx->mo_delta.data(), n_targets);
+    const double reach = mo_reach(ctx->mo.radius, weight, ctx->mo.delta.data(), n_targets);
     if (!(reach <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "a vertex could leave |coordinate| <= 1e18 (conservative bound)");
     return bones ? sk_check_update(ctx, bones, n_bones, fn, &reach) : MCPT_OK;
 }
-// A scene update that has been checked: the caller's arrays (rf_check_update), one matrix per group (xf_check_update), one per bone
-// (sk_check_update), or one weight per morph target -- the one source that combines with another, `bones` (mo_check_update).  `no_source`
-// (§20, mcpt_update_normals): nothing is staged and no vertex moves; the normals pass and the refit run on the arrays as they are.
-struct RfUpdate { const double* vertex; const double* normal; const double* m3x4; const double* bones; const double* morph; bool no_source; };
+// A scene update and where its new vertices come from: the caller's arrays (rf_check_update), one matrix per group (xf_check_update), one per
+// bone (sk_check_update), one weight per morph target alone or in front of the bones (mo_check_update).  None (§20, mcpt_update_normals):
+// nothing is staged and no vertex moves; the normals pass and the refit run on the arrays as they are.
+struct RfUpdate {
+    enum class Source { Arrays, Groups, Skin, Morph, MorphSkin, None } source = Source::None;
+    const double* vertex = nullptr; const double* normal = nullptr; uint32_t n_vertex = 0, n_normal = 0;    // Arrays
+    const double* m3x4 = nullptr; uint32_t n_m3x4 = 0;                                                      // Groups: per group; Skin, MorphSkin: per bone
+    const double* weight = nullptr; uint32_t n_weight = 0;                                                  // Morph, MorphSkin: per target
+    static RfUpdate none() { return RfUpdate(); }
+    static RfUpdate arrays(const double* v, uint32_t nv, const double* n, uint32_t nn) {
+        RfUpdate u; u.source = Source::Arrays; u.vertex = v; u.n_vertex = nv; u.normal = n; u.n_normal = nn; return u;
+    }
+    static RfUpdate matrices(Source to, const double* m, uint32_t n) { RfUpdate u; u.source = to; u.m3x4 = m; u.n_m3x4 = n; return u; }
+    static RfUpdate groups(const double* m, uint32_t n) { return matrices(Source::Groups, m, n); }
+    static RfUpdate skin(const double* m, uint32_t n) { return matrices(Source::Skin, m, n); }
+    static RfUpdate morph(const double* w, uint32_t nw, const double* bones, uint32_t n_bones) {             // bones: null = the morph alone
+        RfUpdate u = matrices(bones ? Source::MorphSkin : Source::Morph, bones, n_bones); u.weight = w; u.n_weight = nw; return u;
+    }
+};
+using Source = RfUpdate::Source;
+static mcpt_status rf_update(mcpt_ctx* ctx, const RfUpdate& u, const char* fn, const mcpt_camera* cm, const mcpt_reproject_opts* opts, bool reproject);
 // The bones of a checked update into the pinned stage of the context's skinning mode: the 3x4 matrices as they are (§18), or one unit dual
 // quaternion per bone (§21).
-static mcpt_status sk_stage_bones(mcpt_ctx* ctx, const double* bones) {
-    if (ctx->sk_mode == MCPT_SKIN_DUAL_QUATERNION) {
-        HIP_TRY(ctx->sk_dq_stage.wait());
-        for (uint32_t b = 0; b < ctx->sk_n_bones; b++) sk_bone_dualquat(bones + 12 * size_t(b), ctx->sk_dq_stage.host + SK_DQ_RECORD * size_t(b));
-    } else {
-        HIP_TRY(ctx->sk_stage.wait());
-        std::memcpy(ctx->sk_stage.host, bones, ctx->sk_table.bytes);
-    }
+static mcpt_status sk_stage(mcpt_ctx* ctx, const double* bones) {
+    mcpt_ctx::Skin& sk = ctx->sk;
+    HIP_TRY(sk.bone_stage().wait());
+    if (!sk.dq()) std::memcpy(sk.stage.host, bones, sk.table.bytes);
+    else for (uint32_t b = 0; b < sk.n_bones; b++) sk_bone_dualquat(bones + 12 * size_t(b), sk.dq_stage.host + SK_DQ_RECORD * size_t(b));
     return MCPT_OK;
 }
 // The staged table to the device, in stream order.
-static mcpt_status sk_send_bones(mcpt_ctx* ctx, hipStream_t s) {
-    if (ctx->sk_mode == MCPT_SKIN_DUAL_QUATERNION) HIP_TRY(ctx->sk_dq_stage.send(ctx->sk_dq_table.p, 0, ctx->sk_dq_table.count(), s));
-    else HIP_TRY(ctx->sk_stage.send(ctx->sk_table.p, 0, ctx->sk_table.count(), s));
-    return MCPT_OK;
-}
+static hipError_t sk_send_bones(mcpt_ctx::Skin& sk, hipStream_t s) { return sk.bone_stage().send(sk.bone_table().p, 0, sk.bone_table().count(), s); }
 // The two skinning kernels of the context's mode: rf_vtx / rf_nrm from the given rest pose.
 static mcpt_status sk_launch(mcpt_ctx* ctx, const double* rest_vtx, const double* rest_nrm, hipStream_t s) {
-    if (ctx->sk_mode == MCPT_SKIN_DUAL_QUATERNION) {
-        HIP_TRY(launch_sk_dq_vertices(rest_vtx, ctx->sk_vbone.p, ctx->sk_vweight.p, ctx->sk_dq_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
-        HIP_TRY(launch_sk_dq_normals(rest_nrm, ctx->sk_nbone.p, ctx->sk_nweight.p, ctx->sk_dq_table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
-    } else {
-        HIP_TRY(launch_sk_vertices(rest_vtx, ctx->sk_vbone.p, ctx->sk_vweight.p, ctx->sk_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
-        HIP_TRY(launch_sk_normals(rest_nrm, ctx->sk_nbone.p, ctx->sk_nweight.p, ctx->sk_table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
-    }
+    mcpt_ctx::Skin& sk = ctx->sk; const double* table = sk.bone_table().p;
+    HIP_TRY((sk.dq() ? launch_sk_dq_vertices : launch_sk_vertices)(rest_vtx, sk.vbone.p, sk.vweight.p, table, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
+    HIP_TRY((sk.dq() ? launch_sk_dq_normals : launch_sk_normals)(rest_nrm, sk.nbone.p, sk.nweight.p, table, ctx->rf_nrm.p, ctx->rf_n_normal, s));
     return MCPT_OK;
 }
-// The update itself: the new vertices and normals reach rf_vtx / rf_nrm -- arrays staged and copied, or the staged table of matrices applied to the
-// groups' or the skin's rest pose on the device --, with auto normals on the chosen normal records are recomputed from them (§20), and both trees
-// are refitted, all on the context's stream.
-static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
-    const size_t vd = ctx->rf_vtx.count(), nd = ctx->rf_nrm.count();
-    const bool auto_normals = ctx->nr_mode != MCPT_NORMALS_OFF;                  // §20: the pass below rewrites rf_nrm, so the refit always reads it
-    const bool upload_normal = u.normal != nullptr;                              // the arrays' route: the caller's normals are copied too
-    const bool normal = u.m3x4 || u.bones || u.morph || auto_normals ? nd != 0 : upload_normal;   // are there new normals
-    if (u.no_source) {                                                           // §20, mcpt_update_normals: nothing to stage
-    } else if (u.morph) {
-        HIP_TRY(ctx->mo_stage.wait());
-        std::memcpy(ctx->mo_stage.host, u.morph, ctx->mo_weight.bytes);
-        if (u.bones) { const mcpt_status st = sk_stage_bones(ctx, u.bones); if (st != MCPT_OK) return st; }
-    } else if (u.bones) {
-        const mcpt_status st = sk_stage_bones(ctx, u.bones); if (st != MCPT_OK) return st;
-    } else if (u.m3x4) {
-        HIP_TRY(ctx->xf_stage.wait());
-        for (uint32_t g = 0; g < ctx->xf_n_groups; g++) xf_group_record(u.m3x4 + 12 * size_t(g), ctx->xf_stage.host + XF_RECORD * size_t(g));
-    } else {
-        HIP_TRY(ctx->rf_stage.wait());
-        std::memcpy(ctx->rf_stage.host, u.vertex, vd * sizeof(double));
-        if (upload_normal) std::memcpy(ctx->rf_stage.host + vd, u.normal, nd * sizeof(double));
+// Per source the two halves of an update.  *_stage: the caller's values into the pinned stage once the last copy out of it has been made -- host
+// work and waits only.  *_enqueue: the stage's copy and the kernels that write rf_vtx / rf_nrm on `s`, inside the record's watch, and counted.
+static mcpt_status rf_stage_arrays(mcpt_ctx* ctx, const RfUpdate& u) {
+    HIP_TRY(ctx->rf_stage.wait());
+    std::memcpy(ctx->rf_stage.host, u.vertex, ctx->rf_vtx.bytes);
+    if (u.normal) std::memcpy(ctx->rf_stage.host + ctx->rf_vtx.count(), u.normal, ctx->rf_nrm.bytes);   // the caller's normals are copied too
+    return MCPT_OK;
+}
+static mcpt_status rf_enqueue_arrays(mcpt_ctx* ctx, const RfUpdate& u, hipStream_t s) {
+    HIP_TRY(ctx->rf_stage.send(ctx->rf_vtx.p, 0, ctx->rf_vtx.count(), s, !u.normal));
+    if (u.normal) HIP_TRY(ctx->rf_stage.send(ctx->rf_nrm.p, ctx->rf_vtx.count(), ctx->rf_nrm.count(), s));
+    return MCPT_OK;
+}
+static mcpt_status xf_stage(mcpt_ctx* ctx, const RfUpdate& u) {
+    HIP_TRY(ctx->xf.stage.wait());
+    for (uint32_t g = 0; g < ctx->xf.n_groups; g++) xf_group_record(u.m3x4 + 12 * size_t(g), ctx->xf.stage.host + XF_RECORD * size_t(g));
+    return MCPT_OK;
+}
+static mcpt_status xf_enqueue(mcpt_ctx* ctx, hipStream_t s) {
+    HIP_TRY(ctx->xf.watch.begin(s));
+    HIP_TRY(ctx->xf.stage.send(ctx->xf.table.p, 0, ctx->xf.table.count(), s));
+    HIP_TRY(launch_xf_vertices(ctx->xf.rest.vtx.p, ctx->xf.vgroup.p, ctx->xf.table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
+    HIP_TRY(launch_xf_normals(ctx->xf.rest.nrm.p, ctx->xf.ngroup.p, ctx->xf.table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+    HIP_TRY(ctx->xf.watch.end(s));
+    ctx->xf.updates++;
+    return MCPT_OK;
+}
+static mcpt_status sk_enqueue(mcpt_ctx* ctx, hipStream_t s) {
+    HIP_TRY(ctx->sk.watch.begin(s));
+    HIP_TRY(sk_send_bones(ctx->sk, s));
+    const mcpt_status st = sk_launch(ctx, ctx->sk.rest.vtx.p, ctx->sk.rest.nrm.p, s); if (st != MCPT_OK) return st;   // in the context's skinning mode (§21)
+    HIP_TRY(ctx->sk.watch.end(s));
+    ctx->sk.updates++;
+    return MCPT_OK;
+}
+static mcpt_status mo_stage(mcpt_ctx* ctx, const RfUpdate& u) {
+    HIP_TRY(ctx->mo.stage.wait());
+    std::memcpy(ctx->mo.stage.host, u.weight, ctx->mo.weight.bytes);
+    return u.source == Source::MorphSkin ? sk_stage(ctx, u.m3x4) : MCPT_OK;
+}
+static mcpt_status mo_enqueue(mcpt_ctx* ctx, const RfUpdate& u, hipStream_t s) {
+    const bool skin = u.source == Source::MorphSkin;                             // morph, then skin: the morphed arrays are the skin kernels' rest pose
+    double* const mv = skin ? ctx->mo.tmp.vtx.p : ctx->rf_vtx.p; double* const mn = skin ? ctx->mo.tmp.nrm.p : ctx->rf_nrm.p;
+    HIP_TRY(ctx->mo.watch.begin(s));
+    HIP_TRY(ctx->mo.stage.send(ctx->mo.weight.p, 0, ctx->mo.weight.count(), s));
+    if (skin) HIP_TRY(sk_send_bones(ctx->sk, s));
+    HIP_TRY(launch_mo_vertices(ctx->mo.rest.vtx.p, ctx->mo.voffset.p, ctx->mo.ventry.p, ctx->mo.weight.p, mv, ctx->rf_n_vertex, s));
+    HIP_TRY(launch_mo_normals(ctx->mo.rest.nrm.p, ctx->mo.noffset.p, ctx->mo.nentry.p, ctx->mo.weight.p, mn, ctx->rf_n_normal, s));
+    if (skin) {
+        const mcpt_status st = sk_launch(ctx, mv, mn, s); if (st != MCPT_OK) return st;   // in the context's skinning mode (§21)
+        ctx->sk.updates++;
     }
+    HIP_TRY(ctx->mo.watch.end(s));
+    ctx->mo.updates++;
+    return MCPT_OK;
+}
+// Does the refit read rf_nrm, i.e. are there new normals?  `upload_normal`: the arrays' route got normals from the caller.
+//     source                            auto normals    the refit reads rf_nrm
+//     Groups, Skin, Morph, MorphSkin    off or on       nd != 0   (a deformer rewrites rf_nrm whenever the scene has normals)
+//     Arrays, None                      on              nd != 0   (so does the normals pass, §20)
+//     Arrays, None                      off             upload_normal   (None uploads nothing: no; mcpt_update_normals refuses it before)
+static bool rf_reads_normals(Source source, size_t nd, bool auto_normals, bool upload_normal) {
+    const bool deformer = source != Source::Arrays && source != Source::None;
+    return deformer || auto_normals ? nd != 0 : upload_normal;
+}
+// The update itself: the new vertices and normals reach rf_vtx / rf_nrm -- arrays staged and copied, or the staged table applied to the source's
+// rest pose on the device --, with auto normals on the chosen normal records are recomputed from them (§20), and both trees are refitted, all on the
+// context's stream.  The order is fixed: all host staging and its waits; then, inside rf_watch, the source's stream work, the normals pass, the refit.
+static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
+    const bool auto_normals = ctx->nr.mode != MCPT_NORMALS_OFF;                  // §20: the pass below rewrites rf_nrm, so the refit always reads it
+    mcpt_status st = MCPT_OK;
+    switch (u.source) {
+    case Source::Arrays: st = rf_stage_arrays(ctx, u); break;
+    case Source::Groups: st = xf_stage(ctx, u); break;
+    case Source::Skin: st = sk_stage(ctx, u.m3x4); break;
+    case Source::Morph: case Source::MorphSkin: st = mo_stage(ctx, u); break;
+    case Source::None: break;                                                    // §20, mcpt_update_normals: nothing to stage ...
+    }
+    if (st != MCPT_OK) return st;
     // Everything below is stream work on the context's stream: it starts after every render enqueued so far has finished (the sub-pipelines'
     // streams joined it at the end of their call, known-length jobs included) and the next render's sub-pipelines fork from it after the last
     // kernel here.
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx->rf_watch.begin(s));
-    if (u.no_source) {                                                           // ... and nothing to write
-    } else if (u.morph) {                                                        // morph, then skin: the morphed arrays are the skin kernels' rest pose
-        double* const mv = u.bones ? ctx->mo_tmp_vtx.p : ctx->rf_vtx.p; double* const mn = u.bones ? ctx->mo_tmp_nrm.p : ctx->rf_nrm.p;
-        HIP_TRY(ctx->mo_watch.begin(s));
-        HIP_TRY(ctx->mo_stage.send(ctx->mo_weight.p, 0, ctx->mo_weight.count(), s));
-        if (u.bones) { const mcpt_status st = sk_send_bones(ctx, s); if (st != MCPT_OK) return st; }
-        HIP_TRY(launch_mo_vertices(ctx->mo_rest_vtx.p, ctx->mo_voffset.p, ctx->mo_ventry.p, ctx->mo_weight.p, mv, ctx->rf_n_vertex, s));
-        HIP_TRY(launch_mo_normals(ctx->mo_rest_nrm.p, ctx->mo_noffset.p, ctx->mo_nentry.p, ctx->mo_weight.p, mn, ctx->rf_n_normal, s));
-        if (u.bones) {
-            const mcpt_status st = sk_launch(ctx, mv, mn, s); if (st != MCPT_OK) return st;   // in the context's skinning mode (§21)
-            ctx->sk_updates++;
-        }
-        HIP_TRY(ctx->mo_watch.end(s));
-        ctx->mo_updates++;
-    } else if (u.bones) {
-        HIP_TRY(ctx->sk_watch.begin(s));
-        mcpt_status st = sk_send_bones(ctx, s); if (st != MCPT_OK) return st;
-        st = sk_launch(ctx, ctx->sk_rest_vtx.p, ctx->sk_rest_nrm.p, s); if (st != MCPT_OK) return st;   // in the context's skinning mode (§21)
-        HIP_TRY(ctx->sk_watch.end(s));
-        ctx->sk_updates++;
-    } else if (u.m3x4) {
-        HIP_TRY(ctx->xf_watch.begin(s));
-        HIP_TRY(ctx->xf_stage.send(ctx->xf_table.p, 0, ctx->xf_table.count(), s));
-        HIP_TRY(launch_xf_vertices(ctx->xf_rest_vtx.p, ctx->xf_vgroup.p, ctx->xf_table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
-        HIP_TRY(launch_xf_normals(ctx->xf_rest_nrm.p, ctx->xf_ngroup.p, ctx->xf_table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
-        HIP_TRY(ctx->xf_watch.end(s));
-        ctx->xf_updates++;
-    } else {
-        HIP_TRY(ctx->rf_stage.send(ctx->rf_vtx.p, 0, vd, s, !upload_normal));
-        if (upload_normal) HIP_TRY(ctx->rf_stage.send(ctx->rf_nrm.p, vd, nd, s));
+    switch (u.source) {
+    case Source::Arrays: st = rf_enqueue_arrays(ctx, u, s); break;
+    case Source::Groups: st = xf_enqueue(ctx, s); break;
+    case Source::Skin: st = sk_enqueue(ctx, s); break;
+    case Source::Morph: case Source::MorphSkin: st = mo_enqueue(ctx, u, s); break;
+    case Source::None: break;                                                    // ... and nothing to write
     }
+    if (st != MCPT_OK) return st;
     if (auto_normals) {                                                          // §20: the chosen records from the faces as they are now, in place
-        HIP_TRY(ctx->nr_watch.begin(s));
-        HIP_TRY(launch_nr_normals(ctx->rf_vtx.p, ctx->nr_offset.p, ctx->nr_entry.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
-        HIP_TRY(ctx->nr_watch.end(s));
-        ctx->nr_updates++;
+        HIP_TRY(ctx->nr.watch.begin(s));
+        HIP_TRY(launch_nr_normals(ctx->rf_vtx.p, ctx->nr.offset.p, ctx->nr.entry.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+        HIP_TRY(ctx->nr.watch.end(s));
+        ctx->nr.updates++;
     }
-    const double* d_nrm = normal ? ctx->rf_nrm.p : nullptr;
+    const double* d_nrm = rf_reads_normals(u.source, ctx->rf_nrm.count(), auto_normals, u.normal != nullptr) ? ctx->rf_nrm.p : nullptr;
     const DevScene& d = ctx->dev;
     HIP_TRY(launch_rf_triangles(ctx->rf_vtx.p, d_nrm, ctx->rf_idx.p, RfCentre{d.centre[0], d.centre[1], d.centre[2]}, ctx->tri_isect.p, ctx->tri_shade.p,
                                 ctx->tri_pos64.p, ctx->rf_tri_box.p, uint32_t(d.n_tris), s));
@@ -1499,52 +1559,31 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
 }
 
 mcpt_status mcpt_update_vertices(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    st = rf_check_update(ctx, vertex, n_vertex, normal, n_normal, "mcpt_update_vertices"); if (st != MCPT_OK) return st;
-    return rf_enqueue_update(ctx, RfUpdate{vertex, normal, nullptr});
+    return rf_update(ctx, RfUpdate::arrays(vertex, n_vertex, normal, n_normal), "mcpt_update_vertices", nullptr, nullptr, false);
 }
 
 // ------------------------------------------------------------------------------------------------ rigid parts
 mcpt_status mcpt_set_vertex_groups(mcpt_ctx* ctx, const uint32_t* vertex_group, uint32_t n_vertex, const uint32_t* normal_group, uint32_t n_normal, uint32_t n_groups) {
     const std::string who = "mcpt_set_vertex_groups: ";
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if ((st = require_dynamic(ctx, who)) != MCPT_OK) return st;
     if (n_vertex != ctx->rf_n_vertex || n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_vertex / n_normal differ from the scene's");
     if (!vertex_group || (n_normal && !normal_group)) return fail(MCPT_ERR_INVALID_ARG, who + "null group array");
     if (n_groups < 1 || uint64_t(n_groups) > uint64_t(n_vertex) + n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_groups must be in [1, n_vertex + n_normal]");
     for (uint32_t v = 0; v < n_vertex; v++) if (vertex_group[v] >= n_groups) return fail(MCPT_ERR_INVALID_ARG, who + "vertex " + std::to_string(v) + ": group id >= n_groups");
     for (uint32_t v = 0; v < n_normal; v++) if (normal_group[v] >= n_groups) return fail(MCPT_ERR_INVALID_ARG, who + "normal " + std::to_string(v) + ": group id >= n_groups");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // rf_vtx / rf_nrm are final, and no copy out of the old stage is under way
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    st = xf_alloc(ctx, n_groups); if (st != MCPT_OK) return st;
-    std::vector<double> vtx(ctx->rf_vtx.count());
-    {   Scratch s(ctx->stream);
-        if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->xf_rest_vtx.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->xf_rest_nrm.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(s.put(ctx->xf_vgroup.p, vertex_group, n_vertex)); HIP_TRY(s.put(ctx->xf_ngroup.p, normal_group, n_normal));
-        HIP_TRY(s.fetch(vtx.data(), ctx->rf_vtx.p, vtx.size())); HIP_TRY(s.finish()); }
-    for (uint32_t v = 0; v < n_vertex; v++) {
-        if (!ctx->rf_used_vertex[v]) continue;
-        double& r = ctx->xf_radius[vertex_group[v]];
-        for (int a = 0; a < 3; a++) r = std::max(r, std::fabs(vtx[3 * size_t(v) + a]));
-    }
-    return MCPT_OK;
+    return rf_capture_rest(ctx, ctx->xf.rest, [&] { return ctx->xf.alloc(ctx, n_groups); },
+        [&](Scratch& s) -> mcpt_status { HIP_TRY(s.put(ctx->xf.vgroup.p, vertex_group, n_vertex)); HIP_TRY(s.put(ctx->xf.ngroup.p, normal_group, n_normal)); return MCPT_OK; },
+        [&](uint32_t v, double far) { double& r = ctx->xf.radius[vertex_group[v]]; r = std::max(r, far); });       // R_g: per group
 }
 
 mcpt_status mcpt_update_transforms(mcpt_ctx* ctx, const double* m3x4, uint32_t n_groups) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    st = xf_check_update(ctx, m3x4, n_groups, "mcpt_update_transforms"); if (st != MCPT_OK) return st;
-    return rf_enqueue_update(ctx, RfUpdate{nullptr, nullptr, m3x4});
+    return rf_update(ctx, RfUpdate::groups(m3x4, n_groups), "mcpt_update_transforms", nullptr, nullptr, false);
 }
 
 mcpt_status mcpt_get_transform_info(mcpt_ctx* ctx, mcpt_transform_info* out) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    HIP_TRY(ctx->xf_watch.settle());
-    std::memset(out, 0, sizeof *out);
-    out->struct_size = sizeof *out; out->n_groups = ctx->xf_n_groups; out->updates = ctx->xf_updates; out->last_ms = ctx->xf_watch.last_ms;
+    const mcpt_status st = info_begin(ctx, out, ctx ? &ctx->xf.watch : nullptr); if (st != MCPT_OK) return st;
+    out->n_groups = ctx->xf.n_groups; out->updates = ctx->xf.updates; out->last_ms = ctx->xf.watch.last_ms;
     return MCPT_OK;
 }
 
@@ -1568,72 +1607,57 @@ mcpt_status mcpt_set_vertex_skin(mcpt_ctx* ctx, const uint32_t* vertex_bone, con
                                  const double* normal_weight, uint32_t n_normal, uint32_t n_bones) {
     const std::string who = "mcpt_set_vertex_skin: ";
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if ((st = require_dynamic(ctx, who)) != MCPT_OK) return st;
     if (n_vertex != ctx->rf_n_vertex || n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_vertex / n_normal differ from the scene's");
     if (!vertex_bone || !vertex_weight || (n_normal && (!normal_bone || !normal_weight))) return fail(MCPT_ERR_INVALID_ARG, who + "null bone or weight array");
     if (n_bones < 1 || uint64_t(n_bones) > SK_INFLUENCES * (uint64_t(n_vertex) + n_normal)) return fail(MCPT_ERR_INVALID_ARG, who + "n_bones must be in [1, 4 (n_vertex + n_normal)]");
     st = sk_check_records(vertex_bone, vertex_weight, n_vertex, n_bones, who, "vertex"); if (st != MCPT_OK) return st;
     st = sk_check_records(normal_bone, normal_weight, n_normal, n_bones, who, "normal"); if (st != MCPT_OK) return st;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // rf_vtx / rf_nrm are final, and no copy out of the old stage is under way
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    st = sk_alloc(ctx, n_bones); if (st != MCPT_OK) return st;
-    std::vector<double> vtx(ctx->rf_vtx.count());
-    {   Scratch s(ctx->stream);
-        if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->sk_rest_vtx.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->sk_rest_nrm.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(s.put(ctx->sk_vbone.p, vertex_bone, ctx->sk_vbone.count())); HIP_TRY(s.put(ctx->sk_vweight.p, vertex_weight, ctx->sk_vweight.count()));
-        HIP_TRY(s.put(ctx->sk_nbone.p, normal_bone, ctx->sk_nbone.count())); HIP_TRY(s.put(ctx->sk_nweight.p, normal_weight, ctx->sk_nweight.count()));
-        HIP_TRY(s.fetch(vtx.data(), ctx->rf_vtx.p, vtx.size())); HIP_TRY(s.finish()); }
-    for (uint32_t v = 0; v < n_vertex; v++) {
-        if (!ctx->rf_used_vertex[v]) continue;
-        double far = 0.0;
-        for (int a = 0; a < 3; a++) far = std::max(far, std::fabs(vtx[3 * size_t(v) + a]));
-        for (int k = 0; k < SK_INFLUENCES; k++)
-            if (vertex_weight[SK_INFLUENCES * size_t(v) + k] > 0.0) { double& r = ctx->sk_radius[vertex_bone[SK_INFLUENCES * size_t(v) + k]]; r = std::max(r, far); }
-    }
-    return MCPT_OK;
+    mcpt_ctx::Skin& sk = ctx->sk;
+    return rf_capture_rest(ctx, sk.rest, [&] { return sk.alloc(ctx, n_bones); },
+        [&](Scratch& s) -> mcpt_status {
+            HIP_TRY(s.put(sk.vbone.p, vertex_bone, sk.vbone.count())); HIP_TRY(s.put(sk.vweight.p, vertex_weight, sk.vweight.count()));
+            HIP_TRY(s.put(sk.nbone.p, normal_bone, sk.nbone.count())); HIP_TRY(s.put(sk.nweight.p, normal_weight, sk.nweight.count()));
+            return MCPT_OK; },
+        [&](uint32_t v, double far) {                                            // R_b: per bone that the vertex gives a weight > 0
+            for (int k = 0; k < SK_INFLUENCES; k++)
+                if (vertex_weight[SK_INFLUENCES * size_t(v) + k] > 0.0) { double& r = sk.radius[vertex_bone[SK_INFLUENCES * size_t(v) + k]]; r = std::max(r, far); }
+        });
 }
 
 mcpt_status mcpt_update_skin(mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    st = sk_check_update(ctx, m3x4, n_bones, "mcpt_update_skin"); if (st != MCPT_OK) return st;
-    return rf_enqueue_update(ctx, RfUpdate{nullptr, nullptr, nullptr, m3x4});
+    return rf_update(ctx, RfUpdate::skin(m3x4, n_bones), "mcpt_update_skin", nullptr, nullptr, false);
 }
 
 // ------------------------------------------------------------------------------------------------ dual-quaternion skinning
 mcpt_status mcpt_set_skin_mode(mcpt_ctx* ctx, uint32_t mode) {
     const std::string who = "mcpt_set_skin_mode: ";
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if ((st = require_dynamic(ctx, who)) != MCPT_OK) return st;
     if (mode != MCPT_SKIN_LINEAR && mode != MCPT_SKIN_DUAL_QUATERNION) return fail(MCPT_ERR_INVALID_ARG, who + "unknown mode");
     HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // no kernel reads the table and no copy out of its stage is under way
     st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    if (mode == ctx->sk_mode) return MCPT_OK;
-    if (mode == MCPT_SKIN_DUAL_QUATERNION && ctx->sk_n_bones) {                  // the table exists while the mode AND a skin are known; all or none
-        const size_t nq = size_t(ctx->sk_n_bones) * SK_DQ_RECORD;
-        HIP_TRY(alloc_all(Want(ctx->sk_dq_table, nq, &ctx->info.device_bytes), Want(ctx->sk_dq_stage, nq)));
+    if (mode == ctx->sk.mode) return MCPT_OK;
+    if (mode == MCPT_SKIN_DUAL_QUATERNION && ctx->sk.n_bones) {                  // the table exists while the mode AND a skin are known; all or none
+        const size_t nq = size_t(ctx->sk.n_bones) * SK_DQ_RECORD;
+        HIP_TRY(alloc_all(Want(ctx->sk.dq_table, nq, &ctx->info.device_bytes), Want(ctx->sk.dq_stage, nq)));
     } else if (mode == MCPT_SKIN_LINEAR) {
-        ctx->sk_dq_table.release(); ctx->sk_dq_stage = Staging<double>{};
+        ctx->sk.dq_table.release(); ctx->sk.dq_stage = Staging<double>{};
     }
-    ctx->sk_mode = mode;
+    ctx->sk.mode = mode;
     return MCPT_OK;
 }
 
 mcpt_status mcpt_get_skin_mode(mcpt_ctx* ctx, uint32_t* out_mode) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!out_mode) return fail(MCPT_ERR_INVALID_ARG, "mcpt_get_skin_mode: null output");
-    *out_mode = ctx->sk_mode;
+    *out_mode = ctx->sk.mode;
     return MCPT_OK;
 }
 
 mcpt_status mcpt_get_skin_info(mcpt_ctx* ctx, mcpt_skin_info* out) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    HIP_TRY(ctx->sk_watch.settle());
-    std::memset(out, 0, sizeof *out);
-    out->struct_size = sizeof *out; out->n_bones = ctx->sk_n_bones; out->updates = ctx->sk_updates; out->last_ms = ctx->sk_watch.last_ms;
+    const mcpt_status st = info_begin(ctx, out, ctx ? &ctx->sk.watch : nullptr); if (st != MCPT_OK) return st;
+    out->n_bones = ctx->sk.n_bones; out->updates = ctx->sk.updates; out->last_ms = ctx->sk.watch.last_ms;
     return MCPT_OK;
 }
 
@@ -1666,7 +1690,7 @@ static mcpt_status mo_check_targets(const mcpt_morph_targets* t, uint32_t n_reco
 mcpt_status mcpt_set_vertex_morph(mcpt_ctx* ctx, const mcpt_morph_targets* vertex, uint32_t n_vertex, const mcpt_morph_targets* normal, uint32_t n_normal) {
     const std::string who = "mcpt_set_vertex_morph: ";
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if ((st = require_dynamic(ctx, who)) != MCPT_OK) return st;
     if (n_vertex != ctx->rf_n_vertex || n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_vertex / n_normal differ from the scene's");
     if (!vertex) return fail(MCPT_ERR_INVALID_ARG, who + "null vertex targets");
     st = mo_check_targets(vertex, n_vertex, vertex->n_targets, who, "vertex"); if (st != MCPT_OK) return st;
@@ -1676,50 +1700,36 @@ mcpt_status mcpt_set_vertex_morph(mcpt_ctx* ctx, const mcpt_morph_targets* verte
     mo_per_record(vertex->target_offset, vertex->index, vertex->delta, n_targets, n_vertex, voff, vent);
     if (normal) mo_per_record(normal->target_offset, normal->index, normal->delta, n_targets, n_normal, noff, nent);
     else noff.assign(size_t(n_normal) + 1, 0);                                   // normals are not morphed: every list is empty, every record is copied
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // rf_vtx / rf_nrm are final, and no copy out of the old stage is under way
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    st = mo_alloc(ctx, n_targets, vent.size(), nent.size()); if (st != MCPT_OK) return st;
-    std::vector<double> vtx(ctx->rf_vtx.count());
-    {   Scratch s(ctx->stream);
-        if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->mo_rest_vtx.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->mo_rest_nrm.p, ctx->rf_nrm.p, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(s.put(ctx->mo_voffset.p, voff.data(), voff.size())); HIP_TRY(s.put(ctx->mo_noffset.p, noff.data(), noff.size()));
-        HIP_TRY(s.put(ctx->mo_ventry.p, vent.data(), vent.size())); HIP_TRY(s.put(ctx->mo_nentry.p, nent.data(), nent.size()));
-        HIP_TRY(s.fetch(vtx.data(), ctx->rf_vtx.p, vtx.size())); HIP_TRY(s.finish()); }
-    for (uint32_t v = 0; v < n_vertex; v++) {
-        if (!ctx->rf_used_vertex[v]) continue;
-        for (int a = 0; a < 3; a++) ctx->mo_radius = std::max(ctx->mo_radius, std::fabs(vtx[3 * size_t(v) + a]));
-    }
+    mcpt_ctx::Morph& mo = ctx->mo;
+    st = rf_capture_rest(ctx, mo.rest, [&] { return mo.alloc(ctx, n_targets, vent.size(), nent.size()); },
+        [&](Scratch& s) -> mcpt_status {
+            HIP_TRY(s.put(mo.voffset.p, voff.data(), voff.size())); HIP_TRY(s.put(mo.noffset.p, noff.data(), noff.size()));
+            HIP_TRY(s.put(mo.ventry.p, vent.data(), vent.size())); HIP_TRY(s.put(mo.nentry.p, nent.data(), nent.size()));
+            return MCPT_OK; },
+        [&](uint32_t, double far) { mo.radius = std::max(mo.radius, far); });    // R: global; D_k below: per target
+    if (st != MCPT_OK) return st;
     for (uint32_t k = 0; k < n_targets; k++)
         for (uint32_t e = vertex->target_offset[k]; e < vertex->target_offset[k + 1]; e++) {
             if (!ctx->rf_used_vertex[vertex->index[e]]) continue;
-            for (int a = 0; a < 3; a++) ctx->mo_delta[k] = std::max(ctx->mo_delta[k], std::fabs(vertex->delta[3 * size_t(e) + a]));
+            for (int a = 0; a < 3; a++) mo.delta[k] = std::max(mo.delta[k], std::fabs(vertex->delta[3 * size_t(e) + a]));
         }
     return MCPT_OK;
 }
 
 mcpt_status mcpt_update_morph(mcpt_ctx* ctx, const double* weight, uint32_t n_targets, const double* bones_m3x4, uint32_t n_bones) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    st = mo_check_update(ctx, weight, n_targets, bones_m3x4, n_bones, "mcpt_update_morph"); if (st != MCPT_OK) return st;
-    if (bones_m3x4) { st = mo_ensure_scratch(ctx); if (st != MCPT_OK) return st; }
-    return rf_enqueue_update(ctx, RfUpdate{nullptr, nullptr, nullptr, bones_m3x4, weight});
+    return rf_update(ctx, RfUpdate::morph(weight, n_targets, bones_m3x4, n_bones), "mcpt_update_morph", nullptr, nullptr, false);
 }
 
 mcpt_status mcpt_get_morph_info(mcpt_ctx* ctx, mcpt_morph_info* out) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    HIP_TRY(ctx->mo_watch.settle());
-    std::memset(out, 0, sizeof *out);
-    out->struct_size = sizeof *out; out->n_targets = ctx->mo_n_targets; out->updates = ctx->mo_updates; out->last_ms = ctx->mo_watch.last_ms;
-    out->vertex_entries = ctx->mo_ventry.count(); out->normal_entries = ctx->mo_nentry.count();
+    const mcpt_status st = info_begin(ctx, out, ctx ? &ctx->mo.watch : nullptr); if (st != MCPT_OK) return st;
+    out->n_targets = ctx->mo.n_targets; out->updates = ctx->mo.updates; out->last_ms = ctx->mo.watch.last_ms;
+    out->vertex_entries = ctx->mo.ventry.count(); out->normal_entries = ctx->mo.nentry.count();
     return MCPT_OK;
 }
 
 mcpt_status mcpt_probe_vertices(mcpt_ctx* ctx, double* out_vertex, double* out_normal) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_probe_vertices: the context was created without MCPT_FLAG_DYNAMIC");
+    if ((st = require_dynamic(ctx, "mcpt_probe_vertices: ")) != MCPT_OK) return st;
     st = read_back(ctx, out_vertex, ctx->rf_vtx.p, out_vertex ? ctx->rf_vtx.bytes : 0); if (st != MCPT_OK) return st;
     return read_back(ctx, out_normal, ctx->rf_nrm.p, out_normal ? ctx->rf_nrm.bytes : 0);
 }
@@ -1729,7 +1739,7 @@ mcpt_status mcpt_set_auto_normals(mcpt_ctx* ctx, const uint8_t* normal_mask, uin
     const char* const fn = "mcpt_set_auto_normals";
     const std::string who = std::string(fn) + ": ";
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if ((st = require_dynamic(ctx, who)) != MCPT_OK) return st;
     if (n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_normal differs from the scene's");
     mcpt_normals_opts o;
     st = read_opts(opts, o, fn, "mcpt_normals_opts"); if (st != MCPT_OK) return st;
@@ -1738,8 +1748,8 @@ mcpt_status mcpt_set_auto_normals(mcpt_ctx* ctx, const uint8_t* normal_mask, uin
     HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // rf_vtx / rf_nrm are final, and no kernel reads the old lists any more
     st = resolve_timing(ctx); if (st != MCPT_OK) return st;
     if (o.mode == MCPT_NORMALS_OFF) {
-        ctx->nr_offset.release(); ctx->nr_entry.release();
-        ctx->nr_mode = MCPT_NORMALS_OFF; ctx->nr_records = 0; ctx->nr_max_valence = 0;
+        ctx->nr.offset.release(); ctx->nr.entry.release();
+        ctx->nr.mode = MCPT_NORMALS_OFF; ctx->nr.records = 0; ctx->nr.max_valence = 0;
         return MCPT_OK;
     }
     // the faces in the description's order, from the leaf-order index arrays and the leaf order itself; the reference pose
@@ -1756,41 +1766,31 @@ mcpt_status mcpt_set_auto_normals(mcpt_ctx* ctx, const uint8_t* normal_mask, uin
     }
     std::vector<uint32_t> offset; std::vector<NrEntry> entry;
     const uint32_t max_valence = nr_per_record(fv.data(), fnm.data(), uint32_t(nt), n_normal, normal_mask, vtx.data(), nrm.data(), offset, entry);
-    st = nr_alloc(ctx, entry.size()); if (st != MCPT_OK) return st;
+    st = ctx->nr.alloc(ctx, entry.size()); if (st != MCPT_OK) return st;
     {   Scratch s(ctx->stream);
-        HIP_TRY(s.put(ctx->nr_offset.p, offset.data(), offset.size())); HIP_TRY(s.put(ctx->nr_entry.p, entry.data(), entry.size())); HIP_TRY(s.finish()); }
-    ctx->nr_mode = o.mode; ctx->nr_max_valence = max_valence; ctx->nr_records = 0;
-    for (uint32_t i = 0; i < n_normal; i++) ctx->nr_records += offset[size_t(i) + 1] > offset[i];
+        HIP_TRY(s.put(ctx->nr.offset.p, offset.data(), offset.size())); HIP_TRY(s.put(ctx->nr.entry.p, entry.data(), entry.size())); HIP_TRY(s.finish()); }
+    ctx->nr.mode = o.mode; ctx->nr.max_valence = max_valence; ctx->nr.records = 0;
+    for (uint32_t i = 0; i < n_normal; i++) ctx->nr.records += offset[size_t(i) + 1] > offset[i];
     return MCPT_OK;
 }
 
 mcpt_status mcpt_update_normals(mcpt_ctx* ctx) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_update_normals: the context was created without MCPT_FLAG_DYNAMIC");
-    if (ctx->nr_mode == MCPT_NORMALS_OFF) return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_normals: auto normals are not set (mcpt_set_auto_normals)");
-    return rf_enqueue_update(ctx, RfUpdate{nullptr, nullptr, nullptr, nullptr, nullptr, true});
+    if ((st = require_dynamic(ctx, "mcpt_update_normals: ")) != MCPT_OK) return st;
+    if (ctx->nr.mode == MCPT_NORMALS_OFF) return fail(MCPT_ERR_INVALID_ARG, "mcpt_update_normals: auto normals are not set (mcpt_set_auto_normals)");
+    return rf_enqueue_update(ctx, RfUpdate::none());
 }
 
 mcpt_status mcpt_get_normals_info(mcpt_ctx* ctx, mcpt_normals_info* out) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    HIP_TRY(ctx->nr_watch.settle());
-    std::memset(out, 0, sizeof *out);
-    out->struct_size = sizeof *out; out->mode = ctx->nr_mode; out->records = ctx->nr_records; out->max_valence = ctx->nr_max_valence;
-    out->entries = ctx->nr_entry.count(); out->updates = ctx->nr_updates; out->last_ms = ctx->nr_watch.last_ms;
+    const mcpt_status st = info_begin(ctx, out, ctx ? &ctx->nr.watch : nullptr); if (st != MCPT_OK) return st;
+    out->mode = ctx->nr.mode; out->records = ctx->nr.records; out->max_valence = ctx->nr.max_valence;
+    out->entries = ctx->nr.entry.count(); out->updates = ctx->nr.updates; out->last_ms = ctx->nr.watch.last_ms;
     return MCPT_OK;
 }
 
 mcpt_status mcpt_get_update_info(mcpt_ctx* ctx, mcpt_update_info* out) {
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
-    HIP_TRY(ctx->rf_watch.settle());
-    std::memset(out, 0, sizeof *out);
-    out->struct_size = sizeof *out; out->updates = ctx->rf_updates; out->last_update_ms = ctx->rf_watch.last_ms; out->wide_area_ratio = 1.0;
+    mcpt_status st = info_begin(ctx, out, ctx ? &ctx->rf_watch : nullptr); if (st != MCPT_OK) return st;
+    out->updates = ctx->rf_updates; out->last_update_ms = ctx->rf_watch.last_ms; out->wide_area_ratio = 1.0;
     if (ctx->rf_updates) {                                                      // the last update left its partial sums behind
         double a = 0.0;
         st = rf_read_area(ctx, a); if (st != MCPT_OK) return st;
@@ -1807,7 +1807,7 @@ mcpt_status mcpt_rebuild_trees(mcpt_ctx* ctx, const mcpt_rebuild_opts* opts) {
     const std::string who = "mcpt_rebuild_trees: ";
     const auto t_entry = std::chrono::steady_clock::now();
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, who + "the context was created without MCPT_FLAG_DYNAMIC");
+    if ((st = require_dynamic(ctx, who)) != MCPT_OK) return st;
     mcpt_rebuild_opts o;
     st = read_opts(opts, o, "mcpt_rebuild_trees", "mcpt_rebuild_opts"); if (st != MCPT_OK) return st;
     if (o.builder > MCPT_REBUILD_DEVICE) return fail(MCPT_ERR_INVALID_ARG, who + "unknown builder");
@@ -2186,47 +2186,45 @@ mcpt_status mcpt_probe_reproject(mcpt_ctx* ctx, const mcpt_camera* old_cam, cons
 }
 
 // ------------------------------------------------------------------------------------------------ motion-vector reprojection
+// Every update entry point, plain or _reproject, once it has named its source.  The order of the refusals is part of the interface: the context,
+// the source's own rules (by its tag), the camera (a _reproject form may pass one), the options.  Morph with bones allocates its scratch next,
+// and only in a call that will not be refused: rp_frame turns away unreadable options and a scene whose binary tree is too deep.
+static mcpt_status rf_update(mcpt_ctx* ctx, const RfUpdate& u, const char* fn, const mcpt_camera* cm, const mcpt_reproject_opts* opts, bool reproject) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if ((st = require_dynamic(ctx, std::string(fn) + ": ")) != MCPT_OK) return st;
+    switch (u.source) {
+    case Source::Arrays: st = rf_check_update(ctx, u.vertex, u.n_vertex, u.normal, u.n_normal, fn); break;
+    case Source::Groups: st = xf_check_update(ctx, u.m3x4, u.n_m3x4, fn); break;
+    case Source::Skin: st = sk_check_update(ctx, u.m3x4, u.n_m3x4, fn); break;
+    case Source::Morph: case Source::MorphSkin: st = mo_check_update(ctx, u.weight, u.n_weight, u.m3x4, u.n_m3x4, fn); break;
+    case Source::None: break;                                                    // (mcpt_update_normals makes its own two checks)
+    }
+    if (st != MCPT_OK) return st;
+    if (reproject && cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
+    if (u.source == Source::MorphSkin && (!reproject || ctx->binary_ok)) {
+        mcpt_reproject_opts o;
+        if (reproject) { st = rp_read_opts(opts, o, fn); if (st != MCPT_OK) return st; }
+        st = ctx->mo.ensure_scratch(ctx); if (st != MCPT_OK) return st;
+    }
+    return reproject ? rp_frame(ctx, &u, cm, opts, fn) : rf_enqueue_update(ctx, u);
+}
+
 mcpt_status mcpt_update_vertices_reproject(mcpt_ctx* ctx, const double* vertex, uint32_t n_vertex, const double* normal, uint32_t n_normal,
                                            const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
-    const char* const fn = "mcpt_update_vertices_reproject";
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    st = rf_check_update(ctx, vertex, n_vertex, normal, n_normal, fn); if (st != MCPT_OK) return st;
-    if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
-    const RfUpdate update{vertex, normal, nullptr};
-    return rp_frame(ctx, &update, cm, opts, fn);
+    return rf_update(ctx, RfUpdate::arrays(vertex, n_vertex, normal, n_normal), "mcpt_update_vertices_reproject", cm, opts, true);
 }
 
 mcpt_status mcpt_update_transforms_reproject(mcpt_ctx* ctx, const double* m3x4, uint32_t n_groups, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
-    const char* const fn = "mcpt_update_transforms_reproject";
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    st = xf_check_update(ctx, m3x4, n_groups, fn); if (st != MCPT_OK) return st;
-    if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
-    const RfUpdate update{nullptr, nullptr, m3x4};                               // §16: the matrices in place of the arrays, the same frame
-    return rp_frame(ctx, &update, cm, opts, fn);
+    return rf_update(ctx, RfUpdate::groups(m3x4, n_groups), "mcpt_update_transforms_reproject", cm, opts, true);
 }
 
 mcpt_status mcpt_update_skin_reproject(mcpt_ctx* ctx, const double* m3x4, uint32_t n_bones, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
-    const char* const fn = "mcpt_update_skin_reproject";
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    st = sk_check_update(ctx, m3x4, n_bones, fn); if (st != MCPT_OK) return st;
-    if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
-    const RfUpdate update{nullptr, nullptr, nullptr, m3x4};                      // §18: the bones in place of the arrays, the same frame
-    return rp_frame(ctx, &update, cm, opts, fn);
+    return rf_update(ctx, RfUpdate::skin(m3x4, n_bones), "mcpt_update_skin_reproject", cm, opts, true);
 }
 
 mcpt_status mcpt_update_morph_reproject(mcpt_ctx* ctx, const double* weight, uint32_t n_targets, const double* bones_m3x4, uint32_t n_bones,
                                         const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
-    const char* const fn = "mcpt_update_morph_reproject";
-    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
-    st = mo_check_update(ctx, weight, n_targets, bones_m3x4, n_bones, fn); if (st != MCPT_OK) return st;
-    if (cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
-    if (bones_m3x4 && ctx->binary_ok) {                                          // the scratch is allocated only by a call that rp_frame will not refuse
-        mcpt_reproject_opts o;
-        st = rp_read_opts(opts, o, fn); if (st != MCPT_OK) return st;
-        st = mo_ensure_scratch(ctx); if (st != MCPT_OK) return st;
-    }
-    const RfUpdate update{nullptr, nullptr, nullptr, bones_m3x4, weight};        // §19: the weights (and bones) in place of the arrays, the same frame
-    return rp_frame(ctx, &update, cm, opts, fn);
+    return rf_update(ctx, RfUpdate::morph(weight, n_targets, bones_m3x4, n_bones), "mcpt_update_morph_reproject", cm, opts, true);
 }
 
 mcpt_status mcpt_probe_first_hits(mcpt_ctx* ctx, int32_t* out_face, float* out_uvt3) {
@@ -2255,7 +2253,7 @@ mcpt_status mcpt_probe_reproject_motion(mcpt_ctx* ctx, const mcpt_camera* old_ca
     const char* const fn = "mcpt_probe_reproject_motion";
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (!old_film_host || !old_feat8_host || !new_feat8_host || !hit_face_host || !hit_uv2_host || !out_film_host || !out_reused) return fail(MCPT_ERR_INVALID_ARG, "null argument");
-    if (!ctx->dynamic) return fail(MCPT_ERR_UNSUPPORTED, std::string(fn) + ": the context was created without MCPT_FLAG_DYNAMIC");
+    if ((st = require_dynamic(ctx, std::string(fn) + ": ")) != MCPT_OK) return st;
     const auto stage_motion = [&](Scratch& s, RpOldScene& old) -> mcpt_status {
         mcpt_status st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
         const size_t n = size_t(ctx->width) * ctx->height, nf = ctx->h_tri_face.size();
