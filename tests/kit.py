@@ -3,7 +3,8 @@ the moved sphere), the reprojection suites' synthetic inputs and comparison, the
 brute-force ray tracer the tree-builder suites hold the kernels to.
 
 A plain module, imported like tests/reproject_ref.py.  Where the suites' copies differed in a default or in the order of their arguments the
-function here takes the argument explicitly and every call site passes the value it always used.
+function here takes the argument explicitly and every call site passes the value it always used.  What only the live-scene deformer
+suites share (S-cornell's skins and bones, `state` and its comparisons, the header-layout and host-check harnesses) is in tests/deform_kit.py.
 """
 from __future__ import annotations
 

@@ -1,8 +1,12 @@
-"""The comparison helpers of tests/kit.py, which most suites lean on: bits() must tell apart what "bit for bit" means to tell apart, and
-compare_with_ref() must reject what lies just past its bounds.  CPU only; milliseconds."""
+"""The comparison helpers of tests/kit.py and tests/deform_kit.py, which most suites lean on: bits() must tell apart what "bit for bit" means to
+tell apart, compare_with_ref() must reject what lies just past its bounds, and assert_same(), assert_records() and c_layout() must name what
+differs.  CPU only; milliseconds, but for two calls of the C compiler."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
+from tests.deform_kit import assert_records, assert_same, c_layout
 from tests.kit import bits, compare_with_ref, synthetic_film
 
 
@@ -115,3 +119,65 @@ def test_compare_with_ref_rejects_a_reused_count_past_the_marginal_share():
             compare_with_ref(got, reused + off, want, marg)
     with pytest.raises(AssertionError):
         compare_with_ref(got, reused + 1, want, np.zeros_like(marg))         # no marginal pixel: the counts must be equal
+
+
+# ------------------------------------------------------------------------------------------------------------------------ assert_same
+def _state():
+    return {"t": np.array([0.5, 1.25, 0.0], np.float32), "face": np.array([3, -1, 7], np.int32), "pos": np.array([[1.0, -2.0], [0.0, 1e-30]])}
+
+
+def test_assert_same_passes_on_equal_dicts_and_honours_skip():
+    a, b = _state(), _state()
+    assert_same(a, b)
+    b["pos"][0, 1] = 9.0
+    assert_same(a, b, skip=("pos",))
+    with pytest.raises(AssertionError):
+        assert_same(a, b, skip=("t",))
+    del b["pos"]
+    with pytest.raises(AssertionError):                                      # the two sides hold the same keys
+        assert_same(a, b)
+
+
+@pytest.mark.parametrize("key", ["t", "pos"])
+def test_assert_same_names_the_key_that_is_one_ulp_off(key):
+    a, b = _state(), _state()
+    b[key].flat[1] = np.nextafter(b[key].flat[1], b[key].dtype.type(0))
+    with pytest.raises(AssertionError) as e:
+        assert_same(a, b)
+    assert e.value.args[0].split("\n")[0] == key
+    assert_same(a, b, skip=(key,))
+
+
+def test_assert_same_names_the_key_whose_zero_changed_its_sign():
+    a, b = _state(), _state()
+    b["pos"][1, 0] = -0.0
+    assert np.array_equal(a["pos"], b["pos"])                                # by value they are equal
+    with pytest.raises(AssertionError) as e:
+        assert_same(a, b)
+    assert e.value.args[0].split("\n")[0] == "pos"
+
+
+# ------------------------------------------------------------------------------------------------------------------------ assert_records
+def test_assert_records_names_the_first_differing_record_and_the_count():
+    want = np.random.default_rng(6).normal(size=(40, 3))
+    assert_records(want.copy(), want, "vertex")
+    assert_records(want.copy(), want.tolist(), "vertex")                     # the restatement's side may be a list
+    got = want.copy()
+    got[17, 2] = np.nextafter(got[17, 2], 0.0); got[30, 0] = -got[30, 0]; got[31] += 1.0
+    with pytest.raises(AssertionError) as e:
+        assert_records(got, want, "vertex")
+    msg = e.value.args[0]
+    assert msg.startswith("vertex 17 of 3 differing") and repr(got[17].tolist()) in msg and repr(want[17].tolist()) in msg
+
+
+# ------------------------------------------------------------------------------------------------------------------------ c_layout
+def test_c_layout_tells_a_class_with_two_fields_swapped_from_the_headers_struct(pkg, tmp_path):
+    class Swapped(C.Structure):                                              # pkg.SkinInfo with `updates` and `last_ms` in each other's place
+        _fields_ = [("struct_size", C.c_uint32), ("n_bones", C.c_uint32), ("last_ms", C.c_double), ("reserved0", C.c_uint32), ("updates", C.c_uint32),
+                    ("reserved", C.c_uint32 * 4)]
+
+    c, py, macros = c_layout(pkg.SkinInfo, "mcpt_skin_info", tmp_path, macros=("MCPT_SKIN_INFLUENCES", "MCPT_SKIN_DUAL_QUATERNION"))
+    assert c == py and macros == [4, 1]
+    c2, py2, _ = c_layout(Swapped, "mcpt_skin_info", tmp_path)
+    assert c2 != py2 and c2[0] == py2[0] == c[0]                             # the same size: only the offsets give it away
+    assert sorted(c2) == sorted(c)                                           # (the header's side is the real struct, asked in the class's order)

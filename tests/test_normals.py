@@ -10,35 +10,21 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests import kit, morph_ref as M, normals_ref as N, skin_ref as S, transform_ref as T
-from tests.kit import ROOT, bits, render_film
+from tests import deform_kit as K, kit, morph_ref as M, normals_ref as N, skin_ref as S, transform_ref as T
+from tests.deform_kit import CENTRE, FLAGS, H, INVALID, LAMP, M_LAMP, M_LOW, N_BONES, SPHERE, UNSUPPORTED, W, clean
+from tests.kit import bits, render_film
 
 NEW_SYMBOLS = ["mcpt_set_auto_normals", "mcpt_update_normals", "mcpt_get_normals_info"]
-INVALID, UNSUPPORTED = 1, 6
-W, H = 64, 64
-SPHERE, LAMP = 4, 3                                                          # materials of S-cornell: the glossy sphere, the ceiling light
-CENTRE = np.array([0.5, 0.3, 0.5])                                           # of the sphere (radius 0.3: it stands on the floor)
-N_BONES = 5                                                                  # §18's bend: 0 the walls, 1 and 2 the sphere's bones, 3 nobody, 4 the lamp
 FAN = 70                                                                     # triangles around the apex of the hand-made scene
 
 
-def clean(m):
-    """The matrices without negative zeros (-0.0 + 0.0 = +0.0; everything else is unchanged)."""
-    return np.ascontiguousarray(m, np.float64) + 0.0
-
-
-M_LOW = clean(T.about(T.rotation((0, 0, 1), -6.0), CENTRE, (0.0, 0.06, 0.0)))
-M_HIGH = clean(T.about(T.rotation((0, 0, 1), 25.0) @ np.diag([0.9, 0.7, 0.9]), (0.5, 0.1, 0.5), (0.03, 0.08, -0.04)))
-M_LAMP = clean(T.about(T.rotation((0, 1, 0), 25.0), (0.5, 0.999, 0.5), (0.1, -0.2, 0.05)))
+M_HIGH = clean(T.about(T.rotation((0, 0, 1), 25.0) @ np.diag([0.9, 0.7, 0.9]), (0.5, 0.1, 0.5), (0.03, 0.08, -0.04)))   # (squashes more than deform_kit's)
 M_SQUASH = clean(T.about(T.rotation((1, 0, 0), 20.0) @ np.diag([1.0, 0.6, 0.8]), CENTRE, (0.1, 0.2, -0.05)))
-BEND = T.identity(N_BONES); BEND[1] = M_LOW; BEND[2] = M_HIGH; BEND[4] = M_LAMP
+BEND = K.mats(low=M_LOW, high=M_HIGH, lamp=M_LAMP)                           # §18's bend: 0 the walls, 1 and 2 the sphere's bones, 3 nobody, 4 the lamp
 GROUPS = np.stack([T.identity(1)[0], M_SQUASH, M_LAMP])                      # 0 the walls, 1 the sphere, 2 the lamp
 WEIGHTS = np.array([0.35, -0.6])
 
@@ -46,11 +32,8 @@ WEIGHTS = np.array([0.35, -0.6])
 # ------------------------------------------------------------------------------------------------------------------------ fixtures
 @functools.lru_cache(maxsize=None)
 def _scene(pkg, which="big"):
-    if which == "big":
-        return pkg.scenes.cornell_box(W, H, sphere_lon=48, sphere_lat=24)     # 1 249 normal records: five 256-blocks with a tail
-    if which == "small":
-        return pkg.scenes.cornell_box_small(W, H)                             # 349 records, two of them unused
-    return _fan_scene(pkg)
+    """deform_kit's S-cornell (1 249 normal records), S-cornell-small (349, two of them unused), or the hand-made fan."""
+    return _fan_scene(pkg) if which == "fan" else K.scene(pkg, which == "small")
 
 
 def _fan_scene(pkg):
@@ -100,17 +83,6 @@ def _moved(pkg, scene, step=1):
 
 
 @functools.lru_cache(maxsize=None)
-def _bend(pkg, which="big"):
-    """§18's five-bone skin: walls on bone 0, lamp on bone 4, every sphere vertex blended between bones 1 and 2 by its height; bone 3 has no member."""
-    s = _scene(pkg, which); sphere, lamp = _part(s, SPHERE), _part(s, LAMP)
-    vb, vw = S.single(np.where(lamp, 4, 0))
-    y = s.vertex[sphere, 1]; w = (y - y.min()) / (y.max() - y.min())
-    vb[sphere, 0] = 1; vb[sphere, 1] = 2; vw[sphere, 0] = 1.0 - w; vw[sphere, 1] = w
-    nb, nw = pkg.skin_normals_from_faces(s, vb, vw)
-    return vb, vw, nb, nw
-
-
-@functools.lru_cache(maxsize=None)
 def _targets(pkg, which="big"):
     """Two vertex targets and NO normal targets (the case glTF tells a client to recompute normals for): a lopsided swell of the sphere and a
     lift of its upper half together with the lamp."""
@@ -131,7 +103,7 @@ def _prepare(pkg, R, which, route):
         vg, ng = pkg.groups_from_faces(s, np.where(s.face[:, 0, 3] == SPHERE, 1, np.where(s.face[:, 0, 3] == LAMP, 2, 0)))
         R.set_vertex_groups(vg, ng, 3)
     if route in ("skin", "morph_then_skin"):
-        R.set_vertex_skin(*_bend(pkg, which), N_BONES)
+        R.set_vertex_skin(*K.bend(pkg, which == "small"), N_BONES)
     if route in ("morph", "morph_then_skin"):
         R.set_vertex_morph(_targets(pkg, which), None)
 
@@ -150,7 +122,7 @@ def _route(pkg, R, which, route, current_normal, reproject=None):
         R.update_transforms(GROUPS) if reproject is None else R.update_transforms_reproject(GROUPS, **reproject)
         return T.transform_vertices(s.vertex, vg, GROUPS), T.transform_normals(s.normal, ng, GROUPS)
     if route == "skin":
-        vb, vw, nb, nw = _bend(pkg, which)
+        vb, vw, nb, nw = K.bend(pkg, which == "small")
         R.update_skin(BEND) if reproject is None else R.update_skin_reproject(BEND, **reproject)
         return S.skin_vertices(s.vertex, vb, vw, BEND), S.skin_normals(s.normal, nb, nw, BEND)
     vt = _targets(pkg, which)
@@ -158,19 +130,7 @@ def _route(pkg, R, which, route, current_normal, reproject=None):
         R.update_morph(WEIGHTS) if reproject is None else R.update_morph_reproject(WEIGHTS, **reproject)
         return M.morph_vertices(s.vertex, vt, WEIGHTS), M.morph_normals(s.normal, None, WEIGHTS)
     R.update_morph(WEIGHTS, BEND) if reproject is None else R.update_morph_reproject(WEIGHTS, BEND, **reproject)
-    return M.morph_then_skin(s.vertex, s.normal, vt, None, WEIGHTS, _bend(pkg, which), BEND)
-
-
-def _layout(cls, c_name, tmp_path):
-    """[sizeof, offsetof ...] of a struct as a C compiler sees include/mcpt.h, and the same of the ctypes class."""
-    fields = [f[0] for f in cls._fields_]
-    line = '  printf("%%zu%s\\n", sizeof(%s)%s);' % (" %zu" * len(fields), c_name, "".join(", offsetof(%s, %s)" % (c_name, f) for f in fields))
-    src = tmp_path / (c_name + ".c"); exe = str(tmp_path / c_name)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mcpt.h"\nint main(void) {\n%s\n  printf("%%u %%u %%u\\n", MCPT_ABI_VERSION, MCPT_NORMALS_OFF, MCPT_NORMALS_AREA);\n  return 0; }\n' % line)
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    out = [[int(x) for x in l.split()] for l in subprocess.check_output([exe]).decode().splitlines()]
-    assert out[1] == [4, 0, 1]
-    return out[0], [C.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    return M.morph_then_skin(s.vertex, s.normal, vt, None, WEIGHTS, K.bend(pkg, which == "small"), BEND)
 
 
 def _brute_lists(face, n_normal, mask=None):
@@ -203,8 +163,8 @@ def test_null_context_is_an_invalid_argument_for_the_normals_calls(pkg):
 def test_normals_structs_have_the_headers_layout(pkg, tmp_path):
     """sizeof and every offsetof of mcpt_normals_opts and mcpt_normals_info as a C compiler sees include/mcpt.h, against the ctypes classes."""
     for cls, name, size in ((pkg.NormalsOpts, "mcpt_normals_opts", 24), (pkg.NormalsInfo, "mcpt_normals_info", 56)):
-        c, py = _layout(cls, name, tmp_path)
-        assert c == py and c[0] == size
+        c, py, modes = K.c_layout(cls, name, tmp_path, macros=("MCPT_NORMALS_OFF", "MCPT_NORMALS_AREA"))
+        assert c == py and c[0] == size and modes == [0, 1]
 
 
 def test_mask_from_faces(pkg):
@@ -352,9 +312,6 @@ def _fan_moved(pkg):
     return v
 
 
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
 def _host_check_cases(pkg):
     """(face, n_normal, mask, vertex, normal) for normals_host_check: the fixtures, the fan, a masked and a moved reference pose, a random soup
     with repeated corners, zero and NaN normals, and the empty cases."""
@@ -373,17 +330,13 @@ def _host_check_cases(pkg):
     return cases
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@K.needs_hipcc
 @pytest.mark.parametrize("sanitized", [False, True])
 def test_host_lists_are_the_restatement_bit_for_bit(pkg, tmp_path, sanitized):
     """The host half of the feature -- nr_per_record of csrc/normals.hip -- built into the stand-alone program tests/normals_host_check.cpp (no
     device is touched) against tests/normals_ref.py: the same offsets, entries and flips.  `sanitized`: the same program under the host's
     address and undefined-behaviour sanitizers, which must stay silent."""
-    csrc = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc")
-    exe = str(tmp_path / "normals_host_check")
-    extra = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-g"] if sanitized else []
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-I" + csrc] + extra +
-                          [os.path.join(csrc, "normals.hip"), os.path.join(ROOT, "tests", "normals_host_check.cpp"), "-o", exe])
+    exe = K.build_host_check("normals_host_check", ["normals.hip"], tmp_path, sanitized)
     cases = _host_check_cases(pkg)
     with open(str(tmp_path / "in.bin"), "wb") as f:
         f.write(np.uint32(len(cases)).tobytes())
@@ -393,9 +346,7 @@ def test_host_lists_are_the_restatement_bit_for_bit(pkg, tmp_path, sanitized):
             if mask is not None:
                 f.write(np.ascontiguousarray(mask, np.uint8).tobytes())
             f.write(np.ascontiguousarray(v, np.float64).tobytes()); f.write(np.ascontiguousarray(n, np.float64).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")                   # (the HIP runtime's start-up allocations are not this program's)
-    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, env=env)
-    assert p.returncode == 0 and "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-3000:]
+    K.run_host_check(exe, tmp_path, sanitized)
     raw = open(str(tmp_path / "out.bin"), "rb").read()
     at = 0
     for k, (face, nn, mask, v, n) in enumerate(cases):
@@ -408,55 +359,9 @@ def test_host_lists_are_the_restatement_bit_for_bit(pkg, tmp_path, sanitized):
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU helpers
-@functools.lru_cache(maxsize=None)
-def _rays(pkg):
-    """Camera rays of the Cornell camera (one per pixel, fixed targets) and random rays through the room: computed once, never changed."""
-    ex = np.array(_scene(pkg, "big").camera.eye); rng = np.random.default_rng(3)
-    t = rng.uniform(0.0, 1.0, (W * H, 3)); t[:, 2] = 0.0                     # towards points of the back wall's plane: all through the room
-    d = t - ex; d /= np.linalg.norm(d, axis=1, keepdims=True)
-    o = rng.uniform(0.01, 0.99, (3000, 3)); q = rng.uniform(0.01, 0.99, (3000, 3))
-    e = q - o; e /= np.linalg.norm(e, axis=1, keepdims=True)
-    return np.concatenate([np.broadcast_to(ex, d.shape), o]), np.concatenate([d, e])
-
-
-def _state(pkg, r, film=True):
-    """Everything the downstream comparisons look at, of one context."""
-    o, d = _rays(pkg)
-    r.validate_trees()
-    t, f, u, v = r.probe_trace4(o, d)
-    hit = f >= 0
-    assert hit.mean() > 0.9
-    shade = r.probe_hit_shade(f[hit], u[hit], v[hit], d[hit])
-    lf, lrec, lpos = r.probe_lights()
-    out = {"t": t, "face": f, "u": u, "v": v, "shade": shade, "light_face": lf, "light_rec": lrec, "light_pos": lpos}
-    if film:
-        out["film"] = render_film(r, 4, 5)
-    return out
-
-
-def _assert_same(a, b):
-    for k in a:
-        assert np.array_equal(bits(a[k]), bits(b[k])), k
-
-
-def _assert_records(got, want, what):
-    """The device's array against the restatement's, bit for bit; a failure names the first record."""
-    bad = np.flatnonzero((bits(got) != bits(np.ascontiguousarray(want, np.float64))).any(axis=1))
-    assert bad.size == 0, "%s %d of %d differing: device %r, restatement %r" % (what, bad[0], bad.size, got[bad[0]].tolist(), np.asarray(want)[bad[0]].tolist())
-
-
-def _assert_arrays(r, v, n):
-    gv, gn = r.vertices()
-    _assert_records(gv, v, "vertex"); _assert_records(gn, n, "normal")
-
-
-FLAGS = lambda pkg: pkg.FLAG_DYNAMIC | pkg.FLAG_DETERMINISTIC
-
-
 def _pair(pkg, which="big", extra=0):
     """The context under test and its oracle (which never has the feature)."""
-    s = _scene(pkg, which)
-    return pkg.Renderer(s, max_depth=8, flags=FLAGS(pkg) | extra), pkg.Renderer(s, max_depth=8, flags=FLAGS(pkg) | extra)
+    return K.pair(pkg, extra=extra, max_depth=8, scene=_scene(pkg, which))
 
 
 def _lists(pkg, which, mask, ref=None):
@@ -472,11 +377,11 @@ def _check_route(pkg, R, O, which, route, mask, film=True, lists=None):
     off, entry = _lists(pkg, which, mask) if lists is None else lists
     n = N.apply(off, entry, v, n_route)
     O.update_vertices(v, n)
-    _assert_arrays(R, v, n)
+    K.assert_arrays(R, v, n)
     keep = np.diff(off.astype(np.int64)) == 0
     assert np.array_equal(bits(n[keep]), bits(np.ascontiguousarray(n_route)[keep])) and not np.array_equal(n[~keep], np.asarray(n_route)[~keep])
-    a, b = _state(pkg, R, film), _state(pkg, O, film)
-    _assert_same(a, b)
+    a, b = K.state(pkg, R, film), K.state(pkg, O, film)
+    K.assert_same(a, b)
     return a, v, n
 
 
@@ -491,7 +396,7 @@ def test_every_route_is_followed_by_the_pass(pkg, route, which_mask):
     R, O = _pair(pkg)
     _prepare(pkg, R, "big", route)
     R.set_auto_normals(mask)
-    _assert_arrays(R, s.vertex, s.normal)                                    # setting it moves nothing
+    K.assert_arrays(R, s.vertex, s.normal)                                   # setting it moves nothing
     rest = R.probe_lights()
     moved, v, n = _check_route(pkg, R, O, "big", route, mask)
     assert not np.array_equal(rest[2], moved["light_pos"])                   # the lamp moved (every route moves it)
@@ -517,8 +422,8 @@ def test_small_scene_and_fan_with_both_builders(pkg, which, gpu_tree):
     v = _moved(pkg, s)[0] if which == "small" else _fan_moved(pkg)
     n = N.apply(off, entry, v, s.normal)
     R.update_vertices(v, None); O.update_vertices(v, n)
-    _assert_arrays(R, v, n)
-    _assert_same(_state(pkg, R), _state(pkg, O))
+    K.assert_arrays(R, v, n)
+    K.assert_same(K.state(pkg, R), K.state(pkg, O))
     ni = R.normals_info()
     count = np.diff(off.astype(np.int64))
     assert (ni.records, ni.entries, ni.max_valence) == (int((count > 0).sum()), entry.shape[0], int(count.max()))
@@ -533,7 +438,7 @@ def test_small_scene_and_fan_with_both_builders(pkg, which, gpu_tree):
 def test_update_normals_alone_and_sequences(pkg):
     s = _scene(pkg); nn = s.normal.shape[0]
     R, O = _pair(pkg)
-    plain = _state(pkg, R, film=False)
+    plain = K.state(pkg, R, film=False)
     base = R.info().device_bytes
     R.set_auto_normals()
     off, entry = _lists(pkg, "big", None)
@@ -541,23 +446,23 @@ def test_update_normals_alone_and_sequences(pkg):
     # update_normals on a context at rest: the restated normals of the rest pose, no vertex moves; twice = once
     n0 = N.apply(off, entry, s.vertex, s.normal)
     R.update_normals(); O.update_vertices(s.vertex, n0)
-    _assert_arrays(R, s.vertex, n0)
-    once = _state(pkg, R)
-    _assert_same(once, _state(pkg, O))
+    K.assert_arrays(R, s.vertex, n0)
+    once = K.state(pkg, R)
+    K.assert_same(once, K.state(pkg, O))
     assert not np.array_equal(bits(once["shade"]), bits(plain["shade"]))     # (the stored normals are rounded to 9 digits: the pass differs in the last bits)
     R.update_normals()
-    _assert_arrays(R, s.vertex, n0)
-    _assert_same(_state(pkg, R), once)
+    K.assert_arrays(R, s.vertex, n0)
+    K.assert_same(K.state(pkg, R), once)
     assert (R.update_info().updates, R.normals_info().updates) == (2, 2)
     # M1 then M2 = M2 alone (the pass reads the current vertices only)
     v1, _ = _moved(pkg, s, step=2); v2, _ = _moved(pkg, s)
     R.update_vertices(v1, None)
-    _assert_arrays(R, v1, N.apply(off, entry, v1, n0))
+    K.assert_arrays(R, v1, N.apply(off, entry, v1, n0))
     R.update_vertices(v2, None)
     n2 = N.apply(off, entry, v2, n0)
     O.update_vertices(v2, n2)
-    _assert_arrays(R, v2, n2)
-    _assert_same(_state(pkg, R), _state(pkg, O))
+    K.assert_arrays(R, v2, n2)
+    K.assert_same(K.state(pkg, R), K.state(pkg, O))
     # a second set_auto_normals takes its reference pose from the MOVED scene, and may change the mask
     mask = _mask(pkg, s, "sphere")
     R.set_auto_normals(mask)
@@ -572,8 +477,8 @@ def test_update_normals_alone_and_sequences(pkg):
     v, n = _moved(pkg, s, step=2)
     for r in (R, O):
         r.update_vertices(v, n); r.update_vertices(v2, None)
-    _assert_arrays(R, v2, n)
-    _assert_same(_state(pkg, R), _state(pkg, O))
+    K.assert_arrays(R, v2, n)
+    K.assert_same(K.state(pkg, R), K.state(pkg, O))
     assert R.normals_info().updates == passes and R.info().device_bytes == O.info().device_bytes
     with pytest.raises(pkg.McptError) as e:
         R.update_normals()
@@ -603,7 +508,7 @@ def test_update_between_renders_without_a_sync(pkg, which):
     O.render(4, seed=9, first_sample=0); O.sync(); O.update_vertices(v1, n1); O.sync(); O.render(4, seed=9, first_sample=4); O.sync()
     O.update_vertices(v2, n2); O.sync(); O.render(2, seed=9, first_sample=8); O.sync()
     assert np.array_equal(bits(got), bits(O.read_accum())) and np.all(got[..., 3] == 10)
-    _assert_arrays(R, v2, n2)
+    K.assert_arrays(R, v2, n2)
     if which == "side":
         R.set_stream(0)
     R.close(); O.close()
@@ -629,8 +534,8 @@ def test_reprojection_follows_the_recomputed_normals(pkg, with_camera, route):
     assert (ia.reprojections, ia.pixels_reused) == (ib.reprojections, ib.pixels_reused) == (1, ib.pixels_reused) and ia.pixels_reused > 0.5 * W * H
     assert np.array_equal(bits(R.features()), bits(O.features()))          # the context holds the new scene's features
     assert R.update_info().updates == 1 and R.normals_info().updates == 1
-    _assert_arrays(R, v, n)
-    _assert_same(_state(pkg, R, film=False), _state(pkg, O, film=False))
+    K.assert_arrays(R, v, n)
+    K.assert_same(K.state(pkg, R, film=False), K.state(pkg, O, film=False))
     R.close(); O.close()
 
 
@@ -655,13 +560,13 @@ def test_clone_rebuild_and_bookkeeping(pkg):
     bare.close()
     ci = clone.normals_info()
     assert (ci.mode, ci.records, ci.entries, ci.max_valence, ci.updates) == (pkg.NORMALS_AREA, int(mask.sum()), entry.shape[0], 6, 0)
-    _assert_arrays(clone, v1, n1)                                            # the clone is the moved scene ...
+    K.assert_arrays(clone, v1, n1)                                           # the clone is the moved scene ...
     v2, _ = _moved(pkg, s, step=2)
     n2 = N.apply(off, entry, v2, n1)
     clone.update_vertices(v2, None); O.update_vertices(v2, n2)               # ... with the lists (taken at the ORIGINAL reference pose)
-    _assert_arrays(clone, v2, n2)
-    _assert_same(_state(pkg, clone), _state(pkg, O))
-    _assert_arrays(R, v1, n1)                                                # the source did not move with its clone
+    K.assert_arrays(clone, v2, n2)
+    K.assert_same(K.state(pkg, clone), K.state(pkg, O))
+    K.assert_arrays(R, v1, n1)                                               # the source did not move with its clone
     # a rebuild with either builder keeps the lists: they follow the description's face order, not the leaf order
     for k, builder in enumerate((pkg.REBUILD_HOST, pkg.REBUILD_DEVICE)):
         R.rebuild(builder); O.rebuild(builder)
@@ -669,8 +574,8 @@ def test_clone_rebuild_and_bookkeeping(pkg):
         v = v2 if k == 0 else v1
         n = N.apply(off, entry, v, R.vertices()[1])
         R.update_vertices(v, None); O.update_vertices(v, n)
-        _assert_arrays(R, v, n)
-        _assert_same(_state(pkg, R, film=k == 1), _state(pkg, O, film=k == 1))
+        K.assert_arrays(R, v, n)
+        K.assert_same(K.state(pkg, R, film=k == 1), K.state(pkg, O, film=k == 1))
     assert R.info().device_bytes == O.info().device_bytes + 4 * (nn + 1) + 16 * entry.shape[0]
     assert (R.normals_info().updates, R.update_info().updates, clone.normals_info().updates) == (3, 3, 1)
     clone.close(); R.close(); O.close()
@@ -687,7 +592,7 @@ def test_normals_refusals(pkg):
     assert plain.normals_info().mode == pkg.NORMALS_OFF                      # the info call works on every context
     plain.close()
     R = pkg.Renderer(s, max_depth=8, flags=FLAGS(pkg))
-    o, d = _rays(pkg)
+    o, d = K.rays(pkg)
     film = render_film(R, 4, 5); trace = R.probe_trace4(o, d); arrays = R.vertices(); bytes0 = [R.info().device_bytes]
     expect = {"mode": 0, "records": 0, "entries": 0, "max_valence": 0}
 
@@ -824,7 +729,7 @@ def test_auto_normals_update_is_not_slower_on_the_device_than_the_upload_it_repl
         R.set_auto_normals()
         R.update_vertices(v, None); auto.append(R.update_info().last_update_ms)
         if i == 0:                                                           # (the lists were taken at the rest pose: the restatement's)
-            _assert_arrays(R, v, n)
+            K.assert_arrays(R, v, n)
         R.set_auto_normals(mode=pkg.NORMALS_OFF)
         R.update_vertices(v, n); up.append(R.update_info().last_update_ms)
     R.validate_trees()

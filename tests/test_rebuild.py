@@ -16,7 +16,7 @@ import time
 import numpy as np
 import pytest
 
-from tests import kit, ploc_ref, transform_ref as T
+from tests import deform_kit, kit, ploc_ref, transform_ref as T
 from tests.kit import ROOT, bits, render_film
 from tests.test_scene_update import _compare_traces, _rays, _same_render
 
@@ -44,20 +44,10 @@ def test_null_context_is_an_invalid_argument_for_the_rebuild_calls(pkg):
 
 def test_rebuild_structs_have_the_headers_layout(pkg, tmp_path):
     """sizeof and every offsetof of mcpt_rebuild_opts / mcpt_rebuild_info as a C compiler sees include/mcpt.h, against the ctypes classes."""
-    structs = {"RebuildOpts": "mcpt_rebuild_opts", "RebuildInfo": "mcpt_rebuild_info"}
-    lines = []
-    for name, struct in structs.items():
-        fields = [f[0] for f in getattr(pkg, name)._fields_]
-        lines.append('  printf("%s %%zu%s\\n", sizeof(%s)%s);' % (name, " %zu" * len(fields), struct, "".join(", offsetof(%s, %s)" % (struct, f) for f in fields)))
-    lines.append('  printf("consts %u %u %u\\n", MCPT_REBUILD_SAME, MCPT_REBUILD_HOST, MCPT_REBUILD_DEVICE);')
-    src = tmp_path / "t.c"; exe = str(tmp_path / "t")
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mcpt.h"\nint main(void) {\n%s\n  return 0; }\n' % "\n".join(lines))
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    out = {l.split()[0]: [int(x) for x in l.split()[1:]] for l in subprocess.check_output([exe]).decode().splitlines()}
-    for name in structs:
-        cls = getattr(pkg, name)
-        assert out[name] == [C.sizeof(cls)] + [getattr(cls, f[0]).offset for f in cls._fields_], name
-    assert out["consts"] == [pkg.REBUILD_SAME, pkg.REBUILD_HOST, pkg.REBUILD_DEVICE]
+    for cls, name in ((pkg.RebuildOpts, "mcpt_rebuild_opts"), (pkg.RebuildInfo, "mcpt_rebuild_info")):
+        c, py, consts = deform_kit.c_layout(cls, name, tmp_path, macros=("MCPT_REBUILD_SAME", "MCPT_REBUILD_HOST", "MCPT_REBUILD_DEVICE"))
+        assert c == py, name
+        assert consts == [pkg.REBUILD_SAME, pkg.REBUILD_HOST, pkg.REBUILD_DEVICE]
 
 
 def test_rebuild_plans_are_inverse_permutations_and_refuse_anything_else(tmp_path):
@@ -145,12 +135,6 @@ def _probes(pkg, r, scene, binary=True):
     return out
 
 
-def _assert_same(a, b):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
-
-
 def _work(r):
     c = r.counters()
     return c.box_tests + c.tri_tests
@@ -191,7 +175,7 @@ def test_a_rebuilt_context_is_the_fresh_context(pkg, builder):
     assert _tree_info(R) == _tree_info(F)
     assert R.info().traversal_bytes == F.info().traversal_bytes and list(R.info().centre) == list(F.info().centre)
     assert refit.info().wide_tree_hash == refit_hash != R.info().wide_tree_hash
-    _assert_same(_probes(pkg, R, moved), _probes(pkg, F, moved))
+    deform_kit.assert_same(_probes(pkg, R, moved), _probes(pkg, F, moved))
     # ---- the film was kept and goes on
     assert np.array_equal(bits(R.read_accum()), bits(film0))
     R.render(8, seed=5, first_sample=8)
@@ -229,7 +213,7 @@ def test_rebuild_right_after_creation_is_the_identity(pkg, builder):
     R.validate_trees()
     assert _tree_info(R) == tree and R.info().device_bytes == info.device_bytes and R.info().traversal_bytes == info.traversal_bytes
     assert (R.info().bvh_build_ms, R.info().upload_ms) == (info.bvh_build_ms, info.upload_ms)
-    _assert_same(_probes(pkg, R, scene), before)
+    deform_kit.assert_same(_probes(pkg, R, scene), before)
     assert np.array_equal(bits(R.read_accum()), bits(film))
     assert np.array_equal(bits(render_film(R, 8, 5)), bits(film))
     ri = R.rebuild_info()

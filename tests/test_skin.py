@@ -9,76 +9,26 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests import kit, skin_ref as S, transform_ref as T
-from tests.kit import ROOT, bits, render_film
+from tests import deform_kit as K, kit, skin_ref as S, transform_ref as T
+from tests.deform_kit import CENTRE, FLAGS, H, INVALID, LAMP, M_HIGH, M_LAMP, M_LOW, N_BONES, SPHERE, UNSUPPORTED, W, clean
+from tests.kit import bits, render_film
 
 NEW_SYMBOLS = ["mcpt_set_vertex_skin", "mcpt_update_skin", "mcpt_update_skin_reproject", "mcpt_get_skin_info"]
-INVALID, UNSUPPORTED = 1, 6
-W, H = 64, 64
-SPHERE, LAMP = 4, 3                                                          # materials of S-cornell: the glossy sphere, the ceiling light
-CENTRE = np.array([0.5, 0.3, 0.5])                                           # of the sphere (radius 0.3: it stands on the floor)
 DYADIC = (0.5, 0.25, 0.125, 0.125)                                           # every partial sum and every product with 0 or 1 is exact
-
-
-def clean(m):
-    """The matrices without negative zeros (-0.0 + 0.0 = +0.0; everything else is unchanged)."""
-    return np.ascontiguousarray(m, np.float64) + 0.0
-
-
-M_LOW = clean(T.about(T.rotation((0, 0, 1), -6.0), CENTRE, (0.0, 0.06, 0.0)))
-M_HIGH = clean(T.about(T.rotation((0, 0, 1), 25.0) @ np.diag([0.9, 0.95, 0.9]), (0.5, 0.1, 0.5), (0.03, 0.08, -0.04)))
 M_THIRD = clean(T.about(T.rotation((1, 2, 3), 30.0) @ np.diag([0.8, 0.6, 0.9]), CENTRE, (0.1, 0.2, -0.05)))
 M_OTHER = clean(T.about(T.rotation((0, 1, 0), -75.0) @ np.diag([0.7, 1.1, 0.7]), CENTRE, (-0.08, 0.1, 0.1)))
-M_LAMP = clean(T.about(T.rotation((0, 1, 0), 25.0), (0.5, 0.999, 0.5), (0.1, -0.2, 0.05)))
 M_UNUSED = clean(T.about(np.diag([1e6, 2.0, 3.0]), (5, 5, 5), (1e17, 0, 0)))     # a bone without members: validated against R_b = 0, never read
-N_BONES = 5                                                                  # 0 the walls, 1 and 2 the sphere's lower and upper bone, 3 nobody, 4 the lamp
-
-
-@functools.lru_cache(maxsize=None)
-def _scene(pkg):
-    return pkg.scenes.cornell_box(W, H, sphere_lon=48, sphere_lat=24)         # 1 249 vertices and normals: five 256-blocks with a tail
-
-
-@functools.lru_cache(maxsize=None)
-def _parts(pkg):
-    """(sphere, lamp) as boolean masks over the vertices."""
-    s = _scene(pkg)
-    out = []
-    for mtl in (SPHERE, LAMP):
-        mask = np.zeros(s.vertex.shape[0], bool); mask[np.unique(s.face[s.face[:, 0, 3] == mtl][:, :, 0])] = True
-        out.append(mask)
-    return out
-
-
-def _with_normals(pkg, vb, vw):
-    nb, nw = pkg.skin_normals_from_faces(_scene(pkg), vb, vw)
-    return vb, vw, nb, nw
-
-
-@functools.lru_cache(maxsize=None)
-def _bend(pkg):
-    """The five-bone skin: walls on bone 0, lamp on bone 4, every sphere vertex blended between bones 1 and 2 by its height; bone 3 has no
-    member.  (vertex ids, vertex weights, normal ids, normal weights.)"""
-    s = _scene(pkg); sphere, lamp = _parts(pkg)
-    vb, vw = S.single(np.where(lamp, 4, 0))
-    y = s.vertex[sphere, 1]; w = (y - y.min()) / (y.max() - y.min())
-    assert w.min() == 0.0 and w.max() == 1.0
-    vb[sphere, 0] = 1; vb[sphere, 1] = 2; vw[sphere, 0] = 1.0 - w; vw[sphere, 1] = w
-    return _with_normals(pkg, vb, vw)
 
 
 @functools.lru_cache(maxsize=None)
 def _four(pkg):
     """Every sphere vertex with four random weights normalised in fp64 over bones 1 .. 3, a third of the slots exactly 0 with a random id of
     ANY bone in them; walls on bone 0, lamp on bone 4."""
-    sphere, lamp = _parts(pkg); n = int(sphere.sum())
+    sphere, lamp = K.parts(pkg); n = int(sphere.sum())
     rng = np.random.default_rng(23)
     vb, vw = S.single(np.where(lamp, 4, 0))
     r = rng.uniform(0.05, 1.0, (n, 4)); ids = rng.integers(1, 4, (n, 4))
@@ -88,21 +38,17 @@ def _four(pkg):
     w = r / r.sum(1, keepdims=True)
     assert (w == 0.0).sum() == zero.sum() > n and np.abs(S.weight_sums(w) - 1.0).max() <= 4 * np.finfo(np.float64).eps
     vb[sphere] = ids; vw[sphere] = w
-    return _with_normals(pkg, vb, vw)
+    return (vb, vw) + tuple(pkg.skin_normals_from_faces(K.scene(pkg), vb, vw))
 
 
 def _mats(low=None, high=None, lamp=None, third=None):
-    m = T.identity(N_BONES)
-    m[3] = M_UNUSED if third is None else third
-    if low is not None: m[1] = low
-    if high is not None: m[2] = high
-    if lamp is not None: m[4] = lamp
-    return m
+    """deform_kit.mats with the far-away bone 3 this suite always had there."""
+    return K.mats(low, high, lamp, M_UNUSED if third is None else third)
 
 
 def _ref(pkg, matrices, skin=None, rest=None):
     """The arrays the bones give, by the restatement."""
-    s = _scene(pkg); vb, vw, nb, nw = _bend(pkg) if skin is None else skin
+    s = K.scene(pkg); vb, vw, nb, nw = K.bend(pkg) if skin is None else skin
     rv, rn = (s.vertex, s.normal) if rest is None else rest
     return S.skin_vertices(rv, vb, vw, matrices), S.skin_normals(rn, nb, nw, matrices)
 
@@ -129,15 +75,9 @@ def test_null_context_is_an_invalid_argument_for_the_skin_calls(pkg):
 
 def test_skin_info_has_the_headers_layout(pkg, tmp_path):
     """sizeof and every offsetof of mcpt_skin_info as a C compiler sees include/mcpt.h, against the ctypes class; MCPT_SKIN_INFLUENCES."""
-    cls = pkg.SkinInfo
-    fields = [f[0] for f in cls._fields_]
-    line = '  printf("%%zu%s\\n", sizeof(mcpt_skin_info)%s);' % (" %zu" * len(fields), "".join(", offsetof(mcpt_skin_info, %s)" % f for f in fields))
-    src = tmp_path / "t.c"; exe = str(tmp_path / "t")
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mcpt.h"\nint main(void) {\n%s\n  printf("%%d %%u\\n", MCPT_SKIN_INFLUENCES, MCPT_ABI_VERSION);\n  return 0; }\n' % line)
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    out = [[int(x) for x in l.split()] for l in subprocess.check_output([exe]).decode().splitlines()]
-    assert out[0] == [C.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
-    assert out[1] == [pkg.SKIN_INFLUENCES, 4]
+    c, py, macros = K.c_layout(pkg.SkinInfo, "mcpt_skin_info", tmp_path, macros=("MCPT_SKIN_INFLUENCES",))
+    assert c == py
+    assert macros == [pkg.SKIN_INFLUENCES]
 
 
 def test_skin_normals_from_faces(pkg):
@@ -172,14 +112,14 @@ def test_skin_normals_from_faces(pkg):
     with pytest.raises(ValueError):
         pkg.skin_normals_from_faces(shared, same_b, one_bit)
     # S-cornell: every normal is paired with one vertex, so the bend's normals carry their vertices' records
-    s = _scene(pkg); vb, vw, nb, nw = _bend(pkg)
+    s = K.scene(pkg); vb, vw, nb, nw = K.bend(pkg)
     assert nb.shape == (s.normal.shape[0], 4)
     assert np.array_equal(nb[s.face[:, :, 1]], vb[s.face[:, :, 0]]) and np.array_equal(bits(nw[s.face[:, :, 1]]), bits(vw[s.face[:, :, 0]]))
-    assert _parts(pkg)[0].sum() > 1000 and _parts(pkg)[1].sum() == 4 and s.vertex.shape[0] == s.normal.shape[0] == 1249
+    assert K.parts(pkg)[0].sum() > 1000 and K.parts(pkg)[1].sum() == 4 and s.vertex.shape[0] == s.normal.shape[0] == 1249
 
 
 def test_restatement_identity_and_single_influence(pkg):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
     rng = np.random.default_rng(4)
     # identity bones with dyadic weights: the blend is the identity exactly, whatever ids the slots name
     ids_v = rng.integers(0, 3, (nv, 4)); ids_n = rng.integers(0, 3, (nn, 4))
@@ -192,7 +132,7 @@ def test_restatement_identity_and_single_influence(pkg):
     again = S.skin_normals(unit, ids_n, dy_n, T.identity(3))
     assert np.array_equal(bits(again.astype(np.float32)), bits(unit.astype(np.float32)))
     # one influence of weight 1 (the other slots: weight 0 on bone 0) gives transform_ref's arrays bit for bit for matrices without -0.0
-    sphere, lamp = _parts(pkg)
+    sphere, lamp = K.parts(pkg)
     group = np.where(sphere, 1, np.where(lamp, 2, 0))
     m = np.stack([T.identity(1)[0], M_THIRD, M_LAMP])
     assert not np.signbit(m[m == 0.0]).any()
@@ -211,13 +151,13 @@ def test_restatement_identity_and_single_influence(pkg):
 
 def test_restatement_blends_matrices_the_way_positions_blend(pkg):
     """Linear-blend skinning: the blended matrix applied to a point is the blend of the transformed points, to rounding."""
-    s = _scene(pkg); vb, vw, nb, nw = _four(pkg)
+    s = K.scene(pkg); vb, vw, nb, nw = _four(pkg)
     m = _mats(low=M_LOW, high=M_HIGH, third=M_THIRD, lamp=M_LAMP)
     got = S.skin_vertices(s.vertex, vb, vw, m)
     each = np.stack([T.transform_vertices(s.vertex, vb[:, k], m) for k in range(4)], 1)          # (n, 4, 3)
     want = (vw[:, :, None] * each).sum(1)
     assert np.abs(got - want).max() <= 1e-15
-    assert not np.array_equal(got, s.vertex) and got[_parts(pkg)[0]].min() > 0.01 and got[_parts(pkg)[0]].max() < 0.99
+    assert not np.array_equal(got, s.vertex) and got[K.parts(pkg)[0]].min() > 0.01 and got[K.parts(pkg)[0]].max() < 0.99
     # normals come out unit length wherever the blend is regular
     n = S.skin_normals(s.normal, nb, nw, m)
     assert np.abs(np.sqrt((n * n).sum(1)) - 1.0).max() <= 4 * np.finfo(np.float64).eps
@@ -230,7 +170,7 @@ def test_restatement_blends_matrices_the_way_positions_blend(pkg):
 
 
 def test_restatement_refusals(pkg):
-    s = _scene(pkg); vb, vw, nb, nw = _bend(pkg)
+    s = K.scene(pkg); vb, vw, nb, nw = K.bend(pkg)
     assert S.accepts_skin(vb, vw, N_BONES) and S.accepts_skin(nb, nw, N_BONES) and S.accepts_skin(*_four(pkg)[:2], N_BONES)
     # the weight sum: 1e-6 is the limit, fp32-normalised weights pass
     for scale, ok in ((1.0 + 0.9e-6, True), (1.0 - 0.9e-6, True), (1.0 + 1.2e-6, False), (1.0 - 1.2e-6, False)):
@@ -246,7 +186,7 @@ def test_restatement_refusals(pkg):
     b[7, 3] = N_BONES
     assert not S.accepts_skin(b, vw, N_BONES) and S.accepts_skin(b, vw, N_BONES + 1)
     # R_b: only vertices that a face uses and that give the bone a weight > 0
-    used = T.used_vertices(s); sphere, lamp = _parts(pkg)
+    used = T.used_vertices(s); sphere, lamp = K.parts(pkg)
     radius = S.bone_radius(s.vertex, vb, vw, used, N_BONES)
     far = np.abs(s.vertex).max(1)
     lower = sphere & (vw[:, 0] > 0.0); upper = sphere & (vw[:, 1] > 0.0)
@@ -268,18 +208,12 @@ def test_restatement_refusals(pkg):
     assert not S.accepts(far_a, radius) and S.accepts(far_a, np.zeros(N_BONES))
 
 
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@K.needs_hipcc
 def test_host_determinant_and_reach_are_the_restatement_bit_for_bit(pkg, tmp_path):
     """The host half of the feature -- sk_bone_det and sk_row_reach of csrc/skin.hip, what mcpt_update_skin validates with -- built into the
     stand-alone program tests/skin_host_check.cpp (no device is touched) against tests/skin_ref.py: the same bits, also where a last bit
     decides (a determinant that cancels to exactly 0, a reach at the limit that the slack factor puts over it)."""
-    csrc = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc")
-    exe = str(tmp_path / "skin_host_check")
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-I" + csrc, os.path.join(csrc, "skin.hip"),
-                           os.path.join(csrc, "transform.hip"), os.path.join(ROOT, "tests", "skin_host_check.cpp"), "-o", exe])
+    exe = K.build_host_check("skin_host_check", ["skin.hip", "transform.hip"], tmp_path)
     rng = np.random.default_rng(5)
     m = rng.normal(0.0, 1.0, (400, 3, 4)) * 10.0 ** rng.integers(-8, 9, (400, 1, 1))
     m[:40, 2, :3] = m[:40, 0, :3] * 3.0 + m[:40, 1, :3]                      # nearly singular: heavy cancellation in the determinant
@@ -288,7 +222,7 @@ def test_host_determinant_and_reach_are_the_restatement_bit_for_bit(pkg, tmp_pat
                         np.array([[1, 0, 0, 1e18], [0, 1, 0, 0], [0, 0, 1, 0.0]]), np.array([[1, 0, 0, 1e18 / (1.0 + 2.0 ** -15)], [0, 1, 0, 0], [0, 0, 1, 0.0]])])
     m = np.concatenate([special, m]); radius = np.concatenate([np.full(len(special), 0.8), rng.uniform(0.0, 2.0, 400)])
     np.concatenate([m.reshape(-1, 12), radius[:, None]], 1).tofile(str(tmp_path / "in.bin"))
-    subprocess.check_call([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")])
+    K.run_host_check(exe, tmp_path)
     got = np.fromfile(str(tmp_path / "out.bin")).reshape(-1, 4)
     with np.errstate(all="ignore"):
         want = np.concatenate([T.determinants(m)[:, None], S.reach(m, radius)], 1)
@@ -297,64 +231,17 @@ def test_host_determinant_and_reach_are_the_restatement_bit_for_bit(pkg, tmp_pat
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU helpers
-@functools.lru_cache(maxsize=None)
-def _rays(pkg):
-    """The camera rays of S-cornell (one per pixel, fixed xi) and random rays through its box: computed once, never changed."""
-    s = _scene(pkg)
-    ex = np.array(s.camera.eye); rng = np.random.default_rng(3)
-    t = rng.uniform(0.0, 1.0, (W * H, 3)); t[:, 2] = 0.0                     # towards points of the back wall's plane: all through the room
-    d = t - ex; d /= np.linalg.norm(d, axis=1, keepdims=True)
-    o = rng.uniform(0.01, 0.99, (3000, 3)); q = rng.uniform(0.01, 0.99, (3000, 3))
-    e = q - o; e /= np.linalg.norm(e, axis=1, keepdims=True)
-    return np.concatenate([np.broadcast_to(ex, d.shape), o]), np.concatenate([d, e])
-
-
-def _state(pkg, r, film=True):
-    """Everything the comparisons look at, of one context."""
-    o, d = _rays(pkg)
-    r.validate_trees()
-    t, f, u, v = r.probe_trace4(o, d)
-    hit = f >= 0
-    assert hit.mean() > 0.9
-    shade = r.probe_hit_shade(f[hit], u[hit], v[hit], d[hit])
-    lf, lrec, lpos = r.probe_lights()
-    out = {"t": t, "face": f, "u": u, "v": v, "shade": shade, "light_face": lf, "light_rec": lrec, "light_pos": lpos}
-    if film:
-        out["film"] = render_film(r, 4, 5)
-    return out
-
-
-def _assert_same(a, b):
-    for k in a:
-        assert np.array_equal(bits(a[k]), bits(b[k])), k
-
-
-@functools.lru_cache(maxsize=None)
-def _unit_rest(pkg):
-    """S-cornell's vertices and its normals NORMALISED by the restatement (§16's _unit_rest reasoning: the file's 9-digit normals are unit length
-    within ~1e-9 only, and v / |v| moves a few of them to another fp32 number; normalised once they are a fixed point of that step in fp32 --
-    asserted in test_restatement_identity_and_single_influence -- so a context put on this pose first comes back to it bit for bit)."""
-    s = _scene(pkg)
-    return s.vertex, T.transform_normals(s.normal, np.zeros(s.normal.shape[0], int), T.identity(1))
-
-
-FLAGS = lambda pkg: pkg.FLAG_DYNAMIC | pkg.FLAG_DETERMINISTIC
-
-
 def _pair(pkg, extra=0, skin="bend"):
     """The context under test (with the five-bone bend, or `skin`, or none) and its oracle."""
-    s = _scene(pkg)
-    R = pkg.Renderer(s, max_depth=6, flags=FLAGS(pkg) | extra); O = pkg.Renderer(s, max_depth=6, flags=FLAGS(pkg) | extra)
-    if skin is not None:
-        R.set_vertex_skin(*(_bend(pkg) if skin == "bend" else skin), N_BONES)
-    return R, O
+    setup = None if skin is None else lambda R: R.set_vertex_skin(*(K.bend(pkg) if skin == "bend" else skin), N_BONES)
+    return K.pair(pkg, setup, extra=extra, max_depth=6)
 
 
 def _check_against_oracle(pkg, R, O, matrices, skin=None, rest=None):
     v, n = _ref(pkg, matrices, skin, rest)
     R.update_skin(matrices); O.update_vertices(v, n)
-    a, b = _state(pkg, R), _state(pkg, O)
-    _assert_same(a, b)
+    a, b = K.state(pkg, R), K.state(pkg, O)
+    K.assert_same(a, b)
     return a
 
 
@@ -368,15 +255,15 @@ BEND2 = _mats(low=M_OTHER, high=M_THIRD)
 def test_bend_of_the_sphere_with_a_moved_lamp(pkg, gpu_tree):
     R, O = _pair(pkg, extra=pkg.FLAG_GPU_BVH_BUILD if gpu_tree else 0)
     v, _ = _ref(pkg, BEND)
-    sphere, lamp = _parts(pkg)
-    assert v[sphere].min() > 0.01 and v[sphere].max() < 0.99 and not np.array_equal(v[sphere], _scene(pkg).vertex[sphere])   # bent, inside the room
-    assert np.array_equal(v[~sphere & ~lamp], _scene(pkg).vertex[~sphere & ~lamp])                                         # the walls stay
-    rest = _state(pkg, R, film=False)
+    sphere, lamp = K.parts(pkg)
+    assert v[sphere].min() > 0.01 and v[sphere].max() < 0.99 and not np.array_equal(v[sphere], K.scene(pkg).vertex[sphere])   # bent, inside the room
+    assert np.array_equal(v[~sphere & ~lamp], K.scene(pkg).vertex[~sphere & ~lamp])                                        # the walls stay
+    rest = K.state(pkg, R, film=False)
     before = R.probe_lights()
     moved = _check_against_oracle(pkg, R, O, BEND)
     assert not np.array_equal(rest["t"], moved["t"])
     assert np.array_equal(before[0], moved["light_face"]) and not np.array_equal(before[2], moved["light_pos"])
-    want = (v[_scene(pkg).face[moved["light_face"], :, 0]] - np.array(list(R.info().centre))).reshape(-1, 9)   # the nine fp64 positions per light
+    want = (v[K.scene(pkg).face[moved["light_face"], :, 0]] - np.array(list(R.info().centre))).reshape(-1, 9)   # the nine fp64 positions per light
     assert np.array_equal(bits(want), bits(moved["light_pos"]))
     info = R.update_info(); si = R.skin_info()
     assert info.updates == 1 and info.last_update_ms > 0 and (si.n_bones, si.updates) == (N_BONES, 1) and 0 < si.last_ms <= info.last_update_ms
@@ -389,7 +276,7 @@ def test_four_influences_with_zero_weight_slots(pkg):
     R, O = _pair(pkg, skin=skin)
     m = _mats(low=M_LOW, high=M_HIGH, third=M_THIRD, lamp=M_LAMP)
     v, _ = _ref(pkg, m, skin)
-    sphere = _parts(pkg)[0]
+    sphere = K.parts(pkg)[0]
     assert v[sphere].min() > 0.01 and v[sphere].max() < 0.99
     _check_against_oracle(pkg, R, O, m, skin)
     R.close(); O.close()
@@ -397,39 +284,39 @@ def test_four_influences_with_zero_weight_slots(pkg):
 
 @pytest.mark.gpu
 def test_identity_bones_leave_the_scene_as_it_was(pkg):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
     R, O = _pair(pkg, skin=None)
-    rest = _unit_rest(pkg)
-    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see _unit_rest
-    before = _state(pkg, R)
+    rest = K.unit_rest(pkg)
+    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see deform_kit.unit_rest
+    before = K.state(pkg, R)
     rng = np.random.default_rng(8)
     vb = rng.integers(0, 3, (nv, 4)); nb = rng.integers(0, 3, (nn, 4))         # dyadic weights on any mix of identity bones: the identity exactly
     skin = (vb, np.tile(DYADIC, (nv, 1)), nb, np.tile(DYADIC, (nn, 1)))
     R.set_vertex_skin(*skin, 3)
-    _assert_same(before, _state(pkg, R))                                     # setting a skin moves nothing
+    K.assert_same(before, K.state(pkg, R))                                   # setting a skin moves nothing
     after = _check_against_oracle(pkg, R, O, T.identity(3), skin, rest)
-    _assert_same(before, after)                                              # traces, shading normals, lights and film: as they were, bit for bit
+    K.assert_same(before, after)                                             # traces, shading normals, lights and film: as they were, bit for bit
     assert R.update_info().updates == O.update_info().updates == 2 and R.update_info().wide_area_ratio == O.update_info().wide_area_ratio
     R.close(); O.close()
 
 
 @pytest.mark.gpu
 def test_single_influence_is_update_transforms(pkg):
-    s = _scene(pkg); sphere, lamp = _parts(pkg)
+    s = K.scene(pkg); sphere, lamp = K.parts(pkg)
     R, X = _pair(pkg, skin=None)
     vg, ng = pkg.groups_from_faces(s, np.where(s.face[:, 0, 3] == SPHERE, 1, np.where(s.face[:, 0, 3] == LAMP, 2, 0)))
     X.set_vertex_groups(vg, ng, 3)
     R.set_vertex_skin(*S.single(vg), *S.single(ng), 3)
     m = np.stack([T.identity(1)[0], M_THIRD, M_LAMP])                          # (made + 0.0-clean above)
     R.update_skin(m); X.update_transforms(m)
-    _assert_same(_state(pkg, R), _state(pkg, X))
+    K.assert_same(K.state(pkg, R), K.state(pkg, X))
     R.close(); X.close()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["one_bone", "one_bone_per_record"])
 def test_extreme_bone_counts(pkg, case):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
     rng = np.random.default_rng(11)
     wv = rng.uniform(0.1, 1.0, (nv, 4)); wv /= wv.sum(1, keepdims=True); wn = rng.uniform(0.1, 1.0, (nn, 4)); wn /= wn.sum(1, keepdims=True)
     if case == "one_bone":                                                   # every slot of every record names bone 0; the weights only sum to 1 within rounding
@@ -438,7 +325,7 @@ def test_extreme_bone_counts(pkg, case):
     else:                                                                    # the widest gather: a matrix of its own per vertex and per normal
         skin = (np.repeat(np.arange(nv), 4).reshape(nv, 4), wv, np.repeat(nv + np.arange(nn), 4).reshape(nn, 4), wn)
         m = T.identity(nv + nn)
-        sphere = _parts(pkg)[0]
+        sphere = K.parts(pkg)[0]
         m[:nv][sphere, :, 3] = rng.uniform(-0.004, 0.004, (int(sphere.sum()), 3))   # pure translations for vertices, identity for normals
     R, O = _pair(pkg, skin=None)
     R.set_vertex_skin(*skin, len(m))
@@ -450,22 +337,22 @@ def test_extreme_bone_counts(pkg, case):
 @pytest.mark.gpu
 def test_bones_are_not_cumulative_and_sequences(pkg):
     R, O = _pair(pkg, skin=None)
-    rest = _unit_rest(pkg)
-    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see _unit_rest
-    R.set_vertex_skin(*_bend(pkg), N_BONES)
-    original = _state(pkg, R)
+    rest = K.unit_rest(pkg)
+    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see deform_kit.unit_rest
+    R.set_vertex_skin(*K.bend(pkg), N_BONES)
+    original = K.state(pkg, R)
     R.update_skin(BEND)
     moved = _check_against_oracle(pkg, R, O, BEND2, rest=rest)               # M1 then M2 = M2 alone (the lamp is back, too)
     assert not np.array_equal(moved["film"], original["film"])
     R.update_skin(BEND2)                                                     # the same bones twice: the same scene
-    _assert_same(_state(pkg, R), moved)
+    K.assert_same(K.state(pkg, R), moved)
     back = _check_against_oracle(pkg, R, O, _mats(), rest=rest)              # M then identity: what the restatement says ...
-    _assert_same(original, back)                                             # ... which is the original film, traces, normals and lights, bit for bit
+    K.assert_same(original, back)                                            # ... which is the original film, traces, normals and lights, bit for bit
     assert R.skin_info().updates == 4 and R.update_info().updates == 5 and O.update_info().updates == 3
     # update_vertices in between moves the scene and leaves the skin's rest pose alone
     v1, n1 = _ref(pkg, BEND2, rest=rest)
     R.update_vertices(v1, n1); O.update_vertices(v1, n1)
-    _assert_same(_state(pkg, R, film=False), _state(pkg, O, film=False))
+    K.assert_same(K.state(pkg, R, film=False), K.state(pkg, O, film=False))
     _check_against_oracle(pkg, R, O, BEND, rest=rest)                        # from the REST pose, not from what update_vertices wrote
     # a second set_vertex_skin takes the current scene as the new rest pose -- and may change the skin
     R.update_vertices(v1, n1)
@@ -477,7 +364,7 @@ def test_bones_are_not_cumulative_and_sequences(pkg):
 
 @pytest.mark.gpu
 def test_groups_and_skin_on_one_context(pkg):
-    s = _scene(pkg)
+    s = K.scene(pkg)
     R, O = _pair(pkg, skin=None)
     vg, ng = pkg.groups_from_faces(s, np.where(s.face[:, 0, 3] == SPHERE, 1, np.where(s.face[:, 0, 3] == LAMP, 2, 0)))
     gm = np.stack([T.identity(1)[0], clean(T.about(T.rotation((0, 1, 0), 15.0), CENTRE, (0.05, 0.0, 0.05))), M_LAMP])
@@ -485,12 +372,12 @@ def test_groups_and_skin_on_one_context(pkg):
 
     def groups_oracle(m):
         O.update_vertices(T.transform_vertices(s.vertex, vg, m), T.transform_normals(s.normal, ng, m))
-        _assert_same(_state(pkg, R), _state(pkg, O))
+        K.assert_same(K.state(pkg, R), K.state(pkg, O))
 
     R.set_vertex_groups(vg, ng, 3)                                           # the groups' rest pose: the scene as created
     R.update_transforms(gm); groups_oracle(gm)
     posed = (T.transform_vertices(s.vertex, vg, gm), T.transform_normals(s.normal, ng, gm))
-    R.set_vertex_skin(*_bend(pkg), N_BONES)                                  # the skin's OWN rest pose: the scene as the groups left it
+    R.set_vertex_skin(*K.bend(pkg), N_BONES)                                 # the skin's OWN rest pose: the scene as the groups left it
     small = _mats(low=clean(T.about(T.rotation((0, 0, 1), 5.0), CENTRE)), high=clean(T.about(T.rotation((0, 0, 1), -12.0), CENTRE, (0.0, 0.04, 0.0))))
     _check_against_oracle(pkg, R, O, small, rest=posed)
     R.update_transforms(gm2); groups_oracle(gm2)                             # each call overwrites the other's result and reads its own rest pose
@@ -505,7 +392,7 @@ def test_groups_and_skin_on_one_context(pkg):
 def test_update_between_renders_without_a_sync(pkg, which):
     import torch
     R, O = _pair(pkg)
-    O.set_vertex_skin(*_bend(pkg), N_BONES)
+    O.set_vertex_skin(*K.bend(pkg), N_BONES)
     if which == "side":
         stream = torch.cuda.Stream()
         R.set_torch_stream(stream)
@@ -541,14 +428,14 @@ def test_reprojection_follows_the_skin(pkg, with_camera):
     assert (ia.reprojections, ia.pixels_reused) == (ib.reprojections, ib.pixels_reused) == (1, ib.pixels_reused) and ia.pixels_reused > 0.5 * W * H
     assert np.array_equal(bits(R.features()), bits(O.features()))          # the context holds the new scene's features
     assert R.update_info().updates == 1 and R.skin_info().updates == 1
-    _assert_same(_state(pkg, R, film=False), _state(pkg, O, film=False))
+    K.assert_same(K.state(pkg, R, film=False), K.state(pkg, O, film=False))
     R.close(); O.close()
 
 
 @pytest.mark.gpu
 def test_skin_refusals(pkg):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
-    vb, vw, nb, nw = _bend(pkg)
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    vb, vw, nb, nw = K.bend(pkg)
     plain = pkg.Renderer(s, max_depth=6, flags=pkg.FLAG_DETERMINISTIC)
     for call in (lambda: plain.set_vertex_skin(vb, vw, nb, nw, N_BONES), lambda: plain.update_skin(_mats()), lambda: plain.update_skin_reproject(_mats())):
         with pytest.raises(pkg.McptError) as e:
@@ -556,7 +443,7 @@ def test_skin_refusals(pkg):
         assert "status %d" % UNSUPPORTED in str(e.value)
     plain.close()
     R = pkg.Renderer(s, max_depth=6, flags=FLAGS(pkg))
-    o, d = _rays(pkg)
+    o, d = K.rays(pkg)
     film = render_film(R, 4, 5); trace = R.probe_trace4(o, d); bytes0 = R.info().device_bytes
     expect = {"n_bones": 0}
 
@@ -656,27 +543,27 @@ def test_skin_refusals(pkg):
 
 @pytest.mark.gpu
 def test_clone_rebuild_and_bookkeeping(pkg):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
     R, O = _pair(pkg, skin=None)
     base = R.info().device_bytes
     assert R.skin_info().n_bones == 0 and R.skin_info().updates == 0
-    R.set_vertex_skin(*_bend(pkg), N_BONES)
+    R.set_vertex_skin(*K.bend(pkg), N_BONES)
     per_record = 24 + 16 + 32                                                # rest pose, ids, weights
     assert R.info().device_bytes - base == per_record * (nv + nn) + 96 * N_BONES
-    R.set_vertex_skin(*_bend(pkg), N_BONES + 4)                              # replaces: the old buffers are released
+    R.set_vertex_skin(*K.bend(pkg), N_BONES + 4)                             # replaces: the old buffers are released
     assert R.info().device_bytes - base == per_record * (nv + nn) + 96 * (N_BONES + 4) and R.skin_info().n_bones == N_BONES + 4
-    R.set_vertex_skin(*_bend(pkg), N_BONES)
+    R.set_vertex_skin(*K.bend(pkg), N_BONES)
     assert R.info().device_bytes - base == per_record * (nv + nn) + 96 * N_BONES
     R.update_skin(BEND)
     clone = R.clone()
     assert clone.info().device_bytes == R.info().device_bytes
     si = clone.skin_info()
     assert (si.n_bones, si.updates) == (N_BONES, 0)
-    _assert_same(_state(pkg, clone), _state(pkg, R))                         # the clone is the bent scene ...
+    K.assert_same(K.state(pkg, clone), K.state(pkg, R))                      # the clone is the bent scene ...
     _check_against_oracle(pkg, clone, O, BEND2)                              # ... with the ORIGINAL rest pose and the skin
     v, n = _ref(pkg, BEND)
     O.update_vertices(v, n)
-    _assert_same(_state(pkg, R), _state(pkg, O))                             # the source did not move with its clone
+    K.assert_same(K.state(pkg, R), K.state(pkg, O))                          # the source did not move with its clone
     far = _mats(); far[1, 1, 1] = 2e18                                       # R_b travelled too: refused only because R_b of the lower bone is > 0
     for r in (R, clone):
         with pytest.raises(pkg.McptError):
@@ -685,7 +572,7 @@ def test_clone_rebuild_and_bookkeeping(pkg):
     for builder in (pkg.REBUILD_HOST, pkg.REBUILD_DEVICE):
         R.rebuild(builder); O.rebuild(builder)
         assert R.skin_info().n_bones == N_BONES
-        _assert_same(_state(pkg, R), _state(pkg, O))
+        K.assert_same(K.state(pkg, R), K.state(pkg, O))
         _check_against_oracle(pkg, R, O, BEND2 if builder == pkg.REBUILD_HOST else BEND)
         with pytest.raises(pkg.McptError):
             R.update_skin(far)
@@ -698,23 +585,13 @@ def test_clone_rebuild_and_bookkeeping(pkg):
     clone.close(); R.close(); O.close()
 
 
-def _height_skin(pkg, scene, part):
-    """Three bones: the vertices of the faces in `part` blended between bones 1 and 2 by their height inside the part's y-extent, the rest bone 0."""
-    vi = np.unique(scene.face[part][:, :, 0])
-    y = scene.vertex[vi, 1]; w = (y - y.min()) / (y.max() - y.min())
-    vb, vw = S.single(np.zeros(scene.vertex.shape[0], int))
-    vb[vi, 0] = 1; vb[vi, 1] = 2; vw[vi, 0] = 1.0 - w; vw[vi, 1] = w
-    nb, nw = pkg.skin_normals_from_faces(scene, vb, vw)
-    return vb, vw, nb, nw
-
-
 @pytest.mark.gpu
 def test_facade_skin(pkg, tmp_path):
     exe = kit.build_facade("facade_skin.cpp", tmp_path)
     a = pkg.scenes.cornell_box(44, 30, sphere_lon=24, sphere_lat=12)
     obj = a.write(str(tmp_path / "a"))
     # the program reads the 9-digit text of the file: the same numbers scenes.py keeps (SceneData is rounded through that text form)
-    vb, vw, nb, nw = _height_skin(pkg, a, a.face[:, 0, 3] == SPHERE)
+    vb, vw, nb, nw = K.height_skin(pkg, a, a.face[:, 0, 3] == SPHERE)
     m = np.stack([T.identity(1)[0], M_LOW, M_HIGH])
     vb.astype(np.uint32).tofile(str(tmp_path / "b.bin")); vw.tofile(str(tmp_path / "w.bin")); m.tofile(str(tmp_path / "m.bin"))
     S.skin_vertices(a.vertex, vb, vw, m).tofile(str(tmp_path / "v.bin")); S.skin_normals(a.normal, nb, nw, m).tofile(str(tmp_path / "n.bin"))
@@ -759,7 +636,7 @@ def test_skin_update_is_not_slower_on_the_device_than_the_upload_it_replaces(pkg
     DESIGN.md §18 and profiles/skin_probe.json (tools/skin_probe.py)."""
     scene = pkg.scenes.bathroom_stress(64, 36, detail=160, tex_size=16)
     part = np.isin(scene.face[:, 0, 3], (5, 6))
-    vb, vw, nb, nw = _height_skin(pkg, scene, part)
+    vb, vw, nb, nw = K.height_skin(pkg, scene, part)
     pivot = scene.vertex[np.unique(scene.face[part][:, :, 0])].mean(0)
     R = pkg.Renderer(scene, max_depth=6, flags=pkg.FLAG_DYNAMIC | pkg.FLAG_GPU_BVH_BUILD)
     R.set_vertex_skin(vb, vw, nb, nw, 3)

@@ -10,21 +10,15 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests import kit, morph_ref as M, normals_ref as NR, skin_dq_ref as D, skin_ref as S, transform_ref as T
-from tests.kit import ROOT, bits, render_film
+from tests import deform_kit as K, kit, morph_ref as M, normals_ref as NR, skin_dq_ref as D, skin_ref as S, transform_ref as T
+from tests.deform_kit import CENTRE, FLAGS, H, INVALID, LAMP, M_LAMP, M_LOW, N_BONES, SPHERE, UNSUPPORTED, W, clean
+from tests.kit import bits, render_film
 
 NEW_SYMBOLS = ["mcpt_set_skin_mode", "mcpt_get_skin_mode"]
-INVALID, UNSUPPORTED = 1, 6
-W, H = 64, 64
-SPHERE, LAMP = 4, 3                                                          # materials of S-cornell: the glossy sphere, the ceiling light
-CENTRE = np.array([0.5, 0.3, 0.5])                                           # of the sphere (radius 0.3: it stands on the floor)
 DYADIC = (0.5, 0.25, 0.125, 0.125)                                           # every partial sum and every product with 0 or 1 is exact
 EPS = np.finfo(np.float64).eps
 # A single influence against the bone's own A p + t: the worst error of the restatement against numpy.longdouble over 20 000 random rigid bones,
@@ -34,17 +28,10 @@ SINGLE_WORST = 1.641e-15
 SINGLE_TOLERANCE = 8.0 * SINGLE_WORST
 
 
-def clean(m):
-    """The matrices without negative zeros (-0.0 + 0.0 = +0.0; everything else is unchanged)."""
-    return np.ascontiguousarray(m, np.float64) + 0.0
-
-
-# test_skin.py's bend with the scalings taken out (dual-quaternion mode takes rigid bones only), and a twist
-M_LOW = clean(T.about(T.rotation((0, 0, 1), -6.0), CENTRE, (0.0, 0.06, 0.0)))
+# test_skin.py's bend with the scalings taken out (dual-quaternion mode takes rigid bones only; M_LOW and M_LAMP are rigid as they are), and a twist
 M_HIGH = clean(T.about(T.rotation((0, 0, 1), 25.0), (0.5, 0.1, 0.5), (0.03, 0.08, -0.04)))
 M_THIRD = clean(T.about(T.rotation((1, 2, 3), 20.0), CENTRE, (0.01, 0.05, -0.02)))
 M_OTHER = clean(T.about(T.rotation((0, 1, 0), -75.0), CENTRE, (-0.02, 0.05, 0.03)))
-M_LAMP = clean(T.about(T.rotation((0, 1, 0), 25.0), (0.5, 0.999, 0.5), (0.1, -0.2, 0.05)))
 M_TWIST = clean(T.about(T.rotation((0, 1, 0), 170.0), CENTRE, (0.0, 0.05, 0.0)))   # linear blending leaves the sphere's waist at 0.087 of its radius
 M_LIFT = clean(T.about(np.eye(3), CENTRE, (0.0, 0.05, 0.0)))
 M_PLUS100 = clean(T.about(T.rotation((0, 1, 0), 100.0), CENTRE, (0.0, 0.05, 0.0)))
@@ -53,7 +40,6 @@ M_UNUSED = clean(T.about(np.eye(3), (5, 5, 5), (6e16, 0, 0)))                # a
 M_SCALED = clean(T.about(T.rotation((0, 0, 1), 25.0) @ np.diag([0.9, 0.95, 0.9]), (0.5, 0.1, 0.5)))
 M_MIRRORED = clean(T.about(T.rotation((0, 0, 1), 25.0) @ np.diag([1.0, 1.0, -1.0]), CENTRE))
 M_SHEARED = clean(T.about(T.rotation((0, 0, 1), 25.0) @ np.array([[1.0, 0.01, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]), CENTRE))
-N_BONES = 5                                                                  # 0 the walls, 1 and 2 the sphere's lower and upper bone, 3 nobody, 4 the lamp
 
 
 def _half_turn(axis):
@@ -69,40 +55,11 @@ N_FOUR = 8                                                                   # t
 
 
 @functools.lru_cache(maxsize=None)
-def _scene(pkg, small=False):
-    """S-cornell with the 48 x 24 sphere (1 249 records: five 256-blocks with a tail) or S-cornell-small (349 records: two blocks with a tail)."""
-    return pkg.scenes.cornell_box_small(W, H) if small else pkg.scenes.cornell_box(W, H, sphere_lon=48, sphere_lat=24)
-
-
-@functools.lru_cache(maxsize=None)
-def _parts(pkg, small=False):
-    """(sphere, lamp) as boolean masks over the vertices."""
-    s = _scene(pkg, small)
-    out = []
-    for mtl in (SPHERE, LAMP):
-        mask = np.zeros(s.vertex.shape[0], bool); mask[np.unique(s.face[s.face[:, 0, 3] == mtl][:, :, 0])] = True
-        out.append(mask)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def _bend(pkg, small=False):
-    """test_skin's five-bone skin: walls on bone 0, lamp on bone 4, every sphere vertex blended between bones 1 and 2 by its height; bone 3 has
-    no member.  (vertex ids, vertex weights, normal ids, normal weights.)"""
-    s = _scene(pkg, small); sphere, lamp = _parts(pkg, small)
-    vb, vw = S.single(np.where(lamp, 4, 0))
-    y = s.vertex[sphere, 1]; w = (y - y.min()) / (y.max() - y.min())
-    assert w.min() == 0.0 and w.max() == 1.0
-    vb[sphere, 0] = 1; vb[sphere, 1] = 2; vw[sphere, 0] = 1.0 - w; vw[sphere, 1] = w
-    return (vb, vw) + tuple(pkg.skin_normals_from_faces(s, vb, vw))
-
-
-@functools.lru_cache(maxsize=None)
 def _four(pkg):
     """Every sphere vertex with four random weights normalised in fp64 over bones 1 .. 3, a third of the slots exactly 0 with a random id of ANY
     of the eight bones in them -- slot 0, the pivot, included; walls on bone 0, lamp on bone 4.  The LAST record of the array is the constructed
     degenerate one: slot 0 of weight 0 on bone 0, then the three opposed bones at a third each."""
-    s = _scene(pkg); sphere, lamp = _parts(pkg); n = int(sphere.sum())
+    s = K.scene(pkg); sphere, lamp = K.parts(pkg); n = int(sphere.sum())
     rng = np.random.default_rng(23)
     vb, vw = S.single(np.where(lamp, 4, 0))
     r = rng.uniform(0.05, 1.0, (n, 4)); ids = rng.integers(1, 4, (n, 4))
@@ -119,11 +76,8 @@ def _four(pkg):
 
 
 def _mats(low=None, high=None, lamp=None, third=None, n=N_BONES):
-    m = T.identity(n)
-    m[3] = M_UNUSED if third is None else third
-    if low is not None: m[1] = low
-    if high is not None: m[2] = high
-    if lamp is not None: m[4] = lamp
+    """deform_kit.mats with this suite's rigid far-away bone 3, and with the three opposed bones where there are eight."""
+    m = K.mats(low, high, lamp, M_UNUSED if third is None else third, n)
     if n == N_FOUR: m[5:] = OPPOSED
     return m
 
@@ -136,7 +90,7 @@ FOUR = _mats(low=M_PLUS100, high=M_270, third=M_THIRD, lamp=M_LAMP, n=N_FOUR)
 
 def _ref(pkg, matrices, skin=None, rest=None, small=False):
     """The arrays the bones give in dual-quaternion mode, by the restatement."""
-    s = _scene(pkg, small); vb, vw, nb, nw = _bend(pkg, small) if skin is None else skin
+    s = K.scene(pkg, small); vb, vw, nb, nw = K.bend(pkg, small) if skin is None else skin
     rv, rn = (s.vertex, s.normal) if rest is None else rest
     return D.skin_vertices(rv, vb, vw, matrices), D.skin_normals(rn, nb, nw, matrices)
 
@@ -166,11 +120,8 @@ def test_null_arguments_are_invalid_for_the_skin_mode_calls(pkg):
 
 
 def test_the_modes_have_the_headers_values(pkg, tmp_path):
-    src = tmp_path / "t.c"; exe = str(tmp_path / "t")
-    src.write_text('#include <stdio.h>\n#include "mcpt.h"\nint main(void) { printf("%u %u %u %zu\\n", MCPT_SKIN_LINEAR, MCPT_SKIN_DUAL_QUATERNION, '
-                   'MCPT_ABI_VERSION, sizeof(mcpt_skin_info)); return 0; }\n')
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    assert subprocess.check_output([exe]).decode().split() == ["0", "1", "4", str(C.sizeof(pkg.SkinInfo))]
+    c, py, modes = K.c_layout(pkg.SkinInfo, "mcpt_skin_info", tmp_path, macros=("MCPT_SKIN_LINEAR", "MCPT_SKIN_DUAL_QUATERNION"))
+    assert modes == [0, 1] and c[0] == C.sizeof(pkg.SkinInfo)
 
 
 def test_restatement_a_twisted_ring_keeps_its_radius():
@@ -192,7 +143,7 @@ def test_restatement_a_twisted_ring_keeps_its_radius():
 
 
 def test_restatement_identity_bones_give_the_rest_pose(pkg):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
     rng = np.random.default_rng(4)
     ids_v = rng.integers(0, 3, (nv, 4)); ids_n = rng.integers(0, 3, (nn, 4))
     dy_v = np.tile(DYADIC, (nv, 1)); dy_n = np.tile(DYADIC, (nn, 1))
@@ -233,7 +184,7 @@ def test_restatement_single_influence_is_the_bones_own_transform(seed):
 
 
 def test_restatement_four_influences_and_the_degenerate_record(pkg):
-    s = _scene(pkg); vb, vw, nb, nw = _four(pkg); sphere = _parts(pkg)[0]
+    s = K.scene(pkg); vb, vw, nb, nw = _four(pkg); sphere = K.parts(pkg)[0]
     q = D.dualquats(FOUR)
     assert D.rigid(FOUR).all()
     ws = D.signed_weights(vb, vw, q)
@@ -257,7 +208,7 @@ def test_restatement_four_influences_and_the_degenerate_record(pkg):
 
 
 def test_restatement_refusals(pkg):
-    s = _scene(pkg); vb, vw, nb, nw = _bend(pkg)
+    s = K.scene(pkg); vb, vw, nb, nw = K.bend(pkg)
     radius = S.bone_radius(s.vertex, vb, vw, T.used_vertices(s), N_BONES)
     assert radius[3] == 0.0 and radius[1] > 0 and radius[2] > 0
     for m in (BEND, BEND2, TWIST, _mats()):
@@ -291,9 +242,6 @@ def test_restatement_refusals(pkg):
     assert D.accepts_dq(_mats(), np.full(N_BONES, 1e16)) and not D.accepts_dq(_mats(), np.full(N_BONES, 2e17))
 
 
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
 def _host_check_cases():
     """(matrices, radii): every Shepperd branch, exact ties between the candidates, half turns about each axis, quaternions whose w comes out
     negative before the sign rule, translations up to 1e17, reaches at the limit, and bones that are not rigid."""
@@ -317,23 +265,17 @@ def _host_check_cases():
     return m, radius, len(special), len(edge)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@K.needs_hipcc
 @pytest.mark.parametrize("sanitized", [False, True])
 def test_host_dual_quaternions_rigid_check_and_reach_are_the_restatement_bit_for_bit(tmp_path, sanitized):
     """The host half of the feature -- sk_bone_dualquat, sk_bone_gram, sk_bone_rigid and sk_dq_reach of csrc/skin.hip, what mcpt_update_skin
     validates and stages with -- built into the stand-alone program tests/skin_dq_host_check.cpp (no device is touched) against
     tests/skin_dq_ref.py: the same bits.  `sanitized`: the same program under the host's address and undefined-behaviour sanitizers, which must
     stay silent."""
-    csrc = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc")
-    exe = str(tmp_path / "skin_dq_host_check")
-    extra = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-g"] if sanitized else []
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-I" + csrc] + extra +
-                          [os.path.join(csrc, "skin.hip"), os.path.join(csrc, "transform.hip"), os.path.join(ROOT, "tests", "skin_dq_host_check.cpp"), "-o", exe])
+    exe = K.build_host_check("skin_dq_host_check", ["skin.hip", "transform.hip"], tmp_path, sanitized)
     m, radius, n_special, n_edge = _host_check_cases()
     np.concatenate([m.reshape(-1, 12), radius[:, None]], 1).tofile(str(tmp_path / "in.bin"))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")                   # (the HIP runtime's start-up allocations are not this program's)
-    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, env=env)
-    assert p.returncode == 0 and "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-3000:]
+    K.run_host_check(exe, tmp_path, sanitized)
     got = np.fromfile(str(tmp_path / "out.bin")).reshape(-1, 16)
     with np.errstate(all="ignore"):
         is_rigid = D.rigid(m)
@@ -352,61 +294,20 @@ def test_host_dual_quaternions_rigid_check_and_reach_are_the_restatement_bit_for
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU helpers
-@functools.lru_cache(maxsize=None)
-def _rays(pkg):
-    """The camera rays of S-cornell (one per pixel, fixed xi) and random rays through its box: computed once, never changed."""
-    s = _scene(pkg)
-    ex = np.array(s.camera.eye); rng = np.random.default_rng(3)
-    t = rng.uniform(0.0, 1.0, (W * H, 3)); t[:, 2] = 0.0                     # towards points of the back wall's plane: all through the room
-    d = t - ex; d /= np.linalg.norm(d, axis=1, keepdims=True)
-    o = rng.uniform(0.01, 0.99, (3000, 3)); q = rng.uniform(0.01, 0.99, (3000, 3))
-    e = q - o; e /= np.linalg.norm(e, axis=1, keepdims=True)
-    return np.concatenate([np.broadcast_to(ex, d.shape), o]), np.concatenate([d, e])
-
-
-def _state(pkg, r, film=True):
-    """Everything the comparisons look at, of one context."""
-    o, d = _rays(pkg)
-    r.validate_trees()
-    t, f, u, v = r.probe_trace4(o, d)
-    hit = f >= 0
-    assert hit.mean() > 0.9
-    shade = r.probe_hit_shade(f[hit], u[hit], v[hit], d[hit])
-    lf, lrec, lpos = r.probe_lights()
-    vtx, nrm = r.vertices()
-    out = {"vertex": vtx, "normal": nrm, "t": t, "face": f, "u": u, "v": v, "shade": shade, "light_face": lf, "light_rec": lrec, "light_pos": lpos}
-    if film:
-        out["film"] = render_film(r, 4, 5)
-    return out
-
-
-def _assert_same(a, b):
-    for k in a:
-        assert np.array_equal(bits(a[k]), bits(b[k])), k
-
-
-@functools.lru_cache(maxsize=None)
-def _unit_rest(pkg):
-    """S-cornell's vertices and its normals NORMALISED by the restatement (test_skin's _unit_rest: a context put on this pose first comes back to
-    it bit for bit in the fp32 numbers the shading streams hold)."""
-    s = _scene(pkg)
-    return s.vertex, T.transform_normals(s.normal, np.zeros(s.normal.shape[0], int), T.identity(1))
-
-
-FLAGS = lambda pkg: pkg.FLAG_DYNAMIC | pkg.FLAG_DETERMINISTIC
 DQ = lambda pkg: pkg.SKIN_DUAL_QUATERNION
 
 
 def _pair(pkg, extra=0, skin="bend", small=False, mode_first=True):
     """The context under test, in dual-quaternion mode (with the five-bone bend, or `skin` = (records..., n_bones), or none), and its oracle."""
-    s = _scene(pkg, small)
-    R = pkg.Renderer(s, max_depth=8, flags=FLAGS(pkg) | extra); O = pkg.Renderer(s, max_depth=8, flags=FLAGS(pkg) | extra)
-    if mode_first:
-        R.set_skin_mode(DQ(pkg))
-    if skin is not None:
-        R.set_vertex_skin(*(_bend(pkg, small) + (N_BONES,) if skin == "bend" else skin))
-    if not mode_first:
-        R.set_skin_mode(DQ(pkg))
+    def setup(R):
+        if mode_first:
+            R.set_skin_mode(DQ(pkg))
+        if skin is not None:
+            R.set_vertex_skin(*(K.bend(pkg, small) + (N_BONES,) if skin == "bend" else skin))
+        if not mode_first:
+            R.set_skin_mode(DQ(pkg))
+
+    R, O = K.pair(pkg, setup, extra=extra, max_depth=8, scene=K.scene(pkg, small))
     assert R.skin_mode() == DQ(pkg) and O.skin_mode() == pkg.SKIN_LINEAR
     return R, O
 
@@ -414,9 +315,9 @@ def _pair(pkg, extra=0, skin="bend", small=False, mode_first=True):
 def _check_against_oracle(pkg, R, O, matrices, skin=None, rest=None, small=False, film=True):
     v, n = _ref(pkg, matrices, skin, rest, small)
     R.update_skin(matrices); O.update_vertices(v, n)
-    a, b = _state(pkg, R, film), _state(pkg, O, film)
+    a, b = K.state(pkg, R, film, arrays=True), K.state(pkg, O, film, arrays=True)
     assert np.array_equal(bits(a["vertex"]), bits(v)) and np.array_equal(bits(a["normal"]), bits(n))   # probe_vertices: the restated arrays
-    _assert_same(a, b)
+    K.assert_same(a, b)
     return a
 
 
@@ -426,9 +327,9 @@ def _check_against_oracle(pkg, R, O, matrices, skin=None, rest=None, small=False
 @pytest.mark.parametrize("small", [False, True])
 def test_bend_and_twist_of_the_sphere_with_a_moved_lamp(pkg, gpu_tree, small):
     R, O = _pair(pkg, extra=pkg.FLAG_GPU_BVH_BUILD if gpu_tree else 0, small=small, mode_first=gpu_tree)
-    s = _scene(pkg, small); sphere, lamp = _parts(pkg, small)
+    s = K.scene(pkg, small); sphere, lamp = K.parts(pkg, small)
     assert s.vertex.shape[0] == s.normal.shape[0] == (349 if small else 1249)
-    rest = _state(pkg, R, film=False)
+    rest = K.state(pkg, R, film=False, arrays=True)
     before = R.probe_lights()
     for k, m in enumerate((BEND, TWIST)):
         v, _ = _ref(pkg, m, small=small)
@@ -445,13 +346,13 @@ def test_bend_and_twist_of_the_sphere_with_a_moved_lamp(pkg, gpu_tree, small):
     axis = CENTRE[[0, 2]]
     ring = lambda a: np.hypot(*(a[sphere][:, [0, 2]] - axis).T)
     r0, r1 = ring(s.vertex), ring(moved["vertex"])
-    lbs = ring(S.skin_vertices(s.vertex, *_bend(pkg, small)[:2], TWIST))
+    lbs = ring(S.skin_vertices(s.vertex, *K.bend(pkg, small)[:2], TWIST))
     assert np.abs(r1 - r0).max() <= 1e-12 and (lbs / np.maximum(r0, 1e-300))[r0 > 0.1].min() < 0.1
     # ... and the half turn, which linear blending collapses onto the axis, comes out at full radius on the device
     half = _mats(low=M_LIFT, high=clean(T.about(T.rotation((0, 1, 0), 180.0), CENTRE, (0.0, 0.05, 0.0))), lamp=M_LAMP)
     R.update_skin(half)
     assert np.abs(ring(R.vertices()[0]) - r0).max() <= 1e-12
-    assert (ring(S.skin_vertices(s.vertex, *_bend(pkg, small)[:2], half)) / np.maximum(r0, 1e-300))[r0 > 0.1].min() < 1e-14
+    assert (ring(S.skin_vertices(s.vertex, *K.bend(pkg, small)[:2], half)) / np.maximum(r0, 1e-300))[r0 > 0.1].min() < 1e-14
     R.validate_trees()
     R.close(); O.close()
 
@@ -459,7 +360,7 @@ def test_bend_and_twist_of_the_sphere_with_a_moved_lamp(pkg, gpu_tree, small):
 @pytest.mark.gpu
 def test_four_influences_zero_weight_slots_the_antipodal_rule_and_the_degenerate_record(pkg):
     skin = _four(pkg)
-    s = _scene(pkg); last = s.vertex.shape[0] - 1
+    s = K.scene(pkg); last = s.vertex.shape[0] - 1
     long = s.normal.copy(); long[last] *= 2.0                                # the degenerate record's rest normal is not of unit length: it must come back as it is
     R, O = _pair(pkg, skin=None)
     R.update_vertices(s.vertex, long); O.update_vertices(s.vertex, long)
@@ -472,16 +373,16 @@ def test_four_influences_zero_weight_slots_the_antipodal_rule_and_the_degenerate
 
 @pytest.mark.gpu
 def test_identity_bones_leave_the_scene_as_it_was(pkg):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
     R, O = _pair(pkg, skin=None)
-    rest = _unit_rest(pkg)
-    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see _unit_rest
-    before = _state(pkg, R)
+    rest = K.unit_rest(pkg)
+    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see deform_kit.unit_rest
+    before = K.state(pkg, R, arrays=True)
     rng = np.random.default_rng(8)
     vb = rng.integers(0, 3, (nv, 4)); nb = rng.integers(0, 3, (nn, 4))         # dyadic weights on any mix of identity bones: the identity exactly
     skin = (vb, np.tile(DYADIC, (nv, 1)), nb, np.tile(DYADIC, (nn, 1)))
     R.set_vertex_skin(*skin, 3)
-    _assert_same(before, _state(pkg, R))                                     # setting a skin moves nothing
+    K.assert_same(before, K.state(pkg, R, arrays=True))                      # setting a skin moves nothing
     after = _check_against_oracle(pkg, R, O, T.identity(3), skin, rest)
     assert np.array_equal(after["vertex"], before["vertex"])                 # by value: a -0 may become +0
     # (the normals went through v / |v| once more: the same fp32 numbers, as test_restatement_identity_bones_give_the_rest_pose shows)
@@ -494,7 +395,7 @@ def test_identity_bones_leave_the_scene_as_it_was(pkg):
 
 @pytest.mark.gpu
 def test_single_influence_is_update_transforms_within_the_measured_tolerance(pkg):
-    s = _scene(pkg)
+    s = K.scene(pkg)
     R, X = _pair(pkg, skin=None)
     vg, ng = pkg.groups_from_faces(s, np.where(s.face[:, 0, 3] == SPHERE, 1, np.where(s.face[:, 0, 3] == LAMP, 2, 0)))
     X.set_vertex_groups(vg, ng, 3)
@@ -514,23 +415,23 @@ def test_single_influence_is_update_transforms_within_the_measured_tolerance(pkg
 
 @pytest.mark.gpu
 def test_mode_state_device_bytes_and_back_to_linear(pkg):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
     R, O = _pair(pkg, skin=None)                                             # the mode first, no skin yet: nothing is allocated
     L = pkg.Renderer(s, max_depth=8, flags=FLAGS(pkg))                       # a context that never leaves linear mode
     base = O.info().device_bytes                                             # (O goes through the same probes and renders as R: what those allocate is in both)
     assert R.info().device_bytes == base and R.skin_info().n_bones == 0
     per_record = 24 + 16 + 32                                                # rest pose, ids, weights
     linear = per_record * (nv + nn) + 96 * N_BONES
-    R.set_vertex_skin(*_bend(pkg), N_BONES); L.set_vertex_skin(*_bend(pkg), N_BONES)
+    R.set_vertex_skin(*K.bend(pkg), N_BONES); L.set_vertex_skin(*K.bend(pkg), N_BONES)
     assert R.info().device_bytes - O.info().device_bytes == linear + 64 * N_BONES and L.info().device_bytes - base == linear and R.skin_mode() == DQ(pkg)
-    R.set_vertex_skin(*_bend(pkg), N_BONES + 4)                              # another n_bones: the mode stays, the table is resized
+    R.set_vertex_skin(*K.bend(pkg), N_BONES + 4)                             # another n_bones: the mode stays, the table is resized
     assert R.info().device_bytes - O.info().device_bytes == linear + 96 * 4 + 64 * (N_BONES + 4) and R.skin_mode() == DQ(pkg) and R.skin_info().n_bones == N_BONES + 4
     more = T.identity(N_BONES + 4); more[:N_BONES] = BEND
     _check_against_oracle(pkg, R, O, more, film=False)
     R.set_vertex_skin(*_four(pkg), N_FOUR)                                   # (takes the bent scene as its rest pose; replaced again below)
     assert R.info().device_bytes - O.info().device_bytes == per_record * (nv + nn) + (96 + 64) * N_FOUR
     R.update_vertices(s.vertex, s.normal); O.update_vertices(s.vertex, s.normal)
-    R.set_vertex_skin(*_bend(pkg), N_BONES)
+    R.set_vertex_skin(*K.bend(pkg), N_BONES)
     assert R.info().device_bytes - O.info().device_bytes == linear + 64 * N_BONES
     R.set_skin_mode(DQ(pkg))                                                 # the mode it has: nothing changes
     assert R.info().device_bytes - O.info().device_bytes == linear + 64 * N_BONES
@@ -538,13 +439,13 @@ def test_mode_state_device_bytes_and_back_to_linear(pkg):
     # LINEAR -> DQ -> LINEAR: §18's arrays bit for bit, and device_bytes is back
     R.set_skin_mode(pkg.SKIN_LINEAR)
     assert R.skin_mode() == pkg.SKIN_LINEAR and R.info().device_bytes - O.info().device_bytes == linear
-    _assert_same(_state(pkg, R, film=False), {k: v for k, v in dq.items() if k != "film"})   # changing the mode moves nothing
+    K.assert_same(K.state(pkg, R, film=False, arrays=True), {k: v for k, v in dq.items() if k != "film"})   # changing the mode moves nothing
     R.update_skin(BEND); L.update_skin(BEND)
-    lin = _state(pkg, R)
-    _assert_same(lin, _state(pkg, L))
-    assert np.array_equal(bits(lin["vertex"]), bits(S.skin_vertices(s.vertex, *_bend(pkg)[:2], BEND))) and not np.array_equal(lin["vertex"], dq["vertex"])
+    lin = K.state(pkg, R, arrays=True)
+    K.assert_same(lin, K.state(pkg, L, arrays=True))
+    assert np.array_equal(bits(lin["vertex"]), bits(S.skin_vertices(s.vertex, *K.bend(pkg)[:2], BEND))) and not np.array_equal(lin["vertex"], dq["vertex"])
     R.update_skin(_mats(high=M_SCALED)); L.update_skin(_mats(high=M_SCALED))  # a scaled bone is linear mode's to take again
-    _assert_same(_state(pkg, R, film=False), _state(pkg, L, film=False))
+    K.assert_same(K.state(pkg, R, film=False, arrays=True), K.state(pkg, L, film=False, arrays=True))
     R.set_skin_mode(DQ(pkg))                                                 # the mode AFTER the skin: the table comes with it
     assert R.info().device_bytes - O.info().device_bytes == linear + 64 * N_BONES
     _check_against_oracle(pkg, R, O, BEND2, film=False)
@@ -555,15 +456,15 @@ def test_mode_state_device_bytes_and_back_to_linear(pkg):
 @pytest.mark.gpu
 def test_bones_are_not_cumulative(pkg):
     R, O = _pair(pkg, skin=None)
-    rest = _unit_rest(pkg)
-    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see _unit_rest
-    R.set_vertex_skin(*_bend(pkg), N_BONES)
-    original = _state(pkg, R)
+    rest = K.unit_rest(pkg)
+    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see deform_kit.unit_rest
+    R.set_vertex_skin(*K.bend(pkg), N_BONES)
+    original = K.state(pkg, R, arrays=True)
     R.update_skin(BEND)
     moved = _check_against_oracle(pkg, R, O, BEND2, rest=rest)               # M1 then M2 = M2 alone (the lamp is back, too)
     assert not np.array_equal(moved["film"], original["film"])
     R.update_skin(BEND2)                                                     # the same bones twice: the same scene
-    _assert_same(_state(pkg, R), moved)
+    K.assert_same(K.state(pkg, R, arrays=True), moved)
     back = _check_against_oracle(pkg, R, O, _mats(), rest=rest)              # M then identity: what the restatement says ...
     for k in original:
         if k not in ("vertex", "normal"):
@@ -576,7 +477,7 @@ def test_bones_are_not_cumulative(pkg):
 @functools.lru_cache(maxsize=None)
 def _targets(pkg):
     """Two morph targets over the sphere: a swell about its centre with normal deltas of its own, and a sparse lift of the cap."""
-    s = _scene(pkg); sphere = _parts(pkg)[0]
+    s = K.scene(pkg); sphere = K.parts(pkg)[0]
     rng = np.random.default_rng(31)
     si = np.flatnonzero(sphere); cap = si[s.vertex[si, 1] > 0.45]
     vt = [(si, s.vertex[si] - CENTRE), (cap, np.tile((0.0, 0.05, 0.0), (len(cap), 1)))]
@@ -586,7 +487,7 @@ def _targets(pkg):
 
 @pytest.mark.gpu
 def test_morph_then_skin_in_dual_quaternion_mode(pkg):
-    s = _scene(pkg); vb, vw, nb, nw = _bend(pkg)
+    s = K.scene(pkg); vb, vw, nb, nw = K.bend(pkg)
     R, O = _pair(pkg)
     vt, nt = _targets(pkg)
     R.set_vertex_morph(vt, nt)
@@ -594,12 +495,12 @@ def test_morph_then_skin_in_dual_quaternion_mode(pkg):
     mv, mn = M.morph_vertices(s.vertex, vt, weights), M.morph_normals(s.normal, nt, weights)
     for bones in (TWIST, BEND):
         v, n = D.skin_vertices(mv, vb, vw, bones), D.skin_normals(mn, nb, nw, bones)
-        assert v[_parts(pkg)[0]].min() > 0.01 and v[_parts(pkg)[0]].max() < 0.99
+        assert v[K.parts(pkg)[0]].min() > 0.01 and v[K.parts(pkg)[0]].max() < 0.99
         R.update_morph(weights, bones); O.update_vertices(v, n)
-        a = _state(pkg, R)
+        a = K.state(pkg, R, arrays=True)
         assert np.array_equal(bits(a["vertex"]), bits(v)) and np.array_equal(bits(a["normal"]), bits(n))
-        _assert_same(a, _state(pkg, O))
-    lv, ln = M.morph_then_skin(s.vertex, s.normal, vt, nt, weights, _bend(pkg), TWIST)
+        K.assert_same(a, K.state(pkg, O, arrays=True))
+    lv, ln = M.morph_then_skin(s.vertex, s.normal, vt, nt, weights, K.bend(pkg), TWIST)
     assert not np.array_equal(lv, D.skin_vertices(mv, vb, vw, TWIST))        # (the linear route gives other arrays)
     cam = pkg.scenes.Camera((0.62, 0.55, 2.25), (0.5, 0.45, 0.0), (0.0, 1.0, 0.0), 40.0, W, H)
     opts = dict(feature_spp=4, feature_seed=3, max_history=16.0)
@@ -608,7 +509,7 @@ def test_morph_then_skin_in_dual_quaternion_mode(pkg):
         r.clear(); r.render(8, seed=5)
     R.update_morph_reproject(weights, BEND2, camera=cam, **opts); O.update_vertices_reproject(v, n, camera=cam, **opts)
     assert np.array_equal(bits(R.read_accum()), bits(O.read_accum()))
-    _assert_same(_state(pkg, R, film=False), _state(pkg, O, film=False))
+    K.assert_same(K.state(pkg, R, film=False, arrays=True), K.state(pkg, O, film=False, arrays=True))
     # the reach bound with E in R_b's place, on the bone without members too; a bone that is not rigid is refused here as well
     used = T.used_vertices(s)
     e = M.reach(M.rest_radius(s.vertex, used), weights, M.target_delta(vt, used))
@@ -628,19 +529,19 @@ def test_morph_then_skin_in_dual_quaternion_mode(pkg):
 
 @pytest.mark.gpu
 def test_groups_and_skin_on_one_context(pkg):
-    s = _scene(pkg)
+    s = K.scene(pkg)
     R, O = _pair(pkg, skin=None)
     vg, ng = pkg.groups_from_faces(s, np.where(s.face[:, 0, 3] == SPHERE, 1, np.where(s.face[:, 0, 3] == LAMP, 2, 0)))
     gm = np.stack([T.identity(1)[0], clean(T.about(T.rotation((0, 1, 0), 15.0), CENTRE, (0.05, 0.0, 0.05))), M_LAMP])
 
     def groups_oracle(m):
         O.update_vertices(T.transform_vertices(s.vertex, vg, m), T.transform_normals(s.normal, ng, m))
-        _assert_same(_state(pkg, R, film=False), _state(pkg, O, film=False))
+        K.assert_same(K.state(pkg, R, film=False, arrays=True), K.state(pkg, O, film=False, arrays=True))
 
     R.set_vertex_groups(vg, ng, 3)                                           # the groups' rest pose: the scene as created
     R.update_transforms(gm); groups_oracle(gm)
     posed = (T.transform_vertices(s.vertex, vg, gm), T.transform_normals(s.normal, ng, gm))
-    R.set_vertex_skin(*_bend(pkg), N_BONES)                                  # the skin's OWN rest pose: the scene as the groups left it
+    R.set_vertex_skin(*K.bend(pkg), N_BONES)                                 # the skin's OWN rest pose: the scene as the groups left it
     small = _mats(low=clean(T.about(T.rotation((0, 0, 1), 5.0), CENTRE)), high=clean(T.about(T.rotation((0, 1, 0), -160.0), CENTRE, (0.0, 0.04, 0.0))))
     _check_against_oracle(pkg, R, O, small, rest=posed)
     R.update_transforms(gm); groups_oracle(gm)                               # each call overwrites the other's result and reads its own rest pose
@@ -650,7 +551,7 @@ def test_groups_and_skin_on_one_context(pkg):
 
 @pytest.mark.gpu
 def test_auto_normals_follow_the_dual_quaternion_route(pkg):
-    s = _scene(pkg); sphere = _parts(pkg)[0]
+    s = K.scene(pkg); sphere = K.parts(pkg)[0]
     R, O = _pair(pkg)
     mask = np.zeros(s.normal.shape[0], np.uint8); mask[np.unique(s.face[s.face[:, 0, 3] == SPHERE][:, :, 1])] = 1
     R.set_auto_normals(mask)
@@ -659,9 +560,9 @@ def test_auto_normals_follow_the_dual_quaternion_route(pkg):
         v, n = _ref(pkg, m)
         n = NR.apply(offset, entry, v, n)                                    # the chosen records from the deformed faces, the rest as the kernel wrote them
         R.update_skin(m); O.update_vertices(v, n)
-        a = _state(pkg, R)
+        a = K.state(pkg, R, arrays=True)
         assert np.array_equal(bits(a["vertex"]), bits(v)) and np.array_equal(bits(a["normal"]), bits(n))
-        _assert_same(a, _state(pkg, O))
+        K.assert_same(a, K.state(pkg, O, arrays=True))
     assert R.normals_info().updates == 2 and int(mask.sum()) == int(sphere.sum())
     R.close(); O.close()
 
@@ -683,7 +584,7 @@ def test_reprojection_follows_the_dual_quaternion_skin(pkg, with_camera):
     assert (ia.reprojections, ia.pixels_reused) == (ib.reprojections, ib.pixels_reused) == (1, ib.pixels_reused) and ia.pixels_reused > 0.5 * W * H
     assert np.array_equal(bits(R.features()), bits(O.features()))          # the context holds the new scene's features
     assert R.update_info().updates == 1 and R.skin_info().updates == 1
-    _assert_same(_state(pkg, R, film=False), _state(pkg, O, film=False))
+    K.assert_same(K.state(pkg, R, film=False, arrays=True), K.state(pkg, O, film=False, arrays=True))
     R.close(); O.close()
 
 
@@ -692,7 +593,7 @@ def test_reprojection_follows_the_dual_quaternion_skin(pkg, with_camera):
 def test_update_between_renders_without_a_sync(pkg, which):
     import torch
     R, O = _pair(pkg)
-    O.set_skin_mode(DQ(pkg)); O.set_vertex_skin(*_bend(pkg), N_BONES)
+    O.set_skin_mode(DQ(pkg)); O.set_vertex_skin(*K.bend(pkg), N_BONES)
     if which == "side":
         stream = torch.cuda.Stream()
         R.set_torch_stream(stream)
@@ -721,21 +622,21 @@ def test_clone_rebuild_and_bookkeeping(pkg):
     assert clone.skin_mode() == DQ(pkg) and clone.info().device_bytes == R.info().device_bytes
     si = clone.skin_info()
     assert (si.n_bones, si.updates) == (N_BONES, 0)
-    _assert_same(_state(pkg, clone), _state(pkg, R))                         # the clone is the twisted scene ...
+    K.assert_same(K.state(pkg, clone, arrays=True), K.state(pkg, R, arrays=True))   # the clone is the twisted scene ...
     _check_against_oracle(pkg, clone, O, BEND2)                              # ... with the ORIGINAL rest pose, the skin, the mode and the table
     with pytest.raises(pkg.McptError):
         clone.update_skin(_mats(high=M_SCALED))                              # (the mode travelled: a scaled bone is refused)
-    plain = pkg.Renderer(_scene(pkg), max_depth=8, flags=FLAGS(pkg)); plain.set_skin_mode(DQ(pkg))
+    plain = pkg.Renderer(K.scene(pkg), max_depth=8, flags=FLAGS(pkg)); plain.set_skin_mode(DQ(pkg))
     c2 = plain.clone()                                                       # the mode travels without a skin, too
     assert c2.skin_mode() == DQ(pkg) and c2.info().device_bytes == plain.info().device_bytes
     c2.close(); plain.close()
     v, n = _ref(pkg, TWIST)
     O.update_vertices(v, n)
-    _assert_same(_state(pkg, R), _state(pkg, O))                             # the source did not move with its clone
+    K.assert_same(K.state(pkg, R, arrays=True), K.state(pkg, O, arrays=True))   # the source did not move with its clone
     for builder in (pkg.REBUILD_HOST, pkg.REBUILD_DEVICE):                   # a rebuild keeps mode, table, skin and rest pose
         R.rebuild(builder); O.rebuild(builder)
         assert R.skin_mode() == DQ(pkg) and R.skin_info().n_bones == N_BONES
-        _assert_same(_state(pkg, R, film=False), _state(pkg, O, film=False))
+        K.assert_same(K.state(pkg, R, film=False, arrays=True), K.state(pkg, O, film=False, arrays=True))
         _check_against_oracle(pkg, R, O, BEND if builder == pkg.REBUILD_HOST else TWIST)
     R.update_skin(_mats()); R.update_skin_reproject(_mats())
     si = R.skin_info()
@@ -747,7 +648,7 @@ def test_clone_rebuild_and_bookkeeping(pkg):
 
 @pytest.mark.gpu
 def test_skin_mode_and_dual_quaternion_refusals(pkg):
-    s = _scene(pkg); vb, vw, nb, nw = _bend(pkg)
+    s = K.scene(pkg); vb, vw, nb, nw = K.bend(pkg)
     plain = pkg.Renderer(s, max_depth=8, flags=pkg.FLAG_DETERMINISTIC)
     for mode in (pkg.SKIN_DUAL_QUATERNION, pkg.SKIN_LINEAR, 7):
         with pytest.raises(pkg.McptError) as e:
@@ -756,7 +657,7 @@ def test_skin_mode_and_dual_quaternion_refusals(pkg):
     assert plain.skin_mode() == pkg.SKIN_LINEAR and plain.lib.mcpt_get_skin_mode(plain.ctx, None) == INVALID
     plain.close()
     R = pkg.Renderer(s, max_depth=8, flags=FLAGS(pkg))
-    o, d = _rays(pkg)
+    o, d = K.rays(pkg)
     film = render_film(R, 4, 5); trace = R.probe_trace4(o, d); arrays = R.vertices()
     expect = {"n_bones": 0, "mode": pkg.SKIN_LINEAR, "bytes": R.info().device_bytes}
 
@@ -828,22 +729,12 @@ def test_skin_mode_and_dual_quaternion_refusals(pkg):
     R.close()
 
 
-def _height_skin(pkg, scene, part):
-    """Three bones: the vertices of the faces in `part` blended between bones 1 and 2 by their height inside the part's y-extent, the rest bone 0."""
-    vi = np.unique(scene.face[part][:, :, 0])
-    y = scene.vertex[vi, 1]; w = (y - y.min()) / (y.max() - y.min())
-    vb, vw = S.single(np.zeros(scene.vertex.shape[0], int))
-    vb[vi, 0] = 1; vb[vi, 1] = 2; vw[vi, 0] = 1.0 - w; vw[vi, 1] = w
-    nb, nw = pkg.skin_normals_from_faces(scene, vb, vw)
-    return vb, vw, nb, nw
-
-
 @pytest.mark.gpu
 def test_facade_skin_dq(pkg, tmp_path):
     exe = kit.build_facade("facade_skin_dq.cpp", tmp_path)
     a = pkg.scenes.cornell_box(44, 30, sphere_lon=24, sphere_lat=12)
     obj = a.write(str(tmp_path / "a"))
-    vb, vw, nb, nw = _height_skin(pkg, a, a.face[:, 0, 3] == SPHERE)
+    vb, vw, nb, nw = K.height_skin(pkg, a, a.face[:, 0, 3] == SPHERE)
     m = np.stack([T.identity(1)[0], M_LOW, M_TWIST])
     vb.astype(np.uint32).tofile(str(tmp_path / "b.bin")); vw.tofile(str(tmp_path / "w.bin")); m.tofile(str(tmp_path / "m.bin"))
     D.skin_vertices(a.vertex, vb, vw, m).tofile(str(tmp_path / "v.bin")); D.skin_normals(a.normal, nb, nw, m).tofile(str(tmp_path / "n.bin"))
@@ -889,7 +780,7 @@ def test_dual_quaternion_update_is_not_slower_on_the_device_than_the_upload_it_r
     not larger.  The figures are in DESIGN.md §21 and profiles/skin_dq_probe.json (tools/skin_dq_probe.py)."""
     scene = pkg.scenes.bathroom_stress(64, 36, detail=160, tex_size=16)
     part = np.isin(scene.face[:, 0, 3], (5, 6))
-    vb, vw, nb, nw = _height_skin(pkg, scene, part)
+    vb, vw, nb, nw = K.height_skin(pkg, scene, part)
     pivot = scene.vertex[np.unique(scene.face[part][:, :, 0])].mean(0)
     R = pkg.Renderer(scene, max_depth=6, flags=pkg.FLAG_DYNAMIC | pkg.FLAG_GPU_BVH_BUILD)
     R.set_vertex_skin(vb, vw, nb, nw, 3)

@@ -9,39 +9,28 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests import kit, transform_ref as T
-from tests.kit import ROOT, bits, render_film
+from tests import deform_kit as K, kit, transform_ref as T
+from tests.deform_kit import CENTRE, FLAGS, H, INVALID, LAMP, M_LAMP, SPHERE, UNSUPPORTED, W
+from tests.kit import bits, render_film
 
 NEW_SYMBOLS = ["mcpt_set_vertex_groups", "mcpt_update_transforms", "mcpt_update_transforms_reproject", "mcpt_get_transform_info"]
-INVALID, UNSUPPORTED = 1, 6
-W, H = 64, 64
-SPHERE, LAMP = 4, 3                                                          # materials of S-cornell: the glossy sphere, the ceiling light
-CENTRE = np.array([0.5, 0.3, 0.5])                                           # of the sphere
-
-
-@functools.lru_cache(maxsize=None)
-def _scene(pkg):
-    return pkg.scenes.cornell_box(W, H, sphere_lon=48, sphere_lat=24)         # ~1 100 sphere vertices: several 256-blocks and a tail
 
 
 @functools.lru_cache(maxsize=None)
 def _groups(pkg):
     """Group 0 the walls, 1 the sphere, 2 the lamp."""
-    s = _scene(pkg)
+    s = K.scene(pkg)
     m = s.face[:, 0, 3]
     return pkg.groups_from_faces(s, np.where(m == SPHERE, 1, np.where(m == LAMP, 2, 0)))
 
 
 def _ref(pkg, matrices, groups=None, rest=None):
     """The arrays the matrices give, by the restatement."""
-    s = _scene(pkg); vg, ng = _groups(pkg) if groups is None else groups
+    s = K.scene(pkg); vg, ng = _groups(pkg) if groups is None else groups
     rv, rn = (s.vertex, s.normal) if rest is None else rest
     return T.transform_vertices(rv, vg, matrices), T.transform_normals(rn, ng, matrices)
 
@@ -56,7 +45,6 @@ def _mats(sphere=None, lamp=None):
 M_RIGID = T.about(T.rotation((1, 2, 3), 30.0) @ np.diag([0.8, 0.6, 0.9]), CENTRE, (0.1, 0.2, -0.05))
 M_OTHER = T.about(T.rotation((0, 1, 0), -75.0) @ np.diag([0.7, 1.1, 0.7]), CENTRE, (-0.08, 0.1, 0.1))
 M_MIRROR = T.about(T.rotation((0, 0, 1), 20.0) @ np.diag([-1.0, 0.9, 1.0]), CENTRE, (0.05, 0.15, 0.0))
-M_LAMP = T.about(T.rotation((0, 1, 0), 25.0), (0.5, 0.999, 0.5), (0.1, -0.2, 0.05))
 
 
 # ------------------------------------------------------------------------------------------------------------------------ CPU
@@ -101,12 +89,12 @@ def test_groups_from_faces(pkg):
     assert "normal" in str(e.value)
     # S-cornell: the sphere and the lamp have vertices of their own
     vg, ng = _groups(pkg)
-    s = _scene(pkg)
+    s = K.scene(pkg)
     assert (vg == 1).sum() == np.unique(s.face[s.face[:, 0, 3] == SPHERE][:, :, 0]).size > 1000 and (vg == 2).sum() == 4
 
 
 def test_restatement_identity_gives_the_rest_pose(pkg):
-    s = _scene(pkg); vg, ng = _groups(pkg)
+    s = K.scene(pkg); vg, ng = _groups(pkg)
     v, n = _ref(pkg, T.identity(3))
     assert np.array_equal(v, s.vertex)                                       # (1 x + 0 y) + 0 z + 0 = x exactly
     # normals are normalised again: |n|^2 of the file's 9-digit normals is 1 within 1e-8, the quotient is rounded once more -- the same fp32
@@ -115,10 +103,10 @@ def test_restatement_identity_gives_the_rest_pose(pkg):
     ln = np.sqrt((n * n).sum(1))
     assert np.abs(ln - 1.0).max() <= 4 * np.finfo(np.float64).eps
     # ... and from there on the step is a fixed point of the fp32 numbers the shading streams hold, which the raw normals are not: what lets the
-    # GPU identity tests ask for bit equality (see _unit_rest)
+    # GPU identity tests ask for bit equality (see deform_kit.unit_rest)
     again = T.transform_normals(n, ng, T.identity(3))
     assert np.array_equal(again.astype(np.float32).view(np.uint32), n.astype(np.float32).view(np.uint32))
-    assert np.array_equal(_unit_rest(pkg)[1], n) and not np.array_equal(n.astype(np.float32), s.normal.astype(np.float32))
+    assert np.array_equal(K.unit_rest(pkg, _groups(pkg)[1], 3)[1], n) and not np.array_equal(n.astype(np.float32), s.normal.astype(np.float32))
     # cofactors of the identity are the identity, its determinant 1, and the validation passes
     assert np.array_equal(T.cofactors(T.identity(2)), np.stack([np.eye(3)] * 2)) and T.determinants(T.identity(2)).tolist() == [1.0, 1.0]
     assert T.accepts(T.identity(3), T.group_radius(s.vertex, vg, T.used_vertices(s), 3))
@@ -158,7 +146,6 @@ def test_restatement_reflection_flips_the_normal(pkg):
     assert not T.accepts(far, r) and T.accepts(far, np.array([0.0]))
 
 
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 HOST_PROG = r'''
 #include <cstdio>
 #include <vector>
@@ -183,15 +170,14 @@ int main(int argc, char** argv) {
 '''
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@K.needs_hipcc
 def test_host_cofactors_and_validation_are_the_restatement_bit_for_bit(pkg, tmp_path):
     """The host half of the feature -- xf_group_record, xf_record_det, xf_row_reach of csrc/transform.hip, what fills the staged table and what
     mcpt_update_transforms validates with -- built into a stand-alone program (no device is touched) against tests/transform_ref.py: the same
     bits, also where a last bit decides (a determinant that cancels to exactly 0, a reach one ulp over the limit)."""
-    csrc = os.path.join(ROOT, "monte-carlo-path-tracer_amd", "csrc")
-    src = str(tmp_path / "host.cpp"); exe = str(tmp_path / "host")
+    src = str(tmp_path / "host.cpp")
     open(src, "w").write(HOST_PROG)
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-I" + csrc, os.path.join(csrc, "transform.hip"), src, "-o", exe])
+    exe = K.build_host_check("host", ["transform.hip"], tmp_path, source=src)
     rng = np.random.default_rng(5)
     m = rng.normal(0.0, 1.0, (400, 3, 4)) * 10.0 ** rng.integers(-8, 9, (400, 1, 1))
     m[:40, 2, :3] = m[:40, 0, :3] * 3.0 + m[:40, 1, :3]                      # nearly singular: heavy cancellation in the determinant
@@ -200,7 +186,7 @@ def test_host_cofactors_and_validation_are_the_restatement_bit_for_bit(pkg, tmp_
                         np.array([[1e3, 0, 0, 1e18], [0, 1, 0, 0], [0, 0, 1, 0.0]]), np.array([[1, 0, 0, 1e18], [0, 1, 0, 0], [0, 0, 1, 0.0]])])
     m = np.concatenate([special, m]); radius = np.concatenate([np.full(len(special), 0.8), rng.uniform(0.0, 2.0, 400)])
     np.concatenate([m.reshape(-1, 12), radius[:, None]], 1).tofile(str(tmp_path / "in.bin"))
-    subprocess.check_call([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")])
+    K.run_host_check(exe, tmp_path)
     got = np.fromfile(str(tmp_path / "out.bin")).reshape(-1, 25)
     with np.errstate(all="ignore"):
         want = np.concatenate([m.reshape(-1, 12), T.cofactors(m).reshape(-1, 9), T.determinants(m)[:, None], T.reach(m, radius)], 1)
@@ -209,68 +195,16 @@ def test_host_cofactors_and_validation_are_the_restatement_bit_for_bit(pkg, tmp_
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU helpers
-@functools.lru_cache(maxsize=None)
-def _rays(pkg):
-    """The camera rays of S-cornell (one per pixel, fixed xi) and random rays through its box: computed once, never changed."""
-    s = _scene(pkg)
-    cam = s.camera
-    ex = np.array(cam.eye); rng = np.random.default_rng(3)
-    t = rng.uniform(0.0, 1.0, (W * H, 3)); t[:, 2] = 0.0                     # towards points of the back wall's plane: all through the room
-    d = t - ex; d /= np.linalg.norm(d, axis=1, keepdims=True)
-    o = rng.uniform(0.01, 0.99, (3000, 3)); q = rng.uniform(0.01, 0.99, (3000, 3))
-    e = q - o; e /= np.linalg.norm(e, axis=1, keepdims=True)
-    return np.concatenate([np.broadcast_to(ex, d.shape), o]), np.concatenate([d, e])
-
-
-def _state(pkg, r, film=True):
-    """Everything the comparisons look at, of one context."""
-    o, d = _rays(pkg)
-    r.validate_trees()
-    t, f, u, v = r.probe_trace4(o, d)
-    hit = f >= 0
-    assert hit.mean() > 0.9
-    shade = r.probe_hit_shade(f[hit], u[hit], v[hit], d[hit])
-    lf, lrec, lpos = r.probe_lights()
-    out = {"t": t, "face": f, "u": u, "v": v, "shade": shade, "light_face": lf, "light_rec": lrec, "light_pos": lpos}
-    if film:
-        out["film"] = render_film(r, 4, 5)
-    return out
-
-
-def _assert_same(a, b, skip=()):
-    for k in a:
-        if k not in skip:
-            assert np.array_equal(bits(a[k]), bits(b[k])), k
-
-
-@functools.lru_cache(maxsize=None)
-def _unit_rest(pkg):
-    """S-cornell's vertices and its normals NORMALISED by the restatement.  The file's normals are 9-digit decimals, unit length within ~1e-9 only:
-    xf_normals_kernel's c / |c| moves 16 of the 1 249 to another fp32 number, so an identity on the raw scene cannot leave the shading streams bit for
-    bit as they were.  Normalised once they are a fixed point of that step in fp32 (asserted in test_restatement_identity_gives_the_rest_pose):
-    a context put on this pose first (update_vertices) must come back to it bit for bit under identity matrices."""
-    s = _scene(pkg)
-    return s.vertex, T.transform_normals(s.normal, _groups(pkg)[1], T.identity(3))
-
-
-FLAGS = lambda pkg: pkg.FLAG_DYNAMIC | pkg.FLAG_DETERMINISTIC
-
-
 def _pair(pkg, extra=0, groups=True):
     """The context under test (with S-cornell's three groups) and its oracle."""
-    s = _scene(pkg)
-    R = pkg.Renderer(s, max_depth=6, flags=FLAGS(pkg) | extra); O = pkg.Renderer(s, max_depth=6, flags=FLAGS(pkg) | extra)
-    if groups:
-        vg, ng = _groups(pkg)
-        R.set_vertex_groups(vg, ng, 3)
-    return R, O
+    return K.pair(pkg, (lambda R: R.set_vertex_groups(*_groups(pkg), 3)) if groups else None, extra=extra, max_depth=6)
 
 
 def _check_against_oracle(pkg, R, O, matrices, groups=None, rest=None):
     v, n = _ref(pkg, matrices, groups, rest)
     R.update_transforms(matrices); O.update_vertices(v, n)
-    a, b = _state(pkg, R), _state(pkg, O)
-    _assert_same(a, b)
+    a, b = K.state(pkg, R), K.state(pkg, O)
+    K.assert_same(a, b)
     return a
 
 
@@ -278,19 +212,19 @@ def _check_against_oracle(pkg, R, O, matrices, groups=None, rest=None):
 @pytest.mark.gpu
 def test_identity_leaves_the_scene_as_it_was(pkg):
     R, O = _pair(pkg, extra=pkg.FLAG_COUNT_TRAVERSAL, groups=False)
-    rest = _unit_rest(pkg)
-    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see _unit_rest
+    rest = K.unit_rest(pkg, _groups(pkg)[1], 3)
+    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see deform_kit.unit_rest
     R.reset_counters()
-    before = _state(pkg, R)
+    before = K.state(pkg, R)
     c0 = R.counters(); work0 = c0.box_tests + c0.tri_tests
     ratio0 = R.update_info().wide_area_ratio
     assert work0 > 0 and abs(ratio0 - 1.0) <= 1e-3
     vg, ng = _groups(pkg)
     R.set_vertex_groups(vg, ng, 3)
-    _assert_same(before, _state(pkg, R))                                     # setting groups moves nothing
+    K.assert_same(before, K.state(pkg, R))                                   # setting groups moves nothing
     R.reset_counters(); O.reset_counters()
     after = _check_against_oracle(pkg, R, O, T.identity(3), rest=rest)
-    _assert_same(before, after)                                              # traces, shading normals, lights and film: as they were, bit for bit
+    K.assert_same(before, after)                                             # traces, shading normals, lights and film: as they were, bit for bit
     cr, co = R.counters(), O.counters()
     assert (cr.box_tests, cr.tri_tests, cr.shaded_hits) == (co.box_tests, co.tri_tests, co.shaded_hits)
     ir, io = R.update_info(), O.update_info()
@@ -309,8 +243,8 @@ def test_rigid_move_of_the_sphere(pkg, gpu_tree):
     m = _mats(sphere=M_RIGID)
     v, _ = _ref(pkg, m)
     vg, _ = _groups(pkg)
-    assert v[vg == 1].min() > 0.01 and v[vg == 1].max() < 0.99 and not np.array_equal(v, _scene(pkg).vertex)   # moved, inside the room
-    rest = _state(pkg, R, film=False)
+    assert v[vg == 1].min() > 0.01 and v[vg == 1].max() < 0.99 and not np.array_equal(v, K.scene(pkg).vertex)   # moved, inside the room
+    rest = K.state(pkg, R, film=False)
     moved = _check_against_oracle(pkg, R, O, m)
     assert not np.array_equal(rest["t"], moved["t"])
     info = R.update_info()
@@ -326,8 +260,8 @@ def test_reflection_turns_the_normals_through_the_cofactors(pkg):
     # cof(A) = det(A) A^-T carries the shading normal the way it carries the triangle's own normal (the cross product of its edges in the stored
     # winding): after the reflection the two are on the same side of every sphere triangle, as they were in the rest pose -- A^-T alone would
     # leave them on opposite sides.  (Pole triangles aside, where a 9-digit normal and a sliver's cross product say little: > 99 % of the hits.)
-    s = _scene(pkg); v, _ = _ref(pkg, _mats(sphere=M_MIRROR))
-    o, d = _rays(pkg)
+    s = K.scene(pkg); v, _ = _ref(pkg, _mats(sphere=M_MIRROR))
+    o, d = K.rays(pkg)
     t, f, u, w = R.probe_trace4(o[:W * H], d[:W * H])
     on_sphere = (f >= 0) & (s.face[np.maximum(f, 0), 0, 3] == SPHERE)
     assert on_sphere.sum() > 100
@@ -351,7 +285,7 @@ def test_moved_lamp_moves_the_light_records(pkg):
     a = _check_against_oracle(pkg, R, O, _mats(lamp=M_LAMP))
     assert np.array_equal(before[0], a["light_face"]) and not np.array_equal(before[2], a["light_pos"])
     # light_pos64 is the moved corners relative to the creation centre
-    s = _scene(pkg); v, _ = _ref(pkg, _mats(lamp=M_LAMP))
+    s = K.scene(pkg); v, _ = _ref(pkg, _mats(lamp=M_LAMP))
     want = (v[s.face[a["light_face"], :, 0]] - np.array(list(R.info().centre))).reshape(-1, 9)
     assert np.array_equal(bits(want), bits(a["light_pos"]))
     R.close(); O.close()
@@ -360,7 +294,7 @@ def test_moved_lamp_moves_the_light_records(pkg):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["one_per_vertex", "one_group", "empty_group"])
 def test_group_counts(pkg, case):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
     R, O = _pair(pkg, groups=False)
     rng = np.random.default_rng(11)
     if case == "one_per_vertex":                                             # the widest gather: a record of its own per vertex and per normal
@@ -383,18 +317,18 @@ def test_group_counts(pkg, case):
 @pytest.mark.gpu
 def test_transforms_are_not_cumulative(pkg):
     R, O = _pair(pkg, groups=False)
-    rest = _unit_rest(pkg)
-    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see _unit_rest
+    rest = K.unit_rest(pkg, _groups(pkg)[1], 3)
+    R.update_vertices(*rest); O.update_vertices(*rest)                       # unit-length normals: see deform_kit.unit_rest
     vg, ng = _groups(pkg)
     R.set_vertex_groups(vg, ng, 3)
-    original = _state(pkg, R)
+    original = K.state(pkg, R)
     R.update_transforms(_mats(sphere=M_RIGID, lamp=M_LAMP))
     moved = _check_against_oracle(pkg, R, O, _mats(sphere=M_OTHER), rest=rest)   # M1 then M2 = M2 alone (the lamp is back, too)
     assert not np.array_equal(moved["film"], original["film"])
     R.update_transforms(_mats(sphere=M_OTHER))                               # the same matrices twice: the same scene
-    _assert_same(_state(pkg, R), moved)
+    K.assert_same(K.state(pkg, R), moved)
     back = _check_against_oracle(pkg, R, O, T.identity(3), rest=rest)        # M then identity: what the restatement says ...
-    _assert_same(original, back)                                             # ... which is the original film, traces, normals and lights, bit for bit
+    K.assert_same(original, back)                                            # ... which is the original film, traces, normals and lights, bit for bit
     assert R.transform_info().updates == 4 and R.update_info().updates == 5 and O.update_info().updates == 3
     R.close(); O.close()
 
@@ -402,12 +336,12 @@ def test_transforms_are_not_cumulative(pkg):
 @pytest.mark.gpu
 def test_interplay_with_vertex_updates(pkg):
     R, O = _pair(pkg)
-    s = _scene(pkg); vg, ng = _groups(pkg)
+    s = K.scene(pkg); vg, ng = _groups(pkg)
     R.update_transforms(_mats(sphere=M_RIGID))
     v1, n1 = _ref(pkg, _mats(sphere=M_OTHER, lamp=M_LAMP))
     R.update_vertices(v1, n1)                                                # moves the scene, leaves the rest pose alone
     O.update_vertices(v1, n1)
-    _assert_same(_state(pkg, R, film=False), _state(pkg, O, film=False))
+    K.assert_same(K.state(pkg, R, film=False), K.state(pkg, O, film=False))
     _check_against_oracle(pkg, R, O, _mats(sphere=M_RIGID))                   # from the REST pose, not from what update_vertices wrote
     # a second set_vertex_groups takes the current scene as the new rest pose
     R.update_vertices(v1, n1)
@@ -447,7 +381,7 @@ def test_update_between_renders_without_a_sync(pkg, which):
 @pytest.mark.parametrize("with_camera", [False, True])
 def test_reprojection_follows_the_transform(pkg, with_camera):
     R, O = _pair(pkg)
-    s = _scene(pkg)
+    s = K.scene(pkg)
     cam = pkg.scenes.Camera((0.62, 0.55, 2.25), (0.5, 0.45, 0.0), (0.0, 1.0, 0.0), 40.0, W, H) if with_camera else None
     m = _mats(sphere=T.about(T.rotation((0, 1, 0), 12.0), CENTRE, (0.03, 0.02, 0.0)))
     v, n = _ref(pkg, m)
@@ -462,13 +396,13 @@ def test_reprojection_follows_the_transform(pkg, with_camera):
     assert (ia.reprojections, ia.pixels_reused) == (ib.reprojections, ib.pixels_reused) == (1, ib.pixels_reused) and ia.pixels_reused > 0.5 * W * H
     assert np.array_equal(bits(R.features()), bits(O.features()))          # the context holds the new scene's features
     assert R.update_info().updates == 1 and R.transform_info().updates == 1
-    _assert_same(_state(pkg, R, film=False), _state(pkg, O, film=False))
+    K.assert_same(K.state(pkg, R, film=False), K.state(pkg, O, film=False))
     R.close(); O.close()
 
 
 @pytest.mark.gpu
 def test_transform_refusals(pkg):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
     vg, ng = _groups(pkg)
     plain = pkg.Renderer(s, max_depth=6, flags=pkg.FLAG_DETERMINISTIC)
     for call in (lambda: plain.set_vertex_groups(vg, ng, 3), lambda: plain.update_transforms(T.identity(3)),
@@ -478,7 +412,7 @@ def test_transform_refusals(pkg):
         assert "status %d" % UNSUPPORTED in str(e.value)
     plain.close()
     R = pkg.Renderer(s, max_depth=6, flags=FLAGS(pkg))
-    o, d = _rays(pkg)
+    o, d = K.rays(pkg)
     film = render_film(R, 4, 5); trace = R.probe_trace4(o, d); bytes0 = R.info().device_bytes
 
     def unchanged():
@@ -543,7 +477,7 @@ def test_transform_refusals(pkg):
 
 @pytest.mark.gpu
 def test_clone_and_bookkeeping(pkg):
-    s = _scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
+    s = K.scene(pkg); nv, nn = s.vertex.shape[0], s.normal.shape[0]
     R, O = _pair(pkg, groups=False)
     vg, ng = _groups(pkg)
     base = R.info().device_bytes
@@ -559,11 +493,11 @@ def test_clone_and_bookkeeping(pkg):
     assert clone.info().device_bytes == R.info().device_bytes
     ti = clone.transform_info()
     assert (ti.n_groups, ti.updates) == (3, 0)
-    _assert_same(_state(pkg, clone), _state(pkg, R))                         # the clone is the moved scene ...
+    K.assert_same(K.state(pkg, clone), K.state(pkg, R))                      # the clone is the moved scene ...
     _check_against_oracle(pkg, clone, O, _mats(sphere=M_OTHER, lamp=M_LAMP))  # ... with the ORIGINAL rest pose and the groups
     v, n = _ref(pkg, _mats(sphere=M_RIGID))
     O.update_vertices(v, n)
-    _assert_same(_state(pkg, R), _state(pkg, O))                             # the source did not move with its clone
+    K.assert_same(K.state(pkg, R), K.state(pkg, O))                          # the source did not move with its clone
     # R_g travelled too: the clone refuses what the source refuses
     far = T.identity(3); far[1, 1, :] = (0.0, 1e3, 0.0, 1e18)               # refused only because R_g of the sphere is > 0
     for r in (R, clone):
