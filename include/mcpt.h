@@ -555,6 +555,79 @@ mcpt_status mcpt_get_skin_info(mcpt_ctx* ctx, mcpt_skin_info* out);   /* synchro
 mcpt_status mcpt_set_skin_mode(mcpt_ctx* ctx, uint32_t mode);
 mcpt_status mcpt_get_skin_mode(mcpt_ctx* ctx, uint32_t* out_mode);
 
+/* ---- baked vertex animation: device-resident keyframes played by time --------------------------------------------------------- */
+/* Cloth, a fluid meshed per frame with fixed topology, a destruction sequence, a point cache, an OBJ sequence: per-vertex motion that no bone and
+ * no sparse target expresses.  The caller uploads the keyframes ONCE -- whole vertex arrays (and, optionally, normal arrays), uniformly spaced in
+ * time -- and then sends ONE DOUBLE, THE TIME, per frame: the device writes the current vertices and normals by interpolating the keyframes.
+ * All four calls need MCPT_FLAG_DYNAMIC (else MCPT_ERR_UNSUPPORTED).
+ *
+ * mcpt_set_vertex_keyframes: set-up, synchronous, the twin of mcpt_set_vertex_morph.  vertex_frames holds n_frames arrays of 3 n_vertex doubles,
+ * frame after frame; normal_frames (NULL, or n_frames arrays of 3 n_normal doubles) the normals of every frame, used AS GIVEN (not normalised
+ * here).  Frame k lies at start_time + k * frame_time.  opts == NULL: MCPT_KEYFRAMES_LINEAR, MCPT_KEYFRAMES_CLAMP, start_time 0, frame_time 1.
+ * Without normal_frames the context's CURRENT normals are captured (device to device) as the keyframes' own rest normals, and every update writes
+ * them, as mcpt_update_morph does without normal targets.  The set is independent of groups, skin and morph: all of them may be set on one
+ * context; a call of any route overwrites what the previous route wrote and touches no other route's rest pose.  Calling it again replaces
+ * frames and options.  On the device a frame's stride is its 3 n doubles rounded up to an EVEN number (3 n is odd when n is odd; the padding is
+ * 0 and never read), so that every frame, like the output arrays, starts 16-byte aligned.  Allocates, counted in device_bytes and reported in
+ * mcpt_keyframe_info::device_bytes: 8 B x n_frames x stride(n_vertex), the same for the normals when normal_frames is given, and 24 B per
+ * vertex and per normal for the pose captured at set-up (of which only the normals are read, and only without normal_frames).  Freed with the
+ * context; mcpt_clone_to_device carries all of it; mcpt_rebuild_trees leaves it alone (it is per vertex, not per leaf).
+ *  - Refused with nothing changed, MCPT_ERR_INVALID_ARG, in this order: a NULL context or NULL vertex_frames; n_vertex / n_normal that differ
+ *    from the scene's; a wrong struct_size; an unknown interpolation; an unknown wrap; n_frames outside [2, MCPT_KEYFRAMES_MAX]; start_time not
+ *    finite; frame_time not finite or <= 0; a coordinate of a vertex that a face uses that is not finite or has |x| > 1e18; a normal component
+ *    that is not finite; a reach E that is not <= 1e18, with E = (1 + 2^-16) (c R), R the largest |coordinate| of a used vertex over all
+ *    frames, c = 1 (linear) or 1.25 (Catmull-Rom: the largest sum of |weights|, reached at u = 1/2).  MCPT_ERR_HIP when an allocation fails.
+ *    Because of these checks an update validates only its time: no device round trip.
+ *
+ * Time to segment, on the host, fp64, one correctly rounded operation each, K = n_frames: x = (time - start_time) / frame_time.
+ *  - MCPT_KEYFRAMES_CLAMP: x <= 0: k = 0, u = 0; x >= K - 1: k = K - 1, u = 0; otherwise k = floor(x), u = x - k.
+ *  - MCPT_KEYFRAMES_LOOP: the period is K frames (frame K - 1 blends into frame 0): x = fmod(x, K); if x < 0: x = x + K; if then !(x < K):
+ *    x = 0; k = floor(x), u = x - k.
+ *  - Taps: (k, k + 1) linear, (k - 1, k, k + 1, k + 2) Catmull-Rom; indices clamped to [0, K - 1] under CLAMP, taken modulo K under LOOP.
+ * Weights (never renormalised): linear (1 - u, u); Catmull-Rom, with u2 = u u and u3 = u2 u: w0 = 0.5 ((2 u2 - u3) - u),
+ * w1 = 0.5 ((3 u3 - 5 u2) + 2), w2 = 0.5 ((4 u2 - 3 u3) + u), w3 = 0.5 (u3 - u2).
+ *
+ * mcpt_update_keyframes: MCPT_ERR_INVALID_ARG for a time that is not finite, then when no keyframes are set.  u == 0: the vertices become frame k
+ * COPIED device to device, bit for bit (negative zeros included), the normals frame k's as given (not normalised) -- or the rest normals.
+ * Otherwise per component, fp64, one rounding per operation: linear out = w0 a + w1 b; Catmull-Rom out = ((w0 a + w1 b) + w2 c) + w3 d; normals
+ * get the same sum and are then divided by sqrt((x x + y y) + z z) when that is finite and > 0, and are otherwise left as they are
+ * (mcpt_update_transforms' rule); without normal_frames they are the rest normals.  Every record is written on every call.  From there on the
+ * call IS mcpt_update_vertices after its upload: the auto-normals pass when it is set, the same refit, ordering and bookkeeping
+ * (mcpt_get_update_info counts it), and what it leaves untouched (film, counters) or drops (features, denoised film, tile error).
+ *  - Asynchronous on the context's stream.  The weights and tap indices travel as kernel arguments: nothing is staged, and back-to-back calls
+ *    cannot overtake each other.
+ *
+ * mcpt_update_keyframes_reproject is mcpt_update_vertices_reproject with the time in place of the upload; validation order: the above, the camera
+ * (when given), the options, MCPT_ERR_BVH_DEPTH. */
+#define MCPT_KEYFRAMES_LINEAR      0u
+#define MCPT_KEYFRAMES_CATMULL_ROM 1u   /* uniform Catmull-Rom spline through the frames: C1 motion, may overshoot by at most 1/4 */
+#define MCPT_KEYFRAMES_CLAMP       0u   /* before the first frame: the first; after the last: the last */
+#define MCPT_KEYFRAMES_LOOP        1u   /* periodic, period n_frames * frame_time */
+#define MCPT_KEYFRAMES_MAX         65536
+typedef struct mcpt_keyframe_opts {
+    uint32_t struct_size;
+    uint32_t interpolation;             /* MCPT_KEYFRAMES_LINEAR / _CATMULL_ROM */
+    uint32_t wrap;                      /* MCPT_KEYFRAMES_CLAMP / _LOOP */
+    uint32_t reserved0;
+    double   start_time, frame_time;    /* frame k lies at start_time + k * frame_time; frame_time > 0 */
+    uint32_t reserved[4];
+} mcpt_keyframe_opts;
+typedef struct mcpt_keyframe_info {
+    uint32_t struct_size, n_frames;     /* frames of the set now (0 = none) */
+    uint32_t interpolation, wrap;       /* of the set now */
+    uint32_t updates, last_frame;       /* mcpt_update_keyframes (+ _reproject) calls on this context so far; k of the last one */
+    double   last_u, last_time;         /* u and the time of the last one */
+    double   last_ms;                   /* device time of the last one's deforming part: the copies or the two kernels */
+    uint64_t device_bytes;              /* what the set holds on the device now */
+    uint32_t reserved[4];
+} mcpt_keyframe_info;
+mcpt_status mcpt_set_vertex_keyframes(mcpt_ctx* ctx, const double* vertex_frames /* n_frames * 3 n_vertex */, uint32_t n_vertex,
+                                      const double* normal_frames /* NULL, or n_frames * 3 n_normal */, uint32_t n_normal,
+                                      uint32_t n_frames, const mcpt_keyframe_opts* opts /* NULL: linear, clamp, start 0, frame_time 1 */);
+mcpt_status mcpt_update_keyframes(mcpt_ctx* ctx, double time);
+mcpt_status mcpt_update_keyframes_reproject(mcpt_ctx* ctx, double time, const mcpt_camera* camera /* NULL = keep */, const mcpt_reproject_opts* opts /* NULL = defaults */);
+mcpt_status mcpt_get_keyframe_info(mcpt_ctx* ctx, mcpt_keyframe_info* out);   /* synchronises */
+
 /* ---- deforming parts: morph targets (blend shapes) on the device -------------------------------------------------------------- */
 /* A facial expression, a bulging muscle or a breathing chest is a weighted sum of per-vertex displacement sets, not a matrix per bone.  The caller
  * names the targets once -- each a sparse list of records and their displacements -- and then sends ONE WEIGHT PER TARGET and frame: the device
@@ -633,7 +706,7 @@ mcpt_status mcpt_probe_vertices(mcpt_ctx* ctx, double* out_vertex /* 3 n_vertex,
 /* None of the update routes yields normals of the DEFORMED surface: mcpt_update_vertices(normal = NULL) keeps the old ones, mcpt_update_morph
  * without normal targets writes the rest pose's, mcpt_update_skin pushes rest normals through a blended matrix.  The tracer orients a surface by
  * its vertex normals alone, so stale normals also give wrong front/back decisions and emission sides.  With auto normals on, every scene update
- * -- mcpt_update_vertices / _transforms / _skin / _morph and their _reproject forms -- runs one extra kernel after the route has written the
+ * -- mcpt_update_vertices / _transforms / _skin / _morph / _keyframes and their _reproject forms -- runs one extra kernel after the route has written the
  * vertices and normals and in front of the refit: each chosen normal record becomes the normalised sum of the area-weighted normals of the faces
  * that use it, computed from the vertices as they are now.  All calls need MCPT_FLAG_DYNAMIC (else MCPT_ERR_UNSUPPORTED).
  *
@@ -698,7 +771,7 @@ mcpt_status mcpt_get_normals_info(mcpt_ctx* ctx, mcpt_normals_info* out);   /* s
  *    rank it has (the creation geometry's, as mcpt_update_vertices documents).
  *  - KEPT, because the scene looks the same from every pixel: the film or a bound accumulator, the counters, the stream binding, the camera, the
  *    feature buffers and the denoised film, the adaptive tile error, the reprojection buffers, the vertex groups with their rest pose and R_g,
- *    the skin with its rest pose and R_b, the morph targets with their rest pose, R and D_k (and the morph-then-skin scratch), the auto-normals lists (§20: they are per face of the description, not per leaf), the materials, the textures, and the light list's membership and order (only the lights' leaf-order
+ *    the skin with its rest pose and R_b, the morph targets with their rest pose, R and D_k (and the morph-then-skin scratch), the keyframes with their options and captured pose (§22), the auto-normals lists (§20: they are per face of the description, not per leaf), the materials, the textures, and the light list's membership and order (only the lights' leaf-order
  *    triangle index is renumbered).
  *  - Afterwards mcpt_update_info::wide_area_ratio is 1.0 (its base is the new tree) and `updates` is unchanged; mcpt_scene_info follows the new
  *    trees: n_nodes, bvh_depth, max_leaf, wide_nodes, wide_depth, traversal_bytes, wide_tree_hash, bvh_builder, and device_bytes counts what is

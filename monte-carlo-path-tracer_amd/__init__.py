@@ -23,6 +23,8 @@ from .rebuild_abi import REBUILD_DEVICE, REBUILD_HOST, REBUILD_SAME, RebuildInfo
 from .skin_abi import SKIN_DUAL_QUATERNION, SKIN_INFLUENCES, SKIN_LINEAR, SkinInfo  # noqa: F401
 # mcpt_set_vertex_morph's and mcpt_get_morph_info's structs and the flattening of a target list; tests/test_morph.py holds the layouts to the header
 from .morph_abi import MORPH_MAX_TARGETS, MorphInfo, MorphTargets, flatten_targets, targets_struct  # noqa: F401
+# mcpt_set_vertex_keyframes' options, mcpt_get_keyframe_info's struct and the interpolation and wrap constants; tests/test_keyframes.py holds the layouts to the header
+from .keyframe_abi import KEYFRAMES_CATMULL_ROM, KEYFRAMES_CLAMP, KEYFRAMES_LINEAR, KEYFRAMES_LOOP, KEYFRAMES_MAX, KeyframeInfo, KeyframeOpts  # noqa: F401
 # mcpt_set_auto_normals' and mcpt_get_normals_info's structs and the mask of the normals a set of faces uses; tests/test_normals.py holds the layouts to the header
 from .normals_abi import NORMALS_AREA, NORMALS_OFF, NormalsInfo, NormalsOpts, normal_mask_from_faces  # noqa: F401
 
@@ -297,6 +299,10 @@ def load_library() -> C.CDLL:
         "mcpt_update_morph_reproject": [vp, vp, C.c_uint32, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
         "mcpt_get_morph_info": [vp, P(MorphInfo)],
         "mcpt_probe_vertices": [vp, vp, vp],
+        "mcpt_set_vertex_keyframes": [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, P(KeyframeOpts)],
+        "mcpt_update_keyframes": [vp, C.c_double],
+        "mcpt_update_keyframes_reproject": [vp, C.c_double, P(CameraC), P(ReprojectOpts)],
+        "mcpt_get_keyframe_info": [vp, P(KeyframeInfo)],
         "mcpt_set_auto_normals": [vp, vp, C.c_uint32, P(NormalsOpts)],
         "mcpt_update_normals": [vp],
         "mcpt_get_normals_info": [vp, P(NormalsInfo)],
@@ -331,6 +337,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_vertex_skin", "mcpt_update_skin", "mcpt_update_skin_reproject", "mcpt_get_skin_info",
     "mcpt_set_skin_mode", "mcpt_get_skin_mode",
     "mcpt_set_vertex_morph", "mcpt_update_morph", "mcpt_update_morph_reproject", "mcpt_get_morph_info", "mcpt_probe_vertices",
+    "mcpt_set_vertex_keyframes", "mcpt_update_keyframes", "mcpt_update_keyframes_reproject", "mcpt_get_keyframe_info",
     "mcpt_set_auto_normals", "mcpt_update_normals", "mcpt_get_normals_info",
     "mcpt_rebuild_trees", "mcpt_get_rebuild_info",
 ]
@@ -671,6 +678,37 @@ class Renderer:
     def morph_info(self) -> MorphInfo:
         i = MorphInfo()
         self._check(self.lib.mcpt_get_morph_info(self.ctx, C.byref(i)))
+        return i
+
+    # ---- baked vertex animation: keyframes played by time
+    def set_vertex_keyframes(self, vertex_frames, normal_frames=None, start_time=0.0, frame_time=1.0, interpolation=KEYFRAMES_LINEAR, wrap=KEYFRAMES_CLAMP):
+        """The keyframes of a baked animation, uploaded once: vertex_frames (n_frames, n_vertex, 3), normal_frames None or (n_frames, n_normal, 3)
+        (None: every update writes the normals the scene has now); frame k lies at start_time + k * frame_time.  interpolation: KEYFRAMES_LINEAR
+        or KEYFRAMES_CATMULL_ROM; wrap: KEYFRAMES_CLAMP or KEYFRAMES_LOOP.  Independent of groups, skin and morph.  Needs FLAG_DYNAMIC.
+        Synchronous."""
+        v = np.ascontiguousarray(vertex_frames, np.float64)
+        n = None if normal_frames is None else np.ascontiguousarray(normal_frames, np.float64)
+        if v.ndim != 3 or v.shape[2] != 3 or (n is not None and (n.ndim != 3 or n.shape[2] != 3 or n.shape[0] != v.shape[0])):
+            raise ValueError("need (n_frames, n, 3) arrays with as many normal frames as vertex frames")
+        o = KeyframeOpts()
+        o.struct_size = C.sizeof(KeyframeOpts); o.interpolation = int(interpolation); o.wrap = int(wrap)
+        o.start_time = float(start_time); o.frame_time = float(frame_time)
+        self._check(self.lib.mcpt_set_vertex_keyframes(self.ctx, _ptr(v), v.shape[1], _ptr(n), self.holder.desc.n_normal if n is None else n.shape[1],
+                                                       v.shape[0], C.byref(o)))
+
+    def update_keyframes(self, time):
+        """The scene at `time` of the keyframes' clock: every vertex and normal interpolated on the device from 2 or 4 frames (on a keyframe:
+        that frame, bit for bit), then update_vertices' refit: only the time crosses the bus.  Asynchronous; the caller clears the film."""
+        self._check(self.lib.mcpt_update_keyframes(self.ctx, float(time)))
+
+    def update_keyframes_reproject(self, time, camera=None, **opts):
+        """update_keyframes that carries the film over, as update_vertices_reproject does; opts: reproject_camera's."""
+        c, o = _camera_and_opts(camera, opts)
+        self._check(self.lib.mcpt_update_keyframes_reproject(self.ctx, float(time), c, o))
+
+    def keyframe_info(self) -> KeyframeInfo:
+        i = KeyframeInfo()
+        self._check(self.lib.mcpt_get_keyframe_info(self.ctx, C.byref(i)))
         return i
 
     def vertices(self):

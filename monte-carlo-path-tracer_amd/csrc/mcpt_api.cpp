@@ -14,6 +14,7 @@
 #include "transform.h"
 #include "skin.h"
 #include "morph.h"
+#include "keyframes.h"
 #include "normals.h"
 #include "reproject.h"
 #include "materials.h"
@@ -299,6 +300,32 @@ struct mcpt_ctx {
             return src.tmp.vtx.p ? ensure_scratch(c) : MCPT_OK;                   // (scratch: its contents are not carried)
         }
     } mo;
+    // Keyframe playback (keyframes.hip), allocated by mcpt_set_vertex_keyframes: the vertex frames and, when the caller gave them,
+    // the normal frames -- n_frames arrays of kf_stride() doubles each -- and the pose rf_capture_rest took at set-up, of which `rest.nrm` is what
+    // every update writes when there are no normal frames.  Nothing is staged per update: the time becomes kernel arguments.  On the host the
+    // options and what the last update played (mcpt_keyframe_info).
+    struct Keyframes {
+        RestPose rest; DevBuf<double> vframes, nframes; Stopwatch watch;
+        uint32_t n_frames = 0, interpolation = 0, wrap = 0, updates = 0, last_frame = 0; double start_time = 0.0, frame_time = 1.0, last_u = 0.0, last_time = 0.0;
+        bool normal_frames() const { return nframes.bytes != 0; }
+        uint64_t device_bytes() const { return rest.vtx.bytes + rest.nrm.bytes + vframes.bytes + nframes.bytes; }
+        mcpt_status alloc(mcpt_ctx* c, uint32_t n, bool normals) {
+            uint64_t* tally = &c->info.device_bytes;
+            DevBuf<double> none;                                                 // (a set without normal frames replaces one that had them)
+            HIP_TRY(alloc_all(Want(rest.vtx, c->rf_vtx.count(), tally), Want(rest.nrm, c->rf_nrm.count(), tally), Want(vframes, n * kf_stride(c->rf_n_vertex), tally),
+                              Want(nframes, n * kf_stride(c->rf_n_normal), tally, normals), Want(watch, 1, nullptr, !watch.ev0)));
+            if (!normals) nframes = std::move(none);
+            n_frames = n;
+            return MCPT_OK;
+        }
+        template <class Copy> mcpt_status clone_from(mcpt_ctx* c, const Keyframes& src, Copy copy) {    // the frames, the rest normals and the options
+            if (!src.n_frames) return MCPT_OK;
+            const mcpt_status st = alloc(c, src.n_frames, src.normal_frames()); if (st != MCPT_OK) return st;
+            interpolation = src.interpolation; wrap = src.wrap; start_time = src.start_time; frame_time = src.frame_time;
+            HIP_TRY(copy(rest.vtx, src.rest.vtx)); HIP_TRY(copy(rest.nrm, src.rest.nrm)); HIP_TRY(copy(vframes, src.vframes)); HIP_TRY(copy(nframes, src.nframes));
+            return MCPT_OK;
+        }
+    } kf;
     // Automatic normals (normals.hip), allocated by mcpt_set_auto_normals: per normal record its list offset (rf_n_normal + 1) and
     // the 16-byte entries, one per face that names the record.  The lists follow the description's face order, not the leaf order: a rebuild
     // keeps them, a clone carries them.  mode == MCPT_NORMALS_OFF: nothing is allocated, no update runs the pass.
@@ -591,7 +618,8 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     auto copy = [&](auto& dst, const auto& from) { return from.bytes ? hipMemcpyPeer(dst.p, c->device, from.p, src->device, from.bytes) : hipSuccess; };
     HIP_TRY(copy(c->rf_idx, src->rf_idx)); HIP_TRY(copy(c->rf_bin_order, src->rf_bin_order)); HIP_TRY(copy(c->rf_vtx, src->rf_vtx)); HIP_TRY(copy(c->rf_nrm, src->rf_nrm));
     if ((st = c->xf.clone_from(c, src->xf, copy)) != MCPT_OK || (st = c->sk.clone_from(c, src->sk, copy)) != MCPT_OK ||
-        (st = c->mo.clone_from(c, src->mo, copy)) != MCPT_OK || (st = c->nr.clone_from(c, src->nr, copy)) != MCPT_OK) return st;
+        (st = c->mo.clone_from(c, src->mo, copy)) != MCPT_OK || (st = c->kf.clone_from(c, src->kf, copy)) != MCPT_OK ||
+        (st = c->nr.clone_from(c, src->nr, copy)) != MCPT_OK) return st;
     HIP_TRY(hipDeviceSynchronize());
     return MCPT_OK;
 }
@@ -1405,15 +1433,25 @@ static mcpt_status mo_check_update(const mcpt_ctx* ctx, const double* weight, ui
     if (!(reach <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "a vertex could leave |coordinate| <= 1e18 (conservative bound)");
     return bones ? sk_check_update(ctx, bones, n_bones, fn, &reach) : MCPT_OK;
 }
+// mcpt_update_keyframes' rules (§22), host only: set-up has bounded every frame and the reach of every blend, so only the time is judged.
+static mcpt_status kf_check_update(const mcpt_ctx* ctx, double time, const char* fn) {
+    const std::string who = std::string(fn) + ": ";
+    if (!std::isfinite(time)) return fail(MCPT_ERR_INVALID_ARG, who + "the time is not finite");
+    if (!ctx->kf.n_frames) return fail(MCPT_ERR_INVALID_ARG, who + "no keyframes are set (mcpt_set_vertex_keyframes)");
+    return MCPT_OK;
+}
 // A scene update and where its new vertices come from: the caller's arrays (rf_check_update), one matrix per group (xf_check_update), one per
-// bone (sk_check_update), one weight per morph target alone or in front of the bones (mo_check_update).  None (§20, mcpt_update_normals):
+// bone (sk_check_update), one weight per morph target alone or in front of the bones (mo_check_update), the time of the keyframes' clock
+// (kf_check_update).  None (§20, mcpt_update_normals):
 // nothing is staged and no vertex moves; the normals pass and the refit run on the arrays as they are.
 struct RfUpdate {
-    enum class Source { Arrays, Groups, Skin, Morph, MorphSkin, None } source = Source::None;
+    enum class Source { Arrays, Groups, Skin, Morph, MorphSkin, Keyframes, None } source = Source::None;
     const double* vertex = nullptr; const double* normal = nullptr; uint32_t n_vertex = 0, n_normal = 0;    // Arrays
     const double* m3x4 = nullptr; uint32_t n_m3x4 = 0;                                                      // Groups: per group; Skin, MorphSkin: per bone
     const double* weight = nullptr; uint32_t n_weight = 0;                                                  // Morph, MorphSkin: per target
+    double time = 0.0;                                                                                      // Keyframes
     static RfUpdate none() { return RfUpdate(); }
+    static RfUpdate keyframes(double t) { RfUpdate u; u.source = Source::Keyframes; u.time = t; return u; }
     static RfUpdate arrays(const double* v, uint32_t nv, const double* n, uint32_t nn) {
         RfUpdate u; u.source = Source::Arrays; u.vertex = v; u.n_vertex = nv; u.normal = n; u.n_normal = nn; return u;
     }
@@ -1500,9 +1538,29 @@ static mcpt_status mo_enqueue(mcpt_ctx* ctx, const RfUpdate& u, hipStream_t s) {
     ctx->mo.updates++;
     return MCPT_OK;
 }
+// Keyframes stage nothing: the time becomes a segment, tap indices and weights on the host, and those are kernel arguments.  On a keyframe
+// (u == 0) the frame is copied as it is; without normal frames every call writes the normals captured at set-up.
+static mcpt_status kf_enqueue(mcpt_ctx* ctx, const RfUpdate& u, hipStream_t s) {
+    mcpt_ctx::Keyframes& kf = ctx->kf;
+    KfBlend b = kf_segment(u.time, kf.start_time, kf.frame_time, kf.n_frames, kf.interpolation, kf.wrap);
+    kf_weights(b.u, kf.interpolation, b.w);
+    const size_t sv = kf_stride(ctx->rf_n_vertex), sn = kf_stride(ctx->rf_n_normal);
+    HIP_TRY(kf.watch.begin(s));
+    if (b.u == 0.0) {
+        if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->rf_vtx.p, kf.vframes.p + sv * b.k, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, s));
+    } else HIP_TRY(launch_kf_vertices(kf.vframes.p, sv, b, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
+    if (!kf.normal_frames() || b.u == 0.0) {
+        const double* from = kf.normal_frames() ? kf.nframes.p + sn * b.k : kf.rest.nrm.p;
+        if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->rf_nrm.p, from, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, s));
+    } else HIP_TRY(launch_kf_normals(kf.nframes.p, sn, b, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+    HIP_TRY(kf.watch.end(s));
+    kf.updates++; kf.last_frame = b.k; kf.last_u = b.u; kf.last_time = u.time;
+    return MCPT_OK;
+}
 // Does the refit read rf_nrm, i.e. are there new normals?  `upload_normal`: the arrays' route got normals from the caller.
 //     source                            auto normals    the refit reads rf_nrm
-//     Groups, Skin, Morph, MorphSkin    off or on       nd != 0   (a deformer rewrites rf_nrm whenever the scene has normals)
+//     Groups, Skin, Morph, MorphSkin,
+//     Keyframes                         off or on       nd != 0   (a deformer rewrites rf_nrm whenever the scene has normals)
 //     Arrays, None                      on              nd != 0   (so does the normals pass, §20)
 //     Arrays, None                      off             upload_normal   (None uploads nothing: no; mcpt_update_normals refuses it before)
 static bool rf_reads_normals(Source source, size_t nd, bool auto_normals, bool upload_normal) {
@@ -1520,6 +1578,7 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     case Source::Groups: st = xf_stage(ctx, u); break;
     case Source::Skin: st = sk_stage(ctx, u.m3x4); break;
     case Source::Morph: case Source::MorphSkin: st = mo_stage(ctx, u); break;
+    case Source::Keyframes: break;                                               // §22: the time travels as kernel arguments
     case Source::None: break;                                                    // §20, mcpt_update_normals: nothing to stage ...
     }
     if (st != MCPT_OK) return st;
@@ -1533,6 +1592,7 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     case Source::Groups: st = xf_enqueue(ctx, s); break;
     case Source::Skin: st = sk_enqueue(ctx, s); break;
     case Source::Morph: case Source::MorphSkin: st = mo_enqueue(ctx, u, s); break;
+    case Source::Keyframes: st = kf_enqueue(ctx, u, s); break;
     case Source::None: break;                                                    // ... and nothing to write
     }
     if (st != MCPT_OK) return st;
@@ -1724,6 +1784,71 @@ mcpt_status mcpt_get_morph_info(mcpt_ctx* ctx, mcpt_morph_info* out) {
     const mcpt_status st = info_begin(ctx, out, ctx ? &ctx->mo.watch : nullptr); if (st != MCPT_OK) return st;
     out->n_targets = ctx->mo.n_targets; out->updates = ctx->mo.updates; out->last_ms = ctx->mo.watch.last_ms;
     out->vertex_entries = ctx->mo.ventry.count(); out->normal_entries = ctx->mo.nentry.count();
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ keyframe playback
+mcpt_status mcpt_set_vertex_keyframes(mcpt_ctx* ctx, const double* vertex_frames, uint32_t n_vertex, const double* normal_frames, uint32_t n_normal, uint32_t n_frames,
+                                      const mcpt_keyframe_opts* opts) {
+    const char* const fn = "mcpt_set_vertex_keyframes";
+    const std::string who = std::string(fn) + ": ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if ((st = require_dynamic(ctx, who)) != MCPT_OK) return st;
+    if (!vertex_frames) return fail(MCPT_ERR_INVALID_ARG, who + "null vertex frames");
+    if (n_vertex != ctx->rf_n_vertex || n_normal != ctx->rf_n_normal) return fail(MCPT_ERR_INVALID_ARG, who + "n_vertex / n_normal differ from the scene's");
+    mcpt_keyframe_opts o;
+    st = read_opts(opts, o, fn, "mcpt_keyframe_opts"); if (st != MCPT_OK) return st;
+    if (!opts) o.frame_time = 1.0;                                               // (linear, clamp and start 0 are the zeros read_opts left)
+    if (o.interpolation != MCPT_KEYFRAMES_LINEAR && o.interpolation != MCPT_KEYFRAMES_CATMULL_ROM) return fail(MCPT_ERR_INVALID_ARG, who + "unknown interpolation");
+    if (o.wrap != MCPT_KEYFRAMES_CLAMP && o.wrap != MCPT_KEYFRAMES_LOOP) return fail(MCPT_ERR_INVALID_ARG, who + "unknown wrap");
+    if (n_frames < 2 || n_frames > MCPT_KEYFRAMES_MAX) return fail(MCPT_ERR_INVALID_ARG, who + "n_frames must be in [2, 65536]");
+    if (!std::isfinite(o.start_time)) return fail(MCPT_ERR_INVALID_ARG, who + "start_time is not finite");
+    if (!(std::isfinite(o.frame_time) && o.frame_time > 0.0)) return fail(MCPT_ERR_INVALID_ARG, who + "frame_time is not finite or not > 0");
+    double radius = 0.0;                                                         // R: over the vertices a face uses, all frames
+    for (uint32_t k = 0; k < n_frames; k++)
+        for (uint32_t v = 0; v < n_vertex; v++) {
+            if (!ctx->rf_used_vertex[v]) continue;
+            const double* x = vertex_frames + 3 * (size_t(k) * n_vertex + v);
+            const double far = std::max({std::fabs(x[0]), std::fabs(x[1]), std::fabs(x[2])});
+            if (!(std::fabs(x[0]) <= MCPT_MAX_COORD && std::fabs(x[1]) <= MCPT_MAX_COORD && std::fabs(x[2]) <= MCPT_MAX_COORD))
+                return fail(MCPT_ERR_INVALID_ARG, who + "frame " + std::to_string(k) + ", vertex " + std::to_string(v) + ": coordinate is not finite or exceeds 1e18");
+            radius = std::max(radius, far);
+        }
+    for (size_t i = 0; normal_frames && i < 3 * size_t(n_frames) * n_normal; i++)
+        if (!std::isfinite(normal_frames[i]))
+            return fail(MCPT_ERR_INVALID_ARG, who + "frame " + std::to_string(i / (3 * size_t(n_normal))) + ", normal " + std::to_string(i / 3 % n_normal) + ": a component is not finite");
+    if (!(kf_reach(radius, o.interpolation) <= MCPT_MAX_COORD)) return fail(MCPT_ERR_INVALID_ARG, who + "an interpolated vertex could leave |coordinate| <= 1e18 (conservative bound)");
+    // the frames at their device stride (the padding is 0), one copy per array
+    auto padded = [&](const double* frames, uint32_t n) {
+        const size_t stride = kf_stride(n), row = 3 * size_t(n);
+        std::vector<double> out(stride * n_frames, 0.0);
+        for (uint32_t k = 0; k < n_frames; k++) std::copy_n(frames + row * k, row, out.begin() + stride * k);
+        return out;
+    };
+    const bool normals = normal_frames && n_normal;
+    const std::vector<double> vf = padded(vertex_frames, n_vertex), nf = normals ? padded(normal_frames, n_normal) : std::vector<double>();
+    mcpt_ctx::Keyframes& kf = ctx->kf;
+    st = rf_capture_rest(ctx, kf.rest, [&] { return kf.alloc(ctx, n_frames, normals); },
+        [&](Scratch& s) -> mcpt_status {
+            HIP_TRY(s.put(kf.vframes.p, vf.data(), vf.size())); HIP_TRY(s.put(kf.nframes.p, nf.data(), nf.size()));
+            return MCPT_OK; },
+        [](uint32_t, double) {});                                                // (R comes from the frames, not from the pose at set-up)
+    if (st != MCPT_OK) return st;
+    kf.interpolation = o.interpolation; kf.wrap = o.wrap; kf.start_time = o.start_time; kf.frame_time = o.frame_time;
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_update_keyframes(mcpt_ctx* ctx, double time) {
+    return rf_update(ctx, RfUpdate::keyframes(time), "mcpt_update_keyframes", nullptr, nullptr, false);
+}
+
+mcpt_status mcpt_get_keyframe_info(mcpt_ctx* ctx, mcpt_keyframe_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if ((st = require_dynamic(ctx, "mcpt_get_keyframe_info: ")) != MCPT_OK) return st;
+    st = info_begin(ctx, out, &ctx->kf.watch); if (st != MCPT_OK) return st;
+    const mcpt_ctx::Keyframes& kf = ctx->kf;
+    out->n_frames = kf.n_frames; out->interpolation = kf.interpolation; out->wrap = kf.wrap; out->updates = kf.updates; out->last_frame = kf.last_frame;
+    out->last_u = kf.last_u; out->last_time = kf.last_time; out->last_ms = kf.watch.last_ms; out->device_bytes = kf.device_bytes();
     return MCPT_OK;
 }
 
@@ -2197,6 +2322,7 @@ static mcpt_status rf_update(mcpt_ctx* ctx, const RfUpdate& u, const char* fn, c
     case Source::Groups: st = xf_check_update(ctx, u.m3x4, u.n_m3x4, fn); break;
     case Source::Skin: st = sk_check_update(ctx, u.m3x4, u.n_m3x4, fn); break;
     case Source::Morph: case Source::MorphSkin: st = mo_check_update(ctx, u.weight, u.n_weight, u.m3x4, u.n_m3x4, fn); break;
+    case Source::Keyframes: st = kf_check_update(ctx, u.time, fn); break;
     case Source::None: break;                                                    // (mcpt_update_normals makes its own two checks)
     }
     if (st != MCPT_OK) return st;
@@ -2225,6 +2351,10 @@ mcpt_status mcpt_update_skin_reproject(mcpt_ctx* ctx, const double* m3x4, uint32
 mcpt_status mcpt_update_morph_reproject(mcpt_ctx* ctx, const double* weight, uint32_t n_targets, const double* bones_m3x4, uint32_t n_bones,
                                         const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
     return rf_update(ctx, RfUpdate::morph(weight, n_targets, bones_m3x4, n_bones), "mcpt_update_morph_reproject", cm, opts, true);
+}
+
+mcpt_status mcpt_update_keyframes_reproject(mcpt_ctx* ctx, double time, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
+    return rf_update(ctx, RfUpdate::keyframes(time), "mcpt_update_keyframes_reproject", cm, opts, true);
 }
 
 mcpt_status mcpt_probe_first_hits(mcpt_ctx* ctx, int32_t* out_face, float* out_uvt3) {

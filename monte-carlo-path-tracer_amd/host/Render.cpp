@@ -152,26 +152,31 @@ bool Render::update_morph_reproject(Scene& scene, const std::vector<double>& wei
 bool Render::update_morph_reproject(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices, const CameraInfo& camera, float max_history) {
     return update_reproject(scene, nullptr, &bone_matrices, true, &weights, &camera, max_history);
 }
-// The geometry comes from `m` (its arrays), from `matrices` (one 3x4 per group, §16, or per bone, §18) or from `weights` (one per morph target,
-// §19, with or without the bones' matrices): the rest is the same.
+bool Render::update_keyframes_reproject(Scene& scene, double time, float max_history) { return update_reproject(scene, nullptr, nullptr, false, nullptr, nullptr, max_history, &time); }
+bool Render::update_keyframes_reproject(Scene& scene, double time, const CameraInfo& camera, float max_history) {
+    return update_reproject(scene, nullptr, nullptr, false, nullptr, &camera, max_history, &time);
+}
+// The geometry comes from `m` (its arrays), from `matrices` (one 3x4 per group, §16, or per bone, §18), from `weights` (one per morph target,
+// §19, with or without the bones' matrices) or from `time` (the keyframes' clock, §22): the rest is the same.
 bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>* matrices, bool bones, const std::vector<double>* weights, const CameraInfo* camera,
-                              float max_history) {
+                              float max_history, const double* time) {
     if (!ctx) return false;
-    const char* const who = m ? "update_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject";
+    const char* const who = m ? "update_reproject" : time ? "update_keyframes_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject";
     if (!m && matrices && (matrices->size() % 12 || matrices->empty())) { std::cerr << "Error: Render::" << who << ": need 12 doubles per " << (bones ? "bone" : "group") << std::endl; return false; }
     bool ok = false;
     const bool upload = film_to_device(scene, who, ok);
     if (!ok) return false;
     mcpt_camera k; if (camera) k = to_camera(*camera);
     mcpt_reproject_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.feature_spp = 4; o.feature_seed = seed; o.max_history = max_history;
-    const mcpt_status st = weights ? mcpt_update_morph_reproject(ctx, weights->data(), uint32_t(weights->size()), matrices ? matrices->data() : nullptr,
+    const mcpt_status st = time ? mcpt_update_keyframes_reproject(ctx, *time, camera ? &k : nullptr, &o)
+                       : weights ? mcpt_update_morph_reproject(ctx, weights->data(), uint32_t(weights->size()), matrices ? matrices->data() : nullptr,
                                                                  matrices ? uint32_t(matrices->size() / 12) : 0u, camera ? &k : nullptr, &o)
                          : m ? mcpt_update_vertices_reproject(ctx, reinterpret_cast<const double*>(m->vertex.data()), uint32_t(m->vertex.size()),
                                                               reinterpret_cast<const double*>(m->normal.data()), uint32_t(m->normal.size()), camera ? &k : nullptr, &o)
                      : bones ? mcpt_update_skin_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o)
                              : mcpt_update_transforms_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o);
     if (st != MCPT_OK) {
-        std::cerr << "Error: mcpt_" << (m ? "update_vertices_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
+        std::cerr << "Error: mcpt_" << (m ? "update_vertices_reproject" : time ? "update_keyframes_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
         if (upload && mcpt_clear_accum(ctx) != MCPT_OK) std::cerr << "Error: mcpt_clear_accum: " << mcpt_last_error() << std::endl;   // the Scene still holds them
         return false;
     }
@@ -302,6 +307,41 @@ bool Render::update_morph(Scene& scene, const std::vector<double>& weights, cons
     if (mcpt_update_morph(ctx, weights.data(), uint32_t(weights.size()), bone_matrices.data(), uint32_t(bone_matrices.size() / 12)) != MCPT_OK) {
         std::cerr << "Error: mcpt_update_morph: " << mcpt_last_error() << std::endl; return false;
     }
+    return restart(scene);
+}
+bool Render::set_keyframes(Scene& scene, Model& m, const std::vector<Model*>& frames, double start_time, double frame_time, uint32_t interpolation, uint32_t wrap) {
+    std::vector<std::vector<dvec3>> vf, nf;
+    for (const Model* f : frames) {
+        if (!f) { std::cerr << "Error: Render::set_keyframes: a null frame" << std::endl; return false; }
+        vf.push_back(f->vertex); nf.push_back(f->normal);
+    }
+    return set_keyframes(scene, m, vf, nf, start_time, frame_time, interpolation, wrap);
+}
+bool Render::set_keyframes(Scene&, Model& m, const std::vector<std::vector<dvec3>>& vertex_frames, const std::vector<std::vector<dvec3>>& normal_frames,
+                           double start_time, double frame_time, uint32_t interpolation, uint32_t wrap) {
+    if (!ctx) return false;
+    const size_t nv = m.vertex.size(), nn = m.normal.size();
+    if (!normal_frames.empty() && normal_frames.size() != vertex_frames.size()) { std::cerr << "Error: Render::set_keyframes: need as many normal frames as vertex frames (or none)" << std::endl; return false; }
+    std::vector<double> v, n;                                                // frame after frame, as mcpt_set_vertex_keyframes reads them
+    for (size_t k = 0; k < vertex_frames.size(); k++) {
+        if (vertex_frames[k].size() != nv || (!normal_frames.empty() && normal_frames[k].size() != nn)) {
+            std::cerr << "Error: Render::set_keyframes: frame " << k << " has other vertex or normal counts than the scene" << std::endl; return false;
+        }
+        const double* p = reinterpret_cast<const double*>(vertex_frames[k].data());
+        v.insert(v.end(), p, p + 3 * nv);
+        if (normal_frames.empty()) continue;
+        const double* q = reinterpret_cast<const double*>(normal_frames[k].data());
+        n.insert(n.end(), q, q + 3 * nn);
+    }
+    mcpt_keyframe_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.interpolation = interpolation; o.wrap = wrap; o.start_time = start_time; o.frame_time = frame_time;
+    if (mcpt_set_vertex_keyframes(ctx, v.empty() ? nullptr : v.data(), uint32_t(nv), normal_frames.empty() ? nullptr : n.data(), uint32_t(nn), uint32_t(vertex_frames.size()), &o) != MCPT_OK) {
+        std::cerr << "Error: mcpt_set_vertex_keyframes: " << mcpt_last_error() << std::endl; return false;
+    }
+    return true;
+}
+bool Render::update_keyframes(Scene& scene, double time) {
+    if (!ctx) return false;
+    if (mcpt_update_keyframes(ctx, time) != MCPT_OK) { std::cerr << "Error: mcpt_update_keyframes: " << mcpt_last_error() << std::endl; return false; }
     return restart(scene);
 }
 bool Render::set_auto_normals(Scene&, Model& m, const std::vector<uint8_t>& face_mask) {

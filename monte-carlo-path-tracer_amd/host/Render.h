@@ -92,6 +92,19 @@ public:
     bool update_morph_reproject(Scene& scene, const std::vector<double>& weights, const CameraInfo& camera, float max_history = 0);
     bool update_morph_reproject(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices, float max_history = 0);
     bool update_morph_reproject(Scene& scene, const std::vector<double>& weights, const std::vector<double>& bone_matrices, const CameraInfo& camera, float max_history = 0);
+    // Baked vertex animation.  set_keyframes: the keyframes of `m_model`, the Model this Render was made from (MCPT_FLAG_DYNAMIC),
+    // uploaded once -- one Model per frame (an OBJ sequence; its vertices and normals are taken, the counts must be m_model's), or one vertex array
+    // per frame and, optionally, as many normal arrays (none: every update writes the normals the scene has now).  Frame k lies at
+    // start_time + k * frame_time; interpolation MCPT_KEYFRAMES_LINEAR / _CATMULL_ROM, wrap MCPT_KEYFRAMES_CLAMP / _LOOP.  The film is not touched.
+    // update_keyframes: the scene at `time`, interpolated on the device (mcpt_update_keyframes) -- only the time crosses the bus.  Starts the
+    // picture again like update(); update_keyframes_reproject carries it over like update_reproject.  false (Render and Scene unchanged) on failure.
+    bool set_keyframes(Scene& scene, Model& m_model, const std::vector<Model*>& frames, double start_time = 0.0, double frame_time = 1.0,
+                       uint32_t interpolation = MCPT_KEYFRAMES_LINEAR, uint32_t wrap = MCPT_KEYFRAMES_CLAMP);
+    bool set_keyframes(Scene& scene, Model& m_model, const std::vector<std::vector<dvec3>>& vertex_frames, const std::vector<std::vector<dvec3>>& normal_frames,
+                       double start_time = 0.0, double frame_time = 1.0, uint32_t interpolation = MCPT_KEYFRAMES_LINEAR, uint32_t wrap = MCPT_KEYFRAMES_CLAMP);
+    bool update_keyframes(Scene& scene, double time);
+    bool update_keyframes_reproject(Scene& scene, double time, float max_history = 0);
+    bool update_keyframes_reproject(Scene& scene, double time, const CameraInfo& camera, float max_history = 0);
     // Smooth normals recomputed on the device after every update.  set_auto_normals: one flag per face of `m_model`, the Model this
     // Render was made from (MCPT_FLAG_DYNAMIC); the normal records that the flagged faces name (an empty face_mask: all records) are from now
     // on recomputed from the deformed faces by every update*() call -- area-weighted, overriding what the call itself wrote for them, Model::normal
@@ -122,7 +135,7 @@ private:
     bool restart(Scene& scene);
     bool film_to_device(Scene& scene, const char* who, bool& ok);
     bool update_reproject(Scene& scene, Model* m_model, const std::vector<double>* matrices, bool bones, const std::vector<double>* weights, const CameraInfo* camera,
-                          float max_history);
+                          float max_history, const double* time = nullptr);
 };
 // Fills an mcpt_scene_desc that points INTO `m` (and into the two scratch vectors); valid while all three live.
 void model_to_desc(Model& m, std::vector<mcpt_material>& mats, std::vector<mcpt_texture>& texs, mcpt_scene_desc& d);

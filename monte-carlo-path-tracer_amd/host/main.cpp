@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cmath>
 #include <algorithm>
+#include <cctype>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -45,10 +46,16 @@ static void usage() {
                  "                                        vertices (one morph target on the device, delta = vertex - centroid, weight AMOUNT sin(2 pi k / N) in frame k:\n"
                  "                                        a uniform scaling, so the normals stay); combines with --bend (morph, then skin, one call per frame);\n"
                  "                                        honours --reproject; not with --wobble or --spin\n"
-                 "                          [--auto-normals]   with --turntable and --wobble, --bend or --swell: the smooth normals are recomputed on the device after\n"
-                 "                                        every frame's update, area-weighted, from the deformed faces -- all normals with --wobble, otherwise those\n"
-                 "                                        of the named material's faces (honours --reproject and --rebuild-above)\n"
-                 "                          [--rebuild-above R]   with --turntable and --wobble, --spin, --bend or --swell: after a frame's update the trees are built anew\n"
+                 "                          [--sequence PATTERN COUNT [--slowdown S] [--smooth]]   with --turntable: baked vertex animation from an OBJ sequence.  PATTERN\n"
+                 "                                        holds one printf integer conversion (cloth_%04d.obj); frames 0 .. COUNT - 1 are loaded, each with the scene's\n"
+                 "                                        vertex and normal counts and its faces, and uploaded once as keyframes one time unit apart (DESIGN.md 22);\n"
+                 "                                        turntable frame j plays time j / S (S = 1 by default), the in-between frames are interpolated on the device,\n"
+                 "                                        linearly or with --smooth as a Catmull-Rom spline; past the last file the last frame stays; honours\n"
+                 "                                        --reproject; not with --wobble, --spin, --bend or --swell\n"
+                 "                          [--auto-normals]   with --turntable and --wobble, --bend, --swell or --sequence: the smooth normals are recomputed on the device\n"
+                 "                                        after every frame's update, area-weighted, from the deformed faces -- all normals with --wobble and --sequence,\n"
+                 "                                        otherwise those of the named material's faces (honours --reproject and --rebuild-above)\n"
+                 "                          [--rebuild-above R]   with --turntable and --wobble, --spin, --bend, --swell or --sequence: after a frame's update the trees are built anew\n"
                  "                                        (mcpt_rebuild_trees, film kept) when wide_area_ratio exceeds R; prints frame, ratio and cost per rebuild\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
@@ -82,6 +89,7 @@ int main(int argc, char** argv) {
     std::string spin, bend, swell; double bend_deg = 0.0, swell_a = 0.0;
     bool rebuild = false; double rebuild_above = 0.0;
     bool auto_normals = false, dual_quat = false;
+    std::string sequence; int sequence_n = 0; bool slowdown_set = false, smooth = false; double slowdown = 1.0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -106,6 +114,9 @@ int main(int argc, char** argv) {
         else if (a == "--bend") { bend = next(); bend_deg = std::atof(next()); }
         else if (a == "--dual-quat") dual_quat = true;
         else if (a == "--swell") { swell = next(); swell_a = std::atof(next()); }
+        else if (a == "--sequence") { sequence = next(); sequence_n = std::atoi(next()); }
+        else if (a == "--slowdown") { slowdown_set = true; slowdown = std::atof(next()); }
+        else if (a == "--smooth") smooth = true;
         else if (a == "--auto-normals") auto_normals = true;
         else if (a == "--rebuild-above") { rebuild = true; rebuild_above = std::atof(next()); }
         else { usage(); return 2; }
@@ -124,16 +135,45 @@ int main(int argc, char** argv) {
     if (!swell.empty() && (!turntable || wobble || !spin.empty() || !(std::fabs(swell_a) <= 1e6))) {
         std::cerr << "Error: --swell MTLNAME AMOUNT needs --turntable N, a finite AMOUNT and neither --wobble nor --spin (all three write the vertices)" << std::endl; return 2;
     }
-    if (rebuild && (!turntable || !(wobble || !spin.empty() || !bend.empty() || !swell.empty()) || !(rebuild_above >= 0.0))) {
-        std::cerr << "Error: --rebuild-above R needs --turntable N with --wobble, --spin, --bend or --swell, and R >= 0" << std::endl; return 2;
+    if ((slowdown_set || smooth) && sequence.empty()) { std::cerr << "Error: --slowdown S and --smooth need --sequence PATTERN COUNT (they choose how it is played)" << std::endl; return 2; }
+    if (!sequence.empty()) {
+        if (!turntable || wobble || !spin.empty() || !bend.empty() || !swell.empty()) {
+            std::cerr << "Error: --sequence PATTERN COUNT needs --turntable N and none of --wobble, --spin, --bend and --swell (all of them write the vertices)" << std::endl; return 2;
+        }
+        // exactly one conversion, %d with an optional zero flag and width: the pattern is handed to snprintf
+        const size_t at = sequence.find('%');
+        size_t end = at == std::string::npos ? at : at + 1;
+        while (end != std::string::npos && end < sequence.size() && std::isdigit(static_cast<unsigned char>(sequence[end]))) end++;
+        if (at == std::string::npos || end >= sequence.size() || sequence[end] != 'd' || end - at > 6 || sequence.find('%', end) != std::string::npos) {
+            std::cerr << "Error: --sequence: PATTERN needs exactly one integer conversion such as %04d" << std::endl; return 2;
+        }
+        if (sequence_n < 2 || sequence_n > MCPT_KEYFRAMES_MAX) { std::cerr << "Error: --sequence: COUNT must be in [2, 65536]" << std::endl; return 2; }
+        if (!(slowdown > 0.0 && slowdown <= 1e6)) { std::cerr << "Error: --sequence: --slowdown S needs a finite S > 0" << std::endl; return 2; }
     }
-    if (auto_normals && (!turntable || !(wobble || !bend.empty() || !swell.empty()))) {
-        std::cerr << "Error: --auto-normals needs --turntable N with --wobble, --bend or --swell (the updates whose normals it recomputes)" << std::endl; return 2;
+    if (rebuild && (!turntable || !(wobble || !spin.empty() || !bend.empty() || !swell.empty() || !sequence.empty()) || !(rebuild_above >= 0.0))) {
+        std::cerr << "Error: --rebuild-above R needs --turntable N with --wobble, --spin, --bend, --swell or --sequence, and R >= 0" << std::endl; return 2;
     }
-    if (wobble || !spin.empty() || !bend.empty() || !swell.empty()) flags |= MCPT_FLAG_DYNAMIC;
+    if (auto_normals && (!turntable || !(wobble || !bend.empty() || !swell.empty() || !sequence.empty()))) {
+        std::cerr << "Error: --auto-normals needs --turntable N with --wobble, --bend, --swell or --sequence (the updates whose normals it recomputes)" << std::endl; return 2;
+    }
+    if (wobble || !spin.empty() || !bend.empty() || !swell.empty() || !sequence.empty()) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
     std::cout << model.face.size() << " " << model.normal.size() << " " << model.vertex.size() << std::endl;   // main.cpp:14
+    // --sequence PATTERN COUNT: the frames' vertices and normals, checked against the scene before anything is created on a device
+    std::vector<std::vector<dvec3>> seq_vertex, seq_normal;
+    for (int j = 0; j < sequence_n && !sequence.empty(); j++) {
+        char path[4096];
+        if (std::snprintf(path, sizeof path, sequence.c_str(), j) >= int(sizeof path)) { std::cerr << "Error: --sequence: the path of frame " << j << " is too long" << std::endl; return 2; }
+        Model frame(path, ref_order);
+        if (!frame.ok) { std::cerr << "Error: --sequence: frame " << j << " (" << path << ") did not load" << std::endl; return 2; }
+        if (frame.vertex.size() != model.vertex.size() || frame.normal.size() != model.normal.size()) {
+            std::cerr << "Error: --sequence: frame " << j << " (" << path << ") has " << frame.vertex.size() << " vertices and " << frame.normal.size() << " normals, the scene "
+                      << model.vertex.size() << " and " << model.normal.size() << std::endl; return 2;
+        }
+        if (frame.face != model.face) { std::cerr << "Error: --sequence: frame " << j << " (" << path << ") has other faces than the scene (the topology must not change)" << std::endl; return 2; }
+        seq_vertex.push_back(frame.vertex); seq_normal.push_back(frame.normal);
+    }
     if (!dump_model.empty()) {   // host-only: everything Model(filename) parsed, as text (tests compare it with the reference's own parse)
         FILE* f = std::fopen(dump_model.c_str(), "w");
         if (!f) { std::cerr << "Error: cannot write " << dump_model << std::endl; return 1; }
@@ -275,11 +315,14 @@ int main(int argc, char** argv) {
             }
             if (!renders[0]->set_morph(scene, model, target)) return 1;
         }
-        // --auto-normals: every update below is followed by the normals pass -- over all normals with --wobble, which moves every
-        // vertex, otherwise over the normals of the faces of --bend's and --swell's materials
+        // --sequence PATTERN COUNT: the frames go to the device once, one time unit apart; past the last one the last frame stays
+        if (!sequence.empty() && !renders[0]->set_keyframes(scene, model, seq_vertex, seq_normal, 0.0, 1.0, smooth ? MCPT_KEYFRAMES_CATMULL_ROM : MCPT_KEYFRAMES_LINEAR,
+                                                            MCPT_KEYFRAMES_CLAMP)) return 1;
+        // --auto-normals: every update below is followed by the normals pass -- over all normals with --wobble and --sequence, which
+        // move every vertex, otherwise over the normals of the faces of --bend's and --swell's materials
         if (auto_normals) {
             std::vector<uint8_t> face_mask;                                  // empty: all
-            if (!wobble) {
+            if (!wobble && sequence.empty()) {
                 const int bend_mtl = bend.empty() ? -1 : model.material_index(bend), swell_mtl = swell.empty() ? -1 : model.material_index(swell);
                 face_mask.assign(model.face.size(), 0);
                 for (size_t i = 0; i < model.face.size(); i++) {
@@ -314,6 +357,10 @@ int main(int argc, char** argv) {
                 }
                 model.camerainfo = cam;
                 if (reproject ? !renders[0]->update_reproject(scene, model, cam, history) : !renders[0]->update(scene, model)) return 1;
+            } else if (!sequence.empty()) {                                  // --sequence: turntable frame j plays time j / S; only that number crosses the bus
+                const double time = double(f) / slowdown;
+                Render& r0 = *renders[0];
+                if (reproject && f > 0 ? !r0.update_keyframes_reproject(scene, time, cam, history) : !(r0.update_keyframes(scene, time) && r0.set_camera(scene, cam))) return 1;
             } else if (!spin.empty()) {                                      // Rodrigues as a matrix: R = cos a I + sin a [k]x + (1 - cos a) k k^T, about the pivot
                 const double R[3][3] = {{ca + k[0] * k[0] * (1.0 - ca), k[0] * k[1] * (1.0 - ca) - k[2] * sa, k[0] * k[2] * (1.0 - ca) + k[1] * sa},
                                         {k[1] * k[0] * (1.0 - ca) + k[2] * sa, ca + k[1] * k[1] * (1.0 - ca), k[1] * k[2] * (1.0 - ca) - k[0] * sa},
