@@ -209,18 +209,36 @@ mcpt_status mcpt_reset_counters(mcpt_ctx* ctx);
  * share of the spp, normal = sum of camera-facing shading normals / max(hits, 1), z = mean hit distance, 0 without hits).  They depend
  * on the scene, the camera, spp and seed only: clearing or writing the film keeps them; a clone starts without them.
  * mcpt_denoise filters a film of {sum rgb, count} records (NULL = the context film, which it never writes) into the context's
- * denoised film {r, g, b, 1} (count 0: {0, 0, 0, 0}) -- a mean, so mcpt_tonemap_buffer displays it as it is. */
+ * denoised film {r, g, b, 1} (count 0: {0, 0, 0, 0}) -- a mean, so mcpt_tonemap_buffer displays it as it is.
+ *
+ * Two opt-in flags (flags = 0 is the filter as it always was):
+ *  - MCPT_DENOISE_SPLIT_EMISSION keeps emitted light apart from reflected light.  The emission buffer E holds per pixel {sum of the radiance
+ *    of the first hits on emitters / spp, their share of the spp}, from the camera rays of the features the context holds (same spp, same
+ *    seed).  A valid pixel's mean c becomes max(c - E.rgb, 0) per channel before it is divided by the albedo; the filter works on that
+ *    reflected part and adds E.rgb back when it writes the pixel.  The subtraction is exact up to rounding when the film holds the feature
+ *    samples (same seed, samples 0 .. spp-1); otherwise E estimates the same expectation and the clamp at 0 absorbs the rest.
+ *    The first call with this flag allocates E (16 B per pixel, counted in device_bytes) and renders it for the features held; afterwards
+ *    every feature render of the context fills it in the same pass.  E is dropped with the features; a clone starts without the buffer.
+ *  - MCPT_DENOISE_CLAMP_FIREFLIES scales a valid pixel whose demodulated luminance l exceeds k times m, the largest unclamped l among the
+ *    valid pixels of its 3x3 neighbourhood, by k m / l before the filter (k = firefly_clamp); the variance that steers the luminance term
+ *    is taken over the clamped values.  A pixel without a valid neighbour is never clamped. */
+#define MCPT_DENOISE_SPLIT_EMISSION  0x1u
+#define MCPT_DENOISE_CLAMP_FIREFLIES 0x2u
+#define MCPT_DENOISE_DEFAULT_FIREFLY_CLAMP 4.0f
 typedef struct mcpt_denoise_opts {
     uint32_t struct_size;                           /* = sizeof(mcpt_denoise_opts) */
     uint32_t iterations;                            /* a-trous levels, 0 = default 5, max 10 */
     float sigma_color, sigma_normal, sigma_depth;   /* 0 = default (4, 128, 4) */
-    uint32_t reserved[3];
+    uint32_t flags;                                 /* MCPT_DENOISE_*; an unknown bit is MCPT_ERR_INVALID_ARG */
+    float firefly_clamp;                            /* k of the clamp: 0 = default (MCPT_DENOISE_DEFAULT_FIREFLY_CLAMP), else finite and >= 1 */
+    uint32_t reserved[1];
 } mcpt_denoise_opts;
 mcpt_status mcpt_render_features(mcpt_ctx* ctx, uint32_t spp, uint64_t seed);          /* 1 <= spp <= 64, asynchronous */
 mcpt_status mcpt_read_features(mcpt_ctx* ctx, float* out8);                            /* synchronises, then D2H: width*height*8 floats */
 mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_denoise_opts* opts);  /* NULL film = ctx film; NULL opts = defaults; asynchronous */
 mcpt_status mcpt_read_denoised(mcpt_ctx* ctx, float* rgba_host);                       /* synchronises, then D2H: width*height*4 floats */
 mcpt_status mcpt_denoised_device_ptr(mcpt_ctx* ctx, void** out_device_rgba);           /* the denoised film on the device (after a first mcpt_denoise) */
+mcpt_status mcpt_read_emission(mcpt_ctx* ctx, float* out4);                            /* synchronises, then D2H: width*height*4 floats; MCPT_ERR_INVALID_ARG when no emission is held */
 
 /* ---- adaptive sampling ------------------------------------------------------------------------------------------- */
 /* Samples go where the image is still noisy, per 8x8 tile.  During a call the samples go into two internal half films H and O (the first and

@@ -40,6 +40,8 @@ FLAG_COUNT_TRAVERSAL = 0x4
 FLAG_GPU_BVH_BUILD = 0x8
 FLAG_REFERENCE_TIE_ORDER = 0x10
 FLAG_DYNAMIC = 0x20
+DENOISE_SPLIT_EMISSION = 0x1          # mcpt_denoise_opts::flags
+DENOISE_CLAMP_FIREFLIES = 0x2
 
 
 class Texture(C.Structure):
@@ -99,7 +101,8 @@ class SceneInfo(C.Structure):
 
 class DenoiseOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
-                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 3)]
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32), ("firefly_clamp", C.c_float),
+                ("reserved", C.c_uint32 * 1)]
 
 
 class AdaptiveOpts(C.Structure):
@@ -265,6 +268,7 @@ def load_library() -> C.CDLL:
         "mcpt_denoise": [vp, vp, P(DenoiseOpts)],
         "mcpt_read_denoised": [vp, vp],
         "mcpt_denoised_device_ptr": [vp, P(vp)],
+        "mcpt_read_emission": [vp, vp],
         "mcpt_render_tile_list": [vp, C.c_uint32, C.c_uint64, C.c_uint32, vp, C.c_uint32],
         "mcpt_render_adaptive": [vp, C.c_uint64, C.c_uint32, P(AdaptiveOpts), P(AdaptiveStats)],
         "mcpt_read_tile_error": [vp, vp],
@@ -327,7 +331,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_get_counters", "mcpt_reset_counters", "mcpt_bind_accum", "mcpt_accum_device_ptr", "mcpt_set_stream",
     "mcpt_set_null_stream", "mcpt_probe_trace", "mcpt_probe_trace4", "mcpt_probe_cast_ray", "mcpt_probe_hit_shade", "mcpt_probe_bsdf", "mcpt_probe_sample_light",
     "mcpt_probe_paths", "mcpt_probe_rng", "mcpt_probe_texture",
-    "mcpt_render_features", "mcpt_read_features", "mcpt_denoise", "mcpt_read_denoised", "mcpt_denoised_device_ptr",
+    "mcpt_render_features", "mcpt_read_features", "mcpt_denoise", "mcpt_read_denoised", "mcpt_denoised_device_ptr", "mcpt_read_emission",
     "mcpt_render_tile_list", "mcpt_render_adaptive", "mcpt_read_tile_error", "mcpt_probe_tile_error",
     "mcpt_set_camera", "mcpt_update_vertices", "mcpt_get_update_info", "mcpt_probe_validate_trees",
     "mcpt_set_camera_reproject", "mcpt_get_reproject_info", "mcpt_probe_reproject",
@@ -883,14 +887,25 @@ class Renderer:
         self._check(self.lib.mcpt_read_features(self.ctx, _ptr(out)))
         return out
 
-    def denoise(self, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, device_ptr: Optional[int] = None) -> np.ndarray:
-        """A-trous filter of the context film (or of the device film at `device_ptr`): (h, w, 4) records {r, g, b, 1}."""
+    def denoise(self, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, device_ptr: Optional[int] = None,
+                split_emission=False, clamp_fireflies=False, firefly_clamp=0.0) -> np.ndarray:
+        """A-trous filter of the context film (or of the device film at `device_ptr`): (h, w, 4) records {r, g, b, 1}.  split_emission: emitted
+        light is kept apart from the reflected light the filter works on; clamp_fireflies: a pixel more than firefly_clamp times brighter than
+        its brightest neighbour is scaled down to that (0 = the default)."""
         o = DenoiseOpts()
         o.struct_size = C.sizeof(DenoiseOpts); o.iterations = iterations
         o.sigma_color = sigma_color; o.sigma_normal = sigma_normal; o.sigma_depth = sigma_depth
+        o.flags = (DENOISE_SPLIT_EMISSION if split_emission else 0) | (DENOISE_CLAMP_FIREFLIES if clamp_fireflies else 0)
+        o.firefly_clamp = firefly_clamp
         self._check(self.lib.mcpt_denoise(self.ctx, None if device_ptr is None else C.c_void_p(device_ptr), C.byref(o)))
         out = np.zeros((self.height, self.width, 4), np.float32)
         self._check(self.lib.mcpt_read_denoised(self.ctx, _ptr(out)))
+        return out
+
+    def emission(self) -> np.ndarray:
+        """(h, w, 4): emitted radiance rgb of the first hits / spp and their share of the spp, for the features held (after a split denoise)."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self.lib.mcpt_read_emission(self.ctx, _ptr(out)))
         return out
 
     def denoised_device_ptr(self) -> int:

@@ -191,6 +191,11 @@ struct mcpt_ctx {
     // two ping-pong {irr, var} buffers and the denoised film (1 float4 / pixel each), allocated by the first mcpt_denoise
     DevBuf<float4> dn_feat, dn_guide, dn_iv0, dn_iv1, dn_out;
     bool dn_have_features = false, dn_have_out = false;
+    // The emission buffer of MCPT_DENOISE_SPLIT_EMISSION (1 float4 / pixel), allocated by the first mcpt_denoise that asks for the split; from
+    // then on every feature render fills it in the same traversal.  dn_feat_spp / dn_feat_seed: what the features held were rendered with.
+    DevBuf<float4> dn_emis;
+    bool dn_have_emis = false;
+    uint32_t dn_feat_spp = 0; uint64_t dn_feat_seed = 0;
     // mcpt_render_tile_list: the caller's list, staged in pinned memory and copied to the device in stream order; both grow to the longest list seen
     DevBuf<uint32_t> tl_dev; Staging<uint32_t> tl_stage;
     // Adaptive sampling (adaptive.hip), allocated by the first mcpt_render_adaptive: the half films H and O (1 float4 / pixel each), per tile
@@ -624,7 +629,7 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     return MCPT_OK;
 }
 // The first-hit features and the last adaptive call's tile error describe the scene as it was.
-static void rf_forget_derived(mcpt_ctx* c) { c->dn_have_features = false; c->dn_have_out = false; c->ad_have_err = false; }
+static void rf_forget_derived(mcpt_ctx* c) { c->dn_have_features = false; c->dn_have_emis = false; c->dn_have_out = false; c->ad_have_err = false; }
 
 // What mcpt_set_vertex_groups / _skin / _morph do once their arguments are checked, in this order: the stream drained (rf_vtx / rf_nrm are final,
 // and no copy out of the old stage is under way), the record's `alloc`, rf_vtx / rf_nrm copied into `rest` on the device, the caller's per-record
@@ -1181,15 +1186,23 @@ mcpt_status mcpt_set_null_stream(mcpt_ctx* ctx) {
 }
 
 // ------------------------------------------------------------------------------------------------ denoised preview
+// The features of the current scene and view into dn_feat (allocated by the caller) on the context's stream -- and, once the context owns the
+// emission buffer, the emission in the same traversal.  Remembers what they were rendered with: a later split denoise renders the emission of
+// features that lack it from the same samples.
+static mcpt_status dn_render_features(mcpt_ctx* ctx, uint32_t spp, uint64_t seed) {
+    HIP_TRY(launch_dn_features(ctx->dev, spp, uint32_t(seed), uint32_t(seed >> 32), ctx->dn_feat.p, ctx->dn_emis.p, ctx->stream));
+    ctx->dn_have_features = true; ctx->dn_have_emis = ctx->dn_emis.p != nullptr;
+    ctx->dn_feat_spp = spp; ctx->dn_feat_seed = seed;
+    return MCPT_OK;
+}
+
 mcpt_status mcpt_render_features(mcpt_ctx* ctx, uint32_t spp, uint64_t seed) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     if (spp < 1 || spp > DN_MAX_SPP) return fail(MCPT_ERR_INVALID_ARG, "mcpt_render_features: need 1 <= spp <= 64");
     if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
     const size_t n = size_t(ctx->width) * ctx->height;
     if (!ctx->dn_feat.p) HIP_TRY(ctx->dn_feat.alloc(2 * n, &ctx->info.device_bytes));
-    HIP_TRY(launch_dn_features(ctx->dev, spp, uint32_t(seed), uint32_t(seed >> 32), ctx->dn_feat.p, ctx->stream));
-    ctx->dn_have_features = true;
-    return MCPT_OK;
+    return dn_render_features(ctx, spp, seed);
 }
 
 mcpt_status mcpt_read_features(mcpt_ctx* ctx, float* out8) {
@@ -1205,10 +1218,18 @@ mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_deno
     st = read_opts(opts, o, "mcpt_denoise", "mcpt_denoise_opts"); if (st != MCPT_OK) return st;
     if (o.iterations > DN_MAX_LEVELS) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: at most 10 iterations");
     if (!(o.sigma_color >= 0.f) || !(o.sigma_normal >= 0.f) || !(o.sigma_depth >= 0.f)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be >= 0 (0 = default)");
+    if (o.flags & ~(MCPT_DENOISE_SPLIT_EMISSION | MCPT_DENOISE_CLAMP_FIREFLIES)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: unknown bit in flags");
+    if (o.firefly_clamp != 0.f && !(std::isfinite(o.firefly_clamp) && o.firefly_clamp >= 1.f)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: firefly_clamp must be finite and >= 1 (0 = default)");
     if (!ctx->dn_have_features) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: no features rendered yet (mcpt_render_features)");
     const size_t n = size_t(ctx->width) * ctx->height;
     uint64_t* tally = &ctx->info.device_bytes;
-    if (!ctx->dn_out.p) HIP_TRY(alloc_all(Want(ctx->dn_guide, n, tally), Want(ctx->dn_iv0, n, tally), Want(ctx->dn_iv1, n, tally), Want(ctx->dn_out, n, tally)));
+    const bool split = (o.flags & MCPT_DENOISE_SPLIT_EMISSION) != 0;
+    HIP_TRY(alloc_all(Want(ctx->dn_guide, n, tally, !ctx->dn_out.p), Want(ctx->dn_iv0, n, tally, !ctx->dn_out.p), Want(ctx->dn_iv1, n, tally, !ctx->dn_out.p),
+                      Want(ctx->dn_out, n, tally, !ctx->dn_out.p), Want(ctx->dn_emis, n, tally, split && !ctx->dn_emis.p)));
+    if (split && !ctx->dn_have_emis) {                                     // features rendered before the context owned the buffer: the same samples again
+        HIP_TRY(launch_dn_features(ctx->dev, ctx->dn_feat_spp, uint32_t(ctx->dn_feat_seed), uint32_t(ctx->dn_feat_seed >> 32), nullptr, ctx->dn_emis.p, ctx->stream));
+        ctx->dn_have_emis = true;
+    }
     DnParams p;
     p.width = ctx->width; p.height = ctx->height;
     p.sigma_c = o.sigma_color > 0.f ? o.sigma_color : 4.f;
@@ -1217,9 +1238,18 @@ mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_deno
     p.theta = float(ctx->dev.cam.h / double(ctx->height));
     const uint32_t levels = o.iterations ? o.iterations : 5u;
     const float4* film = device_rgba ? static_cast<const float4*>(device_rgba) : ctx->accum;
-    HIP_TRY(launch_dn_filter(p, levels, film, ctx->dn_feat.p, ctx->dn_guide.p, ctx->dn_iv0.p, ctx->dn_iv1.p, ctx->dn_out.p, ctx->stream));
+    p.clamp_k = !(o.flags & MCPT_DENOISE_CLAMP_FIREFLIES) ? 0.f : o.firefly_clamp > 0.f ? o.firefly_clamp : MCPT_DENOISE_DEFAULT_FIREFLY_CLAMP;
+    HIP_TRY(launch_dn_filter(p, levels, film, ctx->dn_feat.p, split ? ctx->dn_emis.p : nullptr, ctx->dn_guide.p, ctx->dn_iv0.p, ctx->dn_iv1.p, ctx->dn_out.p,
+                             ctx->stream));
     ctx->dn_have_out = true;
     return MCPT_OK;
+}
+
+mcpt_status mcpt_read_emission(mcpt_ctx* ctx, float* out4) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out4) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    if (!ctx->dn_have_emis) return fail(MCPT_ERR_INVALID_ARG, "mcpt_read_emission: no emission held (mcpt_denoise with MCPT_DENOISE_SPLIT_EMISSION)");
+    return read_back(ctx, out4, ctx->dn_emis.p, ctx->dn_emis.bytes);
 }
 
 mcpt_status mcpt_read_denoised(mcpt_ctx* ctx, float* rgba_host) {
@@ -2240,9 +2270,8 @@ static mcpt_status rp_frame(mcpt_ctx* ctx, const RfUpdate* update, const mcpt_ca
     // Everything below is stream work on the context's stream, ordered like mcpt_set_camera / mcpt_update_vertices: renders enqueued before it have
     // joined the stream, the next render's sub-pipelines fork from it after the last kernel here.
     hipStream_t s = ctx->stream;
-    const uint32_t seed_lo = uint32_t(o.feature_seed), seed_hi = uint32_t(o.feature_seed >> 32);
     HIP_TRY(ctx->rp_watch.begin(s));
-    if (!ctx->dn_have_features) HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, ctx->dn_feat.p, s));
+    if (!ctx->dn_have_features) { st = dn_render_features(ctx, o.feature_spp, o.feature_seed); if (st != MCPT_OK) return st; }
     std::swap(ctx->dn_feat, ctx->rp_feat_old);                             // the old scene's and view's features are kept where they lie
     HIP_TRY(hipMemcpyAsync(ctx->rp_film_old.p, ctx->accum, ctx->rp_film_old.bytes, hipMemcpyDeviceToDevice, s));
     if (update && ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->rp_vtx_old.p, ctx->rf_vtx.p, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, s));
@@ -2250,8 +2279,8 @@ static mcpt_status rp_frame(mcpt_ctx* ctx, const RfUpdate* update, const mcpt_ca
     const DevCamera old_cam = ctx->dev.cam;
     if (update) { st = rf_enqueue_update(ctx, *update); if (st != MCPT_OK) return st; }
     if (cm) apply_camera(ctx, *cm);
-    HIP_TRY(launch_dn_features(ctx->dev, o.feature_spp, seed_lo, seed_hi, ctx->dn_feat.p, s));
-    ctx->dn_have_features = true;                                          // those of the new scene and view: mcpt_denoise may follow at once
+    st = dn_render_features(ctx, o.feature_spp, o.feature_seed);           // those of the new scene and view: mcpt_denoise may follow at once
+    if (st != MCPT_OK) return st;
     if (update) HIP_TRY(launch_rp_first_hit(ctx->dev, ctx->rp_hits.p, s));
     const RpOldScene old{ctx->rp_hits.p, ctx->rp_vtx_old.p, ctx->rp_nrm_old.p};
     st = rp_run(ctx, old_cam, ctx->dev.cam, o, update ? &old : nullptr, ctx->rp_film_old.p, ctx->rp_feat_old.p, ctx->dn_feat.p, ctx->accum, ctx->rp_count.p);

@@ -23,6 +23,7 @@ static void usage() {
     std::cout << "usage: mcpt_cli scene.obj [--spp N] [--batch B] [--depth D] [--gpus G] [--shard samples|tiles] [--out prefix] [--seed S] [--recursive] [--corrected]\n"
                  "                          [--deterministic] [--ref-index-order] [--ref-tie-order] [--gpu-bvh] [--check] [--dump-model file] [--save-every K]\n"
                  "                          [--denoise]   (also writes <prefix><frames>_denoised.png, and one per --save-every image)\n"
+                 "                          [--denoise-robust]   (--denoise with emitted light kept apart and fireflies clamped)\n"
                  "                          [--adaptive T [--min-spp N]]   adaptive sampling per 8x8 tile down to error T, --spp samples at most per pixel\n"
                  "                                        (one GPU; also writes <prefix>_spp.png, a grey map of log2(samples) / log2(spp))\n"
                  "                          [--turntable N]   N frames of --spp samples each, the camera rotated about lookat around up by 360/N degrees per frame\n"
@@ -81,7 +82,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     std::string filename = argv[1], out, dump_model;
-    uint32_t spp = 64, batch = 0, depth = 0, gpus = 1, save_every = 0; uint64_t seed = 20251004; uint32_t flags = 0, integrator = 0; bool ref_order = false, check_only = false, shard_tiles = false, denoise = false;
+    uint32_t spp = 64, batch = 0, depth = 0, gpus = 1, save_every = 0; uint64_t seed = 20251004; uint32_t flags = 0, integrator = 0; bool ref_order = false, check_only = false, shard_tiles = false, denoise = false, denoise_robust = false;
     float adaptive = -1.f; uint32_t min_spp = 0, turntable = 0;
     bool reproject = false; float history = 0.f;
     bool wobble = false; double wobble_a = 0.0;
@@ -104,6 +105,7 @@ int main(int argc, char** argv) {
         else if (a == "--save-every") save_every = uint32_t(std::atoi(next()));
         else if (a == "--shard") shard_tiles = std::string(next()) == "tiles";
         else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-robust") denoise = denoise_robust = true;
         else if (a == "--adaptive") adaptive = float(std::atof(next()));
         else if (a == "--min-spp") min_spp = uint32_t(std::atoi(next()));
         else if (a == "--turntable") turntable = uint32_t(std::atoi(next()));
@@ -424,7 +426,9 @@ int main(int argc, char** argv) {
         std::vector<uint8_t> rgb(size_t(w) * h * 3);
         void* den = nullptr;
         mcpt_ctx* c = renders[0]->handle();
-        if (mcpt_denoise(c, device_film, nullptr) != MCPT_OK || mcpt_denoised_device_ptr(c, &den) != MCPT_OK || mcpt_tonemap_buffer(c, den, rgb.data(), 1) != MCPT_OK)
+        mcpt_denoise_opts dopts; std::memset(&dopts, 0, sizeof dopts); dopts.struct_size = sizeof dopts;
+        if (denoise_robust) dopts.flags = MCPT_DENOISE_SPLIT_EMISSION | MCPT_DENOISE_CLAMP_FIREFLIES;
+        if (mcpt_denoise(c, device_film, &dopts) != MCPT_OK || mcpt_denoised_device_ptr(c, &den) != MCPT_OK || mcpt_tonemap_buffer(c, den, rgb.data(), 1) != MCPT_OK)
             return fail_with(std::string("denoised image: ") + mcpt_last_error());
         const std::string file = out + std::to_string(at) + "_denoised.png";
         if (write_png_rgb8(file, w, h, rgb.data())) std::cout << "Image saved successfully: " << file << std::endl;

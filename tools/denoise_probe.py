@@ -4,6 +4,8 @@ features_ms: mcpt_render_features at spp 4.  denoise_ms: mcpt_denoise with the d
 Both are bracketed by device events on the context's stream (a torch side stream lent to the context) and end in an event synchronise.
 Bytes are the filter's compulsory HBM traffic: per level the guide and {irr, var} read and {irr, var} written (48 B / pixel); the whole
 call adds the prep pass (film + features read, guide + {irr, var} written) and the last level's albedo and film reads.  Not part of bench.py.
+robust_*: the same call with MCPT_DENOISE_SPLIT_EMISSION | MCPT_DENOISE_CLAMP_FIREFLIES (the LDS-staged prep kernel, the emission read in the prep
+pass and the last level), each flag alone, and mcpt_render_features once the context owns the emission buffer (features and emission in one pass).
 
     python tools/denoise_probe.py [--out FILE]
 """
@@ -39,6 +41,18 @@ def measure(pkg, torch, w, h):
     for _ in range(3):
         timed(call)
     den = sorted(timed(call) for _ in range(20))
+
+    def flagged(flags):
+        o = pkg.DenoiseOpts(); o.struct_size = pkg.C.sizeof(pkg.DenoiseOpts); o.flags = flags
+        run = lambda: r._check(r.lib.mcpt_denoise(r.ctx, None, pkg.C.byref(o)))
+        for _ in range(3):
+            timed(run)
+        return round(statistics.median(timed(run) for _ in range(20)), 4)
+
+    clamp_ms = flagged(pkg.DENOISE_CLAMP_FIREFLIES)                      # before the context owns the emission buffer
+    split_ms = flagged(pkg.DENOISE_SPLIT_EMISSION)                       # (the first call allocates it and renders the emission: a warm-up)
+    both_ms = flagged(pkg.DENOISE_SPLIT_EMISSION | pkg.DENOISE_CLAMP_FIREFLIES)
+    feat_emis = [timed(lambda: r.render_features(spp=4, seed=7)) for _ in range(4)]
     n = w * h
     per_level = 48 * n
     total = n * ((16 + 32 + 16 + 16) + per_level // n * (LEVELS - 1) + (16 + 16 + 16 + 16 + 16))
@@ -48,6 +62,8 @@ def measure(pkg, torch, w, h):
         "size": "%dx%d" % (w, h),
         "features_ms_spp4": round(statistics.median(feat[1:]), 4),
         "denoise_ms": round(ms, 4), "denoise_ms_min": round(den[0], 4), "denoise_ms_max": round(den[-1], 4), "levels": LEVELS,
+        "denoise_clamp_ms": clamp_ms, "denoise_split_ms": split_ms, "denoise_robust_ms": both_ms,
+        "features_with_emission_ms_spp4": round(statistics.median(feat_emis[1:]), 4),
         "bytes_per_level": per_level, "bytes_per_call": total,
         "achieved_GBps": round(total / (ms * 1e-3) / 1e9, 1),
         "hbm_floor_ms": round(total / HBM_PEAK * 1e3, 4),
