@@ -1,5 +1,6 @@
 """CPU only: tests/trace_ref.py itself -- the measurement of its K, what its ray families hold, that the admissible sets are not vacuous, that they
-agree with the brute-force tracers the suite already has, and that a planted fault fails the check tests/test_trace_edges.py applies to the kernels."""
+agree with the brute-force tracers the suite already has, and that a planted fault fails the check tests/test_trace_edges.py applies to the kernels;
+the same conditions for the hard poses tests/test_refit_hard.py refits a live scene into."""
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -115,11 +116,11 @@ def test_admissible_sets_are_not_vacuous(pkg, name):
     assert (rs.n_admissible >= 1).all()                                               # every ray has an admissible answer
 
 
-def _brute(scene, o, d, dtype):
+def _brute(scene, o, d, dtype, centre=None):
     """kit.brute_force_trace, the rays in eight slices side by side."""
     cut = np.linspace(0, o.shape[0], 9).astype(int)
     with ThreadPoolExecutor(8) as pool:
-        parts = list(pool.map(lambda k: kit.brute_force_trace(scene, o[cut[k]:cut[k + 1]], d[cut[k]:cut[k + 1]], dtype, chunk=32), range(8)))
+        parts = list(pool.map(lambda k: kit.brute_force_trace(scene, o[cut[k]:cut[k + 1]], d[cut[k]:cut[k + 1]], dtype, chunk=32, centre=centre), range(8)))
     return tuple(np.concatenate(x) for x in zip(*parts))
 
 
@@ -140,9 +141,9 @@ def test_agrees_with_the_brute_force_tracers(pkg, name):
     assert not bad.any(), R.describe(rs, rays, np.nonzero(bad)[0][0], f[np.nonzero(bad)[0][0]])
 
 
-def _closest32(scene, o, d, drop=None):
+def _closest32(scene, o, d, drop=None, centre=None):
     """The fp32 restatement's closest hit of a few rays (tri_test32 + tri_accept_closest), leaving triangle drop[i] out for ray i."""
-    v0, e1, e2, ol, dl = R.records(scene, o, d)
+    v0, e1, e2, ol, dl = R.records(scene, o, d, centre)
     a, t, u, v = R.tri_test32(v0[None], e1[None], e2[None], ol[:, None, :], dl[:, None, :])
     with np.errstate(invalid="ignore"):
         ok = (np.abs(a) >= F32(1e-5)) & (t >= F32(1e-4)) & (t < F32(3.0e38)) & (u >= 0) & (v >= 0) & (F32(1) - u - v >= 0)
@@ -154,17 +155,23 @@ def _closest32(scene, o, d, drop=None):
 @pytest.mark.parametrize("name", ["room16", "soup"])
 def test_planted_faults_fail_the_check(pkg, name):
     """Negative controls, on the fp32 restatement's own answers: the nearest surely accepted triangle dropped on 1 ray in 2 000, u moved by 16 bounds, a blocked verdict flipped -- each makes exactly the tampered rays fail."""
-    scene, rays, rs = R.case(pkg, name)
+    _plant_faults(*R.case(pkg, name))
+
+
+def _plant_faults(scene, rays, rs, centre=None, single_answer=False):
+    """single_answer: the ray that loses its triangle is the first from the usual one on whose only admissible answer is that triangle (in a pose of
+    overlapping slivers the second-nearest triangle of a ray may well be admissible too)."""
     o, d = rays["origin"], rays["direction"]
     pick = np.nonzero(rs.sure_closest > 0)[0][:2000]
-    t, f, u, v = _closest32(scene, o[pick], d[pick])
+    t, f, u, v = _closest32(scene, o[pick], d[pick], centre=centre)
     sub = lambda face, t_, u_, v_: _sub_check(rs, pick, face, t_, u_, v_)
     bad, _ = sub(f, t, u, v)
     assert not bad.any()
     # 1 in 2 000: one ray of these 2 000 loses its nearest surely accepted triangle
     j = 1234 % pick.size
+    if single_answer: j += int(np.argmax(rs.n_admissible[pick[j:]] == 1))
     nearest_sure = rs.face[(rs.ray == pick[j]) & (rs.sc == R.SURE)][np.argmin(rs.t[(rs.ray == pick[j]) & (rs.sc == R.SURE)])]
-    tj, fj, uj, vj = _closest32(scene, o[pick[j:j + 1]], d[pick[j:j + 1]], drop=np.array([nearest_sure]))
+    tj, fj, uj, vj = _closest32(scene, o[pick[j:j + 1]], d[pick[j:j + 1]], drop=np.array([nearest_sure]), centre=centre)
     t2_, f2, u2, v2 = t.copy(), f.copy(), u.copy(), v.copy(); t2_[j], f2[j], u2[j], v2[j] = tj[0], fj[0], uj[0], vj[0]
     bad, _ = sub(f2, t2_, u2, v2)
     assert bad[j] and bad.sum() == 1
@@ -193,3 +200,94 @@ def _sub_check(rs, pick, face, t, u, v):
     F[pick] = face; T[pick] = t; U[pick] = u; V[pick] = v
     bad, ratio = rs.check_closest(F, T, U, V)
     return bad[pick], ratio[pick]
+
+
+# ------------------------------------------------------------------------------------------------------------------------ hard poses
+HIT_POSES = ("scramble", "stretch", "far", "mirror", "fold", "third-degenerate")
+
+
+@pytest.mark.parametrize("name,pose", R.POSE_CASES)
+def test_poses_are_what_they_say(pkg, name, pose):
+    scene, moved, rays, rs = R.pose_case(pkg, name, pose)
+    c = R.centre_of(scene); v, w = scene.vertex, moved.vertex
+    used = R._used(scene)
+    assert np.array_equal(w, w.astype(F32)) and np.array_equal(moved.face, scene.face) and rs.n_faces == scene.face.shape[0]
+    # the probes see fp32 origins about the CREATION centre
+    o = R.records(moved, rays["origin"], rays["direction"], c)[3]
+    assert np.array_equal(o.astype(np.float64) + c, rays["origin"]) and (rs.n_admissible >= 1).all()
+    p = w[moved.face[:, :, 0]]; area2 = np.linalg.norm(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), axis=1)
+    ext = lambda x: x[used].max(0) - x[used].min(0)
+    if pose == "scramble":
+        assert np.array_equal(np.sort(w[used], 0), np.sort(v[used], 0)) and np.array_equal(R.centre_of(moved), c) and (w[used] != v[used]).any(1).mean() > 0.99
+        if name == "room16":                                                          # every triangle spans the scene: the median box covers a twentieth of its volume
+            assert np.median(np.prod(p.max(1) - p.min(1), axis=1)) > 0.05
+    if pose == "stretch":
+        assert np.all(ext(w)[0] / ext(w)[2] >= 2.0 ** 23) and np.allclose(R.centre_of(moved), c, atol=1e-3)
+    if pose == "far":
+        assert np.allclose(R.centre_of(moved) - c, R.FAR, rtol=0, atol=1e-5) and np.abs(w[used] - c).max() > 128
+    if pose == "mirror":
+        q = v[scene.face[:, :, 0]]; n0 = np.cross(q[:, 1] - q[:, 0], q[:, 2] - q[:, 0]); n1 = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+        assert np.all(n0[:, 0] * n1[:, 0] >= 0) and np.all(n0[:, 1] * n1[:, 1] <= 0) and np.all(n0[:, 2] * n1[:, 2] <= 0) and np.array_equal(R.centre_of(moved), c)
+    if pose == "fold":
+        assert np.all(ext(w)[1:] > ext(v)[1:] + R.FOLD)
+    if pose in R.COLLAPSED:
+        flat = {"plane": [2], "line": [1, 2], "point": [0, 1, 2]}[pose]
+        assert np.array_equal(w[used][:, flat], np.broadcast_to(c.astype(F32).astype(np.float64)[flat], (used.size, len(flat))))
+        assert (area2 == 0).all() if pose != "plane" else (area2 > 0).any()
+    if pose == "third-degenerate":
+        assert (area2[::3] == 0).all() and (area2[1::3] > 0).all() and (area2[2::3] > 0).all()
+
+
+@pytest.mark.parametrize("name,pose", R.POSE_CASES)
+def test_pose_admissible_sets_are_not_vacuous(pkg, name, pose):
+    """Conditions on the restatement alone, so that the GPU test of a pose is not vacuous.  Poses that keep triangles: at least half the base rays (the t2
+    family excluded) of soup and room16 have a single admissible answer that is a hit (one / two, which most rays of the list miss: at least a
+    family's worth, 500).  line, point: a miss is every ray's only answer and no verdict may be "blocked".  plane: at least 5 % of the rays have a
+    surely accepted triangle."""
+    scene, moved, rays, rs = R.pose_case(pkg, name, pose)
+    base = rays["family"] != "t2"
+    one = rs.single()
+    share = float((one[base] >= 0).mean()); sure = float((rs.sure_closest > 0).mean())
+    print("\n%s in pose %s: %d rays, single admissible hit %.3f of the base rays, single miss %.3f, a surely accepted triangle %.3f of all rays" % (
+        name, pose, rs.n, share, float((one[base] == -1).mean()), sure))
+    R.print_table("%s, %s" % (name, pose), R.family_table(rs, rays))
+    if pose in HIT_POSES:
+        if name in ("one", "two"): assert (one[base] >= 0).sum() >= R.N_FAMILY
+        else: assert share >= 0.5, share
+        assert rs.forced_any[~base].mean() >= 0.4
+    elif pose == "plane":
+        assert sure >= 0.05, sure
+    else:
+        assert (one == -1).all() and (rs.open_any == 0).all() and rs.key.size == 0
+
+
+@pytest.mark.parametrize("name,pose", R.POSE_CASES)
+def test_poses_agree_with_the_fp32_brute_force_tracer(pkg, name, pose):
+    """kit.brute_force_trace(np.float32) on the posed scene's records about the creation centre is admissible on EVERY ray of every pose."""
+    scene, moved, rays, rs = R.pose_case(pkg, name, pose)
+    t, f, u, v = _brute(moved, rays["origin"], rays["direction"], np.float32, centre=R.centre_of(scene))
+    bad, ratio = rs.check_closest(f, t, u, v)
+    print("\n%s in pose %s: fp32 brute force, worst error / bound %.3f, %.3f of the rays hit" % (name, pose, ratio.max(), (f >= 0).mean()))
+    assert not bad.any(), R.describe(rs, rays, np.nonzero(bad)[0][0], f[np.nonzero(bad)[0][0]])
+
+
+@pytest.mark.parametrize("name,pose", [("room16", "scramble"), ("soup", "stretch"), ("soup", "far"), ("two", "far"), ("room16", "mirror"), ("soup", "fold"),
+                                       ("soup", "plane"), ("soup", "third-degenerate")])
+def test_planted_faults_fail_the_check_in_a_pose(pkg, name, pose):
+    """test_planted_faults_fail_the_check's faults on the posed scenes' restatements."""
+    scene, moved, rays, rs = R.pose_case(pkg, name, pose)
+    _plant_faults(moved, rays, rs, centre=R.centre_of(scene), single_answer=True)
+
+
+@pytest.mark.parametrize("name,pose", [("room16", "line"), ("soup", "point")])
+def test_planted_faults_fail_the_check_in_a_collapsed_pose(pkg, name, pose):
+    """Where nothing can be hit: one reported hit, one "blocked" -- each fails exactly its ray."""
+    scene, moved, rays, rs = R.pose_case(pkg, name, pose)
+    f = np.full(rs.n, -1); z = np.zeros(rs.n)
+    assert not rs.check_closest(f, z, z, z)[0].any() and not rs.check_any(np.zeros(rs.n, bool)).any()
+    f[1234] = 5
+    bad = rs.check_closest(f, z, z, z)[0]
+    assert bad[1234] and bad.sum() == 1
+    blocked = np.zeros(rs.n, bool); blocked[4321] = True
+    bad = rs.check_any(blocked)
+    assert bad[4321] and bad.sum() == 1

@@ -1,5 +1,6 @@
 """The fp64 restatement of the trace kernels' triangle test (tri_test / tri_accept_closest / tri_accept_any, csrc/pt_device.h) with an error model, the
-answers it ADMITS for a ray, and the scenes and ray families of tests/test_trace_ref.py (CPU) and tests/test_trace_edges.py (GPU).  Plain numpy.
+answers it ADMITS for a ray, and the scenes, hard poses and ray families of tests/test_trace_ref.py (CPU), tests/test_trace_edges.py and
+tests/test_refit_hard.py (GPU).  Plain numpy.
 
 Records.  The restatement starts from what the device holds, formed as kit.brute_force_trace(..., np.float32) forms it: first corner and ray origin less
 the fp64 centre of the used vertices, edges from the world coordinates, direction, all rounded to fp32.  Moeller-Trumbore is evaluated on those fp32
@@ -323,6 +324,70 @@ def displaced(scene):
     return dataclasses.replace(scene, vertex=(y * s + off).astype(F32).astype(np.float64))
 
 
+# ------------------------------------------------------------------------------------------------------------------------ hard poses
+# Each pose: creation scene -> posed vertices (fp64, before the rounding to fp32 values that posed() applies).  c is the creation centre, the one
+# the context keeps.  The magnitudes keep every intermediate of tri_test inside fp32 range, which is what the error model assumes.
+FAR = np.array([64.0, -128.0, 32.0])
+STRETCH = np.array([2.0 ** 12, 1.0, 2.0 ** -12])
+FOLD = 3.0                    # (were a pose to miss the condition test_trace_ref.py sets for it, its magnitude is what gets halved, not the condition)
+
+
+def _used(scene):
+    return np.unique(scene.face[:, :, 0])
+
+
+def _scramble(scene, c):
+    v = scene.vertex.copy(); used = _used(scene)
+    v[used] = scene.vertex[np.random.default_rng(11).permutation(used)]
+    return v
+
+
+def _mirror(scene, c):
+    v = scene.vertex.copy(); v[:, 0] = 2.0 * c[0] - v[:, 0]
+    return v
+
+
+def _fold(scene, c):
+    v = scene.vertex.copy()
+    v[:, 1] += FOLD * np.sin(40.0 * v[:, 0]); v[:, 2] += FOLD * np.cos(31.0 * v[:, 1])      # (z from the folded y)
+    return v
+
+
+def _flatten(axes):
+    def pose(scene, c):
+        v = scene.vertex.copy(); v[:, axes] = c[list(axes)]
+        return v
+    return pose
+
+
+def _third_degenerate(scene, c):
+    f = scene.face[::3, :, 0]
+    assert np.unique(scene.face[:, :, 0]).size == 3 * scene.face.shape[0]              # the triangles own their vertices
+    v = scene.vertex.copy(); v[f[:, 1]] = v[f[:, 0]]; v[f[:, 2]] = v[f[:, 0]]
+    return v
+
+
+POSES = {
+    "scramble": _scramble,                                              # the used vertices permuted among their own positions: every triangle spans the scene
+    "stretch": lambda s, c: (s.vertex - c) * STRETCH + c,               # extents 2^24 apart between x and z
+    "far": lambda s, c: s.vertex + FAR,                                 # far from the creation centre, the step of a frame stays small
+    "mirror": _mirror,                                                  # x reflected about the centre: every winding flips
+    "fold": _fold,
+    "plane": _flatten((2,)),                                            # flat on z
+    "line": _flatten((1, 2)),
+    "point": _flatten((0, 1, 2)),                                       # every triangle degenerate, the light's area 0
+    "third-degenerate": _third_degenerate,                              # every third triangle collapsed onto its first corner (soup only)
+}
+COLLAPSED = ("plane", "line", "point")                                  # rays of the creation scene: _soup_rays divides by their zero areas
+POSE_SCENES = {p: (("soup",) if p == "third-degenerate" else ("soup", "room16")) + (("one", "two") if p in ("far", "mirror") else ()) for p in POSES}
+POSE_CASES = [(s, p) for p in POSES for s in POSE_SCENES[p]]
+
+
+def posed(scene, pose):
+    """`scene` in pose POSES[pose]: the vertices rounded to fp32 values, everything else kept."""
+    return dataclasses.replace(scene, vertex=np.asarray(POSES[pose](scene, centre_of(scene)), np.float64).astype(F32).astype(np.float64))
+
+
 # ------------------------------------------------------------------------------------------------------------------------ rays
 NEAR_AXIS = [F32(x) for x in (1e-38, 1e-31, 1e-30, 1e-29, 1e-20, 1e-8)] + [np.nextafter(F32(1e-30), F32(1)), np.nextafter(F32(1e-30), F32(0)), F32(1.0000001e-30)]
 START_NEAR = [F32(0), F32(0.5e-4), np.nextafter(F32(1e-4), F32(0)), F32(1e-4), np.nextafter(F32(1e-4), F32(1)), F32(2e-4), F32(1e-3)]
@@ -510,13 +575,19 @@ def case(pkg, name):
     scene = SCENES[name](pkg)
     rng = np.random.default_rng(1000 + sorted(SCENES).index(name))
     o, d, fam = (_room_rays if name in ROOMS else _soup_rays)(scene, rng)
+    _cases[name] = (scene,) + with_t2_family(scene, o, d, fam)
+    return _cases[name]
+
+
+def with_t2_family(scene, o, d, fam, centre=None):
+    """(rays, Restatement) of the base rays (o, d, fam) against `scene` followed by their t2 family.  centre: as in records()."""
     assert np.isfinite(o).all() and np.isfinite(d).all() and (np.abs(_r(d)) > 0).any(1).all()
     # the t2 family: copies of rays of every family, the limit around the fp32 hit distance of the nearest triangle of the fp64 restatement (1 where
     # there is none).  The five limits within 2^-20 of t leave the verdict open by construction (the bound of t is at least 2^-20 t), the other three
     # force it: each source ray gets one of the five and all of the three.
-    base = restate(scene, o, d)
+    base = restate(scene, o, d, centre=centre)
     src = np.concatenate([np.nonzero(fam == f)[0][:N_T2_SOURCE] for f in np.unique(fam)])
-    v0, e1, e2, ol, dl = records(scene, o[src], d[src])
+    v0, e1, e2, ol, dl = records(scene, o[src], d[src], centre)
     near = np.full(src.size, -1)
     cand = (base.sc != REJ) | (base.sa != REJ)
     for j, i in enumerate(src):
@@ -537,10 +608,27 @@ def case(pkg, name):
     rays = {"origin": np.concatenate([o, o[src2]]), "direction": np.concatenate([d, d[src2]]), "t2": np.concatenate([np.full(nb, 1e300), t2]),
             "family": np.concatenate([fam, np.array(["t2"] * src2.size)]), "t2_kind": np.concatenate([np.array([""] * nb, dtype=kinds.dtype), kinds]),
             "source": np.concatenate([np.arange(nb), src2])}
-    rs = joined(base, restate(scene, o[src2], d[src2], t2))
+    rs = joined(base, restate(scene, o[src2], d[src2], t2, centre=centre))
     for a in rays.values(): a.setflags(write=False)
-    _cases[name] = (scene, rays, rs)
-    return _cases[name]
+    return rays, rs
+
+
+_pose_cases = {}
+
+
+def pose_case(pkg, name, pose):
+    """(creation scene, posed scene, rays, Restatement) of SCENES[name] moved into POSES[pose] by an update of a live context, once per session.
+    The rays are _soup_rays of the posed scene (of the creation scene for the COLLAPSED poses) and their t2 family; the context keeps the CREATION
+    centre, so the origins are fp32 values less that centre and the restatement forms its records about it."""
+    if (name, pose) not in _pose_cases:
+        scene = case(pkg, name)[0]
+        moved = posed(scene, pose)
+        ctr = centre_of(scene)
+        with np.errstate(invalid="ignore", divide="ignore"):                           # (a degenerate triangle's altitude over its longest edge is 0 / 0)
+            o, d, fam = _soup_rays(scene if pose in COLLAPSED else moved, np.random.default_rng(7))
+        o = _r(o - ctr).astype(np.float64) + ctr
+        _pose_cases[(name, pose)] = (scene, moved) + with_t2_family(moved, o, d, fam, centre=ctr)
+    return _pose_cases[(name, pose)]
 
 
 def family_table(rs, rays, ratio=None):
