@@ -646,6 +646,87 @@ mcpt_status mcpt_update_keyframes(mcpt_ctx* ctx, double time);
 mcpt_status mcpt_update_keyframes_reproject(mcpt_ctx* ctx, double time, const mcpt_camera* camera /* NULL = keep */, const mcpt_reproject_opts* opts /* NULL = defaults */);
 mcpt_status mcpt_get_keyframe_info(mcpt_ctx* ctx, mcpt_keyframe_info* out);   /* synchronises */
 
+/* ---- live scenes: each part driven by its own deformer in one update call ----------------------------------------------------- */
+/* mcpt_update_transforms, _skin, _morph and _keyframes each write EVERY record of the scene, so a later call of another route overwrites what the
+ * previous one wrote: a skinned figure, a spinning rigid fan and a keyframed cloth in one scene cannot be animated by them.  Here every vertex
+ * record and every normal record names the ONE route that writes it, and one call runs several routes, lets each write only its own records,
+ * runs the automatic-normals pass once and refits once.  All calls need MCPT_FLAG_DYNAMIC (else MCPT_ERR_UNSUPPORTED).
+ *
+ *     id  owner                  written by
+ *     0   MCPT_OWNER_NONE        no route of a parts update: the record keeps what it holds
+ *     1   MCPT_OWNER_GROUPS      mcpt_update_transforms' arithmetic
+ *     2   MCPT_OWNER_SKIN        mcpt_update_skin's, in the context's skinning mode
+ *     3   MCPT_OWNER_MORPH       mcpt_update_morph's; with MCPT_PARTS_MORPH_THEN_SKIN morph, then skin
+ *     4   MCPT_OWNER_KEYFRAMES   mcpt_update_keyframes'
+ * The route bit is MCPT_ROUTE_x = 1u << MCPT_OWNER_x.
+ *
+ * mcpt_set_vertex_owners: set-up, synchronous: one owner id per vertex and per normal.  The two arrays are independent; pairing them sensibly is
+ * the caller's business.  No route has to be set up yet.  Calling it again replaces the owners.  vertex_owner == NULL drops them and frees what
+ * they hold (device_bytes is what it was before the first call).  Allocates, counted in device_bytes and reported in
+ * mcpt_parts_info::device_bytes: 1 B per vertex and per normal for the owners, and one scratch pair of 24 B per vertex and per normal that the
+ * routes of a parts update write.  Freed with the context; mcpt_clone_to_device carries the owners; mcpt_rebuild_trees keeps them (they are per
+ * record, not per leaf).
+ *  - Refused with nothing changed, MCPT_ERR_INVALID_ARG, in this order: n_vertex / n_normal that differ from the scene's; a NULL normal_owner
+ *    with n_normal > 0; an id > 4 (the message names the record; vertices are judged first).  MCPT_ERR_HIP when an allocation fails.
+ *
+ * mcpt_update_parts runs the routes named in `routes`, in ascending id order, each with the payload of its own call.  Afterwards
+ *  - a record whose owner's route ran holds, bit for bit, what that route's own call -- mcpt_update_transforms, mcpt_update_skin,
+ *    mcpt_update_morph (with the bones iff MCPT_PARTS_MORPH_THEN_SKIN) or mcpt_update_keyframes, with the same payload, on this context -- would
+ *    have written to that record;
+ *  - every other record (owner NONE, or an owner whose route did not run in this call) holds the bits it held before.
+ * A route that runs and owns no record writes nothing; it still advances its own info (mcpt_transform_info::updates ...) as its own call does.
+ * From there on the call IS mcpt_update_vertices after its upload, as for every other route: the auto-normals pass, when set, runs once on the
+ * combined arrays and overrides the records it has entries for; one refit follows, ordered on the context's stream; mcpt_get_update_info counts
+ * one update; film and counters are untouched; features, the denoised film and the tile error are dropped.  Asynchronous.
+ *  - Everything is validated on the host before any device work, and a refusal changes nothing (no stage, no table, no counter).  In this order:
+ *    MCPT_ERR_UNSUPPORTED without MCPT_FLAG_DYNAMIC; then MCPT_ERR_INVALID_ARG for a NULL update; a wrong struct_size; no owners set; routes == 0,
+ *    an unknown route bit or an unknown flag bit; MCPT_PARTS_MORPH_THEN_SKIN without MCPT_ROUTE_MORPH; then per route that runs, in id order,
+ *    that route's own rules for its payload (a route that was never set up, a NULL payload, a wrong count, its value checks).
+ * mcpt_update_parts_reproject is mcpt_update_vertices_reproject with the parts update in place of the upload; validation order: the above, the
+ * camera (when given), the options, MCPT_ERR_BVH_DEPTH.
+ *
+ * The existing calls do not look at the owners: mcpt_update_transforms, _skin, _morph, _keyframes, _vertices and their _reproject forms write
+ * every record, as before. */
+#define MCPT_OWNER_NONE      0u
+#define MCPT_OWNER_GROUPS    1u
+#define MCPT_OWNER_SKIN      2u
+#define MCPT_OWNER_MORPH     3u
+#define MCPT_OWNER_KEYFRAMES 4u
+#define MCPT_ROUTE_GROUPS    (1u << MCPT_OWNER_GROUPS)
+#define MCPT_ROUTE_SKIN      (1u << MCPT_OWNER_SKIN)
+#define MCPT_ROUTE_MORPH     (1u << MCPT_OWNER_MORPH)
+#define MCPT_ROUTE_KEYFRAMES (1u << MCPT_OWNER_KEYFRAMES)
+#define MCPT_PARTS_MORPH_THEN_SKIN 0x1u   /* mcpt_scene_update::flags: the morph route's records are morphed, then skinned by bone_m3x4 */
+typedef struct mcpt_scene_update {
+    uint32_t struct_size;
+    uint32_t routes;                    /* MCPT_ROUTE_*: the routes that run */
+    uint32_t flags;                     /* MCPT_PARTS_MORPH_THEN_SKIN */
+    uint32_t reserved0;
+    const double* group_m3x4;           /* MCPT_ROUTE_GROUPS: mcpt_update_transforms' arguments */
+    uint32_t n_groups, reserved1;
+    const double* bone_m3x4;            /* MCPT_ROUTE_SKIN and / or MCPT_PARTS_MORPH_THEN_SKIN: mcpt_update_skin's */
+    uint32_t n_bones, reserved2;
+    const double* morph_weight;         /* MCPT_ROUTE_MORPH: mcpt_update_morph's weights */
+    uint32_t n_targets, reserved3;
+    double   time;                      /* MCPT_ROUTE_KEYFRAMES: mcpt_update_keyframes' */
+    uint32_t reserved[4];
+} mcpt_scene_update;
+typedef struct mcpt_parts_info {
+    uint32_t struct_size, set;          /* 1: owners are set now */
+    uint32_t updates, last_routes;      /* mcpt_update_parts (+ _reproject) calls on this context so far; `routes` of the last one */
+    uint32_t vertex_records[5];         /* records per owner id, of the owners set now */
+    uint32_t normal_records[5];
+    double   last_ms;                   /* device time of the last call's deforming part: all its routes and their selects */
+    uint64_t device_bytes;              /* what the owners and the scratch pair hold on the device now */
+    uint32_t reserved[4];
+} mcpt_parts_info;
+mcpt_status mcpt_set_vertex_owners(mcpt_ctx* ctx, const uint8_t* vertex_owner /* NULL: drop the owners */, uint32_t n_vertex,
+                                   const uint8_t* normal_owner, uint32_t n_normal);
+mcpt_status mcpt_update_parts(mcpt_ctx* ctx, const mcpt_scene_update* update);
+mcpt_status mcpt_update_parts_reproject(mcpt_ctx* ctx, const mcpt_scene_update* update, const mcpt_camera* camera /* NULL = keep */,
+                                        const mcpt_reproject_opts* opts /* NULL = defaults */);
+mcpt_status mcpt_get_parts_info(mcpt_ctx* ctx, mcpt_parts_info* out);   /* synchronises */
+
 /* ---- deforming parts: morph targets (blend shapes) on the device -------------------------------------------------------------- */
 /* A facial expression, a bulging muscle or a breathing chest is a weighted sum of per-vertex displacement sets, not a matrix per bone.  The caller
  * names the targets once -- each a sparse list of records and their displacements -- and then sends ONE WEIGHT PER TARGET and frame: the device
@@ -789,7 +870,7 @@ mcpt_status mcpt_get_normals_info(mcpt_ctx* ctx, mcpt_normals_info* out);   /* s
  *    rank it has (the creation geometry's, as mcpt_update_vertices documents).
  *  - KEPT, because the scene looks the same from every pixel: the film or a bound accumulator, the counters, the stream binding, the camera, the
  *    feature buffers and the denoised film, the adaptive tile error, the reprojection buffers, the vertex groups with their rest pose and R_g,
- *    the skin with its rest pose and R_b, the morph targets with their rest pose, R and D_k (and the morph-then-skin scratch), the keyframes with their options and captured pose (§22), the auto-normals lists (§20: they are per face of the description, not per leaf), the materials, the textures, and the light list's membership and order (only the lights' leaf-order
+ *    the skin with its rest pose and R_b, the morph targets with their rest pose, R and D_k (and the morph-then-skin scratch), the keyframes with their options and captured pose (§22), the owners of the parts update (§23: per record, not per leaf), the auto-normals lists (§20: they are per face of the description, not per leaf), the materials, the textures, and the light list's membership and order (only the lights' leaf-order
  *    triangle index is renumbered).
  *  - Afterwards mcpt_update_info::wide_area_ratio is 1.0 (its base is the new tree) and `updates` is unchanged; mcpt_scene_info follows the new
  *    trees: n_nodes, bvh_depth, max_leaf, wide_nodes, wide_depth, traversal_bytes, wide_tree_hash, bvh_builder, and device_bytes counts what is

@@ -25,6 +25,9 @@ from .skin_abi import SKIN_DUAL_QUATERNION, SKIN_INFLUENCES, SKIN_LINEAR, SkinIn
 from .morph_abi import MORPH_MAX_TARGETS, MorphInfo, MorphTargets, flatten_targets, targets_struct  # noqa: F401
 # mcpt_set_vertex_keyframes' options, mcpt_get_keyframe_info's struct and the interpolation and wrap constants; tests/test_keyframes.py holds the layouts to the header
 from .keyframe_abi import KEYFRAMES_CATMULL_ROM, KEYFRAMES_CLAMP, KEYFRAMES_LINEAR, KEYFRAMES_LOOP, KEYFRAMES_MAX, KeyframeInfo, KeyframeOpts  # noqa: F401
+# mcpt_update_parts' record, mcpt_get_parts_info's struct, the owner ids and route bits, and the owners a set of faces gives its records; tests/test_parts.py holds the layouts to the header
+from .parts_abi import (OWNER_GROUPS, OWNER_KEYFRAMES, OWNER_MORPH, OWNER_NONE, OWNER_SKIN, PARTS_MORPH_THEN_SKIN, ROUTE_GROUPS, ROUTE_KEYFRAMES,  # noqa: F401
+                        ROUTE_MORPH, ROUTE_SKIN, PartsInfo, SceneUpdate, owners_from_faces)
 # mcpt_set_auto_normals' and mcpt_get_normals_info's structs and the mask of the normals a set of faces uses; tests/test_normals.py holds the layouts to the header
 from .normals_abi import NORMALS_AREA, NORMALS_OFF, NormalsInfo, NormalsOpts, normal_mask_from_faces  # noqa: F401
 
@@ -307,6 +310,10 @@ def load_library() -> C.CDLL:
         "mcpt_update_keyframes": [vp, C.c_double],
         "mcpt_update_keyframes_reproject": [vp, C.c_double, P(CameraC), P(ReprojectOpts)],
         "mcpt_get_keyframe_info": [vp, P(KeyframeInfo)],
+        "mcpt_set_vertex_owners": [vp, vp, C.c_uint32, vp, C.c_uint32],
+        "mcpt_update_parts": [vp, P(SceneUpdate)],
+        "mcpt_update_parts_reproject": [vp, P(SceneUpdate), P(CameraC), P(ReprojectOpts)],
+        "mcpt_get_parts_info": [vp, P(PartsInfo)],
         "mcpt_set_auto_normals": [vp, vp, C.c_uint32, P(NormalsOpts)],
         "mcpt_update_normals": [vp],
         "mcpt_get_normals_info": [vp, P(NormalsInfo)],
@@ -342,6 +349,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_skin_mode", "mcpt_get_skin_mode",
     "mcpt_set_vertex_morph", "mcpt_update_morph", "mcpt_update_morph_reproject", "mcpt_get_morph_info", "mcpt_probe_vertices",
     "mcpt_set_vertex_keyframes", "mcpt_update_keyframes", "mcpt_update_keyframes_reproject", "mcpt_get_keyframe_info",
+    "mcpt_set_vertex_owners", "mcpt_update_parts", "mcpt_update_parts_reproject", "mcpt_get_parts_info",
     "mcpt_set_auto_normals", "mcpt_update_normals", "mcpt_get_normals_info",
     "mcpt_rebuild_trees", "mcpt_get_rebuild_info",
 ]
@@ -713,6 +721,59 @@ class Renderer:
     def keyframe_info(self) -> KeyframeInfo:
         i = KeyframeInfo()
         self._check(self.lib.mcpt_get_keyframe_info(self.ctx, C.byref(i)))
+        return i
+
+    # ---- each part driven by its own deformer in one update call
+    def set_vertex_owners(self, vertex_owner, normal_owner):
+        """One owner id (OWNER_NONE / _GROUPS / _SKIN / _MORPH / _KEYFRAMES) per vertex and per normal (owners_from_faces derives them from
+        faces): the one route of update_parts that writes the record.  Calling it again replaces the owners.  Needs FLAG_DYNAMIC.  Synchronous."""
+        vo = np.ascontiguousarray(vertex_owner, np.uint8).reshape(-1); no = np.ascontiguousarray(normal_owner, np.uint8).reshape(-1)
+        self._check(self.lib.mcpt_set_vertex_owners(self.ctx, _ptr(vo), vo.size, _ptr(no) if no.size else None, no.size))
+
+    def clear_vertex_owners(self):
+        """Drops the owners and frees what they hold on the device; update_parts refuses from then on."""
+        self._check(self.lib.mcpt_set_vertex_owners(self.ctx, None, 0, None, 0))
+
+    def _scene_update(self, groups, bones, weights, time, morph_then_skin, routes):
+        """(the record, the arrays it points into).  The routes run are those whose payload is given -- bones mean the skin route, and with
+        morph_then_skin also the skin behind the morph --, or exactly `routes` (a ROUTE_* mask) when that is given."""
+        u = SceneUpdate(); keep = []
+        u.struct_size = C.sizeof(SceneUpdate)
+        if groups is not None:
+            m = self._matrices(groups); keep.append(m)
+            u.routes |= ROUTE_GROUPS; u.group_m3x4 = m.ctypes.data; u.n_groups = m.shape[0]
+        if bones is not None:
+            m = self._matrices(bones); keep.append(m)
+            u.routes |= ROUTE_SKIN; u.bone_m3x4 = m.ctypes.data; u.n_bones = m.shape[0]
+        if weights is not None:
+            w = np.ascontiguousarray(weights, np.float64).reshape(-1); keep.append(w)
+            u.routes |= ROUTE_MORPH; u.morph_weight = w.ctypes.data; u.n_targets = w.shape[0]
+        if time is not None:
+            u.routes |= ROUTE_KEYFRAMES; u.time = float(time)
+        if morph_then_skin:
+            u.flags |= PARTS_MORPH_THEN_SKIN
+        if routes is not None:
+            u.routes = int(routes)
+        return u, keep
+
+    def update_parts(self, groups=None, bones=None, weights=None, time=None, morph_then_skin=False, routes=None):
+        """Several deformers in one call, each writing only the records it owns (set_vertex_owners), then ONE normals pass and ONE refit.  The
+        routes run are those whose payload is given: groups (update_transforms' matrices), bones (update_skin's), weights (update_morph's), time
+        (update_keyframes').  morph_then_skin: the morph's records are morphed, then skinned by `bones`.  routes: a ROUTE_* mask that replaces
+        the one derived from the payloads (e.g. ROUTE_MORPH alone with bones that only the morph uses).  Records of owner NONE, and of owners
+        whose route does not run, keep their bits.  Asynchronous; the caller clears the film."""
+        u, keep = self._scene_update(groups, bones, weights, time, morph_then_skin, routes)
+        self._check(self.lib.mcpt_update_parts(self.ctx, C.byref(u)))
+
+    def update_parts_reproject(self, groups=None, bones=None, weights=None, time=None, morph_then_skin=False, routes=None, camera=None, **opts):
+        """update_parts that carries the film over, as update_vertices_reproject does; opts: reproject_camera's."""
+        u, keep = self._scene_update(groups, bones, weights, time, morph_then_skin, routes)
+        c, o = _camera_and_opts(camera, opts)
+        self._check(self.lib.mcpt_update_parts_reproject(self.ctx, C.byref(u), c, o))
+
+    def parts_info(self) -> PartsInfo:
+        i = PartsInfo()
+        self._check(self.lib.mcpt_get_parts_info(self.ctx, C.byref(i)))
         return i
 
     def vertices(self):

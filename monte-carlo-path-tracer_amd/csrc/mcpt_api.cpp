@@ -15,6 +15,7 @@
 #include "skin.h"
 #include "morph.h"
 #include "keyframes.h"
+#include "parts.h"
 #include "normals.h"
 #include "reproject.h"
 #include "materials.h"
@@ -331,6 +332,29 @@ struct mcpt_ctx {
             return MCPT_OK;
         }
     } kf;
+    // Parts update (parts.hip), allocated by mcpt_set_vertex_owners: one owner id per vertex and per normal record, and the scratch
+    // pair (rf_vtx's and rf_nrm's sizes) that the routes of mcpt_update_parts write and the select kernel reads.  On the host the records per
+    // owner id and what the last parts update ran (mcpt_parts_info).
+    struct Parts {
+        DevBuf<uint8_t> vowner, nowner; RestPose tmp; Stopwatch watch; PtCounts counts{};
+        bool set = false; uint32_t updates = 0, last_routes = 0;
+        uint64_t device_bytes() const { return vowner.bytes + nowner.bytes + tmp.vtx.bytes + tmp.nrm.bytes; }
+        mcpt_status alloc(mcpt_ctx* c) {
+            uint64_t* tally = &c->info.device_bytes;
+            HIP_TRY(alloc_all(Want(vowner, c->rf_n_vertex, tally), Want(nowner, c->rf_n_normal, tally), Want(tmp.vtx, c->rf_vtx.count(), tally),
+                              Want(tmp.nrm, c->rf_nrm.count(), tally), Want(watch, 1, nullptr, !watch.ev0)));
+            set = true;
+            return MCPT_OK;
+        }
+        void drop() { vowner.release(); nowner.release(); tmp.vtx.release(); tmp.nrm.release(); counts = PtCounts{}; set = false; }
+        template <class Copy> mcpt_status clone_from(mcpt_ctx* c, const Parts& src, Copy copy) {        // the owners and their counts (scratch: its contents are not carried)
+            if (!src.set) return MCPT_OK;
+            const mcpt_status st = alloc(c); if (st != MCPT_OK) return st;
+            counts = src.counts;
+            HIP_TRY(copy(vowner, src.vowner)); HIP_TRY(copy(nowner, src.nowner));
+            return MCPT_OK;
+        }
+    } pt;
     // Automatic normals (normals.hip), allocated by mcpt_set_auto_normals: per normal record its list offset (rf_n_normal + 1) and
     // the 16-byte entries, one per face that names the record.  The lists follow the description's face order, not the leaf order: a rebuild
     // keeps them, a clone carries them.  mode == MCPT_NORMALS_OFF: nothing is allocated, no update runs the pass.
@@ -624,7 +648,7 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     HIP_TRY(copy(c->rf_idx, src->rf_idx)); HIP_TRY(copy(c->rf_bin_order, src->rf_bin_order)); HIP_TRY(copy(c->rf_vtx, src->rf_vtx)); HIP_TRY(copy(c->rf_nrm, src->rf_nrm));
     if ((st = c->xf.clone_from(c, src->xf, copy)) != MCPT_OK || (st = c->sk.clone_from(c, src->sk, copy)) != MCPT_OK ||
         (st = c->mo.clone_from(c, src->mo, copy)) != MCPT_OK || (st = c->kf.clone_from(c, src->kf, copy)) != MCPT_OK ||
-        (st = c->nr.clone_from(c, src->nr, copy)) != MCPT_OK) return st;
+        (st = c->pt.clone_from(c, src->pt, copy)) != MCPT_OK || (st = c->nr.clone_from(c, src->nr, copy)) != MCPT_OK) return st;
     HIP_TRY(hipDeviceSynchronize());
     return MCPT_OK;
 }
@@ -1472,10 +1496,11 @@ static mcpt_status kf_check_update(const mcpt_ctx* ctx, double time, const char*
 }
 // A scene update and where its new vertices come from: the caller's arrays (rf_check_update), one matrix per group (xf_check_update), one per
 // bone (sk_check_update), one weight per morph target alone or in front of the bones (mo_check_update), the time of the keyframes' clock
-// (kf_check_update).  None (§20, mcpt_update_normals):
+// (kf_check_update), several of those at once, each for the records it owns (§23, pt_check_update).  None (§20, mcpt_update_normals):
 // nothing is staged and no vertex moves; the normals pass and the refit run on the arrays as they are.
 struct RfUpdate {
-    enum class Source { Arrays, Groups, Skin, Morph, MorphSkin, Keyframes, None } source = Source::None;
+    enum class Source { Arrays, Groups, Skin, Morph, MorphSkin, Keyframes, Parts, None } source = Source::None;
+    const mcpt_scene_update* parts = nullptr;                                                               // Parts: the caller's record
     const double* vertex = nullptr; const double* normal = nullptr; uint32_t n_vertex = 0, n_normal = 0;    // Arrays
     const double* m3x4 = nullptr; uint32_t n_m3x4 = 0;                                                      // Groups: per group; Skin, MorphSkin: per bone
     const double* weight = nullptr; uint32_t n_weight = 0;                                                  // Morph, MorphSkin: per target
@@ -1491,6 +1516,10 @@ struct RfUpdate {
     static RfUpdate morph(const double* w, uint32_t nw, const double* bones, uint32_t n_bones) {             // bones: null = the morph alone
         RfUpdate u = matrices(bones ? Source::MorphSkin : Source::Morph, bones, n_bones); u.weight = w; u.n_weight = nw; return u;
     }
+    static RfUpdate of_parts(const mcpt_scene_update* p) { RfUpdate u; u.source = Source::Parts; u.parts = p; return u; }
+    // Parts (checked): is its morph followed by the skin?  What its morph route is as an update of its own.
+    bool parts_morph_then_skin() const { return source == Source::Parts && (parts->flags & MCPT_PARTS_MORPH_THEN_SKIN) != 0; }
+    RfUpdate parts_morph() const { return morph(parts->morph_weight, parts->n_targets, parts_morph_then_skin() ? parts->bone_m3x4 : nullptr, parts->n_bones); }
 };
 using Source = RfUpdate::Source;
 static mcpt_status rf_update(mcpt_ctx* ctx, const RfUpdate& u, const char* fn, const mcpt_camera* cm, const mcpt_reproject_opts* opts, bool reproject);
@@ -1505,15 +1534,19 @@ static mcpt_status sk_stage(mcpt_ctx* ctx, const double* bones) {
 }
 // The staged table to the device, in stream order.
 static hipError_t sk_send_bones(mcpt_ctx::Skin& sk, hipStream_t s) { return sk.bone_stage().send(sk.bone_table().p, 0, sk.bone_table().count(), s); }
-// The two skinning kernels of the context's mode: rf_vtx / rf_nrm from the given rest pose.
-static mcpt_status sk_launch(mcpt_ctx* ctx, const double* rest_vtx, const double* rest_nrm, hipStream_t s) {
+// Where a deformer writes: the context's current arrays (rf_current: every single-route call) or the scratch pair of a parts update (§23).
+struct RfDest { double* vtx; double* nrm; };
+static RfDest rf_current(mcpt_ctx* ctx) { return RfDest{ctx->rf_vtx.p, ctx->rf_nrm.p}; }
+// The two skinning kernels of the context's mode: `to` from the given rest pose.
+static mcpt_status sk_launch(mcpt_ctx* ctx, const double* rest_vtx, const double* rest_nrm, RfDest to, hipStream_t s) {
     mcpt_ctx::Skin& sk = ctx->sk; const double* table = sk.bone_table().p;
-    HIP_TRY((sk.dq() ? launch_sk_dq_vertices : launch_sk_vertices)(rest_vtx, sk.vbone.p, sk.vweight.p, table, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
-    HIP_TRY((sk.dq() ? launch_sk_dq_normals : launch_sk_normals)(rest_nrm, sk.nbone.p, sk.nweight.p, table, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+    HIP_TRY((sk.dq() ? launch_sk_dq_vertices : launch_sk_vertices)(rest_vtx, sk.vbone.p, sk.vweight.p, table, to.vtx, ctx->rf_n_vertex, s));
+    HIP_TRY((sk.dq() ? launch_sk_dq_normals : launch_sk_normals)(rest_nrm, sk.nbone.p, sk.nweight.p, table, to.nrm, ctx->rf_n_normal, s));
     return MCPT_OK;
 }
 // Per source the two halves of an update.  *_stage: the caller's values into the pinned stage once the last copy out of it has been made -- host
-// work and waits only.  *_enqueue: the stage's copy and the kernels that write rf_vtx / rf_nrm on `s`, inside the record's watch, and counted.
+// work and waits only.  *_enqueue: the stage's copy and the kernels that write `to` (rf_vtx / rf_nrm, or §23's scratch pair) on `s`, inside the
+// record's watch, and counted.
 static mcpt_status rf_stage_arrays(mcpt_ctx* ctx, const RfUpdate& u) {
     HIP_TRY(ctx->rf_stage.wait());
     std::memcpy(ctx->rf_stage.host, u.vertex, ctx->rf_vtx.bytes);
@@ -1530,19 +1563,19 @@ static mcpt_status xf_stage(mcpt_ctx* ctx, const RfUpdate& u) {
     for (uint32_t g = 0; g < ctx->xf.n_groups; g++) xf_group_record(u.m3x4 + 12 * size_t(g), ctx->xf.stage.host + XF_RECORD * size_t(g));
     return MCPT_OK;
 }
-static mcpt_status xf_enqueue(mcpt_ctx* ctx, hipStream_t s) {
+static mcpt_status xf_enqueue(mcpt_ctx* ctx, hipStream_t s, RfDest to) {
     HIP_TRY(ctx->xf.watch.begin(s));
     HIP_TRY(ctx->xf.stage.send(ctx->xf.table.p, 0, ctx->xf.table.count(), s));
-    HIP_TRY(launch_xf_vertices(ctx->xf.rest.vtx.p, ctx->xf.vgroup.p, ctx->xf.table.p, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
-    HIP_TRY(launch_xf_normals(ctx->xf.rest.nrm.p, ctx->xf.ngroup.p, ctx->xf.table.p, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+    HIP_TRY(launch_xf_vertices(ctx->xf.rest.vtx.p, ctx->xf.vgroup.p, ctx->xf.table.p, to.vtx, ctx->rf_n_vertex, s));
+    HIP_TRY(launch_xf_normals(ctx->xf.rest.nrm.p, ctx->xf.ngroup.p, ctx->xf.table.p, to.nrm, ctx->rf_n_normal, s));
     HIP_TRY(ctx->xf.watch.end(s));
     ctx->xf.updates++;
     return MCPT_OK;
 }
-static mcpt_status sk_enqueue(mcpt_ctx* ctx, hipStream_t s) {
+static mcpt_status sk_enqueue(mcpt_ctx* ctx, hipStream_t s, RfDest to) {
     HIP_TRY(ctx->sk.watch.begin(s));
     HIP_TRY(sk_send_bones(ctx->sk, s));
-    const mcpt_status st = sk_launch(ctx, ctx->sk.rest.vtx.p, ctx->sk.rest.nrm.p, s); if (st != MCPT_OK) return st;   // in the context's skinning mode (§21)
+    const mcpt_status st = sk_launch(ctx, ctx->sk.rest.vtx.p, ctx->sk.rest.nrm.p, to, s); if (st != MCPT_OK) return st;   // in the context's skinning mode (§21)
     HIP_TRY(ctx->sk.watch.end(s));
     ctx->sk.updates++;
     return MCPT_OK;
@@ -1552,16 +1585,17 @@ static mcpt_status mo_stage(mcpt_ctx* ctx, const RfUpdate& u) {
     std::memcpy(ctx->mo.stage.host, u.weight, ctx->mo.weight.bytes);
     return u.source == Source::MorphSkin ? sk_stage(ctx, u.m3x4) : MCPT_OK;
 }
-static mcpt_status mo_enqueue(mcpt_ctx* ctx, const RfUpdate& u, hipStream_t s) {
+// `send_bones`: false when the table of this call's bones is on its way already (§23: the skin route of the same parts update sent it).
+static mcpt_status mo_enqueue(mcpt_ctx* ctx, const RfUpdate& u, hipStream_t s, RfDest to, bool send_bones = true) {
     const bool skin = u.source == Source::MorphSkin;                             // morph, then skin: the morphed arrays are the skin kernels' rest pose
-    double* const mv = skin ? ctx->mo.tmp.vtx.p : ctx->rf_vtx.p; double* const mn = skin ? ctx->mo.tmp.nrm.p : ctx->rf_nrm.p;
+    double* const mv = skin ? ctx->mo.tmp.vtx.p : to.vtx; double* const mn = skin ? ctx->mo.tmp.nrm.p : to.nrm;
     HIP_TRY(ctx->mo.watch.begin(s));
     HIP_TRY(ctx->mo.stage.send(ctx->mo.weight.p, 0, ctx->mo.weight.count(), s));
-    if (skin) HIP_TRY(sk_send_bones(ctx->sk, s));
+    if (skin && send_bones) HIP_TRY(sk_send_bones(ctx->sk, s));
     HIP_TRY(launch_mo_vertices(ctx->mo.rest.vtx.p, ctx->mo.voffset.p, ctx->mo.ventry.p, ctx->mo.weight.p, mv, ctx->rf_n_vertex, s));
     HIP_TRY(launch_mo_normals(ctx->mo.rest.nrm.p, ctx->mo.noffset.p, ctx->mo.nentry.p, ctx->mo.weight.p, mn, ctx->rf_n_normal, s));
     if (skin) {
-        const mcpt_status st = sk_launch(ctx, mv, mn, s); if (st != MCPT_OK) return st;   // in the context's skinning mode (§21)
+        const mcpt_status st = sk_launch(ctx, mv, mn, to, s); if (st != MCPT_OK) return st;   // in the context's skinning mode (§21)
         ctx->sk.updates++;
     }
     HIP_TRY(ctx->mo.watch.end(s));
@@ -1570,27 +1604,92 @@ static mcpt_status mo_enqueue(mcpt_ctx* ctx, const RfUpdate& u, hipStream_t s) {
 }
 // Keyframes stage nothing: the time becomes a segment, tap indices and weights on the host, and those are kernel arguments.  On a keyframe
 // (u == 0) the frame is copied as it is; without normal frames every call writes the normals captured at set-up.
-static mcpt_status kf_enqueue(mcpt_ctx* ctx, const RfUpdate& u, hipStream_t s) {
+static mcpt_status kf_enqueue(mcpt_ctx* ctx, const RfUpdate& u, hipStream_t s, RfDest to) {
     mcpt_ctx::Keyframes& kf = ctx->kf;
     KfBlend b = kf_segment(u.time, kf.start_time, kf.frame_time, kf.n_frames, kf.interpolation, kf.wrap);
     kf_weights(b.u, kf.interpolation, b.w);
     const size_t sv = kf_stride(ctx->rf_n_vertex), sn = kf_stride(ctx->rf_n_normal);
     HIP_TRY(kf.watch.begin(s));
     if (b.u == 0.0) {
-        if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(ctx->rf_vtx.p, kf.vframes.p + sv * b.k, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, s));
-    } else HIP_TRY(launch_kf_vertices(kf.vframes.p, sv, b, ctx->rf_vtx.p, ctx->rf_n_vertex, s));
+        if (ctx->rf_vtx.bytes) HIP_TRY(hipMemcpyAsync(to.vtx, kf.vframes.p + sv * b.k, ctx->rf_vtx.bytes, hipMemcpyDeviceToDevice, s));
+    } else HIP_TRY(launch_kf_vertices(kf.vframes.p, sv, b, to.vtx, ctx->rf_n_vertex, s));
     if (!kf.normal_frames() || b.u == 0.0) {
         const double* from = kf.normal_frames() ? kf.nframes.p + sn * b.k : kf.rest.nrm.p;
-        if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(ctx->rf_nrm.p, from, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, s));
-    } else HIP_TRY(launch_kf_normals(kf.nframes.p, sn, b, ctx->rf_nrm.p, ctx->rf_n_normal, s));
+        if (ctx->rf_nrm.bytes) HIP_TRY(hipMemcpyAsync(to.nrm, from, ctx->rf_nrm.bytes, hipMemcpyDeviceToDevice, s));
+    } else HIP_TRY(launch_kf_normals(kf.nframes.p, sn, b, to.nrm, ctx->rf_n_normal, s));
     HIP_TRY(kf.watch.end(s));
     kf.updates++; kf.last_frame = b.k; kf.last_u = b.u; kf.last_time = u.time;
+    return MCPT_OK;
+}
+// mcpt_update_parts' rules (§23), host only, in the documented order: the record itself, the owners, the plan of `routes` / `flags`, then per
+// route that runs, in id order, that route's own check with its payload.
+static mcpt_status pt_check_update(const mcpt_ctx* ctx, const mcpt_scene_update* p, const char* fn) {
+    const std::string who = std::string(fn) + ": ";
+    if (!p) return fail(MCPT_ERR_INVALID_ARG, who + "null update");
+    if (p->struct_size != sizeof(mcpt_scene_update)) return fail(MCPT_ERR_INVALID_ARG, who + "update->struct_size != sizeof(mcpt_scene_update)");
+    if (!ctx->pt.set) return fail(MCPT_ERR_INVALID_ARG, who + "no owners are set (mcpt_set_vertex_owners)");
+    PtPlan plan;
+    switch (pt_plan(p->routes, p->flags, plan)) {
+    case PT_PLAN_OK: break;
+    case PT_PLAN_NO_ROUTE: return fail(MCPT_ERR_INVALID_ARG, who + "routes names no route");
+    case PT_PLAN_UNKNOWN_ROUTE: return fail(MCPT_ERR_INVALID_ARG, who + "routes has an unknown bit");
+    case PT_PLAN_UNKNOWN_FLAG: return fail(MCPT_ERR_INVALID_ARG, who + "flags has an unknown bit");
+    case PT_PLAN_SKIN_WITHOUT_MORPH: return fail(MCPT_ERR_INVALID_ARG, who + "MCPT_PARTS_MORPH_THEN_SKIN without MCPT_ROUTE_MORPH");
+    }
+    for (uint32_t k = 0; k < plan.n_steps; k++) {
+        mcpt_status st = MCPT_OK;
+        switch (plan.step[k]) {
+        case MCPT_OWNER_GROUPS: st = xf_check_update(ctx, p->group_m3x4, p->n_groups, fn); break;
+        case MCPT_OWNER_SKIN: st = sk_check_update(ctx, p->bone_m3x4, p->n_bones, fn); break;
+        case MCPT_OWNER_MORPH:
+            st = mo_check_update(ctx, p->morph_weight, p->n_targets, plan.morph_then_skin ? p->bone_m3x4 : nullptr, p->n_bones, fn);
+            if (st == MCPT_OK && plan.morph_then_skin && !p->bone_m3x4) st = sk_check_update(ctx, nullptr, p->n_bones, fn);   // (mo_check_update reads null bones as "the morph alone")
+            break;
+        case MCPT_OWNER_KEYFRAMES: st = kf_check_update(ctx, p->time, fn); break;
+        }
+        if (st != MCPT_OK) return st;
+    }
+    return MCPT_OK;
+}
+// The two halves of a checked parts update.  Staging: every route's own, the bones once for the skin route and the skin behind the morph.
+static mcpt_status pt_stage(mcpt_ctx* ctx, const RfUpdate& u) {
+    const mcpt_scene_update& p = *u.parts;
+    PtPlan plan; (void)pt_plan(p.routes, p.flags, plan);
+    mcpt_status st = MCPT_OK;
+    if (p.routes & MCPT_ROUTE_GROUPS) { st = xf_stage(ctx, RfUpdate::groups(p.group_m3x4, p.n_groups)); if (st != MCPT_OK) return st; }
+    if (plan.bones) { st = sk_stage(ctx, p.bone_m3x4); if (st != MCPT_OK) return st; }
+    if (p.routes & MCPT_ROUTE_MORPH) st = mo_stage(ctx, RfUpdate::morph(p.morph_weight, p.n_targets, nullptr, 0));   // (the weights alone: the bones are staged)
+    return st;
+}
+// Route after route in id order on `s`: the route's own enqueue into the scratch pair, then from there the records it owns into rf_vtx / rf_nrm.
+// The scratch pair is reused in stream order; the morph-then-skin scratch (mo.tmp) is another buffer, because that route uses both.
+static mcpt_status pt_enqueue(mcpt_ctx* ctx, const RfUpdate& u, hipStream_t s) {
+    const mcpt_scene_update& p = *u.parts; mcpt_ctx::Parts& pt = ctx->pt;
+    PtPlan plan; (void)pt_plan(p.routes, p.flags, plan);
+    const RfDest tmp{pt.tmp.vtx.p, pt.tmp.nrm.p};
+    bool bones_sent = false;
+    HIP_TRY(pt.watch.begin(s));
+    for (uint32_t k = 0; k < plan.n_steps; k++) {
+        const uint32_t id = plan.step[k];
+        mcpt_status st = MCPT_OK;
+        switch (id) {
+        case MCPT_OWNER_GROUPS: st = xf_enqueue(ctx, s, tmp); break;
+        case MCPT_OWNER_SKIN: st = sk_enqueue(ctx, s, tmp); bones_sent = true; break;
+        case MCPT_OWNER_MORPH: st = mo_enqueue(ctx, u.parts_morph(), s, tmp, !bones_sent); break;
+        case MCPT_OWNER_KEYFRAMES: st = kf_enqueue(ctx, RfUpdate::keyframes(p.time), s, tmp); break;
+        }
+        if (st != MCPT_OK) return st;
+        HIP_TRY(launch_pt_select(tmp.vtx, ctx->rf_vtx.p, pt.vowner.p, id, ctx->rf_n_vertex, s));
+        HIP_TRY(launch_pt_select(tmp.nrm, ctx->rf_nrm.p, pt.nowner.p, id, ctx->rf_n_normal, s));
+    }
+    HIP_TRY(pt.watch.end(s));
+    pt.updates++; pt.last_routes = p.routes;
     return MCPT_OK;
 }
 // Does the refit read rf_nrm, i.e. are there new normals?  `upload_normal`: the arrays' route got normals from the caller.
 //     source                            auto normals    the refit reads rf_nrm
 //     Groups, Skin, Morph, MorphSkin,
-//     Keyframes                         off or on       nd != 0   (a deformer rewrites rf_nrm whenever the scene has normals)
+//     Keyframes, Parts                  off or on       nd != 0   (a deformer rewrites rf_nrm whenever the scene has normals)
 //     Arrays, None                      on              nd != 0   (so does the normals pass, §20)
 //     Arrays, None                      off             upload_normal   (None uploads nothing: no; mcpt_update_normals refuses it before)
 static bool rf_reads_normals(Source source, size_t nd, bool auto_normals, bool upload_normal) {
@@ -1609,6 +1708,7 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     case Source::Skin: st = sk_stage(ctx, u.m3x4); break;
     case Source::Morph: case Source::MorphSkin: st = mo_stage(ctx, u); break;
     case Source::Keyframes: break;                                               // §22: the time travels as kernel arguments
+    case Source::Parts: st = pt_stage(ctx, u); break;
     case Source::None: break;                                                    // §20, mcpt_update_normals: nothing to stage ...
     }
     if (st != MCPT_OK) return st;
@@ -1619,10 +1719,11 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     HIP_TRY(ctx->rf_watch.begin(s));
     switch (u.source) {
     case Source::Arrays: st = rf_enqueue_arrays(ctx, u, s); break;
-    case Source::Groups: st = xf_enqueue(ctx, s); break;
-    case Source::Skin: st = sk_enqueue(ctx, s); break;
-    case Source::Morph: case Source::MorphSkin: st = mo_enqueue(ctx, u, s); break;
-    case Source::Keyframes: st = kf_enqueue(ctx, u, s); break;
+    case Source::Groups: st = xf_enqueue(ctx, s, rf_current(ctx)); break;
+    case Source::Skin: st = sk_enqueue(ctx, s, rf_current(ctx)); break;
+    case Source::Morph: case Source::MorphSkin: st = mo_enqueue(ctx, u, s, rf_current(ctx)); break;
+    case Source::Keyframes: st = kf_enqueue(ctx, u, s, rf_current(ctx)); break;
+    case Source::Parts: st = pt_enqueue(ctx, u, s); break;
     case Source::None: break;                                                    // ... and nothing to write
     }
     if (st != MCPT_OK) return st;
@@ -1879,6 +1980,35 @@ mcpt_status mcpt_get_keyframe_info(mcpt_ctx* ctx, mcpt_keyframe_info* out) {
     const mcpt_ctx::Keyframes& kf = ctx->kf;
     out->n_frames = kf.n_frames; out->interpolation = kf.interpolation; out->wrap = kf.wrap; out->updates = kf.updates; out->last_frame = kf.last_frame;
     out->last_u = kf.last_u; out->last_time = kf.last_time; out->last_ms = kf.watch.last_ms; out->device_bytes = kf.device_bytes();
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ parts update
+mcpt_status mcpt_set_vertex_owners(mcpt_ctx* ctx, const uint8_t* vertex_owner, uint32_t n_vertex, const uint8_t* normal_owner, uint32_t n_normal) {
+    const std::string who = "mcpt_set_vertex_owners: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if ((st = require_dynamic(ctx, who)) != MCPT_OK) return st;
+    PtCounts counts{}; std::string err;
+    if (vertex_owner && !pt_check_owners(vertex_owner, n_vertex, normal_owner, n_normal, ctx->rf_n_vertex, ctx->rf_n_normal, counts, err)) return fail(MCPT_ERR_INVALID_ARG, who + err);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                                  // no kernel reads the old owners or the scratch pair any more
+    st = resolve_timing(ctx); if (st != MCPT_OK) return st;
+    if (!vertex_owner) { ctx->pt.drop(); return MCPT_OK; }
+    st = ctx->pt.alloc(ctx); if (st != MCPT_OK) return st;                       // afresh, all or none: a context that had owners keeps them on failure
+    ctx->pt.counts = counts;
+    Scratch s(ctx->stream);
+    HIP_TRY(s.put(ctx->pt.vowner.p, vertex_owner, n_vertex)); HIP_TRY(s.put(ctx->pt.nowner.p, normal_owner, n_normal)); HIP_TRY(s.finish());
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_update_parts(mcpt_ctx* ctx, const mcpt_scene_update* update) {
+    return rf_update(ctx, RfUpdate::of_parts(update), "mcpt_update_parts", nullptr, nullptr, false);
+}
+
+mcpt_status mcpt_get_parts_info(mcpt_ctx* ctx, mcpt_parts_info* out) {
+    const mcpt_status st = info_begin(ctx, out, ctx ? &ctx->pt.watch : nullptr); if (st != MCPT_OK) return st;
+    const mcpt_ctx::Parts& pt = ctx->pt;
+    out->set = pt.set; out->updates = pt.updates; out->last_routes = pt.last_routes; out->last_ms = pt.watch.last_ms; out->device_bytes = pt.device_bytes();
+    for (int k = 0; k < PT_OWNERS; k++) { out->vertex_records[k] = pt.counts.vertex[k]; out->normal_records[k] = pt.counts.normal[k]; }
     return MCPT_OK;
 }
 
@@ -2352,11 +2482,12 @@ static mcpt_status rf_update(mcpt_ctx* ctx, const RfUpdate& u, const char* fn, c
     case Source::Skin: st = sk_check_update(ctx, u.m3x4, u.n_m3x4, fn); break;
     case Source::Morph: case Source::MorphSkin: st = mo_check_update(ctx, u.weight, u.n_weight, u.m3x4, u.n_m3x4, fn); break;
     case Source::Keyframes: st = kf_check_update(ctx, u.time, fn); break;
+    case Source::Parts: st = pt_check_update(ctx, u.parts, fn); break;
     case Source::None: break;                                                    // (mcpt_update_normals makes its own two checks)
     }
     if (st != MCPT_OK) return st;
     if (reproject && cm) { st = check_camera(ctx, cm, fn); if (st != MCPT_OK) return st; }
-    if (u.source == Source::MorphSkin && (!reproject || ctx->binary_ok)) {
+    if ((u.source == Source::MorphSkin || u.parts_morph_then_skin()) && (!reproject || ctx->binary_ok)) {
         mcpt_reproject_opts o;
         if (reproject) { st = rp_read_opts(opts, o, fn); if (st != MCPT_OK) return st; }
         st = ctx->mo.ensure_scratch(ctx); if (st != MCPT_OK) return st;
@@ -2384,6 +2515,10 @@ mcpt_status mcpt_update_morph_reproject(mcpt_ctx* ctx, const double* weight, uin
 
 mcpt_status mcpt_update_keyframes_reproject(mcpt_ctx* ctx, double time, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
     return rf_update(ctx, RfUpdate::keyframes(time), "mcpt_update_keyframes_reproject", cm, opts, true);
+}
+
+mcpt_status mcpt_update_parts_reproject(mcpt_ctx* ctx, const mcpt_scene_update* update, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
+    return rf_update(ctx, RfUpdate::of_parts(update), "mcpt_update_parts_reproject", cm, opts, true);
 }
 
 mcpt_status mcpt_probe_first_hits(mcpt_ctx* ctx, int32_t* out_face, float* out_uvt3) {

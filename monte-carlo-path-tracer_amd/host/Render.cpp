@@ -88,6 +88,7 @@ static mcpt_camera to_camera(const CameraInfo& c) {
     k.up[0] = c.up.x; k.up[1] = c.up.y; k.up[2] = c.up.z; k.fovy = c.fovy; k.width = c.width; k.height = c.height;
     return k;
 }
+static mcpt_scene_update to_scene_update(const PartsUpdate& u);    // (below, with update_parts)
 bool Render::restart(Scene& scene) {
     if (target && target != &scene) { flush_into(*target); target->detach(this); target = nullptr; }   // another Scene's samples are still that Scene's
     scene.clear();                                    // (drops what this Render held for `scene`: scene_gone)
@@ -157,18 +158,22 @@ bool Render::update_keyframes_reproject(Scene& scene, double time, const CameraI
     return update_reproject(scene, nullptr, nullptr, false, nullptr, &camera, max_history, &time);
 }
 // The geometry comes from `m` (its arrays), from `matrices` (one 3x4 per group, §16, or per bone, §18), from `weights` (one per morph target,
-// §19, with or without the bones' matrices) or from `time` (the keyframes' clock, §22): the rest is the same.
+// §19, with or without the bones' matrices), from `time` (the keyframes' clock, §22) or from several of them at once (`parts`, §23): the rest is
+// the same.
 bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>* matrices, bool bones, const std::vector<double>* weights, const CameraInfo* camera,
-                              float max_history, const double* time) {
+                              float max_history, const double* time, const PartsUpdate* parts) {
     if (!ctx) return false;
-    const char* const who = m ? "update_reproject" : time ? "update_keyframes_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject";
+    const char* const who = parts ? "update_parts_reproject" : m ? "update_reproject" : time ? "update_keyframes_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject";
+    if (parts && (parts->group_matrices.size() % 12 || parts->bone_matrices.size() % 12)) { std::cerr << "Error: Render::" << who << ": need 12 doubles per group and per bone" << std::endl; return false; }
     if (!m && matrices && (matrices->size() % 12 || matrices->empty())) { std::cerr << "Error: Render::" << who << ": need 12 doubles per " << (bones ? "bone" : "group") << std::endl; return false; }
     bool ok = false;
     const bool upload = film_to_device(scene, who, ok);
     if (!ok) return false;
     mcpt_camera k; if (camera) k = to_camera(*camera);
     mcpt_reproject_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.feature_spp = 4; o.feature_seed = seed; o.max_history = max_history;
-    const mcpt_status st = time ? mcpt_update_keyframes_reproject(ctx, *time, camera ? &k : nullptr, &o)
+    mcpt_scene_update pu; if (parts) pu = to_scene_update(*parts);
+    const mcpt_status st = parts ? mcpt_update_parts_reproject(ctx, &pu, camera ? &k : nullptr, &o)
+                          : time ? mcpt_update_keyframes_reproject(ctx, *time, camera ? &k : nullptr, &o)
                        : weights ? mcpt_update_morph_reproject(ctx, weights->data(), uint32_t(weights->size()), matrices ? matrices->data() : nullptr,
                                                                  matrices ? uint32_t(matrices->size() / 12) : 0u, camera ? &k : nullptr, &o)
                          : m ? mcpt_update_vertices_reproject(ctx, reinterpret_cast<const double*>(m->vertex.data()), uint32_t(m->vertex.size()),
@@ -176,7 +181,7 @@ bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>*
                      : bones ? mcpt_update_skin_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o)
                              : mcpt_update_transforms_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o);
     if (st != MCPT_OK) {
-        std::cerr << "Error: mcpt_" << (m ? "update_vertices_reproject" : time ? "update_keyframes_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
+        std::cerr << "Error: mcpt_" << (parts ? "update_parts_reproject" : m ? "update_vertices_reproject" : time ? "update_keyframes_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
         if (upload && mcpt_clear_accum(ctx) != MCPT_OK) std::cerr << "Error: mcpt_clear_accum: " << mcpt_last_error() << std::endl;   // the Scene still holds them
         return false;
     }
@@ -199,16 +204,18 @@ bool Render::rebuild(Scene&, uint32_t builder) {
     if (mcpt_rebuild_trees(ctx, &o) != MCPT_OK) { std::cerr << "Error: mcpt_rebuild_trees: " << mcpt_last_error() << std::endl; return false; }
     return true;
 }
-// One group per vertex and per normal from one per face: whatever a face of group g uses belongs to g; what no face uses, to group 0.
-static bool groups_of(const std::vector<imat3x4>& face, const std::vector<uint32_t>& face_group, int column, size_t n, const char* what, std::vector<uint32_t>& out) {
+// One group per vertex and per normal from one per face: whatever a face of group g uses belongs to g; what no face uses, to group 0.  (§23: the
+// same for owners -- `fn` and `kind` name the caller and its ids in the messages.)
+static bool groups_of(const std::vector<imat3x4>& face, const std::vector<uint32_t>& face_group, int column, size_t n, const char* what, std::vector<uint32_t>& out,
+                      const char* fn = "set_groups", const char* kind = "groups") {
     const uint32_t none = ~0u;
     out.assign(n, none);
     for (size_t f = 0; f < face.size(); f++)
         for (int c = 0; c < 3; c++) {
             const int i = face[f][c][column];
-            if (i < 0 || size_t(i) >= n) { std::cerr << "Error: Render::set_groups: face " << f << " names a " << what << " out of range" << std::endl; return false; }
+            if (i < 0 || size_t(i) >= n) { std::cerr << "Error: Render::" << fn << ": face " << f << " names a " << what << " out of range" << std::endl; return false; }
             if (out[size_t(i)] != none && out[size_t(i)] != face_group[f]) {
-                std::cerr << "Error: Render::set_groups: " << what << " " << i << " is used by faces of groups " << out[size_t(i)] << " and " << face_group[f]
+                std::cerr << "Error: Render::" << fn << ": " << what << " " << i << " is used by faces of " << kind << " " << out[size_t(i)] << " and " << face_group[f]
                           << " (duplicate it in the file)" << std::endl;
                 return false;
             }
@@ -227,6 +234,38 @@ bool Render::set_groups(Scene&, Model& m, const std::vector<uint32_t>& face_grou
         std::cerr << "Error: mcpt_set_vertex_groups: " << mcpt_last_error() << std::endl; return false;
     }
     return true;
+}
+// §23.  A record no face uses gets owner 0, MCPT_OWNER_NONE: groups_of's default is the right one.
+bool Render::set_owners(Scene&, Model& m, const std::vector<uint8_t>& face_owner) {
+    if (!ctx) return false;
+    if (face_owner.size() != m.face.size() || face_owner.empty()) { std::cerr << "Error: Render::set_owners: need one owner per face" << std::endl; return false; }
+    const std::vector<uint32_t> wide(face_owner.begin(), face_owner.end());
+    std::vector<uint32_t> vo, no;
+    if (!groups_of(m.face, wide, 0, m.vertex.size(), "vertex", vo, "set_owners", "owners") || !groups_of(m.face, wide, 1, m.normal.size(), "normal", no, "set_owners", "owners")) return false;
+    const std::vector<uint8_t> v8(vo.begin(), vo.end()), n8(no.begin(), no.end());
+    if (mcpt_set_vertex_owners(ctx, v8.data(), uint32_t(v8.size()), n8.data(), uint32_t(n8.size())) != MCPT_OK) {
+        std::cerr << "Error: mcpt_set_vertex_owners: " << mcpt_last_error() << std::endl; return false;
+    }
+    return true;
+}
+static mcpt_scene_update to_scene_update(const PartsUpdate& u) {
+    mcpt_scene_update p; std::memset(&p, 0, sizeof p);
+    p.struct_size = sizeof p; p.routes = u.routes; p.flags = u.flags; p.time = u.time;
+    p.group_m3x4 = u.group_matrices.empty() ? nullptr : u.group_matrices.data(); p.n_groups = uint32_t(u.group_matrices.size() / 12);
+    p.bone_m3x4 = u.bone_matrices.empty() ? nullptr : u.bone_matrices.data(); p.n_bones = uint32_t(u.bone_matrices.size() / 12);
+    p.morph_weight = u.morph_weights.empty() ? nullptr : u.morph_weights.data(); p.n_targets = uint32_t(u.morph_weights.size());
+    return p;
+}
+bool Render::update_parts(Scene& scene, const PartsUpdate& update) {
+    if (!ctx) return false;
+    if (update.group_matrices.size() % 12 || update.bone_matrices.size() % 12) { std::cerr << "Error: Render::update_parts: need 12 doubles per group and per bone" << std::endl; return false; }
+    const mcpt_scene_update p = to_scene_update(update);
+    if (mcpt_update_parts(ctx, &p) != MCPT_OK) { std::cerr << "Error: mcpt_update_parts: " << mcpt_last_error() << std::endl; return false; }
+    return restart(scene);
+}
+bool Render::update_parts_reproject(Scene& scene, const PartsUpdate& update, float max_history) { return update_reproject(scene, nullptr, nullptr, false, nullptr, nullptr, max_history, nullptr, &update); }
+bool Render::update_parts_reproject(Scene& scene, const PartsUpdate& update, const CameraInfo& camera, float max_history) {
+    return update_reproject(scene, nullptr, nullptr, false, nullptr, &camera, max_history, nullptr, &update);
 }
 bool Render::update_transforms(Scene& scene, const std::vector<double>& matrices) {
     if (!ctx) return false;

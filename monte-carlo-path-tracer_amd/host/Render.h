@@ -8,6 +8,9 @@
 
 // One morph target: the records it displaces, strictly ascending, and 3 doubles of displacement per record.
 struct MorphTarget { std::vector<uint32_t> index; std::vector<double> delta; };
+// One parts update: the routes that run (MCPT_ROUTE_*), the flags (MCPT_PARTS_MORPH_THEN_SKIN) and the payloads of those routes --
+// update_transforms' matrices, update_skin's (also the skin behind the morph), update_morph's weights, update_keyframes' time.
+struct PartsUpdate { uint32_t routes = 0, flags = 0; std::vector<double> group_matrices, bone_matrices, morph_weights; double time = 0.0; };
 
 class Render : public FilmSource {
 public:
@@ -105,6 +108,15 @@ public:
     bool update_keyframes(Scene& scene, double time);
     bool update_keyframes_reproject(Scene& scene, double time, float max_history = 0);
     bool update_keyframes_reproject(Scene& scene, double time, const CameraInfo& camera, float max_history = 0);
+    // Each part driven by its own deformer in one call.  set_owners: one owner id (MCPT_OWNER_*) per face of `m_model`, the Model
+    // this Render was made from (MCPT_FLAG_DYNAMIC): the one route of update_parts that writes the vertices and normals the face uses (what no
+    // face uses: MCPT_OWNER_NONE); false when faces of two owners share a vertex or a normal.  The film is not touched.  update_parts: the routes
+    // of `update` run on the device, each writing only the records it owns, then one normals pass and one refit (mcpt_update_parts).  Starts the
+    // picture again like update(); update_parts_reproject carries it over like update_reproject.  false (Render and Scene unchanged) on failure.
+    bool set_owners(Scene& scene, Model& m_model, const std::vector<uint8_t>& face_owner);
+    bool update_parts(Scene& scene, const PartsUpdate& update);
+    bool update_parts_reproject(Scene& scene, const PartsUpdate& update, float max_history = 0);
+    bool update_parts_reproject(Scene& scene, const PartsUpdate& update, const CameraInfo& camera, float max_history = 0);
     // Smooth normals recomputed on the device after every update.  set_auto_normals: one flag per face of `m_model`, the Model this
     // Render was made from (MCPT_FLAG_DYNAMIC); the normal records that the flagged faces name (an empty face_mask: all records) are from now
     // on recomputed from the deformed faces by every update*() call -- area-weighted, overriding what the call itself wrote for them, Model::normal
@@ -135,7 +147,7 @@ private:
     bool restart(Scene& scene);
     bool film_to_device(Scene& scene, const char* who, bool& ok);
     bool update_reproject(Scene& scene, Model* m_model, const std::vector<double>* matrices, bool bones, const std::vector<double>* weights, const CameraInfo* camera,
-                          float max_history, const double* time = nullptr);
+                          float max_history, const double* time = nullptr, const PartsUpdate* parts = nullptr);
 };
 // Fills an mcpt_scene_desc that points INTO `m` (and into the two scratch vectors); valid while all three live.
 void model_to_desc(Model& m, std::vector<mcpt_material>& mats, std::vector<mcpt_texture>& texs, mcpt_scene_desc& d);

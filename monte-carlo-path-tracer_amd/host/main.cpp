@@ -36,17 +36,20 @@ static void usage() {
                  "                                        (materials and light list edited on the device, the film restarts every frame; not with --reproject)\n"
                  "                          [--spin MTLNAME]   with --turntable: the faces of that material turn as one rigid part, by 360 k / N degrees in frame k about\n"
                  "                                        the camera's up axis through their bounding box's centre (one 3x4 matrix per frame, applied on the device;\n"
-                 "                                        honours --reproject; not with --wobble)\n"
+                 "                                        honours --reproject; not with --wobble).  --spin may be given together with --bend and / or --swell, for\n"
+                 "                                        different materials that share no vertex and no normal: each part is then driven by its own deformer and every\n"
+                 "                                        frame is ONE parts update (DESIGN.md 23) -- --spin's faces by the groups, --bend's / --swell's by the skin\n"
+                 "                                        (--bend alone) or the morph; nothing else moves\n"
                  "                          [--bend MTLNAME DEG]   with --turntable: the faces of that material bend as a two-bone part (linear-blend skinning on the\n"
                  "                                        device): a vertex follows the upper bone by its height inside the part's y-extent, the lower bone stays,\n"
                  "                                        the upper one turns by DEG sin(2 pi k / N) about z through the part's centre in frame k (honours --reproject;\n"
-                 "                                        not with --wobble or --spin)\n"
+                 "                                        not with --wobble)\n"
                  "                          [--dual-quat]   with --bend: the bones are blended as unit dual quaternions instead of matrices (DESIGN.md 21): the bent\n"
                  "                                        part keeps its volume however far it turns; the bones must be rigid, as --bend's are\n"
                  "                          [--swell MTLNAME AMOUNT]   with --turntable: the faces of that material swell and shrink about the centroid of their\n"
                  "                                        vertices (one morph target on the device, delta = vertex - centroid, weight AMOUNT sin(2 pi k / N) in frame k:\n"
                  "                                        a uniform scaling, so the normals stay); combines with --bend (morph, then skin, one call per frame);\n"
-                 "                                        honours --reproject; not with --wobble or --spin\n"
+                 "                                        honours --reproject; not with --wobble\n"
                  "                          [--sequence PATTERN COUNT [--slowdown S] [--smooth]]   with --turntable: baked vertex animation from an OBJ sequence.  PATTERN\n"
                  "                                        holds one printf integer conversion (cloth_%04d.obj); frames 0 .. COUNT - 1 are loaded, each with the scene's\n"
                  "                                        vertex and normal counts and its faces, and uploaded once as keyframes one time unit apart (DESIGN.md 22);\n"
@@ -130,12 +133,15 @@ int main(int argc, char** argv) {
     if (pulse && (!turntable || !(std::fabs(pulse_a) <= 1e6))) { std::cerr << "Error: --light-pulse A needs --turntable N and a finite A" << std::endl; return 2; }
     if (pulse && reproject) { std::cerr << "Error: --light-pulse restarts the film every frame: radiance reprojected across it would be the old light's (drop --reproject)" << std::endl; return 2; }
     if (!spin.empty() && (!turntable || wobble)) { std::cerr << "Error: --spin MTLNAME needs --turntable N and no --wobble (both write the vertices)" << std::endl; return 2; }
-    if (!bend.empty() && (!turntable || wobble || !spin.empty() || !(std::fabs(bend_deg) <= 1e6))) {
-        std::cerr << "Error: --bend MTLNAME DEG needs --turntable N, a finite DEG and neither --wobble nor --spin (all three write the vertices)" << std::endl; return 2;
+    if (!bend.empty() && (!turntable || wobble || !(std::fabs(bend_deg) <= 1e6))) {
+        std::cerr << "Error: --bend MTLNAME DEG needs --turntable N, a finite DEG and no --wobble (which writes every vertex)" << std::endl; return 2;
+    }
+    if (!spin.empty() && (spin == bend || spin == swell)) {
+        std::cerr << "Error: --spin and --" << (spin == bend ? "bend" : "swell") << " name the same material (" << spin << "): a face has one deformer" << std::endl; return 2;
     }
     if (dual_quat && bend.empty()) { std::cerr << "Error: --dual-quat needs --bend MTLNAME DEG (it chooses how --bend's bones are blended)" << std::endl; return 2; }
-    if (!swell.empty() && (!turntable || wobble || !spin.empty() || !(std::fabs(swell_a) <= 1e6))) {
-        std::cerr << "Error: --swell MTLNAME AMOUNT needs --turntable N, a finite AMOUNT and neither --wobble nor --spin (all three write the vertices)" << std::endl; return 2;
+    if (!swell.empty() && (!turntable || wobble || !(std::fabs(swell_a) <= 1e6))) {
+        std::cerr << "Error: --swell MTLNAME AMOUNT needs --turntable N, a finite AMOUNT and no --wobble (which writes every vertex)" << std::endl; return 2;
     }
     if ((slowdown_set || smooth) && sequence.empty()) { std::cerr << "Error: --slowdown S and --smooth need --sequence PATTERN COUNT (they choose how it is played)" << std::endl; return 2; }
     if (!sequence.empty()) {
@@ -238,7 +244,7 @@ int main(int argc, char** argv) {
         if (!(ul > 0.0)) { std::cerr << "Error: --turntable needs a camera with an up vector" << std::endl; return 1; }
         const double k[3] = {base.up.x / ul, base.up.y / ul, base.up.z / ul}, v[3] = {base.eye.x - base.lookat.x, base.eye.y - base.lookat.y, base.eye.z - base.lookat.z};
         // --spin MTLNAME: that material's faces are group 1, everything else group 0
-        double pivot[3] = {0.0, 0.0, 0.0};
+        double pivot[3] = {0.0, 0.0, 0.0}, spin_pivot[3] = {0.0, 0.0, 0.0};
         if (!spin.empty()) {
             const int mtl = model.material_index(spin);
             if (mtl < 0) { std::cerr << "Error: --spin: no material named " << spin << std::endl; return 1; }
@@ -256,7 +262,7 @@ int main(int argc, char** argv) {
                 }
             }
             if (!n_spin) { std::cerr << "Error: --spin: no face uses material " << spin << std::endl; return 1; }
-            for (int a = 0; a < 3; a++) pivot[a] = 0.5 * (lo[a] + hi[a]);
+            for (int a = 0; a < 3; a++) spin_pivot[a] = 0.5 * (lo[a] + hi[a]);
             if (!renders[0]->set_groups(scene, model, face_group)) return 1;
         }
         // --bend MTLNAME DEG: that material's faces follow bones 1 and 2 by height, everything else bone 0
@@ -320,6 +326,45 @@ int main(int argc, char** argv) {
         // --sequence PATTERN COUNT: the frames go to the device once, one time unit apart; past the last one the last frame stays
         if (!sequence.empty() && !renders[0]->set_keyframes(scene, model, seq_vertex, seq_normal, 0.0, 1.0, smooth ? MCPT_KEYFRAMES_CATMULL_ROM : MCPT_KEYFRAMES_LINEAR,
                                                             MCPT_KEYFRAMES_CLAMP)) return 1;
+        // --spin with --bend and / or --swell: every record gets the one route that writes it and every frame below is one parts
+        // update.  Without --spin, or with --spin alone, the CLI makes exactly the calls it always made.
+        const bool parts = !spin.empty() && (!bend.empty() || !swell.empty());
+        const uint32_t deform_owner = swell.empty() ? MCPT_OWNER_SKIN : MCPT_OWNER_MORPH;        // --bend alone: the skin; otherwise the morph (with --bend: morph, then skin)
+        if (parts) {
+            const int spin_mtl = spin.empty() ? -1 : model.material_index(spin), bend_mtl = bend.empty() ? -1 : model.material_index(bend),
+                      swell_mtl = swell.empty() ? -1 : model.material_index(swell);
+            std::vector<uint8_t> face_owner(model.face.size(), uint8_t(MCPT_OWNER_NONE));
+            for (size_t i = 0; i < model.face.size(); i++) {
+                const int mtl = model.face[i][0][3];
+                if (mtl >= 0 && mtl == spin_mtl) face_owner[i] = uint8_t(MCPT_OWNER_GROUPS);
+                else if (mtl >= 0 && (mtl == bend_mtl || mtl == swell_mtl)) face_owner[i] = uint8_t(deform_owner);
+            }
+            // (faces of two owners that share a vertex or a normal: set_owners names the record and refuses)
+            if (!renders[0]->set_owners(scene, model, face_owner)) return 1;
+        }
+        // --spin: Rodrigues as a matrix, R = cos a I + sin a [k]x + (1 - cos a) k k^T, about the pivot; group 0 stays
+        auto spin_matrices = [&](double ca, double sa) {
+            const double R[3][3] = {{ca + k[0] * k[0] * (1.0 - ca), k[0] * k[1] * (1.0 - ca) - k[2] * sa, k[0] * k[2] * (1.0 - ca) + k[1] * sa},
+                                    {k[1] * k[0] * (1.0 - ca) + k[2] * sa, ca + k[1] * k[1] * (1.0 - ca), k[1] * k[2] * (1.0 - ca) - k[0] * sa},
+                                    {k[2] * k[0] * (1.0 - ca) - k[1] * sa, k[2] * k[1] * (1.0 - ca) + k[0] * sa, ca + k[2] * k[2] * (1.0 - ca)}};
+            std::vector<double> m(24, 0.0);
+            m[0] = m[5] = m[10] = 1.0;
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) m[12 + 4 * r + c] = R[r][c];
+                m[12 + 4 * r + 3] = spin_pivot[r] - (R[r][0] * spin_pivot[0] + R[r][1] * spin_pivot[1] + R[r][2] * spin_pivot[2]);
+            }
+            return m;
+        };
+        // --bend: bones 0 and 1 stay; bone 2 turns about z through the part's centre
+        auto bend_matrices = [&](double sa) {
+            const double b = bend_deg * 3.14159265358979323846 / 180.0 * sa, cb = std::cos(b), sb = std::sin(b);
+            std::vector<double> m(36, 0.0);
+            for (int g = 0; g < 3; g++) m[12 * g] = m[12 * g + 5] = m[12 * g + 10] = 1.0;
+            double* u = m.data() + 24;
+            u[0] = cb; u[1] = -sb; u[3] = pivot[0] - (cb * pivot[0] - sb * pivot[1]);
+            u[4] = sb; u[5] = cb; u[7] = pivot[1] - (sb * pivot[0] + cb * pivot[1]);
+            return m;
+        };
         // --auto-normals: every update below is followed by the normals pass -- over all normals with --wobble and --sequence, which
         // move every vertex, otherwise over the normals of the faces of --bend's and --swell's materials
         if (auto_normals) {
@@ -359,29 +404,24 @@ int main(int argc, char** argv) {
                 }
                 model.camerainfo = cam;
                 if (reproject ? !renders[0]->update_reproject(scene, model, cam, history) : !renders[0]->update(scene, model)) return 1;
+            } else if (parts) {                                              // one call per frame: each route's payload is what its own branch below sends
+                PartsUpdate u;
+                u.routes |= MCPT_ROUTE_GROUPS; u.group_matrices = spin_matrices(ca, sa);
+                if (!bend.empty()) u.bone_matrices = bend_matrices(sa);
+                if (!swell.empty()) { u.routes |= MCPT_ROUTE_MORPH; u.morph_weights = {swell_a * sa}; if (!bend.empty()) u.flags |= MCPT_PARTS_MORPH_THEN_SKIN; }
+                else if (!bend.empty()) u.routes |= MCPT_ROUTE_SKIN;
+                Render& r0 = *renders[0];
+                if (reproject && f > 0 ? !r0.update_parts_reproject(scene, u, cam, history) : !(r0.update_parts(scene, u) && r0.set_camera(scene, cam))) return 1;
             } else if (!sequence.empty()) {                                  // --sequence: turntable frame j plays time j / S; only that number crosses the bus
                 const double time = double(f) / slowdown;
                 Render& r0 = *renders[0];
                 if (reproject && f > 0 ? !r0.update_keyframes_reproject(scene, time, cam, history) : !(r0.update_keyframes(scene, time) && r0.set_camera(scene, cam))) return 1;
-            } else if (!spin.empty()) {                                      // Rodrigues as a matrix: R = cos a I + sin a [k]x + (1 - cos a) k k^T, about the pivot
-                const double R[3][3] = {{ca + k[0] * k[0] * (1.0 - ca), k[0] * k[1] * (1.0 - ca) - k[2] * sa, k[0] * k[2] * (1.0 - ca) + k[1] * sa},
-                                        {k[1] * k[0] * (1.0 - ca) + k[2] * sa, ca + k[1] * k[1] * (1.0 - ca), k[1] * k[2] * (1.0 - ca) - k[0] * sa},
-                                        {k[2] * k[0] * (1.0 - ca) - k[1] * sa, k[2] * k[1] * (1.0 - ca) + k[0] * sa, ca + k[2] * k[2] * (1.0 - ca)}};
-                std::vector<double> m(24, 0.0);
-                m[0] = m[5] = m[10] = 1.0;                                   // group 0 stays
-                for (int r = 0; r < 3; r++) {
-                    for (int c = 0; c < 3; c++) m[12 + 4 * r + c] = R[r][c];
-                    m[12 + 4 * r + 3] = pivot[r] - (R[r][0] * pivot[0] + R[r][1] * pivot[1] + R[r][2] * pivot[2]);
-                }
+            } else if (!spin.empty()) {
+                const std::vector<double> m = spin_matrices(ca, sa);
                 if (reproject && f > 0 ? !renders[0]->update_transforms_reproject(scene, m, cam, history)
                                        : !(renders[0]->update_transforms(scene, m) && renders[0]->set_camera(scene, cam))) return 1;
-            } else if (!bend.empty() || !swell.empty()) {                    // bones 0 and 1 stay; bone 2 turns about z through the part's centre
-                const double b = bend_deg * 3.14159265358979323846 / 180.0 * sa, cb = std::cos(b), sb = std::sin(b);
-                std::vector<double> m(36, 0.0);
-                for (int g = 0; g < 3; g++) m[12 * g] = m[12 * g + 5] = m[12 * g + 10] = 1.0;
-                double* u = m.data() + 24;
-                u[0] = cb; u[1] = -sb; u[3] = pivot[0] - (cb * pivot[0] - sb * pivot[1]);
-                u[4] = sb; u[5] = cb; u[7] = pivot[1] - (sb * pivot[0] + cb * pivot[1]);
+            } else if (!bend.empty() || !swell.empty()) {
+                const std::vector<double> m = bend_matrices(sa);
                 const std::vector<double> weights{swell_a * sa};             // --swell: the one target's weight (with --bend: morph, then skin, in one call)
                 Render& r0 = *renders[0];
                 if (!swell.empty() && !bend.empty()) {
