@@ -166,6 +166,7 @@ struct mcpt_ctx {
         std::vector<Event> k_ev;           // per-kernel event chain (only with detailed timing)
         Stream stream;
         Event done_ev;
+        Event shade_ev;                    // recorded after each shade launch of a gated sub-pipeline: what the next one's shade launch waits for (wf_plan.h: wf_shade_wait)
         uint64_t last_iterations = 0, last_timed = 0;
         // Known-length jobs (every item has its own slot and one sample, depth-limited: wf_plan_call) are enqueued whole and NOT waited for:
         // the control-block snapshot taken after their last iteration is looked at later -- by the next call that drains the stream, or when the
@@ -552,6 +553,7 @@ static mcpt_status finish_ctx(mcpt_ctx* c) {
                 L.chk_ev.resize(8);
                 for (auto& ev : L.chk_ev) HIP_TRY(hipEventCreateWithFlags(ev.out(), hipEventDisableTiming));
                 HIP_TRY(hipEventCreateWithFlags(L.done_ev.out(), hipEventDisableTiming));
+                HIP_TRY(hipEventCreateWithFlags(L.shade_ev.out(), hipEventDisableTiming));
                 HIP_TRY(hipStreamCreateWithFlags(L.stream.out(), hipStreamNonBlocking));
                 // the global overflow area of the traversal stack is sized from the wide tree's depth (2 x depth + 3 entries of 8 B per trace lane): a
                 // pathologically deep device-built tree (depth in the hundreds) would ask for a GB per sub-pipeline -- refuse instead of allocating it
@@ -970,6 +972,9 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, const RenderParams& p0, float
         HIP_TRY(hipStreamWaitEvent(L.stream, ctx->fork_ev, 0));
         HIP_TRY(launch_wf_pool_reset(runs[k].pool, L.ctl_buf.p, L.stream));   // every slot DEAD, control block zeroed
     }
+    // the shade interlock (wf_plan.h): `last_shade` recorded the latest shade event of THIS call, so every wait names an event already enqueued
+    auto state_of = [&](uint32_t j) { return WfLaneState{runs[j].done, runs[j].grid}; };
+    int last_shade = WF_NO_LANE; uint32_t n_waits = 0;
     bool all_done = plan.n_active == 0;
     while (!all_done) {
         all_done = true;
@@ -979,8 +984,11 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, const RenderParams& p0, float
             const WfLanePlan& lp = plan.lanes[k]; mcpt_ctx::WfLane& L = ctx->lanes[k];
             IterCtl* ctl = L.ctl_buf.p;
             const bool timed = knobs.time_kernels && r.it % knobs.time_kernels == 0;
+            const int wait_for = wf_shade_wait(plan, p0, knobs, k, state_of, last_shade);
+            if (wait_for != WF_NO_LANE) { HIP_TRY(hipStreamWaitEvent(L.stream, ctx->lanes[wait_for].shade_ev, 0)); n_waits++; }   // (ahead of the first kernel event: the sampled shade time stays the kernel's)
             HIP_TRY(wf_k_event(L, r, timed));
             HIP_TRY(launch_wf_shade(ctx->dev, lp.p, r.pool, ctl, r.it, lp.n_shared, accum, cnt, L.stream));
+            if (wf_lane_gated(plan, p0, knobs, k, state_of(k))) { HIP_TRY(hipEventRecord(L.shade_ev, L.stream)); last_shade = int(k); }
             HIP_TRY(wf_k_event(L, r, timed));
             HIP_TRY(launch_wf_trace(ctx->dev, r.pool, ctl, r.it, ctx->tune, count, cnt, r.grid, L.ovf_buf.p, L.stream));
             HIP_TRY(wf_k_event(L, r, timed));
@@ -1009,6 +1017,7 @@ static mcpt_status render_wavefront(mcpt_ctx* ctx, const RenderParams& p0, float
             if (!r.done) all_done = false;
         }
     }
+    if (knobs.debug) fprintf(stderr, "[wf] interlock waits=%u\n", n_waits);
     for (uint32_t k = 0; k < n_lanes; k++) {
         if (!plan.lanes[k].active) continue;
         mcpt_ctx::WfLane& L = ctx->lanes[k];

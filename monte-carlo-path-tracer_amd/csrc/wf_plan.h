@@ -1,6 +1,6 @@
 // The wavefront scheduler's DECISIONS: what a render call's shape (tiles, samples, sub-pipelines, knobs) makes of it, as data and pure functions.
 // Nothing here touches a device, the HIP runtime, a context or the environment (wavefront.h is included for RenderParams and the block
-// constants): tests/wf_plan_check.cpp runs every plan on the CPU.  mcpt_api.cpp executes a plan.
+// constants): tests/wf_plan_check.cpp runs every plan on the CPU, tests/wf_interlock_check.cpp the shade interlock's decisions.  mcpt_api.cpp executes a plan.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -9,6 +9,8 @@
 #include "../../include/mcpt.h"
 #include "wavefront.h"
 
+constexpr uint32_t WF_INTERLOCK_DEFAULT = 1;      // MCPT_WF_INTERLOCK where it is unset (the measurement behind it)
+
 // What the scheduler takes from the environment (developer knobs): read ONCE per context, by wf_read_knobs.
 struct WfKnobs {
     uint32_t pool_cap;                 // most slots a sub-pipeline's pool may have (MCPT_WF_POOL_LOG2, _SLOTS); pools are allocated on first use, sized to the job
@@ -16,6 +18,7 @@ struct WfKnobs {
     bool private_items, small_job_split, compact, debug;   // MCPT_WF_PRIVATE_ITEMS, _SMALL_JOB_SPLIT (both: wf_plan_call), _COMPACT (drain compaction), _DEBUG (snapshots on stderr)
     uint32_t compact_eighths, max_it;  // MCPT_WF_COMPACT_EIGHTHS: compact when at most this many eighths of the swept slots are alive; MCPT_WF_MAXIT: iteration cap of the host loop
     uint32_t time_kernels;             // MCPT_TIME_KERNELS=N: bracket the two kernels of every Nth iteration with HIP events (0 = off)
+    bool interlock;                    // MCPT_WF_INTERLOCK: the sub-pipelines' shade launches run one after the other (wf_shade_wait)
 };
 template <class Env> WfKnobs wf_read_knobs(Env env) {      // env(name, default): the variable as a number, the default where it is unset
     WfKnobs k;
@@ -26,6 +29,7 @@ template <class Env> WfKnobs wf_read_knobs(Env env) {      // env(name, default)
     k.private_items = env("MCPT_WF_PRIVATE_ITEMS", 1) != 0; k.small_job_split = env("MCPT_WF_SMALL_JOB_SPLIT", 1) != 0;
     k.compact = env("MCPT_WF_COMPACT", 1) != 0; k.compact_eighths = std::max(1u, std::min(7u, uint32_t(env("MCPT_WF_COMPACT_EIGHTHS", 4))));
     k.max_it = env("MCPT_WF_MAXIT", 1u << 20); k.debug = env("MCPT_WF_DEBUG", 0) != 0; k.time_kernels = env("MCPT_TIME_KERNELS", 0);
+    k.interlock = env("MCPT_WF_INTERLOCK", WF_INTERLOCK_DEFAULT) != 0;
     return k;
 }
 
@@ -142,4 +146,36 @@ inline WfPlan wf_plan_call(const RenderParams& p0, uint32_t n_lanes, const WfKno
     plan.shared_grid = std::max(1u, trace_grid / std::max(1u, plan.n_active));
     for (WfLanePlan& r : plan.lanes) if (r.active) r.grid = (plan.small_job && !p0.probe_n && r.n_items <= plan.small_job) ? plan.shared_grid : trace_grid;
     return plan;
+}
+
+// The shade interlock.  Left alone, the sub-pipelines fall into step: their shade launches run beside each other (VALUs waiting on HBM) and then their
+// trace launches queue for each other's CUs with no shade beside them.  With the interlock the shade launches of the gated sub-pipelines
+// run strictly one after the other, in the round-robin order in which the executor enqueues them: the shade launch of sub-pipeline k waits (on k's stream)
+// for an event recorded right after the shade launch enqueued just before it, which belongs to the previous gated sub-pipeline in round order.  Each
+// sub-pipeline's trace launch then sits between its own two shade launches, i.e. beside the other's shade.  Trace launches are never gated: a queued trace
+// launch takes CUs as the other's blocks retire, which keeps the tail of one overlapped with the head of the next.
+// No deadlock: a wait only ever names `last`, the sub-pipeline whose event the executor recorded most recently -- earlier in host enqueue order.
+struct WfLaneState { bool done; uint32_t grid; };   // what the executor knows of a running sub-pipeline: its job has finished; blocks of its trace launches now
+constexpr int WF_NO_LANE = -1;
+// the call as a whole: off for a single active sub-pipeline, a probe and deterministic mode
+inline bool wf_interlock_call(const WfPlan& plan, const RenderParams& p0, const WfKnobs& knobs) {
+    return knobs.interlock && plan.n_active >= 2 && !p0.probe_n && !(p0.flags & MCPT_FLAG_DETERMINISTIC);
+}
+// one sub-pipeline: gated while it is live, polled (a known-length job is enqueued whole and not waited for), on the full trace grid (on shared_grid --
+// a small job, or a draining one after wf_poll saw its compacted sweep -- the chains run side by side by design) and working off more items than it has
+// slots.  A job with a slot per item starts every path in iteration 0 and only drains from there: a chain of dependent launches that get shorter, no
+// steady state to put in order (the display loop's 4-sample call, 800 x 800: 3.95 ms without the interlock, 4.16 ms with).  It records its event iff it is gated.
+inline bool wf_lane_gated(const WfPlan& plan, const RenderParams& p0, const WfKnobs& knobs, uint32_t k, WfLaneState s) {
+    const WfLanePlan& lp = plan.lanes[k];
+    return wf_interlock_call(plan, p0, knobs) && lp.active && !s.done && lp.bound == 0 && lp.n_items > lp.P && s.grid != plan.shared_grid;
+}
+// The sub-pipeline whose latest shade event the next shade launch of sub-pipeline k waits for, or WF_NO_LANE.  state_of(j): WfLaneState of sub-pipeline j;
+// last: the sub-pipeline that recorded the latest shade event of this call (WF_NO_LANE: none yet).  A sub-pipeline that has finished or left the full grid
+// since it recorded is not waited for: the chain is broken for that one launch, which may run beside an earlier shade launch, and is formed again by the next.
+template <class StateOf> int wf_shade_wait(const WfPlan& plan, const RenderParams& p0, const WfKnobs& knobs, uint32_t k, StateOf state_of, int last) {
+    if (!wf_lane_gated(plan, p0, knobs, k, state_of(k))) return WF_NO_LANE;
+    uint32_t gated = 0;
+    for (uint32_t j = 0; j < plan.lanes.size(); j++) gated += wf_lane_gated(plan, p0, knobs, j, state_of(j));
+    if (gated < 2 || last < 0 || uint32_t(last) == k || !wf_lane_gated(plan, p0, knobs, uint32_t(last), state_of(uint32_t(last)))) return WF_NO_LANE;
+    return last;
 }
