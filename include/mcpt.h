@@ -870,7 +870,7 @@ mcpt_status mcpt_get_normals_info(mcpt_ctx* ctx, mcpt_normals_info* out);   /* s
  *    rank it has (the creation geometry's, as mcpt_update_vertices documents).
  *  - KEPT, because the scene looks the same from every pixel: the film or a bound accumulator, the counters, the stream binding, the camera, the
  *    feature buffers and the denoised film, the adaptive tile error, the reprojection buffers, the vertex groups with their rest pose and R_g,
- *    the skin with its rest pose and R_b, the morph targets with their rest pose, R and D_k (and the morph-then-skin scratch), the keyframes with their options and captured pose (§22), the owners of the parts update (§23: per record, not per leaf), the auto-normals lists (§20: they are per face of the description, not per leaf), the materials, the textures, and the light list's membership and order (only the lights' leaf-order
+ *    the skin with its rest pose and R_b, the morph targets with their rest pose, R and D_k (and the morph-then-skin scratch), the keyframes with their options and captured pose (§22), the owners of the parts update (§23: per record, not per leaf), the auto-normals lists (§20: they are per face of the description, not per leaf), the visibility mask (§24: per face too; the builders see a hidden face with the bounds of its vertices, the permuted streams keep it hidden, the next update tightens the boxes again), the materials, the textures, and the light list's membership and order (only the lights' leaf-order
  *    triangle index is renumbered).
  *  - Afterwards mcpt_update_info::wide_area_ratio is 1.0 (its base is the new tree) and `updates` is unchanged; mcpt_scene_info follows the new
  *    trees: n_nodes, bvh_depth, max_leaf, wide_nodes, wide_depth, traversal_bytes, wide_tree_hash, bvh_builder, and device_bytes counts what is
@@ -894,6 +894,57 @@ typedef struct mcpt_rebuild_info {
 } mcpt_rebuild_info;
 mcpt_status mcpt_rebuild_trees(mcpt_ctx* ctx, const mcpt_rebuild_opts* opts /* NULL = defaults */);
 mcpt_status mcpt_get_rebuild_info(mcpt_ctx* ctx, mcpt_rebuild_info* out);
+
+/* ---- live scenes: faces shown and hidden on the device ------------------------------------------------------------------------ */
+/* The face list of a context is fixed at mcpt_create; which of those faces EXIST for the rays is not.  A context holds one visibility byte per
+ * face of the description, in Model::face order (!= 0 = visible).  A door taken away, a prop that pops in on frame 40, a lamp switched off as
+ * geometry: one call, no new upload, no new trees, the film kept.  All calls need MCPT_FLAG_DYNAMIC (else MCPT_ERR_UNSUPPORTED).
+ *
+ * The mask is STICKY: every later scene update, by any route (mcpt_update_vertices, _transforms, _skin, _morph, _keyframes, _parts, _normals and
+ * their _reproject forms), applies it again.  With no mask set every call enqueues exactly the kernels it enqueues without this section.  After
+ * any update on a context with a mask, for every triangle whose face is hidden: record 0 of its intersection stream (first corner, lobe class,
+ * tie rank) is what the update wrote; both edge records are {+0, +0, +0, 0}, so the determinant of the one triangle test every kernel shares is
+ * exactly +-0 for every ray and NO kernel of the library -- wavefront trace, binary cross-check, first hit, features -- can accept it; its refit
+ * box is the point of its first corner, so it no longer inflates its ancestors' boxes and mcpt_probe_validate_trees stays sound; its shading
+ * records and fp64 corners stay as the update wrote them.  Visible triangles hold, bit for bit, what they hold without a mask.
+ *
+ * The light list's membership becomes |radiance| > 0.01 AND visible, still in face order; it is rebuilt on the device whenever the mask changes,
+ * and mcpt_update_materials on a context with a mask applies the same rule.  A call -- of either kind -- that would leave no visible light is
+ * refused with MCPT_ERR_NO_LIGHTS and changes nothing.  mcpt_scene_info::n_lights and mcpt_material_info::n_lights follow the list.
+ *
+ * mcpt_set_face_visibility: `visible` = n_face bytes, or NULL = every face visible and the mask freed (device_bytes is what it was before the
+ * first call, but for the 4 B per face + 4 B per 256 faces of scan scratch that mcpt_update_materials also allocates on first use and that stay).
+ * The bytes are copied before the call returns (staged in pinned memory, sent in stream order).  The call IS a scene update without a source: no
+ * vertex moves; the triangle streams are rewritten from the vertices as they are, the hidden faces hidden, the light list rebuilt, both trees
+ * refitted -- on the context's stream, ordered like mcpt_update_vertices, asynchronous.  mcpt_get_update_info counts one update; film and
+ * counters are untouched; features, the denoised film and the tile error are dropped.  Allocates 1 B per face, counted in device_bytes.
+ *  - Validated on the host before any device work; a refusal changes nothing.  In this order: MCPT_ERR_UNSUPPORTED without MCPT_FLAG_DYNAMIC;
+ *    MCPT_ERR_INVALID_ARG for n_face that differs from the scene's (also with a NULL mask); MCPT_ERR_NO_LIGHTS when no emissive face under the
+ *    current materials would stay visible.
+ * mcpt_set_face_visibility_reproject is mcpt_update_vertices_reproject with the mask in place of the upload; validation order: the above, the
+ * camera (when given), the options, MCPT_ERR_BVH_DEPTH.
+ *
+ * mcpt_clone_to_device carries the mask and the records as they are.  mcpt_rebuild_trees keeps the mask (it is per face, not per leaf): the
+ * builders see a hidden face with the bounds of its vertices, as if it were visible, and the streams are permuted as they are, so hidden stays
+ * hidden; the next update tightens the boxes again.  (A builder that skips hidden faces does not exist.)
+ *
+ * mcpt_probe_triangles: per face, in Model::face order, the nine floats {first corner, edge 1, edge 2} of its intersection records and the six
+ * {lo, hi} of its refit box, as the device holds them; either output may be NULL.  The boxes are scratch of the scene update: asking for them
+ * before the first update after creation or after mcpt_rebuild_trees is MCPT_ERR_INVALID_ARG.  Synchronous; touches nothing. */
+typedef struct mcpt_visibility_info {
+    uint32_t struct_size, set;          /* 1: a mask is in force now */
+    uint32_t n_hidden;                  /* faces it hides */
+    uint32_t n_hidden_emitters;         /* ... of those, faces whose material emits (|radiance| > 0.01) under the current materials */
+    uint32_t updates, reserved0;        /* mcpt_set_face_visibility (+ _reproject) calls that shaped this context so far */
+    double   last_ms;                   /* device time of the last update's hide pass and, where the mask changed, its light rebuild */
+    uint64_t device_bytes;              /* what the mask holds on the device now */
+    uint32_t reserved[4];
+} mcpt_visibility_info;
+mcpt_status mcpt_set_face_visibility(mcpt_ctx* ctx, const uint8_t* visible /* n_face bytes, != 0 = visible; NULL = all visible, frees the mask */, uint32_t n_face);
+mcpt_status mcpt_set_face_visibility_reproject(mcpt_ctx* ctx, const uint8_t* visible, uint32_t n_face, const mcpt_camera* camera /* NULL = keep */,
+                                               const mcpt_reproject_opts* opts /* NULL = defaults */);
+mcpt_status mcpt_get_visibility_info(mcpt_ctx* ctx, mcpt_visibility_info* out);   /* synchronises */
+mcpt_status mcpt_probe_triangles(mcpt_ctx* ctx, float* out_v0e1e2 /* 9 per face */, float* out_box6 /* 6 per face */);   /* face order; either may be NULL */
 
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that

@@ -30,6 +30,8 @@ from .parts_abi import (OWNER_GROUPS, OWNER_KEYFRAMES, OWNER_MORPH, OWNER_NONE, 
                         ROUTE_MORPH, ROUTE_SKIN, PartsInfo, SceneUpdate, owners_from_faces)
 # mcpt_set_auto_normals' and mcpt_get_normals_info's structs and the mask of the normals a set of faces uses; tests/test_normals.py holds the layouts to the header
 from .normals_abi import NORMALS_AREA, NORMALS_OFF, NormalsInfo, NormalsOpts, normal_mask_from_faces  # noqa: F401
+# mcpt_get_visibility_info's struct and the mask that hides a set of materials' faces; tests/test_visibility.py holds the layout to the header
+from .visibility_abi import VisibilityInfo, visibility_from_materials  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmcpt_hip.so")
@@ -319,6 +321,10 @@ def load_library() -> C.CDLL:
         "mcpt_get_normals_info": [vp, P(NormalsInfo)],
         "mcpt_rebuild_trees": [vp, P(RebuildOpts)],
         "mcpt_get_rebuild_info": [vp, P(RebuildInfo)],
+        "mcpt_set_face_visibility": [vp, vp, C.c_uint32],
+        "mcpt_set_face_visibility_reproject": [vp, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
+        "mcpt_get_visibility_info": [vp, P(VisibilityInfo)],
+        "mcpt_probe_triangles": [vp, vp, vp],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -352,6 +358,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_vertex_owners", "mcpt_update_parts", "mcpt_update_parts_reproject", "mcpt_get_parts_info",
     "mcpt_set_auto_normals", "mcpt_update_normals", "mcpt_get_normals_info",
     "mcpt_rebuild_trees", "mcpt_get_rebuild_info",
+    "mcpt_set_face_visibility", "mcpt_set_face_visibility_reproject", "mcpt_get_visibility_info", "mcpt_probe_triangles",
 ]
 
 
@@ -803,6 +810,37 @@ class Renderer:
         i = NormalsInfo()
         self._check(self.lib.mcpt_get_normals_info(self.ctx, C.byref(i)))
         return i
+
+    # ---- faces shown and hidden on the device
+    def _visibility_mask(self, mask):
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(-1)
+        return m, self.holder.desc.n_face if m is None else m.shape[0]
+
+    def set_face_visibility(self, mask):
+        """One entry per face of the scene (visibility_from_materials builds one), != 0 = visible; None = every face visible and the mask freed.
+        Hidden faces cannot be hit by any ray and are no lights; the mask is sticky through every later update.  A scene update without a source:
+        nothing moves, the light list is rebuilt, both trees are refitted.  Needs FLAG_DYNAMIC.  Asynchronous; the caller clears the film."""
+        m, n = self._visibility_mask(mask)
+        self._check(self.lib.mcpt_set_face_visibility(self.ctx, _ptr(m), n))
+
+    def set_face_visibility_reproject(self, mask, camera=None, **opts):
+        """set_face_visibility that carries the film over, as update_vertices_reproject does; opts: reproject_camera's."""
+        m, n = self._visibility_mask(mask)
+        c, o = _camera_and_opts(camera, opts)
+        self._check(self.lib.mcpt_set_face_visibility_reproject(self.ctx, _ptr(m), n, c, o))
+
+    def visibility_info(self) -> VisibilityInfo:
+        i = VisibilityInfo()
+        self._check(self.lib.mcpt_get_visibility_info(self.ctx, C.byref(i)))
+        return i
+
+    def probe_triangles(self, boxes=True):
+        """Per face, in Model::face order, as the device holds them: ((n_face, 9) fp32 {first corner, edge 1, edge 2}, (n_face, 6) fp32 refit box
+        {lo, hi}).  boxes=False: the records alone (the boxes exist once a scene update has run since creation or the last rebuild)."""
+        nf = self.holder.desc.n_face
+        rec = np.zeros((nf, 9), np.float32); box = np.zeros((nf, 6), np.float32) if boxes else None
+        self._check(self.lib.mcpt_probe_triangles(self.ctx, _ptr(rec), _ptr(box)))
+        return (rec, box) if boxes else rec
 
     # ---- material, light and texture edits (DESIGN.md §15)
     def update_materials(self, materials, map_kd=None):

@@ -1,7 +1,7 @@
 // gfx950 kernels of the material update: mcpt_update_materials edits what a surface looks like on a live scene -- same geometry,
 // same trees.  What changes on the device is small: the 64-B material records (copied in by the host), four bits per triangle (the lobe class in
-// tri_isect[3 i].w) and the light list, whose membership follows |radiance| > 0.01 and whose order is the input's face order, not the leaf
-// order: a stream compaction over the faces.  Everything a light record holds is resident already (tri_isect, tri_shade, tri_pos64, mats).
+// tri_isect[3 i].w) and the light list, whose membership follows |radiance| > 0.01 (and, on a context with a visibility mask, "visible": §24) and
+// whose order is the input's face order, not the leaf order: a stream compaction over the faces.  Everything a light record holds is resident already (tri_isect, tri_shade, tri_pos64, mats).
 //
 // Everything runs on the context's stream, ordered like a render call.  The scan is three launches (per-block sums, one block over the sums, the
 // per-block scan from its offset): a launch reads only what earlier launches wrote, so no block ever waits for another block of its own launch.
@@ -35,7 +35,8 @@ __device__ __forceinline__ uint32_t mt_material_of(const float4* __restrict__ tr
 
 // ---------------------------------------------------------------------------------------------- lobe classes and light flags
 __global__ void __launch_bounds__(MT_BLOCK) mt_classes_kernel(float4* __restrict__ tri_isect, const float4* __restrict__ tri_shade, const int32_t* __restrict__ tri_face,
-                                                              const DevMaterial* __restrict__ mats, uint32_t n_mats, uint32_t* __restrict__ flag, uint32_t n_tris) {
+                                                              const DevMaterial* __restrict__ mats, uint32_t n_mats, uint32_t* __restrict__ flag, uint32_t n_tris,
+                                                              const uint8_t* __restrict__ visible) {
     const uint32_t i = blockIdx.x * MT_BLOCK + threadIdx.x;
     if (i >= n_tris) return;
     const uint32_t m = mt_material_of(tri_shade, i), face = (uint32_t)tri_face[i];
@@ -46,7 +47,7 @@ __global__ void __launch_bounds__(MT_BLOCK) mt_classes_kernel(float4* __restrict
     float4 r = I[0];
     r.w = __uint_as_float((__float_as_uint(r.w) & (uint32_t)HIT_TRI_MASK) | (lobe_class << HIT_CLASS_SHIFT));   // the tie rank stays
     I[0] = r;
-    flag[face] = (mflags & MAT_EMIT_REC) ? 1u : 0u;
+    flag[face] = (mflags & MAT_EMIT_REC) && (!visible || visible[face]) ? 1u : 0u;   // §24: a hidden face is no light
 }
 
 // ---------------------------------------------------------------------------------------------- exclusive scan in face order
@@ -85,11 +86,12 @@ __global__ void __launch_bounds__(MT_BLOCK) mt_apply_kernel(uint32_t* __restrict
 __global__ void __launch_bounds__(MT_BLOCK) mt_emit_kernel(const float4* __restrict__ tri_isect, const float4* __restrict__ tri_shade, const double* __restrict__ tri_pos64,
                                                            const int32_t* __restrict__ tri_face, const DevMaterial* __restrict__ mats, uint32_t n_mats,
                                                            const uint32_t* __restrict__ scan, DevLight* __restrict__ lights, double* __restrict__ light_pos64,
-                                                           uint32_t capacity, uint32_t n_tris) {
+                                                           uint32_t capacity, uint32_t n_tris, const uint8_t* __restrict__ visible) {
     const uint32_t i = blockIdx.x * MT_BLOCK + threadIdx.x;
     if (i >= n_tris) return;
     const uint32_t m = mt_material_of(tri_shade, i), face = (uint32_t)tri_face[i];
     if (m >= n_mats || face >= n_tris) return;
+    if (visible && !visible[face]) return;                                // §24: a hidden emitter has no slot (scan[face] is the next visible light's)
     const float4* M = reinterpret_cast<const float4*>(mats + m);         // 64 B: ks ns | radiance flags | ...
     const float4 rad = M[1];
     if (!(__float_as_uint(rad.w) & MAT_EMIT_REC)) return;
@@ -111,9 +113,9 @@ __global__ void __launch_bounds__(MT_BLOCK) mt_emit_kernel(const float4* __restr
 }  // namespace
 
 hipError_t launch_mt_classes(float4* tri_isect, const float4* tri_shade, const int32_t* tri_face, const DevMaterial* mats, uint32_t n_mats,
-                             uint32_t* flag, uint32_t n_tris, hipStream_t stream) {
+                             uint32_t* flag, uint32_t n_tris, hipStream_t stream, const uint8_t* visible) {
     if (n_tris == 0) return hipSuccess;
-    hipLaunchKernelGGL(mt_classes_kernel, dim3(mt_blocks(n_tris)), dim3(MT_BLOCK), 0, stream, tri_isect, tri_shade, tri_face, mats, n_mats, flag, n_tris);
+    hipLaunchKernelGGL(mt_classes_kernel, dim3(mt_blocks(n_tris)), dim3(MT_BLOCK), 0, stream, tri_isect, tri_shade, tri_face, mats, n_mats, flag, n_tris, visible);
     return hipGetLastError();
 }
 
@@ -131,9 +133,9 @@ hipError_t launch_mt_scan(uint32_t* flag, uint32_t* sums, uint32_t n, hipStream_
 
 hipError_t launch_mt_emit(const float4* tri_isect, const float4* tri_shade, const double* tri_pos64, const int32_t* tri_face, const DevMaterial* mats,
                           uint32_t n_mats, const uint32_t* scan, DevLight* lights, double* light_pos64, uint32_t capacity, uint32_t n_tris,
-                          hipStream_t stream) {
+                          hipStream_t stream, const uint8_t* visible) {
     if (n_tris == 0) return hipSuccess;
     hipLaunchKernelGGL(mt_emit_kernel, dim3(mt_blocks(n_tris)), dim3(MT_BLOCK), 0, stream, tri_isect, tri_shade, tri_pos64, tri_face, mats, n_mats, scan, lights,
-                       light_pos64, capacity, n_tris);
+                       light_pos64, capacity, n_tris, visible);
     return hipGetLastError();
 }

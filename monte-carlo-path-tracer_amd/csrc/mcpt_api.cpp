@@ -19,6 +19,8 @@
 #include "normals.h"
 #include "reproject.h"
 #include "materials.h"
+#include "visibility.h"
+#include "visibility_plan.h"
 
 #include <chrono>
 #include <cmath>
@@ -374,6 +376,26 @@ struct mcpt_ctx {
             return MCPT_OK;
         }
     } nr;
+    // Face visibility (visibility.hip), allocated by mcpt_set_face_visibility with a mask: one byte per face of the description on
+    // the device (counted in device_bytes) and its pinned staging.  On the host the same bytes (normalised to 0 / 1), what they hide under the
+    // current materials, and -- from creation on, dynamic contexts only -- every face's material (`face_material`: the light count of a mask is
+    // known before any device work).  `set`: a mask is in force; the hide pass runs when it hides at least one face.  `box_valid`: rf_tri_box holds
+    // the boxes of the streams as they are (an update has run since creation or the last rebuild), what mcpt_probe_triangles reads.
+    struct Visibility {
+        DevBuf<uint8_t> mask; Staging<uint8_t> stage; Stopwatch watch; std::vector<uint8_t> host; std::vector<uint32_t> face_material;
+        bool set = false, box_valid = false; uint32_t n_hidden = 0, n_hidden_emitters = 0, updates = 0;
+        const uint8_t* dev_mask() const { return set ? mask.p : nullptr; }       // what the light list's kernels take
+        void drop() { mask.release(); host.clear(); set = false; n_hidden = 0; n_hidden_emitters = 0; }
+        template <class Copy> mcpt_status clone_from(mcpt_ctx* c, const Visibility& src, Copy copy) {   // the mask and what it hides; the source's counter and duration
+            face_material = src.face_material; updates = src.updates;
+            if (src.watch.ev0) { HIP_TRY(watch.create()); watch.last_ms = src.watch.last_ms; }
+            if (!src.set) return MCPT_OK;
+            HIP_TRY(alloc_all(Want(mask, src.mask.count(), &c->info.device_bytes), Want(stage, src.mask.count())));
+            host = src.host; set = true; n_hidden = src.n_hidden; n_hidden_emitters = src.n_hidden_emitters;
+            HIP_TRY(copy(mask, src.mask));
+            return MCPT_OK;
+        }
+    } vs;
     // Temporal reprojection (reproject.hip), allocated by the first reprojection call: the old view's features (2 per pixel, swapped
     // with dn_feat per call), a copy of the old film and the reuse counter.
     // Motion-vector reprojection adds, on the first mcpt_update_vertices_reproject: the first hit of every pixel-centre ray and
@@ -651,6 +673,8 @@ static mcpt_status rf_clone(mcpt_ctx* c, mcpt_ctx* src) {
     if ((st = c->xf.clone_from(c, src->xf, copy)) != MCPT_OK || (st = c->sk.clone_from(c, src->sk, copy)) != MCPT_OK ||
         (st = c->mo.clone_from(c, src->mo, copy)) != MCPT_OK || (st = c->kf.clone_from(c, src->kf, copy)) != MCPT_OK ||
         (st = c->pt.clone_from(c, src->pt, copy)) != MCPT_OK || (st = c->nr.clone_from(c, src->nr, copy)) != MCPT_OK) return st;
+    HIP_TRY(hipSetDevice(src->device)); HIP_TRY(src->vs.watch.settle()); HIP_TRY(hipSetDevice(c->device));   // (the source's stream is drained: its last duration is there to read)
+    if ((st = c->vs.clone_from(c, src->vs, copy)) != MCPT_OK) return st;             // §24: the scene streams were copied as they are, hidden records included
     HIP_TRY(hipDeviceSynchronize());
     return MCPT_OK;
 }
@@ -768,6 +792,10 @@ mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcp
     c->mt_mats.assign(scene->materials, scene->materials + scene->n_materials); c->mt_tex = hs.tex_info; c->mt_faces = hs.mat_faces;
     if ((st = finish_ctx(c)) != MCPT_OK) return st;
     if ((o.flags & MCPT_FLAG_DYNAMIC) && (st = rf_setup(c, hs, scene)) != MCPT_OK) return st;
+    if (o.flags & MCPT_FLAG_DYNAMIC) {                                    // §24: the material of a face is corner 0's (build_host_scene checked its range)
+        c->vs.face_material.resize(scene->n_face);
+        for (uint32_t f = 0; f < scene->n_face; f++) c->vs.face_material[f] = uint32_t(scene->face[12 * size_t(f) + 3]);
+    }
     in.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out_ctx = guard.release();
     return MCPT_OK;
@@ -1514,7 +1542,9 @@ struct RfUpdate {
     const double* m3x4 = nullptr; uint32_t n_m3x4 = 0;                                                      // Groups: per group; Skin, MorphSkin: per bone
     const double* weight = nullptr; uint32_t n_weight = 0;                                                  // Morph, MorphSkin: per target
     double time = 0.0;                                                                                      // Keyframes
+    bool lights = false; uint32_t n_lights = 0;                                                             // None, §24: the mask changed -- the light list is rebuilt, to this length
     static RfUpdate none() { return RfUpdate(); }
+    static RfUpdate visibility(uint32_t n_lights) { RfUpdate u; u.lights = true; u.n_lights = n_lights; return u; }
     static RfUpdate keyframes(double t) { RfUpdate u; u.source = Source::Keyframes; u.time = t; return u; }
     static RfUpdate arrays(const double* v, uint32_t nv, const double* n, uint32_t nn) {
         RfUpdate u; u.source = Source::Arrays; u.vertex = v; u.n_vertex = nv; u.normal = n; u.n_normal = nn; return u;
@@ -1746,6 +1776,25 @@ static mcpt_status rf_enqueue_update(mcpt_ctx* ctx, const RfUpdate& u) {
     const DevScene& d = ctx->dev;
     HIP_TRY(launch_rf_triangles(ctx->rf_vtx.p, d_nrm, ctx->rf_idx.p, RfCentre{d.centre[0], d.centre[1], d.centre[2]}, ctx->tri_isect.p, ctx->tri_shade.p,
                                 ctx->tri_pos64.p, ctx->rf_tri_box.p, uint32_t(d.n_tris), s));
+    // §24: the mask is sticky -- rf_triangles_kernel has just made every face hittable again, so whatever the route, the hidden ones lose their edges
+    // and shrink to a point before the light records and the trees are derived from the streams.  A call that changed the mask (u.lights) also
+    // rebuilds the light list, by the material update's chain (§15) with the mask as a second membership test.  No mask, no launch.
+    const bool hide = ctx->vs.set && ctx->vs.n_hidden != 0;
+    if (hide || u.lights) {
+        mcpt_ctx::Visibility& vs = ctx->vs; const uint32_t nt = uint32_t(d.n_tris);
+        HIP_TRY(vs.watch.begin(s));
+        if (hide) HIP_TRY(launch_vs_hide(vs.mask.p, d.tri_face, ctx->tri_isect.p, ctx->rf_tri_box.p, nt, s));
+        if (u.lights) {
+            HIP_TRY(launch_mt_classes(ctx->tri_isect.p, d.tri_shade, d.tri_face, d.mats, uint32_t(d.n_mats), ctx->mt_flag.p, nt, s, vs.dev_mask()));
+            HIP_TRY(launch_mt_scan(ctx->mt_flag.p, ctx->mt_sums.p, nt, s));
+            HIP_TRY(launch_mt_emit(d.tri_isect, d.tri_shade, d.tri_pos64, d.tri_face, d.mats, uint32_t(d.n_mats), ctx->mt_flag.p, ctx->lights.p, ctx->light_pos64.p,
+                                   uint32_t(ctx->lights.count()), nt, s, vs.dev_mask()));
+            ctx->dev.n_lights = int32_t(u.n_lights); ctx->info.n_lights = u.n_lights;
+            vs.updates++;
+        }
+        HIP_TRY(vs.watch.end(s));
+    }
+    ctx->vs.box_valid = true;
     HIP_TRY(launch_rf_lights(ctx->lights.p, ctx->light_pos64.p, d.tri_isect, d.tri_pos64, d_nrm, ctx->rf_idx.p, uint32_t(d.n_lights), s));
     for (size_t k = 0; k + 1 < ctx->rf_bin_level.size(); k++)                    // heights, lowest first
         HIP_TRY(launch_rf_binary_level(ctx->nodes.p, ctx->rf_bin_order.p, ctx->rf_bin_level[k], ctx->rf_bin_level[k + 1], ctx->rf_tri_box.p, s));
@@ -2198,6 +2247,7 @@ mcpt_status mcpt_rebuild_trees(mcpt_ctx* ctx, const mcpt_rebuild_opts* opts) {
     ctx->rf_bin_level.swap(bin_level); ctx->rf_wide_level.swap(wide_level); ctx->rf_area0 = area0;
     ctx->h_tri_face.assign(order.begin(), order.end());
     ctx->wide_depth = hs.bvh8_depth; ctx->binary_ok = hs.binary_ok;
+    ctx->vs.box_valid = false;                                                    // §24: rf_tri_box is scratch in the OLD leaf order; the mask is per face and stays
     DevScene& d = ctx->dev;
     d.nodes = ctx->nodes.p; d.nodes8 = ctx->nodes8.p; d.tri_isect = ctx->tri_isect.p; d.tri_shade = ctx->tri_shade.p; d.tri_pos64 = ctx->tri_pos64.p;
     d.tri_face = ctx->tri_face.p; d.lights = ctx->lights.p; d.n_nodes = int32_t(n2); d.n_nodes8 = int32_t(n8);
@@ -2223,6 +2273,20 @@ mcpt_status mcpt_get_rebuild_info(mcpt_ctx* ctx, mcpt_rebuild_info* out) {
 static void mt_records(const mcpt_ctx* ctx, const std::vector<mcpt_material>& mats, DevMaterial* out) {
     for (size_t i = 0; i < mats.size(); i++) out[i] = device_material(mats[i], ctx->mt_tex[size_t(mats[i].map_kd)]);
 }
+// What a rebuild of the light list to `n_lights` entries needs on the device: the scan's scratch (allocated once, one word per face and one per
+// scan block) and a list that long.  The list only grows, and what it held is NOT kept: the caller rebuilds all of it.
+static mcpt_status mt_ensure_list(mcpt_ctx* ctx, uint64_t n_lights) {
+    const uint32_t nt = uint32_t(ctx->dev.n_tris);
+    uint64_t* tally = &ctx->info.device_bytes;
+    if (!ctx->mt_flag.p) HIP_TRY(alloc_all(Want(ctx->mt_flag, nt, tally), Want(ctx->mt_sums, mt_blocks(nt), tally)));
+    if (n_lights > ctx->lights.count()) {
+        // the list grows (rare): kernels enqueued earlier may still read the old buffers, which die when the new ones replace them
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(alloc_all(Want(ctx->lights, size_t(n_lights), tally), Want(ctx->light_pos64, 9 * size_t(n_lights), tally)));
+        ctx->dev.lights = ctx->lights.p; ctx->dev.light_pos64 = ctx->light_pos64.p;
+    }
+    return MCPT_OK;
+}
 // `mats` staged and copied over the device records in stream order (`last`: the staging buffer's only copy of this filling).
 static mcpt_status mt_send_records(mcpt_ctx* ctx, const std::vector<mcpt_material>& mats) {
     HIP_TRY(ctx->mt_stage.wait());
@@ -2238,39 +2302,39 @@ mcpt_status mcpt_update_materials(mcpt_ctx* ctx, const mcpt_material* materials,
     if (!materials) return fail(MCPT_ERR_INVALID_ARG, who + "null materials");
     if (n_materials != uint32_t(ctx->dev.n_mats)) return fail(MCPT_ERR_INVALID_ARG, who + "n_materials differs from the scene's");
     uint64_t n_lights = 0;
+    std::vector<uint8_t> emits(n_materials, 0);
     for (uint32_t i = 0; i < n_materials; i++) {
         const mcpt_material& m = materials[i];
         if (m.map_kd < 0 || size_t(m.map_kd) >= ctx->mt_tex.size()) return fail(MCPT_ERR_INVALID_ARG, who + "material " + std::to_string(i) + ": map_kd out of range");
         bool finite = std::isfinite(m.ns);
         for (int k = 0; k < 3; k++) finite = finite && std::isfinite(m.ks[k]) && std::isfinite(m.radiance[k]);
         if (!finite) return fail(MCPT_ERR_INVALID_ARG, who + "material " + std::to_string(i) + ": ks, ns or radiance is not finite");
-        if (device_material(m, ctx->mt_tex[size_t(m.map_kd)]).flags & MAT_EMIT_REC) n_lights += ctx->mt_faces[i];
+        emits[i] = (device_material(m, ctx->mt_tex[size_t(m.map_kd)]).flags & MAT_EMIT_REC) ? 1 : 0;
+        if (emits[i]) n_lights += ctx->mt_faces[i];
     }
-    if (n_lights == 0) return fail(MCPT_ERR_NO_LIGHTS, who + "no face would be left with |radiance| > 0.01");
+    uint32_t hidden_emitters = 0;
+    if (ctx->vs.set) {                                                    // §24: under a mask a light is an emissive face that is visible
+        const VsPlan plan = vs_plan(ctx->vs.host.data(), ctx->vs.face_material.data(), uint32_t(ctx->vs.face_material.size()), emits.data(), n_materials);
+        n_lights = plan.n_lights; hidden_emitters = plan.n_hidden_emitters;
+    }
+    if (n_lights == 0) return fail(MCPT_ERR_NO_LIGHTS, who + (ctx->vs.set ? "no visible face would be left with |radiance| > 0.01" : "no face would be left with |radiance| > 0.01"));
     const uint32_t nt = uint32_t(ctx->dev.n_tris);
-    uint64_t* tally = &ctx->info.device_bytes;
-    if (!ctx->mt_flag.p) HIP_TRY(alloc_all(Want(ctx->mt_flag, nt, tally), Want(ctx->mt_sums, mt_blocks(nt), tally)));
     if (!ctx->mt_have_watch) { HIP_TRY(ctx->mt_watch.create()); ctx->mt_have_watch = true; }
     HIP_TRY(ctx->mt_stage.wait());
     HIP_TRY(ctx->mt_stage.grow(n_materials));
-    if (n_lights > ctx->lights.count()) {
-        // the list grows (rare): kernels enqueued earlier may still read the old buffers, which die when the new ones replace them
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(alloc_all(Want(ctx->lights, size_t(n_lights), tally), Want(ctx->light_pos64, 9 * size_t(n_lights), tally)));
-        ctx->dev.lights = ctx->lights.p; ctx->dev.light_pos64 = ctx->light_pos64.p;
-    }
+    st = mt_ensure_list(ctx, n_lights); if (st != MCPT_OK) return st;
     // Everything below is stream work on the context's stream, ordered like mcpt_update_vertices: renders enqueued so far have joined it, the
     // next render's sub-pipelines fork from it after the last kernel here.
     hipStream_t s = ctx->stream;
     const std::vector<mcpt_material> mats(materials, materials + n_materials);
     HIP_TRY(ctx->mt_watch.begin(s));
     st = mt_send_records(ctx, mats); if (st != MCPT_OK) return st;
-    HIP_TRY(launch_mt_classes(ctx->tri_isect.p, ctx->dev.tri_shade, ctx->dev.tri_face, ctx->dev.mats, n_materials, ctx->mt_flag.p, nt, s));
+    HIP_TRY(launch_mt_classes(ctx->tri_isect.p, ctx->dev.tri_shade, ctx->dev.tri_face, ctx->dev.mats, n_materials, ctx->mt_flag.p, nt, s, ctx->vs.dev_mask()));
     HIP_TRY(launch_mt_scan(ctx->mt_flag.p, ctx->mt_sums.p, nt, s));
     HIP_TRY(launch_mt_emit(ctx->dev.tri_isect, ctx->dev.tri_shade, ctx->dev.tri_pos64, ctx->dev.tri_face, ctx->dev.mats, n_materials, ctx->mt_flag.p,
-                           ctx->lights.p, ctx->light_pos64.p, uint32_t(ctx->lights.count()), nt, s));
+                           ctx->lights.p, ctx->light_pos64.p, uint32_t(ctx->lights.count()), nt, s, ctx->vs.dev_mask()));
     HIP_TRY(ctx->mt_watch.end(s));
-    ctx->mt_mats = mats;
+    ctx->mt_mats = mats; ctx->vs.n_hidden_emitters = hidden_emitters;
     ctx->dev.n_lights = int32_t(n_lights); ctx->info.n_lights = uint32_t(n_lights);
     ctx->mt_updates++;
     rf_forget_derived(ctx);
@@ -2595,6 +2659,78 @@ mcpt_status mcpt_probe_validate_trees(mcpt_ctx* ctx) {
     if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, "8-wide tree: " + bad);
     bad = validate_bvh2(hs);
     if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, bad);
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ face visibility
+// Both forms of mcpt_set_face_visibility.  Everything that can refuse comes first and is host work: the context, n_face, the light count of the mask
+// under the current materials (vs_plan), and for the _reproject form what rp_frame would turn away.  Then the mask is staged and copied in stream
+// order, and the call becomes a scene update without a source that also rebuilds the light list.
+static mcpt_status vs_set(mcpt_ctx* ctx, const uint8_t* visible, uint32_t n_face, const mcpt_camera* cm, const mcpt_reproject_opts* opts, bool reproject, const char* fn) {
+    const std::string who = std::string(fn) + ": ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if ((st = require_dynamic(ctx, who)) != MCPT_OK) return st;
+    if (n_face != uint32_t(ctx->dev.n_tris)) return fail(MCPT_ERR_INVALID_ARG, who + "n_face differs from the scene's");
+    mcpt_ctx::Visibility& vs = ctx->vs;
+    std::vector<uint8_t> host(visible ? n_face : 0u);
+    for (uint32_t f = 0; f < uint32_t(host.size()); f++) host[f] = visible[f] != 0 ? 1 : 0;
+    const uint32_t n_mats = uint32_t(ctx->mt_mats.size());
+    std::vector<uint8_t> emits(n_mats, 0);
+    for (uint32_t i = 0; i < n_mats; i++) emits[i] = (device_material(ctx->mt_mats[i], ctx->mt_tex[size_t(ctx->mt_mats[i].map_kd)]).flags & MAT_EMIT_REC) ? 1 : 0;
+    const VsPlan plan = vs_plan(visible ? host.data() : nullptr, vs.face_material.data(), n_face, emits.data(), n_mats);
+    if (plan.n_lights == 0) return fail(MCPT_ERR_NO_LIGHTS, who + "no face with |radiance| > 0.01 would stay visible");
+    if (reproject) {
+        if (cm && (st = check_camera(ctx, cm, fn)) != MCPT_OK) return st;
+        mcpt_reproject_opts o;
+        if ((st = rp_read_opts(opts, o, fn)) != MCPT_OK) return st;
+        if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the feature kernel's traversal stack");
+    }
+    // nothing below refuses; what fails is a HIP call
+    if (!visible && vs.set) HIP_TRY(hipStreamSynchronize(ctx->stream));          // kernels enqueued earlier may still read the mask that is about to be freed
+    HIP_TRY(alloc_all(Want(vs.mask, n_face, &ctx->info.device_bytes, visible && !vs.mask.p), Want(vs.stage, n_face, nullptr, visible && vs.stage.cap < n_face),
+                      Want(vs.watch, 1, nullptr, !vs.watch.ev0)));
+    st = mt_ensure_list(ctx, plan.n_lights); if (st != MCPT_OK) return st;
+    if (visible) {
+        HIP_TRY(vs.stage.wait());
+        std::memcpy(vs.stage.host, host.data(), n_face);
+        HIP_TRY(vs.stage.send(vs.mask.p, 0, n_face, ctx->stream));
+        vs.host.swap(host); vs.set = true; vs.n_hidden = plan.n_hidden; vs.n_hidden_emitters = plan.n_hidden_emitters;
+    } else vs.drop();
+    return rf_update(ctx, RfUpdate::visibility(plan.n_lights), fn, cm, opts, reproject);
+}
+
+mcpt_status mcpt_set_face_visibility(mcpt_ctx* ctx, const uint8_t* visible, uint32_t n_face) {
+    return vs_set(ctx, visible, n_face, nullptr, nullptr, false, "mcpt_set_face_visibility");
+}
+
+mcpt_status mcpt_set_face_visibility_reproject(mcpt_ctx* ctx, const uint8_t* visible, uint32_t n_face, const mcpt_camera* cm, const mcpt_reproject_opts* opts) {
+    return vs_set(ctx, visible, n_face, cm, opts, true, "mcpt_set_face_visibility_reproject");
+}
+
+mcpt_status mcpt_get_visibility_info(mcpt_ctx* ctx, mcpt_visibility_info* out) {
+    const mcpt_status st = info_begin(ctx, out, ctx ? &ctx->vs.watch : nullptr); if (st != MCPT_OK) return st;
+    const mcpt_ctx::Visibility& vs = ctx->vs;
+    out->set = vs.set ? 1u : 0u; out->n_hidden = vs.n_hidden; out->n_hidden_emitters = vs.n_hidden_emitters; out->updates = vs.updates;
+    out->last_ms = vs.watch.last_ms; out->device_bytes = vs.mask.bytes;
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_triangles(mcpt_ctx* ctx, float* out_v0e1e2, float* out_box6) {
+    const std::string who = "mcpt_probe_triangles: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if ((st = require_dynamic(ctx, who)) != MCPT_OK) return st;
+    if (out_box6 && !ctx->vs.box_valid) return fail(MCPT_ERR_INVALID_ARG, who + "no scene update has written the boxes since creation or the last rebuild");
+    st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
+    const size_t nt = size_t(ctx->dev.n_tris);
+    std::vector<f4h> isect(out_v0e1e2 ? 3 * nt : 0); std::vector<float> box(out_box6 ? 6 * nt : 0);
+    st = read_back(ctx, isect.data(), ctx->tri_isect.p, isect.size() * sizeof(f4h), false); if (st != MCPT_OK) return st;
+    st = read_back(ctx, box.data(), ctx->rf_tri_box.p, box.size() * sizeof(float)); if (st != MCPT_OK) return st;
+    for (size_t i = 0; i < nt; i++) {
+        const size_t f = size_t(ctx->h_tri_face[i]);
+        if (f >= nt) return fail(MCPT_ERR_HIP, who + "the context's leaf order is damaged");
+        if (out_v0e1e2) for (int k = 0; k < 3; k++) { const f4h& r = isect[3 * i + k]; float* o = out_v0e1e2 + 9 * f + 3 * k; o[0] = r.x; o[1] = r.y; o[2] = r.z; }
+        if (out_box6) std::memcpy(out_box6 + 6 * f, box.data() + 6 * i, 6 * sizeof(float));
+    }
     return MCPT_OK;
 }
 

@@ -161,9 +161,9 @@ bool Render::update_keyframes_reproject(Scene& scene, double time, const CameraI
 // §19, with or without the bones' matrices), from `time` (the keyframes' clock, §22) or from several of them at once (`parts`, §23): the rest is
 // the same.
 bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>* matrices, bool bones, const std::vector<double>* weights, const CameraInfo* camera,
-                              float max_history, const double* time, const PartsUpdate* parts) {
+                              float max_history, const double* time, const PartsUpdate* parts, const std::vector<uint8_t>* visible) {
     if (!ctx) return false;
-    const char* const who = parts ? "update_parts_reproject" : m ? "update_reproject" : time ? "update_keyframes_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject";
+    const char* const who = visible ? "set_visible_reproject" : parts ? "update_parts_reproject" : m ? "update_reproject" : time ? "update_keyframes_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject";
     if (parts && (parts->group_matrices.size() % 12 || parts->bone_matrices.size() % 12)) { std::cerr << "Error: Render::" << who << ": need 12 doubles per group and per bone" << std::endl; return false; }
     if (!m && matrices && (matrices->size() % 12 || matrices->empty())) { std::cerr << "Error: Render::" << who << ": need 12 doubles per " << (bones ? "bone" : "group") << std::endl; return false; }
     bool ok = false;
@@ -172,7 +172,9 @@ bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>*
     mcpt_camera k; if (camera) k = to_camera(*camera);
     mcpt_reproject_opts o; std::memset(&o, 0, sizeof o); o.struct_size = sizeof o; o.feature_spp = 4; o.feature_seed = seed; o.max_history = max_history;
     mcpt_scene_update pu; if (parts) pu = to_scene_update(*parts);
-    const mcpt_status st = parts ? mcpt_update_parts_reproject(ctx, &pu, camera ? &k : nullptr, &o)
+    const mcpt_status st = visible ? mcpt_set_face_visibility_reproject(ctx, visible->empty() ? nullptr : visible->data(), visible->empty() ? face_count() : uint32_t(visible->size()),
+                                                                        camera ? &k : nullptr, &o)   // (§24: the mask in place of the geometry; an empty one drops it)
+                           : parts ? mcpt_update_parts_reproject(ctx, &pu, camera ? &k : nullptr, &o)
                           : time ? mcpt_update_keyframes_reproject(ctx, *time, camera ? &k : nullptr, &o)
                        : weights ? mcpt_update_morph_reproject(ctx, weights->data(), uint32_t(weights->size()), matrices ? matrices->data() : nullptr,
                                                                  matrices ? uint32_t(matrices->size() / 12) : 0u, camera ? &k : nullptr, &o)
@@ -181,7 +183,7 @@ bool Render::update_reproject(Scene& scene, Model* m, const std::vector<double>*
                      : bones ? mcpt_update_skin_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o)
                              : mcpt_update_transforms_reproject(ctx, matrices->data(), uint32_t(matrices->size() / 12), camera ? &k : nullptr, &o);
     if (st != MCPT_OK) {
-        std::cerr << "Error: mcpt_" << (parts ? "update_parts_reproject" : m ? "update_vertices_reproject" : time ? "update_keyframes_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
+        std::cerr << "Error: mcpt_" << (visible ? "set_face_visibility_reproject" : parts ? "update_parts_reproject" : m ? "update_vertices_reproject" : time ? "update_keyframes_reproject" : weights ? "update_morph_reproject" : bones ? "update_skin_reproject" : "update_transforms_reproject") << ": " << mcpt_last_error() << std::endl;
         if (upload && mcpt_clear_accum(ctx) != MCPT_OK) std::cerr << "Error: mcpt_clear_accum: " << mcpt_last_error() << std::endl;   // the Scene still holds them
         return false;
     }
@@ -402,6 +404,25 @@ bool Render::update_normals(Scene& scene) {
     if (!ctx) return false;
     if (mcpt_update_normals(ctx) != MCPT_OK) { std::cerr << "Error: mcpt_update_normals: " << mcpt_last_error() << std::endl; return false; }
     return restart(scene);
+}
+// §24.  An empty mask means "every face visible": the library takes that as a NULL mask with the scene's own face count.
+uint32_t Render::face_count() const {
+    mcpt_scene_info info;
+    return ctx && mcpt_get_scene_info(ctx, &info) == MCPT_OK ? info.n_tris : 0u;
+}
+bool Render::set_visible(Scene& scene, const std::vector<uint8_t>& face_visible) {
+    if (!ctx) return false;
+    const bool all = face_visible.empty();
+    if (mcpt_set_face_visibility(ctx, all ? nullptr : face_visible.data(), all ? face_count() : uint32_t(face_visible.size())) != MCPT_OK) {
+        std::cerr << "Error: mcpt_set_face_visibility: " << mcpt_last_error() << std::endl; return false;
+    }
+    return restart(scene);
+}
+bool Render::set_visible_reproject(Scene& scene, const std::vector<uint8_t>& face_visible, float max_history) {
+    return update_reproject(scene, nullptr, nullptr, false, nullptr, nullptr, max_history, nullptr, nullptr, &face_visible);
+}
+bool Render::set_visible_reproject(Scene& scene, const std::vector<uint8_t>& face_visible, const CameraInfo& camera, float max_history) {
+    return update_reproject(scene, nullptr, nullptr, false, nullptr, &camera, max_history, nullptr, nullptr, &face_visible);
 }
 bool Render::update_materials(Scene& scene, Model& m) {
     if (!ctx) return false;

@@ -124,6 +124,13 @@ public:
     // now, nothing moves; starts the picture again like update().  false (Render and Scene unchanged) on failure.
     bool set_auto_normals(Scene& scene, Model& m_model, const std::vector<uint8_t>& face_mask = {});
     bool update_normals(Scene& scene);
+    // Faces shown and hidden (mcpt_set_face_visibility).  set_visible: one byte per face of the Model this Render was made from
+    // (MCPT_FLAG_DYNAMIC), != 0 = visible; an empty vector shows every face again and frees the mask.  A hidden face cannot be hit by any ray and
+    // is no light; the mask stays in force through every later update*() call.  Refused when no light would stay visible.  Starts the picture
+    // again like update(); set_visible_reproject carries it over like update_reproject.  false (Render and Scene unchanged) on failure.
+    bool set_visible(Scene& scene, const std::vector<uint8_t>& face_visible);
+    bool set_visible_reproject(Scene& scene, const std::vector<uint8_t>& face_visible, float max_history = 0);
+    bool set_visible_reproject(Scene& scene, const std::vector<uint8_t>& face_visible, const CameraInfo& camera, float max_history = 0);
     // New trees for the geometry as it is now (mcpt_rebuild_trees): after update() / update_transforms() have moved the scene far
     // (mcpt_update_info::wide_area_ratio says how far) the refitted trees are sound and slow; this builds them anew on the context.  The picture
     // goes ON: `scene`'s film, the sample numbering and the feature buffers stay, the scene looks the same from every pixel.  Synchronous.  false
@@ -147,7 +154,8 @@ private:
     bool restart(Scene& scene);
     bool film_to_device(Scene& scene, const char* who, bool& ok);
     bool update_reproject(Scene& scene, Model* m_model, const std::vector<double>* matrices, bool bones, const std::vector<double>* weights, const CameraInfo* camera,
-                          float max_history, const double* time = nullptr, const PartsUpdate* parts = nullptr);
+                          float max_history, const double* time = nullptr, const PartsUpdate* parts = nullptr, const std::vector<uint8_t>* visible = nullptr);
+    uint32_t face_count() const;                      // of the scene the context holds
 };
 // Fills an mcpt_scene_desc that points INTO `m` (and into the two scratch vectors); valid while all three live.
 void model_to_desc(Model& m, std::vector<mcpt_material>& mats, std::vector<mcpt_texture>& texs, mcpt_scene_desc& d);

@@ -61,6 +61,12 @@ static void usage() {
                  "                                        otherwise those of the named material's faces (honours --reproject and --rebuild-above)\n"
                  "                          [--rebuild-above R]   with --turntable and --wobble, --spin, --bend, --swell or --sequence: after a frame's update the trees are built anew\n"
                  "                                        (mcpt_rebuild_trees, film kept) when wide_area_ratio exceeds R; prints frame, ratio and cost per rebuild\n"
+                 "                          [--hide MTLNAME]   with --turntable: the faces of that material are hidden in every frame (DESIGN.md 24: a visibility mask\n"
+                 "                                        on the device -- no ray hits them, they are no lights; same upload, same trees)\n"
+                 "                          [--blink MTLNAME K]   with --turntable: the faces of that material are visible in the frames f with (f / K) % 2 == 0 and hidden\n"
+                 "                                        in the others; the mask changes only where that changes.  --hide and --blink honour --reproject (the film is\n"
+                 "                                        carried across the change) and go with the camera alone: not with --wobble, --light-pulse, --spin, --bend,\n"
+                 "                                        --swell or --sequence, and not with each other\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -94,6 +100,7 @@ int main(int argc, char** argv) {
     bool rebuild = false; double rebuild_above = 0.0;
     bool auto_normals = false, dual_quat = false;
     std::string sequence; int sequence_n = 0; bool slowdown_set = false, smooth = false; double slowdown = 1.0;
+    std::string hide, blink; int blink_k = 0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -124,6 +131,8 @@ int main(int argc, char** argv) {
         else if (a == "--smooth") smooth = true;
         else if (a == "--auto-normals") auto_normals = true;
         else if (a == "--rebuild-above") { rebuild = true; rebuild_above = std::atof(next()); }
+        else if (a == "--hide") hide = next();
+        else if (a == "--blink") { blink = next(); blink_k = std::atoi(next()); }
         else { usage(); return 2; }
     }
     if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
@@ -164,7 +173,13 @@ int main(int argc, char** argv) {
     if (auto_normals && (!turntable || !(wobble || !bend.empty() || !swell.empty() || !sequence.empty()))) {
         std::cerr << "Error: --auto-normals needs --turntable N with --wobble, --bend, --swell or --sequence (the updates whose normals it recomputes)" << std::endl; return 2;
     }
-    if (wobble || !spin.empty() || !bend.empty() || !swell.empty() || !sequence.empty()) flags |= MCPT_FLAG_DYNAMIC;
+    if (!hide.empty() || !blink.empty()) {
+        if (!turntable || wobble || pulse || !spin.empty() || !bend.empty() || !swell.empty() || !sequence.empty() || (!hide.empty() && !blink.empty())) {
+            std::cerr << "Error: --hide MTLNAME and --blink MTLNAME K need --turntable N and none of --wobble, --light-pulse, --spin, --bend, --swell and --sequence, and exclude each other" << std::endl; return 2;
+        }
+        if (!blink.empty() && blink_k < 1) { std::cerr << "Error: --blink MTLNAME K needs K >= 1" << std::endl; return 2; }
+    }
+    if (wobble || !spin.empty() || !bend.empty() || !swell.empty() || !sequence.empty() || !hide.empty() || !blink.empty()) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
     std::cout << model.face.size() << " " << model.normal.size() << " " << model.vertex.size() << std::endl;   // main.cpp:14
@@ -379,6 +394,17 @@ int main(int argc, char** argv) {
             }
             if (!renders[0]->set_auto_normals(scene, model, face_mask)) return 1;
         }
+        // --hide / --blink MTLNAME: the mask that hides that material's faces, and whether it is in force
+        std::vector<uint8_t> hide_mask; bool hidden_now = false;
+        if (!hide.empty() || !blink.empty()) {
+            const std::string& name = hide.empty() ? blink : hide; const char* const opt = hide.empty() ? "--blink" : "--hide";
+            const int mtl = model.material_index(name);
+            if (mtl < 0) { std::cerr << "Error: " << opt << ": no material named " << name << std::endl; return 1; }
+            hide_mask.assign(model.face.size(), 1);
+            size_t n_hide = 0;
+            for (size_t i = 0; i < model.face.size(); i++) if (model.face[i][0][3] == mtl) { hide_mask[i] = 0; n_hide++; }
+            if (!n_hide) { std::cerr << "Error: " << opt << ": no face uses material " << name << std::endl; return 1; }
+        }
         for (uint32_t f = 0; f < turntable; f++) {
             const double a = 2.0 * 3.14159265358979323846 * double(f) / double(turntable), ca = std::cos(a), sa = std::sin(a);
             const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2], kx[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
@@ -431,6 +457,11 @@ int main(int argc, char** argv) {
                 } else
                 if (reproject && f > 0 ? !renders[0]->update_skin_reproject(scene, m, cam, history)
                                        : !(renders[0]->update_skin(scene, m) && renders[0]->set_camera(scene, cam))) return 1;
+            } else if (!hide_mask.empty() && (!hide.empty() || (f / uint32_t(blink_k)) % 2 == 1) != hidden_now) {   // --hide / --blink: the mask changes in this frame
+                hidden_now = !hidden_now;
+                const std::vector<uint8_t> mask = hidden_now ? hide_mask : std::vector<uint8_t>();   // (empty: every face visible again)
+                Render& r0 = *renders[0];
+                if (reproject && f > 0 ? !r0.set_visible_reproject(scene, mask, cam, history) : !(r0.set_visible(scene, mask) && r0.set_camera(scene, cam))) return 1;
             } else
             if (reproject && f > 0 ? !renders[0]->set_camera_reproject(scene, cam, history) : !renders[0]->set_camera(scene, cam)) return 1;
             if (rebuild) {                                                   // --rebuild-above R: the refitted trees have grown past R times their built size
