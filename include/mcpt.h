@@ -152,7 +152,12 @@ typedef struct mcpt_ctx mcpt_ctx;
 /* Replaces Render::Render(Model&) (Render.cpp:5-10): copies what it needs from `scene` (the caller may free it
  * afterwards, like the reference's by-value `model` member, Render.h:57), flattens faces into triangles and
  * collects emissive ones as lights (tranform_triangle, Render.cpp:12-44), builds the BVH (BVH.cpp:6-54) and
- * uploads everything to HBM.  Allocates a zeroed width*height accumulator. */
+ * uploads everything to HBM.  Allocates a zeroed width*height accumulator.
+ * Refused with MCPT_ERR_INVALID_ARG, the face named in mcpt_last_error: a vertex coordinate or a texture coordinate that a face uses and that is
+ * not finite or exceeds 1e18 in magnitude (with the barycentrics of an accepted hit the interpolated uv is then always finite; a texcoord that is
+ * not a number would make the texture lookup convert NaN to an integer).  Refused likewise: a camera whose cross(front, up) is zero or not finite
+ * -- `up` parallel to the view direction or zero, eye == lookat, a field that is not finite --, since right = cross / |cross| would make every ray
+ * NaN.  An `up` that is merely not unit or not orthogonal to the view is used as given. */
 mcpt_status mcpt_create(const mcpt_scene_desc* scene, const mcpt_opts* opts, mcpt_ctx** out_ctx);
 mcpt_status mcpt_destroy(mcpt_ctx* ctx);
 /* A second context for the same scene on device `device` (may equal the source's): the scene streams are copied device to device, nothing is
@@ -190,7 +195,8 @@ mcpt_status mcpt_read_accum(mcpt_ctx* ctx, float* rgba_host);     /* synchronise
 mcpt_status mcpt_write_accum(mcpt_ctx* ctx, const float* rgba_host);   /* resume / merge */
 mcpt_status mcpt_clear_accum(mcpt_ctx* ctx);
 /* Scene::getPixelsColor (Scene.cpp:23-33) on the device: mean -> clamp[0,1] -> pow(.,0.5) -> *255.99 -> u8.
- * flip_y != 0 additionally applies Scene::save_image's vertical flip (Scene.cpp:40-46). */
+ * flip_y != 0 additionally applies Scene::save_image's vertical flip (Scene.cpp:40-46).
+ * The mean is sum / count in fp32: a NaN mean gives 0, +inf gives 255, negative and -inf give 0, count 0 with sum 0 gives 0 (0 / 0 is NaN). */
 mcpt_status mcpt_tonemap(mcpt_ctx* ctx, uint8_t* rgb_host, int flip_y);
 /* ABI 4: the same without the last host copy -- *out_rgb points at the context's own pinned host image (width * height * 3 bytes), valid until
  * the next tonemap call on this context or mcpt_destroy.  This is Scene::getPixelsColor's own contract (Scene.cpp:23-33 returns a pointer
@@ -282,8 +288,10 @@ mcpt_status mcpt_probe_tile_error(mcpt_ctx* ctx, const float* h_rgba_host, const
  * (mcpt_denoise / mcpt_read_features / mcpt_read_tile_error answer as on a context that never had them). */
 
 /* New camera for the same film size.  camera->width / height must equal the context's (else MCPT_ERR_INVALID_ARG, nothing changed);
- * eye == lookat or a non-finite field: MCPT_ERR_INVALID_ARG.  Works on every context, MCPT_FLAG_DYNAMIC or not.  The constants are formed by
- * the function mcpt_create uses: the same camera gives the same rays, bit for bit, either way. */
+ * eye == lookat, a non-finite field, or an `up` whose cross(front, up) is zero or not finite (parallel to the view direction, or zero; see
+ * mcpt_create): MCPT_ERR_INVALID_ARG, nothing changed.  Every other call that takes a camera for a live context refuses the same.  Works on
+ * every context, MCPT_FLAG_DYNAMIC or not.  The constants are formed by the function mcpt_create uses: the same camera gives the same rays, bit
+ * for bit, either way. */
 mcpt_status mcpt_set_camera(mcpt_ctx* ctx, const mcpt_camera* camera);
 
 /* New positions (and optionally new normals) for the SAME faces: n_vertex / n_normal must equal those of the mcpt_scene_desc the context was
@@ -992,7 +1000,8 @@ mcpt_status mcpt_probe_sample_light(mcpt_ctx* ctx, uint32_t n, const double* poi
  * wf_trace8_kernel over a path pool, item = entry of an n x 1 film); the cross-check megakernel only under MCPT_PIPELINE=mega. */
 mcpt_status mcpt_probe_paths(mcpt_ctx* ctx, uint32_t n, const double* origin, const double* dir, uint64_t seed, float* out_L3);
 /* Texture::get_color (model.cpp:30-41) of material `material`'s Map_Kd for n (u, v) pairs (fp32, as the device interpolates them):
- * nearest texel, fract + clamp01's 0.999 cap, no v flip; a 1x1 texture returns its constant colour. */
+ * nearest texel, fract + clamp01's 0.999 cap, no v flip; a 1x1 texture returns its constant colour.  A uv that is not finite is refused on the
+ * host (MCPT_ERR_INVALID_ARG, nothing enqueued): no scene mcpt_create accepts can produce one. */
 mcpt_status mcpt_probe_texture(mcpt_ctx* ctx, uint32_t material, uint32_t n, const float* uv2, float* out_rgb3);
 /* The generator itself: n*4 uniforms for (pixel, sample, block) triples -- pins oracle and device to one stream. */
 mcpt_status mcpt_probe_rng(mcpt_ctx* ctx, uint32_t n, const uint32_t* pixel_sample_block3, uint64_t seed, float* out4);

@@ -1434,6 +1434,8 @@ static mcpt_status check_camera(const mcpt_ctx* ctx, const mcpt_camera* cm, cons
     for (int a = 0; a < 3; a++) finite = finite && std::isfinite(cm->eye[a]) && std::isfinite(cm->lookat[a]) && std::isfinite(cm->up[a]);
     if (!finite) return fail(MCPT_ERR_INVALID_ARG, who + "a camera field is not finite");
     if (cm->eye[0] == cm->lookat[0] && cm->eye[1] == cm->lookat[1] && cm->eye[2] == cm->lookat[2]) return fail(MCPT_ERR_INVALID_ARG, who + "eye == lookat");
+    const std::string bad = camera_defect(*cm);
+    if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, who + bad);
     return MCPT_OK;
 }
 // The camera travels by value with every launch (DevScene::cam): launches already enqueued keep the old one, later ones get this one.
@@ -2907,6 +2909,8 @@ mcpt_status mcpt_probe_texture(mcpt_ctx* ctx, uint32_t material, uint32_t n, con
     if (!uv2 || !out_rgb3) return fail(MCPT_ERR_INVALID_ARG, "null argument");
     if (material >= uint32_t(ctx->dev.n_mats)) return fail(MCPT_ERR_INVALID_ARG, "material index out of range");
     if (n == 0) return MCPT_OK;
+    for (size_t i = 0; i < 2 * size_t(n); i++)
+        if (!std::isfinite(uv2[i])) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_texture: uv is not finite");    // (int)(NaN * tex_w) is undefined; a scene's own uv are finite
     Scratch s(ctx->stream); float *d_uv, *d_out;
     HIP_TRY(s.in(uv2, 2 * size_t(n), &d_uv)); HIP_TRY(s.out(3 * size_t(n), &d_out));
     HIP_TRY(launch_probe_texture(ctx->dev, int(material), n, d_uv, d_out, ctx->stream));

@@ -479,6 +479,16 @@ void camera_constants(const mcpt_camera& cm, const double* ctr, DevCamera& cam) 
     for (int a = 0; a < 3; a++) cam.right[a] = rt[a] * inv;
     cam.width = cm.width; cam.height = cm.height;
 }
+// What camera_constants needs of a camera, in its own arithmetic: cross(front, up) with a length it can divide by.  An `up` parallel to the view
+// direction (or zero) gives right = 0 / 0, eye == lookat or a non-finite field a front that is not a number: every ray would be NaN.  Empty = usable.
+std::string camera_defect(const mcpt_camera& cm) {
+    DevCamera cam;
+    const double zero[3] = {0.0, 0.0, 0.0};
+    camera_constants(cm, zero, cam);
+    bool ok = std::isfinite(cam.h) && (cam.right[0] != 0.0 || cam.right[1] != 0.0 || cam.right[2] != 0.0);      // (an `up` of 1e200: 1 / |cross| underflows to 0)
+    for (int a = 0; a < 3; a++) ok = ok && std::isfinite(cam.front[a]) && std::isfinite(cam.right[a]) && std::isfinite(cam.up[a]) && std::isfinite(cam.eye[a]);
+    return ok ? "" : "cross(front, up) is zero or not finite (up parallel to the view direction, eye == lookat, or a field that is not finite)";
+}
 
 // The same containment walk for the binary tree (mcpt_probe_validate_trees): every leaf triangle's fp32 test data inside every child box on its
 // root path, every triangle referenced exactly once, child links in range; empty string = sound.
@@ -687,6 +697,7 @@ mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::stri
     if (d->camera.width <= 0 || d->camera.height <= 0) { err = "camera width/height must be positive"; return MCPT_ERR_INVALID_ARG; }
     if (uint64_t(d->camera.width) * uint64_t(d->camera.height) >= uint64_t(MCPT_FASTDIV_MAX)) { err = "film too large (limit 2^30 - 1 pixels)"; return MCPT_ERR_UNSUPPORTED; }
     if (d->n_face >= (1u << 28)) { err = "too many faces (limit 2^28-1)"; return MCPT_ERR_UNSUPPORTED; }
+    { const std::string bad = camera_defect(d->camera); if (!bad.empty()) { err = "camera: " + bad; return MCPT_ERR_INVALID_ARG; } }
     const uint32_t nf = d->n_face;
 
     // ---- materials + textures
@@ -730,6 +741,12 @@ mcpt_status build_host_scene(const mcpt_scene_desc* d, HostScene& out, std::stri
                 c[4 * k + 2] < 0 || uint32_t(c[4 * k + 2]) >= d->n_texcoord) { err = "face " + std::to_string(f) + ": index out of range"; return MCPT_ERR_INVALID_ARG; }
         }
         if (c[3] < 0 || uint32_t(c[3]) >= d->n_materials) { err = "face " + std::to_string(f) + ": material out of range"; return MCPT_ERR_INVALID_ARG; }
+        // a texcoord that is not a number makes tex_color convert NaN to int (undefined in C++); within the bound the fp32 interpolation of an
+        // accepted hit (|u|, |v|, |1 - u - v| <= 1 up to rounding) stays finite
+        for (int k = 0; k < 3; k++) for (int a = 0; a < 2; a++)
+            if (!(std::fabs(d->texcoord[2 * size_t(c[4 * k + 2]) + a]) <= kMaxCoord)) {
+                err = "face " + std::to_string(f) + ": texture coordinate is not finite or exceeds 1e18"; return MCPT_ERR_INVALID_ARG;
+            }
         BTri& T = bt[f];
         for (int a = 0; a < 3; a++) {
             const double w0 = d->vertex[3 * size_t(c[0]) + a], w1 = d->vertex[3 * size_t(c[4]) + a], w2 = d->vertex[3 * size_t(c[8]) + a];

@@ -85,5 +85,8 @@ bool rf_levels(const std::vector<f4h>& n2, const std::vector<f4h>& n8, std::vect
 DevMaterial device_material(const mcpt_material& m, const TexInfo& t);
 // DevCamera of `camera` for a scene centred at `centre` (fp64, the reference's operation order): used by mcpt_create and mcpt_set_camera.
 void camera_constants(const mcpt_camera& camera, const double* centre, DevCamera& out);
+// Why camera_constants cannot make rays of `camera` (cross(front, up) zero or not finite: `up` parallel to the view, eye == lookat, a field that is
+// not finite), or the empty string: asked by mcpt_create, mcpt_check_scene and every call that takes a camera for a live context.
+std::string camera_defect(const mcpt_camera& camera);
 // The coordinate bound build_host_scene enforces on every vertex a face uses.
 constexpr double MCPT_MAX_COORD = 1e18;

@@ -213,6 +213,38 @@ def test_reference_undefined_behaviour_becomes_error_codes(pkg):
     assert st == 0
 
 
+def test_texcoords_and_cameras_that_would_make_nan_are_refused(pkg):
+    """Two inputs that reach the device unvalidated otherwise: a texture coordinate that is not finite (tex_color would convert NaN to int, undefined
+    in C++) or past the 1e18 the vertices are held to, and a camera whose cross(front, up) is zero or not finite (right = 0 / 0: every ray NaN).
+    MCPT_ERR_INVALID_ARG, the face named; what no face uses is nobody's business, and an `up` 1e-3 rad from the view is a camera."""
+    S = pkg.scenes
+    s = S.open_box(8, 8)
+    f = 5
+    for poison in (np.nan, np.inf, -np.inf, 1e19, -1e19):
+        for corner in range(3):
+            for axis in range(2):
+                t = s.texcoord.copy(); t[int(s.face[f, corner, 2]), axis] = poison
+                st, _, msg = pkg.check_scene(S.SceneData(s.name, s.vertex, s.normal, t, s.face, s.materials, s.camera))
+                faces = [k for k in range(s.n_faces) if int(s.face[f, corner, 2]) in s.face[k, :, 2]]
+                assert st == 1 and "texture coordinate" in msg and "face %d:" % faces[0] in msg, (poison, corner, axis, st, msg)
+    t = s.texcoord.copy(); t[int(s.face[f, 1, 2])] = (1e18, -1e18)                 # the bound itself is inside
+    assert pkg.check_scene(S.SceneData(s.name, s.vertex, s.normal, t, s.face, s.materials, s.camera))[0] == 0
+    t = np.vstack([s.texcoord, [[np.nan, np.inf]]])
+    assert pkg.check_scene(S.SceneData(s.name, s.vertex, s.normal, t, s.face, s.materials, s.camera))[0] == 0
+    c = s.camera
+    front = np.subtract(c.lookat, c.eye)
+    cams = [S.Camera(c.eye, c.lookat, tuple(k * front), c.fovy, 8, 8) for k in (1.0, -2.5, 0.0)]
+    cams += [S.Camera(c.eye, c.eye, c.up, c.fovy, 8, 8), S.Camera(c.eye, c.lookat, (0.0, 1e200, 0.0), c.fovy, 8, 8),
+             S.Camera((np.nan, 0.0, 0.0), c.lookat, c.up, c.fovy, 8, 8), S.Camera(c.eye, c.lookat, (0.0, np.inf, 0.0), c.fovy, 8, 8), S.Camera(c.eye, c.lookat, c.up, np.nan, 8, 8)]
+    for cam in cams:
+        st, _, msg = pkg.check_scene(S.SceneData(s.name, s.vertex, s.normal, s.texcoord, s.face, s.materials, cam))
+        assert st == 1 and msg.startswith("camera: cross(front, up)"), (cam, st, msg)
+    fr = front / np.linalg.norm(front)
+    near = tuple(np.cos(1e-3) * fr + np.sin(1e-3) * np.array([0.0, 1.0, 0.0]))
+    for up in (near, (0.0, 2.5, 0.0), (0.3, 1.0, 0.2)):
+        assert pkg.check_scene(S.SceneData(s.name, s.vertex, s.normal, s.texcoord, s.face, s.materials, S.Camera(c.eye, c.lookat, up, c.fovy, 8, 8)))[0] == 0
+
+
 def test_quantised_bvh8_is_conservative_on_awkward_geometry(pkg):
     """mcpt_check_scene walks the 8-wide tree as the kernel dequantises it and fails if any triangle sticks out of a box on its path.
     Feed it geometry that stresses the 8-bit frames: huge coordinate offsets, tiny and huge triangles side by side, flat boxes."""

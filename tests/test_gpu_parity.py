@@ -722,6 +722,9 @@ def test_refused_probes_leave_nothing_enqueued(pkg, idle_box):
     assert r.lib.mcpt_probe_tile_error(r.ctx, vp(h), vp(h), float("nan"), 64, vp(err), vp(lst), C.byref(n)) == ERR_INVALID_ARG
     face = np.array([0, 10 ** 6], np.int32); uv = np.zeros(2, np.float32); d = np.ones((2, 3), np.float64); out = np.zeros((2, 6), np.float32)
     assert r.lib.mcpt_probe_hit_shade(r.ctx, 2, vp(face), vp(uv), vp(uv), vp(d), vp(out)) == ERR_INVALID_ARG
+    for poison in (np.nan, np.inf, -np.inf):                                   # (int)(NaN * tex_w) is undefined: the texture probe refuses what no scene can hold
+        tuv = np.array([[0.25, 0.5], [0.5, poison]], np.float32); rgb = np.zeros((2, 3), np.float32)
+        assert r.lib.mcpt_probe_texture(r.ctx, 0, 2, vp(tuv), vp(rgb)) == ERR_INVALID_ARG and not rgb.any()
     r.render(4, seed=1); film = r.read_accum()
     r.close()
     assert np.array_equal(bits(film), bits(idle_box["film4"]))
