@@ -954,6 +954,76 @@ mcpt_status mcpt_set_face_visibility_reproject(mcpt_ctx* ctx, const uint8_t* vis
 mcpt_status mcpt_get_visibility_info(mcpt_ctx* ctx, mcpt_visibility_info* out);   /* synchronises */
 mcpt_status mcpt_probe_triangles(mcpt_ctx* ctx, float* out_v0e1e2 /* 9 per face */, float* out_box6 /* 6 per face */);   /* face order; either may be NULL */
 
+/* ---- camera models ---------------------------------------------------------------------------------------------------------- */
+/* A ray-generation stage in front of the unchanged render kernels: mcpt_render_camera writes one primary ray per pixel for the model set here
+ * (a HIP kernel, csrc/camera.hip) and hands the rays to the wavefront pipeline through the hook mcpt_probe_paths uses, once per sample.  A path
+ * of pixel p and sample s draws exactly the random numbers mcpt_render draws for (p, s); the lens sample comes from the camera block's two spare
+ * numbers.  With MCPT_CAMERA_PINHOLE the stage reproduces mcpt_render's film bit for bit.
+ *
+ * The models, with the camera frame of mcpt_set_camera (front, right, `up` as given, h = 2 tan(fovy / 2)), (u, v) the pinhole's image-plane
+ * coordinates of the jittered pixel point and (u0, v0) in [-1/2, 1/2) its position on the film:
+ *   PINHOLE       origin eye, direction normalize(front + u right + v up): mcpt_render's camera.
+ *   THIN_LENS     D = front + u right + v up; the ray leaves the lens point eye + lens_radius (lx right + ly lup), lup = cross(right, front), towards
+ *                 eye + focus_distance D.  What the pinhole sees at distance focus_distance along `front` is sharp; lens_radius 0 is the pinhole.
+ *                 (lx, ly): uniform on the unit disk (blades 0) or on the regular polygon of `blades` corners, the first at angle blade_rotation.
+ *                 An `up` that is not orthogonal to `front` shears the image exactly as it shears the pinhole's: the plane in focus is the pinhole
+ *                 image of that camera.  Documented, not corrected.
+ *   ORTHOGRAPHIC  origin eye + (u0 ortho_height width / height) right + (v0 ortho_height) up, direction front.  fovy is ignored.
+ *   EQUIRECT      origin eye, direction cos(phi) (cos(lambda) front + sin(lambda) right) + sin(phi) lup with lambda = 2 pi u0, phi = pi v0: the whole
+ *                 sphere, the view direction in the film's centre.  fovy is ignored; any film shape is accepted.
+ *
+ * mcpt_set_camera_model: validated on the host, a refusal changes nothing: MCPT_ERR_INVALID_ARG for a struct_size that is not this library's, an
+ * unknown model, or a field of the CHOSEN model outside its range below (fields of other models are ignored).  NULL = PINHOLE.  Works on every
+ * context; free.  mcpt_set_camera keeps the model (its parameters are relative to the camera frame); mcpt_clone_to_device carries the model
+ * and not the ray buffers.
+ *
+ * ONLY mcpt_render_camera and mcpt_probe_camera_rays look at the model.  mcpt_render, mcpt_render_tiles, mcpt_render_tile_list,
+ * mcpt_render_adaptive, mcpt_render_features, mcpt_probe_first_hits, the reprojection calls and mcpt_denoise's guide describe the PINHOLE view
+ * whatever model is set: a denoised, reprojected or adaptively sampled film of another model is guided by features that do not belong to it.
+ * Carrying the models into those kernels is follow-up work.
+ *
+ * mcpt_render_camera: adds `spp` samples (first_sample .. first_sample + spp - 1 of `seed`) of the set model to every pixel of the bound film; on
+ * the context's stream, ordered like mcpt_render.  One pass per sample: the ray kernel, then the wavefront pipeline over width * height
+ * one-sample items -- a many-sample still pays the per-pass overhead that mcpt_render's batching avoids (DESIGN.md §25 has the numbers).  Counted as
+ * ONE launch in mcpt_counters, its paths and rays like mcpt_render's.  The two ray buffers (48 B per pixel together) are allocated by the first
+ * call and counted in mcpt_scene_info::device_bytes.  spp == 0 does nothing.  MCPT_ERR_UNSUPPORTED without the wavefront pipeline
+ * (MCPT_INTEGRATOR_RECURSIVE_NEE, MCPT_PIPELINE=mega); MCPT_ERR_INVALID_ARG when first_sample + spp > 2^32 or the film has more than
+ * 67 108 863 pixels (what one mcpt_probe_paths call takes).
+ *
+ * mcpt_autofocus: the focus_distance that makes pixel (px, py) sharp: t dot(d, front) for the pixel-centre pinhole ray's direction d and its
+ * first hit at t (the kernel behind mcpt_probe_first_hits).  MCPT_ERR_INVALID_ARG for a pixel outside the film or a ray that hits nothing;
+ * MCPT_ERR_BVH_DEPTH where mcpt_probe_first_hits answers it.  Synchronous; touches nothing (the model included: pass the value on).
+ *
+ * mcpt_probe_camera_rays: the stage's device function for n pixels (xy: 2 ints each, inside the film) of sample `sample`: per ray the origin in
+ * DEVICE coordinates (world less mcpt_scene_info::centre) and the direction (fp32 values), 3 doubles each.  Synchronous; touches nothing. */
+#define MCPT_CAMERA_PINHOLE      0u
+#define MCPT_CAMERA_THIN_LENS    1u
+#define MCPT_CAMERA_ORTHOGRAPHIC 2u
+#define MCPT_CAMERA_EQUIRECT     3u
+#define MCPT_CAMERA_MAX_BLADES   16u
+typedef struct mcpt_camera_model {
+    uint32_t struct_size, model;          /* MCPT_CAMERA_* */
+    double   lens_radius, focus_distance; /* THIN_LENS: radius finite and >= 0, focus finite and > 0 */
+    uint32_t blades, reserved0;           /* THIN_LENS: 0 = disk, 3..16 = polygon */
+    double   blade_rotation;              /* radians, finite */
+    double   ortho_height;                /* ORTHOGRAPHIC: finite, > 0 */
+    uint32_t reserved[4];
+} mcpt_camera_model;
+typedef struct mcpt_camera_model_info {
+    uint32_t struct_size, model;          /* the model in force */
+    uint32_t renders, reserved0;          /* mcpt_render_camera calls that enqueued work on this context */
+    uint64_t passes;                      /* ... and their samples: one ray kernel each */
+    double   last_stage_ms;               /* HIP events: the ray kernels of the last call, summed */
+    uint64_t device_bytes;                /* what the ray buffers hold on the device now */
+    uint32_t reserved[4];
+} mcpt_camera_model_info;
+mcpt_status mcpt_set_camera_model(mcpt_ctx* ctx, const mcpt_camera_model* model /* NULL = PINHOLE */);
+mcpt_status mcpt_get_camera_model(mcpt_ctx* ctx, mcpt_camera_model* out, mcpt_camera_model_info* out_info /* may be NULL; not NULL: synchronises */);
+mcpt_status mcpt_render_camera(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample);
+mcpt_status mcpt_autofocus(mcpt_ctx* ctx, int32_t px, int32_t py, double* out_focus_distance);
+mcpt_status mcpt_probe_camera_rays(mcpt_ctx* ctx, uint32_t n, const int32_t* xy, uint32_t sample, uint64_t seed,
+                                   double* out_origin3 /* device coordinates */, double* out_dir3);
+
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that
  * torch.distributed / RCCL all-reduces in place).  NULL re-binds the internal buffer. */

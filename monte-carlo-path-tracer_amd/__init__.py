@@ -32,6 +32,9 @@ from .parts_abi import (OWNER_GROUPS, OWNER_KEYFRAMES, OWNER_MORPH, OWNER_NONE, 
 from .normals_abi import NORMALS_AREA, NORMALS_OFF, NormalsInfo, NormalsOpts, normal_mask_from_faces  # noqa: F401
 # mcpt_get_visibility_info's struct and the mask that hides a set of materials' faces; tests/test_visibility.py holds the layout to the header
 from .visibility_abi import VisibilityInfo, visibility_from_materials  # noqa: F401
+# mcpt_set_camera_model's struct, mcpt_get_camera_model's info and the model constants; tests/test_camera_ref.py holds the layouts to the header
+from .camera_abi import (CAMERA_EQUIRECT, CAMERA_MAX_BLADES, CAMERA_ORTHOGRAPHIC, CAMERA_PINHOLE, CAMERA_THIN_LENS, CameraModel, CameraModelInfo,  # noqa: F401
+                         camera_model)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmcpt_hip.so")
@@ -325,6 +328,11 @@ def load_library() -> C.CDLL:
         "mcpt_set_face_visibility_reproject": [vp, vp, C.c_uint32, P(CameraC), P(ReprojectOpts)],
         "mcpt_get_visibility_info": [vp, P(VisibilityInfo)],
         "mcpt_probe_triangles": [vp, vp, vp],
+        "mcpt_set_camera_model": [vp, P(CameraModel)],
+        "mcpt_get_camera_model": [vp, P(CameraModel), P(CameraModelInfo)],
+        "mcpt_render_camera": [vp, C.c_uint32, C.c_uint64, C.c_uint32],
+        "mcpt_autofocus": [vp, C.c_int32, C.c_int32, P(C.c_double)],
+        "mcpt_probe_camera_rays": [vp, C.c_uint32, vp, C.c_uint32, C.c_uint64, vp, vp],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -359,6 +367,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_auto_normals", "mcpt_update_normals", "mcpt_get_normals_info",
     "mcpt_rebuild_trees", "mcpt_get_rebuild_info",
     "mcpt_set_face_visibility", "mcpt_set_face_visibility_reproject", "mcpt_get_visibility_info", "mcpt_probe_triangles",
+    "mcpt_set_camera_model", "mcpt_get_camera_model", "mcpt_render_camera", "mcpt_autofocus", "mcpt_probe_camera_rays",
 ]
 
 
@@ -841,6 +850,43 @@ class Renderer:
         rec = np.zeros((nf, 9), np.float32); box = np.zeros((nf, 6), np.float32) if boxes else None
         self._check(self.lib.mcpt_probe_triangles(self.ctx, _ptr(rec), _ptr(box)))
         return (rec, box) if boxes else rec
+
+    # ---- camera models through a ray-generation stage
+    def set_camera_model(self, model: int = CAMERA_PINHOLE, lens_radius=0.0, focus_distance=0.0, blades=0, blade_rotation=0.0, ortho_height=0.0):
+        """The camera model render_camera and probe_camera_rays use from now on: CAMERA_PINHOLE, CAMERA_THIN_LENS (lens_radius >= 0,
+        focus_distance > 0, blades 0 = disk or 3..16 = polygon turned by blade_rotation radians), CAMERA_ORTHOGRAPHIC (ortho_height > 0: the
+        film's height in world units) or CAMERA_EQUIRECT.  Fields of other models are ignored.  render() and every other call stay pinhole."""
+        m = camera_model(model, lens_radius, focus_distance, blades, blade_rotation, ortho_height)
+        self._check(self.lib.mcpt_set_camera_model(self.ctx, C.byref(m)))
+
+    def camera_model(self) -> CameraModel:
+        m = CameraModel()
+        self._check(self.lib.mcpt_get_camera_model(self.ctx, C.byref(m), None))
+        return m
+
+    def camera_model_info(self) -> CameraModelInfo:
+        m = CameraModel(); i = CameraModelInfo()
+        self._check(self.lib.mcpt_get_camera_model(self.ctx, C.byref(m), C.byref(i)))
+        return i
+
+    def render_camera(self, spp: int, seed: int = 0, first_sample: int = 0):
+        """`spp` samples of the set camera model added to every pixel of the bound film: per sample the ray kernel, then the wavefront pipeline.
+        With CAMERA_PINHOLE the film is render()'s, bit for bit.  Needs the wavefront pipeline (INTEGRATOR_MIS)."""
+        self._check(self.lib.mcpt_render_camera(self.ctx, spp, seed, first_sample))
+
+    def autofocus(self, px: int, py: int) -> float:
+        """The focus_distance that makes pixel (px, py) sharp: the distance of its pixel-centre first hit along the view direction."""
+        out = C.c_double(0.0)
+        self._check(self.lib.mcpt_autofocus(self.ctx, int(px), int(py), C.byref(out)))
+        return float(out.value)
+
+    def probe_camera_rays(self, xy, sample: int = 0, seed: int = 0):
+        """The set model's primary rays for pixels xy (n, 2) of sample `sample`: ((n, 3) float64 origins in DEVICE coordinates -- world less
+        info().centre --, (n, 3) float64 directions holding fp32 values)."""
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        o = np.zeros((xy.shape[0], 3), np.float64); d = np.zeros((xy.shape[0], 3), np.float64)
+        self._check(self.lib.mcpt_probe_camera_rays(self.ctx, xy.shape[0], _ptr(xy), sample, seed, _ptr(o), _ptr(d)))
+        return o, d
 
     # ---- material, light and texture edits (DESIGN.md §15)
     def update_materials(self, materials, map_kd=None):

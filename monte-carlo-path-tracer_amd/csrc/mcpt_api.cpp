@@ -21,6 +21,7 @@
 #include "materials.h"
 #include "visibility.h"
 #include "visibility_plan.h"
+#include "camera.h"
 
 #include <chrono>
 #include <cmath>
@@ -396,6 +397,20 @@ struct mcpt_ctx {
             return MCPT_OK;
         }
     } vs;
+    // Camera models (camera.hip).  From creation on, on the host: the model in force as the caller gave it (PINHOLE until
+    // mcpt_set_camera_model) and as the ray kernel takes it.  Allocated by the first mcpt_render_camera and counted in device_bytes: the two ray
+    // arrays wf_shade_kernel reads as probe_o / probe_d, 3 doubles per pixel each.  `watch` brackets one pass's ray kernel; stage_ms adds them up
+    // over a call.
+    struct Camera {
+        mcpt_camera_model model{}; CmModel dev{}; DevBuf<double> ray_o, ray_d; Stopwatch watch; uint32_t renders = 0; uint64_t passes = 0; double stage_ms = 0.0;
+        Camera() { model.struct_size = sizeof model; model.model = MCPT_CAMERA_PINHOLE; dev.model = MCPT_CAMERA_PINHOLE; }
+        hipError_t take() {                                                  // the bracketed pass, once it has run, joins the call's sum
+            const bool timed = watch.timed;
+            const hipError_t e = watch.settle();
+            if (e == hipSuccess && timed) stage_ms += watch.last_ms;
+            return e;
+        }
+    } cm;
     // Temporal reprojection (reproject.hip), allocated by the first reprojection call: the old view's features (2 per pixel, swapped
     // with dn_feat per call), a copy of the old film and the reuse counter.
     // Motion-vector reprojection adds, on the first mcpt_update_vertices_reproject: the first hit of every pixel-centre ray and
@@ -824,6 +839,7 @@ mcpt_status mcpt_clone_to_device(mcpt_ctx* src, int32_t device, mcpt_ctx** out_c
     HIP_TRY(copy(&mcpt_ctx::tri_pos64)); HIP_TRY(copy(&mcpt_ctx::tri_face)); HIP_TRY(copy(&mcpt_ctx::mats)); HIP_TRY(copy(&mcpt_ctx::lights));
     HIP_TRY(copy(&mcpt_ctx::light_pos64)); HIP_TRY(copy(&mcpt_ctx::texels));
     c->mt_mats = src->mt_mats; c->mt_tex = src->mt_tex; c->mt_faces = src->mt_faces;
+    c->cm.model = src->cm.model; c->cm.dev = src->cm.dev;                   // §25: the camera model travels, the ray buffers do not
     if ((st = finish_ctx(c)) != MCPT_OK) return st;
     if (src->dynamic && (st = rf_clone(c, src)) != MCPT_OK) return st;
     c->info.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -2736,6 +2752,112 @@ mcpt_status mcpt_probe_triangles(mcpt_ctx* ctx, float* out_v0e1e2, float* out_bo
     return MCPT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ camera models
+mcpt_status mcpt_set_camera_model(mcpt_ctx* ctx, const mcpt_camera_model* model) {
+    const std::string who = "mcpt_set_camera_model: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    mcpt_camera_model m;
+    if ((st = read_opts(model, m, "mcpt_set_camera_model", "mcpt_camera_model")) != MCPT_OK) return st;
+    if (m.model > MCPT_CAMERA_EQUIRECT) return fail(MCPT_ERR_INVALID_ARG, who + "unknown model");
+    if (m.model == MCPT_CAMERA_THIN_LENS) {
+        if (!std::isfinite(m.lens_radius) || m.lens_radius < 0.0) return fail(MCPT_ERR_INVALID_ARG, who + "lens_radius must be finite and >= 0");
+        if (!std::isfinite(m.focus_distance) || !(m.focus_distance > 0.0)) return fail(MCPT_ERR_INVALID_ARG, who + "focus_distance must be finite and > 0");
+        if (m.blades != 0u && (m.blades < 3u || m.blades > MCPT_CAMERA_MAX_BLADES)) return fail(MCPT_ERR_INVALID_ARG, who + "blades must be 0 (a disk) or in [3, 16]");
+        if (!std::isfinite(m.blade_rotation)) return fail(MCPT_ERR_INVALID_ARG, who + "blade_rotation must be finite");
+    }
+    if (m.model == MCPT_CAMERA_ORTHOGRAPHIC && (!std::isfinite(m.ortho_height) || !(m.ortho_height > 0.0))) return fail(MCPT_ERR_INVALID_ARG, who + "ortho_height must be finite and > 0");
+    ctx->cm.model = m; ctx->cm.dev = cm_make_model(m);                     // (by value with every launch, like the camera: launches already enqueued keep the old one)
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_get_camera_model(mcpt_ctx* ctx, mcpt_camera_model* out, mcpt_camera_model_info* out_info) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    *out = ctx->cm.model;
+    if (!out_info) return MCPT_OK;
+    mcpt_ctx::Camera& cm = ctx->cm;
+    HIP_TRY(cm.take());                                                      // (the last call's last pass joins its sum; info_begin then finds the watch settled)
+    st = info_begin(ctx, out_info, &cm.watch); if (st != MCPT_OK) return st;
+    out_info->model = cm.model.model; out_info->renders = cm.renders; out_info->passes = cm.passes; out_info->last_stage_ms = cm.stage_ms;
+    out_info->device_bytes = cm.ray_o.bytes + cm.ray_d.bytes;
+    return MCPT_OK;
+}
+
+// The RenderParams of a probe job but for its three probe_* fields: item i = entry i of an n x 1 film, one sample `sample` of `seed` each.  Shared by
+// mcpt_probe_paths (host rays, a scratch film) and mcpt_render_camera (the stage's rays, the bound film).
+static RenderParams probe_job_params(const mcpt_ctx* ctx, uint32_t sample, uint64_t seed, uint32_t flags) {
+    RenderParams p; std::memset(&p, 0, sizeof p);
+    p.spp = 1; p.first_sample = sample; p.samples_per_item = 1; p.chunks = 1; p.tiles_x = 0x7fffffffu; p.tiles_y = 1; p.tile_mod = 1; p.tile_rem = 0; p.n_owned = 0x7fffffffu;
+    p.max_depth = ctx->opts.max_depth; p.flags = flags; p.integrator = MCPT_INTEGRATOR_MIS;
+    p.seed_lo = uint32_t(seed); p.seed_hi = uint32_t(seed >> 32);
+    return p;
+}
+
+mcpt_status mcpt_render_camera(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample) {
+    const std::string who = "mcpt_render_camera: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->use_wavefront || ctx->lanes.empty()) return fail(MCPT_ERR_UNSUPPORTED, who + "needs the wavefront pipeline (MCPT_INTEGRATOR_MIS, no MCPT_PIPELINE=mega)");
+    if (uint64_t(first_sample) + spp > (1ull << 32)) return fail(MCPT_ERR_INVALID_ARG, who + "first_sample + spp exceeds 2^32");
+    const uint64_t n = uint64_t(ctx->width) * uint64_t(ctx->height);
+    if (n > 0x3ffffffull) return fail(MCPT_ERR_INVALID_ARG, who + "the film has more pixels than a probe call takes");
+    if (spp == 0) return MCPT_OK;
+    mcpt_ctx::Camera& cm = ctx->cm;
+    if (!cm.ray_o.p) HIP_TRY(alloc_all(Want(cm.ray_o, 3 * size_t(n), &ctx->info.device_bytes), Want(cm.ray_d, 3 * size_t(n), &ctx->info.device_bytes), Want(cm.watch, 1, nullptr, !cm.watch.ev0)));
+    HIP_TRY(cm.take());                                                      // (the last call's last pass)
+    cm.stage_ms = 0.0;
+    st = timed_begin(ctx); if (st != MCPT_OK) return st;
+    for (uint32_t k = 0; k < spp; k++) {
+        const uint32_t s = first_sample + k;
+        HIP_TRY(cm.take());
+        HIP_TRY(cm.watch.begin(ctx->stream));
+        HIP_TRY(launch_cm_rays(ctx->dev.cam, cm.dev, s, uint32_t(seed), uint32_t(seed >> 32), cm.ray_o.p, cm.ray_d.p, ctx->stream));
+        HIP_TRY(cm.watch.end(ctx->stream));
+        // the sub-pipeline's stream forks from the context's after the ray kernel and joins it again: the next pass's kernel overwrites the rays only
+        // after this pass's paths have read them
+        RenderParams p = probe_job_params(ctx, s, seed, ctx->opts.flags);
+        p.probe_n = uint32_t(n); p.probe_o = cm.ray_o.p; p.probe_d = cm.ray_d.p;
+        st = render_wavefront(ctx, p, ctx->accum); if (st != MCPT_OK) return st;
+        cm.passes++;
+    }
+    cm.renders++;
+    return timed_end(ctx);
+}
+
+mcpt_status mcpt_autofocus(mcpt_ctx* ctx, int32_t px, int32_t py, double* out_focus_distance) {
+    const std::string who = "mcpt_autofocus: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out_focus_distance) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    if (px < 0 || py < 0 || px >= ctx->width || py >= ctx->height) return fail(MCPT_ERR_INVALID_ARG, who + "the pixel is outside the film");
+    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the first-hit kernel's traversal stack");
+    const size_t n = size_t(ctx->width) * ctx->height, i = size_t(py) * ctx->width + size_t(px);
+    const int32_t xy[2] = {px, py}; const float xi[2] = {0.5f, 0.5f};
+    float rec[4], ray[6];
+    {   Scratch s(ctx->stream); float4* hits; int* d_xy; float *d_xi, *d_ray;
+        HIP_TRY(s.out(n, &hits)); HIP_TRY(s.in(xy, 2, &d_xy)); HIP_TRY(s.in(xi, 2, &d_xi)); HIP_TRY(s.out(6, &d_ray));
+        HIP_TRY(launch_rp_first_hit(ctx->dev, hits, ctx->stream));
+        HIP_TRY(launch_probe_cast_ray(ctx->dev, 1, d_xy, d_xi, d_ray, ctx->stream));      // the same pixel-centre ray: its direction as the device forms it
+        HIP_TRY(s.fetch(rec, hits + i, 4)); HIP_TRY(s.fetch(ray, d_ray, 6)); HIP_TRY(s.finish()); }
+    int32_t tri; std::memcpy(&tri, &rec[0], 4);
+    if (tri < 0) return fail(MCPT_ERR_INVALID_ARG, who + "the pixel-centre ray hits nothing");
+    const double* f = ctx->dev.cam.front;
+    *out_focus_distance = double(rec[3]) * (double(ray[3]) * f[0] + double(ray[4]) * f[1] + double(ray[5]) * f[2]);
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_camera_rays(mcpt_ctx* ctx, uint32_t n, const int32_t* xy, uint32_t sample, uint64_t seed, double* out_origin3, double* out_dir3) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!xy || !out_origin3 || !out_dir3) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    for (size_t k = 0; k < size_t(n); k++)
+        if (xy[2 * k] < 0 || xy[2 * k + 1] < 0 || xy[2 * k] >= ctx->width || xy[2 * k + 1] >= ctx->height)
+            return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_camera_rays: pixel " + std::to_string(k) + " is outside the film");
+    if (n == 0) return MCPT_OK;
+    Scratch s(ctx->stream); int* d_xy; double *d_o, *d_d;
+    HIP_TRY(s.in(xy, 2 * size_t(n), &d_xy)); HIP_TRY(s.out(3 * size_t(n), &d_o)); HIP_TRY(s.out(3 * size_t(n), &d_d));
+    HIP_TRY(launch_cm_probe(ctx->dev.cam, ctx->cm.dev, n, d_xy, sample, uint32_t(seed), uint32_t(seed >> 32), d_o, d_d, ctx->stream));
+    HIP_TRY(s.fetch(out_origin3, d_o, 3 * size_t(n))); HIP_TRY(s.fetch(out_dir3, d_d, 3 * size_t(n))); HIP_TRY(s.finish());
+    return MCPT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ probes
 mcpt_status mcpt_probe_trace(mcpt_ctx* ctx, uint32_t n, const double* origin, const double* dir, const double* t1, const double* t2, int any_hit,
                              float* out_t, int32_t* out_tri, float* out_u, float* out_v) {
@@ -2877,10 +2999,7 @@ mcpt_status mcpt_probe_paths(mcpt_ctx* ctx, uint32_t n, const double* origin, co
     if (ctx->opts.integrator != MCPT_INTEGRATOR_MIS) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_probe_paths drives the MIS integrator only");
     Scratch s(ctx->stream); double *d_o, *d_d; float* d_out; DevCounters* d_cnt;
     HIP_TRY(s.in(s.keep(to_local(ctx, origin, n)), 3 * size_t(n), &d_o)); HIP_TRY(s.in(dir, 3 * size_t(n), &d_d)); HIP_TRY(s.out(3 * size_t(n), &d_out)); HIP_TRY(s.out(1, &d_cnt));
-    RenderParams p; std::memset(&p, 0, sizeof p);
-    p.spp = 1; p.first_sample = 0; p.samples_per_item = 1; p.chunks = 1; p.tiles_x = 0x7fffffffu; p.tiles_y = 1; p.tile_mod = 1; p.tile_rem = 0; p.n_owned = 0x7fffffffu;
-    p.max_depth = ctx->opts.max_depth; p.flags = ctx->opts.flags & ~MCPT_FLAG_COUNT_TRAVERSAL; p.integrator = MCPT_INTEGRATOR_MIS;
-    p.seed_lo = uint32_t(seed); p.seed_hi = uint32_t(seed >> 32);
+    RenderParams p = probe_job_params(ctx, 0u, seed, ctx->opts.flags & ~MCPT_FLAG_COUNT_TRAVERSAL);
     if (ctx->use_wavefront) {
         // the production pipeline: [wf_shade, wf_trace] iterations over the path pool, item i = entry i of an n x 1 film
         if (n > 0x3ffffffu) return fail(MCPT_ERR_UNSUPPORTED, "mcpt_probe_paths: too many paths for one call");

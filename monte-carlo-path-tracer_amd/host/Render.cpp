@@ -50,17 +50,33 @@ Render::~Render() {
 }
 
 void Render::render(Scene& scene) { render(scene, 1); }
-void Render::render(Scene& scene, uint32_t spp) {
-    if (!ctx || spp == 0) return;
-    if (scene.width() * scene.height() * 4 != int(film.size())) { std::cerr << "Error: Render::render: the Scene's size differs from the camera's" << std::endl; return; }
+void Render::render(Scene& scene, uint32_t spp) { (void)render_samples(scene, spp, false); }
+bool Render::render_camera(Scene& scene, uint32_t spp) { return render_samples(scene, spp, true); }
+bool Render::set_camera_model(Scene& scene, const mcpt_camera_model& model) {
+    if (!ctx) return false;
+    if (mcpt_set_camera_model(ctx, &model) != MCPT_OK) { std::cerr << "Error: mcpt_set_camera_model: " << mcpt_last_error() << std::endl; return false; }
+    return restart(scene);
+}
+bool Render::autofocus(Scene&, int px, int py, double& focus_distance) {
+    if (!ctx) return false;
+    if (mcpt_autofocus(ctx, px, py, &focus_distance) != MCPT_OK) { std::cerr << "Error: mcpt_autofocus: " << mcpt_last_error() << std::endl; return false; }
+    return true;
+}
+// `spp` samples into `scene`: of the pinhole camera (mcpt_render), or -- `camera_model` -- of the model set_camera_model chose (mcpt_render_camera, §25)
+bool Render::render_samples(Scene& scene, uint32_t spp, bool camera_model) {
+    if (!ctx || spp == 0) return ctx != nullptr;
+    if (scene.width() * scene.height() * 4 != int(film.size())) { std::cerr << "Error: Render::render: the Scene's size differs from the camera's" << std::endl; return false; }
     // the film lives in `scene` (several Renders may share one Scene); this Render's share of it stays on the device until read
     if (target != &scene) {
         if (target) { flush_into(*target); target->detach(this); }
         target = &scene;
     }
     scene.attach(this);                               // (flushes whichever other Render held samples for `scene`)
-    if (mcpt_render(ctx, spp, seed, next_sample) != MCPT_OK) { std::cerr << "Error: mcpt_render: " << mcpt_last_error() << std::endl; return; }
+    if ((camera_model ? mcpt_render_camera : mcpt_render)(ctx, spp, seed, next_sample) != MCPT_OK) {
+        std::cerr << "Error: " << (camera_model ? "mcpt_render_camera: " : "mcpt_render: ") << mcpt_last_error() << std::endl; return false;
+    }
     next_sample += spp; dirty = true;
+    return true;
 }
 mcpt_adaptive_stats Render::render_adaptive(Scene& scene, const mcpt_adaptive_opts* opts) {
     mcpt_adaptive_stats st; std::memset(&st, 0, sizeof st); st.struct_size = sizeof st;

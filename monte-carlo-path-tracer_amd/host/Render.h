@@ -131,6 +131,15 @@ public:
     bool set_visible(Scene& scene, const std::vector<uint8_t>& face_visible);
     bool set_visible_reproject(Scene& scene, const std::vector<uint8_t>& face_visible, float max_history = 0);
     bool set_visible_reproject(Scene& scene, const std::vector<uint8_t>& face_visible, const CameraInfo& camera, float max_history = 0);
+    // Camera models.  set_camera_model: thin lens (depth of field), orthographic or panorama instead of the pinhole, for
+    // render_camera alone (mcpt_set_camera_model) -- render(), denoised() and the *_reproject calls keep describing the pinhole view.  Works on
+    // every Render.  Starts the picture again like set_camera().  render_camera: render(scene, spp) with the model's rays (mcpt_render_camera: one
+    // pass per sample; needs the wavefront pipeline); with MCPT_CAMERA_PINHOLE the film is render()'s bit for bit.  autofocus: the focus_distance
+    // that makes pixel (px, py) sharp -- the distance of what the pinhole sees there, along the view direction (mcpt_autofocus); touches nothing.
+    // false (Render and Scene unchanged) on failure.
+    bool set_camera_model(Scene& scene, const mcpt_camera_model& model);
+    bool render_camera(Scene& scene, uint32_t spp = 1);
+    bool autofocus(Scene& scene, int px, int py, double& focus_distance);
     // New trees for the geometry as it is now (mcpt_rebuild_trees): after update() / update_transforms() have moved the scene far
     // (mcpt_update_info::wide_area_ratio says how far) the refitted trees are sound and slow; this builds them anew on the context.  The picture
     // goes ON: `scene`'s film, the sample numbering and the feature buffers stay, the scene looks the same from every pixel.  Synchronous.  false
@@ -152,6 +161,7 @@ private:
     std::vector<int32_t> tex_size;                    // width, height of every material's Map_Kd at creation
     void create(Model& m, const mcpt_opts& opts);
     bool restart(Scene& scene);
+    bool render_samples(Scene& scene, uint32_t spp, bool camera_model);
     bool film_to_device(Scene& scene, const char* who, bool& ok);
     bool update_reproject(Scene& scene, Model* m_model, const std::vector<double>* matrices, bool bones, const std::vector<double>* weights, const CameraInfo* camera,
                           float max_history, const double* time = nullptr, const PartsUpdate* parts = nullptr, const std::vector<uint8_t>* visible = nullptr);

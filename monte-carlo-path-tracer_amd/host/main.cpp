@@ -67,6 +67,13 @@ static void usage() {
                  "                                        in the others; the mask changes only where that changes.  --hide and --blink honour --reproject (the film is\n"
                  "                                        carried across the change) and go with the camera alone: not with --wobble, --light-pulse, --spin, --bend,\n"
                  "                                        --swell or --sequence, and not with each other\n"
+                 "                          [--aperture R --focus D | --autofocus X Y [--blades N [--blade-rotation DEG]]]   a thin lens of radius R instead of the\n"
+                 "                                        pinhole (DESIGN.md 25): sharp at distance D along the view direction, or where pixel (X, Y) -- row 0 at the\n"
+                 "                                        top of the saved image -- looks (with --turntable: in the first frame); the aperture a disk, or a polygon of\n"
+                 "                                        N in [3, 16] blades turned by DEG degrees\n"
+                 "                          [--ortho H]   an orthographic camera whose film is H world units high    [--panorama]   a 360 x 180 degree equirectangular camera\n"
+                 "                                        (these three exclude each other; they go with --turntable and --gpus, not with --adaptive or --shard tiles;\n"
+                 "                                        one pass per sample; --denoise and --reproject keep describing the pinhole view)\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -101,6 +108,8 @@ int main(int argc, char** argv) {
     bool auto_normals = false, dual_quat = false;
     std::string sequence; int sequence_n = 0; bool slowdown_set = false, smooth = false; double slowdown = 1.0;
     std::string hide, blink; int blink_k = 0;
+    bool aperture_set = false, focus_set = false, autofocus_set = false, blades_set = false, rotation_set = false, ortho_set = false, panorama = false;
+    double aperture = 0.0, focus = 0.0, blade_deg = 0.0, ortho_h = 0.0; int focus_x = 0, focus_y = 0, blades = 0;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -133,6 +142,13 @@ int main(int argc, char** argv) {
         else if (a == "--rebuild-above") { rebuild = true; rebuild_above = std::atof(next()); }
         else if (a == "--hide") hide = next();
         else if (a == "--blink") { blink = next(); blink_k = std::atoi(next()); }
+        else if (a == "--aperture") { aperture_set = true; aperture = std::atof(next()); }
+        else if (a == "--focus") { focus_set = true; focus = std::atof(next()); }
+        else if (a == "--autofocus") { autofocus_set = true; focus_x = std::atoi(next()); focus_y = std::atoi(next()); }
+        else if (a == "--blades") { blades_set = true; blades = std::atoi(next()); }
+        else if (a == "--blade-rotation") { rotation_set = true; blade_deg = std::atof(next()); }
+        else if (a == "--ortho") { ortho_set = true; ortho_h = std::atof(next()); }
+        else if (a == "--panorama") panorama = true;
         else { usage(); return 2; }
     }
     if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
@@ -179,6 +195,21 @@ int main(int argc, char** argv) {
         }
         if (!blink.empty() && blink_k < 1) { std::cerr << "Error: --blink MTLNAME K needs K >= 1" << std::endl; return 2; }
     }
+    // --aperture / --ortho / --panorama: the camera model of DESIGN.md 25; the render loops below then call render_camera
+    const bool lens = aperture_set || focus_set || autofocus_set || blades_set || rotation_set;
+    const bool camera_model = lens || ortho_set || panorama;
+    if (int(lens) + int(ortho_set) + int(panorama) > 1) { std::cerr << "Error: --aperture, --ortho and --panorama exclude each other" << std::endl; return 2; }
+    if (lens && (!aperture_set || focus_set == autofocus_set || !(aperture >= 0.0 && aperture <= 1e300) || (focus_set && !(focus > 0.0 && focus <= 1e300)))) {
+        std::cerr << "Error: --aperture R needs R >= 0 and exactly one of --focus D (D > 0) and --autofocus X Y" << std::endl; return 2;
+    }
+    if (blades_set && (blades < 3 || blades > int(MCPT_CAMERA_MAX_BLADES))) { std::cerr << "Error: --blades N needs N in [3, 16]" << std::endl; return 2; }
+    if (rotation_set && (!blades_set || !(std::fabs(blade_deg) <= 1e6))) { std::cerr << "Error: --blade-rotation DEG needs --blades N and a finite DEG" << std::endl; return 2; }
+    if (ortho_set && !(ortho_h > 0.0 && ortho_h <= 1e300)) { std::cerr << "Error: --ortho H needs a finite H > 0" << std::endl; return 2; }
+    if (camera_model && (adaptive >= 0.f || shard_tiles || integrator != MCPT_INTEGRATOR_MIS)) {
+        std::cerr << "Error: --aperture, --ortho and --panorama render pass by pass through the wavefront pipeline: not with --adaptive, --shard tiles or --recursive" << std::endl; return 2;
+    }
+    if (camera_model && (denoise || reproject))
+        std::cerr << "Note: --denoise and --reproject are guided by features of the pinhole view, whatever camera model renders the film" << std::endl;
     if (wobble || !spin.empty() || !bend.empty() || !swell.empty() || !sequence.empty() || !hide.empty() || !blink.empty()) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
@@ -249,6 +280,16 @@ int main(int argc, char** argv) {
             renders[0] = new Render(model, o); renders[0]->seed = seed;
         } else renders[g] = new Render(*renders[0], int(g));
         if (!renders[g]->ok()) return 1;
+    }
+    if (camera_model) {
+        mcpt_camera_model cm; std::memset(&cm, 0, sizeof cm); cm.struct_size = sizeof cm;
+        cm.model = lens ? MCPT_CAMERA_THIN_LENS : ortho_set ? MCPT_CAMERA_ORTHOGRAPHIC : MCPT_CAMERA_EQUIRECT;
+        cm.lens_radius = aperture; cm.focus_distance = focus; cm.blades = uint32_t(blades); cm.blade_rotation = blade_deg * 3.14159265358979323846 / 180.0; cm.ortho_height = ortho_h;
+        if (autofocus_set) {                                                 // (X, Y) as in the saved image, whose row 0 is the film's last
+            if (!renders[0]->autofocus(scene, focus_x, h - 1 - focus_y, cm.focus_distance)) return 1;
+            std::cout << "autofocus: pixel (" << focus_x << ", " << focus_y << ") is " << cm.focus_distance << " away along the view direction" << std::endl;
+        }
+        for (auto r : renders) if (!r->set_camera_model(scene, cm)) return 1;
     }
     // --turntable N: the camera moves, the scene stays -- Render::set_camera per frame, no rebuild, no upload
     if (turntable) {
@@ -472,7 +513,7 @@ int main(int argc, char** argv) {
                     std::cout << "rebuild: frame " << f << "    wide_area_ratio before: " << ri.area_ratio_before << "    cost: " << ri.last_ms << " ms\n";
                 }
             }
-            renders[0]->render(scene, spp);
+            if (camera_model ? !renders[0]->render_camera(scene, spp) : (renders[0]->render(scene, spp), false)) return 1;
             scene.sync();
             std::cout << "frame: " << f << "    frame cost: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << "s\n";
             scene.save_image(int(f), out + "_turn");
@@ -549,7 +590,7 @@ int main(int argc, char** argv) {
             mcpt_ctx* c = renders[g]->handle();
             // --shard tiles: device g renders ALL n samples of its interleaved share of the 8x8 tiles (BASELINE.json's "pixel-tile shard");
             // default: its contiguous share of the sample range for every pixel.  Either way the films add up to the frame.
-            const mcpt_status rs = shard_tiles ? mcpt_render_tiles(c, n, seed, frame, gpus, g) : (hi > lo ? mcpt_render(c, hi - lo, seed, lo) : MCPT_OK);
+            const mcpt_status rs = shard_tiles ? mcpt_render_tiles(c, n, seed, frame, gpus, g) : (hi > lo ? (camera_model ? mcpt_render_camera : mcpt_render)(c, hi - lo, seed, lo) : MCPT_OK);
             if (rs != MCPT_OK) return fail_with(std::string("mcpt_render: ") + mcpt_last_error());
             if (mcpt_sync(c) != MCPT_OK) return fail_with(std::string("mcpt_sync: ") + mcpt_last_error());
         };
