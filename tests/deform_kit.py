@@ -163,6 +163,52 @@ def assert_arrays(r, v, n):
     assert_records(gv, v, "vertex"); assert_records(gn, n, "normal")
 
 
+def _any_hits(pkg, r):
+    """Any-hit verdicts of both trace kernels for the suite's rays, each cut off at a fixed random distance."""
+    o, d = rays(pkg)
+    t2 = np.random.default_rng(9).uniform(0.05, 1.6, o.shape[0])
+    return r.probe_trace4(o, d, t2=t2, any_hit=True)[1], r.probe_trace(o, d, t2=t2, any_hit=True)[1]
+
+
+def _full_state(pkg, r):
+    s = state(pkg, r)
+    s["any4"], s["any2"] = _any_hits(pkg, r)
+    return s
+
+
+def _assert_same_rays(a, b, new_of_old, hidden=None):
+    """State `a` of a context over the whole face list against state `b` of a context whose faces are numbered new_of_old[face of a] (-1: a face
+    b does not have).  No ray of `a` names a face without a number; the hit masks are equal; t is bit for bit on hits; the faces are equal
+    except where both report the same t bits -- an exact tie between two triangles, which two different trees may break differently --; u, v
+    and the shade records are bit for bit where the faces agree; the any-hit verdicts are equal; the light lists are equal bit for bit, faces
+    mapped; the films have equal sample counts and differ in rgb on at most 1 % of the pixels (the bound tests/test_gpu_bvh_build.py uses for
+    two trees over one geometry)."""
+    fa, fb = a["face"], b["face"]
+    hit = fa >= 0
+    assert np.array_equal(hit, fb >= 0)
+    mapped = np.where(hit, new_of_old[np.maximum(fa, 0)], -1)
+    assert np.all(mapped[hit] >= 0), "a ray names a hidden face"
+    if hidden is not None:
+        assert not hidden[fa[hit]].any()
+    assert np.array_equal(bits(a["t"])[hit], bits(b["t"])[hit])
+    agree = hit & (mapped == fb)
+    tie = hit & ~agree
+    assert np.array_equal(bits(a["t"])[tie], bits(b["t"])[tie])              # (implied by the line above: a differing face is an exact tie)
+    print("faces agree on %.5f of the hits" % (agree.sum() / max(1, hit.sum())))
+    assert agree.sum() >= 0.99 * hit.sum()
+    for k in ("u", "v"):
+        assert np.array_equal(bits(a[k])[agree], bits(b[k])[agree]), k
+    assert np.array_equal(bits(a["shade"])[agree[hit]], bits(b["shade"])[agree[hit]])
+    assert np.array_equal(a["any4"], b["any4"]) and np.array_equal(a["any2"], b["any2"])
+    assert np.array_equal(new_of_old[a["light_face"]], b["light_face"])
+    assert np.array_equal(bits(a["light_rec"]), bits(b["light_rec"])) and np.array_equal(bits(a["light_pos"]), bits(b["light_pos"]))
+    if "film" in a:
+        assert np.array_equal(a["film"][..., 3], b["film"][..., 3])
+        share = float(np.mean(np.any(bits(a["film"][..., :3]) != bits(b["film"][..., :3]), axis=-1)))
+        print("share of pixels whose rgb differs: %.5f" % share)
+        assert share <= 0.01
+
+
 def c_layout(cls, c_name, tmp_path, macros=()):
     """[sizeof, offsetof ...] of the struct `c_name` as a C compiler sees include/mcpt.h, the same of the ctypes class, and the integer values of
     the header's `macros`.  The header's ABI version is 4."""

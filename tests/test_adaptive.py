@@ -222,6 +222,52 @@ def test_probe_matches_the_reference(pkg, size):
     r.close()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(264, 256), (520, 512), (1001, 799)])
+def test_probe_matches_the_reference_at_the_second_level_of_the_scan(pkg, size):
+    """Films large enough for the second level of the compaction (csrc/adaptive.hip): 1 056 tiles are 264 error blocks, two blocks of
+    ad_scatter_kernel; 4 160 tiles are 1 040 error blocks, so every thread of ad_scan_kernel sums a run of per = 2 and most runs are empty;
+    12 600 tiles give per = 4 with a partial last tile column and row.  Nothing is rendered: two caller films through mcpt_probe_tile_error.
+    The thresholds: every tile active, none, about half -- the middle of the widest gap among the central tenth of the reference's sorted
+    errors, so that no tile lies within the probe's 1e-6 of it --, and a pair of films whose only active tiles are tile 0, the last tile and
+    the first tile of the second scan thread's run (tile 4 * per)."""
+    w, h = size
+    ty, tx = ar.tiles_shape(h, w)
+    n_tiles = ty * tx; nb = (n_tiles + 3) // 4; per = (nb + 1023) // 1024
+    assert (n_tiles, nb > 256, per) == {(264, 256): (1056, True, 1), (520, 512): (4160, True, 2), (1001, 799): (12600, True, 4)}[size]
+    r = pkg.Renderer(pkg.scenes.cornell_box_small(w, h), max_depth=2)
+    rng = np.random.default_rng(w * h)
+    max_spp = 16
+    Hf, Of, ties = _synthetic_halves(h, w, max_spp, rng)
+    E_ref, c_ref = ar.tile_error(Hf, Of)
+    flat = np.sort(E_ref.reshape(-1)); mid = flat[int(0.45 * n_tiles):int(0.55 * n_tiles)]
+    k = int(np.argmax(np.diff(mid)))
+    half = float(np.float32(0.5 * (mid[k] + mid[k + 1])))
+    assert mid[k] + 1e-5 < half < mid[k + 1] - 1e-5
+    for name, thr, cap, count in (("all", 0.0, 1000, n_tiles), ("none", 5.0, max_spp, 0), ("half", half, max_spp, None), ("ties", 0.75, max_spp, None)):
+        err, lst = r.probe_tile_error(Hf, Of, thr, cap)
+        print("%dx%d %s: max |err - ref| %.3g, %d of %d tiles active" % (w, h, name, np.abs(err - E_ref).max(), lst.size, n_tiles))
+        assert np.abs(err - E_ref).max() <= 1e-6
+        want = ar.active_list(E_ref, c_ref, thr, cap)
+        assert count is None or want.size == count, name
+        assert np.array_equal(lst, want), name
+    assert 0.4 * n_tiles < ar.active_list(E_ref, c_ref, half, max_spp).size < 0.6 * n_tiles
+    # the same film twice has no error anywhere; three tiles get one: the first, the last, and the first of scan thread 1's run
+    three = [0, 4 * per, n_tiles - 1]
+    Os = Hf.copy()
+    for t in three:
+        y, x = divmod(t, tx)
+        Hs = Hf[8 * y:8 * y + 8, 8 * x:8 * x + 8]; Ot = Os[8 * y:8 * y + 8, 8 * x:8 * x + 8]    # (views: mean 0.25 against mean 1, e = 3 * 0.5)
+        Hs[..., 3:] = 2.0; Hs[..., :3] = 0.5                                  # two samples each: never a capped tile
+        Ot[..., 3:] = 2.0; Ot[..., :3] = 2.0
+    E3, c3 = ar.tile_error(Hf, Os)
+    err, lst = r.probe_tile_error(Hf, Os, 0.75, max_spp)
+    assert np.abs(err - E3).max() <= 1e-6
+    assert ar.active_list(E3, c3, 0.75, max_spp).tolist() == three and E3.reshape(-1)[three].tolist() == [1.5, 1.5, 1.5]
+    assert lst.tolist() == three
+    r.close()
+
+
 def _adaptive_case(pkg):
     scene = pkg.scenes.cornell_box_small(W, H)
     fl = pkg.FLAG_DETERMINISTIC

@@ -9,11 +9,12 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import time
 
 import numpy as np
 import pytest
 
-from tests import kit
+from tests import kit, visibility_ref as V
 from tests.kit import bits, render_film
 
 NEW_SYMBOLS = ["mcpt_update_materials", "mcpt_update_texture", "mcpt_get_material_info", "mcpt_probe_lights", "mcpt_probe_face_classes"]
@@ -130,6 +131,56 @@ def test_membership_grows_past_capacity_then_shrinks(pkg):
     _assert_same_look(original, _look(r))                                    # and back: the original picture, bit for bit
     assert r.material_info().updates == 3
     r.close()
+
+
+@pytest.mark.gpu
+def test_light_list_of_more_than_256_scan_blocks(pkg):
+    """66 060 faces are 259 blocks of the light list's scan, so every thread of mt_offsets_kernel (csrc/materials.hip) sums a run of per = 2
+    block sums and most runs are empty: the level of the scan that S-cornell's nine blocks never reach.  The sphere becomes an emitter on a live
+    context -- against a fresh context of the edited scene, bit for bit --, then a random half of it is hidden -- against a fresh context of the
+    sub-scene (tests/visibility_ref.py), faces mapped.  Three contexts of this size are created, with the host builder; the test prints what two of
+    the creations took."""
+    scene = pkg.scenes.cornell_box(W, H, sphere_lon=256, sphere_lat=130)
+    nf = scene.face.shape[0]
+    sphere = scene.face[:, 0, 3] == GLOSSY
+    assert nf == 66060 and (nf + 255) // 256 == 259 and int(sphere.sum()) > 65536
+    glow = _edit(scene.materials, m4=dict(radiance=(0.8, 0.5, 0.3)))
+    glowing = _with_materials(pkg, scene, glow)
+    flags = DET | pkg.FLAG_DYNAMIC
+    lp, lxi = kit.light_points(0.0, 1.0, 4096, 11)
+    t0 = time.perf_counter()
+    r = _fresh(pkg, scene, flags)
+    t1 = time.perf_counter()
+    f = _fresh(pkg, glowing, flags)
+    print("[66 060 faces] context creation, host builder: %.2f s and %.2f s" % (t1 - t0, time.perf_counter() - t1))
+    assert f.info().wide_tree_hash == r.info().wide_tree_hash
+    r.update_materials(glow)
+    n_lights = int(sphere.sum()) + 2
+    assert r.info().n_lights == f.info().n_lights == r.material_info().n_lights == n_lights
+    got, want = r.probe_lights(), f.probe_lights()
+    assert got[0].size == n_lights and np.all(np.diff(got[0]) > 0)
+    assert _same(got, want)
+    assert np.array_equal(r.probe_face_classes(), f.probe_face_classes())
+    assert _same(r.probe_sample_light(lp, lxi), f.probe_sample_light(lp, lxi))
+    f.close()
+    # a random half of the sphere hidden: the flags of the scan are no longer one run of ones
+    mask = np.ones(nf, np.uint8); mask[sphere] = np.random.default_rng(23).uniform(size=int(sphere.sum())) < 0.5
+    sub, new_of_old = V.sub_scene(pkg, glowing, mask)
+    s = _fresh(pkg, sub, flags)
+    r.set_face_visibility(mask)
+    n_lights = int(mask[sphere].sum()) + 2
+    assert 0.45 * sphere.sum() < n_lights < 0.55 * sphere.sum()
+    assert r.info().n_lights == s.info().n_lights == r.material_info().n_lights == n_lights
+    assert r.visibility_info().n_hidden_emitters == int(sphere.sum()) + 2 - n_lights
+    got, want = r.probe_lights(), s.probe_lights()
+    assert np.all(np.diff(got[0]) > 0) and np.array_equal(new_of_old[got[0]], want[0])
+    assert _same(got[1], want[1]) and _same(got[2], want[2])
+    assert np.array_equal(r.probe_face_classes()[mask != 0], s.probe_face_classes())
+    sr, ss = r.probe_sample_light(lp, lxi), s.probe_sample_light(lp, lxi)
+    assert np.array_equal(new_of_old[sr[:, 8].astype(np.int64)], ss[:, 8].astype(np.int64))
+    keep = [0, 1, 2, 3, 4, 5, 6, 7, 9]
+    assert _same(sr[:, keep], ss[:, keep])
+    r.close(); s.close()
 
 
 @pytest.mark.gpu
