@@ -275,7 +275,7 @@ inline F3 to_local(const Onb& o, F3 t) { return {dot(t, o.u), dot(t, o.v), dot(t
 
 enum { LOBE_DIFFUSE = 0, LOBE_PHONG = 1, LOBE_MIRROR = 2 };
 struct Lobe { int kind; F3 reflect; float coeff; float weight; };
-struct Scatter { F3 wo{0, 0, 0}, f{0, 0, 0}; float pdf = 0.f; bool mirror = false; };   // BSDF.h:29-38
+struct Scatter { F3 wo{0, 0, 0}, f{0, 0, 0}; float pdf = 0.f; bool mirror = false; int lobe = -1; float sin_t = 1.f; };   // BSDF.h:29-38 (+ lobe, sin_t: PathAux only)
 struct Bsdf { Onb onb; F3 m_wo; Lobe lobe[2]; int n = 0; };
 
 inline F3 lobe_fx(const Lobe& l, F3 m_wo, F3 wi) {
@@ -316,6 +316,7 @@ inline Scatter lobe_sample(const Lobe& l, F3 m_wo, Rng& rng, int bounce) {
         float sinTheta = std::sqrt(1.f - cosTheta * cosTheta);
         F3 H{sinTheta * std::cos(phi), sinTheta * std::sin(phi), cosTheta};
         F3 wi = -m_wo + H * 2.f * dot(H, m_wo);
+        s.sin_t = sinTheta;
         if (wi.z < 0.f) return s;
         float pdf = (l.coeff + 1) / (2.f * PI_F) * std::pow(cosTheta, l.coeff);
         s.wo = wi; s.f = lobe_fx(l, m_wo, wi); s.pdf = pdf;
@@ -367,6 +368,7 @@ inline Scatter bsdf_sample(const Bsdf& b, Rng& rng, int bounce) {               
     int index = int(std::lower_bound(prefix, prefix + b.n, r) - prefix);
     index = std::min(index, b.n - 1);
     Scatter s = lobe_sample(b.lobe[index], b.m_wo, rng, bounce);
+    s.lobe = b.lobe[index].kind;
     s.pdf *= b.lobe[index].weight;
     for (int i = 0; i < b.n; i++) {
         if (i == index) continue;
@@ -428,15 +430,58 @@ inline Ray cast_ray(const Scene& s, int x, int y, Rng& rng) {
     return r;
 }
 
+// ---- optional per-path output and perturbation of trace_mis (oracle_trace_paths_log; tests/path_ref.py).  Null in every other caller.
+// The log, per vertex two words:  A = face << 8 | front << 7 | roulette passed << 6 | emitter term of the NEXT hit << 4 | lobe << 2 | NEE verdict,
+// B = next face << 1 | next front (-1: the continuation ray missed, or none was traced).  Codes below.
+// The perturbation restates freedoms the device is documented to have, one member of a family per call (tests/path_ref.py holds the citations):
+//   dp: the ray origin and every hit point move by dp x a unit vector (axis >= 0: the axis member's +-e_k; else hashed from item, bounce, member)
+//       -- the device keeps origins and hit points in fp32 (wavefront.hip: `p32 = to_f3(p64)`, "the fp32 origin `no` is what travels");
+//   dd: the sampled direction turns by dd (a Phong pick: dd x (1 + 0.5 / max(sin theta, 2^-12))) -- the sampled-direction bounds of tests/shade_ref.py;
+//   db: the throughput factor of the vertex is scaled by 1 +- db -- fp32 products of f, cos and 1/pdf taken with v_rcp_f32.
+// All three zero: no operation is added, the result is bit-equal to the plain run.
+enum { EV_NEE_NOPDF = 0, EV_NEE_BLOCKED = 1, EV_NEE_ADDED = 2 };
+enum { EV_LOBE_DIFFUSE = 0, EV_LOBE_PHONG = 1, EV_LOBE_MIRROR = 2, EV_LOBE_PDF0 = 3 };
+enum { EV_EMIT_NONE = 0, EV_EMIT_MIS = 1, EV_EMIT_MIRROR = 2 };
+enum { EV_END_MISS0 = 0, EV_END_MISS = 1, EV_END_PDF0 = 2, EV_END_ROULETTE = 3, EV_END_DEPTH = 4 };
+enum { EV_MAX_VERTICES = 48, EV_WORDS = 2 + 2 * EV_MAX_VERTICES };
+struct PathAux {
+    int32_t* log = nullptr;              // EV_WORDS words: end reason, vertex count (all of them, logged or not), then A, B per vertex
+    double dp = 0, dd = 0, db = 0; int axis = -1; uint32_t item = 0, member = 0;
+    int nv = 0;
+    bool perturbed() const { return dp != 0 || dd != 0 || db != 0; }
+    D3 unit(int bounce, uint32_t what, double* sign) const {
+        uint32_t v[4] = {item, uint32_t(bounce), member, 0x51ed270bu + what};
+        pcg4d(v);
+        if (sign) *sign = (axis >= 0 ? (axis & 1) != 0 : (v[2] & 1u) != 0) ? -1.0 : 1.0;
+        if (axis >= 0) { D3 e{0, 0, 0}; e[axis >> 1] = (axis & 1) ? -1.0 : 1.0; return e; }
+        const double z = 1.0 - 2.0 * (double(v[0] >> 8) / 16777216.0), phi = 2.0 * PI_D * (double(v[1] >> 8) / 16777216.0), r = std::sqrt(std::max(0.0, 1.0 - z * z));
+        return {r * std::cos(phi), r * std::sin(phi), z};
+    }
+    void move(D3& p, int bounce) const { if (dp != 0) p = p + dp * unit(bounce, 0u, nullptr); }
+    void turn(Scatter& sc, int bounce) const {
+        if (dd == 0) return;
+        const double a = sc.lobe == LOBE_PHONG ? dd * (1.0 + 0.5 / std::max(double(sc.sin_t), 1.0 / 4096.0)) : dd;
+        sc.wo = toF(normalize(toD(sc.wo) + a * unit(bounce, 1u, nullptr)));
+    }
+    void scale(F3& beta, int bounce) const { if (db != 0) { double sg; unit(bounce, 2u, &sg); beta = beta * float(1.0 + sg * db); } }
+    void vertex(const Hit& h) { if (log && nv < EV_MAX_VERTICES) { log[2 + 2 * nv] = (h.tri << 8) | (h.front ? 128 : 0); log[3 + 2 * nv] = -1; } }
+    void mark(int bits) { if (log && nv < EV_MAX_VERTICES) log[2 + 2 * nv] |= bits; }
+    void next(const Hit& h) { if (log && nv < EV_MAX_VERTICES) log[3 + 2 * nv] = (h.tri << 1) | (h.front ? 1 : 0); }
+    void end(int reason, int vertices) { if (log) { log[0] = reason; log[1] = vertices; } }
+};
+
 // Render::ray_tracing(Ray&) (Render.cpp:111-175).  The reference re-traces `ray` at the top of every iteration
 // (:118); for bounces >= 1 that repeats the trace that produced nextInfo (:144) with an identical result, so it
 // is skipped here (and not counted as a ray).
-F3 trace_mis(const Scene& s, Ray ray, Rng& rng, Counters& c) {
+F3 trace_mis(const Scene& s, Ray ray, Rng& rng, Counters& c, PathAux* aux = nullptr) {
     F3 L{0, 0, 0}, beta{1, 1, 1};
     Hit info;
     const float nl = float(s.lights.size());
-    for (int bounces = 0; s.max_depth == 0 || bounces < int(s.max_depth); bounces++) {
-        if (bounces == 0) { c.rays_primary++; if (!bvh_hit(s, 0, ray, info, c)) break; }
+    int end = EV_END_DEPTH, bounces = 0;
+    if (aux) aux->move(ray.start, 0);
+    for (; s.max_depth == 0 || bounces < int(s.max_depth); bounces++) {
+        if (bounces == 0) { c.rays_primary++; if (!bvh_hit(s, 0, ray, info, c)) { end = EV_END_MISS0; break; } if (aux) aux->move(info.point, 1); }
+        if (aux) { aux->nv = bounces; aux->vertex(info); }
         const Mat& mat = s.mats[info.mat];
         if (bounces == 0 && length(mat.radiance) > 0.0001) L += toF(mat.radiance);          // :121-122
         Bsdf bsdf = make_bsdf(s, info);
@@ -445,15 +490,19 @@ F3 trace_mis(const Scene& s, Ray ray, Rng& rng, Counters& c) {
             float cos_theta = std::fabs(dot(toF(info.normal), ls.wo));
             float weight = power_heuristic(ls.pdf / nl, bsdf_pdf(bsdf, ls.wo));
             L += weight * beta * ls.f * bsdf_fx(bsdf, ls.wo) * cos_theta / ls.pdf * nl;
-        }
+            if (aux) aux->mark(EV_NEE_ADDED);
+        } else if (aux && ls.pdf != 0) aux->mark(EV_NEE_BLOCKED);
         Scatter sc = bsdf_sample(bsdf, rng, bounces);                                       // :133-136
-        if (sc.pdf == 0.f) break;
+        if (sc.pdf == 0.f) { if (aux) aux->mark(EV_LOBE_PDF0 << 2); end = EV_END_PDF0; bounces++; break; }
+        if (aux) { aux->mark(sc.lobe << 2); aux->turn(sc, bounces); }
         Ray new_ray; new_ray.start = info.point; new_ray.direction = toD(sc.wo);
         float cos_theta = std::fabs(dot(toF(info.normal), sc.wo));
         beta *= sc.f * cos_theta / sc.pdf;                                                   // :140
+        if (aux) aux->scale(beta, bounces);
         Hit next; Ray tmp = new_ray;
         c.rays_cont++;
-        if (!bvh_hit(s, 0, tmp, next, c)) break;                                            // :144
+        if (!bvh_hit(s, 0, tmp, next, c)) { end = EV_END_MISS; bounces++; break; }          // :144
+        if (aux) { aux->move(next.point, bounces + 2); aux->next(next); }
         if (length(s.mats[next.mat].radiance) && next.front) {                               // :146-162
             if (sc.mirror) L += beta * toF(s.mats[next.mat].radiance);
             else {
@@ -465,14 +514,17 @@ F3 trace_mis(const Scene& s, Ray ray, Rng& rng, Counters& c) {
                 float weight = power_heuristic(sc.pdf, lightPdf);
                 L += beta * toF(s.mats[next.mat].radiance) * weight;
             }
+            if (aux) aux->mark((sc.mirror ? EV_EMIT_MIRROR : EV_EMIT_MIS) << 4);
         }
         if (bounces > 3) {                                                                   // :164-170
             float q = std::min(std::max(std::max(beta.x, beta.y), beta.z), 0.95f);
-            if (rng.get(blockB(bounces), L_RR) > q) break;
+            if (rng.get(blockB(bounces), L_RR) > q) { end = EV_END_ROULETTE; bounces++; break; }
             beta = beta / q;
+            if (aux) aux->mark(64);
         }
         ray = new_ray; info = next;
     }
+    if (aux) aux->end(end, bounces);
     return L;
 }
 
@@ -744,6 +796,22 @@ void oracle_trace_path_counter(void* h, const double* o, const double* d, uint32
     Ray ray; ray.start = P3(o); ray.direction = P3(d);
     put3f(L3, trace(*s, ray, r, c));
 }
+// n COUNTER-mode paths at once (item i = first_item + i, the key oracle_trace_path_counter uses), each with its event log (EV_WORDS words per
+// path, PathAux above; null: none) and, for dp, dd or db != 0, as one member of the perturbation family.  axis: 0..5 = +x -x +y -y +z -z for every
+// shift, turn and sign of the member; -1 = hashed from (item, bounce, member).
+void oracle_trace_paths_log(void* h, int n, const double* o, const double* d, uint32_t first_item, uint64_t seed, double dp, double dd, double db, int axis,
+                            uint32_t member, float* L3, int32_t* log) {
+    Scene* s = static_cast<Scene*>(h);
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int i = 0; i < n; i++) {
+        Rng r; r.pixel = first_item + uint32_t(i); r.sample = 0; r.seed = seed; Counters c;
+        Ray ray; ray.start = P3(o + 3 * i); ray.direction = P3(d + 3 * i);
+        PathAux aux; aux.dp = dp; aux.dd = dd; aux.db = db; aux.axis = axis; aux.item = r.pixel; aux.member = member;
+        if (log) { aux.log = log + size_t(EV_WORDS) * i; for (int k = 0; k < EV_WORDS; k++) aux.log[k] = -1; }
+        put3f(L3 + 3 * i, trace_mis(*s, ray, r, c, &aux));
+    }
+}
+int oracle_log_words() { return EV_WORDS; }
 int oracle_shadow_probe(void* h, const double* o, const double* d, const float* xi, int n, double shrink, int* out2) {
     Scene* s = static_cast<Scene*>(h); Counters c; Rng r = seq_rng(xi, n);
     Ray ray; ray.start = P3(o); ray.direction = P3(d);

@@ -92,6 +92,7 @@ class Oracle:
             L.oracle_trace_pixel.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp]
             L.oracle_trace_path_counter.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, vp]
             L.oracle_shadow_probe.argtypes = [vp, vp, vp, vp, C.c_int, C.c_double, vp]
+            L.oracle_trace_paths_log.argtypes = [vp, C.c_int, vp, vp, C.c_uint32, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint32, vp, vp]
             cls._lib = L
         return cls._lib
 
@@ -209,6 +210,17 @@ class Oracle:
     def trace_path_counter(self, o, d, item, seed=0):
         L3 = np.zeros(3, np.float32)
         self.L.oracle_trace_path_counter(self.h, _p(_d3(o)), _p(_d3(d)), item, seed, _p(L3)); return L3
+
+    def trace_paths_log(self, o, d, seed=0, first_item=0, dp=0.0, dd=0.0, db=0.0, axis=-1, member=0, log=True):
+        """n COUNTER-mode paths (item i = first_item + i): (L (n, 3) fp32, event log (n, oracle_log_words()) int32 or None).  dp, dd, db: one
+        member of the perturbation family of mcpt_oracle.cpp's PathAux (axis 0..5: +-x, +-y, +-z; -1: hashed from item, bounce, member); all zero
+        is the plain run, bit for bit.  The log is decoded by tests/path_ref.py."""
+        o = np.ascontiguousarray(o, np.float64).reshape(-1, 3); d = np.ascontiguousarray(d, np.float64).reshape(-1, 3)
+        n = o.shape[0]; assert d.shape[0] == n
+        L3 = np.zeros((n, 3), np.float32)
+        ev = np.zeros((n, self.L.oracle_log_words()), np.int32) if log else None
+        self.L.oracle_trace_paths_log(self.h, n, _p(o), _p(d), first_item, seed, dp, dd, db, axis, member, _p(L3), _p(ev))
+        return L3, ev
 
     def shadow_probe(self, o, d, xi, shrink=1e-4):
         xi = _f(xi); out = np.zeros(2, np.int32)
