@@ -1024,6 +1024,84 @@ mcpt_status mcpt_autofocus(mcpt_ctx* ctx, int32_t px, int32_t py, double* out_fo
 mcpt_status mcpt_probe_camera_rays(mcpt_ctx* ctx, uint32_t n, const int32_t* xy, uint32_t sample, uint64_t seed,
                                    double* out_origin3 /* device coordinates */, double* out_dir3);
 
+/* ---- surface baking ---------------------------------------------------------------------------------------------------------- */
+/* Lighting seen from the surface instead of from a camera: lightmaps, per-vertex baked lighting, irradiance probes.  A second ray-generation
+ * stage (HIP kernels, csrc/bake.hip) starts one cosine-weighted ray per BAKE POINT on the scene's surfaces and hands the rays to the unchanged
+ * wavefront pipeline through the hook mcpt_probe_paths and mcpt_render_camera use; the finished samples land in a film of the context's own
+ * with one {sum L, count} record per point, never in the bound film.
+ *
+ * A bake point is {face, u, v, flags}: a face in Model::face order, barycentrics (the point is v0 + u (v1 - v0) + v (v2 - v0)) and
+ * MCPT_BAKE_BACK_SIDE for the side the interpolated vertex normal points away from.  The stage reads the context's CURRENT corners and vertex
+ * normals, so a bake after mcpt_update_* sees the scene as it is now.  A point whose interpolated normal AND geometric normal both have length 0
+ * (or not finite) is DEAD: it is traced from its position along +z so that the pipeline sees a proper ray, and resolves to {0, 0, 0, 0}.
+ * Item i of a pass is point i; its direction comes from random-number block 0 of (pixel = i, sample, seed) -- the camera's block -- and its path
+ * draws blocks 1, 2, ... as every path does.
+ *
+ * LIMIT: the first vertex has no next-event estimation.  Direct light reaches a point only through cosine-sampled rays that hit an emitter,
+ * which is noisy under small lamps; from the first hit on, paths sample the lights as always (that needs the shade kernel).
+ *
+ * EMITTERS ARE ONE-SIDED FOR A BAKE POINT.  A point's ray enters the pipeline as a path's PRIMARY ray, whose hit on an emitter adds its radiance
+ * whatever side it is hit from (a camera sees a lamp's back lit); later bounces see emitters from their front only, and a surface point's ray is
+ * morally one of those.  So before each pass a first-hit kernel (the binary tree; about 0.4 ms per pass for 640 000 points) finds the rays that
+ * first meet an emitter from behind and takes that radiance out of their records: such a sample contributes what its path gathers after that hit.
+ * MCPT_ERR_BVH_DEPTH from mcpt_bake where mcpt_probe_first_hits answers it (a device-built binary tree deeper than the kernel's stack).
+ *
+ * mcpt_set_bake_points: synchronous set-up.  Validated on the host before any device work, a refusal changes nothing: MCPT_ERR_INVALID_ARG for a
+ * NULL list with n > 0, a face outside [0, n_face), u or v not finite, u < 0, v < 0 or double(u) + double(v) > 1, an unknown flag bit, or
+ * n > 67 108 863.  n = 0 drops the points and frees everything.  The context holds 16 B (the point) + 1 B (dead) + 16 B (bake film) per point
+ * from this call on and 48 B per point more (the two ray arrays) from the first mcpt_bake on, all counted in mcpt_scene_info::device_bytes.
+ * Setting points zeroes the bake film.  mcpt_rebuild_trees keeps points and bake film; mcpt_clone_to_device's clone starts without points.
+ * Points on faces hidden by mcpt_set_face_visibility stay alive (hiding removes a face from what rays can hit, not its corners or normals):
+ * they bake what the surface would receive with the hidden faces gone.
+ *
+ * mcpt_bake: adds `spp` samples (first_sample .. first_sample + spp - 1 of `seed`) to every point's bake-film record; on the context's stream,
+ * asynchronous, one pass per sample like mcpt_render_camera, ONE launch in mcpt_counters, its paths and rays counted like mcpt_render's.  The
+ * context's flags (MCPT_FLAG_CORRECT_SHADOW_T2, MCPT_FLAG_DETERMINISTIC ...) apply as they do there; a bake of one-sample items is reproducible
+ * bit for bit with or without MCPT_FLAG_DETERMINISTIC.  Consecutive calls are ordered: a pass's ray kernel runs after the pass before it has
+ * read its rays.  MCPT_ERR_UNSUPPORTED without the wavefront pipeline; MCPT_ERR_INVALID_ARG without points or when first_sample + spp > 2^32;
+ * spp == 0 does nothing.  Touches neither the bound film nor the features, the denoised film, the tile error or the camera model.
+ *
+ * mcpt_clear_bake: zeroes the bake film (asynchronous).  mcpt_read_bake: 4 floats per point, synchronous -- with m = sum L / float(count) in fp32,
+ * MCPT_BAKE_IRRADIANCE gives {float(pi) m, count} (for cosine-weighted directions E = pi mean L) and MCPT_BAKE_DIFFUSE {kd * m, count}, the
+ * radiance a diffuse texel of that surface sends out, kd the point's Map_Kd colour at its interpolated uv; a dead point or a count of 0 gives
+ * {0, 0, 0, 0}.  mcpt_read_bake_film: the raw {sum L, count}.
+ *
+ * mcpt_probe_bake_rays: the stage's device function for points first .. first + n - 1 of the set list and sample `sample`: per point the origin
+ * in DEVICE coordinates, the direction (fp32 values), the unit normal the direction was sampled about (3 doubles each; any may be NULL) and the
+ * dead byte.  Synchronous; touches nothing.
+ *
+ * mcpt_lightmap_points: HOST ONLY, no device: the texel-to-surface map of a width x height lightmap over the description's texcoords.  Texel
+ * (i, j) has the centre ((i + 0.5) / width, (j + 0.5) / height); the faces are tested in Model::face order with fp64 edge functions and a texel
+ * belongs to the LOWEST face whose three barycentrics are all >= 0.  A face whose uv area is 0 or not finite is skipped; uv is not wrapped.
+ * Output in texel order: the point (barycentrics rounded to fp32, then clamped so that mcpt_set_bake_points accepts them, flags 0) and the texel
+ * j * width + i.  *out_n is always set; capacity < *out_n is MCPT_ERR_INVALID_ARG with nothing written, as for mcpt_probe_lights. */
+#define MCPT_BAKE_BACK_SIDE   1u          /* mcpt_bake_point::flags */
+#define MCPT_BAKE_IRRADIANCE  0u          /* mcpt_read_bake's mode */
+#define MCPT_BAKE_DIFFUSE     1u
+typedef struct mcpt_bake_point {
+    uint32_t face;                        /* Model::face order */
+    float    u, v;                        /* barycentrics of corners 1 and 2 */
+    uint32_t flags;                       /* MCPT_BAKE_BACK_SIDE */
+} mcpt_bake_point;
+typedef struct mcpt_bake_info {
+    uint32_t struct_size, n_points;
+    uint32_t n_dead, bakes;               /* dead points as of the last mcpt_bake; mcpt_bake calls that enqueued work on this context */
+    uint64_t passes;                      /* ... and their samples: one ray kernel each */
+    double   last_stage_ms;               /* HIP events: the ray kernels of the last call, summed */
+    uint64_t device_bytes;                /* points + dead bytes + bake film + ray arrays, as held now */
+    uint32_t reserved[4];
+} mcpt_bake_info;
+mcpt_status mcpt_set_bake_points(mcpt_ctx* ctx, const mcpt_bake_point* points, uint32_t n);
+mcpt_status mcpt_bake(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample);
+mcpt_status mcpt_clear_bake(mcpt_ctx* ctx);
+mcpt_status mcpt_read_bake(mcpt_ctx* ctx, uint32_t mode /* MCPT_BAKE_IRRADIANCE / _DIFFUSE */, float* out4 /* 4 per point */);
+mcpt_status mcpt_read_bake_film(mcpt_ctx* ctx, float* out4 /* 4 per point */);
+mcpt_status mcpt_get_bake_info(mcpt_ctx* ctx, mcpt_bake_info* out);                 /* synchronises */
+mcpt_status mcpt_probe_bake_rays(mcpt_ctx* ctx, uint32_t sample, uint64_t seed, uint32_t first, uint32_t n, double* out_origin3 /* device coordinates */,
+                                 double* out_dir3, double* out_normal3, uint8_t* out_dead);
+mcpt_status mcpt_lightmap_points(const mcpt_scene_desc* scene, uint32_t width, uint32_t height, uint32_t capacity, mcpt_bake_point* out_points,
+                                 uint32_t* out_texel, uint32_t* out_n);
+
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that
  * torch.distributed / RCCL all-reduces in place).  NULL re-binds the internal buffer. */

@@ -35,6 +35,9 @@ from .visibility_abi import VisibilityInfo, visibility_from_materials  # noqa: F
 # mcpt_set_camera_model's struct, mcpt_get_camera_model's info and the model constants; tests/test_camera_ref.py holds the layouts to the header
 from .camera_abi import (CAMERA_EQUIRECT, CAMERA_MAX_BLADES, CAMERA_ORTHOGRAPHIC, CAMERA_PINHOLE, CAMERA_THIN_LENS, CameraModel, CameraModelInfo,  # noqa: F401
                          camera_model)
+# mcpt_bake_point, mcpt_get_bake_info's struct, the constants, the makers of bake-point lists and Renderer's baking methods; tests/test_bake_ref.py holds the layouts to the header
+from .bake_abi import (BAKE_BACK_SIDE, BAKE_DIFFUSE, BAKE_IRRADIANCE, BAKE_MAX_POINTS, BakeInfo, BakeMethods, BakePoint, bake_points, lightmap_points,  # noqa: F401
+                       vertex_bake_points)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmcpt_hip.so")
@@ -333,6 +336,14 @@ def load_library() -> C.CDLL:
         "mcpt_render_camera": [vp, C.c_uint32, C.c_uint64, C.c_uint32],
         "mcpt_autofocus": [vp, C.c_int32, C.c_int32, P(C.c_double)],
         "mcpt_probe_camera_rays": [vp, C.c_uint32, vp, C.c_uint32, C.c_uint64, vp, vp],
+        "mcpt_set_bake_points": [vp, vp, C.c_uint32],
+        "mcpt_bake": [vp, C.c_uint32, C.c_uint64, C.c_uint32],
+        "mcpt_clear_bake": [vp],
+        "mcpt_read_bake": [vp, C.c_uint32, vp],
+        "mcpt_read_bake_film": [vp, vp],
+        "mcpt_get_bake_info": [vp, P(BakeInfo)],
+        "mcpt_probe_bake_rays": [vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp],
+        "mcpt_lightmap_points": [P(SceneDesc), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, P(C.c_uint32)],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -368,6 +379,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_rebuild_trees", "mcpt_get_rebuild_info",
     "mcpt_set_face_visibility", "mcpt_set_face_visibility_reproject", "mcpt_get_visibility_info", "mcpt_probe_triangles",
     "mcpt_set_camera_model", "mcpt_get_camera_model", "mcpt_render_camera", "mcpt_autofocus", "mcpt_probe_camera_rays",
+    "mcpt_set_bake_points", "mcpt_bake", "mcpt_clear_bake", "mcpt_read_bake", "mcpt_read_bake_film", "mcpt_get_bake_info", "mcpt_probe_bake_rays", "mcpt_lightmap_points",
 ]
 
 
@@ -449,8 +461,8 @@ def check_scene(scene: "scenes.SceneData"):
     return st, info, (lib.mcpt_last_error() or b"").decode() if st != MCPT_OK else ""
 
 
-class Renderer:
-    """One mcpt_ctx = one scene on one GPU (the reference's ``Render`` object)."""
+class Renderer(BakeMethods):
+    """One mcpt_ctx = one scene on one GPU (the reference's ``Render`` object).  Surface baking: bake_abi.BakeMethods."""
 
     def __init__(self, scene: "scenes.SceneData", max_depth=0, integrator=INTEGRATOR_MIS, flags=0, device=0,
                  samples_per_item=0):

@@ -22,6 +22,8 @@
 #include "visibility.h"
 #include "visibility_plan.h"
 #include "camera.h"
+#include "bake.h"
+#include "bake_plan.h"
 
 #include <chrono>
 #include <cmath>
@@ -411,6 +413,29 @@ struct mcpt_ctx {
             return e;
         }
     } cm;
+    // Surface baking (bake.hip), allocated by mcpt_set_bake_points and counted in device_bytes: the points with their leaf-order
+    // triangle, a dead byte and a bake-film record {sum L, count} per point; by the first mcpt_bake the two ray arrays wf_shade_kernel reads as
+    // probe_o / probe_d, 3 doubles per point each.  On the host the points in FACE terms: mcpt_rebuild_trees permutes the leaf order and derives
+    // the device list anew from them.  `watch` brackets one pass's ray kernel; stage_ms adds them up over a call.  A clone starts without points.
+    struct Bake {
+        std::vector<mcpt_bake_point> host; DevBuf<BkPoint> pts; DevBuf<uint8_t> dead; DevBuf<float4> film; DevBuf<double> ray_o, ray_d;
+        Stopwatch watch; uint32_t bakes = 0; uint64_t passes = 0; double stage_ms = 0.0;
+        uint32_t n() const { return uint32_t(host.size()); }
+        uint64_t device_bytes() const { return pts.bytes + dead.bytes + film.bytes + ray_o.bytes + ray_d.bytes; }
+        void drop() { host.clear(); pts.release(); dead.release(); film.release(); ray_o.release(); ray_d.release(); }
+        hipError_t take() {                                                  // the bracketed pass, once it has run, joins the call's sum
+            const bool timed = watch.timed;
+            const hipError_t e = watch.settle();
+            if (e == hipSuccess && timed) stage_ms += watch.last_ms;
+            return e;
+        }
+        // the device list for a leaf order: point i names leaf_of_face[its face]
+        std::vector<BkPoint> in_leaf_terms(const std::vector<int32_t>& leaf_of_face) const {
+            std::vector<BkPoint> v(host.size());
+            for (size_t i = 0; i < host.size(); i++) v[i] = BkPoint{leaf_of_face[size_t(host[i].face)], host[i].u, host[i].v, host[i].flags};
+            return v;
+        }
+    } bk;
     // Temporal reprojection (reproject.hip), allocated by the first reprojection call: the old view's features (2 per pixel, swapped
     // with dn_feat per call), a copy of the old film and the reuse counter.
     // Motion-vector reprojection adds, on the first mcpt_update_vertices_reproject: the first hit of every pixel-centre ray and
@@ -2242,6 +2267,15 @@ mcpt_status mcpt_rebuild_trees(mcpt_ctx* ctx, const mcpt_rebuild_opts* opts) {
     HIP_TRY(hipMemcpyAsync(nodes.p, hs.nodes.data(), nodes.bytes, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(nodes8.p, hs.nodes8.data(), nodes8.bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(rf_bin_order.p, bin_order.data(), rf_bin_order.bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_src.p, plan.src_of_dst.data(), d_src.bytes, hipMemcpyHostToDevice, s)); HIP_TRY(hipMemcpyAsync(d_dst.p, plan.dst_of_src.data(), d_dst.bytes, hipMemcpyHostToDevice, s));
+    // §27: bake points name leaves; the list for the new order, from the face-order copy (the bake film is per point and stays)
+    DevBuf<BkPoint> bk_pts; std::vector<BkPoint> bk_host;
+    if (ctx->bk.n()) {
+        std::vector<int32_t> leaf_of_face(nt, -1);
+        for (size_t i = 0; i < order.size(); i++) leaf_of_face[size_t(order[i])] = int32_t(i);
+        bk_host = ctx->bk.in_leaf_terms(leaf_of_face);
+        HIP_TRY(bk_pts.alloc(bk_host.size(), tally));
+        HIP_TRY(hipMemcpyAsync(bk_pts.p, bk_host.data(), bk_pts.bytes, hipMemcpyHostToDevice, s));
+    }
     HIP_TRY(hipMemsetAsync(tri_isect.p + 3 * size_t(nt), 0, 3 * sizeof(float4), s));                     // the spare record
     if (lights.bytes) HIP_TRY(hipMemcpyAsync(lights.p, ctx->lights.p, lights.bytes, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipEventRecord(ev[2], s));
@@ -2264,6 +2298,7 @@ mcpt_status mcpt_rebuild_trees(mcpt_ctx* ctx, const mcpt_rebuild_opts* opts) {
     for (size_t l = 0; l < ovf.size(); l++) if (ovf[l].p) ctx->lanes[l].ovf_buf = std::move(ovf[l]);
     ctx->rf_bin_level.swap(bin_level); ctx->rf_wide_level.swap(wide_level); ctx->rf_area0 = area0;
     ctx->h_tri_face.assign(order.begin(), order.end());
+    if (bk_pts.p) ctx->bk.pts = std::move(bk_pts);
     ctx->wide_depth = hs.bvh8_depth; ctx->binary_ok = hs.binary_ok;
     ctx->vs.box_valid = false;                                                    // §24: rf_tri_box is scratch in the OLD leaf order; the mask is per face and stays
     DevScene& d = ctx->dev;
@@ -2855,6 +2890,141 @@ mcpt_status mcpt_probe_camera_rays(mcpt_ctx* ctx, uint32_t n, const int32_t* xy,
     HIP_TRY(s.in(xy, 2 * size_t(n), &d_xy)); HIP_TRY(s.out(3 * size_t(n), &d_o)); HIP_TRY(s.out(3 * size_t(n), &d_d));
     HIP_TRY(launch_cm_probe(ctx->dev.cam, ctx->cm.dev, n, d_xy, sample, uint32_t(seed), uint32_t(seed >> 32), d_o, d_d, ctx->stream));
     HIP_TRY(s.fetch(out_origin3, d_o, 3 * size_t(n))); HIP_TRY(s.fetch(out_dir3, d_d, 3 * size_t(n))); HIP_TRY(s.finish());
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ surface baking
+mcpt_status mcpt_set_bake_points(mcpt_ctx* ctx, const mcpt_bake_point* points, uint32_t n) {
+    const std::string who = "mcpt_set_bake_points: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    const std::string bad = bk_check_points(points, n, uint32_t(ctx->dev.n_tris));
+    if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, who + bad);
+    mcpt_ctx::Bake& bk = ctx->bk;
+    // nothing below refuses; what fails is a HIP call
+    st = use_drained(ctx); if (st != MCPT_OK) return st;                     // bakes enqueued earlier read the buffers that are about to be replaced
+    HIP_TRY(bk.take());
+    if (n == 0) { bk.drop(); return MCPT_OK; }
+    st = fetch_tri_face(ctx); if (st != MCPT_OK) return st;
+    std::vector<int32_t> leaf_of_face(ctx->h_tri_face.size(), -1);
+    for (size_t i = 0; i < ctx->h_tri_face.size(); i++) leaf_of_face[size_t(ctx->h_tri_face[i])] = int32_t(i);
+    uint64_t* tally = &ctx->info.device_bytes;
+    HIP_TRY(alloc_all(Want(bk.pts, n, tally), Want(bk.dead, n, tally), Want(bk.film, n, tally), Want(bk.watch, 1, nullptr, !bk.watch.ev0)));
+    if (bk.ray_o.p && bk.ray_o.count() != 3 * size_t(n)) { bk.ray_o.release(); bk.ray_d.release(); }   // (the first bake of the new list allocates its own)
+    bk.host.assign(points, points + n);
+    const std::vector<BkPoint> dev = bk.in_leaf_terms(leaf_of_face);
+    HIP_TRY(hipMemcpyAsync(bk.pts.p, dev.data(), bk.pts.bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(bk.dead.p, 0, bk.dead.bytes, ctx->stream));
+    HIP_TRY(hipMemsetAsync(bk.film.p, 0, bk.film.bytes, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                              // (`dev` has been read)
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_bake(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample) {
+    const std::string who = "mcpt_bake: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->use_wavefront || ctx->lanes.empty()) return fail(MCPT_ERR_UNSUPPORTED, who + "needs the wavefront pipeline (MCPT_INTEGRATOR_MIS, no MCPT_PIPELINE=mega)");
+    mcpt_ctx::Bake& bk = ctx->bk;
+    const uint32_t n = bk.n();
+    if (n == 0) return fail(MCPT_ERR_INVALID_ARG, who + "no bake points are set");
+    if (uint64_t(first_sample) + spp > (1ull << 32)) return fail(MCPT_ERR_INVALID_ARG, who + "first_sample + spp exceeds 2^32");
+    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the first-hit kernel's traversal stack");
+    if (spp == 0) return MCPT_OK;
+    if (!bk.ray_o.p) HIP_TRY(alloc_all(Want(bk.ray_o, 3 * size_t(n), &ctx->info.device_bytes), Want(bk.ray_d, 3 * size_t(n), &ctx->info.device_bytes)));
+    HIP_TRY(bk.take());                                                      // (the last call's last pass)
+    bk.stage_ms = 0.0;
+    st = timed_begin(ctx); if (st != MCPT_OK) return st;
+    for (uint32_t k = 0; k < spp; k++) {
+        const uint32_t s = first_sample + k;
+        HIP_TRY(bk.take());
+        HIP_TRY(bk.watch.begin(ctx->stream));
+        HIP_TRY(launch_bk_rays(ctx->dev, bk.pts.p, n, s, uint32_t(seed), uint32_t(seed >> 32), bk.ray_o.p, bk.ray_d.p, bk.dead.p, ctx->stream));
+        HIP_TRY(bk.watch.end(ctx->stream));
+        // a primary hit emits from either side, a surface point must not see a lamp's back: where the ray first meets an emitter from behind, the
+        // radiance the pass will add is taken out of the record beforehand (bk_unlit_kernel; still on the context's stream, ahead of the fork)
+        HIP_TRY(launch_bk_unlit(ctx->dev, bk.ray_o.p, bk.ray_d.p, bk.dead.p, n, bk.film.p, ctx->stream));
+        // as in mcpt_render_camera: the sub-pipelines' streams fork from the context's after the ray kernel and join it again, so the next pass's
+        // kernel -- of this call or of the next one -- overwrites the rays only after this pass's paths have read them
+        RenderParams p = probe_job_params(ctx, s, seed, ctx->opts.flags);
+        p.probe_n = n; p.probe_o = bk.ray_o.p; p.probe_d = bk.ray_d.p;
+        st = render_wavefront(ctx, p, bk.film.p); if (st != MCPT_OK) return st;
+        bk.passes++;
+    }
+    bk.bakes++;
+    return timed_end(ctx);
+}
+
+mcpt_status mcpt_clear_bake(mcpt_ctx* ctx) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (ctx->bk.film.bytes) HIP_TRY(hipMemsetAsync(ctx->bk.film.p, 0, ctx->bk.film.bytes, ctx->stream));
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_read_bake(mcpt_ctx* ctx, uint32_t mode, float* out4) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (mode > MCPT_BAKE_DIFFUSE) return fail(MCPT_ERR_INVALID_ARG, "mcpt_read_bake: unknown mode");
+    const mcpt_ctx::Bake& bk = ctx->bk;
+    if (bk.n() == 0) return MCPT_OK;
+    if (!out4) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    {   Scratch s(ctx->stream); float4* d_out;
+        HIP_TRY(s.out(size_t(bk.n()), &d_out));
+        HIP_TRY(launch_bk_resolve(ctx->dev, bk.pts.p, bk.dead.p, bk.film.p, bk.n(), mode, d_out, ctx->stream));
+        HIP_TRY(s.fetch(reinterpret_cast<float4*>(out4), d_out, size_t(bk.n()))); HIP_TRY(s.finish()); }
+    return resolve_timing(ctx);
+}
+
+mcpt_status mcpt_read_bake_film(mcpt_ctx* ctx, float* out4) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (ctx->bk.n() == 0) return MCPT_OK;
+    if (!out4) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    return read_back(ctx, out4, ctx->bk.film.p, ctx->bk.film.bytes);
+}
+
+mcpt_status mcpt_get_bake_info(mcpt_ctx* ctx, mcpt_bake_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    mcpt_ctx::Bake& bk = ctx->bk;
+    Stopwatch none;                                                          // (a context that never had points has no watch of its own)
+    HIP_TRY(bk.take());
+    st = info_begin(ctx, out, bk.watch.ev0 ? &bk.watch : &none); if (st != MCPT_OK) return st;
+    std::vector<uint8_t> dead(bk.n());
+    st = read_back(ctx, dead.data(), bk.dead.p, dead.size(), false); if (st != MCPT_OK) return st;
+    uint32_t n_dead = 0;
+    for (uint8_t d : dead) n_dead += d ? 1u : 0u;
+    out->n_points = bk.n(); out->n_dead = n_dead; out->bakes = bk.bakes; out->passes = bk.passes; out->last_stage_ms = bk.stage_ms; out->device_bytes = bk.device_bytes();
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_bake_rays(mcpt_ctx* ctx, uint32_t sample, uint64_t seed, uint32_t first, uint32_t n, double* out_origin3, double* out_dir3, double* out_normal3,
+                                 uint8_t* out_dead) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    const mcpt_ctx::Bake& bk = ctx->bk;
+    if (uint64_t(first) + n > bk.n()) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_bake_rays: first + n exceeds the number of bake points set");
+    if (n == 0) return MCPT_OK;
+    Scratch s(ctx->stream); double *d_o, *d_d, *d_n; uint8_t* d_dead;
+    HIP_TRY(s.out(3 * size_t(n), &d_o)); HIP_TRY(s.out(3 * size_t(n), &d_d)); HIP_TRY(s.out(3 * size_t(n), &d_n)); HIP_TRY(s.out(size_t(n), &d_dead));
+    HIP_TRY(launch_bk_probe(ctx->dev, bk.pts.p, first, n, sample, uint32_t(seed), uint32_t(seed >> 32), d_o, d_d, d_n, d_dead, ctx->stream));
+    if (out_origin3) HIP_TRY(s.fetch(out_origin3, d_o, 3 * size_t(n)));
+    if (out_dir3) HIP_TRY(s.fetch(out_dir3, d_d, 3 * size_t(n)));
+    if (out_normal3) HIP_TRY(s.fetch(out_normal3, d_n, 3 * size_t(n)));
+    if (out_dead) HIP_TRY(s.fetch(out_dead, d_dead, size_t(n)));
+    HIP_TRY(s.finish());
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_lightmap_points(const mcpt_scene_desc* scene, uint32_t width, uint32_t height, uint32_t capacity, mcpt_bake_point* out_points, uint32_t* out_texel,
+                                 uint32_t* out_n) {
+    const std::string who = "mcpt_lightmap_points: ";
+    if (!scene || !out_n) return fail(MCPT_ERR_INVALID_ARG, who + "null argument");
+    *out_n = 0;
+    std::vector<mcpt_bake_point> points; std::vector<uint32_t> texel;
+    const std::string bad = bk_lightmap_points(scene, width, height, points, texel);
+    if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, who + bad);
+    *out_n = uint32_t(points.size());
+    if (capacity < points.size()) return fail(MCPT_ERR_INVALID_ARG, who + "capacity < the number of covered texels");
+    if (points.empty()) return MCPT_OK;
+    if (!out_points || !out_texel) return fail(MCPT_ERR_INVALID_ARG, who + "null argument");
+    std::memcpy(out_points, points.data(), points.size() * sizeof(mcpt_bake_point));
+    std::memcpy(out_texel, texel.data(), texel.size() * sizeof(uint32_t));
     return MCPT_OK;
 }
 

@@ -62,6 +62,24 @@ bool Render::autofocus(Scene&, int px, int py, double& focus_distance) {
     if (mcpt_autofocus(ctx, px, py, &focus_distance) != MCPT_OK) { std::cerr << "Error: mcpt_autofocus: " << mcpt_last_error() << std::endl; return false; }
     return true;
 }
+bool Render::set_bake_points(Scene&, const std::vector<mcpt_bake_point>& points) {
+    if (!ctx) return false;
+    if (mcpt_set_bake_points(ctx, points.data(), uint32_t(points.size())) != MCPT_OK) { std::cerr << "Error: mcpt_set_bake_points: " << mcpt_last_error() << std::endl; return false; }
+    bake_points = uint32_t(points.size()); next_bake_sample = 0;
+    return true;
+}
+bool Render::bake(Scene&, uint32_t spp) {
+    if (!ctx) return false;
+    if (mcpt_bake(ctx, spp, seed, next_bake_sample) != MCPT_OK) { std::cerr << "Error: mcpt_bake: " << mcpt_last_error() << std::endl; return false; }
+    next_bake_sample += spp;
+    return true;
+}
+std::vector<float> Render::read_bake(Scene&, uint32_t mode) {
+    std::vector<float> out(4 * size_t(bake_points));
+    if (!ctx || out.empty()) return {};
+    if (mcpt_read_bake(ctx, mode, out.data()) != MCPT_OK) { std::cerr << "Error: mcpt_read_bake: " << mcpt_last_error() << std::endl; return {}; }
+    return out;
+}
 // `spp` samples into `scene`: of the pinhole camera (mcpt_render), or -- `camera_model` -- of the model set_camera_model chose (mcpt_render_camera, §25)
 bool Render::render_samples(Scene& scene, uint32_t spp, bool camera_model) {
     if (!ctx || spp == 0) return ctx != nullptr;

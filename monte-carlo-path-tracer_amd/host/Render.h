@@ -140,6 +140,15 @@ public:
     bool set_camera_model(Scene& scene, const mcpt_camera_model& model);
     bool render_camera(Scene& scene, uint32_t spp = 1);
     bool autofocus(Scene& scene, int px, int py, double& focus_distance);
+    // Surface baking: lighting seen from the surface -- lightmaps, per-vertex lighting, irradiance probes.  set_bake_points: the
+    // points to bake, each a face of the Model this Render was made from, barycentrics and a side (mcpt_set_bake_points; mcpt_lightmap_points
+    // makes them for a lightmap); an empty vector drops them; the bake film and the bake's sample numbering start again.  bake: `spp` more
+    // samples of `seed` for every point (mcpt_bake: one pass per sample; needs the wavefront pipeline).  read_bake: 4 floats per point,
+    // {irradiance or outgoing diffuse radiance, samples} (mcpt_read_bake; empty on failure).  None of them touches `scene`, its film or the
+    // camera's sample numbering.  false (Render unchanged) on failure.
+    bool set_bake_points(Scene& scene, const std::vector<mcpt_bake_point>& points);
+    bool bake(Scene& scene, uint32_t spp = 1);
+    std::vector<float> read_bake(Scene& scene, uint32_t mode = MCPT_BAKE_IRRADIANCE);
     // New trees for the geometry as it is now (mcpt_rebuild_trees): after update() / update_transforms() have moved the scene far
     // (mcpt_update_info::wide_area_ratio says how far) the refitted trees are sound and slow; this builds them anew on the context.  The picture
     // goes ON: `scene`'s film, the sample numbering and the feature buffers stay, the scene looks the same from every pixel.  Synchronous.  false
@@ -153,6 +162,7 @@ public:
 private:
     mcpt_ctx* ctx = nullptr;
     uint32_t next_sample = 0;
+    uint32_t next_bake_sample = 0, bake_points = 0;   // §27: the bake film's own numbering; the length of the list set
     std::vector<float> film;
     Scene* target = nullptr;                          // the Scene the device film belongs to
     bool dirty = false;                               // the device film holds samples `target` has not seen

@@ -74,6 +74,11 @@ static void usage() {
                  "                          [--ortho H]   an orthographic camera whose film is H world units high    [--panorama]   a 360 x 180 degree equirectangular camera\n"
                  "                                        (these three exclude each other; they go with --turntable and --gpus, not with --adaptive or --shard tiles;\n"
                  "                                        one pass per sample; --denoise and --reproject keep describing the pinhole view)\n"
+                 "                          [--bake-lightmap W H OUT.ppm [--bake-spp N] [--bake-irradiance]]   instead of a picture: a W x H lightmap over the scene's texture\n"
+                 "                                        coordinates (DESIGN.md 27), N samples per texel (64 by default) started ON the surfaces: the radiance a diffuse texel\n"
+                 "                                        sends out, or with --bake-irradiance the irradiance it receives; through the picture's transfer curve; texels no\n"
+                 "                                        face covers are black; row 0 of the file is v = 0, as a Map_Kd image is read (one GPU; honours --depth, --seed,\n"
+                 "                                        --corrected, --deterministic; not with --recursive)\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -110,6 +115,7 @@ int main(int argc, char** argv) {
     std::string hide, blink; int blink_k = 0;
     bool aperture_set = false, focus_set = false, autofocus_set = false, blades_set = false, rotation_set = false, ortho_set = false, panorama = false;
     double aperture = 0.0, focus = 0.0, blade_deg = 0.0, ortho_h = 0.0; int focus_x = 0, focus_y = 0, blades = 0;
+    std::string bake_out; int bake_w = 0, bake_h = 0, bake_spp = 64; bool bake_irradiance = false, bake_opts = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -149,6 +155,9 @@ int main(int argc, char** argv) {
         else if (a == "--blade-rotation") { rotation_set = true; blade_deg = std::atof(next()); }
         else if (a == "--ortho") { ortho_set = true; ortho_h = std::atof(next()); }
         else if (a == "--panorama") panorama = true;
+        else if (a == "--bake-lightmap") { bake_w = std::atoi(next()); bake_h = std::atoi(next()); bake_out = next(); }
+        else if (a == "--bake-spp") { bake_opts = true; bake_spp = std::atoi(next()); }
+        else if (a == "--bake-irradiance") bake_opts = bake_irradiance = true;
         else { usage(); return 2; }
     }
     if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
@@ -210,6 +219,15 @@ int main(int argc, char** argv) {
     }
     if (camera_model && (denoise || reproject))
         std::cerr << "Note: --denoise and --reproject are guided by features of the pinhole view, whatever camera model renders the film" << std::endl;
+    // --bake-lightmap W H OUT.ppm: the surface baking of DESIGN.md 27 instead of a picture
+    const bool bake = bake_w != 0 || bake_h != 0 || !bake_out.empty();
+    if (bake_opts && !bake) { std::cerr << "Error: --bake-spp N and --bake-irradiance need --bake-lightmap W H OUT.ppm" << std::endl; return 2; }
+    if (bake && (bake_w < 1 || bake_h < 1 || bake_w > 8192 || bake_h > 8192 || bake_out.empty() || bake_out == "0" || bake_spp < 1)) {
+        std::cerr << "Error: --bake-lightmap W H OUT.ppm needs W and H in [1, 8192], a file name and --bake-spp N >= 1" << std::endl; return 2;
+    }
+    if (bake && (gpus > 1 || turntable || adaptive >= 0.f || camera_model || integrator != MCPT_INTEGRATOR_MIS)) {
+        std::cerr << "Error: --bake-lightmap bakes on one GPU through the wavefront pipeline: not with --gpus, --turntable, --adaptive, a camera model or --recursive" << std::endl; return 2;
+    }
     if (wobble || !spin.empty() || !bend.empty() || !swell.empty() || !sequence.empty() || !hide.empty() || !blink.empty()) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
     if (!model.ok) { std::cerr << "Error: scene did not load" << std::endl; return 1; }
@@ -290,6 +308,35 @@ int main(int argc, char** argv) {
             std::cout << "autofocus: pixel (" << focus_x << ", " << focus_y << ") is " << cm.focus_distance << " away along the view direction" << std::endl;
         }
         for (auto r : renders) if (!r->set_camera_model(scene, cm)) return 1;
+    }
+    if (bake) {
+        std::vector<mcpt_material> mats; std::vector<mcpt_texture> texs; mcpt_scene_desc d;
+        model_to_desc(model, mats, texs, d);
+        const size_t n_texel = size_t(bake_w) * size_t(bake_h);
+        std::vector<mcpt_bake_point> points(n_texel); std::vector<uint32_t> texel(n_texel); uint32_t n = 0;
+        if (mcpt_lightmap_points(&d, uint32_t(bake_w), uint32_t(bake_h), uint32_t(n_texel), points.data(), texel.data(), &n) != MCPT_OK) {
+            std::cerr << "Error: mcpt_lightmap_points: " << mcpt_last_error() << std::endl; return 1;
+        }
+        points.resize(n); texel.resize(n);
+        std::vector<unsigned char> rgb(3 * n_texel, 0);                      // texels no face covers stay black
+        if (n) {
+            Render& r0 = *renders[0];
+            if (!r0.set_bake_points(scene, points) || !r0.bake(scene, uint32_t(bake_spp))) return 1;
+            const std::vector<float> lit = r0.read_bake(scene, bake_irradiance ? MCPT_BAKE_IRRADIANCE : MCPT_BAKE_DIFFUSE);
+            if (lit.size() != 4 * size_t(n)) return 1;
+            for (uint32_t k = 0; k < n; k++)
+                for (int c = 0; c < 3; c++) {                                // mcpt_tonemap's transfer (Scene::getPixelsColor) on the resolved value
+                    float m = std::fmin(std::fmax(lit[4 * size_t(k) + c], 0.f), 1.f);
+                    m = std::pow(m, 0.5f);
+                    rgb[3 * size_t(texel[k]) + c] = (unsigned char)(m * 255.99f);
+                }
+        }
+        FILE* f = std::fopen(bake_out.c_str(), "wb");
+        if (!f) { std::cerr << "Error: cannot write " << bake_out << std::endl; return 1; }
+        std::fprintf(f, "P6\n%d %d\n255\n", bake_w, bake_h); std::fwrite(rgb.data(), 1, rgb.size(), f); std::fclose(f);
+        std::cout << "baked " << n << " of " << n_texel << " texels, " << bake_spp << " samples each: " << bake_out << std::endl;
+        for (auto r : renders) delete r;
+        return 0;
     }
     // --turntable N: the camera moves, the scene stays -- Render::set_camera per frame, no rebuild, no upload
     if (turntable) {
