@@ -245,6 +245,17 @@ mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_deno
 mcpt_status mcpt_read_denoised(mcpt_ctx* ctx, float* rgba_host);                       /* synchronises, then D2H: width*height*4 floats */
 mcpt_status mcpt_denoised_device_ptr(mcpt_ctx* ctx, void** out_device_rgba);           /* the denoised film on the device (after a first mcpt_denoise) */
 mcpt_status mcpt_read_emission(mcpt_ctx* ctx, float* out4);                            /* synchronises, then D2H: width*height*4 floats; MCPT_ERR_INVALID_ARG when no emission is held */
+/* The filter alone on caller data of this context's film size: a film of width * height {sum rgb, count} records, features as
+ * mcpt_read_features returns them, and -- with MCPT_DENOISE_SPLIT_EMISSION, and only then -- an emission buffer as mcpt_read_emission returns
+ * it (NULL otherwise).  The options are checked as mcpt_denoise checks them (NULL = defaults); the depth term's pixel angle is that of the
+ * context's camera.  out gets what mcpt_read_denoised would return.  Synchronous; works in scratch buffers: the context's features, emission,
+ * denoised film and device_bytes are neither read nor written.
+ * PRECONDITION: every feature depth z >= 0.  The filter marks an invalid pixel for its later passes by a negative depth, so a valid pixel
+ * with z < 0 would be filtered as valid by the first pass and skipped as invalid by the others (mcpt_render_features never writes one:
+ * z is a mean of hit distances >= 1e-4, or 0).  A depth < 0, a non-finite feature or emission value, a null film, features or output, an
+ * emission buffer without the flag or the flag without one: MCPT_ERR_INVALID_ARG, and out is not written. */
+mcpt_status mcpt_probe_denoise(mcpt_ctx* ctx, const float* film_rgba_host, const float* feat8_host, const float* emis4_host,
+                               const mcpt_denoise_opts* opts, float* out_rgba_host);
 
 /* ---- adaptive sampling ------------------------------------------------------------------------------------------- */
 /* Samples go where the image is still noisy, per 8x8 tile.  During a call the samples go into two internal half films H and O (the first and

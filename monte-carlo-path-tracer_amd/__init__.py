@@ -277,6 +277,7 @@ def load_library() -> C.CDLL:
         "mcpt_render_features": [vp, C.c_uint32, C.c_uint64],
         "mcpt_read_features": [vp, vp],
         "mcpt_denoise": [vp, vp, P(DenoiseOpts)],
+        "mcpt_probe_denoise": [vp, vp, vp, vp, P(DenoiseOpts), vp],
         "mcpt_read_denoised": [vp, vp],
         "mcpt_denoised_device_ptr": [vp, P(vp)],
         "mcpt_read_emission": [vp, vp],
@@ -364,6 +365,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_null_stream", "mcpt_probe_trace", "mcpt_probe_trace4", "mcpt_probe_cast_ray", "mcpt_probe_hit_shade", "mcpt_probe_bsdf", "mcpt_probe_sample_light",
     "mcpt_probe_paths", "mcpt_probe_rng", "mcpt_probe_texture",
     "mcpt_render_features", "mcpt_read_features", "mcpt_denoise", "mcpt_read_denoised", "mcpt_denoised_device_ptr", "mcpt_read_emission",
+    "mcpt_probe_denoise",
     "mcpt_render_tile_list", "mcpt_render_adaptive", "mcpt_read_tile_error", "mcpt_probe_tile_error",
     "mcpt_set_camera", "mcpt_update_vertices", "mcpt_get_update_info", "mcpt_probe_validate_trees",
     "mcpt_set_camera_reproject", "mcpt_get_reproject_info", "mcpt_probe_reproject",
@@ -399,6 +401,15 @@ def _reproject_opts(feature_spp=0, feature_seed=0, max_history=0.0, depth_tolera
     o = ReprojectOpts()
     o.struct_size = C.sizeof(ReprojectOpts); o.feature_spp = feature_spp; o.feature_seed = feature_seed
     o.max_history = max_history; o.depth_tolerance = depth_tolerance; o.normal_threshold = normal_threshold
+    return o
+
+
+def _denoise_opts(iterations, sigma_color, sigma_normal, sigma_depth, split_emission, clamp_fireflies, firefly_clamp) -> DenoiseOpts:
+    o = DenoiseOpts()
+    o.struct_size = C.sizeof(DenoiseOpts); o.iterations = iterations
+    o.sigma_color = sigma_color; o.sigma_normal = sigma_normal; o.sigma_depth = sigma_depth
+    o.flags = (DENOISE_SPLIT_EMISSION if split_emission else 0) | (DENOISE_CLAMP_FIREFLIES if clamp_fireflies else 0)
+    o.firefly_clamp = firefly_clamp
     return o
 
 
@@ -1049,14 +1060,23 @@ class Renderer(BakeMethods):
         """A-trous filter of the context film (or of the device film at `device_ptr`): (h, w, 4) records {r, g, b, 1}.  split_emission: emitted
         light is kept apart from the reflected light the filter works on; clamp_fireflies: a pixel more than firefly_clamp times brighter than
         its brightest neighbour is scaled down to that (0 = the default)."""
-        o = DenoiseOpts()
-        o.struct_size = C.sizeof(DenoiseOpts); o.iterations = iterations
-        o.sigma_color = sigma_color; o.sigma_normal = sigma_normal; o.sigma_depth = sigma_depth
-        o.flags = (DENOISE_SPLIT_EMISSION if split_emission else 0) | (DENOISE_CLAMP_FIREFLIES if clamp_fireflies else 0)
-        o.firefly_clamp = firefly_clamp
+        o = _denoise_opts(iterations, sigma_color, sigma_normal, sigma_depth, split_emission, clamp_fireflies, firefly_clamp)
         self._check(self.lib.mcpt_denoise(self.ctx, None if device_ptr is None else C.c_void_p(device_ptr), C.byref(o)))
         out = np.zeros((self.height, self.width, 4), np.float32)
         self._check(self.lib.mcpt_read_denoised(self.ctx, _ptr(out)))
+        return out
+
+    def probe_denoise(self, film, feat, emis=None, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0,
+                      split_emission=False, clamp_fireflies=False, firefly_clamp=0.0) -> np.ndarray:
+        """The filter alone on a caller film (h, w, 4), features (h, w, 8) and -- with split_emission, and only then -- emission (h, w, 4):
+        what denoise() would return for them.  The context's own features, emission and denoised film are untouched."""
+        a = np.ascontiguousarray(film, np.float32); b = np.ascontiguousarray(feat, np.float32)
+        e = None if emis is None else np.ascontiguousarray(emis, np.float32)
+        n = self.width * self.height
+        assert a.size == 4 * n and b.size == 8 * n and (e is None or e.size == 4 * n)
+        o = _denoise_opts(iterations, sigma_color, sigma_normal, sigma_depth, split_emission, clamp_fireflies, firefly_clamp)
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self.lib.mcpt_probe_denoise(self.ctx, _ptr(a), _ptr(b), None if e is None else _ptr(e), C.byref(o), _ptr(out)))
         return out
 
     def emission(self) -> np.ndarray:

@@ -54,7 +54,12 @@ __global__ void __launch_bounds__(MCPT_BLOCK) dn_features_kernel(DevScene sc, ui
 #define DN_BX 64               // a wave is one row segment of 64 pixels: every tap of the 5x5 stencil is a coalesced row read
 #define DN_BY 4
 
-DEV float dn_lum(float r, float g, float b) { return r * 0.212671f + g * 0.715160f + b * 0.072169f; }   // make_bsdf's luminance
+// make_bsdf's luminance, with its roundings spelled out.  Written as r * 0.212671f + g * 0.715160f + b * 0.072169f under -ffp-contract=fast the
+// compiler picked which product to keep apart per kernel instantiation: dn_prep_robust_kernel<true, *> rounded the variance's luminance otherwise
+// than dn_prep_kernel and dn_prep_robust_kernel<false, true>, so a split with E = 0 was not the filter without the split, bit for bit.  The two
+// spellings are the ones the prep kernels of flags = 0 and the a-trous kernels always had: flags = 0 gives the bits it always gave.
+DEV float dn_lum_prep(float r, float g, float b) { return fmaf(b, 0.072169f, fmaf(g, 0.715160f, r * 0.212671f)); }   // the prep kernels'
+DEV float dn_lum(float r, float g, float b) { return fmaf(b, 0.072169f, fmaf(r, 0.212671f, g * 0.715160f)); }        // the a-trous kernels'
 DEV bool dn_valid(const float4 film, const float4 fa) { return film.w > 0.f && fa.w >= 0.5f; }
 // demodulated irradiance of a valid pixel: mean / albedo per channel (channels of albedo <= 1e-3 keep the mean)
 DEV f3 dn_irr(const float4 film, const float4 fa) {
@@ -81,7 +86,7 @@ __global__ void __launch_bounds__(DN_BX * DN_BY) dn_prep_kernel(DnParams p, cons
             const float4 qf = film[q], qa = feat[2 * q];
             if (!dn_valid(qf, qa)) continue;
             const f3 c = dn_irr(qf, qa);
-            const float l = dn_lum(c.x, c.y, c.z);
+            const float l = dn_lum_prep(c.x, c.y, c.z);
             s1 += l; s2 += l * l; cnt += 1.f;
         }
     }
@@ -127,7 +132,7 @@ __global__ void __launch_bounds__(DN_BX * DN_BY) dn_prep_robust_kernel(DnParams 
             const float4 qf = film[q], qa = feat[2 * q];
             if (dn_valid(qf, qa)) {
                 const f3 c = dn_irr_split<SPLIT>(qf, qa, emis, q);
-                l = dn_lum(c.x, c.y, c.z);
+                l = dn_lum_prep(c.x, c.y, c.z);
             }
         }
         s_raw[k] = l;

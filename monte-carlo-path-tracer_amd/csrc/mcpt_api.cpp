@@ -1314,14 +1314,33 @@ mcpt_status mcpt_read_features(mcpt_ctx* ctx, float* out8) {
     return read_back(ctx, out8, ctx->dn_feat.p, ctx->dn_feat.bytes);
 }
 
+// The options of a filter call, read and checked: what mcpt_denoise and mcpt_probe_denoise both refuse, before anything else of the call.
+static mcpt_status dn_read_opts(const mcpt_denoise_opts* opts, mcpt_denoise_opts& o, const char* fn) {
+    const mcpt_status st = read_opts(opts, o, fn, "mcpt_denoise_opts"); if (st != MCPT_OK) return st;
+    const std::string who = std::string(fn) + ": ";
+    if (o.iterations > DN_MAX_LEVELS) return fail(MCPT_ERR_INVALID_ARG, who + "at most 10 iterations");
+    if (!(o.sigma_color >= 0.f) || !(o.sigma_normal >= 0.f) || !(o.sigma_depth >= 0.f)) return fail(MCPT_ERR_INVALID_ARG, who + "sigmas must be >= 0 (0 = default)");
+    if (o.flags & ~(MCPT_DENOISE_SPLIT_EMISSION | MCPT_DENOISE_CLAMP_FIREFLIES)) return fail(MCPT_ERR_INVALID_ARG, who + "unknown bit in flags");
+    if (o.firefly_clamp != 0.f && !(std::isfinite(o.firefly_clamp) && o.firefly_clamp >= 1.f)) return fail(MCPT_ERR_INVALID_ARG, who + "firefly_clamp must be finite and >= 1 (0 = default)");
+    return MCPT_OK;
+}
+// The filter's parameters from checked options (defaults filled in) and the context's film size and camera; `levels` gets the a-trous levels.
+static DnParams dn_params(const mcpt_ctx* ctx, const mcpt_denoise_opts& o, uint32_t& levels) {
+    DnParams p;
+    p.width = ctx->width; p.height = ctx->height;
+    p.sigma_c = o.sigma_color > 0.f ? o.sigma_color : 4.f;
+    p.sigma_n = o.sigma_normal > 0.f ? o.sigma_normal : 128.f;
+    p.sigma_z = o.sigma_depth > 0.f ? o.sigma_depth : 4.f;
+    p.theta = float(ctx->dev.cam.h / double(ctx->height));
+    p.clamp_k = !(o.flags & MCPT_DENOISE_CLAMP_FIREFLIES) ? 0.f : o.firefly_clamp > 0.f ? o.firefly_clamp : MCPT_DENOISE_DEFAULT_FIREFLY_CLAMP;
+    levels = o.iterations ? o.iterations : 5u;
+    return p;
+}
+
 mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_denoise_opts* opts) {
     mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
     mcpt_denoise_opts o;
-    st = read_opts(opts, o, "mcpt_denoise", "mcpt_denoise_opts"); if (st != MCPT_OK) return st;
-    if (o.iterations > DN_MAX_LEVELS) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: at most 10 iterations");
-    if (!(o.sigma_color >= 0.f) || !(o.sigma_normal >= 0.f) || !(o.sigma_depth >= 0.f)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be >= 0 (0 = default)");
-    if (o.flags & ~(MCPT_DENOISE_SPLIT_EMISSION | MCPT_DENOISE_CLAMP_FIREFLIES)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: unknown bit in flags");
-    if (o.firefly_clamp != 0.f && !(std::isfinite(o.firefly_clamp) && o.firefly_clamp >= 1.f)) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: firefly_clamp must be finite and >= 1 (0 = default)");
+    st = dn_read_opts(opts, o, "mcpt_denoise"); if (st != MCPT_OK) return st;
     if (!ctx->dn_have_features) return fail(MCPT_ERR_INVALID_ARG, "mcpt_denoise: no features rendered yet (mcpt_render_features)");
     const size_t n = size_t(ctx->width) * ctx->height;
     uint64_t* tally = &ctx->info.device_bytes;
@@ -1332,18 +1351,42 @@ mcpt_status mcpt_denoise(mcpt_ctx* ctx, const void* device_rgba, const mcpt_deno
         HIP_TRY(launch_dn_features(ctx->dev, ctx->dn_feat_spp, uint32_t(ctx->dn_feat_seed), uint32_t(ctx->dn_feat_seed >> 32), nullptr, ctx->dn_emis.p, ctx->stream));
         ctx->dn_have_emis = true;
     }
-    DnParams p;
-    p.width = ctx->width; p.height = ctx->height;
-    p.sigma_c = o.sigma_color > 0.f ? o.sigma_color : 4.f;
-    p.sigma_n = o.sigma_normal > 0.f ? o.sigma_normal : 128.f;
-    p.sigma_z = o.sigma_depth > 0.f ? o.sigma_depth : 4.f;
-    p.theta = float(ctx->dev.cam.h / double(ctx->height));
-    const uint32_t levels = o.iterations ? o.iterations : 5u;
+    uint32_t levels;
+    const DnParams p = dn_params(ctx, o, levels);
     const float4* film = device_rgba ? static_cast<const float4*>(device_rgba) : ctx->accum;
-    p.clamp_k = !(o.flags & MCPT_DENOISE_CLAMP_FIREFLIES) ? 0.f : o.firefly_clamp > 0.f ? o.firefly_clamp : MCPT_DENOISE_DEFAULT_FIREFLY_CLAMP;
     HIP_TRY(launch_dn_filter(p, levels, film, ctx->dn_feat.p, split ? ctx->dn_emis.p : nullptr, ctx->dn_guide.p, ctx->dn_iv0.p, ctx->dn_iv1.p, ctx->dn_out.p,
                              ctx->stream));
     ctx->dn_have_out = true;
+    return MCPT_OK;
+}
+
+// The filter alone on caller films, features and emission of the context's film size, in scratch buffers on the context's stream: nothing of
+// the context's own denoiser state (features, emission, denoised film, device_bytes) is read or written.
+mcpt_status mcpt_probe_denoise(mcpt_ctx* ctx, const float* film_rgba_host, const float* feat8_host, const float* emis4_host, const mcpt_denoise_opts* opts,
+                               float* out_rgba_host) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!film_rgba_host || !feat8_host || !out_rgba_host) return fail(MCPT_ERR_INVALID_ARG, "null argument");
+    mcpt_denoise_opts o;
+    st = dn_read_opts(opts, o, "mcpt_probe_denoise"); if (st != MCPT_OK) return st;
+    const bool split = (o.flags & MCPT_DENOISE_SPLIT_EMISSION) != 0;
+    if (split && !emis4_host) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_denoise: MCPT_DENOISE_SPLIT_EMISSION needs an emission buffer");
+    if (!split && emis4_host) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_denoise: an emission buffer without MCPT_DENOISE_SPLIT_EMISSION");
+    const size_t n = size_t(ctx->width) * ctx->height;
+    for (size_t i = 0; i < 8 * n; i++)
+        if (!std::isfinite(feat8_host[i])) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_denoise: a feature is not finite");
+    for (size_t i = 0; i < n; i++)
+        if (feat8_host[8 * i + 7] < 0.f) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_denoise: a feature depth is < 0 (the filter marks invalid pixels by a negative depth)");
+    for (size_t i = 0; split && i < 4 * n; i++)
+        if (!std::isfinite(emis4_host[i])) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_denoise: an emission value is not finite");
+    uint32_t levels;
+    const DnParams p = dn_params(ctx, o, levels);
+    Scratch s(ctx->stream); float4 *film, *feat, *emis = nullptr, *guide, *iv0, *iv1, *out;
+    HIP_TRY(s.in(reinterpret_cast<const float4*>(film_rgba_host), n, &film)); HIP_TRY(s.in(reinterpret_cast<const float4*>(feat8_host), 2 * n, &feat));
+    if (split) HIP_TRY(s.in(reinterpret_cast<const float4*>(emis4_host), n, &emis));
+    HIP_TRY(s.out(n, &guide)); HIP_TRY(s.out(n, &iv0)); HIP_TRY(s.out(n, &iv1)); HIP_TRY(s.out(n, &out));
+    HIP_TRY(launch_dn_filter(p, levels, film, feat, emis, guide, iv0, iv1, out, ctx->stream));
+    HIP_TRY(s.fetch(reinterpret_cast<float4*>(out_rgba_host), out, n));
+    HIP_TRY(s.finish());
     return MCPT_OK;
 }
 

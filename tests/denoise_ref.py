@@ -32,16 +32,59 @@ def _shift(a: np.ndarray, dy: int, dx: int):
     return out, ok
 
 
+def decisions(film, feat):
+    """What the device decides per pixel, decided as it decides it: on the fp32 inputs against the fp32 constants (dn_valid, dn_irr).
+    float32(1e-3) is greater than the double 1e-3, so a test of the widened albedo against the double would divide out an albedo of exactly
+    float32(1e-3) that the device keeps.  Returns (sampled = count > 0, valid = sampled and coverage >= 0.5, demod = albedo > 1e-3f per
+    channel, passed = the fp32 mean float32(sum) / float32(count) of the sampled pixels, 0 elsewhere: what an invalid pixel passes through,
+    and the device's division is correctly rounded)."""
+    film = np.asarray(film, np.float32); feat = np.asarray(feat, np.float32)
+    sampled = film[..., 3] > np.float32(0)
+    valid = sampled & (feat[..., 3] >= np.float32(0.5))
+    demod = feat[..., :3] > np.float32(1e-3)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        passed = np.where(sampled[..., None], film[..., :3] / np.where(sampled, film[..., 3], np.float32(1))[..., None], np.float32(0))
+    return sampled, valid, demod, passed.astype(np.float64)
+
+
+def variance3x3(lum, valid):
+    """Variance of `lum` over the valid pixels of every valid pixel's 3x3 neighbourhood, in two passes: their mean, then the mean of the squared
+    deviations from it -- exactly 0 on a constant patch.  The device forms E[l^2] - E[l]^2 from single-pass fp32 sums, which cancels: nine equal
+    luminances l can leave it sqrt(var) up to ~ 6e-4 l.  Measured through mcpt_probe_denoise on films without noise that costs at most 7e-5 of
+    max(1, |out|), so the device is held to the exact variance, not to a restatement of its cancellation."""
+    s1 = np.zeros_like(lum); n = np.zeros_like(lum)
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            lq, ok = _shift(lum, dy, dx); vq, _ = _shift(valid, dy, dx)
+            m = ok & vq
+            s1 += np.where(m, lq, 0); n += m
+    n = np.maximum(n, 1)
+    mean = s1 / n
+    s2 = np.zeros_like(lum)
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            lq, ok = _shift(lum, dy, dx); vq, _ = _shift(valid, dy, dx)
+            s2 += np.where(ok & vq, (lq - mean) ** 2, 0)
+    return np.where(valid, s2 / n, 0.0)
+
+
+def assert_identity_level(h, before, after):
+    """From the level whose step h reaches the image's larger side every tap but the centre's leaves the image: the level is the identity on irr
+    (up to the rounding of (w x) / w)."""
+    if h >= max(before.shape[:2]):
+        assert np.allclose(after, before, rtol=1e-14, atol=0.0), h
+
+
 def denoise_ref(film, feat, theta, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0):
-    film = np.asarray(film, np.float64); feat = np.asarray(feat, np.float64)
+    sampled, valid, demod, passed = decisions(film, feat)
+    film = np.asarray(film, np.float32).astype(np.float64); feat = np.asarray(feat, np.float32).astype(np.float64)
     L = iterations or DEFAULTS["iterations"]
     sc = sigma_color or DEFAULTS["sigma_color"]; sn = sigma_normal or DEFAULTS["sigma_normal"]; sz = sigma_depth or DEFAULTS["sigma_depth"]
     cnt = film[..., 3]
     a = feat[..., :3]
-    valid = (cnt > 0) & (feat[..., 3] >= 0.5)
     with np.errstate(divide="ignore", invalid="ignore"):
-        c = np.where(cnt[..., None] > 0, film[..., :3] / np.where(cnt > 0, cnt, 1)[..., None], 0.0)
-        irr = np.where(a > 1e-3, c / np.where(a > 1e-3, a, 1.0), c)
+        c = np.where(sampled[..., None], film[..., :3] / np.where(sampled, cnt, 1)[..., None], 0.0)
+        irr = np.where(demod, c / np.where(demod, a, 1.0), c)
     irr = np.where(valid[..., None], irr, 0.0)
     nrm = feat[..., 4:7]
     nl = np.sqrt((nrm * nrm).sum(-1, keepdims=True))
@@ -49,15 +92,7 @@ def denoise_ref(film, feat, theta, iterations=0, sigma_color=0.0, sigma_normal=0
     z = feat[..., 7]
 
     # 3x3 variance of the luminance over valid neighbours
-    lum = irr @ LUM
-    s1 = np.zeros_like(lum); s2 = np.zeros_like(lum); n = np.zeros_like(lum)
-    for dy in (-1, 0, 1):
-        for dx in (-1, 0, 1):
-            lq, ok = _shift(lum, dy, dx); vq, _ = _shift(valid, dy, dx)
-            m = ok & vq
-            s1 += np.where(m, lq, 0); s2 += np.where(m, lq * lq, 0); n += m
-    n = np.maximum(n, 1)
-    var = np.where(valid, np.maximum(s2 / n - (s1 / n) ** 2, 0.0), 0.0)
+    var = variance3x3(irr @ LUM, valid)
 
     for i in range(L):
         h = 1 << i
@@ -84,11 +119,13 @@ def denoise_ref(film, feat, theta, iterations=0, sigma_color=0.0, sigma_normal=0
                 w = np.where(m, w, 0.0)
                 sw += w; si += w[..., None] * iq; sv += w * w * vq
         sw = np.where(valid, sw, 1.0)
+        before = irr
         irr = np.where(valid[..., None], si / sw[..., None], 0.0)
+        assert_identity_level(h, before, irr)
         var = np.where(valid, sv / (sw * sw), 0.0)
 
     out = np.zeros(film.shape, np.float64)
-    rem = np.where(a > 1e-3, irr * a, irr)
-    out[..., :3] = np.where(valid[..., None], rem, c)
-    out[..., 3] = np.where(cnt > 0, 1.0, 0.0)
+    rem = np.where(demod, irr * a, irr)
+    out[..., :3] = np.where(valid[..., None], rem, passed)
+    out[..., 3] = np.where(sampled, 1.0, 0.0)
     return out

@@ -11,7 +11,7 @@ import math
 
 import numpy as np
 
-from tests.denoise_ref import DEFAULTS, K5, LUM, _shift
+from tests.denoise_ref import DEFAULTS, K5, LUM, _shift, assert_identity_level, decisions, variance3x3
 
 SPLIT = 0x1                    # MCPT_DENOISE_SPLIT_EMISSION
 CLAMP = 0x2                    # MCPT_DENOISE_CLAMP_FIREFLIES
@@ -36,20 +36,20 @@ def clamp_fireflies(irr, valid, k):
 
 
 def denoise_robust_ref(film, feat, emis, theta, flags=0, firefly_clamp=0.0, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0):
-    film = np.asarray(film, np.float64); feat = np.asarray(feat, np.float64)
+    sampled, valid, demod, passed = decisions(film, feat)
+    film = np.asarray(film, np.float32).astype(np.float64); feat = np.asarray(feat, np.float32).astype(np.float64)
     L = iterations or DEFAULTS["iterations"]
     sc = sigma_color or DEFAULTS["sigma_color"]; sn = sigma_normal or DEFAULTS["sigma_normal"]; sz = sigma_depth or DEFAULTS["sigma_depth"]
     k = firefly_clamp or DEFAULT_FIREFLY_CLAMP
     cnt = film[..., 3]
     a = feat[..., :3]
-    valid = (cnt > 0) & (feat[..., 3] >= 0.5)
     with np.errstate(divide="ignore", invalid="ignore"):
-        c = np.where(cnt[..., None] > 0, film[..., :3] / np.where(cnt > 0, cnt, 1)[..., None], 0.0)
+        c = np.where(sampled[..., None], film[..., :3] / np.where(sampled, cnt, 1)[..., None], 0.0)
         refl = c
         if flags & SPLIT:
-            e = np.asarray(emis, np.float64)[..., :3]
+            e = np.asarray(emis, np.float32).astype(np.float64)[..., :3]
             refl = np.maximum(c - e, 0.0)
-        irr = np.where(a > 1e-3, refl / np.where(a > 1e-3, a, 1.0), refl)
+        irr = np.where(demod, refl / np.where(demod, a, 1.0), refl)
     irr = np.where(valid[..., None], irr, 0.0)
     if flags & CLAMP:
         irr, _ = clamp_fireflies(irr, valid, k)
@@ -59,15 +59,7 @@ def denoise_robust_ref(film, feat, emis, theta, flags=0, firefly_clamp=0.0, iter
     z = feat[..., 7]
 
     # 3x3 variance of the (clamped) luminance over valid neighbours
-    lum = irr @ LUM
-    s1 = np.zeros_like(lum); s2 = np.zeros_like(lum); n = np.zeros_like(lum)
-    for dy in (-1, 0, 1):
-        for dx in (-1, 0, 1):
-            lq, ok = _shift(lum, dy, dx); vq, _ = _shift(valid, dy, dx)
-            m = ok & vq
-            s1 += np.where(m, lq, 0); s2 += np.where(m, lq * lq, 0); n += m
-    n = np.maximum(n, 1)
-    var = np.where(valid, np.maximum(s2 / n - (s1 / n) ** 2, 0.0), 0.0)
+    var = variance3x3(irr @ LUM, valid)
 
     for i in range(L):
         h = 1 << i
@@ -94,13 +86,15 @@ def denoise_robust_ref(film, feat, emis, theta, flags=0, firefly_clamp=0.0, iter
                 w = np.where(m, w, 0.0)
                 sw += w; si += w[..., None] * iq; sv += w * w * vq
         sw = np.where(valid, sw, 1.0)
+        before = irr
         irr = np.where(valid[..., None], si / sw[..., None], 0.0)
+        assert_identity_level(h, before, irr)
         var = np.where(valid, sv / (sw * sw), 0.0)
 
     out = np.zeros(film.shape, np.float64)
-    rem = np.where(a > 1e-3, irr * a, irr)
+    rem = np.where(demod, irr * a, irr)
     if flags & SPLIT:
         rem = rem + e
-    out[..., :3] = np.where(valid[..., None], rem, c)
-    out[..., 3] = np.where(cnt > 0, 1.0, 0.0)
+    out[..., :3] = np.where(valid[..., None], rem, passed)
+    out[..., 3] = np.where(sampled, 1.0, 0.0)
     return out

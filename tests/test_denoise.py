@@ -165,11 +165,12 @@ def _film_and_features(pkg, scene, spp=4, seed=7, depth=8, **kw):
 
 
 def _assert_matches_ref(out, ref):
+    """Every pixel within 1e-3 max(1, |ref|).  (Until the restatement decided the albedo threshold in fp32 and the filter had been probed at
+    its edges, 0.1 % of the pixels were let off at 1e-2; measured on the MI355X no pixel of any film here comes near: worst 7.1e-6.)"""
     d = np.abs(out.astype(np.float64) - ref)
     tol = np.maximum(1.0, np.abs(ref))
-    frac = float(np.mean(np.all(d <= 1e-3 * tol, axis=-1)))
-    assert frac >= 0.999, frac
-    assert np.all(d <= 1e-2 * tol), float((d / tol).max())
+    print("[denoise] worst |out - ref| / max(1, |ref|) = %.3e" % float((d / tol).max()))
+    assert np.all(d <= 1e-3 * tol), float((d / tol).max())
 
 
 @pytest.mark.gpu
