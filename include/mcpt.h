@@ -1048,13 +1048,36 @@ mcpt_status mcpt_probe_camera_rays(mcpt_ctx* ctx, uint32_t n, const int32_t* xy,
  * Item i of a pass is point i; its direction comes from random-number block 0 of (pixel = i, sample, seed) -- the camera's block -- and its path
  * draws blocks 1, 2, ... as every path does.
  *
- * LIMIT: the first vertex has no next-event estimation.  Direct light reaches a point only through cosine-sampled rays that hit an emitter,
- * which is noisy under small lamps; from the first hit on, paths sample the lights as always (that needs the shade kernel).
+ * DIRECT LIGHT (mcpt_set_bake_direct).  MCPT_BAKE_DIRECT_OFF, the default: direct light reaches a point only through cosine-sampled rays that hit
+ * an emitter, which is noisy under small lamps; from the first hit on, paths sample the lights as always.  MCPT_BAKE_DIRECT_MIS adds next-event
+ * estimation at the bake point itself, combined with the cosine ray by the power heuristic.  The record keeps its meaning (the mean of L over
+ * cosine-weighted directions).  Per live item a kernel that takes the first-hit kernel's place (below) forms, in fp32:
+ *   sub -- for the cosine ray's first hit: Le for an emitter met from behind (the rule below); (1 - w_b) Le for a LIGHT (|radiance| > 0.01) met from
+ *          its front, with p_b = max(d.n, 0) / pi, p_l = t^2 / (cos_l n_lights area) (the pdf a later bounce uses) and w_b = p_b^2 / (p_b^2 + p_l^2);
+ *          0 otherwise -- a faint emitter (0.0001 < |radiance| <= 0.01) is in no light list and keeps its full radiance;
+ *   add -- one light sample from random-number block 0xFFFFFFFF of the item (a path would need 2^31 bounces to draw it): it counts if its pdf is finite
+ *          and > 0 (a light seen from behind gives nothing), its distance exceeds 1e-4, cos_p = wo.n > 0 and the segment to it is free; then
+ *          p_bl = cos_p / pi, p_lf = pdf / n_lights, w_l = p_lf^2 / (p_lf^2 + p_bl^2), add = w_l Le p_bl / p_lf.
+ * and adds (add - sub) to the item's record before the pass.  The bake's own vertex ignores the light sample's self-occlusion verdict and always
+ * behaves as MCPT_FLAG_CORRECT_SHADOW_T2 does: that quirk exists for parity with a reference that has no baker.  Everything from the first hit on
+ * is the pipeline's, unchanged.  The stage's two traversals are not counted in mcpt_counters.
+ *
+ * mcpt_set_bake_direct: an unknown mode is MCPT_ERR_INVALID_ARG with nothing changed.  Works with or without points; the mode survives
+ * mcpt_set_bake_points, mcpt_clear_bake and mcpt_rebuild_trees; a clone starts with OFF.  It holds for the passes enqueued after it and drains
+ * nothing.  Costs no device memory.  mcpt_bake_info::direct_mode reports it.
+ *
+ * mcpt_probe_bake_direct: the kernel's device function for points first .. first + n - 1 and sample `sample`, whatever the mode, touching no film;
+ * synchronous; either array may be NULL.  out12 per point: sub[3], add[3], w_b, w_l, p_b, p_l, p_bl, p_lf (terms not reached are 0: w_b, p_b, p_l
+ * belong to a light met from its front; w_l, p_bl, p_lf to the states OCCLUDED and COUNTED).  out4 per point: the first-hit face in Model::face
+ * order (-1 for a miss), whether it was met from its front (0 / 1), the sampled light's face, and MCPT_BAKE_DIRECT_STATE_*: DEAD (a dead point:
+ * faces -1, all else 0), NO_PDF (pdf not positive or not finite, or distance <= 1e-4), BELOW (under the point's horizon), OCCLUDED, COUNTED.
+ * MCPT_ERR_BVH_DEPTH where mcpt_bake answers it.
  *
  * EMITTERS ARE ONE-SIDED FOR A BAKE POINT.  A point's ray enters the pipeline as a path's PRIMARY ray, whose hit on an emitter adds its radiance
  * whatever side it is hit from (a camera sees a lamp's back lit); later bounces see emitters from their front only, and a surface point's ray is
  * morally one of those.  So before each pass a first-hit kernel (the binary tree; about 0.4 ms per pass for 640 000 points) finds the rays that
  * first meet an emitter from behind and takes that radiance out of their records: such a sample contributes what its path gathers after that hit.
+ * (With MCPT_BAKE_DIRECT_MIS the direct-light kernel does this in the same traversal.)
  * MCPT_ERR_BVH_DEPTH from mcpt_bake where mcpt_probe_first_hits answers it (a device-built binary tree deeper than the kernel's stack).
  *
  * mcpt_set_bake_points: synchronous set-up.  Validated on the host before any device work, a refusal changes nothing: MCPT_ERR_INVALID_ARG for a
@@ -1089,6 +1112,13 @@ mcpt_status mcpt_probe_camera_rays(mcpt_ctx* ctx, uint32_t n, const int32_t* xy,
 #define MCPT_BAKE_BACK_SIDE   1u          /* mcpt_bake_point::flags */
 #define MCPT_BAKE_IRRADIANCE  0u          /* mcpt_read_bake's mode */
 #define MCPT_BAKE_DIFFUSE     1u
+#define MCPT_BAKE_DIRECT_OFF  0u          /* mcpt_set_bake_direct's mode */
+#define MCPT_BAKE_DIRECT_MIS  1u
+#define MCPT_BAKE_DIRECT_STATE_DEAD     0 /* mcpt_probe_bake_direct's out4[3] */
+#define MCPT_BAKE_DIRECT_STATE_NO_PDF   1
+#define MCPT_BAKE_DIRECT_STATE_BELOW    2
+#define MCPT_BAKE_DIRECT_STATE_OCCLUDED 3
+#define MCPT_BAKE_DIRECT_STATE_COUNTED  4
 typedef struct mcpt_bake_point {
     uint32_t face;                        /* Model::face order */
     float    u, v;                        /* barycentrics of corners 1 and 2 */
@@ -1100,7 +1130,10 @@ typedef struct mcpt_bake_info {
     uint64_t passes;                      /* ... and their samples: one ray kernel each */
     double   last_stage_ms;               /* HIP events: the ray kernels of the last call, summed */
     uint64_t device_bytes;                /* points + dead bytes + bake film + ray arrays, as held now */
-    uint32_t reserved[4];
+    union {                               /* (anonymous: C11, C++ and every C99 compiler in use) */
+        uint32_t direct_mode;             /* MCPT_BAKE_DIRECT_*: reserved[0]'s word, which was always 0, so 0 keeps its meaning */
+        uint32_t reserved[4];             /* [1] .. [3] stay reserved */
+    };
 } mcpt_bake_info;
 mcpt_status mcpt_set_bake_points(mcpt_ctx* ctx, const mcpt_bake_point* points, uint32_t n);
 mcpt_status mcpt_bake(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first_sample);
@@ -1110,6 +1143,9 @@ mcpt_status mcpt_read_bake_film(mcpt_ctx* ctx, float* out4 /* 4 per point */);
 mcpt_status mcpt_get_bake_info(mcpt_ctx* ctx, mcpt_bake_info* out);                 /* synchronises */
 mcpt_status mcpt_probe_bake_rays(mcpt_ctx* ctx, uint32_t sample, uint64_t seed, uint32_t first, uint32_t n, double* out_origin3 /* device coordinates */,
                                  double* out_dir3, double* out_normal3, uint8_t* out_dead);
+mcpt_status mcpt_set_bake_direct(mcpt_ctx* ctx, uint32_t mode /* MCPT_BAKE_DIRECT_* */);
+mcpt_status mcpt_probe_bake_direct(mcpt_ctx* ctx, uint32_t sample, uint64_t seed, uint32_t first, uint32_t n, float* out12 /* 12 per point */,
+                                   int32_t* out4 /* 4 per point */);
 mcpt_status mcpt_lightmap_points(const mcpt_scene_desc* scene, uint32_t width, uint32_t height, uint32_t capacity, mcpt_bake_point* out_points,
                                  uint32_t* out_texel, uint32_t* out_n);
 

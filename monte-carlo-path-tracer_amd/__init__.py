@@ -36,7 +36,7 @@ from .visibility_abi import VisibilityInfo, visibility_from_materials  # noqa: F
 from .camera_abi import (CAMERA_EQUIRECT, CAMERA_MAX_BLADES, CAMERA_ORTHOGRAPHIC, CAMERA_PINHOLE, CAMERA_THIN_LENS, CameraModel, CameraModelInfo,  # noqa: F401
                          camera_model)
 # mcpt_bake_point, mcpt_get_bake_info's struct, the constants, the makers of bake-point lists and Renderer's baking methods; tests/test_bake_ref.py holds the layouts to the header
-from .bake_abi import (BAKE_BACK_SIDE, BAKE_DIFFUSE, BAKE_IRRADIANCE, BAKE_MAX_POINTS, BakeInfo, BakeMethods, BakePoint, bake_points, lightmap_points,  # noqa: F401
+from .bake_abi import (BAKE_BACK_SIDE, BAKE_DIFFUSE, BAKE_DIRECT_MIS, BAKE_DIRECT_OFF, BAKE_IRRADIANCE, BAKE_MAX_POINTS, BakeInfo, BakeMethods, BakePoint, bake_points, lightmap_points,  # noqa: F401
                        vertex_bake_points)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -345,6 +345,8 @@ def load_library() -> C.CDLL:
         "mcpt_get_bake_info": [vp, P(BakeInfo)],
         "mcpt_probe_bake_rays": [vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp],
         "mcpt_lightmap_points": [P(SceneDesc), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, P(C.c_uint32)],
+        "mcpt_set_bake_direct": [vp, C.c_uint32],
+        "mcpt_probe_bake_direct": [vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -382,6 +384,7 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_face_visibility", "mcpt_set_face_visibility_reproject", "mcpt_get_visibility_info", "mcpt_probe_triangles",
     "mcpt_set_camera_model", "mcpt_get_camera_model", "mcpt_render_camera", "mcpt_autofocus", "mcpt_probe_camera_rays",
     "mcpt_set_bake_points", "mcpt_bake", "mcpt_clear_bake", "mcpt_read_bake", "mcpt_read_bake_film", "mcpt_get_bake_info", "mcpt_probe_bake_rays", "mcpt_lightmap_points",
+    "mcpt_set_bake_direct", "mcpt_probe_bake_direct",
 ]
 
 

@@ -1,6 +1,7 @@
 """ctypes mirror of include/mcpt.h's surface-baking section: mcpt_bake_point, mcpt_bake_info, the constants, and the two makers
 of bake-point lists -- lightmap_points (mcpt_lightmap_points: host only, no device) and vertex_bake_points.  Re-exported by the package, whose
-Renderer mixes BakeMethods in; tests/test_bake_ref.py holds the structs' sizes and offsets to the header."""
+Renderer mixes BakeMethods in; tests/test_bake_ref.py holds the structs' sizes and offsets to the header (BakeInfo keeps the header's
+`reserved` array whole and reads `direct_mode`, the name the header gives its first word, through a property: tests/test_bake_direct_ref.py)."""
 import ctypes as C
 
 import numpy as np
@@ -9,6 +10,10 @@ BAKE_BACK_SIDE = 1
 BAKE_IRRADIANCE = 0
 BAKE_DIFFUSE = 1
 BAKE_MAX_POINTS = 0x3ffffff
+BAKE_DIRECT_OFF = 0
+BAKE_DIRECT_MIS = 1
+# probe_bake_direct's state column
+BAKE_DIRECT_STATE_DEAD, BAKE_DIRECT_STATE_NO_PDF, BAKE_DIRECT_STATE_BELOW, BAKE_DIRECT_STATE_OCCLUDED, BAKE_DIRECT_STATE_COUNTED = range(5)
 
 # numpy's view of a list of mcpt_bake_point
 POINT_DTYPE = np.dtype([("face", np.uint32), ("u", np.float32), ("v", np.float32), ("flags", np.uint32)])
@@ -22,8 +27,13 @@ class BakeInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_points", C.c_uint32), ("n_dead", C.c_uint32), ("bakes", C.c_uint32), ("passes", C.c_uint64),
                 ("last_stage_ms", C.c_double), ("device_bytes", C.c_uint64), ("reserved", C.c_uint32 * 4)]
 
+    @property
+    def direct_mode(self) -> int:
+        """BAKE_DIRECT_*: the header's name for reserved[0]'s word."""
+        return int(self.reserved[0])
+
     def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+        return dict({k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}, direct_mode=self.direct_mode)
 
 
 def bake_points(face, u, v, flags=0) -> np.ndarray:
@@ -98,6 +108,20 @@ class BakeMethods:
         i = BakeInfo()
         self._check(self.lib.mcpt_get_bake_info(self.ctx, C.byref(i)))
         return i
+
+    def set_bake_direct(self, mode: int):
+        """BAKE_DIRECT_OFF (the default) or BAKE_DIRECT_MIS: next-event estimation at the bake point, MIS-weighted against the cosine ray.  Holds
+        for the passes enqueued after it; survives set_bake_points, clear_bake and rebuild."""
+        self._check(self.lib.mcpt_set_bake_direct(self.ctx, int(mode)))
+
+    def probe_bake_direct(self, sample: int = 0, seed: int = 0, first: int = 0, n=None):
+        """The direct-light kernel's two terms for points first .. first + n - 1 (n None: to the end of the list) of sample `sample`, whatever the
+        mode: ((n, 12) float32 sub[3], add[3], w_b, w_l, p_b, p_l, p_bl, p_lf; (n, 4) int32 first-hit face or -1, front, light face, state)."""
+        n = getattr(self, "_n_bake", 0) - int(first) if n is None else int(n)
+        f = np.zeros((max(n, 0), 12), np.float32); k = np.zeros((max(n, 0), 4), np.int32)
+        self._check(self.lib.mcpt_probe_bake_direct(self.ctx, sample, seed, int(first), max(n, 0) if n >= 0 else 0xffffffff, f.ctypes.data_as(C.c_void_p),
+                                                    k.ctypes.data_as(C.c_void_p)))
+        return f, k
 
     def probe_bake_rays(self, sample: int = 0, seed: int = 0, first: int = 0, n=None):
         """The stage's rays for points first .. first + n - 1 (n None: to the end of the list) of sample `sample`: ((n, 3) float64 origins in

@@ -21,7 +21,16 @@ hipError_t launch_bk_rays(const DevScene& sc, const BkPoint* points, uint32_t n,
 // hold) and, where that is an emitter seen from BEHIND, subtracts the emitter's radiance from film[i] -- what the pass then adds for a primary
 // hit, whatever its side.  Dead items are left alone.
 hipError_t launch_bk_unlit(const DevScene& sc, const double* origin, const double* dir, const uint8_t* dead, uint32_t n, float4* film, hipStream_t stream);
-// The same device function for points first .. first + n - 1 (item numbers included): ray k goes to row k of the outputs, the unit normal too.
+// MCPT_BAKE_DIRECT_MIS: launched in launch_bk_unlit's place.  One lane per item adds to film[i] the MIS-weighted light sample of the bake point and
+// takes out what the pass would add too much for the ray's first hit -- an emitter's back as above, and the share 1 - w_b of a light's front
+// (bk_direct in bake.hip).  `points` and the sample's key give the normal again; `dir` is the ray kernel's array.  Dead items are left alone.
+hipError_t launch_bk_direct(const DevScene& sc, const BkPoint* points, const double* dir, uint32_t n, uint32_t sample, uint32_t seed_lo, uint32_t seed_hi, float4* film,
+                            hipStream_t stream);
+// The same device function for points first .. first + n - 1 (item numbers included), no film touched: 12 floats and 4 ints per point, see
+// mcpt_probe_bake_direct.
+hipError_t launch_bk_direct_probe(const DevScene& sc, const BkPoint* points, uint32_t first, uint32_t n, uint32_t sample, uint32_t seed_lo, uint32_t seed_hi, float* out12,
+                                  int32_t* out4, hipStream_t stream);
+// The ray kernel's device function for points first .. first + n - 1 (item numbers included): ray k goes to row k of the outputs, the unit normal too.
 hipError_t launch_bk_probe(const DevScene& sc, const BkPoint* points, uint32_t first, uint32_t n, uint32_t sample, uint32_t seed_lo, uint32_t seed_hi, double* origin,
                            double* dir, double* normal, uint8_t* dead, hipStream_t stream);
 // One lane per point: out[i] from film[i] = {sum L, count} by `mode` (MCPT_BAKE_*); {0, 0, 0, 0} for a dead point or a count of 0.

@@ -420,6 +420,7 @@ struct mcpt_ctx {
     struct Bake {
         std::vector<mcpt_bake_point> host; DevBuf<BkPoint> pts; DevBuf<uint8_t> dead; DevBuf<float4> film; DevBuf<double> ray_o, ray_d;
         Stopwatch watch; uint32_t bakes = 0; uint64_t passes = 0; double stage_ms = 0.0;
+        uint32_t direct = MCPT_BAKE_DIRECT_OFF;                              // mcpt_set_bake_direct's mode: no buffer hangs on it, drop() keeps it
         uint32_t n() const { return uint32_t(host.size()); }
         uint64_t device_bytes() const { return pts.bytes + dead.bytes + film.bytes + ray_o.bytes + ray_d.bytes; }
         void drop() { host.clear(); pts.release(); dead.release(); film.release(); ray_o.release(); ray_d.release(); }
@@ -2984,7 +2985,11 @@ mcpt_status mcpt_bake(mcpt_ctx* ctx, uint32_t spp, uint64_t seed, uint32_t first
         HIP_TRY(bk.watch.end(ctx->stream));
         // a primary hit emits from either side, a surface point must not see a lamp's back: where the ray first meets an emitter from behind, the
         // radiance the pass will add is taken out of the record beforehand (bk_unlit_kernel; still on the context's stream, ahead of the fork)
-        HIP_TRY(launch_bk_unlit(ctx->dev, bk.ray_o.p, bk.ray_d.p, bk.dead.p, n, bk.film.p, ctx->stream));
+        // MCPT_BAKE_DIRECT_MIS: the direct-light kernel in its place -- the same traversal, the same correction, and the point's own light sample
+        if (bk.direct == MCPT_BAKE_DIRECT_MIS)
+            HIP_TRY(launch_bk_direct(ctx->dev, bk.pts.p, bk.ray_d.p, n, s, uint32_t(seed), uint32_t(seed >> 32), bk.film.p, ctx->stream));
+        else
+            HIP_TRY(launch_bk_unlit(ctx->dev, bk.ray_o.p, bk.ray_d.p, bk.dead.p, n, bk.film.p, ctx->stream));
         // as in mcpt_render_camera: the sub-pipelines' streams fork from the context's after the ray kernel and join it again, so the next pass's
         // kernel -- of this call or of the next one -- overwrites the rays only after this pass's paths have read them
         RenderParams p = probe_job_params(ctx, s, seed, ctx->opts.flags);
@@ -3034,6 +3039,29 @@ mcpt_status mcpt_get_bake_info(mcpt_ctx* ctx, mcpt_bake_info* out) {
     uint32_t n_dead = 0;
     for (uint8_t d : dead) n_dead += d ? 1u : 0u;
     out->n_points = bk.n(); out->n_dead = n_dead; out->bakes = bk.bakes; out->passes = bk.passes; out->last_stage_ms = bk.stage_ms; out->device_bytes = bk.device_bytes();
+    out->direct_mode = bk.direct;
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_set_bake_direct(mcpt_ctx* ctx, uint32_t mode) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (mode > MCPT_BAKE_DIRECT_MIS) return fail(MCPT_ERR_INVALID_ARG, "mcpt_set_bake_direct: unknown mode");
+    ctx->bk.direct = mode;                                                   // read by mcpt_bake when it enqueues a pass: nothing in flight depends on it
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_bake_direct(mcpt_ctx* ctx, uint32_t sample, uint64_t seed, uint32_t first, uint32_t n, float* out12, int32_t* out4) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    const mcpt_ctx::Bake& bk = ctx->bk;
+    if (uint64_t(first) + n > bk.n()) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_bake_direct: first + n exceeds the number of bake points set");
+    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the first-hit kernel's traversal stack");
+    if (n == 0) return MCPT_OK;
+    Scratch s(ctx->stream); float* d_f; int32_t* d_i;
+    HIP_TRY(s.out(12 * size_t(n), &d_f)); HIP_TRY(s.out(4 * size_t(n), &d_i));
+    HIP_TRY(launch_bk_direct_probe(ctx->dev, bk.pts.p, first, n, sample, uint32_t(seed), uint32_t(seed >> 32), d_f, d_i, ctx->stream));
+    if (out12) HIP_TRY(s.fetch(out12, d_f, 12 * size_t(n)));
+    if (out4) HIP_TRY(s.fetch(out4, d_i, 4 * size_t(n)));
+    HIP_TRY(s.finish());
     return MCPT_OK;
 }
 

@@ -68,6 +68,11 @@ bool Render::set_bake_points(Scene&, const std::vector<mcpt_bake_point>& points)
     bake_points = uint32_t(points.size()); next_bake_sample = 0;
     return true;
 }
+bool Render::set_bake_direct(Scene&, uint32_t mode) {
+    if (!ctx) return false;
+    if (mcpt_set_bake_direct(ctx, mode) != MCPT_OK) { std::cerr << "Error: mcpt_set_bake_direct: " << mcpt_last_error() << std::endl; return false; }
+    return true;
+}
 bool Render::bake(Scene&, uint32_t spp) {
     if (!ctx) return false;
     if (mcpt_bake(ctx, spp, seed, next_bake_sample) != MCPT_OK) { std::cerr << "Error: mcpt_bake: " << mcpt_last_error() << std::endl; return false; }

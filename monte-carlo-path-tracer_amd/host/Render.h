@@ -145,8 +145,10 @@ public:
     // makes them for a lightmap); an empty vector drops them; the bake film and the bake's sample numbering start again.  bake: `spp` more
     // samples of `seed` for every point (mcpt_bake: one pass per sample; needs the wavefront pipeline).  read_bake: 4 floats per point,
     // {irradiance or outgoing diffuse radiance, samples} (mcpt_read_bake; empty on failure).  None of them touches `scene`, its film or the
-    // camera's sample numbering.  false (Render unchanged) on failure.
+    // camera's sample numbering.  false (Render unchanged) on failure.  set_bake_direct: MCPT_BAKE_DIRECT_MIS samples the lights at the bake
+    // point itself, MIS-weighted against the cosine ray (mcpt_set_bake_direct); holds for the bakes after it, with or without points.
     bool set_bake_points(Scene& scene, const std::vector<mcpt_bake_point>& points);
+    bool set_bake_direct(Scene& scene, uint32_t mode);
     bool bake(Scene& scene, uint32_t spp = 1);
     std::vector<float> read_bake(Scene& scene, uint32_t mode = MCPT_BAKE_IRRADIANCE);
     // New trees for the geometry as it is now (mcpt_rebuild_trees): after update() / update_transforms() have moved the scene far

@@ -74,11 +74,12 @@ static void usage() {
                  "                          [--ortho H]   an orthographic camera whose film is H world units high    [--panorama]   a 360 x 180 degree equirectangular camera\n"
                  "                                        (these three exclude each other; they go with --turntable and --gpus, not with --adaptive or --shard tiles;\n"
                  "                                        one pass per sample; --denoise and --reproject keep describing the pinhole view)\n"
-                 "                          [--bake-lightmap W H OUT.ppm [--bake-spp N] [--bake-irradiance]]   instead of a picture: a W x H lightmap over the scene's texture\n"
+                 "                          [--bake-lightmap W H OUT.ppm [--bake-spp N] [--bake-irradiance] [--bake-direct]]   instead of a picture: a W x H lightmap over the scene's texture\n"
                  "                                        coordinates (DESIGN.md 27), N samples per texel (64 by default) started ON the surfaces: the radiance a diffuse texel\n"
                  "                                        sends out, or with --bake-irradiance the irradiance it receives; through the picture's transfer curve; texels no\n"
                  "                                        face covers are black; row 0 of the file is v = 0, as a Map_Kd image is read (one GPU; honours --depth, --seed,\n"
-                 "                                        --corrected, --deterministic; not with --recursive)\n"
+                 "                                        --corrected, --deterministic; not with --recursive).  --bake-direct: sample the lights at the texel itself,\n"
+                 "                                        MIS-weighted against the cosine ray (less noise in direct light under small lamps)\n"
                  "       mcpt_cli --decode-image texture.(png|jpg|ppm|bmp|tga|hdr) out.(ppm|pfm)\n";
 }
 
@@ -115,7 +116,7 @@ int main(int argc, char** argv) {
     std::string hide, blink; int blink_k = 0;
     bool aperture_set = false, focus_set = false, autofocus_set = false, blades_set = false, rotation_set = false, ortho_set = false, panorama = false;
     double aperture = 0.0, focus = 0.0, blade_deg = 0.0, ortho_h = 0.0; int focus_x = 0, focus_y = 0, blades = 0;
-    std::string bake_out; int bake_w = 0, bake_h = 0, bake_spp = 64; bool bake_irradiance = false, bake_opts = false;
+    std::string bake_out; int bake_w = 0, bake_h = 0, bake_spp = 64; bool bake_irradiance = false, bake_opts = false, bake_direct = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
         if (a == "--spp") spp = uint32_t(std::atoi(next())); else if (a == "--batch") batch = uint32_t(std::atoi(next()));
@@ -158,6 +159,7 @@ int main(int argc, char** argv) {
         else if (a == "--bake-lightmap") { bake_w = std::atoi(next()); bake_h = std::atoi(next()); bake_out = next(); }
         else if (a == "--bake-spp") { bake_opts = true; bake_spp = std::atoi(next()); }
         else if (a == "--bake-irradiance") bake_opts = bake_irradiance = true;
+        else if (a == "--bake-direct") bake_opts = bake_direct = true;
         else { usage(); return 2; }
     }
     if (adaptive >= 0.f && gpus > 1) { std::cerr << "Error: --adaptive renders on one GPU only (drop --gpus)" << std::endl; return 2; }
@@ -221,7 +223,7 @@ int main(int argc, char** argv) {
         std::cerr << "Note: --denoise and --reproject are guided by features of the pinhole view, whatever camera model renders the film" << std::endl;
     // --bake-lightmap W H OUT.ppm: the surface baking of DESIGN.md 27 instead of a picture
     const bool bake = bake_w != 0 || bake_h != 0 || !bake_out.empty();
-    if (bake_opts && !bake) { std::cerr << "Error: --bake-spp N and --bake-irradiance need --bake-lightmap W H OUT.ppm" << std::endl; return 2; }
+    if (bake_opts && !bake) { std::cerr << "Error: --bake-spp N, --bake-irradiance and --bake-direct need --bake-lightmap W H OUT.ppm" << std::endl; return 2; }
     if (bake && (bake_w < 1 || bake_h < 1 || bake_w > 8192 || bake_h > 8192 || bake_out.empty() || bake_out == "0" || bake_spp < 1)) {
         std::cerr << "Error: --bake-lightmap W H OUT.ppm needs W and H in [1, 8192], a file name and --bake-spp N >= 1" << std::endl; return 2;
     }
@@ -321,6 +323,7 @@ int main(int argc, char** argv) {
         std::vector<unsigned char> rgb(3 * n_texel, 0);                      // texels no face covers stay black
         if (n) {
             Render& r0 = *renders[0];
+            if (bake_direct && !r0.set_bake_direct(scene, MCPT_BAKE_DIRECT_MIS)) return 1;
             if (!r0.set_bake_points(scene, points) || !r0.bake(scene, uint32_t(bake_spp))) return 1;
             const std::vector<float> lit = r0.read_bake(scene, bake_irradiance ? MCPT_BAKE_IRRADIANCE : MCPT_BAKE_DIFFUSE);
             if (lit.size() != 4 * size_t(n)) return 1;
