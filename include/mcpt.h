@@ -1036,7 +1036,8 @@ mcpt_status mcpt_probe_camera_rays(mcpt_ctx* ctx, uint32_t n, const int32_t* xy,
                                    double* out_origin3 /* device coordinates */, double* out_dir3);
 
 /* ---- surface baking ---------------------------------------------------------------------------------------------------------- */
-/* Lighting seen from the surface instead of from a camera: lightmaps, per-vertex baked lighting, irradiance probes.  A second ray-generation
+/* Lighting seen from the surface instead of from a camera: lightmaps and per-vertex baked lighting (irradiance probes, points in free space
+ * without a surface, are the next section's: mcpt_set_sh_probes).  A second ray-generation
  * stage (HIP kernels, csrc/bake.hip) starts one cosine-weighted ray per BAKE POINT on the scene's surfaces and hands the rays to the unchanged
  * wavefront pipeline through the hook mcpt_probe_paths and mcpt_render_camera use; the finished samples land in a film of the context's own
  * with one {sum L, count} record per point, never in the bound film.
@@ -1148,6 +1149,79 @@ mcpt_status mcpt_probe_bake_direct(mcpt_ctx* ctx, uint32_t sample, uint64_t seed
                                    int32_t* out4 /* 4 per point */);
 mcpt_status mcpt_lightmap_points(const mcpt_scene_desc* scene, uint32_t width, uint32_t height, uint32_t capacity, mcpt_bake_point* out_points,
                                  uint32_t* out_texel, uint32_t* out_n);
+
+/* ---- light probes: L2 spherical harmonics at free-space points ---------------------------------------------------------------- */
+/* What an object that moves through a baked scene is lit by.  A LIGHT PROBE is a point in free space, no surface and no normal; it stores the
+ * radiance arriving from all around it as 9 real spherical-harmonic coefficients per colour channel (bands l = 0, 1, 2; k = l (l + 1) + m):
+ *   Y0 = 0.282095   Y1 = 0.488603 y   Y2 = 0.488603 z   Y3 = 0.488603 x   Y4 = 1.092548 x y   Y5 = 1.092548 y z
+ *   Y6 = 0.315392 (3 z^2 - 1)   Y7 = 1.092548 x z   Y8 = 0.546274 (x^2 - y^2)
+ * A third ray-generation stage (HIP kernels, csrc/shprobe.hip) starts 64 rays per probe and PASS, one wave64 per probe: item i of a pass is
+ * probe i >> 6 and direction slot j = i & 63 of an 8 x 8 stratification of the sphere -- with (xi0, xi1) from random-number block 0 of
+ * (pixel = i, sample, seed), u = ((j & 7) + xi0) / 8, v = ((j >> 3) + xi1) / 8: z = 1 - 2 u, r = 2 sqrt(u (1 - u)), phi = 2 pi v,
+ * d = (r cos phi, r sin phi, z), fp64 rounded to fp32.  The rays go through the unchanged wavefront pipeline (the hook of mcpt_probe_paths,
+ * mcpt_render_camera and mcpt_bake) into a scratch film of one record per item; a projection kernel then forms per item the 27 products
+ * L_c Y_k(d) in fp32 (a component of L that is not finite counts as 0), sums the wave's 64 items in ONE fixed tree -- s[j] + s[j + 32], then
+ * + 16, ... + 1; no atomics, so a bake is reproducible bit for bit and tests/shprobe_ref.py restates it to the bit -- and adds the sums to the
+ * probe's 27 fp32 accumulators, 64 to its ray count and the pass's hits from behind and misses to two more counts.
+ *
+ * EMITTERS ARE ONE-SIDED FOR A PROBE, as for a bake point: before each pass a first-hit kernel (the binary tree) takes the radiance of an
+ * emitter first met from BEHIND out of the item's record, and writes the item's class byte: 0 a miss, 1 a hit from the front, 2 a hit from
+ * behind.  A probe whose share of back hits (counts[1] / counts[0]) is large sits inside geometry.
+ *
+ * mcpt_set_sh_probes: synchronous set-up; positions in WORLD coordinates, 3 doubles per probe.  Validated on the host before any device work, a
+ * refusal changes nothing: MCPT_ERR_INVALID_ARG for a NULL list with n > 0, a coordinate that is not finite (the message names the first bad
+ * probe) or n > 1 048 575 (a pass is one probe job of 64 n items).  n = 0 drops the probes and frees everything.  The context holds 24 B (the
+ * position in device coordinates) + 108 B (accumulators) + 12 B (counts) per probe from this call on and, from the first mcpt_bake_sh on,
+ * 64 x (48 B ray arrays + 16 B scratch film + 1 B class) per probe more, all counted in mcpt_scene_info::device_bytes.  Setting probes zeroes
+ * accumulators and counts.  The context keeps the world positions: mcpt_rebuild_trees derives the device coordinates anew and keeps probes and
+ * accumulators; mcpt_clone_to_device's clone starts without probes.
+ *
+ * mcpt_bake_sh: adds `passes` passes (samples first_sample .. first_sample + passes - 1 of `seed`) of 64 rays to every probe; mcpt_bake's
+ * contract: on the context's stream, asynchronous, ONE launch in mcpt_counters, the context's flags apply, it reads the context's CURRENT scene
+ * (after mcpt_update_* or mcpt_set_face_visibility: the scene as it is now).  MCPT_ERR_UNSUPPORTED without the wavefront pipeline;
+ * MCPT_ERR_INVALID_ARG without probes or when first_sample + passes > 2^32; MCPT_ERR_BVH_DEPTH where mcpt_bake answers it; passes == 0 does
+ * nothing.  Touches neither the bound film nor the bake film, the bake points, the features or the camera model.  (The ray count is a uint32:
+ * it wraps after 2^26 passes without mcpt_clear_sh.)
+ *
+ * mcpt_clear_sh: zeroes accumulators and counts (asynchronous).  mcpt_read_sh: 27 floats per probe, channel-major (out[27 p + 9 c + k]),
+ * synchronous: MCPT_SH_RADIANCE gives c[k] = (float(4 pi) / float(rays)) acc[k], the coefficients of the incident radiance, and
+ * MCPT_SH_IRRADIANCE those times float(pi), float(2 pi / 3), float(pi / 4) for l = 0, 1, 2 (the cosine lobe's convolution), so that
+ * mcpt_sh_eval gives the irradiance for a normal; all 0 where rays == 0.  mcpt_read_sh_film: the raw accumulators (27 per probe) and
+ * {rays, hits from behind, misses} (3 uint32 per probe); either may be NULL.
+ *
+ * mcpt_probe_sh_rays: the stage's device function for items first_item .. first_item + n_items - 1 (item numbers included) of sample `sample`:
+ * the origin in DEVICE coordinates and the direction (fp32 values), 3 doubles each; either may be NULL.  Synchronous; touches nothing.
+ * mcpt_read_sh_pass: the scratch film (4 floats per item: the item's L and count 1) and the class bytes as the LAST pass left them; either may
+ * be NULL; synchronises; MCPT_ERR_INVALID_ARG before the first pass of the set list.
+ *
+ * HOST ONLY, no device and no context: mcpt_sh_grid -- the cell centres of the box [lo, hi] cut into nx x ny x nz cells, x fastest, cell i at
+ * lo + ((i + 0.5) / n) (hi - lo) per axis; *out_n is always set, capacity < *out_n is MCPT_ERR_INVALID_ARG with nothing written
+ * (mcpt_lightmap_points' protocol); refused: a NULL bound, no cells or more than 1 048 575, a bound that is not finite, lo > hi.
+ * mcpt_sh_eval -- out[c] = sum_k coeffs[9 c + k] Y_k(normal / |normal|) in fp64, k ascending; {0, 0, 0} for a normal of length 0. */
+#define MCPT_SH_RADIANCE    0u            /* mcpt_read_sh's mode */
+#define MCPT_SH_IRRADIANCE  1u
+#define MCPT_SH_DIRECTIONS  64u           /* rays per probe and pass */
+#define MCPT_SH_MAX_PROBES  1048575u
+typedef struct mcpt_sh_info {
+    uint32_t struct_size, n_probes;
+    uint32_t bakes, reserved0;            /* mcpt_bake_sh calls that enqueued work on this context */
+    uint64_t passes;                      /* ... and their passes: one ray, first-hit and projection kernel each */
+    double   last_stage_ms;               /* HIP events: the ray and first-hit kernels (with the scratch film's fill) of the last call, summed */
+    uint64_t device_bytes;               /* positions + accumulators + counts + ray arrays + scratch film + class bytes, as held now */
+    uint32_t reserved[4];
+} mcpt_sh_info;
+mcpt_status mcpt_set_sh_probes(mcpt_ctx* ctx, const double* world_xyz /* 3 per probe */, uint32_t n);
+mcpt_status mcpt_bake_sh(mcpt_ctx* ctx, uint32_t passes, uint64_t seed, uint32_t first_sample);
+mcpt_status mcpt_clear_sh(mcpt_ctx* ctx);
+mcpt_status mcpt_read_sh(mcpt_ctx* ctx, uint32_t mode /* MCPT_SH_RADIANCE / _IRRADIANCE */, float* out27 /* 27 per probe */);
+mcpt_status mcpt_read_sh_film(mcpt_ctx* ctx, float* out27 /* 27 per probe */, uint32_t* out_counts3 /* 3 per probe */);
+mcpt_status mcpt_get_sh_info(mcpt_ctx* ctx, mcpt_sh_info* out);                     /* synchronises */
+mcpt_status mcpt_probe_sh_rays(mcpt_ctx* ctx, uint32_t sample, uint64_t seed, uint32_t first_item, uint32_t n_items, double* out_origin3 /* device coordinates */,
+                               double* out_dir3);
+mcpt_status mcpt_read_sh_pass(mcpt_ctx* ctx, float* out_film4 /* 4 per item */, uint8_t* out_class /* 1 per item */);
+mcpt_status mcpt_sh_grid(const double* lo3, const double* hi3, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t capacity, double* out_xyz /* 3 per probe */,
+                         uint32_t* out_n);
+mcpt_status mcpt_sh_eval(const float* coeffs27, const double* normal3, double* out_rgb3);
 
 /* ---- plumbing for multi-GPU hosts (one context per GPU / rank) ---------------------------------------- */
 /* Use a caller-owned device buffer of width*height*4 floats as the accumulator (e.g. a torch tensor that

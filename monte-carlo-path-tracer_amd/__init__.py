@@ -38,6 +38,8 @@ from .camera_abi import (CAMERA_EQUIRECT, CAMERA_MAX_BLADES, CAMERA_ORTHOGRAPHIC
 # mcpt_bake_point, mcpt_get_bake_info's struct, the constants, the makers of bake-point lists and Renderer's baking methods; tests/test_bake_ref.py holds the layouts to the header
 from .bake_abi import (BAKE_BACK_SIDE, BAKE_DIFFUSE, BAKE_DIRECT_MIS, BAKE_DIRECT_OFF, BAKE_IRRADIANCE, BAKE_MAX_POINTS, BakeInfo, BakeMethods, BakePoint, bake_points, lightmap_points,  # noqa: F401
                        vertex_bake_points)
+# mcpt_get_sh_info's struct, the constants, the host-only helpers and Renderer's light-probe methods; tests/test_shprobe_ref.py holds the layout to the header
+from .shprobe_abi import SH_DIRECTIONS, SH_IRRADIANCE, SH_MAX_PROBES, SH_RADIANCE, ShInfo, ShProbeMethods, sh_eval, sh_grid  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmcpt_hip.so")
@@ -347,6 +349,16 @@ def load_library() -> C.CDLL:
         "mcpt_lightmap_points": [P(SceneDesc), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, P(C.c_uint32)],
         "mcpt_set_bake_direct": [vp, C.c_uint32],
         "mcpt_probe_bake_direct": [vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
+        "mcpt_set_sh_probes": [vp, vp, C.c_uint32],
+        "mcpt_bake_sh": [vp, C.c_uint32, C.c_uint64, C.c_uint32],
+        "mcpt_clear_sh": [vp],
+        "mcpt_read_sh": [vp, C.c_uint32, vp],
+        "mcpt_read_sh_film": [vp, vp, vp],
+        "mcpt_get_sh_info": [vp, P(ShInfo)],
+        "mcpt_probe_sh_rays": [vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
+        "mcpt_read_sh_pass": [vp, vp, vp],
+        "mcpt_sh_grid": [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, P(C.c_uint32)],
+        "mcpt_sh_eval": [vp, vp, vp],
     }
     for name, args in sigs.items():
         if not hasattr(lib, name) and "MCPT_LIB_PATH" in os.environ:
@@ -385,6 +397,8 @@ EXPORTED_SYMBOLS = [
     "mcpt_set_camera_model", "mcpt_get_camera_model", "mcpt_render_camera", "mcpt_autofocus", "mcpt_probe_camera_rays",
     "mcpt_set_bake_points", "mcpt_bake", "mcpt_clear_bake", "mcpt_read_bake", "mcpt_read_bake_film", "mcpt_get_bake_info", "mcpt_probe_bake_rays", "mcpt_lightmap_points",
     "mcpt_set_bake_direct", "mcpt_probe_bake_direct",
+    "mcpt_set_sh_probes", "mcpt_bake_sh", "mcpt_clear_sh", "mcpt_read_sh", "mcpt_read_sh_film", "mcpt_get_sh_info", "mcpt_probe_sh_rays", "mcpt_read_sh_pass", "mcpt_sh_grid",
+    "mcpt_sh_eval",
 ]
 
 
@@ -475,8 +489,9 @@ def check_scene(scene: "scenes.SceneData"):
     return st, info, (lib.mcpt_last_error() or b"").decode() if st != MCPT_OK else ""
 
 
-class Renderer(BakeMethods):
-    """One mcpt_ctx = one scene on one GPU (the reference's ``Render`` object).  Surface baking: bake_abi.BakeMethods."""
+class Renderer(BakeMethods, ShProbeMethods):
+    """One mcpt_ctx = one scene on one GPU (the reference's ``Render`` object).  Surface baking: bake_abi.BakeMethods; light
+    probes: shprobe_abi.ShProbeMethods."""
 
     def __init__(self, scene: "scenes.SceneData", max_depth=0, integrator=INTEGRATOR_MIS, flags=0, device=0,
                  samples_per_item=0):

@@ -24,6 +24,8 @@
 #include "camera.h"
 #include "bake.h"
 #include "bake_plan.h"
+#include "shprobe.h"
+#include "shprobe_plan.h"
 
 #include <chrono>
 #include <cmath>
@@ -437,6 +439,26 @@ struct mcpt_ctx {
             return v;
         }
     } bk;
+    // Light probes (shprobe.hip), allocated by mcpt_set_sh_probes and counted in device_bytes: per probe its position in device
+    // coordinates, 27 fp32 accumulators and the counts {rays, hits from behind, misses}; by the first mcpt_bake_sh, per ITEM (64 per probe) the two
+    // ray arrays wf_shade_kernel reads as probe_o / probe_d, the scratch film of one pass and the class byte.  On the host the WORLD positions:
+    // mcpt_rebuild_trees derives the device coordinates anew from them.  `watch` brackets one pass's ray and first-hit kernels; stage_ms adds them
+    // up over a call.  `have_pass`: a pass of the set list has been enqueued (mcpt_read_sh_pass).  A clone starts without probes.
+    struct ShProbes {
+        std::vector<double> host; DevBuf<double> pos; DevBuf<float> acc; DevBuf<uint32_t> counts; DevBuf<double> ray_o, ray_d; DevBuf<float4> film; DevBuf<uint8_t> cls;
+        Stopwatch watch; uint32_t bakes = 0; uint64_t passes = 0; double stage_ms = 0.0; bool have_pass = false;
+        uint32_t n() const { return uint32_t(host.size() / 3); }
+        uint32_t items() const { return n() * SH_DIRS; }
+        uint64_t device_bytes() const { return pos.bytes + acc.bytes + counts.bytes + ray_o.bytes + ray_d.bytes + film.bytes + cls.bytes; }
+        void drop_pass() { ray_o.release(); ray_d.release(); film.release(); cls.release(); have_pass = false; }
+        void drop() { host.clear(); pos.release(); acc.release(); counts.release(); drop_pass(); }
+        hipError_t take() {                                                  // the bracketed pass, once it has run, joins the call's sum
+            const bool timed = watch.timed;
+            const hipError_t e = watch.settle();
+            if (e == hipSuccess && timed) stage_ms += watch.last_ms;
+            return e;
+        }
+    } sh;
     // Temporal reprojection (reproject.hip), allocated by the first reprojection call: the old view's features (2 per pixel, swapped
     // with dn_feat per call), a copy of the old film and the reuse counter.
     // Motion-vector reprojection adds, on the first mcpt_update_vertices_reproject: the first hit of every pixel-centre ray and
@@ -2320,6 +2342,13 @@ mcpt_status mcpt_rebuild_trees(mcpt_ctx* ctx, const mcpt_rebuild_opts* opts) {
         HIP_TRY(bk_pts.alloc(bk_host.size(), tally));
         HIP_TRY(hipMemcpyAsync(bk_pts.p, bk_host.data(), bk_pts.bytes, hipMemcpyHostToDevice, s));
     }
+    // §28: probe positions are relative to the centre; the device list for the centre this call leaves in force, from the world-coordinate copy
+    DevBuf<double> sh_pos; std::vector<double> sh_host;
+    if (ctx->sh.n()) {
+        sh_host = to_local(ctx, ctx->sh.host.data(), ctx->sh.n());
+        HIP_TRY(sh_pos.alloc(sh_host.size(), tally));
+        HIP_TRY(hipMemcpyAsync(sh_pos.p, sh_host.data(), sh_pos.bytes, hipMemcpyHostToDevice, s));
+    }
     HIP_TRY(hipMemsetAsync(tri_isect.p + 3 * size_t(nt), 0, 3 * sizeof(float4), s));                     // the spare record
     if (lights.bytes) HIP_TRY(hipMemcpyAsync(lights.p, ctx->lights.p, lights.bytes, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipEventRecord(ev[2], s));
@@ -2343,6 +2372,7 @@ mcpt_status mcpt_rebuild_trees(mcpt_ctx* ctx, const mcpt_rebuild_opts* opts) {
     ctx->rf_bin_level.swap(bin_level); ctx->rf_wide_level.swap(wide_level); ctx->rf_area0 = area0;
     ctx->h_tri_face.assign(order.begin(), order.end());
     if (bk_pts.p) ctx->bk.pts = std::move(bk_pts);
+    if (sh_pos.p) ctx->sh.pos = std::move(sh_pos);
     ctx->wide_depth = hs.bvh8_depth; ctx->binary_ok = hs.binary_ok;
     ctx->vs.box_valid = false;                                                    // §24: rf_tri_box is scratch in the OLD leaf order; the mask is per face and stays
     DevScene& d = ctx->dev;
@@ -3096,6 +3126,153 @@ mcpt_status mcpt_lightmap_points(const mcpt_scene_desc* scene, uint32_t width, u
     if (!out_points || !out_texel) return fail(MCPT_ERR_INVALID_ARG, who + "null argument");
     std::memcpy(out_points, points.data(), points.size() * sizeof(mcpt_bake_point));
     std::memcpy(out_texel, texel.data(), texel.size() * sizeof(uint32_t));
+    return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ light probes
+mcpt_status mcpt_set_sh_probes(mcpt_ctx* ctx, const double* world_xyz, uint32_t n) {
+    const std::string who = "mcpt_set_sh_probes: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    const std::string bad = sh_check_probes(world_xyz, n);
+    if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, who + bad);
+    mcpt_ctx::ShProbes& sh = ctx->sh;
+    // nothing below refuses; what fails is a HIP call
+    st = use_drained(ctx); if (st != MCPT_OK) return st;                     // passes enqueued earlier read the buffers that are about to be replaced
+    HIP_TRY(sh.take());
+    if (n == 0) { sh.drop(); return MCPT_OK; }
+    uint64_t* tally = &ctx->info.device_bytes;
+    HIP_TRY(alloc_all(Want(sh.pos, 3 * size_t(n), tally), Want(sh.acc, SH_COEFFS * size_t(n), tally), Want(sh.counts, 3 * size_t(n), tally),
+                      Want(sh.watch, 1, nullptr, !sh.watch.ev0)));
+    if (sh.ray_o.p && sh.ray_o.count() != 3 * size_t(n) * SH_DIRS) sh.drop_pass();                      // (the first bake of the new list allocates its own)
+    sh.have_pass = false;
+    sh.host.assign(world_xyz, world_xyz + 3 * size_t(n));
+    const std::vector<double> local = to_local(ctx, world_xyz, n);
+    HIP_TRY(hipMemcpyAsync(sh.pos.p, local.data(), sh.pos.bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(sh.acc.p, 0, sh.acc.bytes, ctx->stream));
+    HIP_TRY(hipMemsetAsync(sh.counts.p, 0, sh.counts.bytes, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                              // (`local` has been read)
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_bake_sh(mcpt_ctx* ctx, uint32_t passes, uint64_t seed, uint32_t first_sample) {
+    const std::string who = "mcpt_bake_sh: ";
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!ctx->use_wavefront || ctx->lanes.empty()) return fail(MCPT_ERR_UNSUPPORTED, who + "needs the wavefront pipeline (MCPT_INTEGRATOR_MIS, no MCPT_PIPELINE=mega)");
+    mcpt_ctx::ShProbes& sh = ctx->sh;
+    const uint32_t n = sh.n(), items = sh.items();
+    if (n == 0) return fail(MCPT_ERR_INVALID_ARG, who + "no probes are set");
+    if (uint64_t(first_sample) + passes > (1ull << 32)) return fail(MCPT_ERR_INVALID_ARG, who + "first_sample + passes exceeds 2^32");
+    if (!ctx->binary_ok) return fail(MCPT_ERR_BVH_DEPTH, "the binary tree of this (device-built) scene is deeper than the first-hit kernel's traversal stack");
+    if (passes == 0) return MCPT_OK;
+    if (!sh.ray_o.p) {
+        uint64_t* tally = &ctx->info.device_bytes;
+        HIP_TRY(alloc_all(Want(sh.ray_o, 3 * size_t(items), tally), Want(sh.ray_d, 3 * size_t(items), tally), Want(sh.film, size_t(items), tally), Want(sh.cls, size_t(items), tally)));
+    }
+    HIP_TRY(sh.take());                                                      // (the last call's last pass)
+    sh.stage_ms = 0.0;
+    st = timed_begin(ctx); if (st != MCPT_OK) return st;
+    for (uint32_t k = 0; k < passes; k++) {
+        const uint32_t s = first_sample + k;
+        HIP_TRY(sh.take());
+        HIP_TRY(sh.watch.begin(ctx->stream));
+        HIP_TRY(launch_sh_rays(sh.pos.p, n, s, uint32_t(seed), uint32_t(seed >> 32), sh.ray_o.p, sh.ray_d.p, ctx->stream));
+        // the pass's target is a scratch film, not the accumulators: the projection needs each item's own L.  Zeroed, then the first-hit kernel
+        // takes an emitter's back out of it and classes the item (still on the context's stream, ahead of the fork)
+        HIP_TRY(hipMemsetAsync(sh.film.p, 0, sh.film.bytes, ctx->stream));
+        HIP_TRY(launch_sh_first_hit(ctx->dev, sh.ray_o.p, sh.ray_d.p, items, sh.film.p, sh.cls.p, ctx->stream));
+        HIP_TRY(sh.watch.end(ctx->stream));
+        RenderParams p = probe_job_params(ctx, s, seed, ctx->opts.flags);
+        p.probe_n = items; p.probe_o = sh.ray_o.p; p.probe_d = sh.ray_d.p;
+        st = render_wavefront(ctx, p, sh.film.p); if (st != MCPT_OK) return st;
+        // render_wavefront has joined the context's stream: the projection reads the finished film, and the next pass's ray kernel -- of this call
+        // or of the next one -- overwrites rays, film and classes only after it
+        HIP_TRY(launch_sh_project(sh.film.p, sh.ray_d.p, sh.cls.p, n, sh.acc.p, sh.counts.p, ctx->stream));
+        sh.passes++; sh.have_pass = true;
+    }
+    sh.bakes++;
+    return timed_end(ctx);
+}
+
+mcpt_status mcpt_clear_sh(mcpt_ctx* ctx) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (ctx->sh.acc.bytes) {
+        HIP_TRY(hipMemsetAsync(ctx->sh.acc.p, 0, ctx->sh.acc.bytes, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->sh.counts.p, 0, ctx->sh.counts.bytes, ctx->stream));
+    }
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_read_sh(mcpt_ctx* ctx, uint32_t mode, float* out27) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (mode > MCPT_SH_IRRADIANCE) return fail(MCPT_ERR_INVALID_ARG, "mcpt_read_sh: unknown mode");
+    const mcpt_ctx::ShProbes& sh = ctx->sh;
+    if (sh.n() == 0) return MCPT_OK;
+    if (!out27) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    {   Scratch s(ctx->stream); float* d_out;
+        HIP_TRY(s.out(SH_COEFFS * size_t(sh.n()), &d_out));
+        HIP_TRY(launch_sh_resolve(sh.acc.p, sh.counts.p, sh.n(), mode, d_out, ctx->stream));
+        HIP_TRY(s.fetch(out27, d_out, SH_COEFFS * size_t(sh.n()))); HIP_TRY(s.finish()); }
+    return resolve_timing(ctx);
+}
+
+mcpt_status mcpt_read_sh_film(mcpt_ctx* ctx, float* out27, uint32_t* out_counts3) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    const mcpt_ctx::ShProbes& sh = ctx->sh;
+    if (sh.n() == 0) return MCPT_OK;
+    if (out27) HIP_TRY(hipMemcpyAsync(out27, sh.acc.p, sh.acc.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return read_back(ctx, out_counts3, sh.counts.p, out_counts3 ? sh.counts.bytes : 0);
+}
+
+mcpt_status mcpt_get_sh_info(mcpt_ctx* ctx, mcpt_sh_info* out) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    if (!out) return fail(MCPT_ERR_INVALID_ARG, "null output");
+    mcpt_ctx::ShProbes& sh = ctx->sh;
+    Stopwatch none;                                                          // (a context that never had probes has no watch of its own)
+    HIP_TRY(sh.take());
+    st = info_begin(ctx, out, sh.watch.ev0 ? &sh.watch : &none); if (st != MCPT_OK) return st;
+    out->n_probes = sh.n(); out->bakes = sh.bakes; out->passes = sh.passes; out->last_stage_ms = sh.stage_ms; out->device_bytes = sh.device_bytes();
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_probe_sh_rays(mcpt_ctx* ctx, uint32_t sample, uint64_t seed, uint32_t first_item, uint32_t n_items, double* out_origin3, double* out_dir3) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    const mcpt_ctx::ShProbes& sh = ctx->sh;
+    if (uint64_t(first_item) + n_items > sh.items()) return fail(MCPT_ERR_INVALID_ARG, "mcpt_probe_sh_rays: first_item + n_items exceeds 64 x the number of probes set");
+    if (n_items == 0) return MCPT_OK;
+    Scratch s(ctx->stream); double *d_o, *d_d;
+    HIP_TRY(s.out(3 * size_t(n_items), &d_o)); HIP_TRY(s.out(3 * size_t(n_items), &d_d));
+    HIP_TRY(launch_sh_probe(sh.pos.p, first_item, n_items, sample, uint32_t(seed), uint32_t(seed >> 32), d_o, d_d, ctx->stream));
+    if (out_origin3) HIP_TRY(s.fetch(out_origin3, d_o, 3 * size_t(n_items)));
+    if (out_dir3) HIP_TRY(s.fetch(out_dir3, d_d, 3 * size_t(n_items)));
+    HIP_TRY(s.finish());
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_read_sh_pass(mcpt_ctx* ctx, float* out_film4, uint8_t* out_class) {
+    mcpt_status st = use(ctx); if (st != MCPT_OK) return st;
+    const mcpt_ctx::ShProbes& sh = ctx->sh;
+    if (!sh.have_pass) return fail(MCPT_ERR_INVALID_ARG, "mcpt_read_sh_pass: no pass has run for the probes set");
+    if (out_film4) HIP_TRY(hipMemcpyAsync(out_film4, sh.film.p, sh.film.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return read_back(ctx, out_class, sh.cls.p, out_class ? sh.cls.bytes : 0);
+}
+
+mcpt_status mcpt_sh_grid(const double* lo3, const double* hi3, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t capacity, double* out_xyz, uint32_t* out_n) {
+    const std::string who = "mcpt_sh_grid: ";
+    if (!out_n) return fail(MCPT_ERR_INVALID_ARG, who + "null argument");
+    *out_n = 0;
+    std::vector<double> xyz;
+    const std::string bad = sh_grid_points(lo3, hi3, nx, ny, nz, xyz);
+    if (!bad.empty()) return fail(MCPT_ERR_INVALID_ARG, who + bad);
+    *out_n = uint32_t(xyz.size() / 3);
+    if (capacity < xyz.size() / 3) return fail(MCPT_ERR_INVALID_ARG, who + "capacity < the number of cells");
+    if (!out_xyz) return fail(MCPT_ERR_INVALID_ARG, who + "null argument");
+    std::memcpy(out_xyz, xyz.data(), xyz.size() * sizeof(double));
+    return MCPT_OK;
+}
+
+mcpt_status mcpt_sh_eval(const float* coeffs27, const double* normal3, double* out_rgb3) {
+    if (!coeffs27 || !normal3 || !out_rgb3) return fail(MCPT_ERR_INVALID_ARG, "mcpt_sh_eval: null argument");
+    sh_eval_probe(coeffs27, normal3, out_rgb3);
     return MCPT_OK;
 }
 

@@ -85,6 +85,32 @@ std::vector<float> Render::read_bake(Scene&, uint32_t mode) {
     if (mcpt_read_bake(ctx, mode, out.data()) != MCPT_OK) { std::cerr << "Error: mcpt_read_bake: " << mcpt_last_error() << std::endl; return {}; }
     return out;
 }
+bool Render::set_sh_probes(Scene&, const std::vector<double>& positions) {
+    if (!ctx) return false;
+    if (positions.size() % 3) { std::cerr << "Error: Render::set_sh_probes: 3 doubles per probe" << std::endl; return false; }
+    if (mcpt_set_sh_probes(ctx, positions.data(), uint32_t(positions.size() / 3)) != MCPT_OK) { std::cerr << "Error: mcpt_set_sh_probes: " << mcpt_last_error() << std::endl; return false; }
+    sh_probes = uint32_t(positions.size() / 3); next_sh_sample = 0;
+    return true;
+}
+bool Render::bake_sh(Scene&, uint32_t passes) {
+    if (!ctx) return false;
+    if (mcpt_bake_sh(ctx, passes, seed, next_sh_sample) != MCPT_OK) { std::cerr << "Error: mcpt_bake_sh: " << mcpt_last_error() << std::endl; return false; }
+    next_sh_sample += passes;
+    return true;
+}
+std::vector<float> Render::read_sh(Scene&, uint32_t mode) {
+    std::vector<float> out(27 * size_t(sh_probes));
+    if (!ctx || out.empty()) return {};
+    if (mcpt_read_sh(ctx, mode, out.data()) != MCPT_OK) { std::cerr << "Error: mcpt_read_sh: " << mcpt_last_error() << std::endl; return {}; }
+    return out;
+}
+std::vector<float> Render::read_sh_back_share(Scene&) {
+    std::vector<uint32_t> counts(3 * size_t(sh_probes)); std::vector<float> out(sh_probes);
+    if (!ctx || out.empty()) return {};
+    if (mcpt_read_sh_film(ctx, nullptr, counts.data()) != MCPT_OK) { std::cerr << "Error: mcpt_read_sh_film: " << mcpt_last_error() << std::endl; return {}; }
+    for (size_t p = 0; p < out.size(); p++) out[p] = counts[3 * p] ? float(double(counts[3 * p + 1]) / double(counts[3 * p])) : 0.f;
+    return out;
+}
 // `spp` samples into `scene`: of the pinhole camera (mcpt_render), or -- `camera_model` -- of the model set_camera_model chose (mcpt_render_camera, §25)
 bool Render::render_samples(Scene& scene, uint32_t spp, bool camera_model) {
     if (!ctx || spp == 0) return ctx != nullptr;

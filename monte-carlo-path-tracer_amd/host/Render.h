@@ -140,7 +140,8 @@ public:
     bool set_camera_model(Scene& scene, const mcpt_camera_model& model);
     bool render_camera(Scene& scene, uint32_t spp = 1);
     bool autofocus(Scene& scene, int px, int py, double& focus_distance);
-    // Surface baking: lighting seen from the surface -- lightmaps, per-vertex lighting, irradiance probes.  set_bake_points: the
+    // Surface baking: lighting seen from the surface -- lightmaps and per-vertex lighting (irradiance probes in free space: the
+    // light probes below).  set_bake_points: the
     // points to bake, each a face of the Model this Render was made from, barycentrics and a side (mcpt_set_bake_points; mcpt_lightmap_points
     // makes them for a lightmap); an empty vector drops them; the bake film and the bake's sample numbering start again.  bake: `spp` more
     // samples of `seed` for every point (mcpt_bake: one pass per sample; needs the wavefront pipeline).  read_bake: 4 floats per point,
@@ -151,6 +152,17 @@ public:
     bool set_bake_direct(Scene& scene, uint32_t mode);
     bool bake(Scene& scene, uint32_t spp = 1);
     std::vector<float> read_bake(Scene& scene, uint32_t mode = MCPT_BAKE_IRRADIANCE);
+    // Light probes: what an object moving through the scene is lit by.  set_sh_probes: points in free space, world coordinates,
+    // 3 doubles each (mcpt_set_sh_probes; mcpt_sh_grid makes a box of them); an empty vector drops them; the accumulators and the probes' own
+    // pass numbering start again.  bake_sh: `passes` more passes of 64 rays of `seed` for every probe (mcpt_bake_sh; needs the wavefront
+    // pipeline).  read_sh: 27 floats per probe, 9 spherical-harmonic coefficients per channel, of the radiance around the probe or
+    // (MCPT_SH_IRRADIANCE) of the irradiance by normal, mcpt_sh_eval's input (mcpt_read_sh; empty on failure).  read_sh_back_share: per probe the
+    // share of its rays that first met a surface from behind -- large for a probe inside geometry.  None of them touches `scene`, its film, the
+    // bake film or the other sample numberings.  false (Render unchanged) on failure.
+    bool set_sh_probes(Scene& scene, const std::vector<double>& positions);
+    bool bake_sh(Scene& scene, uint32_t passes = 1);
+    std::vector<float> read_sh(Scene& scene, uint32_t mode = MCPT_SH_RADIANCE);
+    std::vector<float> read_sh_back_share(Scene& scene);
     // New trees for the geometry as it is now (mcpt_rebuild_trees): after update() / update_transforms() have moved the scene far
     // (mcpt_update_info::wide_area_ratio says how far) the refitted trees are sound and slow; this builds them anew on the context.  The picture
     // goes ON: `scene`'s film, the sample numbering and the feature buffers stay, the scene looks the same from every pixel.  Synchronous.  false
@@ -165,6 +177,7 @@ private:
     mcpt_ctx* ctx = nullptr;
     uint32_t next_sample = 0;
     uint32_t next_bake_sample = 0, bake_points = 0;   // §27: the bake film's own numbering; the length of the list set
+    uint32_t next_sh_sample = 0, sh_probes = 0;       // §28: the probes' own numbering; the length of the list set
     std::vector<float> film;
     Scene* target = nullptr;                          // the Scene the device film belongs to
     bool dirty = false;                               // the device film holds samples `target` has not seen

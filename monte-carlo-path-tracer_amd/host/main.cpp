@@ -74,6 +74,10 @@ static void usage() {
                  "                          [--ortho H]   an orthographic camera whose film is H world units high    [--panorama]   a 360 x 180 degree equirectangular camera\n"
                  "                                        (these three exclude each other; they go with --turntable and --gpus, not with --adaptive or --shard tiles;\n"
                  "                                        one pass per sample; --denoise and --reproject keep describing the pinhole view)\n"
+                 "                          [--sh-grid NX NY NZ OUT.txt [--sh-passes N] [--sh-irradiance]]   instead of a picture: NX x NY x NZ light probes at the cell centres of\n"
+                 "                                        the scene's bounds, N passes (default 16) of 64 rays each; one line per probe: position, 27 spherical-harmonic\n"
+                 "                                        coefficients (per channel k = l (l + 1) + m, l <= 2) of the radiance around it or, with --sh-irradiance, of the\n"
+                 "                                        irradiance by normal, and the share of rays that met a surface from behind (not with --recursive)\n"
                  "                          [--bake-lightmap W H OUT.ppm [--bake-spp N] [--bake-irradiance] [--bake-direct]]   instead of a picture: a W x H lightmap over the scene's texture\n"
                  "                                        coordinates (DESIGN.md 27), N samples per texel (64 by default) started ON the surfaces: the radiance a diffuse texel\n"
                  "                                        sends out, or with --bake-irradiance the irradiance it receives; through the picture's transfer curve; texels no\n"
@@ -116,6 +120,7 @@ int main(int argc, char** argv) {
     std::string hide, blink; int blink_k = 0;
     bool aperture_set = false, focus_set = false, autofocus_set = false, blades_set = false, rotation_set = false, ortho_set = false, panorama = false;
     double aperture = 0.0, focus = 0.0, blade_deg = 0.0, ortho_h = 0.0; int focus_x = 0, focus_y = 0, blades = 0;
+    std::string sh_out; int sh_n[3] = {0, 0, 0}, sh_passes = 16; bool sh_grid = false, sh_irradiance = false, sh_opts = false;
     std::string bake_out; int bake_w = 0, bake_h = 0, bake_spp = 64; bool bake_irradiance = false, bake_opts = false, bake_direct = false;
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i]; auto next = [&]() { return i + 1 < argc ? argv[++i] : (char*)"0"; };
@@ -157,6 +162,9 @@ int main(int argc, char** argv) {
         else if (a == "--ortho") { ortho_set = true; ortho_h = std::atof(next()); }
         else if (a == "--panorama") panorama = true;
         else if (a == "--bake-lightmap") { bake_w = std::atoi(next()); bake_h = std::atoi(next()); bake_out = next(); }
+        else if (a == "--sh-grid") { sh_grid = true; for (int k = 0; k < 3; k++) sh_n[k] = std::atoi(next()); sh_out = next(); }
+        else if (a == "--sh-passes") { sh_opts = true; sh_passes = std::atoi(next()); }
+        else if (a == "--sh-irradiance") sh_opts = sh_irradiance = true;
         else if (a == "--bake-spp") { bake_opts = true; bake_spp = std::atoi(next()); }
         else if (a == "--bake-irradiance") bake_opts = bake_irradiance = true;
         else if (a == "--bake-direct") bake_opts = bake_direct = true;
@@ -229,6 +237,15 @@ int main(int argc, char** argv) {
     }
     if (bake && (gpus > 1 || turntable || adaptive >= 0.f || camera_model || integrator != MCPT_INTEGRATOR_MIS)) {
         std::cerr << "Error: --bake-lightmap bakes on one GPU through the wavefront pipeline: not with --gpus, --turntable, --adaptive, a camera model or --recursive" << std::endl; return 2;
+    }
+    // --sh-grid NX NY NZ OUT.txt: the light probes of DESIGN.md 28 instead of a picture
+    if (sh_opts && !sh_grid) { std::cerr << "Error: --sh-passes N and --sh-irradiance need --sh-grid NX NY NZ OUT.txt" << std::endl; return 2; }
+    if (sh_grid && (sh_n[0] < 1 || sh_n[1] < 1 || sh_n[2] < 1 || sh_n[0] > 1024 || sh_n[1] > 1024 || sh_n[2] > 1024 || sh_out.empty() || sh_out == "0" || sh_passes < 1 ||
+                    uint64_t(sh_n[0]) * uint64_t(sh_n[1]) * uint64_t(sh_n[2]) > MCPT_SH_MAX_PROBES)) {
+        std::cerr << "Error: --sh-grid NX NY NZ OUT.txt needs NX, NY and NZ in [1, 1024] with at most 1 048 575 probes in all, a file name and --sh-passes N >= 1" << std::endl; return 2;
+    }
+    if (sh_grid && (bake || gpus > 1 || turntable || adaptive >= 0.f || camera_model || integrator != MCPT_INTEGRATOR_MIS)) {
+        std::cerr << "Error: --sh-grid bakes on one GPU through the wavefront pipeline: not with --bake-lightmap, --gpus, --turntable, --adaptive, a camera model or --recursive" << std::endl; return 2;
     }
     if (wobble || !spin.empty() || !bend.empty() || !swell.empty() || !sequence.empty() || !hide.empty() || !blink.empty()) flags |= MCPT_FLAG_DYNAMIC;
     Model model(filename, ref_order);
@@ -338,6 +355,36 @@ int main(int argc, char** argv) {
         if (!f) { std::cerr << "Error: cannot write " << bake_out << std::endl; return 1; }
         std::fprintf(f, "P6\n%d %d\n255\n", bake_w, bake_h); std::fwrite(rgb.data(), 1, rgb.size(), f); std::fclose(f);
         std::cout << "baked " << n << " of " << n_texel << " texels, " << bake_spp << " samples each: " << bake_out << std::endl;
+        for (auto r : renders) delete r;
+        return 0;
+    }
+    if (sh_grid) {
+        // the grid spans the bounds of the vertices the faces use; one line per probe: position, 27 coefficients (channel-major, k = l (l + 1) + m), back-hit share
+        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+        for (auto& fc : model.face)
+            for (int c = 0; c < 3; c++) {
+                const dvec3& v = model.vertex[size_t(fc[c][0])];
+                const double x[3] = {v.x, v.y, v.z};
+                for (int k = 0; k < 3; k++) { lo[k] = std::fmin(lo[k], x[k]); hi[k] = std::fmax(hi[k], x[k]); }
+            }
+        uint32_t n = uint32_t(sh_n[0]) * uint32_t(sh_n[1]) * uint32_t(sh_n[2]);
+        std::vector<double> pos(3 * size_t(n));
+        if (mcpt_sh_grid(lo, hi, uint32_t(sh_n[0]), uint32_t(sh_n[1]), uint32_t(sh_n[2]), n, pos.data(), &n) != MCPT_OK) {
+            std::cerr << "Error: mcpt_sh_grid: " << mcpt_last_error() << std::endl; return 1;
+        }
+        Render& r0 = *renders[0];
+        if (!r0.set_sh_probes(scene, pos) || !r0.bake_sh(scene, uint32_t(sh_passes))) return 1;
+        const std::vector<float> coeffs = r0.read_sh(scene, sh_irradiance ? MCPT_SH_IRRADIANCE : MCPT_SH_RADIANCE), back = r0.read_sh_back_share(scene);
+        if (coeffs.size() != 27 * size_t(n) || back.size() != n) return 1;
+        FILE* f = std::fopen(sh_out.c_str(), "w");
+        if (!f) { std::cerr << "Error: cannot write " << sh_out << std::endl; return 1; }
+        for (uint32_t p = 0; p < n; p++) {
+            std::fprintf(f, "%.17g %.17g %.17g", pos[3 * size_t(p)], pos[3 * size_t(p) + 1], pos[3 * size_t(p) + 2]);
+            for (int q = 0; q < 27; q++) std::fprintf(f, " %.9g", coeffs[27 * size_t(p) + q]);
+            std::fprintf(f, " %.6g\n", back[p]);
+        }
+        std::fclose(f);
+        std::cout << "baked " << n << " probes, " << sh_passes << " passes of 64 rays each: " << sh_out << std::endl;
         for (auto r : renders) delete r;
         return 0;
     }
